@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s (primary + shadow) of the HIP intersection path on BASELINE config 4
-(sponza 1920x1080, 64 spp), with the dominant kernel's roofline and the CPU (SSE) baseline beside it.
+(sponza 1920x1080, 64 spp); with `--full`, the dominant kernel's roofline and the CPU (SSE) baseline beside it.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times K steps and prints the line; `--dump-outputs DIR` also writes what the last timed
+step computed as DIR/<name>.npy (the frame's framebuffer, or the irradiance estimates of `--config photon`).  `--full`
+adds everything that takes runs of its own: the `roofline` object (live rocprofv3 passes, the reference-counted visits)
+and the `cpu_baseline` object.
 
 A step = one pass of the hot path over one frame, everything inside the timed region: mr_render_direct generates every
 primary ray from the camera (Camera::eyeRay), traces it, builds and traces the shadow ray of every hit and shades the
@@ -48,6 +53,29 @@ ROUND_TAG = "r03"
 PMC_FILE = next((f for f in (os.path.join(ROOT, "profiles", "%s_bench_pmc.json" % t) for t in (ROUND_TAG, "r02")) if os.path.exists(f)),
                 os.path.join(ROOT, "profiles", "r02_bench_pmc.json"))
 SQ_COUNTERS = "SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_THREAD_CYCLES_VALU SQ_WAVES SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY"
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: the whole dump, sample row indices included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64 only).  When the arrays together would pass
+    DUMP_LIMIT_BYTES, every array of two or more dimensions is cut to a fixed, seeded sample of its leading-axis rows
+    (image rows, queries), and the sampled row numbers go to DIR/<name>_rows.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError("--dump-outputs: %s is %s, not float32 / float64" % (k, v.dtype))
+    small = sum(v.nbytes for v in arrays.values() if v.ndim < 2)
+    big = [v for v in arrays.values() if v.ndim > 1]
+    frac = 1.0
+    if small + sum(v.nbytes for v in big) > DUMP_LIMIT_BYTES:
+        frac = (0.95 * DUMP_LIMIT_BYTES - small) / sum(v.nbytes + 8 * v.shape[0] for v in big)
+    for k, v in arrays.items():
+        if frac < 1.0 and v.ndim > 1:
+            rows = np.sort(np.random.RandomState(168).choice(v.shape[0], max(1, int(v.shape[0] * frac)), replace=False))
+            np.save(os.path.join(out_dir, k + "_rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def algorithmic_bytes_per_ray(V, T):
@@ -275,15 +303,16 @@ def photon_main(a, world, rank, local_dev, dev, red_dev, backend):
         scene.final_gather(maps[0], maps[1], fr.d_rays, fr.d_hits, n, scratch, rgb, max_dist=max_dist, nphotons=k, spp=1, stream=stream)
     P, N = scratch[:3 * n].view(n, 3), scratch[3 * n:6 * n].view(n, 3)
     nq = int((N[:, 0] == N[:, 0]).sum().item()) if n else 0           # NaN normal = no query (miss / non-diffuse hit)
-    out = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev)
+    outs = [torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev) for _ in maps]     # one estimate per map
+    out = outs[-1]
     torch.cuda.synchronize()
 
     def one_step(events=None):
-        for m in maps:
+        for m, o in zip(maps, outs):
             e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if events is not None else None
             if e: e[0].record(stream)
             if n:
-                m.irradiance_estimate(P, N, n, out, max_dist=max_dist, nphotons=k, stream=stream)
+                m.irradiance_estimate(P, N, n, o, max_dist=max_dist, nphotons=k, stream=stream)
             if e:
                 e[1].record(stream)
                 events.append(e)
@@ -300,7 +329,7 @@ def photon_main(a, world, rank, local_dev, dev, red_dev, backend):
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    events = []
+    events = [] if a.full else None
     t0 = time.perf_counter()
     for _ in range(a.steps):
         one_step(events)
@@ -309,6 +338,8 @@ def photon_main(a, world, rank, local_dev, dev, red_dev, backend):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:      # this rank's queries: the photon step has no collective
+        dump_outputs(a.dump_outputs, {"irradiance_" + name: o[:n].cpu().numpy() for name, o in zip(("global", "caustic"), outs)})
     tot = torch.tensor([float(nq * len(maps)), elapsed], dtype=torch.float64, device=red_dev)
     ranks_seen = 1
     if world > 1:
@@ -319,7 +350,9 @@ def photon_main(a, world, rank, local_dev, dev, red_dev, backend):
         est_per_step, elapsed, ranks_seen = float(q_all.item()), float(tmax.item()), int(round(float(ones.item())))
     else:
         est_per_step = float(nq * len(maps))
-    if rank == 0:
+    workload = "%s %dx%d 1spp hits: %d queries x 2 photon maps of %d, k=%d" % (label, W, H, int(est_per_step / len(maps)), a.photons, k)
+    roof = None
+    if rank == 0 and a.full:
         ms = [e0.elapsed_time(e1) for e0, e1 in events]
         avg_ms = sum(ms) / max(len(ms), 1)
         launch_s = avg_ms * 1e-3
@@ -334,7 +367,6 @@ def photon_main(a, world, rank, local_dev, dev, red_dev, backend):
         rec_pre = sum(w["records_prepass"] for w in work.values()) / len(maps)
         boxes = sum(w["boxes_measured"] for w in work.values()) / len(maps)
         alg_bytes = 32.0 * (rec_search + rec_pre) + 64.0 * boxes + 24.0 * nq + 12.0 * nq   # records + child boxes + query in + irradiance out
-        workload = "%s %dx%d 1spp hits: %d queries x 2 photon maps of %d, k=%d" % (label, W, H, int(est_per_step / len(maps)), a.photons, k)
         pmc, pmc_source, pmc_note = None, None, None
         if world == 1 and not a.no_pmc:
             leg = ["--config", "photon", "--pmc-leg", "--no-cpu-baseline", "--no-pmc", "--width", str(W), "--height", str(H),
@@ -397,6 +429,7 @@ def photon_main(a, world, rank, local_dev, dev, red_dev, backend):
         if traffic is not None and launch_s > 0:
             roof["hbm"]["measured_GBps"] = round(traffic / launch_s / 1e9, 1)
             roof["hbm"]["hbm_measured_frac"] = round(traffic / launch_s / 1e9 / HBM_PEAK_GBPS, 4)
+    if rank == 0:
         outj = {"metric": "Mqueries/s (photon-map irradiance estimates, k=%d)" % k, "value": round(est_per_step * a.steps / elapsed / 1e6, 3),
                 "unit": "Mqueries/s", "n_gpus": world, "rccl_ranks": ranks_seen if backend == "nccl" or world == 1 else 0,
                 "dist_backend": backend if world > 1 else None, "steps": a.steps, "warmup": a.warmup,
@@ -407,9 +440,10 @@ def photon_main(a, world, rank, local_dev, dev, red_dev, backend):
                            "step": "mr_irradiance_estimate on the global and on the caustic map for every query (queries resident in HBM)",
                            "photon_maps": "synthetic: photons uniform on the scene's surfaces, cosine-distributed directions, seeds 168 / 169 (SURVEY 8d)",
                            "balance_and_upload_s": round(t_bal, 3),
-                           "parallelism": "queries of the frame's interleaved row bands of %d over %d GPU(s), maps replicated, no collective" % (band, world)},
-                "roofline": roof}
-        if world == 1 and not a.no_cpu_baseline:
+                           "parallelism": "queries of the frame's interleaved row bands of %d over %d GPU(s), maps replicated, no collective" % (band, world)}}
+        if roof is not None:
+            outj["roofline"] = roof
+        if a.full and world == 1 and not a.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import pyoracle as po
             Ph, Nh = P.cpu().numpy(), N.cpu().numpy()
@@ -487,22 +521,30 @@ def main():
                     help="the round-1 pipeline: resident ray buffers, five kernels per step (eye rays generated once, outside "
                          "the step)")
     ap.add_argument("--image-order", action="store_true", help="samples in image order instead of the tiled order (< 64 spp)")
-    ap.add_argument("--cpu-spp", type=int, default=8, help="samples per pixel of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 passes (use the committed profiles/rNN_bench_pmc.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the `roofline` object (live rocprofv3 passes, reference-counted "
+                         "visits, device work counters) and the `cpu_baseline` object")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (rank 0; float32 / float64, "
+                         "at most 64 MB, larger outputs as a seeded sample of rows)")
+    ap.add_argument("--cpu-spp", type=int, default=8, help="--full: samples per pixel of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline object")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the live rocprofv3 passes (use the committed profiles/rNN_bench_pmc.json)")
     ap.add_argument("--pmc-leg", action="store_true", help=argparse.SUPPRESS)   # internal: the profiled child
     ap.add_argument("--config", choices=["frame", "photon"], default="frame",
                     help="frame: BASELINE config 4 (the default); photon: BASELINE config 5, Photon_map::irradiance_estimate on the "
                          "frame's primary hits")
     ap.add_argument("--photons", type=int, default=200000, help="--config photon: photons per map (Scene.h:67-68)")
     ap.add_argument("--k", type=int, default=500, help="--config photon: PHOTON_SAMPLES (Miro.h:16)")
-    ap.add_argument("--cpu-queries", type=int, default=20000, help="--config photon: queries of the CPU baseline sample")
+    ap.add_argument("--cpu-queries", type=int, default=20000, help="--config photon --full: queries of the CPU baseline sample")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, rendezvous, count them with an all-reduce, print {n_gpus, rccl_ranks} and stop: "
                          "checks the launch path on a box without GPUs (with MIRO_DIST_BACKEND=gloo); renders nothing")
     a = ap.parse_args()
     if a.steps is None:
         a.steps = 5 if a.config == "photon" else 50
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -647,7 +689,7 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    events = []
+    events = [] if a.full else None
     t0 = time.perf_counter()
     for _ in range(a.steps):
         one_step(events)
@@ -681,8 +723,19 @@ def main():
         rays_per_step = float(n_p + n_s)
         ranks_seen = 1
 
-    if rank == 0:
-        workload = "%s %dx%d %dspp %s" % (label, W, H, spp, a.mode)
+    if a.dump_outputs:
+        # the last timed frame as its caller receives it: the whole framebuffer (on rank 0, gathered) and the rays it traced
+        counts = torch.tensor([float(n_p), float(n_s)], dtype=torch.float64, device=red_dev)
+        if world > 1:
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            last = (frame_no[0] - 1) % len(frs)
+            rgb = gathers[last].full if gathers is not None else frs[last].d_rgb[:fr0.n_pixels].view(H, W, 3)
+            dump_outputs(a.dump_outputs, {"rgb": rgb.cpu().numpy(), "rays_per_step": counts.cpu().numpy()})
+
+    workload = "%s %dx%d %dspp %s" % (label, W, H, spp, a.mode)
+    roof = None
+    if rank == 0 and a.full:
         # ---- dominant kernel: live HIP-event durations of its launches on rank 0's stream
         if fused:
             ms_k = [e[0].elapsed_time(e[1]) for e in events]
@@ -764,6 +817,7 @@ def main():
             "measured_GBps": round(traffic / kernel_s_per_step / 1e9, 1) if traffic is not None else None,
             "hbm_measured_frac": round(traffic / kernel_s_per_step / 1e9 / HBM_PEAK_GBPS, 4) if traffic is not None else None,
         }
+    if rank == 0:
         out = {
             "metric": "Mrays/s (%s)" % a.mode,
             "value": round(rays_per_step * a.steps / elapsed / 1e6, 2),
@@ -798,9 +852,10 @@ def main():
                 # shadows, 524 288 rays in 0.166750 s (writeup/A2/Readme.tex:83,98) -- not this workload, so no vs_baseline
                 "reference_writeup_mrays_s_sponza_512x512": 3.14,
             },
-            "roofline": roof,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if roof is not None:
+            out["roofline"] = roof
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(desc, label, W, H, a.cpu_spp)
         print(json.dumps(out))
     if world > 1:

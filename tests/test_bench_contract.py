@@ -1,10 +1,11 @@
-"""bench.py's output contract: ONE JSON line on stdout with the driver's fields, the `roofline` object of the dominant
-kernel and the `cpu_baseline` object -- checked on a small frame so that the test takes seconds."""
+"""bench.py's output contract: ONE JSON line on stdout with the driver's fields; with `--full` also the `roofline` object
+of the dominant kernel and the `cpu_baseline` object -- checked on a small frame so that the test takes seconds."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--width", "320", "--height", "184", "--spp", "4", "--cpu-spp", "1"],
+                        "--width", "320", "--height", "184", "--spp", "4", "--cpu-spp", "1", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -50,7 +51,7 @@ def test_bench_batched_pipeline_still_runs():
     """`--batched`: the round-1 step (five kernels over resident rays) stays available for comparison; its line carries the
     per-launch times of both trace launches and no VALU fraction (the committed counters belong to the fused kernel)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batched",
-                        "--width", "320", "--height", "184", "--spp", "4", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--width", "320", "--height", "184", "--spp", "4", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert j["value"] > 0 and j["config"]["step"].startswith("batched")
@@ -117,11 +118,11 @@ def test_bench_gpus_n_refuses_to_measure_fewer_gpus():
 
 @pytest.mark.gpu
 def test_bench_photon_config_prints_one_contract_line():
-    """`bench.py --config photon` (BASELINE config 5) on a small frame and small maps: one JSON line with the driver's fields,
+    """`bench.py --config photon --full` (BASELINE config 5) on a small frame and small maps: one JSON line with the driver's fields,
     the irradiance kernel's `roofline` (live PMC or the committed counters, device work counters, algorithmic bytes) and the
     oracle-timed `cpu_baseline`."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "photon", "--width", "160", "--height", "90",
-                        "--photons", "20000", "--k", "50", "--steps", "1", "--warmup", "1", "--cpu-queries", "400"],
+                        "--photons", "20000", "--k", "50", "--steps", "1", "--warmup", "1", "--cpu-queries", "400", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -150,3 +151,97 @@ def test_bench_primary_only_mode():
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert j["metric"] == "Mrays/s (primary)" and j["config"]["rays_per_step"] == 128 * 128
     assert j["config"]["shadow_query"].startswith("none")
+
+
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config")
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_stays_within_64_mb_as_a_seeded_sample(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files: as they are when they fit in 64 MB, else every image-sized array
+    becomes a fixed, seeded sample of its rows (the same rows in every run) with the row numbers beside it."""
+    bench = _load_bench()
+    small = {"rgb": np.random.RandomState(1).rand(184, 320, 3).astype(np.float32), "rays_per_step": np.array([5.0, 3.0])}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert sorted(os.listdir(tmp_path / "small")) == ["rays_per_step.npy", "rgb.npy"]
+    for k, v in small.items():
+        got = np.load(tmp_path / "small" / (k + ".npy"))
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    big = {"rgb": np.arange(2400 * 3840 * 3, dtype=np.float32).reshape(2400, 3840, 3), "rays_per_step": np.array([1.0, 2.0])}
+    for d in ("big_a", "big_b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    sizes = sum(os.path.getsize(tmp_path / "big_a" / f) for f in os.listdir(tmp_path / "big_a"))
+    assert sizes <= 64 << 20, sizes
+    rows = np.load(tmp_path / "big_a" / "rgb_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) > 1000 and np.all(np.diff(rows) > 0)
+    got = np.load(tmp_path / "big_a" / "rgb.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, big["rgb"][rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "big_a" / "rays_per_step.npy"), big["rays_per_step"])
+    for f in os.listdir(tmp_path / "big_a"):
+        assert np.array_equal(np.load(tmp_path / "big_a" / f), np.load(tmp_path / "big_b" / f)), f
+    with pytest.raises(TypeError):
+        bench.dump_outputs(str(tmp_path / "ints"), {"prim": np.zeros((4, 4), np.uint32)})
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_frame(miro, tmp_path):
+    """Without --full the line holds the headline fields only (no roofline, no cpu_baseline), and --steps sets the timed
+    steps.  --dump-outputs writes the last timed frame: its framebuffer -- bit for bit the frame the library renders for the
+    same camera, samples and seed -- and the rays it traced; two runs with the same arguments write the same arrays."""
+    import torch
+    from miro_amd import frame as mframe
+    from miro_amd import scenes
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--width", "320", "--height", "184", "--spp", "4", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        j = json.loads(lines[0])
+        for k in HEADLINE:
+            assert k in j, k
+        assert "roofline" not in j and "cpu_baseline" not in j
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0 and j["dtype"] == "f32"
+        rgb, counts = np.load(d / "rgb.npy"), np.load(d / "rays_per_step.npy")
+        assert rgb.dtype == np.float32 and rgb.shape == (184, 320, 3) and np.isfinite(rgb).all() and rgb.max() > 0
+        assert counts.dtype == np.float64 and counts[0] == 320 * 184 * 4 and counts.sum() == j["config"]["rays_per_step"]
+        dumps.append((rgb, counts))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+    desc = scenes.SCENES["sponza"]
+    scene = miro.Scene(0)
+    scenes.populate(scene, desc)
+    scene.build(4)
+    fr = mframe.FusedFrame(scene, desc, 320, 184, spp=4, jitter=True, seed=168, tiled=True)
+    fr.step()
+    torch.cuda.synchronize()
+    assert np.array_equal(fr.d_rgb.cpu().numpy().reshape(184, 320, 3), dumps[0][0])
+
+
+@pytest.mark.gpu
+def test_bench_photon_plain_run_dumps_both_estimates(tmp_path):
+    """`--config photon` without --full: the headline line only; --dump-outputs writes the last step's irradiance estimate
+    of each photon map, one row per query."""
+    d = tmp_path / "photon"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "photon", "--width", "160", "--height", "90",
+                        "--photons", "20000", "--k", "50", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    j = json.loads(lines[0])
+    assert "roofline" not in j and "cpu_baseline" not in j and j["steps"] == 2 and j["ms_per_step"] > 0
+    g, c = np.load(d / "irradiance_global.npy"), np.load(d / "irradiance_caustic.npy")
+    for a in (g, c):
+        assert a.dtype == np.float32 and a.shape == (160 * 90, 3) and np.isfinite(a).all() and a.max() > 0
+    assert not np.array_equal(g, c)         # two maps of different photons
