@@ -44,6 +44,12 @@ void release_device(mr_scene *s) {
     d = DeviceScene();
     (void)hipFree(s->d_stats); s->d_stats = nullptr;
     (void)hipFree(s->d_work_counters); s->d_work_counters = nullptr;
+    for (EyeTables &t : s->eye_tables.set) {
+        (void)hipFree(t.d);
+        if (t.ready) (void)hipEventDestroy(static_cast<hipEvent_t>(t.ready));
+        t = EyeTables();
+    }
+    s->eye_tables.calls = 0;
     (void)hipFree(s->d_stage_rays); (void)hipFree(s->d_stage_hits);
     s->d_stage_rays = s->d_stage_hits = nullptr;
     s->stage_cap = 0;
@@ -806,7 +812,8 @@ mr_status mr_render_direct(mr_scene *s, const mr_frame_desc *frame, float *d_rgb
     if (fd.band_world <= 1) { fd.band_world = 1; fd.band_rank = 0; if (fd.band_rows == 0) fd.band_rows = 1; }
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_frame(s->dev, fd, d_rgb, d_hits, d_shadow_hits, reinterpret_cast<unsigned long long *>(d_counts),
-                        s->d_work_counters + kWorkCounters + (s->next_counter.fetch_add(1) % kWorkCounters), static_cast<hipStream_t>(stream));
+                        s->d_work_counters + kWorkCounters + (s->next_counter.fetch_add(1) % kWorkCounters), s->eye_tables,
+                        static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_scene_set_materials(mr_scene *s, const mr_material *mats, uint32_t n_mats, const uint32_t *prim_material) {

@@ -15,6 +15,8 @@
 // rays, hit records and pixels are the same bits as the batched pipeline's -- tests/test_frame.py compares them.
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+
 #include "mr_eye.h"
 #include "mr_internal.h"
 #include "mr_phong.h"
@@ -40,7 +42,43 @@ struct FrameArgs {
     // which chunks (kTraceBlock consecutive samples) a workgroup renders: see frame_schedule()
     uint32_t body_wgs, body_iters, tail_base, tail_chunks;      // tail_base = body_wgs * body_iters: the first tail chunk
     unsigned *tail_counter;      // hand-out counter of the tail chunks: 0 before the launch, left at 0 by its last reader
+    // eye-relative tables of the primary trace (kEyeRel kernels; eye_tables): node records and root box with the eye subtracted
+    // from every corner, triangle records of tri_test_rel.  `build` != 0: this launch writes the tables from tp.nodes /
+    // tp.tris (n_inner nodes, n_rec records) instead of rendering
+    float4 *rel_nodes, *rel_tris;
+    float rel_root_lo[3], rel_root_hi[3];
+    uint32_t build, n_inner, n_rec;
 };
+
+// The eye-relative tables, one thread per node record and per triangle record, every value in the fp32 operations the trace
+// itself would do: corner - eye is the subtraction of slab_axis / slab_box_oct / exact_quot, tri_origin_terms is the function
+// tri_test<true> calls.  The node flag is the scene's, or-ed with "the eye is irregular" (regular_pos): lane_is_regular sees
+// a zero origin in the relative trace, and it is through the flag that such an eye still sends every visit to the reference's
+// own divisions ((a - 0) / d there is (corner - o) / d).
+__device__ __forceinline__ void eye_tables(const FrameArgs &a) {
+    const unsigned i = blockIdx.x * (unsigned)kTraceBlock + threadIdx.x;
+    const float ex = a.eye.eye[0], ey = a.eye.eye[1], ez = a.eye.eye[2];
+    if (i < a.n_inner) {
+        const float4 *q = a.tp.nodes + 4 * (size_t)i;
+        const float4 q0 = q[0], q1 = q[1], q2 = q[2];     // (c0 x, c0 y), (c1 x, c1 y), (c0 z, c1 z): lo, hi each
+        int4 q3 = *reinterpret_cast<const int4 *>(q + 3);
+        if (!(regular_pos(ex) && regular_pos(ey) && regular_pos(ez))) q3.z |= 1;
+        float4 *d = a.rel_nodes + 4 * (size_t)i;
+        d[0] = make_float4(q0.x - ex, q0.y - ex, q0.z - ey, q0.w - ey);
+        d[1] = make_float4(q1.x - ex, q1.y - ex, q1.z - ey, q1.w - ey);
+        d[2] = make_float4(q2.x - ez, q2.y - ez, q2.z - ez, q2.w - ez);
+        *reinterpret_cast<int4 *>(d + 3) = q3;
+    }
+    if (i < a.n_rec) {
+        const float4 *q = a.tp.tris + 3 * (size_t)i;
+        const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+        const TriOriginTerms o = tri_origin_terms(q0, q1, q2, ex, ey, ez);
+        float4 *d = a.rel_tris + 3 * (size_t)i;
+        d[0] = make_float4(q2.y, q2.z, q2.w, o.pn);      // n, dot(eye - A, n)
+        d[1] = make_float4(o.u.x, o.u.y, o.u.z, o.w.x);  // cross(eye - A, C - A), cross(B - A, eye - A).x
+        d[2] = make_float4(o.w.y, o.w.z, 0.0f, 0.0f);
+    }
+}
 
 // the longest run of chunks one reading of the tail counter hands out: a quarter of a body workgroup's share, 1 ... 8
 __device__ __forceinline__ unsigned tail_first_run(unsigned body_iters) {
@@ -124,6 +162,10 @@ inline FrameShape frame_schedule(unsigned long long chunks) {
 // end time (100 MHz constant clock), the CU it ran on and its XCD -- where the launch's idle VALU cycles sit
 __device__ unsigned long long g_wg_times[4 * 131072];
 #endif
+// kEyeRel (VAR 794, the default traversal of triangle-only scenes, every SHADOW / MAT form): the primary ray is traced on the
+// eye-relative tables from a zero origin (trace_ray's REL), the shadow ray on the scene's own.  Every primary ray starts at
+// the eye, so the origin's share of each slab and triangle test is the same for all of them: computed once per eye by a build
+// launch (eye_tables, eye_tables_for) instead of once per visit in every lane -- 12 VALU of a two-child visit, 26 of a triangle test.
 template <int VAR, int SHADOW, bool MAT>
 #ifndef MIRO_FRAME_WAVES
 #define MIRO_FRAME_WAVES 7      /* 72 registers; 6 (80 registers, nothing spilled to scratch) is 6.5 % slower on the bench frame: profiles/r03_tail_ab.log */
@@ -132,6 +174,11 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
 #if defined(MIRO_WG_TIMES) && MIRO_TRACE_BLOCK == 256
     const unsigned long long wg_t0 = wall_clock64();
 #endif
+    constexpr bool kEyeRel = VAR == 794;
+    if (kEyeRel && a.build) {
+        eye_tables(a);
+        return;
+    }
     extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
     __shared__ unsigned s_shadow_rays[kTraceBlock / 64];
     const int tid = threadIdx.x;
@@ -200,7 +247,17 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
             ray_setup(r, ra, rb);
             Lane L;
             int plane_hit;
-            trace_ray<true, false, false, VAR>(a.tp, r, rb.w, live, L, plane_hit, s_stack, tid, st);
+            if (kEyeRel) {
+                TraceParams tp = a.tp;
+                tp.nodes = a.rel_nodes; tp.tris = a.rel_tris;
+                for (int k = 0; k < 3; k++) {       // read where used: once per ray, not held in registers across the loop
+                    tp.root_lo[k] = kernarg_now<float>(offsetof(FrameArgs, rel_root_lo) + 4 * k);
+                    tp.root_hi[k] = kernarg_now<float>(offsetof(FrameArgs, rel_root_hi) + 4 * k);
+                }
+                trace_ray<true, false, false, VAR, kEyeRel>(tp, r, rb.w, live, L, plane_hit, s_stack, tid, st);
+            } else {
+                trace_ray<true, false, false, VAR>(a.tp, r, rb.w, live, L, plane_hit, s_stack, tid, st);
+            }
             h = make_hit<kObj>(a.tp, L, plane_hit, rb.w);
         }
         if (a.hits && live) reinterpret_cast<float4 *>(a.hits)[idx] = *reinterpret_cast<const float4 *>(&h);
@@ -216,16 +273,18 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
         float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(1.f, 1.f, 1.f, -1.f);
         if (hit) {
             float P[3], N[3];
+            // the ray's origin: the eye (a hit lane is a live one); kEyeRel reads it from the arguments, uniform, where it is used
+            const float ox = kEyeRel ? a.eye.eye[0] : ra.x, oy = kEyeRel ? a.eye.eye[1] : ra.y, oz = kEyeRel ? a.eye.eye[2] : ra.z;
             if (MAT) {
                 rec::MeshMat mm;
                 mm.s = a.m; mm.mats = a.mats; mm.prim_mat = a.prim_mat;
                 rec::LightArgs la;
                 for (int k = 0; k < 3; k++) { la.L[k] = a.lt.L[k]; la.color[k] = a.lt.color[k]; }
                 la.wattage = a.lt.wattage;
-                rec::surface_point_od(mm, ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
+                rec::surface_point_od(mm, ox, oy, oz, rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
                 rec::phong_terms(la, rec::material_of(mm, h.prim), P, N, rb.x, rb.y, rb.z, c, highlight);
             } else {
-                surface_od<true>(a.m, ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
+                surface_od<true>(a.m, ox, oy, oz, rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
             }
             if (SHADOW != 2) shadow_ray_of(P, a.lt.L[0], a.lt.L[1], a.lt.L[2], sa, sb);
             if (!MAT) phong_direct(a.lt, P, N, rb.x, rb.y, rb.z, c);                            // Phong.cpp:116-156
@@ -352,10 +411,67 @@ mr_status launch_frame_default(const FrameArgs &a, bool any, bool no_shadows, bo
 #ifndef MR_FRAME_ENTRY
 #define MR_FRAME_ENTRY launch_frame_b256
 #endif
+// The eye-relative tables for the eye of `a` (kEyeRel kernels): a set of the pool that holds them already, else the least recently
+// used set rebuilt by a launch of the frame kernel in its build mode on `stream` (EyeTablePool, mr_internal.h).  A set built on
+// another stream is waited for through the event recorded after its build.
+static mr_status eye_tables_for(const DeviceScene &ds, EyeTablePool &pool, FrameArgs &a, hipStream_t stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    MR_HIP_CHECK(hipStreamIsCapturing(stream, &cs));
+    const bool capturing = cs != hipStreamCaptureStatusNone;
+    std::lock_guard<std::mutex> lock(pool.mu);
+    const uint64_t call = ++pool.calls;
+    EyeTables *e = nullptr;
+    if (!capturing)
+        for (EyeTables &c : pool.set)
+            if (c.reusable && memcmp(c.eye, a.eye.eye, sizeof(c.eye)) == 0) { e = &c; break; }
+    const bool build = e == nullptr;
+    if (build) {
+        e = &pool.set[0];
+        for (EyeTables &c : pool.set)
+            if (c.last_use < e->last_use) e = &c;
+        e->reusable = false;
+        if (!e->d || !e->ready) {
+            // the first use of a set may be inside a graph capture: allocations are no stream work, let them pass
+            hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+            MR_HIP_CHECK(hipThreadExchangeStreamCaptureMode(&mode));
+            hipError_t err = e->d ? hipSuccess : hipMalloc(reinterpret_cast<void **>(&e->d), eye_table_bytes(ds));
+            if (err == hipSuccess && !e->ready)
+                err = hipEventCreateWithFlags(reinterpret_cast<hipEvent_t *>(&e->ready), hipEventDisableTiming);
+            MR_HIP_CHECK(hipThreadExchangeStreamCaptureMode(&mode));
+            MR_HIP_CHECK(err);
+        }
+    } else if (e->stream != (void *)stream) {
+        MR_HIP_CHECK(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(e->ready), 0));
+    }
+    e->last_use = call;
+    a.rel_nodes = e->d;
+    a.rel_tris = e->d + 4 * (size_t)ds.n_inner;
+    for (int c = 0; c < 3; c++) { a.rel_root_lo[c] = ds.root_lo[c] - a.eye.eye[c]; a.rel_root_hi[c] = ds.root_hi[c] - a.eye.eye[c]; }
+    if (!build) return MR_OK;
+    FrameArgs b = a;
+    b.build = 1; b.n_inner = ds.n_inner; b.n_rec = ds.n_tris;
+    const uint32_t n = ds.n_inner > ds.n_tris ? ds.n_inner : ds.n_tris;
+    if (n) {
+        hipLaunchKernelGGL((frame_kernel<794, 0, false>), dim3((n + kTraceBlock - 1) / kTraceBlock), dim3(kTraceBlock), 0, stream, b);
+        MR_HIP_CHECK(hipGetLastError());
+    }
+    if (capturing) e->captured = true;
+    if (!e->captured) {     // (a captured set is never reused: nobody waits for it)
+        MR_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(e->ready), stream));
+        memcpy(e->eye, a.eye.eye, sizeof(e->eye));
+        e->stream = (void *)stream;
+        e->reusable = true;
+    }
+    return MR_OK;
+}
+
 mr_status MR_FRAME_ENTRY(const DeviceScene &ds, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, mr_hit *d_shadow_hits,
-                         unsigned long long *d_counts, unsigned long long *work_counter, hipStream_t stream) {
+                         unsigned long long *d_counts, unsigned long long *work_counter, EyeTablePool &eye_pool, hipStream_t stream) {
     FrameArgs a;
     a.tail_counter = reinterpret_cast<unsigned *>(work_counter);
+    a.rel_nodes = nullptr; a.rel_tris = nullptr;
+    for (int c = 0; c < 3; c++) { a.rel_root_lo[c] = 0.0f; a.rel_root_hi[c] = 0.0f; }
+    a.build = 0; a.n_inner = 0; a.n_rec = 0;
     const uint32_t spp = fd.spp;
     if (spp == 0 || spp > 64 || (spp & (spp - 1)))
         return fail(MR_ERR_INVALID, "mr_render_direct: spp must be a power of two <= 64 (got %u); use the batched pipeline", spp);
@@ -415,6 +531,9 @@ mr_status MR_FRAME_ENTRY(const DeviceScene &ds, const mr_frame_desc &fd, float *
         return product ? launch_frame_plain<43>(a, any, stream) : launch_frame_default<826>(a, any, no_shadows, mat, stream);
     if (vote) return product ? launch_frame_plain<73>(a, any, stream) : launch_frame_plain<88>(a, any, stream);
     if (product) return launch_frame_plain<267>(a, any, stream);
+    // the eye-relative tables (and the root box relative to the eye, in the same fp32 subtraction as the trace's)
+    mr_status st = eye_tables_for(ds, eye_pool, a, stream);
+    if (st != MR_OK) return st;
     return launch_frame_default<794>(a, any, no_shadows, mat, stream);
 }
 

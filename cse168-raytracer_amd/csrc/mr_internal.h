@@ -156,17 +156,40 @@ mr_status launch_untile(const float *d_slots, float *d_image, uint32_t W, uint32
                         hipStream_t stream);
 
 // the fused direct-light frame (mr_frame.hip)
+// The eye-relative tables of the fused frame (mr_frame.hip: eye_tables), per scene: up to kWorkCounters sets, each built for
+// one eye.  A call whose eye a set already holds uses it as it is; otherwise it rebuilds the least recently used set -- whose
+// last user is at least kWorkCounters calls back, so finished by the contract of mr_render_direct (miro_hip.h).  A set built
+// inside a graph capture is rebuilt by every replay of the graph, whenever that is: from then on it is never taken as holding
+// any eye (every call that picks it rebuilds it).
+struct EyeTables {
+    float4 *d = nullptr;          // n_inner node records of 64 bytes, then n_tris triangle records of 48 (eye_table_bytes)
+    float eye[3] = {0.f, 0.f, 0.f};
+    bool reusable = false;        // holds the tables of `eye` (built outside a capture)
+    bool captured = false;        // a captured graph rebuilds it
+    uint64_t last_use = 0;        // pool call number of its last user, 0 = never used
+    void *ready = nullptr;        // hipEvent_t recorded after its build, on the stream it was built on
+    void *stream = nullptr;
+};
+struct EyeTablePool {
+    std::mutex mu;
+    EyeTables set[kWorkCounters];
+    uint64_t calls = 0;
+};
+inline size_t eye_table_bytes(const DeviceScene &ds) {
+    const size_t b = (size_t)ds.n_inner * 64 + (size_t)ds.n_tris * 48;
+    return b ? b : 64;
+}
 mr_status launch_frame_b256(const DeviceScene &ds, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, mr_hit *d_shadow_hits,
-                            unsigned long long *d_counts, unsigned long long *work_counter, hipStream_t stream);
+                            unsigned long long *d_counts, unsigned long long *work_counter, EyeTablePool &eye_pool, hipStream_t stream);
 mr_status launch_frame_b128(const DeviceScene &ds, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, mr_hit *d_shadow_hits,
-                            unsigned long long *d_counts, unsigned long long *work_counter, hipStream_t stream);
+                            unsigned long long *d_counts, unsigned long long *work_counter, EyeTablePool &eye_pool, hipStream_t stream);
 // mr_frame.hip in its two workgroup sizes: frames of up to ~10 M samples (1080p at 4 spp) in 128-thread workgroups
 inline mr_status launch_frame(const DeviceScene &ds, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, mr_hit *d_shadow_hits,
-                              unsigned long long *d_counts, unsigned long long *work_counter, hipStream_t stream) {
+                              unsigned long long *d_counts, unsigned long long *work_counter, EyeTablePool &eye_pool, hipStream_t stream) {
     const unsigned long long rows = fd.band_world > 1 ? (fd.H + fd.band_world - 1) / fd.band_world : (fd.y1 > fd.y0 ? fd.y1 - fd.y0 : 0);
     const unsigned long long samples = rows * fd.W * fd.spp;
-    return samples <= 10000000ull ? launch_frame_b128(ds, fd, d_rgb, d_hits, d_shadow_hits, d_counts, work_counter, stream)
-                                  : launch_frame_b256(ds, fd, d_rgb, d_hits, d_shadow_hits, d_counts, work_counter, stream);
+    return samples <= 10000000ull ? launch_frame_b128(ds, fd, d_rgb, d_hits, d_shadow_hits, d_counts, work_counter, eye_pool, stream)
+                                  : launch_frame_b256(ds, fd, d_rgb, d_hits, d_shadow_hits, d_counts, work_counter, eye_pool, stream);
 }
 
 mr_status launch_shade_accumulate(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
@@ -224,6 +247,8 @@ struct mr_scene {
     unsigned long long *d_stats = nullptr;
     unsigned long long *d_work_counters = nullptr;   // ring of kWorkCounters hand-out counters
     std::atomic<uint32_t> next_counter{0};
+    // eye-relative tables of mr_render_direct, a set allocated on first use: mr::eye_table_bytes each
+    mr::EyeTablePool eye_tables;
     // grow-only staging buffers for host-pointer traces; stage_mutex serialises the calls that use them, so that
     // mr_trace may be called concurrently from several host threads (Scene::trace is const and re-entrant,
     // Scene.cpp:112-115 calls it from every OpenMP worker)

@@ -224,27 +224,57 @@ __device__ __forceinline__ void slab_box_lean(float lox, float hix, float loy, f
 // Triangle::intersect (Triangle.cpp:150-158).  q0..q2 = the 48-byte record.  Returns true when the
 // reference's reject test passes with tMax = best; outputs t, beta, gamma.
 // ---------------------------------------------------------------------------------------------------
+// The origin's share of the exact Triangle::intersect: p = o - A, dot(p, n), u = cross(p, C-A), w = cross(B-A, p), each
+// fp32 op rounded on its own in the reference's order.  tri_test<true> calls these per ray; the eye-relative table of the
+// fused frame (mr_frame.hip: eye_tables) calls them once per frame for o = the camera eye through tri_origin_terms -- the
+// same functions, so the stored terms are the bits tri_test<true> would compute for every primary ray.
+// (q0..q2: A, B-A, C-A, (B-A)x(C-A) as in the record; tri_test<true> interleaves the pieces with the direction's terms as
+// before -- computing all of them first cost the 267 frame kernel two spilled registers.)
+__device__ __forceinline__ float3 tri_p(const float4 q0, float ox, float oy, float oz) {
+    return make_float3(ox - q0.x, oy - q0.y, oz - q0.z);                                 // o - A
+}
+__device__ __forceinline__ float tri_pn(const float3 p, const float4 q2) {
+    return (p.x * q2.y + p.y * q2.z) + p.z * q2.w;                                       // dot(o - A, n)
+}
+__device__ __forceinline__ float3 tri_u(const float3 p, const float4 q1, const float4 q2) {
+    const float Cx = q1.z, Cy = q1.w, Cz = q2.x;                                         // cross(o - A, C - A)
+    return make_float3(p.y * Cz - p.z * Cy, p.z * Cx - p.x * Cz, p.x * Cy - p.y * Cx);
+}
+__device__ __forceinline__ float3 tri_w(const float3 p, const float4 q0, const float4 q1) {
+    const float Bx = q0.w, By = q1.x, Bz = q1.y;                                         // cross(B - A, o - A)
+    return make_float3(By * p.z - Bz * p.y, Bz * p.x - Bx * p.z, Bx * p.y - By * p.x);
+}
+struct TriOriginTerms { float pn; float3 u, w; };
+__device__ __forceinline__ TriOriginTerms tri_origin_terms(const float4 q0, const float4 q1, const float4 q2, float ox, float oy,
+                                                           float oz) {
+    const float3 p = tri_p(q0, ox, oy, oz);
+    TriOriginTerms o;
+    o.pn = tri_pn(p, q2);
+    o.u = tri_u(p, q1, q2);
+    o.w = tri_w(p, q0, q1);
+    return o;
+}
+
 template <bool EXACT>
 __device__ __forceinline__ bool tri_test(const float4 q0, const float4 q1, const float4 q2, const RayRegs &r,
                                          float tmax, float &t, float &beta, float &gamma) {
-    const float Ax = q0.x, Ay = q0.y, Az = q0.z;
-    const float Bx = q0.w, By = q1.x, Bz = q1.y;      // B - A
-    const float Cx = q1.z, Cy = q1.w, Cz = q2.x;      // C - A
-    const float nx = q2.y, ny = q2.z, nz = q2.w;      // (B-A) x (C-A)
-    const float px = r.ox - Ax, py = r.oy - Ay, pz = r.oz - Az;   // o - A
     if (EXACT) {
+        const float nx = q2.y, ny = q2.z, nz = q2.w;      // (B-A) x (C-A)
+        const float3 p = tri_p(q0, r.ox, r.oy, r.oz);
         const float ddotn = (r.mx_ * nx + r.my_ * ny) + r.mz_ * nz;
-        t = ((px * nx + py * ny) + pz * nz) / ddotn;
+        t = tri_pn(p, q2) / ddotn;
         // (Leaving with "rejected" as soon as t alone rejects the triangle in every active lane -- skipping the two other
         // divisions and both cross products -- was measured: 16.21 vs 16.32 Grays/s on the bench frame, 7.56 vs 7.65 at 1 spp:
         // the wave-wide test costs more than the rare whole-wave rejection saves, profiles/r03_t_first_ab.log.)
-        // cross(o-A, C-A)
-        const float ux = py * Cz - pz * Cy, uy = pz * Cx - px * Cz, uz = px * Cy - py * Cx;
-        beta = ((r.mx_ * ux + r.my_ * uy) + r.mz_ * uz) / ddotn;
-        // cross(B-A, o-A)
-        const float wx = By * pz - Bz * py, wy = Bz * px - Bx * pz, wz = Bx * py - By * px;
-        gamma = ((r.mx_ * wx + r.my_ * wy) + r.mz_ * wz) / ddotn;
+        const float3 u = tri_u(p, q1, q2);
+        beta = ((r.mx_ * u.x + r.my_ * u.y) + r.mz_ * u.z) / ddotn;
+        const float3 w = tri_w(p, q0, q1);
+        gamma = ((r.mx_ * w.x + r.my_ * w.y) + r.mz_ * w.z) / ddotn;
     } else {
+        const float Bx = q0.w, By = q1.x, Bz = q1.y;      // B - A
+        const float Cx = q1.z, Cy = q1.w, Cz = q2.x;      // C - A
+        const float nx = q2.y, ny = q2.z, nz = q2.w;      // (B-A) x (C-A)
+        const float px = r.ox - q0.x, py = r.oy - q0.y, pz = r.oz - q0.z;   // o - A
         const float ddotn = fmaf(r.mz_, nz, fmaf(r.my_, ny, r.mx_ * nx));
         const float rcp = __builtin_amdgcn_rcpf(ddotn);
         t = fmaf(pz, nz, fmaf(py, ny, px * nx)) * rcp;
@@ -254,6 +284,20 @@ __device__ __forceinline__ bool tri_test(const float4 q0, const float4 q1, const
         gamma = fmaf(r.mz_, wz, fmaf(r.my_, wy, r.mx_ * wx)) * rcp;
     }
     // reject iff beta < -eps || gamma < -eps || beta+gamma > 1+eps || t < tMin || t > tMax  (:158)
+    const bool reject = (beta < -kEps) || (gamma < -kEps) || (beta + gamma > 1 + kEps) || (t < r.tmin) || (t > tmax);
+    return !reject;
+}
+
+// The exact test on an eye-relative record (REL traversals: every ray starts at the origin of the table, the eye):
+// q0 = (n, dot(eye - A, n)), q1 = (u, w.x), q2 = (w.y, w.z) from tri_origin_terms.  What is left per ray is what depends on
+// the direction -- dot(-d, n), the two numerator dots, the three divisions and the reject test -- on the same operands in
+// the same order as tri_test<true>: the same t, beta, gamma.
+__device__ __forceinline__ bool tri_test_rel(const float4 q0, const float4 q1, const float2 q2, const RayRegs &r,
+                                             float tmax, float &t, float &beta, float &gamma) {
+    const float ddotn = (r.mx_ * q0.x + r.my_ * q0.y) + r.mz_ * q0.z;
+    t = q0.w / ddotn;
+    beta = ((r.mx_ * q1.x + r.my_ * q1.y) + r.mz_ * q1.z) / ddotn;
+    gamma = ((r.mx_ * q1.w + r.my_ * q2.x) + r.mz_ * q2.y) / ddotn;
     const bool reject = (beta < -kEps) || (gamma < -kEps) || (beta + gamma > 1 + kEps) || (t < r.tmin) || (t > tmax);
     return !reject;
 }
@@ -274,10 +318,13 @@ __device__ __forceinline__ bool sphere_test(const float4 q0, const RayRegs &r, f
     return false;
 }
 
-// the object test of a leaf slot: Triangle::intersect, or Sphere::intersect when OBJ and the record carries the tag
-template <bool EXACT, bool OBJ>
+// the object test of a leaf slot: Triangle::intersect, or Sphere::intersect when OBJ and the record carries the tag;
+// REL: the eye-relative record of tri_test_rel (triangle-only scenes, exact test)
+template <bool EXACT, bool OBJ, bool REL = false>
 __device__ __forceinline__ bool object_test(const float4 q0, const float4 q1, const float4 q2, const RayRegs &r,
                                             float tmax, float &t, float &beta, float &gamma) {
+    static_assert(!REL || (EXACT && !OBJ), "eye-relative records hold exact triangle tests only");
+    if (REL) return tri_test_rel(q0, q1, make_float2(q2.x, q2.y), r, tmax, t, beta, gamma);
     if (OBJ && __float_as_uint(q2.w) == kSphereTag) {
         beta = 0.0f; gamma = 0.0f;
         return sphere_test(q0, r, tmax, t);
@@ -497,8 +544,32 @@ __device__ __forceinline__ void load_tri_scalar(const float4 *tris, unsigned pos
     q1 = make_float4(b[0], b[1], b[2], b[3]);
     q2 = make_float4(c[0], c[1], c[2], c[3]);
 }
+// the 40 bytes an eye-relative record uses (tri_test_rel), through the scalar cache
+typedef float v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void load_tri_rel_scalar(const float4 *tris, unsigned pos_uniform, float4 &q0, float4 &q1, float4 &q2) {
+    const float4 *ptr = tris + 3 * (size_t)pos_uniform;
+    v4f a, b;
+    v2f c;
+    asm volatile("s_load_dwordx4 %0, %3, 0x0\n\ts_load_dwordx4 %1, %3, 0x10\n\ts_load_dwordx2 %2, %3, 0x20\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(a), "=&s"(b), "=&s"(c) : "s"(ptr) : "memory");
+    q0 = make_float4(a[0], a[1], a[2], a[3]);
+    q1 = make_float4(b[0], b[1], b[2], b[3]);
+    q2 = make_float4(c[0], c[1], 0.0f, 0.0f);
+}
+template <bool REL>
+__device__ __forceinline__ void load_tri_uniform(const float4 *tris, unsigned pos_uniform, float4 &q0, float4 &q1, float4 &q2) {
+    if (REL) load_tri_rel_scalar(tris, pos_uniform, q0, q1, q2);
+    else load_tri_scalar(tris, pos_uniform, q0, q1, q2);
+}
+// one record per lane (REL: its first 40 bytes)
+template <bool REL>
+__device__ __forceinline__ void load_tri(const float4 *tr, float4 &q0, float4 &q1, float4 &q2) {
+    q0 = tr[0]; q1 = tr[1];
+    if (REL) { const float2 c = *reinterpret_cast<const float2 *>(tr + 2); q2 = make_float4(c.x, c.y, 0.0f, 0.0f); }
+    else q2 = tr[2];
+}
 
-template <bool EXACT, bool ANY, bool STATS, bool SCALAR = false, bool OBJ = false>
+template <bool EXACT, bool ANY, bool STATS, bool SCALAR = false, bool OBJ = false, bool REL = false>
 __device__ __forceinline__ void leaf_step(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, int tid, Stats &st) {
     // ---- leaf (BVH.cpp:493-509)
     const unsigned bits = ~(unsigned)L.cur;
@@ -515,10 +586,10 @@ __device__ __forceinline__ void leaf_step(const TraceParams &p, const RayRegs &r
             const unsigned cnt0 = (unsigned)__builtin_amdgcn_readfirstlane((int)cnt);
             for (unsigned k = 0; k < cnt0; k++) {
                 float4 q0, q1, q2;
-                load_tri_scalar(p.tris, first0 + k, q0, q1, q2);
+                load_tri_uniform<REL>(p.tris, first0 + k, q0, q1, q2);
                 if (!(ANY && done)) {
                     float t, b, g;
-                    const bool ok = object_test<EXACT, OBJ>(q0, q1, q2, r, L.best_t, t, b, g);
+                    const bool ok = object_test<EXACT, OBJ, REL>(q0, q1, q2, r, L.best_t, t, b, g);
                     if (ok && t < L.best_t) {
                         L.best_t = t; L.best_b = b; L.best_g = g; L.best_pos = (int)(first0 + k);
                         if (ANY) done = true;
@@ -529,9 +600,10 @@ __device__ __forceinline__ void leaf_step(const TraceParams &p, const RayRegs &r
     }
     if (!uniform) {
         for (unsigned k = 0; k < cnt; k++) {
-            const float4 *tr = p.tris + 3 * (size_t)(first + k);
+            float4 q0, q1, q2;
+            load_tri<REL>(p.tris + 3 * (size_t)(first + k), q0, q1, q2);
             float t, b, g;
-            const bool ok = object_test<EXACT, OBJ>(tr[0], tr[1], tr[2], r, L.best_t, t, b, g);
+            const bool ok = object_test<EXACT, OBJ, REL>(q0, q1, q2, r, L.best_t, t, b, g);
             if (ok && t < L.best_t) {             // strict-less replacement (:500)
                 L.best_t = t; L.best_b = b; L.best_g = g; L.best_pos = (int)(first + k);
                 if (ANY) { done = true; break; }
@@ -557,7 +629,7 @@ __device__ __forceinline__ void leaf_step(const TraceParams &p, const RayRegs &r
 // One triangle of the lane's current leaf (voting traversal): the leaf is decoded on its first step, popped after its
 // last.  Same tests in the same order with the same running best_t as leaf_step.  When every participating lane is at
 // the start of the same leaf, the whole leaf goes through the scalar cache in this one step (the coherent case).
-template <bool EXACT, bool ANY, bool STATS, bool SCALAR, bool OBJ>
+template <bool EXACT, bool ANY, bool STATS, bool SCALAR, bool OBJ, bool REL = false>
 __device__ __forceinline__ void tri_step(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, Stats &st) {
     bool done = false;
     if (SCALAR) {
@@ -569,10 +641,10 @@ __device__ __forceinline__ void tri_step(const TraceParams &p, const RayRegs &r,
             if (cnt0 == kLeafCountMask) cnt0 = p.leaf_cnt_ext[first0];
             for (unsigned k = 0; k < cnt0; k++) {
                 float4 q0, q1, q2;
-                load_tri_scalar(p.tris, first0 + k, q0, q1, q2);
+                load_tri_uniform<REL>(p.tris, first0 + k, q0, q1, q2);
                 if (!(ANY && done)) {
                     float t, b, g;
-                    const bool ok = object_test<EXACT, OBJ>(q0, q1, q2, r, L.best_t, t, b, g);
+                    const bool ok = object_test<EXACT, OBJ, REL>(q0, q1, q2, r, L.best_t, t, b, g);
                     if (ok && t < L.best_t) {
                         L.best_t = t; L.best_b = b; L.best_g = g; L.best_pos = (int)(first0 + k);
                         if (ANY) done = true;
@@ -600,9 +672,10 @@ __device__ __forceinline__ void tri_step(const TraceParams &p, const RayRegs &r,
         }
     }
     if (L.lpos < L.lend) {
-        const float4 *tr = p.tris + 3 * (size_t)L.lpos;
+        float4 q0, q1, q2;
+        load_tri<REL>(p.tris + 3 * (size_t)L.lpos, q0, q1, q2);
         float t, b, g;
-        const bool ok = object_test<EXACT, OBJ>(tr[0], tr[1], tr[2], r, L.best_t, t, b, g);
+        const bool ok = object_test<EXACT, OBJ, REL>(q0, q1, q2, r, L.best_t, t, b, g);
         if (ok && t < L.best_t) {                    // strict-less replacement (BVH.cpp:500)
             L.best_t = t; L.best_b = b; L.best_g = g; L.best_pos = L.lpos;
             if (ANY) done = true;
@@ -624,7 +697,7 @@ __device__ __forceinline__ void tri_step(const TraceParams &p, const RayRegs &r,
 //         long as its slowest lane's search for a leaf (incoherent batches: 14 of 64 lanes active per VALU
 //         instruction, profiles/r02_before_random); with the vote at least half of the unfinished lanes are active in every step.  The order of
 //         every lane's own steps -- and so its hit record -- is the same in all three modes.
-template <bool EXACT, bool ANY, bool STATS, int SLAB, int MODE, bool SCALAR, bool OBJ = false, int OCT = 8>
+template <bool EXACT, bool ANY, bool STATS, int SLAB, int MODE, bool SCALAR, bool OBJ = false, int OCT = 8, bool REL = false>
 __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, int tid, Stats &st) {
     if (MODE == 2) {
         L.lpos = 0; L.lend = 0;
@@ -635,18 +708,18 @@ __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r,
             if (__popcll(m_node) >= __popcll(m_tri)) {
                 if (want_node) node_step<EXACT, STATS, SLAB, SCALAR, OCT>(p, r, L, s_stack, tid, st);
             } else {
-                if (want_tri) tri_step<EXACT, ANY, STATS, SCALAR, OBJ>(p, r, L, s_stack, st);
+                if (want_tri) tri_step<EXACT, ANY, STATS, SCALAR, OBJ, REL>(p, r, L, s_stack, st);
             }
         }
     } else if (MODE == 1) {
         while (__any(L.have())) {
             while (L.cur >= 0) node_step<EXACT, STATS, SLAB, SCALAR, OCT>(p, r, L, s_stack, tid, st);
-            if (L.have()) leaf_step<EXACT, ANY, STATS, SCALAR, OBJ>(p, r, L, s_stack, tid, st);
+            if (L.have()) leaf_step<EXACT, ANY, STATS, SCALAR, OBJ, REL>(p, r, L, s_stack, tid, st);
         }
     } else {
         while (L.have()) {
             if (L.cur >= 0) node_step<EXACT, STATS, SLAB, SCALAR>(p, r, L, s_stack, tid, st);
-            else leaf_step<EXACT, ANY, STATS, false, OBJ>(p, r, L, s_stack, tid, st);
+            else leaf_step<EXACT, ANY, STATS, false, OBJ, REL>(p, r, L, s_stack, tid, st);
         }
     }
 }
@@ -660,10 +733,19 @@ __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r,
 //     through the scalar cache; bit 4: every slab distance is the reference's true quotient (the default trace;
 //     MR_COUNT_STATS implies it); bit 5: the scene holds spheres and / or planes; bit 8: octant-specialised slab tests
 //     for waves whose rays share an octant.
+// REL: p holds the eye-relative tables of the fused frame (mr_frame.hip: eye_tables) -- node corners and root box minus the
+//     eye, triangle records of tri_test_rel -- and every ray starts at the eye: the origin is taken as the constant 0, so the
+//     slab distances (corner - o) / d become (corner - eye) / d on the stored differences with no subtraction left, the
+//     same operands and the same bits as on the scene's own tables.  The eye's own regularity (lane_is_regular sees 0 here)
+//     travels in the node flags: an irregular eye marks every node irregular, so every visit divides (SLAB 3) as the
+//     scene's tables would have had it do.  Default traversal of triangle-only scenes only.
 // ---------------------------------------------------------------------------------------------------
-template <bool EXACT, bool ANY, bool STATS, int VAR>
-__device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r, float tmax0, bool live, Lane &L,
+template <bool EXACT, bool ANY, bool STATS, int VAR, bool REL = false>
+__device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r_in, float tmax0, bool live, Lane &L,
                                           int &plane_hit, int *s_stack, int tid, Stats &st) {
+    static_assert(!REL || ((VAR & 16) && !(VAR & 32) && !STATS), "eye-relative tables: default traversal, triangles only");
+    RayRegs r = r_in;
+    if (REL) { r.ox = 0.0f; r.oy = 0.0f; r.oz = 0.0f; }
     constexpr bool kStrict = STATS || (VAR & 16);
     constexpr int kBaseSlab = kStrict ? 3 : 0;
     constexpr bool kMinMax = !kStrict && (VAR & 1);
@@ -701,14 +783,14 @@ __device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r
             if (__all(!live || oct == oct0) && (kOctSlab != 6 || __all(!live || r.tmin == 0.0f))) {
                 done_oct = true;
                 switch (oct0) {
-                    case 0: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 0>(p, r, L, s_stack, tid, st); break;
-                    case 1: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 1>(p, r, L, s_stack, tid, st); break;
-                    case 2: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 2>(p, r, L, s_stack, tid, st); break;
-                    case 3: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 3>(p, r, L, s_stack, tid, st); break;
-                    case 4: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 4>(p, r, L, s_stack, tid, st); break;
-                    case 5: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 5>(p, r, L, s_stack, tid, st); break;
-                    case 6: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 6>(p, r, L, s_stack, tid, st); break;
-                    default: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 7>(p, r, L, s_stack, tid, st); break;
+                    case 0: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 0, REL>(p, r, L, s_stack, tid, st); break;
+                    case 1: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 1, REL>(p, r, L, s_stack, tid, st); break;
+                    case 2: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 2, REL>(p, r, L, s_stack, tid, st); break;
+                    case 3: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 3, REL>(p, r, L, s_stack, tid, st); break;
+                    case 4: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 4, REL>(p, r, L, s_stack, tid, st); break;
+                    case 5: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 5, REL>(p, r, L, s_stack, tid, st); break;
+                    case 6: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 6, REL>(p, r, L, s_stack, tid, st); break;
+                    default: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 7, REL>(p, r, L, s_stack, tid, st); break;
                 }
             }
         }
@@ -728,8 +810,8 @@ __device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r
         // VAR bit 10: ... and the voting control flow suits it better (random rays 3.86 -> 4.09 Grays/s, the atrium's bounce
         // rays 4.96 -> 5.31, 1-spp shadow rays in image order 3.73 -> 4.31 without the caller's MR_TRACE_INCOHERENT hint)
         constexpr int kMixedFlow = ((VAR & 1024) && kWW == 1) ? 2 : kWW;
-        if (good_wave) traverse<EXACT, ANY, STATS, 4, kMixedFlow, kScalar, kObj>(p, r, L, s_stack, tid, st);
-        else traverse<EXACT, ANY, STATS, 3, kWW, kScalar, kObj>(p, r, L, s_stack, tid, st);
+        if (good_wave) traverse<EXACT, ANY, STATS, 4, kMixedFlow, kScalar, kObj, 8, REL>(p, r, L, s_stack, tid, st);
+        else traverse<EXACT, ANY, STATS, 3, kWW, kScalar, kObj, 8, REL>(p, r, L, s_stack, tid, st);
     } else {
         traverse<EXACT, ANY, STATS, kBaseSlab, kWW, kStrict && kScalar, kObj>(p, r, L, s_stack, tid, st);
     }

@@ -286,7 +286,12 @@ typedef struct mr_frame_desc {
  * Streams: a frame of 60 000 chunks of 256 samples or more hands the last 6 % of its chunks out through one of 64 per-scene
  * device counters (taken round-robin per call, re-armed by the launch itself, so a captured HIP graph replays): calls on one
  * scene may overlap on different streams, up to 64 at a time; a captured graph keeps its counter -- do not replay it while
- * other frames of the same scene are in flight on other streams. */
+ * other frames of the same scene are in flight on other streams.
+ * Memory: the default traversal of a triangle-only scene traces primary rays on tables relative to the camera eye, built on
+ * `stream` by a launch in front of the frame when no earlier call left them for this eye; a scene keeps up to 64 such sets
+ * (the least recently used one is rebuilt), each allocated on first use: 64 bytes per inner node + 48 per triangle record
+ * (about the size of the scene's own node and triangle arrays), freed with the scene.  A captured graph rebuilds its set at
+ * every replay. */
 mr_status mr_render_direct(mr_scene *scene, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, mr_hit *d_shadow_hits,
                            uint64_t *d_counts, void *stream);
 
