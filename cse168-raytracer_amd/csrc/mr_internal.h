@@ -235,6 +235,34 @@ mr_status launch_irradiance(const PhotonMapDev &pm, unsigned *work_counter, cons
                             hipStream_t stream);
 constexpr int kPhotonStats = 12;  // see mr_photon_map_get_stats (miro_hip.h)
 
+// photon tracing (mr_photon_walk.hip): one round = emissions first ... first + count - 1 of one light, walked to their end
+struct PhotonWalkLight {
+    float position[3], direction[3], t1[3], t2[3];   // getTangents of the normal (Utility.h:25-31), computed on the host
+    float power[3], radius;                          // the emitted power (Scene.cpp:380-385 / :442-447)
+};
+struct PhotonRoundHeader {
+    uint32_t emitted;             // emissions of the round that count: up to and including the one that reaches the target
+    uint32_t reached;             // the running total reached the target inside this round
+    unsigned long long stored, segments;   // over those emissions
+};
+struct PhotonRoundBuffers {
+    float4 *slots = nullptr;      // capacity * max_depth records of three float4 (mr_photon_record), written by the walk
+    float4 *compact = nullptr;    // the same size: the round's records in emission order
+    uint32_t *words = nullptr;    // per emission: stores | segments << 8
+    uint32_t *offsets = nullptr;  // per emission: records of the round in front of its own
+    unsigned *next = nullptr;     // the round's emission counter
+    PhotonRoundHeader *header = nullptr;
+    uint32_t capacity = 0;        // emissions per round the buffers hold
+};
+constexpr uint32_t kPhotonEventDomain = 0x70686f74u, kPhotonDiscDomain = 0x64697363u;   // seed domains, see mr_trace_photons
+constexpr uint32_t kPhotonMaxDepth = 32;
+// need: stores still missing to the target (> 0)
+mr_status launch_photon_round(const DeviceScene &ds, const PhotonWalkLight &lt, uint32_t seed, uint32_t caustic, uint32_t max_depth,
+                              uint32_t first, uint32_t count, unsigned long long need, const PhotonRoundBuffers &b, hipStream_t stream);
+// what mr_trace_photons needs to know of a map (the struct lives in mr_photon.cpp)
+int32_t photon_map_device(const mr_photon_map *m);
+bool photon_map_balanced(const mr_photon_map *m);
+
 }  // namespace mr
 
 struct mr_scene {

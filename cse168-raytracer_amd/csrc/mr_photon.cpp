@@ -129,6 +129,11 @@ void release(mr_photon_map *m) {
 
 }  // namespace
 
+namespace mr {
+int32_t photon_map_device(const mr_photon_map *m) { return m->device; }
+bool photon_map_balanced(const mr_photon_map *m) { return m->balanced; }
+}  // namespace mr
+
 extern "C" {
 
 mr_status mr_photon_map_create(int32_t device, uint32_t max_photons, mr_photon_map **out) {

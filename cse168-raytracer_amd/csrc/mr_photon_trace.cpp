@@ -1,0 +1,167 @@
+// mr_photon_trace.cpp -- host side of mr_trace_photons: Scene::tracePhotons / traceCausticPhotons for one
+// DirectionalAreaLight (Scene.cpp:351-472).  The photons are walked on the device (mr_photon_walk.hip) in rounds of
+// emissions; after each round the host reads one small header, copies the round's compacted records and pushes them
+// through mr_photon_map_store, until the target is reached or max_emissions are spent; then scale_photon_power(1/emitted).
+//
+// The result does not depend on the round size: a round's header says how many of its emissions count (up to and including
+// the one whose stores reach the target), and only their records -- in emission order -- are taken.
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mr_internal.h"
+
+using namespace mr;
+
+namespace {
+
+constexpr float kPI = 3.1415926535897932384626433832795028841972f;   // Miro.h:10
+constexpr uint32_t kRoundMin = 16384;
+constexpr uint64_t kRoundRecords = 5ull << 20;                        // record slots per round (48 bytes each, twice)
+
+struct Timing { double kernel_ms = 0, readback_ms = 0, store_ms = 0; };
+thread_local Timing g_timing;
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+void cross3(const float a[3], const float b[3], float o[3]) {
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+struct Buffers : PhotonRoundBuffers {
+    ~Buffers() {
+        (void)hipFree(slots); (void)hipFree(compact); (void)hipFree(words); (void)hipFree(offsets); (void)hipFree(next); (void)hipFree(header);
+    }
+};
+
+mr_status allocate(Buffers &b, uint32_t capacity, uint32_t max_depth) {
+    const size_t rec = (size_t)capacity * max_depth * 3 * sizeof(float4);
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&b.slots), rec));
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&b.compact), rec));
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&b.words), (size_t)capacity * sizeof(uint32_t)));
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&b.offsets), (size_t)capacity * sizeof(uint32_t)));
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&b.next), sizeof(unsigned)));
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&b.header), sizeof(PhotonRoundHeader)));
+    b.capacity = capacity;
+    return MR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+mr_status mr_trace_photons(mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, mr_photon_trace_result *result,
+                           mr_photon_record *d_records, uint64_t records_capacity, void *stream_) {
+    if (!s || !map || !desc) return fail(MR_ERR_INVALID, "mr_trace_photons: NULL scene, map or desc");
+    if (desc->max_emissions == 0) return fail(MR_ERR_INVALID, "mr_trace_photons: max_emissions is 0 (the hard stop is required)");
+    const mr_disc_light &lt = desc->light;
+    if (!(lt.radius > 0.0f) || !std::isfinite(lt.radius)) return fail(MR_ERR_INVALID, "mr_trace_photons: the light's radius must be positive");
+    if (lt.normal[0] == 0.0f && lt.normal[1] == 0.0f && lt.normal[2] == 0.0f) return fail(MR_ERR_INVALID, "mr_trace_photons: the light's normal is zero");
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(lt.normal[c]) || !std::isfinite(lt.position[c])) return fail(MR_ERR_INVALID, "mr_trace_photons: the light's position and normal must be finite");
+    if (desc->max_depth > kPhotonMaxDepth) return fail(MR_ERR_INVALID, "mr_trace_photons: max_depth is at most %u", kPhotonMaxDepth);
+    for (int k = 0; k < 6; k++)
+        if (desc->reserved[k] != 0) return fail(MR_ERR_INVALID, "mr_photon_trace_desc.reserved must be 0");
+    if (reinterpret_cast<uintptr_t>(d_records) & 3) return fail(MR_ERR_INVALID, "mr_trace_photons: d_records must be 4-byte aligned");
+    if (s->device != photon_map_device(map)) return fail(MR_ERR_INVALID, "mr_trace_photons: scene on device %d, photon map on device %d", s->device, photon_map_device(map));
+    if (!s->built) return fail(MR_ERR_STATE, "mr_bvh_build has not been called on this scene");
+    if (!s->on_device) return fail(MR_ERR_STATE, "scene was built host_only: nothing is resident on a device and there is no CPU fallback");
+    if (photon_map_balanced(map)) return fail(MR_ERR_STATE, "photon map is immutable after mr_photon_map_balance");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    g_timing = Timing();
+
+    const uint32_t max_depth = desc->max_depth ? desc->max_depth : 5u;          // TRACE_DEPTH_PHOTONS (Miro.h:14)
+    PhotonWalkLight wl;
+    {
+        const float ez[3] = {0.f, 0.f, 1.f}, ey[3] = {0.f, 1.f, 0.f};
+        cross3(ez, lt.normal, wl.t1);                                            // getTangents (Utility.h:25-31)
+        if ((double)((wl.t1[0] * wl.t1[0] + wl.t1[1] * wl.t1[1]) + wl.t1[2] * wl.t1[2]) < 1e-6) cross3(ey, lt.normal, wl.t1);
+        cross3(wl.t1, lt.normal, wl.t2);
+        float k = kPI * lt.radius * lt.radius;                                   // Scene.cpp:384
+        if (desc->caustic) k = k / 10.f;                                         // :446
+        for (int c = 0; c < 3; c++) {
+            wl.position[c] = lt.position[c]; wl.direction[c] = lt.normal[c];
+            wl.power[c] = (lt.color[c] * lt.wattage) * k;
+        }
+        wl.radius = lt.radius;
+    }
+
+    mr_photon_trace_result res = {0, 0, 0, 0};
+    if (desc->target > 0) {
+        MR_HIP_CHECK(hipSetDevice(s->device));
+        uint64_t limit = kRoundRecords / max_depth;
+        if (limit > (1u << 20)) limit = 1u << 20;
+        // the first round: one emission per wanted photon (a photon stores less than once per emission in most rooms)
+        uint64_t round = desc->round_emissions ? desc->round_emissions : (desc->target > kRoundMin ? desc->target : kRoundMin);
+        if (round > limit) round = limit;
+        if (round > desc->max_emissions) round = desc->max_emissions;
+        Buffers b;
+        mr_status st = allocate(b, (uint32_t)round, max_depth);
+        if (st != MR_OK) return st;
+        std::vector<mr_photon_record> recs;
+        std::vector<float> power, pos, dir;
+        bool reached = false;
+        while (!reached && res.emitted < desc->max_emissions) {
+            uint64_t count = round;
+            if (!desc->round_emissions && res.rounds > 0) {
+                // later rounds from the measured yield, with an eighth to spare; none stored yet: the largest round
+                count = res.stored ? (uint64_t)((double)(desc->target - res.stored) * (double)res.emitted / (double)res.stored * 1.125) + 1024 : b.capacity;
+                if (count < kRoundMin) count = kRoundMin;
+            }
+            if (count > b.capacity) count = b.capacity;
+            if (count > desc->max_emissions - res.emitted) count = desc->max_emissions - res.emitted;
+            auto t0 = std::chrono::steady_clock::now();
+            st = launch_photon_round(s->dev, wl, desc->seed, desc->caustic ? 1u : 0u, max_depth, (uint32_t)res.emitted, (uint32_t)count,
+                                     desc->target - res.stored, b, stream);
+            if (st != MR_OK) return st;
+            PhotonRoundHeader hdr;
+            MR_HIP_CHECK(hipMemcpyAsync(&hdr, b.header, sizeof(hdr), hipMemcpyDeviceToHost, stream));
+            MR_HIP_CHECK(hipStreamSynchronize(stream));
+            g_timing.kernel_ms += ms_since(t0);
+            if (hdr.emitted > count || hdr.stored > (uint64_t)count * max_depth)
+                return fail(MR_ERR_HIP, "mr_trace_photons: inconsistent round header (%u emissions of %llu)", hdr.emitted, (unsigned long long)count);
+
+            t0 = std::chrono::steady_clock::now();
+            recs.resize(hdr.stored);
+            if (hdr.stored) MR_HIP_CHECK(hipMemcpyAsync(recs.data(), b.compact, hdr.stored * sizeof(mr_photon_record), hipMemcpyDeviceToHost, stream));
+            if (d_records && res.stored < records_capacity && hdr.stored) {
+                const uint64_t room = records_capacity - res.stored, n = hdr.stored < room ? hdr.stored : room;
+                MR_HIP_CHECK(hipMemcpyAsync(d_records + res.stored, b.compact, n * sizeof(mr_photon_record), hipMemcpyDeviceToDevice, stream));
+            }
+            MR_HIP_CHECK(hipStreamSynchronize(stream));
+            g_timing.readback_ms += ms_since(t0);
+
+            t0 = std::chrono::steady_clock::now();
+            power.resize(3 * recs.size()); pos.resize(3 * recs.size()); dir.resize(3 * recs.size());
+            for (size_t i = 0; i < recs.size(); i++)
+                for (int c = 0; c < 3; c++) { power[3 * i + c] = recs[i].power[c]; pos[3 * i + c] = recs[i].pos[c]; dir[3 * i + c] = recs[i].dir[c]; }
+            for (size_t at = 0; at < recs.size(); at += 1u << 30) {       // mr_photon_map_store counts in 32 bits
+                const size_t n = recs.size() - at < (1u << 30) ? recs.size() - at : (1u << 30);
+                st = mr_photon_map_store(map, (uint32_t)n, power.data() + 3 * at, pos.data() + 3 * at, dir.data() + 3 * at);
+                if (st != MR_OK) return st;
+            }
+            g_timing.store_ms += ms_since(t0);
+
+            res.emitted += hdr.emitted; res.stored += hdr.stored; res.segments += hdr.segments; res.rounds++;
+            reached = hdr.reached != 0;
+        }
+        if (res.emitted) {
+            mr_status st2 = mr_photon_map_scale(map, 1.0f / (float)res.emitted);      // Scene.cpp:402
+            if (st2 != MR_OK) return st2;
+        }
+    }
+    if (result) *result = res;
+    return MR_OK;
+}
+
+mr_status mr_trace_photons_timing(double *kernel_ms, double *readback_ms, double *store_ms) {
+    if (kernel_ms) *kernel_ms = g_timing.kernel_ms;
+    if (readback_ms) *readback_ms = g_timing.readback_ms;
+    if (store_ms) *store_ms = g_timing.store_ms;
+    return MR_OK;
+}
+
+}  // extern "C"

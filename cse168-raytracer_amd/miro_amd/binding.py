@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "mr_photon_map_balance", "mr_photon_map_count", "mr_photon_map_export", "mr_irradiance_estimate",
     "mr_photon_map_count_stats", "mr_photon_map_get_stats",
     "mr_final_gather",
+    "mr_trace_photons", "mr_trace_photons_timing",
     "mr_last_error", "mr_version",
 ]
 
@@ -101,6 +102,26 @@ class LevelDesc(C.Structure):
 class Material(C.Structure):
     _fields_ = [("diffuse", C.c_float * 3), ("specular", C.c_float * 3), ("transmission", C.c_float * 3),
                 ("shininess", C.c_float), ("refract_index", C.c_float)]
+
+
+class DiscLight(C.Structure):
+    """mr_disc_light (miro_hip.h): a DirectionalAreaLight"""
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3), ("color", C.c_float * 3),
+                ("wattage", C.c_float), ("radius", C.c_float)]
+
+
+class PhotonTraceDesc(C.Structure):
+    _fields_ = [("light", DiscLight), ("target", C.c_uint32), ("max_emissions", C.c_uint32), ("caustic", C.c_uint32),
+                ("seed", C.c_uint32), ("max_depth", C.c_uint32), ("round_emissions", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+class PhotonTraceResult(C.Structure):
+    _fields_ = [("emitted", C.c_uint64), ("stored", C.c_uint64), ("segments", C.c_uint64), ("rounds", C.c_uint64)]
+
+
+# mr_photon_record (miro_hip.h): the optional raw output of mr_trace_photons
+PHOTON_RECORD_DTYPE = np.dtype([("pos", "<f4", 3), ("dir", "<f4", 3), ("power", "<f4", 3),
+                                ("emission", "<u4"), ("depth", "<u4"), ("flags", "<u4")])
 
 
 def lib_path():
@@ -172,6 +193,8 @@ def load_library(path=None):
     L.mr_gen_path_rays.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
     L.mr_trace_level.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mr_final_gather.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.mr_trace_photons.argtypes = [vp, vp, C.POINTER(PhotonTraceDesc), C.POINTER(PhotonTraceResult), vp, C.c_uint64, vp]
+    L.mr_trace_photons_timing.argtypes = [C.POINTER(C.c_double)] * 3
     L.mr_photon_map_create.argtypes = [C.c_int32, C.c_uint32, C.POINTER(vp)]
     L.mr_photon_map_destroy.argtypes = [vp]
     L.mr_photon_map_store.argtypes = [vp, C.c_uint32, f32p, f32p, f32p]
@@ -501,6 +524,31 @@ class Scene:
                                       caustic_map.h if caustic_map is not None else None, d_rays.data_ptr(),
                                       d_hits.data_ptr(), n, max_dist, nphotons, spp, d_scratch.data_ptr(), d_rgb.data_ptr(),
                                       _stream_ptr(stream)))
+
+    def trace_photons(self, photon_map, light, target, max_emissions, caustic=False, seed=168, max_depth=0, round_emissions=0,
+                      d_records=None, records_capacity=None, stream=None):
+        """mr_trace_photons: Scene::tracePhotons (caustic: traceCausticPhotons) for one disc light into `photon_map`, which
+        the caller balances afterwards.  light: dict with position, normal, color, wattage, radius.  d_records: optional
+        device tensor of PHOTON_RECORD_DTYPE-sized (48-byte) records.  Returns a dict: emitted, stored, segments, rounds and
+        the wall time of the call's parts (kernel_ms, readback_ms, store_ms)."""
+        desc = PhotonTraceDesc()
+        desc.light.position[:] = light["position"]
+        desc.light.normal[:] = light["normal"]
+        desc.light.color[:] = light.get("color", (1.0, 1.0, 1.0))
+        desc.light.wattage = light["wattage"]
+        desc.light.radius = light["radius"]
+        desc.target, desc.max_emissions, desc.caustic, desc.seed = target, max_emissions, 1 if caustic else 0, seed
+        desc.max_depth, desc.round_emissions = max_depth, round_emissions
+        res = PhotonTraceResult()
+        if d_records is not None and records_capacity is None:
+            records_capacity = d_records.numel() * d_records.element_size() // PHOTON_RECORD_DTYPE.itemsize
+        _check(self.L.mr_trace_photons(self.h, photon_map.h, C.byref(desc), C.byref(res),
+                                       d_records.data_ptr() if d_records is not None else None, records_capacity or 0,
+                                       _stream_ptr(stream)))
+        t = [C.c_double(), C.c_double(), C.c_double()]
+        _check(self.L.mr_trace_photons_timing(*(C.byref(x) for x in t)))
+        return dict(emitted=res.emitted, stored=res.stored, segments=res.segments, rounds=res.rounds,
+                    kernel_ms=t[0].value, readback_ms=t[1].value, store_ms=t[2].value)
 
     def set_materials(self, materials, prim_material=None):
         """materials: list of (diffuse, specular, transmission, shininess, refract_index) as Phong's constructor takes

@@ -85,6 +85,48 @@ SCENES["a1sphere"] = dict(models=[], floor=None,
                           wattage=500.0)
 
 
+def _box_triangles(lo, hi):
+    """The twelve triangles of a closed box seen from INSIDE (vertex normals point into the box, so that a diffuse bounce
+    off a wall -- Ray::random samples around hit.N -- stays in the room)."""
+    (x0, y0, z0), (x1, y1, z1) = lo, hi
+    faces = [((x0, y0, z0), (x0, y0, z1), (x0, y1, z1), (x0, y1, z0), (1, 0, 0)),
+             ((x1, y0, z0), (x1, y1, z0), (x1, y1, z1), (x1, y0, z1), (-1, 0, 0)),
+             ((x0, y0, z0), (x1, y0, z0), (x1, y0, z1), (x0, y0, z1), (0, 1, 0)),
+             ((x0, y1, z0), (x0, y1, z1), (x1, y1, z1), (x1, y1, z0), (0, -1, 0)),
+             ((x0, y0, z0), (x0, y1, z0), (x1, y1, z0), (x1, y0, z0), (0, 0, 1)),
+             ((x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1), (0, 0, -1))]
+    out = []
+    for a, b, c, d, n in faces:
+        out.append(("tri", a + b + c, n * 3))
+        out.append(("tri", a + c + d, n * 3))
+    return out
+
+
+_INF = float("inf")
+# A closed room for photon tracing (mr_trace_photons): a DirectionalAreaLight under the ceiling facing down, coloured diffuse
+# walls (a box of twelve triangles), a glass sphere, a mirror sphere, and a slightly glossy floor PLANE inside the box.
+# materials: (kd, ks, kt, shininess, refraction index) as Phong's constructor takes them, already inside its energy clamps;
+# prim_material: per bounded object in `objects` order (planes carry their own id).
+SCENES["photon_room"] = dict(
+    models=[], floor=None,
+    objects=_box_triangles((-2.0, -0.5, -2.0), (2.0, 4.0, 2.0)) + [
+        ("sphere", (-0.8, 0.85, 0.25), 0.75), ("sphere", (1.0, 0.7, -0.5), 0.6),
+        ("plane", (0.0, 1.0, 0.0), (0.0, 0.0, 0.0), 1)],
+    materials=[((0.7, 0.6, 0.5), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), _INF, 1.0),
+               ((0.6, 0.6, 0.6), (0.1, 0.1, 0.1), (0.0, 0.0, 0.0), _INF, 1.0),
+               ((0.0, 0.0, 0.0), (0.05, 0.05, 0.05), (0.9, 0.9, 0.9), _INF, 1.5),
+               ((0.0, 0.0, 0.0), (0.9, 0.9, 0.9), (0.0, 0.0, 0.0), _INF, 1.0)],
+    prim_material=[0] * 12 + [2, 3],
+    disc_light=dict(position=(0.0, 3.9, 0.0), normal=(0.0, -1.0, 0.0), color=(1.0, 1.0, 1.0), wattage=100.0, radius=0.8),
+    eye=(0.0, 1.8, 1.9), lookat=(0.0, 0.8, -0.5), up=UP, fov=60.0, light=(0.0, 3.5, 0.0), wattage=100.0)
+# the same room with nothing in it: every surface is the diffuse wall material (no escape, no specular event)
+SCENES["photon_room_diffuse"] = dict(
+    models=[], floor=None, objects=_box_triangles((-2.0, -0.5, -2.0), (2.0, 4.0, 2.0)),
+    materials=[((0.7, 0.6, 0.5), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), _INF, 1.0)], prim_material=[0] * 12,
+    disc_light=dict(position=(0.0, 3.9, 0.0), normal=(0.0, -1.0, 0.0), color=(1.0, 1.0, 1.0), wattage=100.0, radius=0.8),
+    eye=(0.0, 1.8, 1.9), lookat=(0.0, 0.8, -0.5), up=UP, fov=60.0, light=(0.0, 3.5, 0.0), wattage=100.0)
+
+
 # ---------------------------------------------------------------------------------------------
 # makeBunny20Scene (assignment2.cpp:124-339): twenty transformed copies of bunny.obj.  The transforms are scene
 # constants, composed here with the reference's own fp32 arithmetic -- Matrix4x4::operator*= (Matrix4x4.h:463-493:
@@ -198,7 +240,7 @@ def populate(scene, desc, cache_dir=None):
         if obj[0] == "sphere":
             scene.add_sphere(obj[1], obj[2])
         elif obj[0] == "plane":
-            scene.add_plane(obj[1], obj[2])
+            scene.add_plane(obj[1], obj[2], *obj[3:4])      # optional fourth entry: the plane's material id
         else:
             scene.add_triangle(np.asarray(obj[1], np.float32), np.asarray(obj[2], np.float32))
         n += 1

@@ -422,6 +422,77 @@ mr_status mr_final_gather(mr_scene *scene, mr_photon_map *global_map, mr_photon_
                           const mr_hit *d_hits, uint64_t n, float max_dist, uint32_t nphotons, uint32_t spp,
                           float *d_scratch, float *d_rgb, void *stream);
 
+/* ---- photon tracing: Scene::tracePhotons / traceCausticPhotons (Scene.cpp:351-472) for ONE DirectionalAreaLight ----------
+ * Emits photons from the disc light and walks each with Scene::tracePhoton (Scene.cpp:529-655), as the serial (non-OpenMP)
+ * build does, on the device: one lane per photon, emission -> Scene::trace -> roulette -> store / next segment, in one kernel
+ * (csrc/mr_photon_walk.hip).  There is no CPU path.
+ *   Emission: power = color * wattage * PI * radius^2 (/ 10 when caustic), direction = normal (as given, not normalised),
+ *   origin = position + x * t1 + y * t2, (x, y) from sampleDisc (Utility.h:82-95), t1 / t2 from getTangents (Utility.h:25-31).
+ *   Walk: Ray(position + epsilon * direction, direction), Scene::trace(0, MIRO_TMAX); at a hit the cumulative probabilities
+ *   prob[0..2] from the averages of the material's kd, ks, kt (the table of mr_scene_set_materials; the white Lambert
+ *   without one), one draw rnd: rnd > prob[2] absorbs; rnd < prob[0] is the diffuse event -- the photon is stored from its
+ *   second hit on (power, hit.P, incoming direction), a caustic photon whose FIRST hit is diffuse dies, and the walk goes on
+ *   along Ray::random with power kd * power / prob[0]; rnd < prob[1] mirrors, rnd < prob[2] transmits (one more draw against
+ *   the Fresnel coefficient: reflect or refract); a global (non-caustic) photon whose first event is specular dies.
+ *   Directions: the mirror and refraction directions are those of the reference's default build (no -DPATH_TRACING), i.e. of
+ *   mr_gen_secondary_rays; the diffuse direction is that of mr_gen_path_rays(kinds = MR_PATH_DIFFUSE) with id = emission
+ *   index and bounce = depth.  The Fresnel coefficient, which here DECIDES a branch, is computed on the shared functions of
+ *   miro_math.h as mr_gen_path_rays computes it (not on libm's sinf / acosf as mr_gen_secondary_rays does), so that the
+ *   decision is the same bits on the device and in a host restatement.
+ *   depth counts the photon's hits from 1 (tracePhoton's depth after its increment); a photon walks at most max_depth + 1
+ *   segments and stores at most max_depth records (depths 2 ... max_depth + 1).
+ * Random numbers: the reference's rand() cannot be reproduced; every draw is the counter-based generator of the eye-ray
+ * jitter, H(x) = pcg32(x), u(h) = (h >> 8) / 2^24, keyed by integers (e = emission index, counted from 0 per call):
+ *   diffuse direction at depth d   hray = H(H(seed) ^ e) + 4 d;   hk = H(hray + 3);   u1 = u(H(hk)), u2 = u(H(hk ^ 0x68bc21eb))
+ *                                  (exactly mr_gen_path_rays' diffuse child for id = e, bounce = d)
+ *   roulette draw at depth d       hev = H(H(seed ^ 0x70686f74) ^ e) + 2 d;   rnd = u(H(H(hev)))
+ *   Fresnel draw at depth d        u(H(H(hev + 1)))
+ *   disc sample, attempt a         hd = H(H(seed ^ 0x64697363) ^ e);   hk = H(hd + a);   x = (2 u(H(hk)) - 1) radius,
+ *                                  y = (2 u(H(hk ^ 0x68bc21eb)) - 1) radius; accepted unless x^2 + y^2 > radius^2; after 64
+ *                                  rejected attempts (probability 1e-43) the disc's centre is taken
+ *   The three seed domains (seed, seed ^ 0x70686f74, seed ^ 0x64697363) keep the event and disc keys apart from the
+ *   direction keys of the same bounce.
+ * Termination: let s(i) be the number of photons emission i stores.  emitted = the smallest E <= max_emissions with
+ *   s(0) + ... + s(E-1) >= target, or max_emissions if there is none (0 when target == 0).  The map receives, through
+ *   mr_photon_map_store (photons beyond max_photons are dropped silently), exactly the records of emissions 0 ... E-1,
+ *   ordered by emission index and by depth within an emission -- the last emission's records all count, so stored may exceed
+ *   target.  The result does not depend on round_emissions or on how the device schedules the photons; only `rounds` does.
+ *   Then scale_photon_power(1 / emitted) (Scene.cpp:402).  The call does NOT balance: several lights can be traced into one
+ *   map before mr_photon_map_balance.  stored == 0 is MR_OK.
+ * d_records (may be NULL): the same records in the same order as a device array, at most records_capacity of them (the rest
+ *   are counted in result->stored, never written); powers as stored, before the scaling.
+ * The call synchronises `stream` (it copies the records into the map's host store) and returns when the map is filled.
+ * Errors: NULL scene / map / desc, max_emissions == 0, radius <= 0, zero or non-finite normal, max_depth > 32, scene and map
+ *   on different devices: MR_ERR_INVALID (before any device call); scene not built or host_only, map already balanced:
+ *   MR_ERR_STATE. */
+typedef struct mr_disc_light {                        /* DirectionalAreaLight.h:7-38 on SquareLight.h / PointLight.h */
+    float position[3], normal[3], color[3], wattage, radius;
+} mr_disc_light;
+typedef struct mr_photon_trace_desc {
+    mr_disc_light light;
+    uint32_t target;          /* PhotonsPerLightSource: emit until at least this many photons have been stored */
+    uint32_t max_emissions;   /* required > 0: hard stop (the reference loops forever when nothing is ever stored) */
+    uint32_t caustic;         /* 0: Scene::tracePhotons; 1: traceCausticPhotons (Scene.cpp:413-472), power / 10 */
+    uint32_t seed;
+    uint32_t max_depth;       /* 0 = TRACE_DEPTH_PHOTONS (Miro.h:14) = 5; at most 32 */
+    uint32_t round_emissions; /* emissions per device round, 0 = chosen by the library (from the yield of the first round);
+                                 any value gives the same map and the same emitted / stored / segments */
+    uint32_t reserved[6];     /* must be 0 */
+} mr_photon_trace_desc;
+typedef struct mr_photon_trace_result {
+    uint64_t emitted, stored, segments, rounds;   /* segments: Scene::trace calls of emissions 0 ... emitted-1 */
+} mr_photon_trace_result;
+typedef struct mr_photon_record {                     /* 48 bytes */
+    float pos[3], dir[3], power[3];
+    uint32_t emission, depth, flags;                  /* flags bit 0: the photon's first bounce was specular */
+} mr_photon_record;
+mr_status mr_trace_photons(mr_scene *scene, mr_photon_map *map, const mr_photon_trace_desc *desc,
+                           mr_photon_trace_result *result, mr_photon_record *d_records, uint64_t records_capacity,
+                           void *stream);
+/* Where the calling thread's last mr_trace_photons spent its wall time, in milliseconds (any pointer may be NULL): the
+ * device rounds (walk + bookkeeping kernels, including the wait for them), the copies of the records, the host store. */
+mr_status mr_trace_photons_timing(double *kernel_ms, double *readback_ms, double *store_ms);
+
 const char *mr_last_error(void);
 const char *mr_version(void);
 
