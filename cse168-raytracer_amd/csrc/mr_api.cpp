@@ -930,6 +930,57 @@ mr_status mr_trace_level(mr_scene *s, const mr_level_desc *level, const mr_ray *
                         reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
+mr_status mr_scene_set_lights(mr_scene *s, const mr_light_desc *lights, uint32_t n_lights) {
+    if (!s) return fail(MR_ERR_INVALID, "mr_scene_set_lights: NULL scene");
+    if (n_lights > MR_MAX_LIGHTS) return fail(MR_ERR_INVALID, "mr_scene_set_lights: %u lights, at most %u", n_lights, (unsigned)MR_MAX_LIGHTS);
+    if (n_lights > 0 && !lights) return fail(MR_ERR_INVALID, "mr_scene_set_lights: NULL list of %u lights", n_lights);
+    std::vector<ShadeLight> list(n_lights);
+    for (uint32_t i = 0; i < n_lights; i++) {
+        const mr_light_desc &in = lights[i];
+        if (in.kind != MR_LIGHT_POINT && in.kind != MR_LIGHT_DISC) return fail(MR_ERR_INVALID, "light %u: unknown kind %u", i, in.kind);
+        for (int k = 0; k < 4; k++)
+            if (in.reserved[k] != 0) return fail(MR_ERR_INVALID, "light %u: mr_light_desc.reserved must be 0", i);
+        for (int c = 0; c < 3; c++)
+            if (!std::isfinite(in.position[c]) || !std::isfinite(in.color[c])) return fail(MR_ERR_INVALID, "light %u: position and color must be finite", i);
+        if (!std::isfinite(in.wattage)) return fail(MR_ERR_INVALID, "light %u: wattage must be finite", i);
+        ShadeLight &o = list[i];
+        o = ShadeLight();
+        o.kind = in.kind;
+        for (int c = 0; c < 3; c++) { o.position[c] = in.position[c]; o.color[c] = in.color[c]; }
+        o.wattage = in.wattage;
+        if (in.kind == MR_LIGHT_DISC) {
+            if (!(in.radius > 0.0f) || !std::isfinite(in.radius)) return fail(MR_ERR_INVALID, "light %u: a disc light's radius must be positive", i);
+            for (int c = 0; c < 3; c++)
+                if (!std::isfinite(in.normal[c])) return fail(MR_ERR_INVALID, "light %u: a disc light's normal must be finite", i);
+            if (in.normal[0] == 0.0f && in.normal[1] == 0.0f && in.normal[2] == 0.0f) return fail(MR_ERR_INVALID, "light %u: a disc light's normal is zero", i);
+            for (int c = 0; c < 3; c++) o.normal[c] = in.normal[c];
+            o.radius = in.radius;
+        }
+    }
+    s->lights.swap(list);
+    return MR_OK;
+}
+
+mr_status mr_shade_lights(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels,
+                          uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb, uint64_t *d_counts, void *stream) {
+    mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (s->lights.empty()) return fail(MR_ERR_STATE, "mr_shade_lights: the scene has no lights (mr_scene_set_lights)");
+    if (!d_rays || !d_hits || (!d_rgb && !d_ray_rgb)) return fail(MR_ERR_INVALID, "NULL argument");
+    if (spp == 0) return fail(MR_ERR_INVALID, "spp is 0");
+    if (n / spp > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "too many pixels");
+    if (flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT | MR_TRACE_ANY))
+        return fail(MR_ERR_INVALID, "mr_shade_lights: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_TRACE_ANY only");
+    if ((flags & MR_TRACE_ANY) && s->dev.refractive)
+        return fail(MR_ERR_STATE, "mr_shade_lights: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)");
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3))
+        return fail(MR_ERR_INVALID, "ray / hit buffers must be 16-byte aligned, counters 8-byte aligned");
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    return launch_shade_lights(s->dev, s->lights.data(), (uint32_t)s->lights.size(), d_rays, d_hits, d_weights, d_pixels, n, spp,
+                               flags, d_rgb, d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+}
+
 mr_status mr_tonemap(mr_scene *s, const float *d_rgb, uint64_t n_values, uint8_t *d_out, void *stream) {
     if (!s || !d_rgb || !d_out) return fail(MR_ERR_INVALID, "NULL argument");
     MR_HIP_CHECK(hipSetDevice(s->device));

@@ -213,6 +213,17 @@ mr_status launch_level(const DeviceScene &ds, const mr_level_desc &ld, const mr_
                        float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_out_count,
                        unsigned long long *d_counts, hipStream_t stream);
 
+// Phong::shade over the scene's light list (mr_lights.hip): a light of mr_scene_set_lights as the kernel takes it (the
+// list travels in the kernel arguments).  normal / radius: MR_LIGHT_DISC only.
+struct ShadeLight {
+    uint32_t kind;
+    float position[3], normal[3], color[3], wattage, radius;
+};
+mr_status launch_shade_lights(const DeviceScene &ds, const ShadeLight *lights, uint32_t n_lights, const mr_ray *d_rays,
+                              const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels, unsigned long long n,
+                              uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts,
+                              hipStream_t stream);
+
 // photon map on the device: three float4 planes in kd-tree heap order, 1-based (children of i: 2i, 2i+1)
 struct PhotonMapDev {
     float4 *rec = nullptr;        // two per photon, one 32-byte record: (x, y, z, split axis as int bits), then the incoming
@@ -296,4 +307,6 @@ struct mr_scene {
     // materials (host copy; uploaded by mr_scene_set_materials / mr_bvh_build)
     std::vector<float> materials;          // 11 per material, clamped as the Phong constructor does
     std::vector<uint32_t> prim_material;   // empty: material 0 everywhere
+    // Scene::lights() for mr_shade_lights (host only: the list travels in the kernel arguments), at most MR_MAX_LIGHTS
+    std::vector<mr::ShadeLight> lights;
 };

@@ -30,6 +30,9 @@ MR_PATH_MIRROR, MR_PATH_REFRACT, MR_PATH_DIFFUSE = 1, 2, 4
 MR_LEVEL_LAST, MR_LEVEL_SPECULAR, MR_LEVEL_PATH = 0, 1, 2
 MR_LAYOUT_DFS, MR_LAYOUT_PAIRS, MR_LAYOUT_TREELETS, MR_LAYOUT_ALIGN_LEAVES = 0, 1, 2, 16
 
+MR_LIGHT_POINT, MR_LIGHT_DISC = 0, 1
+MR_MAX_LIGHTS = 8
+
 MR_OK, MR_ERR_INVALID, MR_ERR_IO, MR_ERR_NOMEM, MR_ERR_HIP, MR_ERR_STATE = 0, -1, -2, -3, -4, -5
 
 # every symbol include/miro_hip.h declares (tests check the library exports each one)
@@ -45,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "mr_photon_map_count_stats", "mr_photon_map_get_stats",
     "mr_final_gather",
     "mr_trace_photons", "mr_trace_photons_timing",
+    "mr_scene_set_lights", "mr_shade_lights",
     "mr_last_error", "mr_version",
 ]
 
@@ -108,6 +112,29 @@ class DiscLight(C.Structure):
     """mr_disc_light (miro_hip.h): a DirectionalAreaLight"""
     _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3), ("color", C.c_float * 3),
                 ("wattage", C.c_float), ("radius", C.c_float)]
+
+
+class LightDesc(C.Structure):
+    """mr_light_desc (miro_hip.h): one light of the scene's list, a PointLight or a DirectionalAreaLight"""
+    _fields_ = [("kind", C.c_uint32), ("position", C.c_float * 3), ("normal", C.c_float * 3), ("color", C.c_float * 3),
+                ("wattage", C.c_float), ("radius", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+def light_desc(light):
+    """A LightDesc from a LightDesc, or from a dict as miro_amd.scenes writes them: dict(position, normal, color, wattage,
+    radius) is a disc light (a `disc_light` entry), dict(position, color, wattage) a point light; color defaults to white."""
+    if isinstance(light, LightDesc):
+        return light
+    ld = LightDesc()
+    disc = "normal" in light or "radius" in light
+    ld.kind = MR_LIGHT_DISC if disc else MR_LIGHT_POINT
+    ld.position[:] = light["position"]
+    ld.color[:] = light.get("color", (1.0, 1.0, 1.0))
+    ld.wattage = light["wattage"]
+    if disc:
+        ld.normal[:] = light["normal"]
+        ld.radius = light["radius"]
+    return ld
 
 
 class PhotonTraceDesc(C.Structure):
@@ -195,6 +222,8 @@ def load_library(path=None):
     L.mr_final_gather.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.mr_trace_photons.argtypes = [vp, vp, C.POINTER(PhotonTraceDesc), C.POINTER(PhotonTraceResult), vp, C.c_uint64, vp]
     L.mr_trace_photons_timing.argtypes = [C.POINTER(C.c_double)] * 3
+    L.mr_scene_set_lights.argtypes = [vp, C.POINTER(LightDesc), C.c_uint32]
+    L.mr_shade_lights.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.mr_photon_map_create.argtypes = [C.c_int32, C.c_uint32, C.POINTER(vp)]
     L.mr_photon_map_destroy.argtypes = [vp]
     L.mr_photon_map_store.argtypes = [vp, C.c_uint32, f32p, f32p, f32p]
@@ -587,6 +616,23 @@ class Scene:
                                             d_out_rays.data_ptr(), d_out_weights.data_ptr(), d_out_pixels.data_ptr(),
                                             d_count.data_ptr(), out_capacity,
                                             d_out_octants.data_ptr() if d_out_octants is not None else None, _stream_ptr(stream)))
+
+    def set_lights(self, lights):
+        """mr_scene_set_lights: Scene::addLight for the whole list (replaces an earlier one; an empty list clears it).
+        lights: LightDesc objects or dicts (see light_desc)."""
+        arr = (LightDesc * max(len(lights), 1))()
+        for i, lt in enumerate(lights):
+            arr[i] = light_desc(lt)
+        _check(self.L.mr_scene_set_lights(self.h, arr, len(lights)))
+
+    def shade_lights(self, d_rays, d_hits, n, d_rgb=None, d_weights=None, d_pixels=None, spp=1, flags=0, d_ray_rgb=None,
+                     d_counts=None, stream=None):
+        """mr_shade_lights: Phong::shade over the scene's light list for n traced rays in one launch; weight * L / spp is added
+        to d_rgb[pixel], the un-weighted L of every ray written to d_ray_rgb (either may be None, not both)."""
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        _check(self.L.mr_shade_lights(self.h, d_rays.data_ptr(), d_hits.data_ptr(), ptr(d_weights), ptr(d_pixels), n, spp, flags,
+                                      ptr(d_rgb), ptr(d_ray_rgb), ptr(d_counts), _stream_ptr(stream)))
 
     def tonemap(self, d_rgb, n_values, d_out, stream=None):
         _check(self.L.mr_tonemap(self.h, d_rgb.data_ptr(), n_values, d_out.data_ptr(), _stream_ptr(stream)))

@@ -291,7 +291,7 @@ class FrameRenderer:
         return g
 
     def render_specular(self, depth=10, stream=None, path_tracing=False, path_seed=168, path_kinds=None, fused=False,
-                        group_octants=False):
+                        group_octants=False, lights=None):
         """Scene::traceScene with reflective / refractive materials (Scene.cpp:270-346) as wavefront bounces: every
         level traces its queue, shades it (weight x Phong::shade added to the ray's pixel), and emits the reflect /
         Fresnel / refract children of the next level by ballot compaction.  depth = TRACE_DEPTH (Miro.h:13): rays are
@@ -306,15 +306,23 @@ class FrameRenderer:
         group_octants: the generators also write one octant byte per child, and every level after the first works on its
         queue through mr_order_by_octant's index (rays grouped by direction octant inside chunks of 16 384; the same hits and
         children).  Off by default: the bounce rays' own traversal gains 9-13 %, the frame does not (the shadow rays of grouped
-        lanes are no more coherent, the pixel runs of accumulate_runs break up, profiles/r03_octant_order.log)."""
+        lanes are no more coherent, the pixel runs of accumulate_runs break up, profiles/r03_octant_order.log).
+        lights: a light list (binding.LightDesc objects or the dicts of scenes.py, point and disc lights) instead of the
+        description's single point light: it becomes the scene's list (Scene.set_lights) and every level is trace ->
+        mr_shade_lights -> the generators, three launches without shadow-ray buffers.  The first level's hits stay in d_hits
+        (final_gather works on them).  `fused` must be falsy: mr_trace_level keeps its single point light."""
         sc, L, W = self.scene, self.desc["light"], self.desc["wattage"]
+        if lights is not None:
+            if fused:
+                raise ValueError("render_specular: a light list needs fused=False (mr_trace_level shades by one point light)")
+            sc.set_lights(lights)
         # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
         # each other on torch's current stream, so `stream` must be that stream (or a torch Stream, made current here)
         if stream is not None and not isinstance(stream, torch.cuda.Stream):
             raise TypeError("render_specular: pass a torch.cuda.Stream (or None for the current stream), not a raw handle")
         if stream is not None and stream != torch.cuda.current_stream(self.device):
             with torch.cuda.stream(stream):
-                return self.render_specular(depth, stream, path_tracing, path_seed, path_kinds, fused, group_octants)
+                return self.render_specular(depth, stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights)
         self.d_slots.zero_()
         if path_kinds is None:
             path_kinds = binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT
@@ -359,10 +367,11 @@ class FrameRenderer:
                 if path_tracing:
                     ids = out_ids[:n]
                 continue
-            hits = torch.empty((n, 4), **f32)
-            sh_rays = torch.empty((n, 8), **f32)
-            sh_hits = torch.empty((n, 4), **f32)
-            src = torch.empty(n, dtype=torch.int32, device=self.device)
+            hits = torch.empty((n, 4), **f32) if lights is None or level > 0 else self.d_hits
+            if lights is None:
+                sh_rays = torch.empty((n, 8), **f32)
+                sh_hits = torch.empty((n, 4), **f32)
+                src = torch.empty(n, dtype=torch.int32, device=self.device)
             cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
             # bounce queues are compacted in wave order, not in image order: from the first bounce on the batches carry the
             # MR_TRACE_INCOHERENT hint (voting control flow; the same hit records)
@@ -372,10 +381,14 @@ class FrameRenderer:
                 sc.trace_grouped(rays, n, hits, order, self.flags & binding.MR_MATH_PRODUCT, d_octants=octs, stream=stream)
             else:
                 sc.trace_device(rays, n, hits, fl, stream=stream)
-            sc.gen_shadow_rays(rays, hits, n, L, sh_rays, src, cnt, stream=stream)
-            sc.trace_indirect(sh_rays, cnt, n, sh_hits, fl, stream=stream)               # closest hit: the occluder matters
-            sc.shade_accumulate(rays, hits, weights, pixels, n, sh_rays, sh_hits, src, cnt, L, W, self.d_slots,
-                                spp=self.spp, stream=stream)
+            if lights is not None:
+                sc.shade_lights(rays, hits, n, self.d_slots, d_weights=weights, d_pixels=pixels, spp=self.spp,
+                                flags=fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT), d_counts=cnt, stream=stream)
+            else:
+                sc.gen_shadow_rays(rays, hits, n, L, sh_rays, src, cnt, stream=stream)
+                sc.trace_indirect(sh_rays, cnt, n, sh_hits, fl, stream=stream)           # closest hit: the occluder matters
+                sc.shade_accumulate(rays, hits, weights, pixels, n, sh_rays, sh_hits, src, cnt, L, W, self.d_slots,
+                                    spp=self.spp, stream=stream)
             n_shadow = int(cnt.item())
             per_level.append((n, n_shadow))
             if level == depth:

@@ -204,6 +204,16 @@ SCENES["bunny20"] = dict(models=_bunny20_models(), floor=((-100, 0, -100), (0, 0
                          wattage=1000.0)
 
 
+# the light lists of mr_shade_lights (Scene::addLight): the rooms are lit by the disc light their photons come from; the
+# two-light room adds the point light the single-light entry points use (`light` / `wattage`)
+for _name in ("photon_room", "photon_room_diffuse"):
+    SCENES[_name]["lights"] = [dict(SCENES[_name]["disc_light"])]
+SCENES["photon_room_two_lights"] = dict(
+    SCENES["photon_room"],
+    lights=[dict(SCENES["photon_room"]["disc_light"]),
+            dict(position=SCENES["photon_room"]["light"], color=(1.0, 1.0, 1.0), wattage=SCENES["photon_room"]["wattage"])])
+
+
 def sponza_label():
     p = os.environ.get("MIRO_SPONZA_OBJ", "")
     return "sponza" if p and os.path.exists(p) else "sponza-standin"

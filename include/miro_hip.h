@@ -381,6 +381,56 @@ mr_status mr_trace_level(mr_scene *scene, const mr_level_desc *level, const mr_r
                          float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, uint64_t *d_out_count,
                          uint64_t *d_counts, void *stream);
 
+/* ---- Phong::shade over the scene's LIGHT LIST (Phong.cpp:59-63), point and disc lights, in ONE launch ---------------------
+ * mr_scene_set_lights is Scene::addLight (Scene.h:29-30, assignment3.cpp:77-84,141-152) for the whole list: it replaces an
+ * earlier list, n_lights == 0 clears it; before or after mr_bvh_build (the list lives on the host and travels in the kernel
+ * arguments).  Only mr_shade_lights reads it: every other shading entry keeps its single mr_light argument.
+ *   MR_LIGHT_POINT  PointLight (PointLight.h:8-59): position, color, wattage; normal and radius are ignored.
+ *   MR_LIGHT_DISC   DirectionalAreaLight (DirectionalAreaLight.h:7-38 on SquareLight.h): the light mr_trace_photons emits from.
+ * mr_shade_lights is Phong::shade (Phong.cpp:44-160) for n traced rays: per ray with a hit (a miss contributes nothing), L = 0;
+ * for every light IN LIST ORDER the shadow ray is built (Phong.cpp:80-92) and traced (Scene::trace, closest hit: the occluder's
+ * material matters), the occluder's light scale applied (Phong.cpp:97-113: opaque -> the light is skipped, refractive ->
+ * dot(N, l), skipped if negative or < epsilon), and the light's diffuse term times the scale plus its highlight
+ * (Phong.cpp:116-156) added to L; then weight * L / spp is added to d_rgb[pixel] exactly as mr_shade_accumulate does it
+ * (d_weights NULL = 1, d_pixels NULL = ray index / spp, float atomics).  Materials: the table of mr_scene_set_materials, or the
+ * white Lambert without one.  With ONE point light the result is, bit for bit where every pixel receives one addition, that of
+ *   mr_gen_shadow_rays -> mr_trace_indirect -> mr_shade_accumulate
+ * with that light, without the shadow-ray, shadow-hit, source-index and light-scale buffers (csrc/mr_lights.hip: the lane
+ * keeps its hit point and builds and traces every shadow ray itself).
+ * The disc light, as the reference treats it -- quirks reproduced, not repaired:
+ *   - DirectionalAreaLight::getLightDirection ignores the origin Phong::shade samples (Phong.cpp:80-81): shading by a disc
+ *     light uses NO random number.
+ *   - l = -normal (as given); falloff = |l|^2; l /= sqrt(falloff).  Shadow ray: origin P + l * epsilon, direction l, tMin = 0,
+ *     tMax = sqrt(falloff) = |normal| (Phong.cpp:85-97): with a unit normal an occluder is looked for only ONE UNIT towards
+ *     the light, whatever the distance to the disc.
+ *   - after the shadow test (the shadow ray is traced and counted either way): nDotL = dot(N, -normal) with the normal as
+ *     given (not normalised), t = dot(normal, position - P) / -1.0f, and the light is skipped when
+ *     |(P - t * normal) - position|^2 > radius^2 (the hit lies outside the disc's cylinder, Phong.cpp:128-133); falloff = 1 / PI
+ *     instead of the point light's 1 / (4 PI^2 r^2) (Phong.cpp:135,140).
+ *   - diffuse term and highlight are the point light's expressions with that nDotL / falloff and the normalised l
+ *     (Phong.cpp:146-156).
+ * d_ray_rgb (may be NULL): 3n floats, the un-weighted L of every ray (0 for a miss).  The sum over the lights happens in one
+ *   lane in list order, so this output is deterministic; d_rgb carries the float-atomic order caveat of mr_shade_accumulate.
+ *   d_rgb may be NULL when d_ray_rgb is given.
+ * d_counts (may be NULL): [0] += shadow rays traced (= rays with a hit x lights); not zeroed by the call.
+ * flags: MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, and MR_TRACE_ANY for the shadow rays (refused with MR_ERR_STATE when the
+ *   material table holds a refractive material, Phong.cpp:99-113).
+ * With device buffers only, the call only enqueues one kernel on `stream` (it can be captured into a HIP graph).
+ * Errors: NULL scene, n_lights > MR_MAX_LIGHTS, NULL list with n_lights > 0, unknown kind, non-zero reserved, a non-finite
+ *   field, a disc with radius <= 0 or a zero normal: MR_ERR_INVALID (before any device call); mr_shade_lights on a scene
+ *   that is not built, was built host_only or has no lights: MR_ERR_STATE. */
+enum { MR_LIGHT_POINT = 0, MR_LIGHT_DISC = 1 };
+#define MR_MAX_LIGHTS 8
+typedef struct mr_light_desc {                        /* PointLight.h:8-59 / DirectionalAreaLight.h:7-38 */
+    uint32_t kind;
+    float position[3], normal[3], color[3], wattage, radius;   /* normal, radius: MR_LIGHT_DISC only */
+    uint32_t reserved[4];                             /* must be 0 */
+} mr_light_desc;
+mr_status mr_scene_set_lights(mr_scene *scene, const mr_light_desc *lights, uint32_t n_lights);
+mr_status mr_shade_lights(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
+                          const uint32_t *d_pixels, uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb,
+                          uint64_t *d_counts, void *stream);
+
 /* sigmoid(6v-3) tone map + 8-bit quantisation (Scene.cpp:87-91,177-202; Image.cpp:44-50) */
 mr_status mr_tonemap(mr_scene *scene, const float *d_rgb, uint64_t n_values, uint8_t *d_out, void *stream);
 
