@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "mr_internal.h"
+#include "mr_launch.h"
 #include "mr_tile.h"
 
 namespace mr {
@@ -550,16 +551,9 @@ mr_status mr_trace(mr_scene *s, const mr_ray *rays, uint64_t n, mr_hit *hits, ui
         }
         if (!hits_dev) d_hits = static_cast<mr_hit *>(s->d_stage_hits);
     }
-    TraceParams p;
-    p.nodes = s->dev.nodes; p.tris = s->dev.tris; p.tri_prim = s->dev.tri_prim; p.leaf_cnt_ext = s->dev.leaf_cnt_ext;
-    memcpy(p.root_lo, s->dev.root_lo, sizeof(p.root_lo));
-    memcpy(p.root_hi, s->dev.root_hi, sizeof(p.root_hi));
-    p.root_ref = s->dev.root_ref;
-    p.stack_depth = (int32_t)s->dev.stack_depth;
-    p.rays = d_rays; p.hits = d_hits; p.n = n; p.n_dev = nullptr; p.stats = s->d_stats;
-    p.planes = s->dev.planes; p.n_planes = s->dev.n_planes; p.n_spheres = s->dev.n_spheres;
+    TraceParams p = scene_trace_params(s->dev);
+    p.rays = d_rays; p.hits = d_hits; p.n = n; p.stats = s->d_stats;
     p.work_counter = s->d_work_counters + (s->next_counter.fetch_add(1) % kWorkCounters);
-    p.order = nullptr;
     if (staged.owns_lock() && n > kStageChunk) {
         // host buffers, large batch: chunk k+1 uploads and chunk k-1 downloads while chunk k is traced (full overlap when
         // the caller's buffers are pinned -- mr_host_alloc --, since only then are the copies asynchronous to this thread)
@@ -626,18 +620,10 @@ mr_status mr_trace_indirect(mr_scene *s, const mr_ray *d_rays, const uint64_t *d
         (reinterpret_cast<uintptr_t>(d_count) & 7))
         return fail(MR_ERR_INVALID, "device ray/hit buffers must be 16-byte aligned, the count 8-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
-    TraceParams p;
-    p.nodes = s->dev.nodes; p.tris = s->dev.tris; p.tri_prim = s->dev.tri_prim; p.leaf_cnt_ext = s->dev.leaf_cnt_ext;
-    memcpy(p.root_lo, s->dev.root_lo, sizeof(p.root_lo));
-    memcpy(p.root_hi, s->dev.root_hi, sizeof(p.root_hi));
-    p.root_ref = s->dev.root_ref;
-    p.stack_depth = (int32_t)s->dev.stack_depth;
-    p.rays = d_rays; p.hits = d_hits; p.n = max_rays;
+    TraceParams p = scene_trace_params(s->dev);
+    p.rays = d_rays; p.hits = d_hits; p.n = max_rays; p.stats = s->d_stats;
     p.n_dev = reinterpret_cast<const unsigned long long *>(d_count);
-    p.stats = s->d_stats;
-    p.planes = s->dev.planes; p.n_planes = s->dev.n_planes; p.n_spheres = s->dev.n_spheres;
     p.work_counter = s->d_work_counters + (s->next_counter.fetch_add(1) % kWorkCounters);
-    p.order = nullptr;
     return launch_trace(p, flags, static_cast<hipStream_t>(stream_v));
 }
 
@@ -670,16 +656,8 @@ mr_status mr_trace_grouped(mr_scene *s, const mr_ray *d_rays, const uint8_t *d_o
         st = launch_octant_order(d_rays, d_octants, n, chunk_log2, d_order, stream);
         if (st != MR_OK) return st;
     }
-    TraceParams p;
-    p.nodes = s->dev.nodes; p.tris = s->dev.tris; p.tri_prim = s->dev.tri_prim; p.leaf_cnt_ext = s->dev.leaf_cnt_ext;
-    memcpy(p.root_lo, s->dev.root_lo, sizeof(p.root_lo));
-    memcpy(p.root_hi, s->dev.root_hi, sizeof(p.root_hi));
-    p.root_ref = s->dev.root_ref;
-    p.stack_depth = (int32_t)s->dev.stack_depth;
-    p.rays = d_rays; p.hits = d_hits; p.n = n; p.n_dev = nullptr;
-    p.stats = s->d_stats;
-    p.planes = s->dev.planes; p.n_planes = s->dev.n_planes; p.n_spheres = s->dev.n_spheres;
-    p.work_counter = nullptr;
+    TraceParams p = scene_trace_params(s->dev);
+    p.rays = d_rays; p.hits = d_hits; p.n = n; p.stats = s->d_stats;
     p.order = d_order;
     return launch_trace(p, flags & ~(uint32_t)(MR_RAYS_ON_DEVICE | MR_HITS_ON_DEVICE | MR_TRACE_PERSISTENT), stream);
 }

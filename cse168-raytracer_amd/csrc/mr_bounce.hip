@@ -12,14 +12,13 @@
 #include <hip/hip_runtime.h>
 
 #include "mr_internal.h"
+#include "mr_launch.h"
 #include "mr_recursion.h"
 
 namespace mr {
 namespace {
 
 using namespace rec;
-
-constexpr int kBlock = 256;
 
 __global__ __launch_bounds__(kBlock) void light_scale_kernel(MeshMat m, const mr_ray *shadow_rays, const mr_hit *shadow_hits,
                                                              const uint32_t *src, const unsigned long long *count,
@@ -228,13 +227,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATH ? M
         }
         __syncthreads();                                                             // s_list / s_cnt are reused by the next chunk
     }
-}
-
-inline unsigned grid_for(unsigned long long n) {
-    unsigned long long blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 256ull * 32ull) blocks = 256ull * 32ull;
-    if (blocks == 0) blocks = 1;
-    return (unsigned)blocks;
 }
 
 }  // namespace

@@ -19,6 +19,7 @@
 
 #include "mr_eye.h"
 #include "mr_internal.h"
+#include "mr_launch.h"
 #include "mr_phong.h"
 #include "mr_recursion.h"
 #include "mr_surface.h"
@@ -162,7 +163,7 @@ inline FrameShape frame_schedule(unsigned long long chunks) {
 // end time (100 MHz constant clock), the CU it ran on and its XCD -- where the launch's idle VALU cycles sit
 __device__ unsigned long long g_wg_times[4 * 131072];
 #endif
-// kEyeRel (VAR 794, the default traversal of triangle-only scenes, every SHADOW / MAT form): the primary ray is traced on the
+// kEyeRel (VAR kTraceEyeRel, the default traversal of triangle-only scenes, every SHADOW / MAT form): the primary ray is traced on the
 // eye-relative tables from a zero origin (trace_ray's REL), the shadow ray on the scene's own.  Every primary ray starts at
 // the eye, so the origin's share of each slab and triangle test is the same for all of them: computed once per eye by a build
 // launch (eye_tables, eye_tables_for) instead of once per visit in every lane -- 12 VALU of a two-child visit, 26 of a triangle test.
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
 #if defined(MIRO_WG_TIMES) && MIRO_TRACE_BLOCK == 256
     const unsigned long long wg_t0 = wall_clock64();
 #endif
-    constexpr bool kEyeRel = VAR == 794;
+    constexpr bool kEyeRel = VAR == kTraceEyeRel;
     if (kEyeRel && a.build) {
         eye_tables(a);
         return;
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
     __shared__ unsigned s_shadow_rays[kTraceBlock / 64];
     const int tid = threadIdx.x;
     const unsigned long long n = a.eye.n, n_round = (n + 63ull) & ~63ull;
-    constexpr bool kObj = (VAR & 32) != 0;
+    constexpr bool kObj = (VAR & kVarObjects) != 0;
     const uint32_t spp = a.eye.spp;
     const float inv_spp = 1.0f / (float)spp;
     Stats st = {0ull, 0ull};
@@ -376,11 +377,9 @@ namespace {
 
 template <int VAR, int SHADOW, bool MAT>
 mr_status launch_frame_t(FrameArgs a, hipStream_t stream) {
-    const size_t lds = (size_t)a.tp.stack_depth * kTraceBlock * sizeof(int);
-    if (lds > 150 * 1024) return fail(MR_ERR_INVALID, "traversal stack of depth %d does not fit in LDS", a.tp.stack_depth);
-    if (lds > 48 * 1024)
-        MR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&frame_kernel<VAR, SHADOW, MAT>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    size_t lds = 0;
+    const mr_status st = stack_lds(&frame_kernel<VAR, SHADOW, MAT>, a.tp.stack_depth, kStackLdsShared, lds);
+    if (st != MR_OK) return st;
     const FrameShape shape = frame_schedule((a.eye.n + kTraceBlock - 1) / kTraceBlock);
     a.body_wgs = shape.body_wgs; a.body_iters = shape.body_iters; a.tail_chunks = shape.tail_chunks;
     a.tail_base = shape.body_wgs * shape.body_iters;
@@ -452,7 +451,7 @@ static mr_status eye_tables_for(const DeviceScene &ds, EyeTablePool &pool, Frame
     b.build = 1; b.n_inner = ds.n_inner; b.n_rec = ds.n_tris;
     const uint32_t n = ds.n_inner > ds.n_tris ? ds.n_inner : ds.n_tris;
     if (n) {
-        hipLaunchKernelGGL((frame_kernel<794, 0, false>), dim3((n + kTraceBlock - 1) / kTraceBlock), dim3(kTraceBlock), 0, stream, b);
+        hipLaunchKernelGGL((frame_kernel<kTraceEyeRel, 0, false>), dim3((n + kTraceBlock - 1) / kTraceBlock), dim3(kTraceBlock), 0, stream, b);
         MR_HIP_CHECK(hipGetLastError());
     }
     if (capturing) e->captured = true;
@@ -500,14 +499,8 @@ mr_status MR_FRAME_ENTRY(const DeviceScene &ds, const mr_frame_desc &fd, float *
     }
     if (a.eye.n == 0) return MR_OK;
     if (a.eye.n >= (1ull << 32) * spp) return fail(MR_ERR_INVALID, "mr_render_direct: window too large");
-    TraceParams &p = a.tp;
-    p.nodes = ds.nodes; p.tris = ds.tris; p.tri_prim = ds.tri_prim; p.leaf_cnt_ext = ds.leaf_cnt_ext;
-    for (int c = 0; c < 3; c++) { p.root_lo[c] = ds.root_lo[c]; p.root_hi[c] = ds.root_hi[c]; }
-    p.root_ref = ds.root_ref;
-    p.stack_depth = (int32_t)ds.stack_depth;
-    p.rays = nullptr; p.hits = nullptr; p.n = a.eye.n; p.n_dev = nullptr; p.stats = nullptr;
-    p.planes = ds.planes; p.n_planes = ds.n_planes; p.n_spheres = ds.n_spheres;
-    p.work_counter = nullptr; p.order = nullptr;
+    a.tp = scene_trace_params(ds);
+    a.tp.n = a.eye.n;
     a.m = surface_ptrs(ds);
     for (int c = 0; c < 3; c++) {
         a.lt.L[c] = fd.light.position[c]; a.lt.color[c] = fd.light.color[c]; a.lt.diffuse[c] = fd.diffuse[c]; a.lt.bg[c] = 0.0f;
@@ -527,14 +520,16 @@ mr_status MR_FRAME_ENTRY(const DeviceScene &ds, const mr_frame_desc &fd, float *
     if ((mat || no_shadows) && (product || vote || (mat && any)))
         return fail(MR_ERR_INVALID, "mr_render_direct: per-object materials and MR_FRAME_NO_SHADOWS come with the default traversal only "
                                     "(no MR_MATH_PRODUCT / MR_TRACE_INCOHERENT%s)", mat ? " / MR_TRACE_ANY" : "");
+    // the table of with_trace_variant (mr_launch.h), except that only the default traversals have every shadow / material form
     if (ds.n_planes || ds.n_spheres)
-        return product ? launch_frame_plain<43>(a, any, stream) : launch_frame_default<826>(a, any, no_shadows, mat, stream);
-    if (vote) return product ? launch_frame_plain<73>(a, any, stream) : launch_frame_plain<88>(a, any, stream);
-    if (product) return launch_frame_plain<267>(a, any, stream);
-    // the eye-relative tables (and the root box relative to the eye, in the same fp32 subtraction as the trace's)
+        return product ? launch_frame_plain<kTraceProductObj>(a, any, stream) : launch_frame_default<kTraceExactObj>(a, any, no_shadows, mat, stream);
+    if (vote) return product ? launch_frame_plain<kTraceVoteProduct>(a, any, stream) : launch_frame_plain<kTraceVote>(a, any, stream);
+    if (product) return launch_frame_plain<kTraceProduct>(a, any, stream);
+    // on purpose kTraceEyeRel where that table has kTraceExact: the default without kVarMixedVote, its primary rays on the
+    // eye-relative tables (and the root box relative to the eye, in the same fp32 subtraction as the trace's)
     mr_status st = eye_tables_for(ds, eye_pool, a, stream);
     if (st != MR_OK) return st;
-    return launch_frame_default<794>(a, any, no_shadows, mat, stream);
+    return launch_frame_default<kTraceEyeRel>(a, any, no_shadows, mat, stream);
 }
 
 }  // namespace mr

@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "mr_internal.h"
+#include "mr_launch.h"
 #include "mr_surface.h"
 #include "mr_eye.h"
 #include "mr_phong.h"
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel(TraceParams p) {
     const int tid = threadIdx.x;
     const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
     Stats st = {0ull, 0ull};
-    constexpr bool kWW = (VAR & (2 | 64)) != 0;      // wave-cooperative control flow: whole waves enter the loop
+    constexpr bool kWW = (VAR & (kVarWhileWhile | kVarVote)) != 0;      // wave-cooperative control flow: whole waves enter the loop
 
     // indirect batches: the ray count lives on the device (e.g. written by the shadow-ray compaction)
     unsigned long long n_rays = p.n;
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel(TraceParams p) {
         int plane_hit;
         trace_ray<EXACT, ANY, STATS, VAR>(p, r, rb.w, live, L, plane_hit, s_stack, tid, st);
         if (live) {
-            const mr_hit h = make_hit<(VAR & 32) != 0>(p, L, plane_hit, rb.w);
+            const mr_hit h = make_hit<(VAR & kVarObjects) != 0>(p, L, plane_hit, rb.w);
             asm volatile("" ::: "memory");                // the index is read again rather than kept in registers across the traversal
             const unsigned long long dst = p.order ? (unsigned long long)p.order[idx] : idx;
             reinterpret_cast<float4 *>(p.hits)[dst] = *reinterpret_cast<const float4 *>(&h);
@@ -356,49 +357,23 @@ __global__ __launch_bounds__(kBlock) void hit_attrs_kernel(SurfacePtrs m, const 
     }
 }
 
-inline unsigned grid_for(unsigned long long n) {
-    // memory/latency-bound kernels: cap the grid and grid-stride the rest (256 CUs x 8 blocks)
-    unsigned long long blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 256ull * 32ull) blocks = 256ull * 32ull;
-    if (blocks == 0) blocks = 1;
-    return (unsigned)blocks;
-}
-
-// workgroups per trace launch.  -DMIRO_DEV builds read MIRO_TRACE_GRID_CAP once (A/B tooling); the shipped library
-// has no environment switches on the launch path.
-inline int trace_grid_cap() {
-#ifdef MIRO_DEV
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("MIRO_TRACE_GRID_CAP");
-        v = e ? atoi(e) : kTraceGridCap;
-        if (v < 1) v = 1;
-    }
-    return v;
-#else
-    return kTraceGridCap;
-#endif
-}
-
 template <bool EXACT, bool ANY, bool STATS, int VAR>
 mr_status launch_trace_t(const TraceParams &p, hipStream_t stream) {
-    size_t lds = (size_t)p.stack_depth * kTraceBlock * sizeof(int);
+    size_t lds = 0, pad = 0;
+    unsigned long long cap = kTraceGridCap;
 #ifdef MIRO_DEV
-    // occupancy experiments: MIRO_LDS_PAD bytes of unused LDS per workgroup (fewer workgroups per CU)
-    { static const size_t pad = getenv("MIRO_LDS_PAD") ? (size_t)atoi(getenv("MIRO_LDS_PAD")) : 0; lds += pad; }
+    // A/B tooling, read once (the shipped library has no environment switches on the launch path): MIRO_LDS_PAD bytes of
+    // unused LDS per workgroup (occupancy experiments: fewer workgroups per CU), MIRO_TRACE_GRID_CAP workgroups per launch
+    static const int env_pad = getenv("MIRO_LDS_PAD") ? atoi(getenv("MIRO_LDS_PAD")) : 0;
+    static const int env_cap = getenv("MIRO_TRACE_GRID_CAP") ? atoi(getenv("MIRO_TRACE_GRID_CAP")) : kTraceGridCap;
+    pad = (size_t)env_pad; cap = env_cap < 1 ? 1 : env_cap;
 #endif
-    if (lds > 160 * 1024) return fail(MR_ERR_INVALID, "traversal stack of depth %d does not fit in LDS", p.stack_depth);
-    if (lds > 64 * 1024)
-        MR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&trace_kernel<EXACT, ANY, STATS, VAR>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const mr_status st = stack_lds(&trace_kernel<EXACT, ANY, STATS, VAR>, p.stack_depth, kStackLdsWhole, lds, pad);
+    if (st != MR_OK) return st;
     // Many short-lived workgroups balance better than a resident grid that strides over its rays: with exactly one
     // chip-full of workgroups (1792) the 33 M-ray frame runs 13 % slower than with the capped grid below, because the
     // hardware dispatcher rebalances at workgroup granularity while a static stride cannot.
-    unsigned long long blocks = (p.n + kTraceBlock - 1) / kTraceBlock;
-    const unsigned long long cap = (unsigned long long)trace_grid_cap();
-    if (blocks > cap) blocks = cap;
-    const unsigned grid = blocks ? (unsigned)blocks : 1u;
-    hipLaunchKernelGGL((trace_kernel<EXACT, ANY, STATS, VAR>), dim3(grid), dim3(kTraceBlock), lds, stream, p);
+    hipLaunchKernelGGL((trace_kernel<EXACT, ANY, STATS, VAR>), dim3(trace_grid(p.n, cap)), dim3(kTraceBlock), lds, stream, p);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;
 }
@@ -407,58 +382,60 @@ mr_status launch_trace_t(const TraceParams &p, hipStream_t stream) {
 
 template <bool EXACT, bool ANY, bool QUOT, int REFILL_MIN, bool VOTE = false>
 static mr_status launch_persistent(const TraceParams &p, hipStream_t stream) {
-    const size_t lds = (size_t)p.stack_depth * kTraceBlock * sizeof(int);
-    if (lds > 160 * 1024) return fail(MR_ERR_INVALID, "traversal stack of depth %d does not fit in LDS", p.stack_depth);
     auto kern = &trace_persistent_kernel<EXACT, ANY, QUOT, REFILL_MIN, VOTE>;
-    if (lds > 64 * 1024)
-        MR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int dev = 0, cus = 256, per_cu = 1;
-    MR_HIP_CHECK(hipGetDevice(&dev));
-    MR_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    MR_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), kTraceBlock, lds));
-    if (per_cu < 1) per_cu = 1;
-    unsigned long long want = (p.n + kTraceBlock - 1) / kTraceBlock;
-    unsigned long long grid = (unsigned long long)cus * (unsigned)per_cu;
-    if (want < grid) grid = want;
+    size_t lds = 0;
+    unsigned grid = 1;
+    mr_status st = stack_lds(kern, p.stack_depth, kStackLdsWhole, lds);
+    if (st == MR_OK) st = resident_grid(kern, lds, (p.n + kTraceBlock - 1) / kTraceBlock, grid);
+    if (st != MR_OK) return st;
     MR_HIP_CHECK(hipMemsetAsync(p.work_counter, 0, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kTraceBlock), lds, stream, p, p.work_counter);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTraceBlock), lds, stream, p, p.work_counter);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;
+}
+
+// the closest-hit or the any-hit form of a kernel
+template <bool EXACT, bool STATS, int VAR>
+static mr_status launch_trace_a(const TraceParams &p, bool any, hipStream_t stream) {
+    return any ? launch_trace_t<EXACT, true, STATS, VAR>(p, stream) : launch_trace_t<EXACT, false, STATS, VAR>(p, stream);
+}
+template <bool QUOT, bool VOTE>
+static mr_status launch_persistent_a(const TraceParams &p, bool any, hipStream_t stream) {
+    return any ? launch_persistent<true, true, QUOT, 16, VOTE>(p, stream) : launch_persistent<true, false, QUOT, 16, VOTE>(p, stream);
 }
 
 #ifdef MIRO_DEV
 // development builds only (make DEV=1): MIRO_TRACE_VARIANT selects a control-flow / slab-test variant of the
 // MR_MATH_PRODUCT kernel for tools/ab_variants.py:
-//   0..15  one launch-time ray per lane (bit 0: min/max slabs, bit 1: while-while, bit 2: lean fma slabs,
-//          bit 3: wave-uniform nodes through the scalar cache)
+//   0..15  one launch-time ray per lane, the variant bits themselves (kVarMinMax, kVarWhileWhile, kVarLeanFma, kVarScalar)
 //   16,17  persistent waves with ballot/prefix re-arming of idle lanes (refill threshold 1 / 16 lanes)
 static int trace_variant() {
     static int v = -1;
     if (v < 0) {
         const char *e = getenv("MIRO_TRACE_VARIANT");
-        v = e ? (atoi(e) & 31) : 11;
+        v = e ? (atoi(e) & 31) : kTraceDevProduct;
     }
     return v;
 }
 template <bool ANY>
 static mr_status launch_product(const TraceParams &p, hipStream_t stream) {
     switch (trace_variant()) {
-        case 0: return launch_trace_t<true, ANY, false, 0>(p, stream);
-        case 1: return launch_trace_t<true, ANY, false, 1>(p, stream);
-        case 2: return launch_trace_t<true, ANY, false, 2>(p, stream);
-        case 3: return launch_trace_t<true, ANY, false, 3>(p, stream);
-        case 7: return launch_trace_t<true, ANY, false, 7>(p, stream);
-        case 9: return launch_trace_t<true, ANY, false, 9>(p, stream);
+        case kTracePlain: return launch_trace_t<true, ANY, false, kTracePlain>(p, stream);
+        case kVarMinMax: return launch_trace_t<true, ANY, false, kVarMinMax>(p, stream);
+        case kVarWhileWhile: return launch_trace_t<true, ANY, false, kVarWhileWhile>(p, stream);
+        case kVarWhileWhile | kVarMinMax: return launch_trace_t<true, ANY, false, kVarWhileWhile | kVarMinMax>(p, stream);
+        case kVarLeanFma | kVarWhileWhile | kVarMinMax: return launch_trace_t<true, ANY, false, kVarLeanFma | kVarWhileWhile | kVarMinMax>(p, stream);
+        case kVarScalar | kVarMinMax: return launch_trace_t<true, ANY, false, kVarScalar | kVarMinMax>(p, stream);
         case 16: return launch_persistent<true, ANY, false, 1>(p, stream);
         case 17: return launch_persistent<true, ANY, false, 16>(p, stream);
-        default: return launch_trace_t<true, ANY, false, 11>(p, stream);
+        default: return launch_trace_t<true, ANY, false, kTraceDevProduct>(p, stream);
     }
 }
 #else
 // MR_MATH_PRODUCT: min/max slabs on (corner - o) * (1/d), while-while, wave-uniform nodes through the scalar cache
 template <bool ANY>
 static mr_status launch_product(const TraceParams &p, hipStream_t stream) {
-    return launch_trace_t<true, ANY, false, 267>(p, stream);
+    return launch_trace_a<true, false, kTraceProduct>(p, ANY, stream);
 }
 #endif
 
@@ -474,6 +451,8 @@ mr_status launch_octant_order(const mr_ray *d_rays, const uint8_t *d_octants, un
     return MR_OK;
 }
 
+// Which kernel traces a batch.  Unlike the table mr_trace_level and mr_shade_lights share (with_trace_variant, mr_launch.h)
+// this one also has the counting, fast, persistent and development forms.
 mr_status launch_trace(const TraceParams &p, uint32_t flags, hipStream_t stream) {
     if (p.n == 0) return MR_OK;
     // a ray order (mr_trace_grouped) is gathered by the one-shot kernels only
@@ -481,49 +460,33 @@ mr_status launch_trace(const TraceParams &p, uint32_t flags, hipStream_t stream)
     const bool fast = flags & MR_MATH_FAST, any = flags & MR_TRACE_ANY, stats = flags & MR_COUNT_STATS;
     const bool product = flags & MR_MATH_PRODUCT, vote = flags & MR_TRACE_INCOHERENT;
     if (p.n_planes || p.n_spheres) {
-        // scenes with spheres / planes: the exact kernels with the object dispatch compiled in (VAR bit 5); the fast
+        // scenes with spheres / planes: the exact kernels with the object dispatch compiled in (kVarObjects); the fast
         // and persistent forms cover triangle scenes only
-        if (stats) return any ? launch_trace_t<true, true, true, 32>(p, stream) : launch_trace_t<true, false, true, 32>(p, stream);
-        if (vote) {
-            if (product) return any ? launch_trace_t<true, true, false, 105>(p, stream) : launch_trace_t<true, false, false, 105>(p, stream);
-            return any ? launch_trace_t<true, true, false, 120>(p, stream) : launch_trace_t<true, false, false, 120>(p, stream);
-        }
-        if (product) return any ? launch_trace_t<true, true, false, 43>(p, stream) : launch_trace_t<true, false, false, 43>(p, stream);
-        return any ? launch_trace_t<true, true, false, 826>(p, stream) : launch_trace_t<true, false, false, 826>(p, stream);
+        if (stats) return launch_trace_a<true, true, kTracePlainObj>(p, any, stream);
+        // on purpose beyond the shared table, which ignores `vote` here: voting kernels for scenes with objects
+        if (vote) return product ? launch_trace_a<true, false, kTraceVoteProductObj>(p, any, stream) : launch_trace_a<true, false, kTraceVoteObj>(p, any, stream);
+        return product ? launch_trace_a<true, false, kTraceProductObj>(p, any, stream) : launch_trace_a<true, false, kTraceExactObj>(p, any, stream);
     }
-    if (stats) {
-        // counting mode is diagnostic: always the literal-division kernel in the reference's control flow
-        return any ? launch_trace_t<true, true, true, 0>(p, stream) : launch_trace_t<true, false, true, 0>(p, stream);
-    }
-    // MR_MATH_FAST: lean fma slabs + fmaf/rcp triangle test, with the same scalar-cache path as the exact kernels (VAR 15)
-    if (fast) return any ? launch_trace_t<false, true, false, 15>(p, stream) : launch_trace_t<false, false, false, 15>(p, stream);
-    if ((flags & MR_TRACE_PERSISTENT) && vote) {
-        if (product) return any ? launch_persistent<true, true, false, 16, true>(p, stream) : launch_persistent<true, false, false, 16, true>(p, stream);
-        return any ? launch_persistent<true, true, true, 16, true>(p, stream) : launch_persistent<true, false, true, 16, true>(p, stream);
-    }
+    // counting mode is diagnostic: always the literal-division kernel in the reference's control flow
+    if (stats) return launch_trace_a<true, true, kTracePlain>(p, any, stream);
+    // MR_MATH_FAST: lean fma slabs + fmaf/rcp triangle test, with the same scalar-cache path as the exact kernels
+    if (fast) return launch_trace_a<false, false, kTraceFast>(p, any, stream);
+    if ((flags & MR_TRACE_PERSISTENT) && vote) return product ? launch_persistent_a<false, true>(p, any, stream) : launch_persistent_a<true, true>(p, any, stream);
 #ifdef MIRO_DEV
-    // development builds only: MIRO_EXACT_CORRECTION=1 runs the default trace on the correction steps alone (VAR bit 9 clear)
+    // development builds only: MIRO_EXACT_CORRECTION=1 runs the default trace on the correction steps alone (kVarGuarded clear)
     static const bool corr_only = getenv("MIRO_EXACT_CORRECTION") && atoi(getenv("MIRO_EXACT_CORRECTION")) != 0;
-    if (corr_only && !product && !vote && !(flags & MR_TRACE_PERSISTENT)) {
-        return any ? launch_trace_t<true, true, false, 282>(p, stream) : launch_trace_t<true, false, false, 282>(p, stream);
-    }
+    if (corr_only && !product && !vote && !(flags & MR_TRACE_PERSISTENT)) return launch_trace_a<true, false, kTraceCorrection>(p, any, stream);
 #endif
-    if (vote) {
-        // MR_TRACE_INCOHERENT: the voting control flow (VAR bit 6) on the same arithmetic
-        if (product) return any ? launch_trace_t<true, true, false, 73>(p, stream) : launch_trace_t<true, false, false, 73>(p, stream);
-        // (on the correction steps alone: incoherent batches are bound by their fetches, and the guard's wave-wide branch
-        // costs them 5 %, profiles/r02_guarded_products_ab.log)
-        return any ? launch_trace_t<true, true, false, 88>(p, stream) : launch_trace_t<true, false, false, 88>(p, stream);
-    }
-    if (flags & MR_TRACE_PERSISTENT) {
-        if (product) return any ? launch_persistent<true, true, false, 16>(p, stream) : launch_persistent<true, false, false, 16>(p, stream);
-        return any ? launch_persistent<true, true, true, 16>(p, stream) : launch_persistent<true, false, true, 16>(p, stream);
-    }
+    // MR_TRACE_INCOHERENT: the voting control flow (kVarVote) on the same arithmetic
+    // (the exact form on the correction steps alone: incoherent batches are bound by their fetches, and the guard's wave-wide
+    // branch costs them 5 %, profiles/r02_guarded_products_ab.log)
+    if (vote) return product ? launch_trace_a<true, false, kTraceVoteProduct>(p, any, stream) : launch_trace_a<true, false, kTraceVote>(p, any, stream);
+    if (flags & MR_TRACE_PERSISTENT) return product ? launch_persistent_a<false, false>(p, any, stream) : launch_persistent_a<true, false>(p, any, stream);
     // MR_MATH_PRODUCT: slab distances as products with the rounded 1/d (and its development variants)
     if (product) return any ? launch_product<true>(p, stream) : launch_product<false>(p, stream);
     // default: the reference's quotients -- guarded products, correction steps where a decision is close -- while-while,
-    // scalar path, octant-specialised; waves whose rays point into several octants vote (VAR 16 | 2 | 8 | 256 | 512 | 1024)
-    return any ? launch_trace_t<true, true, false, 1818>(p, stream) : launch_trace_t<true, false, false, 1818>(p, stream);
+    // scalar path, octant-specialised; waves whose rays point into several octants vote
+    return launch_trace_a<true, false, kTraceExact>(p, any, stream);
 }
 
 mr_status launch_eye_rays(const mr_camera &cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1,

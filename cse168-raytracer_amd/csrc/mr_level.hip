@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mr_internal.h"
+#include "mr_launch.h"
 #include "mr_phong.h"
 #include "mr_recursion.h"
 #include "mr_traverse.h"
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(CHI
     const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
     const unsigned long long n = a.tp.n;
     const unsigned long long n_round = (n + (unsigned long long)kTraceBlock - 1ull) / kTraceBlock * kTraceBlock;   // whole workgroups
-    constexpr bool kObj = (VAR & 32) != 0;
+    constexpr bool kObj = (VAR & kVarObjects) != 0;
     constexpr bool kPath = CHILDREN == 2;
     Stats st = {0ull, 0ull};
     unsigned my_shadow_rays = 0;
@@ -163,14 +164,10 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(CHI
 
 template <int VAR, int CHILDREN>
 mr_status launch_level_t(const LevelArgs &a, hipStream_t stream) {
-    const size_t lds = (size_t)a.tp.stack_depth * kTraceBlock * sizeof(int);
-    if (lds > 150 * 1024) return fail(MR_ERR_INVALID, "traversal stack of depth %d does not fit in LDS", a.tp.stack_depth);
-    if (lds > 48 * 1024)
-        MR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&level_kernel<VAR, CHILDREN>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    unsigned long long blocks = (a.tp.n + kTraceBlock - 1) / kTraceBlock;
-    if (blocks > (unsigned long long)kTraceGridCap) blocks = kTraceGridCap;
-    hipLaunchKernelGGL((level_kernel<VAR, CHILDREN>), dim3((unsigned)blocks), dim3(kTraceBlock), lds, stream, a);
+    size_t lds = 0;
+    const mr_status st = stack_lds(&level_kernel<VAR, CHILDREN>, a.tp.stack_depth, kStackLdsShared, lds);
+    if (st != MR_OK) return st;
+    hipLaunchKernelGGL((level_kernel<VAR, CHILDREN>), dim3(trace_grid(a.tp.n)), dim3(kTraceBlock), lds, stream, a);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;
 }
@@ -193,14 +190,8 @@ mr_status launch_level(const DeviceScene &ds, const mr_level_desc &ld, const mr_
     if (ld.children != MR_LEVEL_LAST) MR_HIP_CHECK(hipMemsetAsync(d_out_count, 0, sizeof(unsigned long long), stream));
     if (n == 0) return MR_OK;
     LevelArgs a;
-    TraceParams &p = a.tp;
-    p.nodes = ds.nodes; p.tris = ds.tris; p.tri_prim = ds.tri_prim; p.leaf_cnt_ext = ds.leaf_cnt_ext;
-    for (int c = 0; c < 3; c++) { p.root_lo[c] = ds.root_lo[c]; p.root_hi[c] = ds.root_hi[c]; }
-    p.root_ref = ds.root_ref;
-    p.stack_depth = (int32_t)ds.stack_depth;
-    p.rays = d_rays; p.hits = nullptr; p.n = n; p.n_dev = nullptr; p.stats = nullptr;
-    p.planes = ds.planes; p.n_planes = ds.n_planes; p.n_spheres = ds.n_spheres;
-    p.work_counter = nullptr; p.order = ld.d_order;
+    a.tp = scene_trace_params(ds);
+    a.tp.rays = d_rays; a.tp.n = n; a.tp.order = ld.d_order;
     a.m = mesh_of(ds);
     for (int c = 0; c < 3; c++) { a.lt.L[c] = ld.light.position[c]; a.lt.color[c] = ld.light.color[c]; }
     a.lt.wattage = ld.light.wattage;
@@ -212,10 +203,8 @@ mr_status launch_level(const DeviceScene &ds, const mr_level_desc &ld, const mr_
     a.out.octants = ld.d_out_octants;
     a.counts = d_counts;
 
-    const bool product = ld.flags & MR_MATH_PRODUCT, vote = ld.flags & MR_TRACE_INCOHERENT;
-    if (ds.n_planes || ds.n_spheres) return product ? launch_level_c<43>(a, ld.children, stream) : launch_level_c<826>(a, ld.children, stream);
-    if (vote) return product ? launch_level_c<73>(a, ld.children, stream) : launch_level_c<88>(a, ld.children, stream);
-    return product ? launch_level_c<267>(a, ld.children, stream) : launch_level_c<1818>(a, ld.children, stream);
+    return with_trace_variant(ds.n_planes || ds.n_spheres, ld.flags & MR_MATH_PRODUCT, ld.flags & MR_TRACE_INCOHERENT,
+                              [&](auto var) { return launch_level_c<decltype(var)::value>(a, ld.children, stream); });
 }
 
 }  // namespace mr

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mr_internal.h"
+#include "mr_launch.h"
 #include "mr_phong.h"
 #include "mr_recursion.h"
 #include "mr_traverse.h"
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
     const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
     const unsigned long long n = a.tp.n;
     const unsigned long long n_round = (n + (unsigned long long)kTraceBlock - 1ull) / kTraceBlock * kTraceBlock;   // whole workgroups
-    constexpr bool kObj = (VAR & 32) != 0;
+    constexpr bool kObj = (VAR & kVarObjects) != 0;
     Stats st = {0ull, 0ull};
     unsigned my_shadow_rays = 0;
 
@@ -189,14 +190,10 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
 
 template <int VAR, bool ANY>
 mr_status launch_lights_t(const LightsArgs &a, hipStream_t stream) {
-    const size_t lds = (size_t)a.tp.stack_depth * kTraceBlock * sizeof(int);
-    if (lds > 150 * 1024) return fail(MR_ERR_INVALID, "traversal stack of depth %d does not fit in LDS", a.tp.stack_depth);
-    if (lds > 48 * 1024)
-        MR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&shade_lights_kernel<VAR, ANY>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    unsigned long long blocks = (a.tp.n + kTraceBlock - 1) / kTraceBlock;
-    if (blocks > (unsigned long long)kTraceGridCap) blocks = kTraceGridCap;
-    hipLaunchKernelGGL((shade_lights_kernel<VAR, ANY>), dim3((unsigned)blocks), dim3(kTraceBlock), lds, stream, a);
+    size_t lds = 0;
+    const mr_status st = stack_lds(&shade_lights_kernel<VAR, ANY>, a.tp.stack_depth, kStackLdsShared, lds);
+    if (st != MR_OK) return st;
+    hipLaunchKernelGGL((shade_lights_kernel<VAR, ANY>), dim3(trace_grid(a.tp.n)), dim3(kTraceBlock), lds, stream, a);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;
 }
@@ -214,14 +211,8 @@ mr_status launch_shade_lights(const DeviceScene &ds, const ShadeLight *lights, u
                               hipStream_t stream) {
     if (n == 0) return MR_OK;
     LightsArgs a;
-    TraceParams &p = a.tp;
-    p.nodes = ds.nodes; p.tris = ds.tris; p.tri_prim = ds.tri_prim; p.leaf_cnt_ext = ds.leaf_cnt_ext;
-    for (int c = 0; c < 3; c++) { p.root_lo[c] = ds.root_lo[c]; p.root_hi[c] = ds.root_hi[c]; }
-    p.root_ref = ds.root_ref;
-    p.stack_depth = (int32_t)ds.stack_depth;
-    p.rays = d_rays; p.hits = nullptr; p.n = n; p.n_dev = nullptr; p.stats = nullptr;
-    p.planes = ds.planes; p.n_planes = ds.n_planes; p.n_spheres = ds.n_spheres;
-    p.work_counter = nullptr; p.order = nullptr;
+    a.tp = scene_trace_params(ds);
+    a.tp.rays = d_rays; a.tp.n = n;
     a.m = mesh_of(ds);
     a.hits = d_hits; a.weights = d_weights; a.pixels = d_pixels;
     a.spp = spp; a.n_lights = n_lights; a.inv_spp = 1.0f / (float)spp;
@@ -229,10 +220,9 @@ mr_status launch_shade_lights(const DeviceScene &ds, const ShadeLight *lights, u
     for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = lights[i < n_lights ? i : 0];
 
     // the traversal variants of launch_level / launch_trace: the same hit records from each of them
-    const bool product = flags & MR_MATH_PRODUCT, vote = flags & MR_TRACE_INCOHERENT, any = flags & MR_TRACE_ANY;
-    if (ds.n_planes || ds.n_spheres) return product ? launch_lights_a<43>(a, any, stream) : launch_lights_a<826>(a, any, stream);
-    if (vote) return product ? launch_lights_a<73>(a, any, stream) : launch_lights_a<88>(a, any, stream);
-    return product ? launch_lights_a<267>(a, any, stream) : launch_lights_a<1818>(a, any, stream);
+    const bool any = flags & MR_TRACE_ANY;
+    return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT,
+                              [&](auto var) { return launch_lights_a<decltype(var)::value>(a, any, stream); });
 }
 
 }  // namespace mr

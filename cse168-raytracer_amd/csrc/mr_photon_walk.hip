@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mr_internal.h"
+#include "mr_launch.h"
 #include "mr_recursion.h"
 #include "mr_traverse.h"
 
@@ -51,7 +52,7 @@ template <int VAR>
 __global__ __launch_bounds__(kTraceBlock) void photon_walk_kernel(WalkArgs a) {
     extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
     const int tid = threadIdx.x, lane = tid & 63;
-    constexpr bool kObj = (VAR & 32) != 0;
+    constexpr bool kObj = (VAR & kVarObjects) != 0;
     Stats st = {0ull, 0ull};
 
     uint32_t my = kNoPhoton, state = 0;               // local emission index of the lane's photon
@@ -228,22 +229,14 @@ __global__ __launch_bounds__(kBlock) void photon_compact_kernel(const float4 *sl
 
 template <int VAR>
 mr_status launch_walk_t(const WalkArgs &a, hipStream_t stream) {
-    const size_t lds = (size_t)a.tp.stack_depth * kTraceBlock * sizeof(int);
-    if (lds > 150 * 1024) return fail(MR_ERR_INVALID, "traversal stack of depth %d does not fit in LDS", a.tp.stack_depth);
     auto kern = &photon_walk_kernel<VAR>;
-    if (lds > 48 * 1024)
-        MR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    size_t lds = 0;
+    unsigned grid = 1;
+    mr_status st = stack_lds(kern, a.tp.stack_depth, kStackLdsShared, lds);
     // a resident grid: every wave keeps pulling emissions until the round is handed out
-    int dev = 0, cus = 256, per_cu = 1;
-    MR_HIP_CHECK(hipGetDevice(&dev));
-    MR_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    MR_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), kTraceBlock, lds));
-    if (per_cu < 1) per_cu = 1;
-    unsigned long long grid = (unsigned long long)cus * (unsigned)per_cu;
-    const unsigned long long want = ((unsigned long long)a.count + kTraceBlock - 1) / kTraceBlock;
-    if (want < grid) grid = want;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kTraceBlock), lds, stream, a);
+    if (st == MR_OK) st = resident_grid(kern, lds, ((unsigned long long)a.count + kTraceBlock - 1) / kTraceBlock, grid);
+    if (st != MR_OK) return st;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTraceBlock), lds, stream, a);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;
 }
@@ -254,14 +247,8 @@ mr_status launch_photon_round(const DeviceScene &ds, const PhotonWalkLight &lt, 
                               uint32_t first, uint32_t count, unsigned long long need, const PhotonRoundBuffers &b, hipStream_t stream) {
     if (count == 0 || count > b.capacity) return fail(MR_ERR_INVALID, "photon round of %u emissions (buffers hold %u)", count, b.capacity);
     WalkArgs a;
-    TraceParams &p = a.tp;
-    p.nodes = ds.nodes; p.tris = ds.tris; p.tri_prim = ds.tri_prim; p.leaf_cnt_ext = ds.leaf_cnt_ext;
-    for (int c = 0; c < 3; c++) { p.root_lo[c] = ds.root_lo[c]; p.root_hi[c] = ds.root_hi[c]; }
-    p.root_ref = ds.root_ref;
-    p.stack_depth = (int32_t)ds.stack_depth;
-    p.rays = nullptr; p.hits = nullptr; p.n = count; p.n_dev = nullptr; p.stats = nullptr;
-    p.planes = ds.planes; p.n_planes = ds.n_planes; p.n_spheres = ds.n_spheres;
-    p.work_counter = nullptr; p.order = nullptr;
+    a.tp = scene_trace_params(ds);
+    a.tp.n = count;
     a.m = mesh_of(ds);
     for (int c = 0; c < 3; c++) { a.pos[c] = lt.position[c]; a.dir[c] = lt.direction[c]; a.t1[c] = lt.t1[c]; a.t2[c] = lt.t2[c]; a.power[c] = lt.power[c]; }
     a.radius = lt.radius;
@@ -270,7 +257,7 @@ mr_status launch_photon_round(const DeviceScene &ds, const PhotonWalkLight &lt, 
     a.slots = b.slots; a.words = b.words; a.next = b.next;
     MR_HIP_CHECK(hipMemsetAsync(b.next, 0, sizeof(unsigned), stream));
     // photons walk incoherently after their first bounce: the voting control flow of the default (exact) traversal
-    mr_status st = (ds.n_planes || ds.n_spheres) ? launch_walk_t<120>(a, stream) : launch_walk_t<88>(a, stream);
+    mr_status st = (ds.n_planes || ds.n_spheres) ? launch_walk_t<kTraceVoteObj>(a, stream) : launch_walk_t<kTraceVote>(a, stream);
     if (st != MR_OK) return st;
     hipLaunchKernelGGL(photon_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, b.words, count, need, b.offsets, b.header);
     MR_HIP_CHECK(hipGetLastError());

@@ -10,14 +10,13 @@
 #include <hip/hip_runtime.h>
 
 #include "mr_internal.h"
+#include "mr_launch.h"
 #include "mr_phong.h"
 #include "mr_surface.h"
 #include "mr_tile.h"
 
 namespace mr {
 namespace {
-
-constexpr int kBlock = 256;
 
 __global__ __launch_bounds__(kBlock) void occlusion_scatter_kernel(const mr_hit *shadow_hits, const uint32_t *src,
                                                                    const unsigned long long *count,
@@ -167,13 +166,6 @@ __global__ __launch_bounds__(kBlock) void deinterleave_kernel(const float *recv,
         const uint32_t band = y / band_rows, rank = band % world, local = (band / world) * band_rows + y % band_rows;
         full[i] = recv[((unsigned long long)rank * shard_rows + local) * row_floats + x];
     }
-}
-
-inline unsigned grid_for(unsigned long long n) {
-    unsigned long long blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 256ull * 32ull) blocks = 256ull * 32ull;
-    if (blocks == 0) blocks = 1;
-    return (unsigned)blocks;
 }
 
 }  // namespace

@@ -13,19 +13,11 @@
 #include <hip/hip_runtime.h>
 
 #include "mr_internal.h"
+#include "mr_launch.h"
 
 namespace mr {
 namespace {
 
-constexpr int kBlock = 256;          // 4 waves per workgroup
-#ifndef MIRO_TRACE_BLOCK
-#define MIRO_TRACE_BLOCK 256
-#endif
-constexpr int kTraceBlock = MIRO_TRACE_BLOCK;   // threads per workgroup of the trace kernels (their LDS stack is [depth][kTraceBlock])
-#ifndef MIRO_GRID_CAP
-#define MIRO_GRID_CAP 32768
-#endif
-constexpr int kTraceGridCap = MIRO_GRID_CAP; // workgroups per trace launch (see launch_trace_t)
 // the fused frame kernel on frames of 2^18 chunks or more (1080p at 64 spp is 518 400): twice the workgroups, and XCD runs of 256
 // chunks instead of 64 -- +1.1 % there, while frames of 4 to 16 samples per pixel lose 1.5-4 % to either (profiles/r03_grid_ab.log)
 #ifndef MIRO_CAP_LARGE
@@ -333,13 +325,7 @@ __device__ __forceinline__ bool object_test(const float4 q0, const float4 q1, co
 }
 
 // ---------------------------------------------------------------------------------------------------
-// closest-hit / any-hit traversal, one ray per lane.
-// VAR bit 0: when no lane of the wave can produce a NaN in a slab product (o, d, 1/d all finite -- wave-uniform
-//            test via __all), the select chains of the slab test collapse to v_min/v_max, which give the same
-//            decisions (they differ only in the sign of a zero);
-// VAR bit 1: "while-while" control flow: lanes run inner nodes until each holds a leaf (or is done), then the
-//            wave does the leaves together -- same per-lane visiting order, better SIMD utilisation in the
-//            triangle loop.
+// closest-hit / any-hit traversal, one ray per lane (its slab forms and control flows: the kVar... bits of mr_launch.h)
 // ---------------------------------------------------------------------------------------------------
 // `cur` is the node the lane is at: >= 0 inner node, < 0 leaf reference, kDone = no more work.  `sp` is the BYTE
 // offset in LDS of the lane's next free stack slot (slots of one lane are kTraceBlock * 4 bytes apart); the bottom slot
@@ -728,11 +714,7 @@ __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r,
 // One ray per lane from the root test to the unbounded-object scan: Scene::trace (Scene.cpp:214-230) ->
 // BVH::intersect (BVH.cpp:438-469) -> intersectChildren.  `live` = the lane holds a ray; the call is made by whole
 // waves (the while-while loop votes with __any).  Result in L (best_t / best_pos / beta / gamma) and plane_hit.
-// VAR bit 0: min/max slabs on the products (corner - o) * (1/d) for waves that cannot produce a NaN;
-//     bit 1: while-while control flow (bit 6: the voting control flow instead); bit 2: lean fma slabs (MR_MATH_FAST); bit 3: wave-uniform nodes and leaves
-//     through the scalar cache; bit 4: every slab distance is the reference's true quotient (the default trace;
-//     MR_COUNT_STATS implies it); bit 5: the scene holds spheres and / or planes; bit 8: octant-specialised slab tests
-//     for waves whose rays share an octant.
+// VAR: the kVar... bits of mr_launch.h, which also names the combinations the launchers use.
 // REL: p holds the eye-relative tables of the fused frame (mr_frame.hip: eye_tables) -- node corners and root box minus the
 //     eye, triangle records of tri_test_rel -- and every ray starts at the eye: the origin is taken as the constant 0, so the
 //     slab distances (corner - o) / d become (corner - eye) / d on the stored differences with no subtraction left, the
@@ -743,16 +725,16 @@ __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r,
 template <bool EXACT, bool ANY, bool STATS, int VAR, bool REL = false>
 __device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r_in, float tmax0, bool live, Lane &L,
                                           int &plane_hit, int *s_stack, int tid, Stats &st) {
-    static_assert(!REL || ((VAR & 16) && !(VAR & 32) && !STATS), "eye-relative tables: default traversal, triangles only");
+    static_assert(!REL || ((VAR & kVarStrict) && !(VAR & kVarObjects) && !STATS), "eye-relative tables: default traversal, triangles only");
     RayRegs r = r_in;
     if (REL) { r.ox = 0.0f; r.oy = 0.0f; r.oz = 0.0f; }
-    constexpr bool kStrict = STATS || (VAR & 16);
+    constexpr bool kStrict = STATS || (VAR & kVarStrict);
     constexpr int kBaseSlab = kStrict ? 3 : 0;
-    constexpr bool kMinMax = !kStrict && (VAR & 1);
-    constexpr int kWW = (VAR & 64) ? 2 : ((VAR & 2) ? 1 : 0);   // control flow of traverse()
-    constexpr int kSafeSlab = (VAR & 4) ? 2 : 1;      // slab form for waves whose rays cannot produce a NaN
-    constexpr bool kScalar = (VAR & 8) != 0;          // wave-uniform nodes through the scalar cache
-    constexpr bool kObj = (VAR & 32) != 0;            // the scene holds spheres and / or planes
+    constexpr bool kMinMax = !kStrict && (VAR & kVarMinMax);
+    constexpr int kWW = (VAR & kVarVote) ? 2 : ((VAR & kVarWhileWhile) ? 1 : 0);   // control flow of traverse()
+    constexpr int kSafeSlab = (VAR & kVarLeanFma) ? 2 : 1;      // slab form for waves whose rays cannot produce a NaN
+    constexpr bool kScalar = (VAR & kVarScalar) != 0;          // wave-uniform nodes through the scalar cache
+    constexpr bool kObj = (VAR & kVarObjects) != 0;            // the scene holds spheres and / or planes
 
     L.best_t = tmax0;                             // minHit.t = tMax (BVH.cpp:444)
     L.best_b = 0.0f; L.best_g = 0.0f;
@@ -767,10 +749,10 @@ __device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r
         L.cur = (live && !((mn > mx) || (mn > tmax0) || (mx < r.tmin))) ? p.root_ref : kDone;
     }
 
-    // VAR bit 8: when the wave's live rays all point into one octant the slab tests take their near / far corners by
+    // kVarOctant: when the wave's live rays all point into one octant the slab tests take their near / far corners by
     // position (slab_box_oct): eight copies of the loop, chosen once per ray batch of the wave
-    constexpr bool kOct = (VAR & 256) != 0;
-    constexpr int kExactSlab = (VAR & 512) ? 5 : 4;   // VAR bit 9: guarded products (node_slabs_guarded) instead of the correction steps
+    constexpr bool kOct = (VAR & kVarOctant) != 0;
+    constexpr int kExactSlab = (VAR & kVarGuarded) ? 5 : 4;   // guarded products (node_slabs_guarded) instead of the correction steps
     constexpr int kGoodSlab = kMinMax ? kSafeSlab : kExactSlab;
     constexpr int kOctSlab = kGoodSlab == 5 ? 6 : kGoodSlab;     // the octant loops' guard assumes tMin == 0 (node_slabs_guarded)
     const bool good_wave = kMinMax ? __all(lane_is_nan_free(r) || !live) : ((kStrict && !STATS) ? __all(lane_is_regular(r) || !live) : false);
@@ -802,14 +784,14 @@ __device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r
         if (good_wave) traverse<EXACT, ANY, STATS, kSafeSlab, kWW, kScalar, kObj>(p, r, L, s_stack, tid, st);
         else traverse<EXACT, ANY, STATS, 0, kWW, false, kObj>(p, r, L, s_stack, tid, st);
     } else if (kStrict && !STATS) {
-        // the default trace: where every lane's ray is regular, the quotients' decisions from guarded products (VAR bit 9)
+        // the default trace: where every lane's ray is regular, the quotients' decisions from guarded products (kVarGuarded)
         // or from the correction steps (then the lanes' quotients are NaN-free too and the min/max form decides like the
         // select form); the reference's own divisions otherwise
         // (a wave whose rays point into several octants is an incoherent one: bound by its record fetches, it gains nothing
         // from the guarded products and would pay for their wave-wide branch -- the correction steps alone here)
-        // VAR bit 10: ... and the voting control flow suits it better (random rays 3.86 -> 4.09 Grays/s, the atrium's bounce
+        // kVarMixedVote: ... and the voting control flow suits it better (random rays 3.86 -> 4.09 Grays/s, the atrium's bounce
         // rays 4.96 -> 5.31, 1-spp shadow rays in image order 3.73 -> 4.31 without the caller's MR_TRACE_INCOHERENT hint)
-        constexpr int kMixedFlow = ((VAR & 1024) && kWW == 1) ? 2 : kWW;
+        constexpr int kMixedFlow = ((VAR & kVarMixedVote) && kWW == 1) ? 2 : kWW;
         if (good_wave) traverse<EXACT, ANY, STATS, 4, kMixedFlow, kScalar, kObj, 8, REL>(p, r, L, s_stack, tid, st);
         else traverse<EXACT, ANY, STATS, 3, kWW, kScalar, kObj, 8, REL>(p, r, L, s_stack, tid, st);
     } else {
