@@ -65,6 +65,9 @@ void release_device(mr_scene *s) {
     (void)hipFree(s->d_light_scale);
     s->d_light_scale = nullptr;
     s->light_scale_cap = 0;
+    (void)hipFree(s->d_env);
+    s->d_env = nullptr;
+    s->env_dirty = s->env.W != 0;          // the image outlives the device records: the next shade call uploads it again
 }
 
 inline int32_t leaf_ref(uint32_t first, uint32_t count) {
@@ -353,6 +356,47 @@ mr_status require_device(const mr_scene *s) {
     if (!s->on_device)
         return fail(MR_ERR_STATE, "scene was built host_only: nothing is resident on a device and there is no CPU fallback");
     return MR_OK;
+}
+
+// LoadedTexture::LoadedTexture (Texture.cpp:30-92) for a FIT_RGBF image of W x H pixels: m_maxIntensity and the low-res image,
+// written behind the image's own records in e.rec
+void build_environment_image(HostEnvironment &e, const float *px) {
+    const int w = (int)e.W, h = (int)e.H;
+    const int lrw = (int)e.lw, lrh = (int)e.lh;
+    e.rec.assign(4 * ((size_t)w * h + (size_t)lrw * lrh), 0.0f);
+    float max_intensity = -1e15;                                               // :34
+    for (int i = 0; i < h; i++)                                                // :41-50
+        for (int j = 0; j < w; j++) {
+            const float *p = px + 3 * ((size_t)i * w + j);
+            float *r = &e.rec[4 * ((size_t)i * w + j)];
+            for (int k = 0; k < 3; k++) {
+                if (max_intensity < p[k]) max_intensity = p[k];
+                r[k] = p[k];
+            }
+        }
+    e.max_intensity = max_intensity;
+    const float PI = 3.1415926535897932384626433832795028841972f;               // Miro.h:10
+    float *low = &e.rec[4 * (size_t)w * h];
+    for (int i = 0; i < lrh; i++)                                              // :63-91
+        for (int j = 0; j < lrw; j++) {
+            long double acc[3] = {0.0, 0.0, 0.0};
+            const int midX = (w / lrw) * j + (w / lrw) / 2;
+            const int midY = (h / lrh) * i + (h / lrh) / 2;
+            for (int ii = (h / lrh) * i; ii < (h / lrh) * i + (h / lrh) && ii < h; ii++)
+                for (int jj = (w / lrw) * j; jj < (w / lrw) * j + (w / lrw) && jj < w; jj++) {
+                    const float *p = px + 3 * ((size_t)ii * w + jj);
+                    const float x = jj - midX, y = ii - midY;
+                    const float sigma = 1;
+                    const long double g = 1.0 / (2.0 * PI * sigma) * std::exp(-(x * x + y * y) / (2 * sigma));   // :80, exp(float)
+                    acc[0] += g * p[0];
+                    acc[1] += g * p[1];
+                    acc[2] += g * p[2];
+                }
+            float *r = low + 4 * ((size_t)i * lrw + j);
+            r[0] = (float)acc[0];                                              // setPixel, FIT_RGBF (:118-124): red = value[0],
+            r[1] = (float)acc[2];                                              // green = value[2],
+            r[2] = (float)acc[1];                                              // blue = value[1]
+        }
 }
 
 }  // namespace
@@ -957,6 +1001,91 @@ mr_status mr_shade_lights(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hit
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_shade_lights(s->dev, s->lights.data(), (uint32_t)s->lights.size(), d_rays, d_hits, d_weights, d_pixels, n, spp,
                                flags, d_rgb, d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_scene_set_environment(mr_scene *s, const mr_environment_desc *env) {
+    if (!s) return fail(MR_ERR_INVALID, "mr_scene_set_environment: NULL scene");
+    HostEnvironment e;
+    if (env) {
+        for (int k = 0; k < 6; k++)
+            if (env->reserved[k] != 0) return fail(MR_ERR_INVALID, "mr_environment_desc.reserved must be 0");
+        for (int c = 0; c < 3; c++)
+            if (!std::isfinite(env->bg_color[c])) return fail(MR_ERR_INVALID, "environment: bg_color must be finite");
+        if (!std::isfinite(env->rotation[0]) || !std::isfinite(env->rotation[1])) return fail(MR_ERR_INVALID, "environment: rotation must be finite");
+        // beyond these ranges the reference's lookup indexes outside its bitmap (phi is folded back by 2 PI once only)
+        if (!(env->rotation[0] >= 0.0f && env->rotation[0] <= 6.2831853071795864769f))
+            return fail(MR_ERR_INVALID, "environment: rotation[0] = %g is outside [0, 2 pi]", (double)env->rotation[0]);
+        if (!(env->rotation[1] >= 0.0f && env->rotation[1] <= 1.5707963267948966192f))
+            return fail(MR_ERR_INVALID, "environment: rotation[1] = %g is outside [0, pi / 2]", (double)env->rotation[1]);
+        for (int c = 0; c < 3; c++) e.bg[c] = env->bg_color[c];
+        e.rot[0] = env->rotation[0]; e.rot[1] = env->rotation[1];
+        if (env->pixels) {
+            const uint32_t W = env->W, H = env->H;
+            if (W < kEnvLowresWidth) return fail(MR_ERR_INVALID, "environment: image width %u, at least %u (the low-res image's)", W, kEnvLowresWidth);
+            if (W > 65536u || H > 65536u) return fail(MR_ERR_INVALID, "environment: image of %u x %u pixels, at most 65536 each way", W, H);
+            const int lrh = (int)((float)kEnvLowresWidth * ((float)H / (float)W));                   // Texture.cpp:53
+            if (lrh < 1) return fail(MR_ERR_INVALID, "environment: image height %u gives a low-res image of height 0", H);
+            if ((uint32_t)lrh > kEnvMaxLowresHeight) return fail(MR_ERR_INVALID, "environment: image height %u is more than 4 x its width %u", H, W);
+            const size_t n = 3 * (size_t)W * H;
+            for (size_t i = 0; i < n; i++)
+                if (!std::isfinite(env->pixels[i])) return fail(MR_ERR_INVALID, "environment: pixel value %zu is not finite", i);
+            e.W = W; e.H = H; e.lw = kEnvLowresWidth; e.lh = (uint32_t)lrh;
+            build_environment_image(e, env->pixels);
+        }
+    }
+    s->env = std::move(e);
+    s->env_dirty = s->env.W != 0;
+    return MR_OK;
+}
+
+mr_status mr_scene_get_environment(const mr_scene *s, uint32_t which, uint32_t *W, uint32_t *H, float *max_intensity, float *pixels) {
+    if (!s) return fail(MR_ERR_INVALID, "mr_scene_get_environment: NULL scene");
+    if (which > 1) return fail(MR_ERR_INVALID, "mr_scene_get_environment: which = %u (0: the image, 1: the low-res image)", which);
+    const HostEnvironment &e = s->env;
+    const uint32_t w = which ? e.lw : e.W, h = which ? e.lh : e.H;
+    if (W) *W = w;
+    if (H) *H = h;
+    if (max_intensity) *max_intensity = e.max_intensity;
+    if (pixels) {
+        const float *r = e.rec.data() + (which ? 4 * (size_t)e.W * e.H : 0);
+        for (size_t i = 0; i < (size_t)w * h; i++)
+            for (int c = 0; c < 3; c++) pixels[3 * i + c] = r[4 * i + c];
+    }
+    return MR_OK;
+}
+
+mr_status mr_shade_environment(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels,
+                               const uint8_t *d_lowres, uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb,
+                               uint64_t *d_counts, void *stream) {
+    mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (!d_rays || !d_hits || (!d_rgb && !d_ray_rgb)) return fail(MR_ERR_INVALID, "NULL argument");
+    if (spp == 0) return fail(MR_ERR_INVALID, "spp is 0");
+    if (n / spp > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "too many pixels");
+    if (flags & ~(uint32_t)MR_ENV_LOWRES) return fail(MR_ERR_INVALID, "mr_shade_environment: flags may hold MR_ENV_LOWRES only");
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_weights) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_pixels) & 3))
+        return fail(MR_ERR_INVALID, "ray / hit buffers must be 16-byte aligned, counters 8-byte aligned");
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    const HostEnvironment &e = s->env;
+    if (s->env_dirty) {                        // the texel records, on this call's stream (e.rec stays until the next change)
+        (void)hipFree(s->d_env);
+        s->d_env = nullptr;
+        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&s->d_env), e.rec.size() * sizeof(float)));
+        MR_HIP_CHECK(hipMemcpyAsync(s->d_env, e.rec.data(), e.rec.size() * sizeof(float), hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
+        s->env_dirty = false;
+    }
+    EnvParams p = {};
+    if (e.W) {
+        p.full = s->d_env; p.low = s->d_env + (size_t)e.W * e.H;
+        p.W = e.W; p.H = e.H; p.lw = e.lw; p.lh = e.lh;
+        p.max_intensity = e.max_intensity;
+    }
+    p.rot[0] = e.rot[0]; p.rot[1] = e.rot[1];
+    for (int c = 0; c < 3; c++) p.bg[c] = e.bg[c];
+    return launch_shade_environment(p, d_rays, d_hits, d_weights, d_pixels, d_lowres, n, spp, flags, d_rgb, d_ray_rgb,
+                                    reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_tonemap(mr_scene *s, const float *d_rgb, uint64_t n_values, uint8_t *d_out, void *stream) {

@@ -224,6 +224,28 @@ mr_status launch_shade_lights(const DeviceScene &ds, const ShadeLight *lights, u
                               uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts,
                               hipStream_t stream);
 
+// The environment of rays that miss (mr_environment.hip; Scene::getEnvironmentMap, Scene.cpp:657-688).  The host copy is what
+// mr_scene_set_environment made of the caller's image (LoadedTexture::LoadedTexture, Texture.cpp:30-92); the device copy holds
+// one 16-byte record (r, g, b, 0) per texel, full image then low-res image, so that a texel fetch is one dwordx4.
+struct HostEnvironment {
+    float bg[3] = {0.f, 0.f, 0.f};
+    float rot[2] = {0.f, 0.f};
+    uint32_t W = 0, H = 0, lw = 0, lh = 0;     // W == 0: no image (m_environment = 0)
+    float max_intensity = 0.f;
+    std::vector<float> rec;                    // (r, g, b, 0) per texel: W * H of the image, then lw * lh of the low-res image
+                                               // as setPixel stored it (green and blue exchanged); what the device copy holds
+};
+struct EnvParams {                             // the environment as the kernel takes it
+    const float4 *full, *low;                  // nullptr: colour only
+    uint32_t W, H, lw, lh;
+    float rot[2], max_intensity, bg[3];
+};
+constexpr uint32_t kEnvLowresWidth = 24;       // LoadedTexture::LOWRES_WIDTH (Texture.h:297)
+constexpr uint32_t kEnvMaxLowresHeight = 96;   // H <= 4 W: the low-res image (at most 36 KB) is staged in LDS
+mr_status launch_shade_environment(const EnvParams &env, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
+                                   const uint32_t *d_pixels, const uint8_t *d_lowres, unsigned long long n, uint32_t spp,
+                                   uint32_t flags, float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts, hipStream_t stream);
+
 // photon map on the device: three float4 planes in kd-tree heap order, 1-based (children of i: 2i, 2i+1)
 struct PhotonMapDev {
     float4 *rec = nullptr;        // two per photon, one 32-byte record: (x, y, z, split axis as int bits), then the incoming
@@ -309,4 +331,9 @@ struct mr_scene {
     std::vector<uint32_t> prim_material;   // empty: material 0 everywhere
     // Scene::lights() for mr_shade_lights (host only: the list travels in the kernel arguments), at most MR_MAX_LIGHTS
     std::vector<mr::ShadeLight> lights;
+    // Scene::m_environment / m_bgColor / m_environmentRotation for mr_shade_environment.  d_env: the texel records on the
+    // device (full image, then low-res), uploaded by the first shade call after a change (env_dirty)
+    mr::HostEnvironment env;
+    float4 *d_env = nullptr;
+    bool env_dirty = false;
 };

@@ -296,9 +296,30 @@ private:
     int m_device;
 };
 
-// Scene (Scene.h:14-73), intersection part: addObject, preCalc -> BVH::build, trace.
+// Texture (Texture.h:58-71) as far as Scene::setEnvironment needs it, and LoadedTexture (Texture.h:277-299) as a data
+// carrier: there is no image decoder here, so it is constructed from the float pixels FreeImage would have loaded
+// (FIT_RGBF; w * h * 3 floats, row y = scanline y, row 0 = the bottom of the picture) instead of from a file name.  The
+// constructor's work (m_maxIntensity, the low-res image, Texture.cpp:30-92) is done by mr_scene_set_environment.
+class Texture {
+public:
+    virtual ~Texture() {}
+};
+class LoadedTexture : public Texture {
+public:
+    LoadedTexture(const float *pixels, int w, int h) : m_pixels(pixels, pixels + 3 * (size_t)w * (size_t)h), m_w(w), m_h(h) {}
+    const float *pixels() const { return m_pixels.data(); }
+    int width() const { return m_w; }
+    int height() const { return m_h; }
+private:
+    std::vector<float> m_pixels;
+    int m_w, m_h;
+};
+
+// Scene (Scene.h:14-73), intersection part: addObject, preCalc -> BVH::build, trace; and what a ray that leaves the scene is
+// worth (setBgColor / setEnvironment / setEnvironmentRotation, Scene.h:46-51 -> mr_scene_set_environment).
 class Scene {
 public:
+    Scene() : m_environment(0), m_bgColor(0.0f), m_rotPhi(0.0f), m_rotTheta(0.0f) {}       // Scene.h:17-18
     void addObject(Object *pObj) {                        // Scene.h:20-25
         if (pObj->isBounded()) m_objects.push_back(pObj);
         else m_unboundedObjects.push_back(pObj);
@@ -306,7 +327,19 @@ public:
     const Objects *objects() const { return &m_objects; }
     const Objects *unboundedObjects() const { return &m_unboundedObjects; }
     void setDevice(int device) { m_bvh.setDevice(device); }
-    void preCalc() { m_bvh.setUnbounded(&m_unboundedObjects); m_bvh.build(&m_objects); }   // Scene.cpp:50-84, the BVH part (:72)
+    void preCalc() {                                      // Scene.cpp:50-84, the BVH part (:72)
+        m_bvh.setUnbounded(&m_unboundedObjects);
+        m_bvh.build(&m_objects);
+        applyEnvironment();
+    }
+
+    // Scene.h:46-51.  May be called before or after preCalc(); the scene keeps the pointer, as the reference does, and
+    // the library copies the pixels.  Only LoadedTexture environments exist here; 0 = none (m_bgColor is used).
+    void setEnvironment(Texture *environment) { m_environment = environment; applyEnvironment(); }
+    void setBgColor(Vector3 color) { m_bgColor = color; applyEnvironment(); }
+    void setEnvironmentRotation(float phi, float theta) { m_rotPhi = phi; m_rotTheta = theta; applyEnvironment(); }
+    // Scene::getEnvironmentMap for the misses of a traced batch, on the device: see mr_shade_environment
+    mr_scene *handle() const { return m_bvh.handle(); }
 
     bool trace(HitInfo &minHit, const Ray &ray, float tMin = 0.0f, float tMax = MIRO_TMAX) const {   // Scene.cpp:214
         bool hit = false;
@@ -326,8 +359,23 @@ public:
     const BVH &bvh() const { return m_bvh; }
 
 private:
+    void applyEnvironment() {
+        if (!m_bvh.handle()) return;                      // before preCalc(): applied there
+        mr_environment_desc d = mr_environment_desc();
+        d.bg_color[0] = m_bgColor.x; d.bg_color[1] = m_bgColor.y; d.bg_color[2] = m_bgColor.z;
+        d.rotation[0] = m_rotPhi; d.rotation[1] = m_rotTheta;
+        if (m_environment) {
+            const LoadedTexture *t = dynamic_cast<const LoadedTexture *>(m_environment);
+            if (!t) throw MiroHipError(MR_ERR_INVALID, "the environment must be a LoadedTexture");
+            d.pixels = t->pixels(); d.W = (uint32_t)t->width(); d.H = (uint32_t)t->height();
+        }
+        check(mr_scene_set_environment(m_bvh.handle(), &d));
+    }
     Objects m_objects, m_unboundedObjects;
     BVH m_bvh;
+    Texture *m_environment;
+    Vector3 m_bgColor;
+    float m_rotPhi, m_rotTheta;
 };
 
 }  // namespace miro

@@ -30,6 +30,8 @@ MR_PATH_MIRROR, MR_PATH_REFRACT, MR_PATH_DIFFUSE = 1, 2, 4
 MR_LEVEL_LAST, MR_LEVEL_SPECULAR, MR_LEVEL_PATH = 0, 1, 2
 MR_LAYOUT_DFS, MR_LAYOUT_PAIRS, MR_LAYOUT_TREELETS, MR_LAYOUT_ALIGN_LEAVES = 0, 1, 2, 16
 
+MR_ENV_LOWRES = 1 << 16
+
 MR_LIGHT_POINT, MR_LIGHT_DISC = 0, 1
 MR_MAX_LIGHTS = 8
 
@@ -49,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "mr_final_gather",
     "mr_trace_photons", "mr_trace_photons_timing",
     "mr_scene_set_lights", "mr_shade_lights",
+    "mr_scene_set_environment", "mr_scene_get_environment", "mr_shade_environment",
     "mr_last_error", "mr_version",
 ]
 
@@ -135,6 +138,12 @@ def light_desc(light):
         ld.normal[:] = light["normal"]
         ld.radius = light["radius"]
     return ld
+
+
+class EnvironmentDesc(C.Structure):
+    """mr_environment_desc (miro_hip.h): Scene::setBgColor / setEnvironment / setEnvironmentRotation"""
+    _fields_ = [("bg_color", C.c_float * 3), ("pixels", C.POINTER(C.c_float)), ("W", C.c_uint32), ("H", C.c_uint32),
+                ("rotation", C.c_float * 2), ("reserved", C.c_uint32 * 6)]
 
 
 class PhotonTraceDesc(C.Structure):
@@ -224,6 +233,9 @@ def load_library(path=None):
     L.mr_trace_photons_timing.argtypes = [C.POINTER(C.c_double)] * 3
     L.mr_scene_set_lights.argtypes = [vp, C.POINTER(LightDesc), C.c_uint32]
     L.mr_shade_lights.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.mr_scene_set_environment.argtypes = [vp, C.POINTER(EnvironmentDesc)]
+    L.mr_scene_get_environment.argtypes = [vp, C.c_uint32, u32p, u32p, f32p, f32p]
+    L.mr_shade_environment.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.mr_photon_map_create.argtypes = [C.c_int32, C.c_uint32, C.POINTER(vp)]
     L.mr_photon_map_destroy.argtypes = [vp]
     L.mr_photon_map_store.argtypes = [vp, C.c_uint32, f32p, f32p, f32p]
@@ -633,6 +645,47 @@ class Scene:
             return t.data_ptr() if t is not None else None
         _check(self.L.mr_shade_lights(self.h, d_rays.data_ptr(), d_hits.data_ptr(), ptr(d_weights), ptr(d_pixels), n, spp, flags,
                                       ptr(d_rgb), ptr(d_ray_rgb), ptr(d_counts), _stream_ptr(stream)))
+
+    def set_environment(self, bg_color=(0.0, 0.0, 0.0), pixels=None, rotation=(0.0, 0.0)):
+        """mr_scene_set_environment: Scene::setBgColor, Scene::setEnvironment (pixels: a float image [H, W, 3], row 0 = the
+        bottom scanline, as FreeImage keeps it; None = no image, every miss is bg_color) and setEnvironmentRotation(phi, theta).
+        set_environment() with no argument restores the default (a miss is worth 0)."""
+        d = EnvironmentDesc()
+        d.bg_color[:] = bg_color
+        d.rotation[:] = rotation
+        px = None
+        if pixels is not None:
+            px = np.ascontiguousarray(pixels, dtype=np.float32)
+            if px.ndim != 3 or px.shape[2] != 3:
+                raise ValueError("set_environment: pixels must have the shape [H, W, 3]")
+            d.H, d.W = px.shape[0], px.shape[1]
+            d.pixels = _f32p(px)
+        _check(self.L.mr_scene_set_environment(self.h, C.byref(d)))
+
+    def clear_environment(self):
+        """mr_scene_set_environment(NULL): back to the default"""
+        _check(self.L.mr_scene_set_environment(self.h, None))
+
+    def get_environment(self, which=0):
+        """mr_scene_get_environment: (pixels [H, W, 3] float32, max_intensity) of the image (which = 0) or of the low-res image
+        as stored, green and blue exchanged (which = 1); (None, 0.0) without an image."""
+        W, H, mx = C.c_uint32(), C.c_uint32(), C.c_float()
+        _check(self.L.mr_scene_get_environment(self.h, which, C.byref(W), C.byref(H), C.byref(mx), None))
+        if W.value == 0:
+            return None, mx.value
+        px = np.empty((H.value, W.value, 3), np.float32)
+        _check(self.L.mr_scene_get_environment(self.h, which, None, None, None, _f32p(px)))
+        return px, mx.value
+
+    def shade_environment(self, d_rays, d_hits, n, d_rgb=None, d_weights=None, d_pixels=None, d_lowres=None, spp=1, flags=0,
+                          d_ray_rgb=None, d_counts=None, stream=None):
+        """mr_shade_environment: Scene::getEnvironmentMap for every ray of a traced batch that missed; weight * value / spp is
+        added to d_rgb[pixel], the un-weighted value of every ray written to d_ray_rgb (either may be None, not both).
+        d_lowres: uint8 per ray, non-zero = the low-res image (ray.isDiffuse); flags: MR_ENV_LOWRES for all rays."""
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        _check(self.L.mr_shade_environment(self.h, d_rays.data_ptr(), d_hits.data_ptr(), ptr(d_weights), ptr(d_pixels), ptr(d_lowres),
+                                           n, spp, flags, ptr(d_rgb), ptr(d_ray_rgb), ptr(d_counts), _stream_ptr(stream)))
 
     def tonemap(self, d_rgb, n_values, d_out, stream=None):
         _check(self.L.mr_tonemap(self.h, d_rgb.data_ptr(), n_values, d_out.data_ptr(), _stream_ptr(stream)))

@@ -291,7 +291,7 @@ class FrameRenderer:
         return g
 
     def render_specular(self, depth=10, stream=None, path_tracing=False, path_seed=168, path_kinds=None, fused=False,
-                        group_octants=False, lights=None):
+                        group_octants=False, lights=None, environment=None):
         """Scene::traceScene with reflective / refractive materials (Scene.cpp:270-346) as wavefront bounces: every
         level traces its queue, shades it (weight x Phong::shade added to the ray's pixel), and emits the reflect /
         Fresnel / refract children of the next level by ballot compaction.  depth = TRACE_DEPTH (Miro.h:13): rays are
@@ -310,8 +310,31 @@ class FrameRenderer:
         lights: a light list (binding.LightDesc objects or the dicts of scenes.py, point and disc lights) instead of the
         description's single point light: it becomes the scene's list (Scene.set_lights) and every level is trace ->
         mr_shade_lights -> the generators, three launches without shadow-ray buffers.  The first level's hits stay in d_hits
-        (final_gather works on them).  `fused` must be falsy: mr_trace_level keeps its single point light."""
+        (final_gather works on them).  `fused` must be falsy: mr_trace_level keeps its single point light.
+        environment: what a ray that leaves the scene is worth (Scene::getEnvironmentMap, Scene.cpp:338-342,657-688): a dict
+        with bg_color / pixels / rotation (the arguments of Scene.set_environment; it becomes the scene's), or True for the
+        environment the scene already has.  Every level, the last one included (traceScene at depth 0 still traces and
+        still returns the environment), then calls mr_shade_environment on its queue after tracing it.  `fused` must be
+        falsy: mr_trace_level keeps no hit records.  The low-res image (the reference's ray.isDiffuse) is used for every level
+        after the first when path_kinds == MR_PATH_DIFFUSE and never for specular children; with an IMAGE, MR_PATH_DIFFUSE
+        mixed with other kinds is refused (the child queue does not record which child came from Ray::random).  None: a miss
+        is worth 0 and no launch is added."""
         sc, L, W = self.scene, self.desc["light"], self.desc["wattage"]
+        if environment is not None and environment is not False:
+            if fused:
+                raise ValueError("render_specular: an environment needs fused=False (mr_trace_level keeps no hit records)")
+            if environment is not True:
+                sc.set_environment(**environment)
+            has_image = sc.get_environment(0)[0] is not None
+            kinds = binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT if path_kinds is None else path_kinds
+            diffuse_children = path_tracing and bool(kinds & binding.MR_PATH_DIFFUSE)
+            if has_image and diffuse_children and kinds != binding.MR_PATH_DIFFUSE:
+                raise ValueError("render_specular: an environment image with MR_PATH_DIFFUSE mixed with other kinds "
+                                 "(the queue does not record which child came from Ray::random)")
+            env_lowres = binding.MR_ENV_LOWRES if diffuse_children and kinds == binding.MR_PATH_DIFFUSE else 0
+            environment = True
+        else:
+            environment = False
         if lights is not None:
             if fused:
                 raise ValueError("render_specular: a light list needs fused=False (mr_trace_level shades by one point light)")
@@ -322,7 +345,8 @@ class FrameRenderer:
             raise TypeError("render_specular: pass a torch.cuda.Stream (or None for the current stream), not a raw handle")
         if stream is not None and stream != torch.cuda.current_stream(self.device):
             with torch.cuda.stream(stream):
-                return self.render_specular(depth, stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights)
+                return self.render_specular(depth, stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights,
+                                            environment or None)
         self.d_slots.zero_()
         if path_kinds is None:
             path_kinds = binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT
@@ -381,6 +405,9 @@ class FrameRenderer:
                 sc.trace_grouped(rays, n, hits, order, self.flags & binding.MR_MATH_PRODUCT, d_octants=octs, stream=stream)
             else:
                 sc.trace_device(rays, n, hits, fl, stream=stream)
+            if environment:
+                sc.shade_environment(rays, hits, n, self.d_slots, d_weights=weights, d_pixels=pixels, spp=self.spp,
+                                     flags=env_lowres if level > 0 else 0, stream=stream)
             if lights is not None:
                 sc.shade_lights(rays, hits, n, self.d_slots, d_weights=weights, d_pixels=pixels, spp=self.spp,
                                 flags=fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT), d_counts=cnt, stream=stream)

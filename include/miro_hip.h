@@ -431,6 +431,74 @@ mr_status mr_shade_lights(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d
                           const uint32_t *d_pixels, uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb,
                           uint64_t *d_counts, void *stream);
 
+/* ---- the environment of rays that MISS: Scene::getEnvironmentMap (Scene.cpp:338-342,657-688) ------------------------------
+ * Scene::traceScene ends a ray that leaves the scene with shadeResult = getEnvironmentMap(ray), which its parent multiplies by
+ * the reflection / refraction factor like any child result.  getEnvironmentMap returns m_bgColor (Scene::setBgColor, default 0)
+ * or, with an image (Scene::setEnvironment(new LoadedTexture(...)), setEnvironmentRotation, assignment3.cpp:50-52), a bilinear
+ * lookup into the lat-long image: the full image for ordinary rays, the 24-texel-wide blurred copy the LoadedTexture
+ * constructor builds (Texture.cpp:52-91) for rays made by Ray::random (ray.isDiffuse).  Without mr_scene_set_environment
+ * (m_environment = 0, m_bgColor = 0) a miss is worth 0, which is what every other entry point assumes: only
+ * mr_shade_environment reads the environment.
+ *
+ * mr_scene_set_environment -- host only (works on a host_only scene and without a device), before or after mr_bvh_build;
+ * copies the image; env == NULL restores the default.  The device copy is made by the first mr_shade_environment after a
+ * change, on that call's stream.  pixels: a float RGB image (FreeImage's FIT_RGBF; 8-bit FIT_BITMAP images are not
+ * supported), W * H * 3 floats, row y = FreeImage scanline y (row 0 is the BOTTOM row of the picture).  The call reproduces
+ * LoadedTexture::LoadedTexture (Texture.cpp:30-92) as written:
+ *   - m_maxIntensity = the maximum over all channels of all pixels, starting from -1e15.
+ *   - the low-res image: width 24, height lrh = (int)(24.0f * ((float)H / (float)W)); texel (j, i) is the UN-NORMALISED
+ *     Gaussian-weighted sum over its block of (W / 24) x (H / lrh) pixels (integer divisions), sigma = 1, centred on the
+ *     block's middle pixel: weight 1.0 / (2.0 * PI * sigma) * exp(float), accumulated in long double (it is no average: the
+ *     weights of a block sum to about 1 only because sigma = 1).
+ *   - the texel is stored through setPixel's FIT_RGBF arm (Texture.cpp:118-124), which EXCHANGES GREEN AND BLUE: the
+ *     low-res image holds (r, b, g).
+ * Errors (MR_ERR_INVALID, the earlier environment stays): NULL scene, a non-zero reserved word, a non-finite bg_color /
+ * rotation / pixel, pixels with W < 24, with a low-res height of 0 or with H > 4 W (the low-res image is kept in LDS),
+ * rotation[0] outside [0, 2 pi] or rotation[1] outside [0, pi / 2] (beyond them the reference's lookup leaves its bitmap).
+ *
+ * mr_scene_get_environment -- which = 0: the image as given, 1: the low-res image as stored (green and blue exchanged).
+ * *W, *H, *max_intensity (any may be NULL) and, when pixels != NULL, W * H * 3 floats.  Without an image: W = H = 0,
+ * max_intensity = 0.
+ *
+ * mr_shade_environment -- for n traced rays: every ray whose hit record is a MISS takes value = getEnvironmentMap(ray) and
+ * adds weight * value / spp to d_rgb[pixel] exactly as mr_shade_accumulate does (d_weights NULL = 1, d_pixels NULL = ray
+ * index / spp, float atomics); rays with a hit contribute nothing.  The lookup (Scene.cpp:664-681, Texture.cpp:161-185), every
+ * operation in fp32 in the reference's order, with atan2 / asin from miro_math.h (the same bits in a host checker):
+ *     phi = atan2(d.x, d.z) + rot[0] + PI;   theta = asin(d.y) + rot[1];
+ *     if (theta > PI / 2) { phi += PI; theta -= 2 * (theta - PI / 2); }      if (phi > 2 PI) phi -= 2 PI;   (once)
+ *     u = phi / (2 PI);   v = theta / PI + 0.5;
+ *     px = (float)w * u;   x1 = (int)px;  x2 = x1 + 1;  x1 %= w;  x2 %= w;   x1_error = px - (float)x1;    (the same in y)
+ *     f = (p(x1,y1) * (1 - x1_error) + p(x2,y1) * x1_error) * (1 - y1_error) + (p(x1,y2) * (1 - x1_error) + p(x2,y2) * x1_error) * y1_error
+ *     value = min(powf(f / max_intensity, 0.5f) * 1.5f, 1.0f) per channel   (std::min: a NaN stays a NaN)
+ *   x1_error is taken from the WRAPPED x1: at u == 1 (or v == 1) the index wraps to 0, the error term is w (or h) and the
+ *   blend extrapolates -- reproduced.  Where the reference's arithmetic leaves the image -- u or v not finite (a direction
+ *   whose |y| exceeds 1 by an ulp: asin gives NaN), an index beyond int, a negative index -- its behaviour is undefined;
+ *   here such a lookup is DEFINED as 0 and counted.
+ * The low-res image is used for ray i when flags & MR_ENV_LOWRES or d_lowres && d_lowres[i] (the reference's ray.isDiffuse).
+ * Without an image every miss yields bg_color; without any environment the call is valid and adds nothing.
+ * d_ray_rgb (may be NULL): 3n floats, the un-weighted value of every ray, 0 for a hit; deterministic.  d_rgb may be NULL when
+ *   d_ray_rgb is given.
+ * d_counts (may be NULL): [0] += misses shaded, [1] += undefined lookups; not zeroed by the call.
+ * flags: MR_ENV_LOWRES only.
+ * With device buffers the call only enqueues on `stream`; once the device copy of the image exists (after one call) it can be
+ * captured into a HIP graph.  One mr_scene_set_environment at a time, and none while a shade call is in flight.
+ * Errors: NULL scene / rays / hits, both outputs NULL, spp == 0, other flags, misaligned buffers: MR_ERR_INVALID; a scene that
+ *   is not built or was built host_only: MR_ERR_STATE. */
+typedef struct mr_environment_desc {
+    float bg_color[3];            /* Scene::setBgColor; used when pixels == NULL */
+    const float *pixels;          /* host, W*H*3 floats, row y = FreeImage scanline y (row 0 = bottom), or NULL */
+    uint32_t W, H;
+    float rotation[2];            /* setEnvironmentRotation(phi, theta) */
+    uint32_t reserved[6];         /* must be 0 */
+} mr_environment_desc;
+enum { MR_ENV_LOWRES = 1u << 16 };
+mr_status mr_scene_set_environment(mr_scene *scene, const mr_environment_desc *env);
+mr_status mr_scene_get_environment(const mr_scene *scene, uint32_t which, uint32_t *W, uint32_t *H, float *max_intensity,
+                                   float *pixels);
+mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
+                               const uint32_t *d_pixels, const uint8_t *d_lowres, uint64_t n, uint32_t spp, uint32_t flags,
+                               float *d_rgb, float *d_ray_rgb, uint64_t *d_counts, void *stream);
+
 /* sigmoid(6v-3) tone map + 8-bit quantisation (Scene.cpp:87-91,177-202; Image.cpp:44-50) */
 mr_status mr_tonemap(mr_scene *scene, const float *d_rgb, uint64_t n_values, uint8_t *d_out, void *stream);
 

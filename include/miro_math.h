@@ -1,6 +1,7 @@
 /*
  * miro_math.h -- the transcendental functions of the reference's path-tracing ray generators (Ray::random, and the
  * PATH_TRACING branches of Ray::reflect / Ray::refract, Ray.h:124-158,235-239; alignHemisphereToVector, Utility.h:34-50)
+ * and of the environment lookup (atan2 and asin of the ray direction, Scene::getEnvironmentMap, Scene.cpp:665-666)
  * as ONE deterministic implementation for every side that has to agree bit for bit.
  *
  * The reference calls libm's float functions (asinf, acosf, sinf, cosf, powf through <cmath>); their last bit is not
@@ -164,6 +165,38 @@ MM_FN double mm_exp(double z) {
     return p * scale;
 }
 
+/* atan(t), 0 <= t <= 1: above tan(pi/8) atan t = pi/4 + atan((t-1)/(t+1)), whose argument lies in [-tan(pi/8), 0]; then the
+ * Taylor series atan s = s * sum (-1)^k s^2k / (2k+1) to k = 23 for |s| <= 0.4143 (next term < 1e-20). */
+MM_FN double mm_atan01(double t) {
+    static const double c[24] = {
+        1.0, -1.0 / 3.0, 1.0 / 5.0, -1.0 / 7.0, 1.0 / 9.0, -1.0 / 11.0, 1.0 / 13.0, -1.0 / 15.0, 1.0 / 17.0, -1.0 / 19.0,
+        1.0 / 21.0, -1.0 / 23.0, 1.0 / 25.0, -1.0 / 27.0, 1.0 / 29.0, -1.0 / 31.0, 1.0 / 33.0, -1.0 / 35.0, 1.0 / 37.0,
+        -1.0 / 39.0, 1.0 / 41.0, -1.0 / 43.0, 1.0 / 45.0, -1.0 / 47.0};
+    const int high = t > 0.41421356237309503;
+    const double s = high ? (t - 1.0) / (t + 1.0) : t;
+    const double z = s * s;
+    double p = c[23];
+    MM_NOUNROLL
+    for (int i = 22; i >= 0; i--) p = p * z + c[i];
+    const double a = s * p;
+    return high ? (0.5 * MM_PI_2_HI + a) + 0.5 * MM_PI_2_LO : a;
+}
+/* atan2(y, x) in double for float arguments, every case of C's atan2: signed zeros, the axes, infinities; NaN for a NaN */
+MM_FN double mm_atan2(double y, double x) {
+    uint64_t yb, xb;
+    memcpy(&yb, &y, 8);
+    memcpy(&xb, &x, 8);
+    const double ay = (yb >> 63) ? -y : y, ax = (xb >> 63) ? -x : x;   /* by the sign bit: |-0| = +0 */
+    if (!(ay == ay) || !(ax == ax)) return x + y;           /* NaN */
+    const double lo = ay < ax ? ay : ax, hi = ay < ax ? ax : ay;
+    double t = 0.0;                                         /* atan2(0, 0): the angle of (+-0, +-0) */
+    if (hi > 0.0) t = lo == hi ? 1.0 : lo / hi;             /* (inf, inf): the diagonal; finite / inf = 0 */
+    double a = mm_atan01(t);
+    if (ay > ax) a = (MM_PI_2_HI - a) + MM_PI_2_LO;
+    if (xb >> 63) a = (2.0 * MM_PI_2_HI - a) + 2.0 * MM_PI_2_LO;
+    return (yb >> 63) ? -a : a;
+}
+
 /* ---- the float functions the ray generators use (float in, float out, rounded once) ---------------------------- */
 MM_FN float mm_sinf(float x) { double s, c; mm_sincos((double)x, &s, &c); return (float)s; }
 MM_FN float mm_cosf(float x) { double s, c; mm_sincos((double)x, &s, &c); return (float)c; }
@@ -175,6 +208,17 @@ MM_FN float mm_acosf(float t) {
     if (t >= 0.0f) return (float)mm_acos01((double)t);
     return (float)((2.0 * MM_PI_2_HI - mm_acos01(-(double)t)) + 2.0 * MM_PI_2_LO);
 }
+/* asinf on [-1, 1], signed (asin(-t) = -asin(t), asinf(-0) = -0); NaN outside, as libm.  Scene::getEnvironmentMap's
+ * theta = asin(ray.d.y) (Scene.cpp:666): a direction whose y exceeds 1 by an ulp gives NaN there too. */
+MM_FN float mm_asinf(float t) {
+    if (!(t >= -1.0f && t <= 1.0f)) { uint32_t q = 0x7fc00000u; float f; memcpy(&f, &q, 4); return f; }
+    uint32_t b;
+    memcpy(&b, &t, 4);
+    const float r = (float)mm_asin01((b >> 31) ? -(double)t : (double)t);
+    return (b >> 31) ? -r : r;
+}
+/* atan2f(y, x): Scene::getEnvironmentMap's phi = atan2(ray.d.x, ray.d.z) (Scene.cpp:665) */
+MM_FN float mm_atan2f(float y, float x) { return (float)mm_atan2((double)y, (double)x); }
 /* powf(x, y) for 0 <= x <= 1, 0 <= y <= 1 (x = frand(), y = 1 / (1 + shininess)); powf(x, 0) = 1, powf(0, y > 0) = 0 */
 MM_FN float mm_powf01(float x, float y) {
     if (y == 0.0f) return 1.0f;
