@@ -13,6 +13,7 @@
 
 #include "mr_internal.h"
 #include "mr_launch.h"
+#include "mr_phong.h"
 #include "mr_recursion.h"
 
 namespace mr {
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void shade_accumulate_kernel(AccumArgs a) {
         float v[3] = {0.f, 0.f, 0.f};
         uint32_t pix = 0xFFFFFFFFu;
         if (k < a.n) {
-            pix = a.pixels ? a.pixels[k] : (uint32_t)(k / a.spp);
+            pix = pixel_of(a.pixels, k, a.spp);
             const float4 h = reinterpret_cast<const float4 *>(a.hits)[k];
             const uint32_t prim = __float_as_uint(h.y);
             const float scale = prim != MR_MISS ? a.light_scale[k] : 0.0f;                // a miss: m_bgColor = 0 contributes nothing
@@ -67,8 +68,8 @@ __global__ __launch_bounds__(kBlock) void shade_accumulate_kernel(AccumArgs a) {
                 const float4 rb = reinterpret_cast<const float4 *>(a.rays)[2 * k + 1];
                 phong_terms(a.lt, material_of(a.m, prim), P, N, rb.x, rb.y, rb.z, diffuse, highlight);
                 phong_combine(diffuse, highlight, scale, out);
-                float w[3] = {1.f, 1.f, 1.f};
-                if (a.weights) { w[0] = a.weights[3 * k]; w[1] = a.weights[3 * k + 1]; w[2] = a.weights[3 * k + 2]; }
+                float w[3];
+                weight_of(a.weights, k, w);
                 for (int c = 0; c < 3; c++) v[c] = out[c] * w[c] * a.inv_spp;
             }
         }
@@ -212,9 +213,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATH ? M
                 surface_point(a.m, a.rays, k, h, g.P, g.N);
                 const float4 rb = reinterpret_cast<const float4 *>(a.rays)[2 * k + 1];
                 g.d[0] = rb.x; g.d[1] = rb.y; g.d[2] = rb.z;
-                g.w0[0] = g.w0[1] = g.w0[2] = 1.f;
-                if (a.weights) { g.w0[0] = a.weights[3 * k]; g.w0[1] = a.weights[3 * k + 1]; g.w0[2] = a.weights[3 * k + 2]; }
-                const uint32_t pix = a.pixels ? a.pixels[k] : (uint32_t)(k / a.spp);
+                weight_of(a.weights, k, g.w0);
+                const uint32_t pix = pixel_of(a.pixels, k, a.spp);
                 uint32_t id = 0;
                 if (PATH) {
                     id = a.ids ? a.ids[k] : (uint32_t)k;
@@ -243,8 +243,7 @@ mr_status launch_shade_accumulate(const DeviceScene &ds, const mr_ray *d_rays, c
     MR_HIP_CHECK(hipGetLastError());
     AccumArgs a;
     a.m = m; a.rays = d_rays; a.hits = d_hits; a.weights = d_weights; a.pixels = d_pixels; a.light_scale = d_light_scale;
-    for (int c = 0; c < 3; c++) { a.lt.L[c] = light.position[c]; a.lt.color[c] = light.color[c]; }
-    a.lt.wattage = light.wattage; a.spp = spp; a.inv_spp = 1.0f / (float)spp; a.n = n; a.rgb = d_rgb;
+    a.lt = light_args_of(light); a.spp = spp; a.inv_spp = 1.0f / (float)spp; a.n = n; a.rgb = d_rgb;
     hipLaunchKernelGGL(shade_accumulate_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;

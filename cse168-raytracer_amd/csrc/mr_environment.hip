@@ -26,6 +26,7 @@
 #include "mr_internal.h"
 #include "mr_launch.h"
 #include "mr_recursion.h"
+#include "mr_traverse.h"
 
 namespace mr {
 namespace {
@@ -82,8 +83,9 @@ __device__ __forceinline__ float env_blend(float p11, float p21, float p12, floa
 template <bool IMAGE, bool WEIGHTS, bool PIXELS>
 __global__ __launch_bounds__(kBlock) void shade_environment_kernel(EnvArgs a) {
     extern __shared__ float4 s_low[];                 // IMAGE: the low-res image, lw * lh records
-    __shared__ unsigned s_counts[2][kBlock / 64];
     const int tid = threadIdx.x;
+    __builtin_assume(!PIXELS || a.pixels != nullptr);     // what launch_env_i chose the variant by
+    __builtin_assume(!WEIGHTS || a.weights != nullptr);
     const bool any_lowres = IMAGE && (a.all_lowres || a.lowres);
     if (any_lowres) {
         const unsigned n_low = a.env.lw * a.env.lh;
@@ -135,10 +137,10 @@ __global__ __launch_bounds__(kBlock) void shade_environment_kernel(EnvArgs a) {
         if (a.rgb) {                                                    // wave-uniform
             uint32_t pix = 0xFFFFFFFFu;
             float o[3] = {0.f, 0.f, 0.f};
-            if (live) pix = PIXELS ? a.pixels[k] : (uint32_t)(k / a.spp);
+            if (live) pix = rec::pixel_of(PIXELS ? a.pixels : nullptr, k, a.spp);
             if (miss) {
-                float wt[3] = {1.f, 1.f, 1.f};
-                if (WEIGHTS) { wt[0] = a.weights[3 * k]; wt[1] = a.weights[3 * k + 1]; wt[2] = a.weights[3 * k + 2]; }
+                float wt[3];
+                rec::weight_of(WEIGHTS ? a.weights : nullptr, k, wt);
                 for (int c = 0; c < 3; c++) o[c] = val[c] * wt[c] * a.inv_spp;
             }
             rec::accumulate_runs(a.rgb, pix, o[0], o[1], o[2]);
@@ -146,15 +148,8 @@ __global__ __launch_bounds__(kBlock) void shade_environment_kernel(EnvArgs a) {
     }
 
     if (a.counts) {
-        unsigned m = my_misses, ud = my_undefined;
-        for (int off = 32; off > 0; off >>= 1) { m += __shfl_down(m, off, 64); ud += __shfl_down(ud, off, 64); }
-        if ((tid & 63) == 0) { s_counts[0][tid >> 6] = m; s_counts[1][tid >> 6] = ud; }
-        __syncthreads();
-        if (tid < 2) {
-            unsigned long long tot = 0;
-            for (int j = 0; j < kBlock / 64; j++) tot += s_counts[tid][j];
-            if (tot) atomicAdd(&a.counts[tid], tot);
-        }
+        const unsigned mine[2] = {my_misses, my_undefined};
+        workgroup_add<kBlock>(mine, a.counts);
     }
 }
 

@@ -157,7 +157,7 @@ inline FrameShape frame_schedule(unsigned long long chunks) {
 // (Phong.cpp:91), BASELINE config 2's "primary rays only".
 // MAT: Phong::shade with the scene's per-object materials (mr_scene_set_materials) instead of the frame's uniform one:
 // diffuse term and highlight from the hit's material (Phong.cpp:116-156) and light through a refractive occluder scaled by
-// dot(N, l) of the occluder (Phong.cpp:99-113) -- the pieces of mr_recursion.h that mr_trace_level shades with.
+// dot(N, l) of the occluder (Phong.cpp:99-113) -- the pieces of mr_phong.h that mr_trace_level shades with.
 #if defined(MIRO_WG_TIMES) && MIRO_TRACE_BLOCK == 256
 // measurement build only (make VARIANT=_wgt FRAME_DEFS=-DMIRO_WG_TIMES; tools/wg_timeline.py): every workgroup leaves its start and
 // end time (100 MHz constant clock), the CU it ran on and its XCD -- where the launch's idle VALU cycles sit
@@ -242,6 +242,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
             eye_ray_of(a.eye, x, y, sm, ra, rb);
         }
         // ---- primary ray
+        // (trace_hit of mr_traverse.h spelled out, here and for the shadow ray: through the helper every frame kernel comes out
+        // with other registers and the eye-relative ones a few instructions longer -- nothing a measurement is likely to see, but
+        // this is the benchmark's kernel and its code is kept as it was)
         mr_hit h;
         {
             RayRegs r;
@@ -277,13 +280,15 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
             // the ray's origin: the eye (a hit lane is a live one); kEyeRel reads it from the arguments, uniform, where it is used
             const float ox = kEyeRel ? a.eye.eye[0] : ra.x, oy = kEyeRel ? a.eye.eye[1] : ra.y, oz = kEyeRel ? a.eye.eye[2] : ra.z;
             if (MAT) {
+                // (the MeshMat and the LightArgs are put together here and again below as they always were: built once per kernel,
+                // or with phong_terms called on a.lt's fields, the four MAT kernels come out 6 to 240 instructions longer)
                 rec::MeshMat mm;
                 mm.s = a.m; mm.mats = a.mats; mm.prim_mat = a.prim_mat;
-                rec::LightArgs la;
+                LightArgs la;
                 for (int k = 0; k < 3; k++) { la.L[k] = a.lt.L[k]; la.color[k] = a.lt.color[k]; }
                 la.wattage = a.lt.wattage;
                 rec::surface_point_od(mm, ox, oy, oz, rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
-                rec::phong_terms(la, rec::material_of(mm, h.prim), P, N, rb.x, rb.y, rb.z, c, highlight);
+                phong_terms(la, rec::material_of(mm, h.prim), P, N, rb.x, rb.y, rb.z, c, highlight);
             } else {
                 surface_od<true>(a.m, ox, oy, oz, rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
             }
@@ -304,14 +309,14 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
                 if (hit) {
                     rec::MeshMat mm;
                     mm.s = a.m; mm.mats = a.mats; mm.prim_mat = a.prim_mat;
-                    rec::phong_combine(c, highlight, rec::light_scale_of(mm, sa, sb, *reinterpret_cast<const float4 *>(&hs)), c);
+                    phong_combine(c, highlight, light_scale_of(mm, sa, sb, *reinterpret_cast<const float4 *>(&hs)), c);
                 }
             } else if (hs.prim != MR_MISS) {
                 c[0] = 0.f; c[1] = 0.f; c[2] = 0.f;
             }
         } else {
             if (a.shadow_hits && live) reinterpret_cast<float4 *>(a.shadow_hits)[idx] = make_float4(0.0f, __uint_as_float(MR_MISS), 0.0f, 0.0f);
-            if (MAT && hit) rec::phong_combine(c, highlight, 1.0f, c);
+            if (MAT && hit) phong_combine(c, highlight, 1.0f, c);
         }
         // the pixel's mean (Scene.cpp:126-139)
         // spp is a power of two <= 64 (checked by the host): a pixel's samples are `spp` consecutive, aligned lanes; the
@@ -344,7 +349,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
     if (a.counts) {
         // rays traced.  Shadow rays: one atomic per workgroup (a single counter word drains ~88 atomics per microsecond:
         // a 1-spp frame's 8 100 workgroups are already a measurable 4 % with two words each); primary rays: the launch's
-        // sample count, added once.
+        // sample count, added once.  (workgroup_add of mr_traverse.h spelled out, like the traces above.)
         unsigned w = my_shadow_rays;
         for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
         if ((tid & 63) == 0) s_shadow_rays[tid >> 6] = w;
@@ -502,10 +507,7 @@ mr_status MR_FRAME_ENTRY(const DeviceScene &ds, const mr_frame_desc &fd, float *
     a.tp = scene_trace_params(ds);
     a.tp.n = a.eye.n;
     a.m = surface_ptrs(ds);
-    for (int c = 0; c < 3; c++) {
-        a.lt.L[c] = fd.light.position[c]; a.lt.color[c] = fd.light.color[c]; a.lt.diffuse[c] = fd.diffuse[c]; a.lt.bg[c] = 0.0f;
-    }
-    a.lt.wattage = fd.light.wattage;
+    a.lt = direct_light_of(fd.light, fd.diffuse);
     a.hits = d_hits; a.shadow_hits = d_shadow_hits; a.rgb = d_rgb; a.counts = d_counts;
 
     a.mats = ds.materials; a.prim_mat = ds.prim_material;

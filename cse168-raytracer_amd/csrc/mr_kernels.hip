@@ -53,6 +53,8 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel(TraceParams p) {
             ra = reinterpret_cast<const float4 *>(p.rays)[2 * src];
             rb = reinterpret_cast<const float4 *>(p.rays)[2 * src + 1];
         }
+        // (trace_hit of mr_traverse.h spelled out: through the helper the hit record is made for lanes without a ray too, and
+        // every variant of this kernel comes out with other code -- it is kept as it was)
         RayRegs r;
         ray_setup(r, ra, rb);
         Lane L;
@@ -67,7 +69,8 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel(TraceParams p) {
     }
 
     if (STATS) {
-        // wave64 reduction, one atomic pair per wave
+        // wave64 reduction, one atomic pair per wave (64-bit counts and no static LDS beside a stack that may fill the CU's:
+        // not workgroup_add)
         for (int off = 32; off > 0; off >>= 1) {
             st.box += __shfl_down(st.box, off, 64);
             st.tri += __shfl_down(st.tri, off, 64);

@@ -60,12 +60,10 @@ struct LevelArgs {
 template <int VAR, int CHILDREN>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(CHILDREN == 2 ? MIRO_LEVEL_PATH_WAVES : 6, 8))) void level_kernel(LevelArgs a) {
     extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
-    __shared__ unsigned s_shadow_rays[kTraceBlock / 64];
     const int tid = threadIdx.x;
     const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
     const unsigned long long n = a.tp.n;
-    const unsigned long long n_round = (n + (unsigned long long)kTraceBlock - 1ull) / kTraceBlock * kTraceBlock;   // whole workgroups
-    constexpr bool kObj = (VAR & kVarObjects) != 0;
+    const unsigned long long n_round = whole_workgroups(n);
     constexpr bool kPath = CHILDREN == 2;
     Stats st = {0ull, 0ull};
     unsigned my_shadow_rays = 0;
@@ -78,15 +76,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(CHI
             ra = reinterpret_cast<const float4 *>(a.tp.rays)[2 * s0]; rb = reinterpret_cast<const float4 *>(a.tp.rays)[2 * s0 + 1];
         }
         // ---- the ray (Scene.cpp:278)
-        mr_hit h;
-        {
-            RayRegs r;
-            ray_setup(r, ra, rb);
-            Lane L;
-            int plane_hit;
-            trace_ray<true, false, false, VAR>(a.tp, r, rb.w, live, L, plane_hit, s_stack, tid, st);
-            h = make_hit<kObj>(a.tp, L, plane_hit, rb.w);
-        }
+        const mr_hit h = trace_hit<true, false, false, VAR>(a.tp, ra, rb, rb.w, live, s_stack, tid, st);
         const bool hit = live && h.prim != MR_MISS;
 
         // ---- Phong::shade.  The unoccluded terms are computed BEFORE the shadow ray is traced: four values stay live
@@ -100,24 +90,16 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(CHI
             phong_terms(a.lt, material_of(a.m, h.prim), P, N, rb.x, rb.y, rb.z, diffuse, highlight);
             my_shadow_rays++;
         }
-        float4 sh;
-        {
-            RayRegs r;
-            ray_setup(r, sa, sb);
-            Lane L;
-            int plane_hit;
-            trace_ray<true, false, false, VAR>(a.tp, r, sb.w, hit, L, plane_hit, s_stack, tid, st);      // closest hit: the occluder matters
-            const mr_hit hs = make_hit<kObj>(a.tp, L, plane_hit, sb.w);
-            sh = *reinterpret_cast<const float4 *>(&hs);
-        }
+        const mr_hit hs = trace_hit<true, false, false, VAR>(a.tp, sa, sb, sb.w, hit, s_stack, tid, st);      // closest hit: the occluder matters
+        const float4 sh = *reinterpret_cast<const float4 *>(&hs);
         asm volatile("" ::: "memory");                   // the index is read again rather than kept in registers across the traversals
         unsigned long long src = k;
         if (live && a.tp.order) src = a.tp.order[k];
         uint32_t pix = 0xFFFFFFFFu;
         float w0[3] = {1.f, 1.f, 1.f}, v[3] = {0.f, 0.f, 0.f};
-        if (live) pix = a.pixels ? a.pixels[src] : (uint32_t)(src / a.spp);
+        if (live) pix = pixel_of(a.pixels, src, a.spp);
         if (hit) {
-            if (a.weights) { w0[0] = a.weights[3 * src]; w0[1] = a.weights[3 * src + 1]; w0[2] = a.weights[3 * src + 2]; }
+            weight_of(a.weights, src, w0);
             float out[3];
             phong_combine(diffuse, highlight, light_scale_of(a.m, sa, sb, sh), out);
             for (int c = 0; c < 3; c++) v[c] = out[c] * w0[c] * a.inv_spp;
@@ -149,16 +131,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(CHI
     }
 
     if (a.counts) {
-        unsigned w = my_shadow_rays;
-        for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
-        if ((tid & 63) == 0) s_shadow_rays[tid >> 6] = w;
-        __syncthreads();
-        if (tid == 0) {
-            unsigned long long tot = 0;
-            for (int j = 0; j < kTraceBlock / 64; j++) tot += s_shadow_rays[j];
-            if (tot) atomicAdd(&a.counts[1], tot);
-            if (blockIdx.x == 0) atomicAdd(&a.counts[0], n);
-        }
+        workgroup_add<kTraceBlock>(my_shadow_rays, &a.counts[1]);
+        if (tid == 0 && blockIdx.x == 0) atomicAdd(&a.counts[0], n);
     }
 }
 
@@ -193,8 +167,7 @@ mr_status launch_level(const DeviceScene &ds, const mr_level_desc &ld, const mr_
     a.tp = scene_trace_params(ds);
     a.tp.rays = d_rays; a.tp.n = n; a.tp.order = ld.d_order;
     a.m = mesh_of(ds);
-    for (int c = 0; c < 3; c++) { a.lt.L[c] = ld.light.position[c]; a.lt.color[c] = ld.light.color[c]; }
-    a.lt.wattage = ld.light.wattage;
+    a.lt = light_args_of(ld.light);
     a.weights = d_weights; a.pixels = d_pixels; a.ids = d_ids;
     a.spp = ld.spp; a.inv_spp = 1.0f / (float)ld.spp; a.hbase = pcg32(ld.seed); a.bounce = ld.bounce; a.kinds = ld.path_kinds;
     a.rgb = d_rgb;

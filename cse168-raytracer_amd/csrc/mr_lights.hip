@@ -18,14 +18,14 @@
 // profiles/r02_level_probe.log for the level kernel) -- dense first levels are what it is for.
 //
 // Two kinds of light:
-//   MR_LIGHT_POINT  PointLight (PointLight.h:8-59): shadow_ray_of / phong_terms / phong_combine / light_scale_of, the code of
-//                   the batched chain, so that one point light gives the chain's bits.
+//   MR_LIGHT_POINT  PointLight (PointLight.h:8-59): shadow_ray_of / phong_terms / phong_combine / light_scale_of (mr_phong.h),
+//                   the code of the batched chain, so that one point light gives the chain's bits.
 //   MR_LIGHT_DISC   DirectionalAreaLight (DirectionalAreaLight.h:7-38) as Phong::shade treats it, quirks included:
 //                   getLightDirection ignores the sampled origin (no random number); l = -normal, the shadow ray runs from
 //                   P + l * epsilon along l / |l| with tMax = |normal| (:81-97: sqrt(falloff) of the UN-normalised l -- with a
 //                   unit normal occluders are looked for one unit towards the light only); after the shadow test
 //                   nDotL = dot(N, -normal) with the normal as given, the hit must lie inside the disc's cylinder
-//                   (:132-133), falloff = 1 / PI (:135).
+//                   (:132-133), falloff = 1 / PI (:135): shadow_ray_for / disc_terms of mr_phong.h.
 #include <hip/hip_runtime.h>
 
 #include "mr_internal.h"
@@ -53,59 +53,15 @@ struct LightsArgs {
     ShadeLight lights[MR_MAX_LIGHTS];
 };
 
-// DirectionalAreaLight::getLightDirection and what Phong::shade makes of it (Phong.cpp:81-92): l = -normal,
-// falloff = |l|^2, l /= sqrt(falloff); Ray(P + l * epsilon, l), tMin = 0, tMax = sqrt(falloff)
-__device__ __forceinline__ void disc_shadow_ray_of(const float P[3], const ShadeLight &lt, float4 &a, float4 &b) {
-    constexpr float eps = 1e-4f;                                   // Miro.h:9
-    float lx = -lt.normal[0], ly = -lt.normal[1], lz = -lt.normal[2];
-    const float falloff = (lx * lx + ly * ly) + lz * lz;
-    const float len = sqrtf(falloff);
-    const float inv = 1.0f / len;
-    lx *= inv; ly *= inv; lz *= inv;
-    a = make_float4(P[0] + lx * eps, P[1] + ly * eps, P[2] + lz * eps, 0.0f);
-    b = make_float4(lx, ly, lz, len);
-}
-
-// Phong.cpp:121-136 and :146-156 for a DirectionalAreaLight.  l: the normalised direction (the shadow ray's).  Returns false
-// when the hit lies outside the disc's cylinder (:133, the light is skipped); otherwise the diffuse term and the highlight in
-// phong_terms' form, with nDotL = dot(N, -normal) on the normal as given and falloff = 1 / PI.
-__device__ __forceinline__ bool disc_terms(const ShadeLight &lt, const float *mt, const float P[3], const float N[3], const float l[3],
-                                           float dx, float dy, float dz, float diffuse[3], float &highlight) {
-    const float *n = lt.normal;
-    const float nDotL = (N[0] * -n[0] + N[1] * -n[1]) + N[2] * -n[2];                          // :128
-    const float t = ((n[0] * (lt.position[0] - P[0]) + n[1] * (lt.position[1] - P[1])) + n[2] * (lt.position[2] - P[2])) / -1.0f;   // :132
-    const float qx = (P[0] - n[0] * t) - lt.position[0], qy = (P[1] - n[1] * t) - lt.position[1], qz = (P[2] - n[2] * t) - lt.position[2];
-    if ((qx * qx + qy * qy) + qz * qz > lt.radius * lt.radius) return false;                   // :133
-    const float f2 = 1.0f / kPI;                                                               // :135
-    const float diff = fmaxf(0.0f, nDotL * f2 * lt.wattage);
-    for (int c = 0; c < 3; c++) diffuse[c] = lt.color[c] * (diff * mt[c] * mt[c]);             // :146
-    highlight = 0.0f;
-    if (mt[9] < rec::kInf) {                                                                   // :149-156
-        const float two = 2 * ((l[0] * N[0] + l[1] * N[1]) + l[2] * N[2]);
-        const float rx = -l[0] + two * N[0], ry = -l[1] + two * N[1], rz = -l[2] + two * N[2];
-        float e = (-dx * rx + -dy * ry) + -dz * rz;
-        e = powf(fmaxf(0.0f, fminf(1.0f, e)), 500.0f);
-        highlight = fmaxf(0.0f, e * f2 * lt.wattage);
-    }
-    return true;
-}
-
-__device__ __forceinline__ void shadow_ray_for(const ShadeLight &lt, const float P[3], float4 &sa, float4 &sb) {
-    if (lt.kind == MR_LIGHT_DISC) disc_shadow_ray_of(P, lt, sa, sb);
-    else shadow_ray_of(P, lt.position[0], lt.position[1], lt.position[2], sa, sb);
-}
-
 // VAR: the traversal variant of trace_ray (mr_traverse.h); ANY: the shadow rays stop at their first accepted hit (scenes
 // without a refractive material only: every occluder then scales the light to 0, whichever it is)
 template <int VAR, bool ANY>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void shade_lights_kernel(LightsArgs a) {
     extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
-    __shared__ unsigned s_shadow_rays[kTraceBlock / 64];
     const int tid = threadIdx.x;
     const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
     const unsigned long long n = a.tp.n;
-    const unsigned long long n_round = (n + (unsigned long long)kTraceBlock - 1ull) / kTraceBlock * kTraceBlock;   // whole workgroups
-    constexpr bool kObj = (VAR & kVarObjects) != 0;
+    const unsigned long long n_round = whole_workgroups(n);
     Stats st = {0ull, 0ull};
     unsigned my_shadow_rays = 0;
 
@@ -131,12 +87,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
             {
                 float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(1.f, 1.f, 1.f, -1.f);
                 if (hit) shadow_ray_for(lt, P, sa, sb);
-                RayRegs r;
-                ray_setup(r, sa, sb);
-                Lane ln;
-                int plane_hit;
-                trace_ray<true, ANY, false, VAR>(a.tp, r, sb.w, hit, ln, plane_hit, s_stack, tid, st);
-                const mr_hit hs = make_hit<kObj>(a.tp, ln, plane_hit, sb.w);
+                const mr_hit hs = trace_hit<true, ANY, false, VAR>(a.tp, sa, sb, sb.w, hit, s_stack, tid, st);
                 sh = *reinterpret_cast<const float4 *>(&hs);
             }
             if (hit) {
@@ -150,10 +101,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
                         const float l[3] = {sb.x, sb.y, sb.z};
                         lit = disc_terms(lt, mt, P, N, l, d[0], d[1], d[2], diffuse, highlight);
                     } else {
-                        LightArgs la;
-                        for (int c = 0; c < 3; c++) { la.L[c] = lt.position[c]; la.color[c] = lt.color[c]; }
-                        la.wattage = lt.wattage;
-                        phong_terms(la, mt, P, N, d[0], d[1], d[2], diffuse, highlight);
+                        phong_terms(lt.position, lt.color, lt.wattage, mt, P, N, d[0], d[1], d[2], diffuse, highlight);
                     }
                 }
                 if (lit) phong_combine(diffuse, highlight, scale, out);
@@ -165,27 +113,17 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
         if (a.rgb) {                                                   // wave-uniform
             uint32_t pix = 0xFFFFFFFFu;
             float v[3] = {0.f, 0.f, 0.f};
-            if (live) pix = a.pixels ? a.pixels[k] : (uint32_t)(k / a.spp);
+            if (live) pix = pixel_of(a.pixels, k, a.spp);
             if (hit) {
-                float w[3] = {1.f, 1.f, 1.f};
-                if (a.weights) { w[0] = a.weights[3 * k]; w[1] = a.weights[3 * k + 1]; w[2] = a.weights[3 * k + 2]; }
+                float w[3];
+                weight_of(a.weights, k, w);
                 for (int c = 0; c < 3; c++) v[c] = L[c] * w[c] * a.inv_spp;
             }
             accumulate_runs(a.rgb, pix, v[0], v[1], v[2]);
         }
     }
 
-    if (a.counts) {
-        unsigned w = my_shadow_rays;
-        for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
-        if ((tid & 63) == 0) s_shadow_rays[tid >> 6] = w;
-        __syncthreads();
-        if (tid == 0) {
-            unsigned long long tot = 0;
-            for (int j = 0; j < kTraceBlock / 64; j++) tot += s_shadow_rays[j];
-            if (tot) atomicAdd(&a.counts[0], tot);
-        }
-    }
+    if (a.counts) workgroup_add<kTraceBlock>(my_shadow_rays, &a.counts[0]);
 }
 
 template <int VAR, bool ANY>

@@ -1,62 +1,151 @@
-// mr_phong.h -- the two pieces of Phong::shade (Phong.cpp:44-160) that follow a hit, shared by the batched kernels
-// (shadow_rays_kernel, shade kernels) and the fused frame kernel so that both produce the same bits:
-//   shadow_ray_of   the shadow ray towards a point light (Phong.cpp:80-97)
-//   phong_direct    direct light of an unoccluded hit: diffuse term + highlight (Phong.cpp:116-156), with the normal
-//                   normalised as Scene::trace leaves it (Scene.cpp:262)
-// Device code only.
+// mr_phong.h -- the pieces of Phong::shade (Phong.cpp:44-160) that follow a hit, written once for the batched kernels
+// (shadow_rays_kernel, the shade kernels of mr_shade.hip and mr_bounce.hip), the fused frame and level kernels and the
+// light-list kernel, so that all of them produce the same bits:
+//   shadow_ray_of    the shadow ray towards a point light (Phong.cpp:80-97); shadow_ray_for: towards a light of the list,
+//                    point or disc -- one tail (shadow_ray_along) for both
+//   light_scale_of   what Phong::shade does with the shadow hit (Phong.cpp:97-113): opaque occluder -> 0,
+//                    refractive occluder -> dot(N, l) (0 if negative or < epsilon), no occluder -> 1
+//   phong_terms      diffuse term and highlight of a hit (Phong.cpp:116-156) for a material record and a point light;
+//                    disc_terms: for a DirectionalAreaLight; highlight_of is the one highlight (:149-156) of all of them
+//   phong_combine    the two terms and the light scale put together
+//   phong_direct     direct light of an unoccluded hit on the frame's uniform material, with the normal normalised as
+//                    Scene::trace leaves it (Scene.cpp:262): phong_terms + phong_combine
+//   light_args_of / direct_light_of   the host's mr_light as the kernels take it
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include "mr_internal.h"
+#include "mr_surface.h"
+
 namespace mr {
 
+constexpr float kPhongEps = 1e-4f;                                               // Miro.h:9
+constexpr float kPhongPI = 3.1415926535897932384626433832795028841972f;          // Miro.h:10
+
+struct LightArgs {
+    float L[3], color[3], wattage;
+};
+inline LightArgs light_args_of(const mr_light &light) {
+    LightArgs a;
+    for (int c = 0; c < 3; c++) { a.L[c] = light.position[c]; a.color[c] = light.color[c]; }
+    a.wattage = light.wattage;
+    return a;
+}
+
+// a point light and the uniform material of mr_shade_direct / mr_render_direct; bg: Scene::m_bgColor
 struct DirectLight {
     float L[3], color[3], diffuse[3], bg[3];
     float wattage;
 };
+inline DirectLight direct_light_of(const mr_light &light, const float diffuse[3]) {
+    DirectLight a;
+    for (int c = 0; c < 3; c++) { a.L[c] = light.position[c]; a.color[c] = light.color[c]; a.diffuse[c] = diffuse[c]; a.bg[c] = 0.0f; }
+    a.wattage = light.wattage;
+    return a;
+}
 
-// origin P + l*eps, direction l = normalise(L - P), tMin = 0, tMax = |L - P|   (PointLight::getLightDirection)
-__device__ __forceinline__ void shadow_ray_of(const float P[3], float Lx, float Ly, float Lz, float4 &a, float4 &b) {
-    constexpr float eps = 1e-4f;                                   // Miro.h:9
-    const float Px = P[0], Py = P[1], Pz = P[2];
-    float lx = Lx - Px, ly = Ly - Py, lz = Lz - Pz;
+// Phong.cpp:84-92 from getLightDirection's l (not normalised) on: falloff = |l|^2, l /= sqrt(falloff);
+// Ray(P + l * epsilon, l), tMin = 0, tMax = sqrt(falloff)
+__device__ __forceinline__ void shadow_ray_along(const float P[3], float lx, float ly, float lz, float4 &a, float4 &b) {
     const float falloff = (lx * lx + ly * ly) + lz * lz;
     const float len = sqrtf(falloff);
     const float inv = 1.0f / len;                                  // l /= sqrt(falloff)
     lx *= inv; ly *= inv; lz *= inv;
-    a = make_float4(Px + lx * eps, Py + ly * eps, Pz + lz * eps, 0.0f);
+    a = make_float4(P[0] + lx * kPhongEps, P[1] + ly * kPhongEps, P[2] + lz * kPhongEps, 0.0f);
     b = make_float4(lx, ly, lz, len);
 }
+// PointLight::getLightDirection: l = L - P
+__device__ __forceinline__ void shadow_ray_of(const float P[3], float Lx, float Ly, float Lz, float4 &a, float4 &b) {
+    shadow_ray_along(P, Lx - P[0], Ly - P[1], Lz - P[2], a, b);
+}
+// ... of a light of the list.  DirectionalAreaLight::getLightDirection ignores the sampled origin: l = -normal
+__device__ __forceinline__ void shadow_ray_for(const ShadeLight &lt, const float P[3], float4 &sa, float4 &sb) {
+    if (lt.kind == MR_LIGHT_DISC) shadow_ray_along(P, -lt.normal[0], -lt.normal[1], -lt.normal[2], sa, sb);
+    else shadow_ray_of(P, lt.position[0], lt.position[1], lt.position[2], sa, sb);
+}
 
-// N: the un-normalised HitInfo::N; (dx, dy, dz): direction of the ray that produced the hit
+// The factor Phong::shade puts on the light behind a shadow hit (Phong.cpp:97-113).  sa / sb: the shadow ray; sh: its
+// hit record (prim = MR_MISS: no occluder).
+__device__ __forceinline__ float light_scale_of(const rec::MeshMat &m, const float4 sa, const float4 sb, const float4 sh) {
+    const uint32_t prim = __float_as_uint(sh.y);
+    float scale = 1.0f;
+    if (prim != MR_MISS) {
+        scale = 0.0f;
+        const float *om = rec::material_of(m, prim);
+        if (rec::any_pos(om + 6)) {                                       // refractive occluder (Phong.cpp:99-113)
+            float P[3], N[3];
+            rec::surface_point_od(m, sa.x, sa.y, sa.z, sb.x, sb.y, sb.z, sh.x, prim, sh.z, sh.w, P, N);
+            const float d = (N[0] * sb.x + N[1] * sb.y) + N[2] * sb.z;
+            if (!(d < 0) && !(d < kPhongEps)) scale = d;
+        }
+    }
+    return scale;
+}
+
+// The specular highlight (Phong.cpp:149-156).  l: the normalised direction to the light, N normalised, (dx, dy, dz) the
+// direction of the ray that produced the hit, f2 the light's falloff factor.
+__device__ __forceinline__ float highlight_of(const float l[3], const float N[3], float dx, float dy, float dz, float f2, float wattage) {
+    const float two = 2 * ((l[0] * N[0] + l[1] * N[1]) + l[2] * N[2]);
+    const float rx = -l[0] + two * N[0], ry = -l[1] + two * N[1], rz = -l[2] + two * N[2];
+    float e = (-dx * rx + -dy * ry) + -dz * rz;
+    e = powf(fmaxf(0.0f, fminf(1.0f, e)), 500.0f);
+    return fmaxf(0.0f, e * f2 * wattage);
+}
+// Phong.cpp:146-156 once the light has given l, nDotL and its falloff factor f2: diffuse[c] (to be multiplied by the light
+// scale, :146) and the highlight (added unscaled; 0 for a material of infinite shininess)
+__device__ __forceinline__ void lit_terms(const float color[3], float wattage, const float *mt, const float N[3], const float l[3],
+                                          float nDotL, float f2, float dx, float dy, float dz, float diffuse[3], float &highlight) {
+    const float diff = fmaxf(0.0f, nDotL * f2 * wattage);
+    for (int c = 0; c < 3; c++) diffuse[c] = color[c] * (diff * mt[c] * mt[c]);               // :146
+    highlight = mt[9] < __builtin_huge_valf() ? highlight_of(l, N, dx, dy, dz, f2, wattage) : 0.0f;
+}
+
+// Phong::shade's direct light at a hit (Phong.cpp:116-156) for a point light at L, in lit_terms' two parts.  The shaded value
+// of a hit with light scale s != 0 is diffuse[c] * s + highlight, and 0 for s == 0 (Phong.cpp:100-103 skips the light).
+// mt: the hit's material record; N normalised; (dx, dy, dz) the direction of the ray that produced the hit.
+__device__ __forceinline__ void phong_terms(const float L[3], const float color[3], float wattage, const float *mt, const float P[3],
+                                            const float N[3], float dx, float dy, float dz, float diffuse[3], float &highlight) {
+    float l[3] = {L[0] - P[0], L[1] - P[1], L[2] - P[2]};
+    const float falloff = (l[0] * l[0] + l[1] * l[1]) + l[2] * l[2];
+    const float inv = 1.0f / sqrtf(falloff);
+    l[0] *= inv; l[1] *= inv; l[2] *= inv;
+    const float nDotL = (N[0] * l[0] + N[1] * l[1]) + N[2] * l[2];
+    const float f2 = 1.0f / (falloff * 4.0f * kPhongPI * kPhongPI);                           // :140
+    lit_terms(color, wattage, mt, N, l, nDotL, f2, dx, dy, dz, diffuse, highlight);
+}
+__device__ __forceinline__ void phong_terms(const LightArgs &a, const float *mt, const float P[3], const float N[3], float dx,
+                                            float dy, float dz, float diffuse[3], float &highlight) {
+    phong_terms(a.L, a.color, a.wattage, mt, P, N, dx, dy, dz, diffuse, highlight);
+}
+// Phong.cpp:121-136 for a DirectionalAreaLight.  l: the normalised direction (the shadow ray's).  Returns false when the hit
+// lies outside the disc's cylinder (:133, the light is skipped); otherwise lit_terms with nDotL = dot(N, -normal) on the
+// normal as given and falloff = 1 / PI.
+__device__ __forceinline__ bool disc_terms(const ShadeLight &lt, const float *mt, const float P[3], const float N[3], const float l[3],
+                                           float dx, float dy, float dz, float diffuse[3], float &highlight) {
+    const float *n = lt.normal;
+    const float nDotL = (N[0] * -n[0] + N[1] * -n[1]) + N[2] * -n[2];                          // :128
+    const float t = ((n[0] * (lt.position[0] - P[0]) + n[1] * (lt.position[1] - P[1])) + n[2] * (lt.position[2] - P[2])) / -1.0f;   // :132
+    const float qx = (P[0] - n[0] * t) - lt.position[0], qy = (P[1] - n[1] * t) - lt.position[1], qz = (P[2] - n[2] * t) - lt.position[2];
+    if ((qx * qx + qy * qy) + qz * qz > lt.radius * lt.radius) return false;                   // :133
+    lit_terms(lt.color, lt.wattage, mt, N, l, nDotL, 1.0f / kPhongPI, dx, dy, dz, diffuse, highlight);   // :135
+    return true;
+}
+
+__device__ __forceinline__ void phong_combine(const float diffuse[3], float highlight, float scale, float out[3]) {
+    if (scale == 0.0f) { out[0] = 0.f; out[1] = 0.f; out[2] = 0.f; return; }
+    for (int c = 0; c < 3; c++) out[c] = diffuse[c] * scale + highlight;
+}
+
+// The uniform-material callers' form: N is the un-normalised HitInfo::N and is normalised in place; the material is Phong's
+// default but for its diffuse colour (shininess 1 < infinity: the highlight is on), the light is not occluded.
 __device__ __forceinline__ void phong_direct(const DirectLight &a, const float P[3], float N[3], float dx, float dy, float dz,
                                              float out[3]) {
-    constexpr float kPI = 3.1415926535897932384626433832795028841972f;   // Miro.h:10
-    {   // Scene.cpp:262 -- N.normalize()
-        const float inv = 1.0f / sqrtf((N[0] * N[0] + N[1] * N[1]) + N[2] * N[2]);
-        N[0] *= inv; N[1] *= inv; N[2] *= inv;
-    }
-    float l[3] = {a.L[0] - P[0], a.L[1] - P[1], a.L[2] - P[2]};
-    const float falloff = (l[0] * l[0] + l[1] * l[1]) + l[2] * l[2];
-    {
-        const float inv = 1.0f / sqrtf(falloff);
-        l[0] *= inv; l[1] *= inv; l[2] *= inv;
-    }
-    const float nDotL = (N[0] * l[0] + N[1] * l[1]) + N[2] * l[2];
-    const float f2 = 1.0f / (falloff * 4.0f * kPI * kPI);                                   // Phong.cpp:140
-    const float diff = fmaxf(0.0f, nDotL * f2 * a.wattage);
-    for (int c = 0; c < 3; c++) out[c] = a.color[c] * (diff * a.diffuse[c] * a.diffuse[c]);  // :146
-    // specular highlight (:149-156); Phong's default shininess 1 < infinity
-    const float lDotN = (l[0] * N[0] + l[1] * N[1]) + l[2] * N[2];
-    float eDotr = 0.0f;
-    {
-        const float two = 2 * lDotN;
-        const float rx = -l[0] + two * N[0], ry = -l[1] + two * N[1], rz = -l[2] + two * N[2];
-        eDotr = (-dx * rx + -dy * ry) + -dz * rz;
-    }
-    eDotr = powf(fmaxf(0.0f, fminf(1.0f, eDotr)), 500.0f);
-    const float highlights = fmaxf(0.0f, eDotr * f2 * a.wattage);
-    out[0] += highlights; out[1] += highlights; out[2] += highlights;
+    normalize3(N);                                                 // Scene.cpp:262
+    const float mt[11] = {a.diffuse[0], a.diffuse[1], a.diffuse[2], 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.0f, 1.0f};
+    float diffuse[3], highlight;
+    phong_terms(a.L, a.color, a.wattage, mt, P, N, dx, dy, dz, diffuse, highlight);
+    phong_combine(diffuse, highlight, 1.0f, out);
 }
 
 }  // namespace mr

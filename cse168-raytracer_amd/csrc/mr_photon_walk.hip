@@ -52,7 +52,6 @@ template <int VAR>
 __global__ __launch_bounds__(kTraceBlock) void photon_walk_kernel(WalkArgs a) {
     extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
     const int tid = threadIdx.x, lane = tid & 63;
-    constexpr bool kObj = (VAR & kVarObjects) != 0;
     Stats st = {0ull, 0ull};
 
     uint32_t my = kNoPhoton, state = 0;               // local emission index of the lane's photon
@@ -91,15 +90,8 @@ __global__ __launch_bounds__(kTraceBlock) void photon_walk_kernel(WalkArgs a) {
         if (!__any(live)) break;
 
         // ---- Scene::trace(hit, ray, 0, MIRO_TMAX) (Scene.cpp:539)
-        mr_hit h;
-        {
-            RayRegs r;
-            ray_setup(r, make_float4(o[0], o[1], o[2], 0.0f), make_float4(d[0], d[1], d[2], 1e12f));
-            Lane L;
-            int plane_hit;
-            trace_ray<true, false, false, VAR>(a.tp, r, 1e12f, live, L, plane_hit, s_stack, tid, st);
-            h = make_hit<kObj>(a.tp, L, plane_hit, 1e12f);
-        }
+        const mr_hit h = trace_hit<true, false, false, VAR>(a.tp, make_float4(o[0], o[1], o[2], 0.0f), make_float4(d[0], d[1], d[2], 1e12f), 1e12f,
+                                                            live, s_stack, tid, st);
         if (live) {
             state += 1u;                                                                 // ++depth (:538)
             const uint32_t depth = state & 255u;

@@ -1,12 +1,12 @@
-// mr_recursion.h -- the per-ray pieces of Scene::traceScene's recursion (Scene.cpp:270-346) and of Phong::shade with
-// per-triangle materials (Phong.cpp:44-160), shared by the batched kernels of mr_bounce.hip and the fused level kernel
-// of mr_level.hip so that both produce the same bits:
-//   light_scale_of       what Phong::shade does with the shadow hit (Phong.cpp:97-113): opaque occluder -> 0,
-//                        refractive occluder -> dot(N, l) (0 if negative or < epsilon), no occluder -> 1
-//   phong_terms          diffuse term and highlight of a hit (Phong.cpp:116-156) for a material record
+// mr_recursion.h -- the per-ray pieces of Scene::traceScene's recursion (Scene.cpp:270-346), shared by the batched kernels
+// of mr_bounce.hip, the fused level kernel of mr_level.hip and the photon walk so that all produce the same bits:
+//   weight_of / pixel_of a queue's optional per-ray path weight and pixel
+//   accumulate_runs      weight * L / spp added to the ray's pixel, runs of equal pixels summed inside the wave first
 //   ChildGen<PATH>       Ray::reflect / getReflectionCoefficient / refract (Ray.h:143-243, Scene.cpp:302-336), or their
 //                        PATH_TRACING build plus Ray::random (Ray.h:124-158,235-239)
-//   write_children       wave64 ballot compaction of the children, one atomic per workgroup
+//   write_children       wave64 ballot compaction of the children, one atomic per workgroup (workgroup_reserve)
+//   pcg32 / unit01       the counter-based random numbers
+// The hit point, the normal and the material of a hit are mr_surface.h (rec::MeshMat), Phong::shade is mr_phong.h.
 // Device code only.
 #pragma once
 
@@ -21,87 +21,14 @@ namespace rec {
 
 constexpr float kEps = 1e-4f;                                                    // Miro.h:9
 constexpr float kPI = 3.1415926535897932384626433832795028841972f;               // Miro.h:10
-constexpr float kInf = __builtin_huge_valf();
 
-struct MeshMat {
-    SurfacePtrs s;
-    const float *mats;            // 11 floats per material: diffuse, specular, transmission, shininess, index
-    const uint32_t *prim_mat;     // NULL: material 0 everywhere
-};
-
-inline MeshMat mesh_of(const DeviceScene &ds) {
-    MeshMat m;
-    m.s = surface_ptrs(ds); m.mats = ds.materials; m.prim_mat = ds.prim_material;
-    return m;
+// a queue's per-ray path weight (weights == NULL: 1) and pixel (pixels == NULL: ray index / spp)
+__device__ __forceinline__ void weight_of(const float *weights, unsigned long long k, float w[3]) {
+    w[0] = 1.f; w[1] = 1.f; w[2] = 1.f;
+    if (weights) { w[0] = weights[3 * k]; w[1] = weights[3 * k + 1]; w[2] = weights[3 * k + 2]; }
 }
-
-__device__ __forceinline__ const float *material_of(const MeshMat &m, uint32_t prim) {
-    return m.mats + 11 * (size_t)material_id(m.s, m.prim_mat, prim);
-}
-__device__ __forceinline__ bool any_pos(const float *c) { return c[0] > 0.f || c[1] > 0.f || c[2] > 0.f; }
-
-// HitInfo::P and the normalised N that Scene::trace hands to its callers (mr_surface.h, Scene.cpp:262), from the ray
-// (origin o, direction d) and its hit record in registers
-__device__ __forceinline__ void surface_point_od(const MeshMat &m, float ox, float oy, float oz, float dx, float dy, float dz,
-                                                 float t, uint32_t prim, float beta, float gamma, float P[3], float N[3]) {
-    surface_od<true>(m.s, ox, oy, oz, dx, dy, dz, t, prim, beta, gamma, P, N);
-    const float inv = 1.0f / sqrtf((N[0] * N[0] + N[1] * N[1]) + N[2] * N[2]);
-    N[0] *= inv; N[1] *= inv; N[2] *= inv;
-}
-__device__ __forceinline__ void surface_point(const MeshMat &m, const mr_ray *rays, unsigned long long k, const float4 h,
-                                              float P[3], float N[3]) {
-    const float4 ra = reinterpret_cast<const float4 *>(rays)[2 * k], rb = reinterpret_cast<const float4 *>(rays)[2 * k + 1];
-    surface_point_od(m, ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, h.x, __float_as_uint(h.y), h.z, h.w, P, N);
-}
-
-// The factor Phong::shade puts on the light behind a shadow hit (Phong.cpp:97-113).  sa / sb: the shadow ray; sh: its
-// hit record (prim = MR_MISS: no occluder).
-__device__ __forceinline__ float light_scale_of(const MeshMat &m, const float4 sa, const float4 sb, const float4 sh) {
-    const uint32_t prim = __float_as_uint(sh.y);
-    float scale = 1.0f;
-    if (prim != MR_MISS) {
-        scale = 0.0f;
-        const float *om = material_of(m, prim);
-        if (any_pos(om + 6)) {                                            // refractive occluder (Phong.cpp:99-113)
-            float P[3], N[3];
-            surface_point_od(m, sa.x, sa.y, sa.z, sb.x, sb.y, sb.z, sh.x, prim, sh.z, sh.w, P, N);
-            const float d = (N[0] * sb.x + N[1] * sb.y) + N[2] * sb.z;
-            if (!(d < 0) && !(d < kEps)) scale = d;
-        }
-    }
-    return scale;
-}
-
-struct LightArgs {
-    float L[3], color[3], wattage;
-};
-
-// Phong::shade's direct light at a hit (Phong.cpp:116-156) in two parts: diffuse[c] (to be multiplied by the light scale,
-// :146) and the highlight (:149-156, added unscaled; 0 for a material of infinite shininess).  The shaded value of a hit
-// with light scale s != 0 is diffuse[c] * s + highlight, and 0 for s == 0 (Phong.cpp:100-103 skips the light).
-// N normalised; (dx, dy, dz) the direction of the ray that produced the hit.
-__device__ __forceinline__ void phong_terms(const LightArgs &a, const float *mt, const float P[3], const float N[3], float dx,
-                                            float dy, float dz, float diffuse[3], float &highlight) {
-    float l[3] = {a.L[0] - P[0], a.L[1] - P[1], a.L[2] - P[2]};
-    const float falloff = (l[0] * l[0] + l[1] * l[1]) + l[2] * l[2];
-    const float inv = 1.0f / sqrtf(falloff);
-    l[0] *= inv; l[1] *= inv; l[2] *= inv;
-    const float nDotL = (N[0] * l[0] + N[1] * l[1]) + N[2] * l[2];
-    const float f2 = 1.0f / (falloff * 4.0f * kPI * kPI);
-    const float diff = fmaxf(0.0f, nDotL * f2 * a.wattage);
-    for (int c = 0; c < 3; c++) diffuse[c] = a.color[c] * (diff * mt[c] * mt[c]);            // Phong.cpp:146
-    highlight = 0.0f;
-    if (mt[9] < kInf) {                                                                       // :149-156
-        const float two = 2 * ((l[0] * N[0] + l[1] * N[1]) + l[2] * N[2]);
-        const float rx = -l[0] + two * N[0], ry = -l[1] + two * N[1], rz = -l[2] + two * N[2];
-        float e = (-dx * rx + -dy * ry) + -dz * rz;
-        e = powf(fmaxf(0.0f, fminf(1.0f, e)), 500.0f);
-        highlight = fmaxf(0.0f, e * f2 * a.wattage);
-    }
-}
-__device__ __forceinline__ void phong_combine(const float diffuse[3], float highlight, float scale, float out[3]) {
-    if (scale == 0.0f) { out[0] = 0.f; out[1] = 0.f; out[2] = 0.f; return; }
-    for (int c = 0; c < 3; c++) out[c] = diffuse[c] * scale + highlight;
+__device__ __forceinline__ uint32_t pixel_of(const uint32_t *pixels, unsigned long long k, uint32_t spp) {
+    return pixels ? pixels[k] : (uint32_t)(k / spp);
 }
 
 // weight * L / spp added to the ray's pixel.  Called by ALL lanes of the wave (a lane without a contribution brings

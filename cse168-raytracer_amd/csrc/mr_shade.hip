@@ -102,12 +102,8 @@ __global__ __launch_bounds__(kBlock) void gather_queries_kernel(SurfacePtrs m, c
         float P[3] = {0.f, 0.f, 0.f}, N[3];
         N[0] = N[1] = N[2] = __uint_as_float(0x7fc00000u);
         if (prim != MR_MISS) {
-            const float *mt = mats + 11 * (size_t)material_id(m, prim_mat, prim);
-            if (mt[0] > 0.f || mt[1] > 0.f || mt[2] > 0.f) {
-                surface<true>(m, rays, k, h.x, prim, h.z, h.w, P, N);
-                const float inv = 1.0f / sqrtf((N[0] * N[0] + N[1] * N[1]) + N[2] * N[2]);   // Scene.cpp:262
-                N[0] *= inv; N[1] *= inv; N[2] *= inv;
-            }
+            const rec::MeshMat mm = {m, mats, prim_mat};
+            if (rec::any_pos(rec::material_of(mm, prim))) rec::surface_point(mm, rays, k, h, P, N);
         }
         for (int c = 0; c < 3; c++) { pos[3 * k + c] = P[c]; nrm[3 * k + c] = N[c]; }
     }
@@ -181,8 +177,7 @@ mr_status launch_shade(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit
     ShadeArgs a;
     a.m = surface_ptrs(ds);
     a.rays = d_rays; a.hits = d_hits; a.occluded = d_occluded;
-    for (int c = 0; c < 3; c++) { a.lt.L[c] = light.position[c]; a.lt.color[c] = light.color[c]; a.lt.diffuse[c] = diffuse[c]; a.lt.bg[c] = 0.0f; }
-    a.lt.wattage = light.wattage;
+    a.lt = direct_light_of(light, diffuse);
     a.spp = spp;
     a.n_pixels = n / spp;
     a.rgb = d_rgb;

@@ -5,7 +5,8 @@
 //   sphere    P = o + t*d, N = (P - centre) / |P - centre|                                        Sphere.cpp:61-63
 //   plane     P = o + t*d, N = the plane's normal as set                                          Plane.cpp:42-44
 //
-// N is what the object's intersect() leaves in HitInfo; Scene::trace normalises it afterwards (Scene.cpp:262).
+// N is what the object's intersect() leaves in HitInfo; Scene::trace normalises it afterwards (Scene.cpp:262):
+// rec::surface_point[_od] below is the form with that normalisation, on a scene's mesh and material tables (rec::MeshMat).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,6 +28,12 @@ inline SurfacePtrs surface_ptrs(const DeviceScene &ds) {
     return m;
 }
 
+// Vector3::normalize as Scene.cpp:262 and Sphere.cpp:63 apply it to a normal
+__device__ __forceinline__ void normalize3(float N[3]) {
+    const float inv = 1.0f / sqrtf((N[0] * N[0] + N[1] * N[1]) + N[2] * N[2]);
+    N[0] *= inv; N[1] *= inv; N[2] *= inv;
+}
+
 // The hit's ray given in registers (o, d): used by the fused frame kernel, and by surface() below once it has
 // fetched the ray.  o / d are read only for spheres and planes.
 template <bool WANT_N>
@@ -41,8 +48,7 @@ __device__ __forceinline__ void surface_od(const SurfacePtrs &m, float ox, float
         } else {
             const float4 sp = m.spheres[m.vi[3 * (size_t)prim + 1]];
             N[0] = P[0] - sp.x; N[1] = P[1] - sp.y; N[2] = P[2] - sp.z;
-            const float inv = 1.0f / sqrtf((N[0] * N[0] + N[1] * N[1]) + N[2] * N[2]);   // N.normalize()
-            N[0] *= inv; N[1] *= inv; N[2] *= inv;
+            normalize3(N);
         }
         return;
     }
@@ -78,4 +84,39 @@ __device__ __forceinline__ uint32_t material_id(const SurfacePtrs &m, const uint
     return prim_mat ? prim_mat[prim] : 0u;
 }
 
+namespace rec {      // (the namespace is part of the names of the kernels that take a MeshMat)
+
+// a scene's mesh with its materials
+struct MeshMat {
+    SurfacePtrs s;
+    const float *mats;            // 11 floats per material: diffuse, specular, transmission, shininess, index
+    const uint32_t *prim_mat;     // NULL: material 0 everywhere
+};
+
+inline MeshMat mesh_of(const DeviceScene &ds) {
+    MeshMat m;
+    m.s = surface_ptrs(ds); m.mats = ds.materials; m.prim_mat = ds.prim_material;
+    return m;
+}
+
+__device__ __forceinline__ const float *material_of(const MeshMat &m, uint32_t prim) {
+    return m.mats + 11 * (size_t)material_id(m.s, m.prim_mat, prim);
+}
+__device__ __forceinline__ bool any_pos(const float *c) { return c[0] > 0.f || c[1] > 0.f || c[2] > 0.f; }
+
+// HitInfo::P and the normalised N that Scene::trace hands to its callers (Scene.cpp:262), from the ray (origin o,
+// direction d) and its hit record in registers
+__device__ __forceinline__ void surface_point_od(const MeshMat &m, float ox, float oy, float oz, float dx, float dy, float dz,
+                                                 float t, uint32_t prim, float beta, float gamma, float P[3], float N[3]) {
+    surface_od<true>(m.s, ox, oy, oz, dx, dy, dz, t, prim, beta, gamma, P, N);
+    normalize3(N);
+}
+// ... of ray k of a batch and its hit record h
+__device__ __forceinline__ void surface_point(const MeshMat &m, const mr_ray *rays, unsigned long long k, const float4 h,
+                                              float P[3], float N[3]) {
+    const float4 ra = reinterpret_cast<const float4 *>(rays)[2 * k], rb = reinterpret_cast<const float4 *>(rays)[2 * k + 1];
+    surface_point_od(m, ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, h.x, __float_as_uint(h.y), h.z, h.w, P, N);
+}
+
+}  // namespace rec
 }  // namespace mr

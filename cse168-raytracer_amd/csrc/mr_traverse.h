@@ -1,6 +1,7 @@
 // mr_traverse.h -- device-side machinery of the intersection path, shared by the batched trace kernels
 // (mr_kernels.hip) and the fused frame kernel (mr_frame.hip): slab tests, Triangle::intersect, Sphere::intersect,
-// the per-lane LDS stack and the "while-while" traversal loop.  Device code only; include from .hip files.
+// the per-lane LDS stack and the "while-while" traversal loop; at the end what the kernels around a traversal share: trace_hit,
+// whole_workgroups, workgroup_add.  Device code only; include from .hip files.
 //
 //   BVH::intersect / intersectChildren   BVH.cpp:438-658 (scalar branch)
 //   Triangle::intersect                  Triangle.cpp:136-169
@@ -827,6 +828,49 @@ __device__ __forceinline__ mr_hit make_hit(const TraceParams &p, const Lane &L, 
     return h;
 }
 
+// "Trace one ray held in registers (ra = origin | tMin, rb = direction | -) and give me its hit record": trace_ray and
+// make_hit on a fresh RayRegs / Lane.  Called by whole waves like trace_ray; a lane that is not live gets the miss record.
+template <bool EXACT, bool ANY, bool STATS, int VAR, bool REL = false>
+__device__ __forceinline__ mr_hit trace_hit(const TraceParams &p, const float4 &ra, const float4 &rb, float tmax, bool live,
+                                            int *s_stack, int tid, Stats &st) {
+    RayRegs r;
+    ray_setup(r, ra, rb);
+    Lane L;
+    int plane_hit;
+    trace_ray<EXACT, ANY, STATS, VAR, REL>(p, r, tmax, live, L, plane_hit, s_stack, tid, st);
+    return make_hit<(VAR & kVarObjects) != 0>(p, L, plane_hit, tmax);
+}
+
+// n rounded up to whole workgroups: the loop bound of kernels whose iterations hold a barrier (workgroup_reserve)
+__device__ __forceinline__ unsigned long long whole_workgroups(unsigned long long n) {
+    return (n + (unsigned long long)kTraceBlock - 1ull) / kTraceBlock * kTraceBlock;
+}
+
+// counters[j] += the workgroup's sum of mine[j]: a wave shuffle-reduce, one LDS slot per wave, then ONE atomic per word
+// and workgroup, and none for a sum of zero (a single counter word drains ~88 atomics per microsecond: a 1-spp frame's
+// 8 100 workgroups are already a measurable 4 % with two words each).  Called once, by all threads of the workgroup.
+template <int BLOCK, int WORDS>
+__device__ __forceinline__ void workgroup_add(const unsigned (&mine)[WORDS], unsigned long long *counters) {
+    __shared__ unsigned s_part[WORDS][BLOCK / 64];
+    const int tid = threadIdx.x;
+    unsigned w[WORDS];
+    for (int j = 0; j < WORDS; j++) w[j] = mine[j];
+    for (int off = 32; off > 0; off >>= 1)
+        for (int j = 0; j < WORDS; j++) w[j] += __shfl_down(w[j], off, 64);
+    if ((tid & 63) == 0)
+        for (int j = 0; j < WORDS; j++) s_part[j][tid >> 6] = w[j];
+    __syncthreads();
+    if (tid < WORDS) {
+        unsigned long long tot = 0;
+        for (int k = 0; k < BLOCK / 64; k++) tot += s_part[tid][k];
+        if (tot) atomicAdd(&counters[tid], tot);
+    }
+}
+template <int BLOCK>
+__device__ __forceinline__ void workgroup_add(unsigned mine, unsigned long long *counter) {
+    const unsigned m[1] = {mine};
+    workgroup_add<BLOCK, 1>(m, counter);
+}
 
 }  // namespace
 }  // namespace mr
