@@ -1,0 +1,64 @@
+// mr_accumulate_body.h -- the body of shade_accumulate_kernel (mr_bounce.hip, where the kernel is described) as a
+// __device__ template: its textured form (mr_textures.hip) is the same code with the hit's diffuseColor looked up first
+// (Phong.cpp:51-56; diffuse_color_of).  Arguments by value, as in mr_lights_body.h.  Included by the .hip units that instantiate it (everything here is local to its unit).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "mr_internal.h"
+#include "mr_launch.h"
+#include "mr_phong.h"
+#include "mr_recursion.h"
+#include "mr_texture.h"
+#include "mr_uv.h"
+
+namespace mr {
+namespace {
+
+struct AccumArgs {
+    rec::MeshMat m;
+    const mr_ray *rays;
+    const mr_hit *hits;
+    const float *weights;         // rgb per ray or NULL (= 1)
+    const uint32_t *pixels;       // pixel per ray or NULL (= ray index / spp)
+    const float *light_scale;     // per ray
+    LightArgs lt;
+    float inv_spp;
+    uint32_t spp;
+    unsigned long long n;
+    float *rgb;
+};
+
+template <bool TEX>
+__device__ __forceinline__ void shade_accumulate_body(const AccumArgs a, const TexParams t) {
+    using namespace rec;
+    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
+    const unsigned long long n_round = (a.n + 63ull) & ~63ull;                            // whole waves: accumulate_runs shuffles
+    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < n_round; k += stride) {
+        float v[3] = {0.f, 0.f, 0.f};
+        uint32_t pix = 0xFFFFFFFFu;
+        if (k < a.n) {
+            pix = pixel_of(a.pixels, k, a.spp);
+            const float4 h = reinterpret_cast<const float4 *>(a.hits)[k];
+            const uint32_t prim = __float_as_uint(h.y);
+            const float scale = prim != MR_MISS ? a.light_scale[k] : 0.0f;                // a miss: m_bgColor = 0 contributes nothing
+            if (scale != 0.0f) {
+                float P[3], N[3], diffuse[3], highlight, out[3];
+                surface_point(a.m, a.rays, k, h, P, N);
+                const float4 rb = reinterpret_cast<const float4 *>(a.rays)[2 * k + 1];
+                const float *mt = material_of(a.m, prim);
+                float col[3] = {0.f, 0.f, 0.f};
+                if (TEX) diffuse_color_of(a.m, t, material_id(a.m.s, a.m.prim_mat, prim), prim, P, col);
+                phong_terms(a.lt, mt, TEX ? col : mt, P, N, rb.x, rb.y, rb.z, diffuse, highlight);
+                phong_combine(diffuse, highlight, scale, out);
+                float w[3];
+                weight_of(a.weights, k, w);
+                for (int c = 0; c < 3; c++) v[c] = out[c] * w[c] * a.inv_spp;
+            }
+        }
+        accumulate_runs(a.rgb, pix, v[0], v[1], v[2]);
+    }
+}
+
+}  // namespace
+}  // namespace mr

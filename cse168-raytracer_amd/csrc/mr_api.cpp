@@ -42,6 +42,7 @@ void release_device(mr_scene *s) {
     (void)hipFree(d.v); (void)hipFree(d.n); (void)hipFree(d.vi); (void)hipFree(d.ni);
     (void)hipFree(d.materials); (void)hipFree(d.prim_material);
     (void)hipFree(d.spheres); (void)hipFree(d.planes);
+    (void)hipFree(d.texcoords); (void)hipFree(d.ti);
     d = DeviceScene();
     (void)hipFree(s->d_stats); s->d_stats = nullptr;
     (void)hipFree(s->d_work_counters); s->d_work_counters = nullptr;
@@ -68,6 +69,9 @@ void release_device(mr_scene *s) {
     (void)hipFree(s->d_env);
     s->d_env = nullptr;
     s->env_dirty = s->env.W != 0;          // the image outlives the device records: the next shade call uploads it again
+    (void)hipFree(s->d_tex);
+    s->d_tex = nullptr;
+    s->tex_dirty = !s->tex.blob.empty();   // and so does the texture table
 }
 
 inline int32_t leaf_ref(uint32_t first, uint32_t count) {
@@ -76,6 +80,7 @@ inline int32_t leaf_ref(uint32_t first, uint32_t count) {
 }
 
 mr_status upload_materials(mr_scene *s);
+mr_status upload_texcoords(mr_scene *s);
 
 // Storage order of the inner nodes (MR_LAYOUT_*): the list of host node indices in the order their records are stored;
 // -1 = an unused padding record.  Node identity, references and visiting order do not depend on it.
@@ -284,7 +289,24 @@ mr_status flatten_and_upload(mr_scene *s, uint32_t layout) {
     // the tails of large frames (zero here, re-armed by the launch's last reader: mr_frame.hip)
     MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&s->d_work_counters), 2 * kWorkCounters * sizeof(unsigned long long)));
     MR_HIP_CHECK(hipMemset(s->d_work_counters, 0, 2 * kWorkCounters * sizeof(unsigned long long)));
+    if ((st = upload_texcoords(s)) != MR_OK) return st;
     return upload_materials(s);
+}
+
+// the texture coordinates and their three indices per object (mr_uv.h); objects added behind the last one that has any get none
+mr_status upload_texcoords(mr_scene *s) {
+    DeviceScene &d = s->dev;
+    const HostMesh &m = s->mesh;
+    (void)hipFree(d.texcoords); (void)hipFree(d.ti);
+    d.texcoords = nullptr; d.ti = nullptr;
+    if (m.t.empty()) return MR_OK;
+    if (m.ti.size() > m.vi.size()) return fail(MR_ERR_STATE, "texture-coordinate indices cover %zu objects, the scene holds %u", m.ti.size() / 3, m.n_triangles());
+    std::vector<uint32_t> ti(m.ti);
+    ti.resize(m.vi.size(), kNoTexcoord);
+    uint64_t bytes = 0;
+    mr_status st;
+    if ((st = upload(d.texcoords, m.t.data(), m.t.size(), bytes)) != MR_OK) return st;
+    return upload(d.ti, ti.data(), ti.size(), bytes);
 }
 
 // default: one white Lambert = Phong(Vector3(1)) (Lambert.h:9, Phong.h:10-14: shininess 1, index 1)
@@ -356,6 +378,32 @@ mr_status require_device(const mr_scene *s) {
     if (!s->on_device)
         return fail(MR_ERR_STATE, "scene was built host_only: nothing is resident on a device and there is no CPU fallback");
     return MR_OK;
+}
+
+// the texture table on the device, uploaded on `stream` by the first shading call after a change; `p`: as the kernels take it
+mr_status texture_params(mr_scene *s, hipStream_t stream, TexParams &p) {
+    const HostTextures &t = s->tex;
+    if (s->tex_dirty) {
+        (void)hipFree(s->d_tex);
+        s->d_tex = nullptr;
+        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&s->d_tex), t.blob.size() * sizeof(float4)));
+        MR_HIP_CHECK(hipMemcpyAsync(s->d_tex, t.blob.data(), t.blob.size() * sizeof(float4), hipMemcpyHostToDevice, stream));
+        s->tex_dirty = false;
+    }
+    p.recs = s->d_tex;
+    p.texels = s->d_tex + t.texel_base;
+    p.mat_tex = reinterpret_cast<const uint32_t *>(s->d_tex + t.mat_base);
+    p.texcoords = s->dev.texcoords;
+    p.ti = s->dev.ti;
+    return MR_OK;
+}
+
+// what the entry points that shade without the texture lookup answer on a scene with a texture table
+mr_status refuse_textured(const mr_scene *s, const char *who) {
+    if (s->tex.blob.empty()) return MR_OK;
+    return fail(MR_ERR_STATE, "%s: the scene has a texture table (mr_scene_set_textures) and this call shades without the lookup; "
+                              "use the batched calls mr_trace -> mr_shade_lights, or mr_gen_shadow_rays -> mr_trace_indirect -> "
+                              "mr_shade_accumulate", who);
 }
 
 // LoadedTexture::LoadedTexture (Texture.cpp:30-92) for a FIT_RGBF image of W x H pixels: m_maxIntensity and the low-res image,
@@ -773,6 +821,7 @@ mr_status mr_shade_direct(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hit
     // this call shades a uniform material and knows occluders as a flag per ray (opaque occluders, see the header): in a
     // scene with a refractive material the light behind such an occluder is attenuated, not removed (Phong.cpp:99-113) --
     // mr_shade_accumulate (batched) and mr_render_direct / mr_trace_level (one launch) implement that
+    if ((st = refuse_textured(s, "mr_shade_direct")) != MR_OK) return st;
     if (s->dev.refractive)
         return fail(MR_ERR_STATE, "mr_shade_direct: the scene has a refractive material; use mr_shade_accumulate, mr_render_direct "
                                   "or mr_trace_level, which let light through refractive occluders as Phong.cpp:99-113 does");
@@ -826,6 +875,7 @@ mr_status mr_render_direct(mr_scene *s, const mr_frame_desc *frame, float *d_rgb
     mr_status st = require_device(s);
     if (st != MR_OK) return st;
     if (!frame || !d_rgb) return fail(MR_ERR_INVALID, "NULL argument");
+    if ((st = refuse_textured(s, "mr_render_direct")) != MR_OK) return st;
     if (frame->W == 0 || frame->H == 0) return fail(MR_ERR_INVALID, "empty image");
     if ((reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_shadow_hits) & 15) ||
         (reinterpret_cast<uintptr_t>(d_counts) & 7) || (reinterpret_cast<uintptr_t>(d_rgb) & 3))
@@ -840,6 +890,9 @@ mr_status mr_render_direct(mr_scene *s, const mr_frame_desc *frame, float *d_rgb
 
 mr_status mr_scene_set_materials(mr_scene *s, const mr_material *mats, uint32_t n_mats, const uint32_t *prim_material) {
     if (!s || !mats || n_mats == 0) return fail(MR_ERR_INVALID, "NULL argument or no materials");
+    if (!s->tex.blob.empty())
+        return fail(MR_ERR_STATE, "mr_scene_set_materials: the scene's texture table names materials by index; clear it first "
+                                  "(mr_scene_set_textures with n_textures = 0) and set it again afterwards");
     const uint32_t nt = s->mesh.n_triangles();
     if (prim_material)
         for (uint32_t i = 0; i < nt; i++)
@@ -887,9 +940,12 @@ mr_status mr_shade_accumulate(mr_scene *s, const mr_ray *d_rays, const mr_hit *d
         MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&s->d_light_scale), n * sizeof(float)));
         s->light_scale_cap = n;
     }
+    TexParams tex;
+    const bool textured = !s->tex.blob.empty();
+    if (textured && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
     return launch_shade_accumulate(s->dev, d_rays, d_hits, d_weights, d_pixels, n, d_shadow_rays, d_shadow_hits, d_shadow_src,
                                    reinterpret_cast<const unsigned long long *>(d_shadow_count), s->d_light_scale, *light, spp,
-                                   d_rgb, static_cast<hipStream_t>(stream));
+                                   d_rgb, textured ? &tex : nullptr, static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_gen_secondary_rays(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
@@ -930,6 +986,7 @@ mr_status mr_trace_level(mr_scene *s, const mr_level_desc *level, const mr_ray *
     mr_status st = require_device(s);
     if (st != MR_OK) return st;
     if (!level || !d_rays || !d_rgb) return fail(MR_ERR_INVALID, "NULL argument");
+    if ((st = refuse_textured(s, "mr_trace_level")) != MR_OK) return st;
     if (level->children > MR_LEVEL_PATH) return fail(MR_ERR_INVALID, "mr_trace_level: children must be MR_LEVEL_LAST, _SPECULAR or _PATH");
     if (level->children != MR_LEVEL_LAST && (!d_out_rays || !d_out_weights || !d_out_pixels || !d_out_count))
         return fail(MR_ERR_INVALID, "mr_trace_level: a level with children needs the output queue");
@@ -999,6 +1056,13 @@ mr_status mr_shade_lights(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hit
         (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3))
         return fail(MR_ERR_INVALID, "ray / hit buffers must be 16-byte aligned, counters 8-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
+    if (!s->tex.blob.empty()) {
+        TexParams tex;
+        if ((st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+        return launch_shade_lights_tex(s->dev, tex, s->lights.data(), (uint32_t)s->lights.size(), d_rays, d_hits, d_weights, d_pixels, n,
+                                       spp, flags, d_rgb, d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts),
+                                       static_cast<hipStream_t>(stream));
+    }
     return launch_shade_lights(s->dev, s->lights.data(), (uint32_t)s->lights.size(), d_rays, d_hits, d_weights, d_pixels, n, spp,
                                flags, d_rgb, d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
@@ -1086,6 +1150,156 @@ mr_status mr_shade_environment(mr_scene *s, const mr_ray *d_rays, const mr_hit *
     for (int c = 0; c < 3; c++) p.bg[c] = e.bg[c];
     return launch_shade_environment(p, d_rays, d_hits, d_weights, d_pixels, d_lowres, n, spp, flags, d_rgb, d_ray_rgb,
                                     reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_scene_set_texcoords(mr_scene *s, const float *texcoords, uint32_t n_texcoords, const uint32_t *tidx) {
+    if (!s) return fail(MR_ERR_INVALID, "mr_scene_set_texcoords: NULL scene");
+    if (n_texcoords > 0 && (!texcoords || !tidx)) return fail(MR_ERR_INVALID, "mr_scene_set_texcoords: NULL array with %u texture coordinates", n_texcoords);
+    const size_t nt = s->mesh.n_triangles();
+    for (size_t i = 0; i < 2 * (size_t)n_texcoords; i++)
+        if (!std::isfinite(texcoords[i])) return fail(MR_ERR_INVALID, "mr_scene_set_texcoords: texture coordinate %zu is not finite", i / 2);
+    if (n_texcoords > 0)
+        for (size_t i = 0; i < nt; i++) {
+            const uint32_t *t = tidx + 3 * i;
+            if (t[0] == kNoTexcoord && t[1] == kNoTexcoord && t[2] == kNoTexcoord) continue;
+            for (int k = 0; k < 3; k++)
+                if (t[k] >= n_texcoords) return fail(MR_ERR_INVALID, "mr_scene_set_texcoords: object %zu has texture coordinate %u of %u", i, t[k], n_texcoords);
+        }
+    if (n_texcoords > 0) {
+        s->mesh.t.assign(texcoords, texcoords + 2 * (size_t)n_texcoords);
+        s->mesh.ti.assign(tidx, tidx + 3 * nt);
+    } else {
+        s->mesh.t.clear();
+        s->mesh.ti.clear();
+    }
+    if (s->on_device) {
+        MR_HIP_CHECK(hipSetDevice(s->device));
+        MR_HIP_CHECK(hipDeviceSynchronize());
+        return upload_texcoords(s);
+    }
+    return MR_OK;
+}
+
+mr_status mr_scene_get_texcoords(const mr_scene *s, uint32_t *n_texcoords, float *texcoords, uint32_t *tidx) {
+    if (!s) return fail(MR_ERR_INVALID, "mr_scene_get_texcoords: NULL scene");
+    if (n_texcoords) *n_texcoords = (uint32_t)(s->mesh.t.size() / 2);
+    if (texcoords && !s->mesh.t.empty()) memcpy(texcoords, s->mesh.t.data(), s->mesh.t.size() * sizeof(float));
+    if (tidx)
+        for (size_t i = 0; i < s->mesh.vi.size(); i++) tidx[i] = i < s->mesh.ti.size() ? s->mesh.ti[i] : kNoTexcoord;
+    return MR_OK;
+}
+
+mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, uint32_t n_textures, const uint32_t *material_texture) {
+    if (!s) return fail(MR_ERR_INVALID, "mr_scene_set_textures: NULL scene");
+    if (n_textures > MR_MAX_TEXTURES) return fail(MR_ERR_INVALID, "mr_scene_set_textures: %u textures, at most %u", n_textures, (unsigned)MR_MAX_TEXTURES);
+    if (n_textures > 0 && !textures) return fail(MR_ERR_INVALID, "mr_scene_set_textures: NULL list of %u textures", n_textures);
+    if (n_textures == 0) {                     // clears the table (the materials keep the m_diffuse an earlier call gave them)
+        s->tex = HostTextures();
+        s->tex_dirty = false;
+        return MR_OK;
+    }
+    if (material_texture && s->materials.empty())
+        return fail(MR_ERR_INVALID, "mr_scene_set_textures: material_texture without a material table (mr_scene_set_materials)");
+    const uint32_t n_mats = s->materials.empty() ? 1u : (uint32_t)(s->materials.size() / 11);
+    HostTextures h;
+    h.n_textures = n_textures; h.n_materials = n_mats;
+    size_t texels = 0;
+    for (uint32_t i = 0; i < n_textures; i++) {
+        const mr_texture_desc &in = textures[i];
+        if (in.kind != MR_TEX_CHECKER && in.kind != MR_TEX_IMAGE) return fail(MR_ERR_INVALID, "texture %u: unknown kind %u", i, in.kind);
+        for (int k = 0; k < 5; k++)
+            if (in.reserved[k] != 0) return fail(MR_ERR_INVALID, "texture %u: mr_texture_desc.reserved must be 0", i);
+        if (in.kind == MR_TEX_CHECKER) {
+            for (int c = 0; c < 3; c++)
+                if (!std::isfinite(in.color1[c]) || !std::isfinite(in.color2[c])) return fail(MR_ERR_INVALID, "texture %u: the checker's colours must be finite", i);
+            if (!std::isfinite(in.scale)) return fail(MR_ERR_INVALID, "texture %u: the checker's scale must be finite", i);
+        } else {
+            if (in.W == 0 || in.H == 0 || !in.pixels) return fail(MR_ERR_INVALID, "texture %u: an image needs pixels and W, H > 0", i);
+            if (in.W > 65536u || in.H > 65536u) return fail(MR_ERR_INVALID, "texture %u: image of %u x %u pixels, at most 65536 each way", i, in.W, in.H);
+            if (in.hdr > 1) return fail(MR_ERR_INVALID, "texture %u: hdr must be 0 (FIT_BITMAP) or 1 (FIT_RGBF)", i);
+            const size_t n = 3 * (size_t)in.W * in.H;
+            for (size_t k = 0; k < n; k++)
+                if (!std::isfinite(in.pixels[k])) return fail(MR_ERR_INVALID, "texture %u: pixel value %zu is not finite", i, k);
+            texels += (size_t)in.W * in.H;
+        }
+    }
+    if (texels >= (1ull << 31)) return fail(MR_ERR_INVALID, "mr_scene_set_textures: %zu texels in all, fewer than 2^31", texels);
+    if (material_texture)
+        for (uint32_t i = 0; i < n_mats; i++)
+            if (material_texture[i] != kNoTexture && material_texture[i] >= n_textures)
+                return fail(MR_ERR_INVALID, "material %u names texture %u of %u", i, material_texture[i], n_textures);
+
+    h.texel_base = 3 * (size_t)n_textures;
+    h.mat_base = h.texel_base + texels;
+    h.blob.assign(h.mat_base + (n_mats + 3) / 4, make_float4(0.f, 0.f, 0.f, 0.f));
+    const auto bits = [](uint32_t v) { float f; memcpy(&f, &v, sizeof(f)); return f; };
+    size_t at = 0;
+    for (uint32_t i = 0; i < n_textures; i++) {
+        const mr_texture_desc &in = textures[i];
+        float4 *q = &h.blob[3 * (size_t)i];
+        if (in.kind == MR_TEX_CHECKER) {
+            q[0] = make_float4(bits(MR_TEX_CHECKER), 0.f, 0.f, 0.f);
+            q[1] = make_float4(in.color1[0], in.color1[1], in.color1[2], in.scale);
+            q[2] = make_float4(in.color2[0], in.color2[1], in.color2[2], 0.f);
+            continue;
+        }
+        float max_intensity = -1e15;                                              // Texture.cpp:34,41-50
+        float4 *px = &h.blob[h.texel_base + at];
+        for (size_t k = 0; k < (size_t)in.W * in.H; k++) {
+            const float *p = in.pixels + 3 * k;
+            for (int c = 0; c < 3; c++)
+                if (max_intensity < p[c]) max_intensity = p[c];
+            px[k] = make_float4(p[0], p[1], p[2], 0.f);
+        }
+        q[0] = make_float4(bits(MR_TEX_IMAGE), bits(in.W), bits(in.H), bits((uint32_t)at));
+        q[1] = make_float4(max_intensity, bits(in.hdr), 0.f, 0.f);
+        at += (size_t)in.W * in.H;
+    }
+    uint32_t *mat_tex = reinterpret_cast<uint32_t *>(&h.blob[h.mat_base]);
+    bool changed = false;
+    for (uint32_t i = 0; i < n_mats; i++) {
+        mat_tex[i] = material_texture ? material_texture[i] : kNoTexture;
+        if (mat_tex[i] == kNoTexture) continue;
+        // TexturedPhong::TexturedPhong (Texture.cpp:513-514): Phong(kd = 1, ks, kt, ...), so m_diffuse is what the constructor's
+        // clamp (Phong.cpp:29-31) makes of 1, whatever diffuse the caller's mr_material held
+        float *o = &s->materials[11 * (size_t)i];
+        for (int c = 0; c < 3; c++) {
+            const float kd = fmaxf(fminf(1.0f, 1.0f - o[3 + c] - o[6 + c]), 0.f);
+            if (o[c] != kd) { o[c] = kd; changed = true; }
+        }
+    }
+    s->tex = std::move(h);
+    s->tex_dirty = true;
+    if (changed && s->on_device) {
+        MR_HIP_CHECK(hipSetDevice(s->device));
+        MR_HIP_CHECK(hipDeviceSynchronize());
+        return upload_materials(s);
+    }
+    return MR_OK;
+}
+
+mr_status mr_hit_uv(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, uint64_t n, float *d_uv, void *stream) {
+    mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (!d_hits || !d_uv) return fail(MR_ERR_INVALID, "NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_uv) & 3))
+        return fail(MR_ERR_INVALID, "ray / hit buffers must be 16-byte aligned");
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    return launch_hit_uv(s->dev, d_rays, d_hits, n, d_uv, static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_texture_lookup(mr_scene *s, uint32_t texture, const float *d_uv, uint64_t n, float *d_rgb, uint64_t *d_counts, void *stream) {
+    mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (s->tex.blob.empty()) return fail(MR_ERR_STATE, "mr_texture_lookup: the scene has no textures (mr_scene_set_textures)");
+    if (texture >= s->tex.n_textures) return fail(MR_ERR_INVALID, "mr_texture_lookup: texture %u of %u", texture, s->tex.n_textures);
+    if (!d_uv || !d_rgb) return fail(MR_ERR_INVALID, "NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_uv) & 3) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_counts) & 7))
+        return fail(MR_ERR_INVALID, "float buffers must be 4-byte aligned, counters 8-byte aligned");
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    TexParams tex;
+    if ((st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+    return launch_texture_lookup(tex, texture, d_uv, n, d_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_tonemap(mr_scene *s, const float *d_rgb, uint64_t n_values, uint8_t *d_out, void *stream) {

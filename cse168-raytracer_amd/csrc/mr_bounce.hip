@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mr_internal.h"
+#include "mr_accumulate_body.h"
 #include "mr_launch.h"
 #include "mr_phong.h"
 #include "mr_recursion.h"
@@ -37,44 +38,9 @@ __global__ __launch_bounds__(kBlock) void light_scale_kernel(MeshMat m, const mr
     }
 }
 
-struct AccumArgs {
-    MeshMat m;
-    const mr_ray *rays;
-    const mr_hit *hits;
-    const float *weights;         // rgb per ray or NULL (= 1)
-    const uint32_t *pixels;       // pixel per ray or NULL (= ray index / spp)
-    const float *light_scale;     // per ray
-    LightArgs lt;
-    float inv_spp;
-    uint32_t spp;
-    unsigned long long n;
-    float *rgb;
-};
-
+// the body is shade_accumulate_body (mr_accumulate_body.h), which the textured form in mr_textures.hip shares
 __global__ __launch_bounds__(kBlock) void shade_accumulate_kernel(AccumArgs a) {
-    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
-    const unsigned long long n_round = (a.n + 63ull) & ~63ull;                            // whole waves: accumulate_runs shuffles
-    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < n_round; k += stride) {
-        float v[3] = {0.f, 0.f, 0.f};
-        uint32_t pix = 0xFFFFFFFFu;
-        if (k < a.n) {
-            pix = pixel_of(a.pixels, k, a.spp);
-            const float4 h = reinterpret_cast<const float4 *>(a.hits)[k];
-            const uint32_t prim = __float_as_uint(h.y);
-            const float scale = prim != MR_MISS ? a.light_scale[k] : 0.0f;                // a miss: m_bgColor = 0 contributes nothing
-            if (scale != 0.0f) {
-                float P[3], N[3], diffuse[3], highlight, out[3];
-                surface_point(a.m, a.rays, k, h, P, N);
-                const float4 rb = reinterpret_cast<const float4 *>(a.rays)[2 * k + 1];
-                phong_terms(a.lt, material_of(a.m, prim), P, N, rb.x, rb.y, rb.z, diffuse, highlight);
-                phong_combine(diffuse, highlight, scale, out);
-                float w[3];
-                weight_of(a.weights, k, w);
-                for (int c = 0; c < 3; c++) v[c] = out[c] * w[c] * a.inv_spp;
-            }
-        }
-        accumulate_runs(a.rgb, pix, v[0], v[1], v[2]);
-    }
+    shade_accumulate_body<false>(a, TexParams());
 }
 
 struct BounceArgs {
@@ -235,12 +201,13 @@ mr_status launch_shade_accumulate(const DeviceScene &ds, const mr_ray *d_rays, c
                                   const uint32_t *d_pixels, unsigned long long n, const mr_ray *d_shadow_rays,
                                   const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src,
                                   const unsigned long long *d_shadow_count, float *d_light_scale, const mr_light &light,
-                                  uint32_t spp, float *d_rgb, hipStream_t stream) {
+                                  uint32_t spp, float *d_rgb, const TexParams *tex, hipStream_t stream) {
     if (n == 0) return MR_OK;
     const MeshMat m = mesh_of(ds);
     hipLaunchKernelGGL(light_scale_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, m, d_shadow_rays, d_shadow_hits,
                        d_shadow_src, d_shadow_count, n, d_light_scale);
     MR_HIP_CHECK(hipGetLastError());
+    if (tex) return launch_shade_accumulate_tex(ds, *tex, d_rays, d_hits, d_weights, d_pixels, n, d_light_scale, light, spp, d_rgb, stream);
     AccumArgs a;
     a.m = m; a.rays = d_rays; a.hits = d_hits; a.weights = d_weights; a.pixels = d_pixels; a.light_scale = d_light_scale;
     a.lt = light_args_of(light); a.spp = spp; a.inv_spp = 1.0f / (float)spp; a.n = n; a.rgb = d_rgb;

@@ -14,7 +14,8 @@
 // a loop over the lanes).  The grid of the image variants is held to 8 workgroups per CU so that this copy stays small
 // beside the batch.
 //
-// The arithmetic of the lookup is the reference's, operation for operation in fp32 (this unit is compiled with
+// The arithmetic of the lookup is the reference's (the bilinear part is mr_texture.h, shared with the material textures),
+// operation for operation in fp32 (this unit is compiled with
 // -ffp-contract=off like the rest), on mm_atan2f / mm_asinf of miro_math.h: texture coordinates are the same bits as a host
 // restatement's.  powf is the device library's (the tolerance of the shaded value, as in mr_lights.hip).
 //
@@ -26,6 +27,7 @@
 #include "mr_internal.h"
 #include "mr_launch.h"
 #include "mr_recursion.h"
+#include "mr_texture.h"
 #include "mr_traverse.h"
 
 namespace mr {
@@ -60,24 +62,6 @@ __device__ __forceinline__ void env_coords(const float rot[2], float dx, float d
     if (phi > 2.0f * kPI) phi -= (2.0f * kPI);                          // :672
     u = phi / (2.0f * kPI);                                             // :675
     v = (float)((double)(theta / kPI) + 0.5);                           // :676 (0.5 is a double)
-}
-
-// Texture.cpp:170-178 for one axis: the two texel indices and the error term -- taken from the WRAPPED first index (:174).
-// false: the reference's arithmetic leaves the image (undefined there, defined as 0 here)
-__device__ __forceinline__ bool env_axis(int w, float c, int &i1, int &i2, float &err) {
-    const float p = (float)w * c;                                       // :170
-    if (!(fabsf(p) < 2147483520.0f)) return false;                      // NaN, or (int)p overflows
-    i1 = (int)p; i2 = i1 + 1;                                           // :172
-    i1 %= w; i2 %= w;                                                   // :173
-    err = p - (float)i1;                                                // :174
-    return i1 >= 0 && i2 >= 0;
-}
-
-// Texture.cpp:181 for one channel, then tonemapValue (:27): std::min(a, b) = b < a ? b : a keeps a NaN
-__device__ __forceinline__ float env_blend(float p11, float p21, float p12, float p22, float xe, float ye, float max_intensity) {
-    const float f = (p11 * (1 - xe) + p21 * xe) * (1 - ye) + (p12 * (1 - xe) + p22 * xe) * ye;
-    const float a = powf(f / max_intensity, 0.5f) * 1.5f;
-    return 1.0f < a ? 1.0f : a;
 }
 
 template <bool IMAGE, bool WEIGHTS, bool PIXELS>
@@ -116,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void shade_environment_kernel(EnvArgs a) {
                 float u, v, xe = 0.f, ye = 0.f;
                 int x1 = 0, x2 = 0, y1 = 0, y2 = 0;
                 env_coords(a.env.rot, rb.x, rb.y, rb.z, u, v);
-                const bool okx = env_axis(w, u, x1, x2, xe), oky = env_axis(h, v, y1, y2, ye);
+                const bool okx = bilinear_axis(w, u, x1, x2, xe), oky = bilinear_axis(h, v, y1, y2, ye);
                 if (okx && oky) {
                     float4 p11, p21, p12, p22;
                     if (low) {
@@ -125,9 +109,9 @@ __global__ __launch_bounds__(kBlock) void shade_environment_kernel(EnvArgs a) {
                         const float4 *r1 = a.env.full + (size_t)y1 * w, *r2 = a.env.full + (size_t)y2 * w;
                         p11 = r1[x1]; p21 = r1[x2]; p12 = r2[x1]; p22 = r2[x2];
                     }
-                    val[0] = env_blend(p11.x, p21.x, p12.x, p22.x, xe, ye, a.env.max_intensity);
-                    val[1] = env_blend(p11.y, p21.y, p12.y, p22.y, xe, ye, a.env.max_intensity);
-                    val[2] = env_blend(p11.z, p21.z, p12.z, p22.z, xe, ye, a.env.max_intensity);
+                    val[0] = bilinear_blend(p11.x, p21.x, p12.x, p22.x, xe, ye, a.env.max_intensity);
+                    val[1] = bilinear_blend(p11.y, p21.y, p12.y, p22.y, xe, ye, a.env.max_intensity);
+                    val[2] = bilinear_blend(p11.z, p21.z, p12.z, p22.z, xe, ye, a.env.max_intensity);
                 } else {
                     my_undefined++;
                 }

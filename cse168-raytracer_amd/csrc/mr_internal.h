@@ -47,6 +47,8 @@ struct HostTree {
 // (Scene.cpp:220-230); a hit on plane k reports prim = kPlaneBit | k.
 constexpr uint32_t kSphereSlot = 0xFFFFFFFFu;
 constexpr uint32_t kPlaneBit = 0x80000000u;
+constexpr uint32_t kNoTexcoord = 0xFFFFFFFFu;   // a texture-coordinate index: the triangle's mesh has none (numTextCoords() == 0)
+constexpr uint32_t kNoTexture = 0xFFFFFFFFu;    // a material's texture id: plain Phong
 constexpr uint32_t kSphereTag = 0x7fc00168u;   // bits of q2.w of a sphere's 48-byte leaf record (a NaN no product yields)
 
 struct HostMesh {
@@ -54,6 +56,9 @@ struct HostMesh {
     std::vector<uint32_t> vi, ni;   // 3 per object
     std::vector<float> spheres;     // cx, cy, cz, radius
     std::vector<float> planes;      // normal xyz, origin xyz
+    std::vector<float> t;           // texture coordinates, uv pairs (TriangleMesh::m_texCoords); empty: no object has any
+    std::vector<uint32_t> ti;       // 3 per object, kNoTexcoord in all three = the object's mesh has none; may be shorter than
+                                    // vi (objects added without texture coordinates behind the last one that had some)
     std::vector<uint32_t> plane_material;
     uint32_t n_vertices() const { return (uint32_t)(v.size() / 3); }
     uint32_t n_normals() const { return (uint32_t)(n.size() / 3); }
@@ -104,6 +109,9 @@ struct DeviceScene {
     float4   *spheres = nullptr;       // (c.xyz, radius) per sphere; nullptr when the scene has none
     float4   *planes = nullptr;        // 2 per plane; nullptr when the scene has none
     uint32_t n_spheres = 0, n_planes = 0;
+    // texture coordinates (mr_uv.h): uv pairs and three indices per object; both nullptr when no object has any
+    float    *texcoords = nullptr;
+    uint32_t *ti = nullptr;
     float root_lo[3] = {0, 0, 0}, root_hi[3] = {0, 0, 0};
     int32_t root_ref = 0;
     uint32_t n_inner = 0, n_tris = 0, stack_depth = 1;
@@ -192,11 +200,13 @@ inline mr_status launch_frame(const DeviceScene &ds, const mr_frame_desc &fd, fl
                                   : launch_frame_b256(ds, fd, d_rgb, d_hits, d_shadow_hits, d_counts, work_counter, eye_pool, stream);
 }
 
+// tex: the scene's texture table (below), or NULL for the untextured kernel
+struct TexParams;
 mr_status launch_shade_accumulate(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
                                   const uint32_t *d_pixels, unsigned long long n, const mr_ray *d_shadow_rays,
                                   const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src,
                                   const unsigned long long *d_shadow_count, float *d_light_scale, const mr_light &light,
-                                  uint32_t spp, float *d_rgb, hipStream_t stream);
+                                  uint32_t spp, float *d_rgb, const TexParams *tex, hipStream_t stream);
 mr_status launch_secondary_rays(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
                                 const uint32_t *d_pixels, unsigned long long n, uint32_t spp, mr_ray *d_out_rays,
                                 float *d_out_weights, uint32_t *d_out_pixels, unsigned long long *d_count,
@@ -223,6 +233,35 @@ mr_status launch_shade_lights(const DeviceScene &ds, const ShadeLight *lights, u
                               const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels, unsigned long long n,
                               uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts,
                               hipStream_t stream);
+
+// 2-D textures of TexturedPhong materials (mr_textures.hip; Texture.h:112-133, Texture.cpp:23-28,131-185, Phong.cpp:51-56).  The
+// host copy is one blob as the device holds it: three float4 per texture (TexParams below), then the texels of the
+// image textures as 16-byte records (r, g, b, 0) like the environment's, then one texture id per material.
+struct HostTextures {
+    uint32_t n_textures = 0, n_materials = 0;
+    size_t texel_base = 0, mat_base = 0;       // offsets into blob, in float4
+    std::vector<float4> blob;                  // empty: the scene has no texture table
+};
+struct TexParams {                             // the table as the kernels take it
+    const float4 *recs;                        // 3 per texture: (kind, W, H, first texel as bits) (color1 | max_intensity, hdr) (color2)
+    const float4 *texels;
+    const uint32_t *mat_tex;                   // per material: texture id or kNoTexture
+    const float *texcoords;                    // the scene's texture coordinates (mr_uv.h), nullptr: none
+    const uint32_t *ti;
+};
+// the textured forms of shade_lights_kernel / shade_accumulate_kernel and the two inspection kernels (mr_textures.hip)
+mr_status launch_shade_lights_tex(const DeviceScene &ds, const TexParams &tex, const ShadeLight *lights, uint32_t n_lights,
+                                  const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels,
+                                  unsigned long long n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb,
+                                  unsigned long long *d_counts, hipStream_t stream);
+mr_status launch_shade_accumulate_tex(const DeviceScene &ds, const TexParams &tex, const mr_ray *d_rays, const mr_hit *d_hits,
+                                      const float *d_weights, const uint32_t *d_pixels, unsigned long long n,
+                                      const float *d_light_scale, const mr_light &light, uint32_t spp, float *d_rgb,
+                                      hipStream_t stream);
+mr_status launch_hit_uv(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, unsigned long long n, float *d_uv,
+                        hipStream_t stream);
+mr_status launch_texture_lookup(const TexParams &tex, uint32_t texture, const float *d_uv, unsigned long long n, float *d_rgb,
+                                unsigned long long *d_counts, hipStream_t stream);
 
 // The environment of rays that miss (mr_environment.hip; Scene::getEnvironmentMap, Scene.cpp:657-688).  The host copy is what
 // mr_scene_set_environment made of the caller's image (LoadedTexture::LoadedTexture, Texture.cpp:30-92); the device copy holds
@@ -336,4 +375,9 @@ struct mr_scene {
     mr::HostEnvironment env;
     float4 *d_env = nullptr;
     bool env_dirty = false;
+    // the texture table of mr_scene_set_textures.  d_tex: its device copy, uploaded by the first shading call after a change
+    // (tex_dirty), like the environment's
+    mr::HostTextures tex;
+    float4 *d_tex = nullptr;
+    bool tex_dirty = false;
 };

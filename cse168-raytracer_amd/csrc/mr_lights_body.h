@@ -1,0 +1,127 @@
+// mr_lights_body.h -- the body of shade_lights_kernel (mr_lights.hip, where the kernel is described) as a __device__
+// template, so that its textured form (mr_textures.hip) is the same code with one more step: TEX looks the hit's
+// diffuseColor up once per hit, before the light loop, as Phong.cpp:51-56 does, and keeps the colour (three registers)
+// across the shadow traversals.  Without TEX the colour is the material's own m_diffuse, read where it is used: the
+// untextured kernels are what they were -- the arguments are taken BY VALUE for that: through a reference to the kernel's
+// argument block the same body compiles to other register and scratch figures.  Included by the .hip units that instantiate it (everything here is local to its unit).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "mr_internal.h"
+#include "mr_launch.h"
+#include "mr_phong.h"
+#include "mr_recursion.h"
+#include "mr_texture.h"
+#include "mr_traverse.h"
+#include "mr_uv.h"
+
+namespace mr {
+namespace {
+
+struct LightsArgs {
+    TraceParams tp;              // scene arrays, root box; tp.rays = the batch, tp.n its length
+    rec::MeshMat m;
+    const mr_hit *hits;
+    const float *weights;        // rgb per ray or NULL (= 1)
+    const uint32_t *pixels;      // pixel per ray or NULL (= ray index / spp)
+    uint32_t spp, n_lights;
+    float inv_spp;
+    float *rgb;                  // may be NULL (then ray_rgb is not)
+    float *ray_rgb;              // may be NULL: the un-weighted L of every ray
+    unsigned long long *counts;  // optional: [0] += shadow rays traced
+    ShadeLight lights[MR_MAX_LIGHTS];
+};
+
+template <int VAR, bool ANY, bool TEX>
+__device__ __forceinline__ void shade_lights_body(const LightsArgs a, const TexParams t) {
+    using namespace rec;
+    extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
+    const int tid = threadIdx.x;
+    const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
+    const unsigned long long n = a.tp.n;
+    const unsigned long long n_round = whole_workgroups(n);
+    Stats st = {0ull, 0ull};
+    unsigned my_shadow_rays = 0;
+
+    for (unsigned long long k = (unsigned long long)xcd_block_id() * kTraceBlock + tid; k < n_round; k += stride) {
+        const bool live = k < n;
+        float4 h = make_float4(0.f, __uint_as_float(MR_MISS), 0.f, 0.f);
+        if (live) h = reinterpret_cast<const float4 *>(a.hits)[k];
+        const bool hit = __float_as_uint(h.y) != MR_MISS;              // a miss contributes nothing (m_bgColor = 0)
+        float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 1.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
+        const float *mt = a.m.mats;
+        float col[3] = {0.f, 0.f, 0.f};                                // TEX: diffuseColor
+        if (hit) {
+            surface_point(a.m, a.tp.rays, k, h, P, N);
+            const float4 rb = reinterpret_cast<const float4 *>(a.tp.rays)[2 * k + 1];
+            d[0] = rb.x; d[1] = rb.y; d[2] = rb.z;
+            mt = material_of(a.m, __float_as_uint(h.y));
+            if (TEX) diffuse_color_of(a.m, t, material_id(a.m.s, a.m.prim_mat, __float_as_uint(h.y)), __float_as_uint(h.y), P, col);
+            my_shadow_rays += a.n_lights;
+        }
+        const float *dc = TEX ? col : mt;
+
+        float L[3] = {0.f, 0.f, 0.f};
+        for (uint32_t li = 0; li < a.n_lights; li++) {                 // Phong.cpp:63, wave-uniform
+            const ShadeLight &lt = a.lights[li];
+            float4 sh;
+            {
+                float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(1.f, 1.f, 1.f, -1.f);
+                if (hit) shadow_ray_for(lt, P, sa, sb);
+                const mr_hit hs = trace_hit<true, ANY, false, VAR>(a.tp, sa, sb, sb.w, hit, s_stack, tid, st);
+                sh = *reinterpret_cast<const float4 *>(&hs);
+            }
+            if (hit) {
+                float4 sa, sb;
+                shadow_ray_for(lt, P, sa, sb);                         // rebuilt rather than kept across the traversal
+                const float scale = light_scale_of(a.m, sa, sb, sh);
+                float diffuse[3] = {0.f, 0.f, 0.f}, highlight = 0.0f, out[3] = {0.f, 0.f, 0.f};
+                bool lit = scale != 0.0f;                              // Phong.cpp:100-111: the light is skipped
+                if (lit) {
+                    if (lt.kind == MR_LIGHT_DISC) {
+                        const float l[3] = {sb.x, sb.y, sb.z};
+                        lit = disc_terms(lt, mt, dc, P, N, l, d[0], d[1], d[2], diffuse, highlight);
+                    } else {
+                        phong_terms(lt.position, lt.color, lt.wattage, mt, dc, P, N, d[0], d[1], d[2], diffuse, highlight);
+                    }
+                }
+                if (lit) phong_combine(diffuse, highlight, scale, out);
+                L[0] += out[0]; L[1] += out[1]; L[2] += out[2];
+            }
+        }
+
+        if (a.ray_rgb && live) { a.ray_rgb[3 * k] = L[0]; a.ray_rgb[3 * k + 1] = L[1]; a.ray_rgb[3 * k + 2] = L[2]; }
+        if (a.rgb) {                                                   // wave-uniform
+            uint32_t pix = 0xFFFFFFFFu;
+            float v[3] = {0.f, 0.f, 0.f};
+            if (live) pix = pixel_of(a.pixels, k, a.spp);
+            if (hit) {
+                float w[3];
+                weight_of(a.weights, k, w);
+                for (int c = 0; c < 3; c++) v[c] = L[c] * w[c] * a.inv_spp;
+            }
+            accumulate_runs(a.rgb, pix, v[0], v[1], v[2]);
+        }
+    }
+
+    if (a.counts) workgroup_add<kTraceBlock>(my_shadow_rays, &a.counts[0]);
+}
+
+// what launch_shade_lights and its textured form fill in the same way
+inline LightsArgs lights_args_of(const DeviceScene &ds, const ShadeLight *lights, uint32_t n_lights, const mr_ray *d_rays,
+                                 const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels, unsigned long long n,
+                                 uint32_t spp, float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts) {
+    LightsArgs a;
+    a.tp = scene_trace_params(ds);
+    a.tp.rays = d_rays; a.tp.n = n;
+    a.m = rec::mesh_of(ds);
+    a.hits = d_hits; a.weights = d_weights; a.pixels = d_pixels;
+    a.spp = spp; a.n_lights = n_lights; a.inv_spp = 1.0f / (float)spp;
+    a.rgb = d_rgb; a.ray_rgb = d_ray_rgb; a.counts = d_counts;
+    for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = lights[i < n_lights ? i : 0];
+    return a;
+}
+
+}  // namespace
+}  // namespace mr

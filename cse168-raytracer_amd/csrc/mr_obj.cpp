@@ -2,6 +2,10 @@
 // normal values (and therefore hit t / P / N) agree with TriangleMesh::load:
 //   * records are read in chunks of at most 79 characters (fgets(line, 80, fp), TriangleMeshLoad.cpp:119,180)
 //   * only "v", "vn", "vt", "f" records; faces are triangles; indices are 1-based v, v/t, v/t/n, v//n (:81-111)
+//   * vt -> (u, v) as read (:154-158); a face corner's texture index is kept when it is non-zero (:198-204, :228-250).  A file
+//     without vt records gives a mesh without texture coordinates (numTextCoords() == 0: kNoTexcoord in all three indices
+//     of its triangles).  In a file WITH vt records, a corner without a texture index leaves m_texCoordIndices
+//     uninitialised in the reference; here it is index 0 of the file's coordinates, and so is an index outside them
 //   * v -> ctm * v with w = 1 (Matrix4x4.h:581-587); vn -> normalise((ctm^-1)^T * n) (:176-178,:184-197)
 //   * a face whose LAST corner has no normal index gets three copies of its face normal (:252-281);
 //     those synthesised normals are later replaced by the average of all normals incident on the
@@ -122,7 +126,8 @@ mr_status load_obj(const char *path, const float *ctm16, HostMesh &mesh, uint32_
 
     std::vector<F3> verts, normals;
     std::vector<char> synthesised;            // per normal slot: must be averaged
-    std::vector<uint32_t> vidx, nidx;
+    std::vector<uint32_t> vidx, nidx, tidx;
+    std::vector<float> texcoords;             // uv pairs
     std::vector<std::pair<uint32_t, uint32_t>> incidence;   // (vertex, normal slot) in encounter order
 
     // walk the file in fgets(…, 80) records: up to 79 bytes, ending after '\n'
@@ -144,7 +149,8 @@ mr_status load_obj(const char *path, const float *ctm16, HostMesh &mesh, uint32_
                 normals.push_back(unit(nctm.apply({x, y, z})));
                 synthesised.push_back(0);
             } else if (rec[1] == 't') {
-                // texture coordinates do not take part in intersection
+                sscanf(rec + 2, "%f %f", &x, &y);
+                texcoords.push_back(x); texcoords.push_back(y);
             } else {
                 sscanf(rec + 1, "%f %f %f", &x, &y, &z);
                 verts.push_back(ctm.apply({x, y, z}));
@@ -174,7 +180,7 @@ mr_status load_obj(const char *path, const float *ctm16, HostMesh &mesh, uint32_
                 }
                 for (int k = 0; k < 3; k++) incidence.emplace_back(tri_v[k], tri_n[k]);
             }
-            for (int k = 0; k < 3; k++) { vidx.push_back(tri_v[k]); nidx.push_back(tri_n[k]); }
+            for (int k = 0; k < 3; k++) { vidx.push_back(tri_v[k]); nidx.push_back(tri_n[k]); tidx.push_back(c[k].t > 0 ? (uint32_t)(c[k].t - 1) : 0u); }
         }
     }
     for (uint32_t ni : nidx)
@@ -185,6 +191,12 @@ mr_status load_obj(const char *path, const float *ctm16, HostMesh &mesh, uint32_
     for (auto &e : incidence)
         if (e.second >= normals.size())
             return fail(MR_ERR_IO, "\"%s\": normal index %u out of range", path, e.second + 1);
+
+    // A texture index outside the file's vt records is read out of bounds by the reference only when a texture is looked up
+    // (Triangle.cpp:184-186), not by the loader: such a file loads, and the index becomes 0 like a missing one.
+    const uint32_t n_tex = (uint32_t)(texcoords.size() / 2);
+    for (uint32_t &ti : tidx)
+        if (ti >= n_tex) ti = 0;
 
     // smooth the synthesised normals: CSR of (vertex -> incident normal slots) in encounter order
     {
@@ -209,6 +221,12 @@ mr_status load_obj(const char *path, const float *ctm16, HostMesh &mesh, uint32_
     for (auto &p : normals) { mesh.n.push_back(p.x); mesh.n.push_back(p.y); mesh.n.push_back(p.z); }
     for (uint32_t i : vidx) mesh.vi.push_back(i + vbase);
     for (uint32_t i : nidx) mesh.ni.push_back(i + nbase);
+    if (n_tex) {
+        const uint32_t tbase = (uint32_t)(mesh.t.size() / 2);
+        mesh.ti.resize(mesh.vi.size() - vidx.size(), kNoTexcoord);      // the objects in front of this mesh that have none
+        mesh.t.insert(mesh.t.end(), texcoords.begin(), texcoords.end());
+        for (uint32_t i : tidx) mesh.ti.push_back(i + tbase);
+    }
     if (n_tris_out) *n_tris_out = (uint32_t)(vidx.size() / 3);
     return MR_OK;
 }

@@ -94,42 +94,63 @@ __device__ __forceinline__ float highlight_of(const float l[3], const float N[3]
 }
 // Phong.cpp:146-156 once the light has given l, nDotL and its falloff factor f2: diffuse[c] (to be multiplied by the light
 // scale, :146) and the highlight (added unscaled; 0 for a material of infinite shininess)
+// dc: the hit's diffuseColor (Phong.cpp:51-56) -- the texture's colour for a TexturedPhong (mr_texture.h), m_diffuse itself for a
+// plain Phong (Phong::diffuse2D), which is the second form.  The highlight does not see it.
+__device__ __forceinline__ void lit_terms(const float color[3], float wattage, const float *mt, const float *dc, const float N[3],
+                                          const float l[3], float nDotL, float f2, float dx, float dy, float dz, float diffuse[3],
+                                          float &highlight) {
+    const float diff = fmaxf(0.0f, nDotL * f2 * wattage);
+    for (int c = 0; c < 3; c++) diffuse[c] = color[c] * (diff * dc[c] * mt[c]);               // :146
+    highlight = mt[9] < __builtin_huge_valf() ? highlight_of(l, N, dx, dy, dz, f2, wattage) : 0.0f;
+}
 __device__ __forceinline__ void lit_terms(const float color[3], float wattage, const float *mt, const float N[3], const float l[3],
                                           float nDotL, float f2, float dx, float dy, float dz, float diffuse[3], float &highlight) {
-    const float diff = fmaxf(0.0f, nDotL * f2 * wattage);
-    for (int c = 0; c < 3; c++) diffuse[c] = color[c] * (diff * mt[c] * mt[c]);               // :146
-    highlight = mt[9] < __builtin_huge_valf() ? highlight_of(l, N, dx, dy, dz, f2, wattage) : 0.0f;
+    lit_terms(color, wattage, mt, mt, N, l, nDotL, f2, dx, dy, dz, diffuse, highlight);
 }
 
 // Phong::shade's direct light at a hit (Phong.cpp:116-156) for a point light at L, in lit_terms' two parts.  The shaded value
 // of a hit with light scale s != 0 is diffuse[c] * s + highlight, and 0 for s == 0 (Phong.cpp:100-103 skips the light).
-// mt: the hit's material record; N normalised; (dx, dy, dz) the direction of the ray that produced the hit.
-__device__ __forceinline__ void phong_terms(const float L[3], const float color[3], float wattage, const float *mt, const float P[3],
-                                            const float N[3], float dx, float dy, float dz, float diffuse[3], float &highlight) {
+// mt: the hit's material record, dc its diffuseColor (lit_terms; the forms without dc are a plain Phong's); N normalised;
+// (dx, dy, dz) the direction of the ray that produced the hit.
+__device__ __forceinline__ void phong_terms(const float L[3], const float color[3], float wattage, const float *mt, const float *dc,
+                                            const float P[3], const float N[3], float dx, float dy, float dz, float diffuse[3],
+                                            float &highlight) {
     float l[3] = {L[0] - P[0], L[1] - P[1], L[2] - P[2]};
     const float falloff = (l[0] * l[0] + l[1] * l[1]) + l[2] * l[2];
     const float inv = 1.0f / sqrtf(falloff);
     l[0] *= inv; l[1] *= inv; l[2] *= inv;
     const float nDotL = (N[0] * l[0] + N[1] * l[1]) + N[2] * l[2];
     const float f2 = 1.0f / (falloff * 4.0f * kPhongPI * kPhongPI);                           // :140
-    lit_terms(color, wattage, mt, N, l, nDotL, f2, dx, dy, dz, diffuse, highlight);
+    lit_terms(color, wattage, mt, dc, N, l, nDotL, f2, dx, dy, dz, diffuse, highlight);
+}
+__device__ __forceinline__ void phong_terms(const float L[3], const float color[3], float wattage, const float *mt, const float P[3],
+                                            const float N[3], float dx, float dy, float dz, float diffuse[3], float &highlight) {
+    phong_terms(L, color, wattage, mt, mt, P, N, dx, dy, dz, diffuse, highlight);
+}
+__device__ __forceinline__ void phong_terms(const LightArgs &a, const float *mt, const float *dc, const float P[3], const float N[3],
+                                            float dx, float dy, float dz, float diffuse[3], float &highlight) {
+    phong_terms(a.L, a.color, a.wattage, mt, dc, P, N, dx, dy, dz, diffuse, highlight);
 }
 __device__ __forceinline__ void phong_terms(const LightArgs &a, const float *mt, const float P[3], const float N[3], float dx,
                                             float dy, float dz, float diffuse[3], float &highlight) {
-    phong_terms(a.L, a.color, a.wattage, mt, P, N, dx, dy, dz, diffuse, highlight);
+    phong_terms(a.L, a.color, a.wattage, mt, mt, P, N, dx, dy, dz, diffuse, highlight);
 }
 // Phong.cpp:121-136 for a DirectionalAreaLight.  l: the normalised direction (the shadow ray's).  Returns false when the hit
 // lies outside the disc's cylinder (:133, the light is skipped); otherwise lit_terms with nDotL = dot(N, -normal) on the
 // normal as given and falloff = 1 / PI.
-__device__ __forceinline__ bool disc_terms(const ShadeLight &lt, const float *mt, const float P[3], const float N[3], const float l[3],
-                                           float dx, float dy, float dz, float diffuse[3], float &highlight) {
+__device__ __forceinline__ bool disc_terms(const ShadeLight &lt, const float *mt, const float *dc, const float P[3], const float N[3],
+                                           const float l[3], float dx, float dy, float dz, float diffuse[3], float &highlight) {
     const float *n = lt.normal;
     const float nDotL = (N[0] * -n[0] + N[1] * -n[1]) + N[2] * -n[2];                          // :128
     const float t = ((n[0] * (lt.position[0] - P[0]) + n[1] * (lt.position[1] - P[1])) + n[2] * (lt.position[2] - P[2])) / -1.0f;   // :132
     const float qx = (P[0] - n[0] * t) - lt.position[0], qy = (P[1] - n[1] * t) - lt.position[1], qz = (P[2] - n[2] * t) - lt.position[2];
     if ((qx * qx + qy * qy) + qz * qz > lt.radius * lt.radius) return false;                   // :133
-    lit_terms(lt.color, lt.wattage, mt, N, l, nDotL, 1.0f / kPhongPI, dx, dy, dz, diffuse, highlight);   // :135
+    lit_terms(lt.color, lt.wattage, mt, dc, N, l, nDotL, 1.0f / kPhongPI, dx, dy, dz, diffuse, highlight);   // :135
     return true;
+}
+__device__ __forceinline__ bool disc_terms(const ShadeLight &lt, const float *mt, const float P[3], const float N[3], const float l[3],
+                                           float dx, float dy, float dz, float diffuse[3], float &highlight) {
+    return disc_terms(lt, mt, mt, P, N, l, dx, dy, dz, diffuse, highlight);
 }
 
 __device__ __forceinline__ void phong_combine(const float diffuse[3], float highlight, float scale, float out[3]) {

@@ -69,6 +69,9 @@ mr_status mr_trace_photons(mr_scene *s, mr_photon_map *map, const mr_photon_trac
     if (s->device != photon_map_device(map)) return fail(MR_ERR_INVALID, "mr_trace_photons: scene on device %d, photon map on device %d", s->device, photon_map_device(map));
     if (!s->built) return fail(MR_ERR_STATE, "mr_bvh_build has not been called on this scene");
     if (!s->on_device) return fail(MR_ERR_STATE, "scene was built host_only: nothing is resident on a device and there is no CPU fallback");
+    if (!s->tex.blob.empty())                // the roulette reads diffuse2D (Scene.cpp:545-551); the walk has no texture lookup
+        return fail(MR_ERR_STATE, "mr_trace_photons: the scene has a texture table (mr_scene_set_textures) and the photon walk's roulette "
+                                  "has no texture lookup; trace photons before setting textures, or clear them (n_textures = 0)");
     if (photon_map_balanced(map)) return fail(MR_ERR_STATE, "photon map is immutable after mr_photon_map_balance");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     g_timing = Timing();

@@ -35,6 +35,10 @@ MR_ENV_LOWRES = 1 << 16
 MR_LIGHT_POINT, MR_LIGHT_DISC = 0, 1
 MR_MAX_LIGHTS = 8
 
+MR_TEX_CHECKER, MR_TEX_IMAGE = 0, 1
+MR_MAX_TEXTURES = 16
+MR_NO_TEXTURE = MR_NO_TEXCOORD = 0xFFFFFFFF
+
 MR_OK, MR_ERR_INVALID, MR_ERR_IO, MR_ERR_NOMEM, MR_ERR_HIP, MR_ERR_STATE = 0, -1, -2, -3, -4, -5
 
 # every symbol include/miro_hip.h declares (tests check the library exports each one)
@@ -52,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "mr_trace_photons", "mr_trace_photons_timing",
     "mr_scene_set_lights", "mr_shade_lights",
     "mr_scene_set_environment", "mr_scene_get_environment", "mr_shade_environment",
+    "mr_scene_set_texcoords", "mr_scene_get_texcoords", "mr_scene_set_textures", "mr_hit_uv", "mr_texture_lookup",
     "mr_last_error", "mr_version",
 ]
 
@@ -146,6 +151,13 @@ class EnvironmentDesc(C.Structure):
                 ("rotation", C.c_float * 2), ("reserved", C.c_uint32 * 6)]
 
 
+class TextureDesc(C.Structure):
+    """mr_texture_desc (miro_hip.h): a CheckerBoardTexture or a LoadedTexture"""
+    _fields_ = [("kind", C.c_uint32), ("color1", C.c_float * 3), ("color2", C.c_float * 3), ("scale", C.c_float),
+                ("pixels", C.POINTER(C.c_float)), ("W", C.c_uint32), ("H", C.c_uint32), ("hdr", C.c_uint32),
+                ("reserved", C.c_uint32 * 5)]
+
+
 class PhotonTraceDesc(C.Structure):
     _fields_ = [("light", DiscLight), ("target", C.c_uint32), ("max_emissions", C.c_uint32), ("caustic", C.c_uint32),
                 ("seed", C.c_uint32), ("max_depth", C.c_uint32), ("round_emissions", C.c_uint32), ("reserved", C.c_uint32 * 6)]
@@ -236,6 +248,11 @@ def load_library(path=None):
     L.mr_scene_set_environment.argtypes = [vp, C.POINTER(EnvironmentDesc)]
     L.mr_scene_get_environment.argtypes = [vp, C.c_uint32, u32p, u32p, f32p, f32p]
     L.mr_shade_environment.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.mr_scene_set_texcoords.argtypes = [vp, f32p, C.c_uint32, u32p]
+    L.mr_scene_get_texcoords.argtypes = [vp, u32p, f32p, u32p]
+    L.mr_scene_set_textures.argtypes = [vp, C.POINTER(TextureDesc), C.c_uint32, u32p]
+    L.mr_hit_uv.argtypes = [vp, vp, vp, C.c_uint64, vp, vp]
+    L.mr_texture_lookup.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
     L.mr_photon_map_create.argtypes = [C.c_int32, C.c_uint32, C.POINTER(vp)]
     L.mr_photon_map_destroy.argtypes = [vp]
     L.mr_photon_map_store.argtypes = [vp, C.c_uint32, f32p, f32p, f32p]
@@ -337,6 +354,7 @@ class Scene:
         self.h = C.c_void_p()
         _check(self.L.mr_scene_create(device, C.byref(self.h)))
         self.device = device
+        self.n_textures = 0            # textures of the last set_textures (FrameRenderer.render_specular reads it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -686,6 +704,66 @@ class Scene:
             return t.data_ptr() if t is not None else None
         _check(self.L.mr_shade_environment(self.h, d_rays.data_ptr(), d_hits.data_ptr(), ptr(d_weights), ptr(d_pixels), ptr(d_lowres),
                                            n, spp, flags, ptr(d_rgb), ptr(d_ray_rgb), ptr(d_counts), _stream_ptr(stream)))
+
+    def set_texcoords(self, texcoords, tidx):
+        """mr_scene_set_texcoords: texcoords [n, 2] float32 and tidx [objects, 3] uint32 in addObject order (MR_NO_TEXCOORD in
+        all three = the triangle's mesh has none); texcoords=None (or empty) clears the table."""
+        if texcoords is None or len(texcoords) == 0:
+            _check(self.L.mr_scene_set_texcoords(self.h, None, 0, None))
+            return
+        t = np.ascontiguousarray(texcoords, dtype=np.float32).reshape(-1, 2)
+        ti = np.ascontiguousarray(tidx, dtype=np.uint32).reshape(-1, 3)
+        if len(ti) != self.info().n_triangles:
+            raise ValueError("set_texcoords: tidx must hold three indices for each of the scene's %d objects" % self.info().n_triangles)
+        _check(self.L.mr_scene_set_texcoords(self.h, _f32p(t), len(t), _u32p(ti)))
+
+    def get_texcoords(self):
+        """mr_scene_get_texcoords: (texcoords [n, 2] float32, tidx [objects, 3] uint32)"""
+        n = C.c_uint32(0)
+        _check(self.L.mr_scene_get_texcoords(self.h, C.byref(n), None, None))
+        t = np.zeros((n.value, 2), np.float32)
+        ti = np.zeros((self.info().n_triangles, 3), np.uint32)
+        _check(self.L.mr_scene_get_texcoords(self.h, None, _f32p(t) if n.value else None, _u32p(ti) if len(ti) else None))
+        return t, ti
+
+    def set_textures(self, textures, material_texture=None):
+        """mr_scene_set_textures.  textures: TextureDesc objects or dicts -- dict(color1, color2, scale) is a checker,
+        dict(pixels [H, W, 3] float32 with row 0 = the bottom scanline, hdr) an image; an empty list clears the table.
+        material_texture: a texture id per material (MR_NO_TEXTURE = plain Phong).  A material that names a texture becomes a
+        TexturedPhong: its stored diffuse is replaced by clamp(1 - ks - kt), see miro_hip.h."""
+        arr = (TextureDesc * max(len(textures), 1))()
+        keep = []
+        for i, t in enumerate(textures):
+            if isinstance(t, TextureDesc):
+                arr[i] = t
+            elif "pixels" in t:
+                px = np.ascontiguousarray(t["pixels"], dtype=np.float32)
+                if px.ndim != 3 or px.shape[2] != 3:
+                    raise ValueError("set_textures: pixels must have the shape [H, W, 3]")
+                keep.append(px)
+                arr[i].kind, arr[i].H, arr[i].W, arr[i].hdr = MR_TEX_IMAGE, px.shape[0], px.shape[1], int(t.get("hdr", 0))
+                arr[i].pixels = _f32p(px)
+            else:
+                arr[i].kind = MR_TEX_CHECKER
+                arr[i].color1[:] = t.get("color1", (1.0, 1.0, 1.0))
+                arr[i].color2[:] = t.get("color2", (0.0, 0.0, 0.0))
+                arr[i].scale = t.get("scale", 1.0)
+        mt = None
+        if material_texture is not None:
+            mt = np.ascontiguousarray(material_texture, dtype=np.uint32)
+        _check(self.L.mr_scene_set_textures(self.h, arr, len(textures), _u32p(mt) if mt is not None else None))
+        self.n_textures = len(textures)
+
+    def hit_uv(self, d_rays, d_hits, n, d_uv, stream=None):
+        """mr_hit_uv: Object::toUVCoordinates(hit.P) of n traced rays into d_uv [n, 2] ((0, 0) for a miss)"""
+        _check(self.L.mr_hit_uv(self.h, d_rays.data_ptr() if d_rays is not None else None, d_hits.data_ptr(), n, d_uv.data_ptr(),
+                                _stream_ptr(stream)))
+
+    def texture_lookup(self, texture, d_uv, n, d_rgb, d_counts=None, stream=None):
+        """mr_texture_lookup: Texture::lookup2D of texture `texture` at d_uv [n, 2] into d_rgb [n, 3]; d_counts[0] += the
+        lookups the reference leaves undefined"""
+        _check(self.L.mr_texture_lookup(self.h, texture, d_uv.data_ptr(), n, d_rgb.data_ptr(),
+                                        d_counts.data_ptr() if d_counts is not None else None, _stream_ptr(stream)))
 
     def tonemap(self, d_rgb, n_values, d_out, stream=None):
         _check(self.L.mr_tonemap(self.h, d_rgb.data_ptr(), n_values, d_out.data_ptr(), _stream_ptr(stream)))

@@ -318,8 +318,13 @@ class FrameRenderer:
         falsy: mr_trace_level keeps no hit records.  The low-res image (the reference's ray.isDiffuse) is used for every level
         after the first when path_kinds == MR_PATH_DIFFUSE and never for specular children; with an IMAGE, MR_PATH_DIFFUSE
         mixed with other kinds is refused (the child queue does not record which child came from Ray::random).  None: a miss
-        is worth 0 and no launch is added."""
+        is worth 0 and no launch is added.
+        A scene with a texture table (Scene.set_textures) takes the batched path for every level, whatever `fused` says
+        (fused="auto" included): mr_trace_level shades without the texture lookup and refuses such a scene; the batched
+        path's mr_shade_accumulate / mr_shade_lights look the diffuse colour up (Phong.cpp:51-56)."""
         sc, L, W = self.scene, self.desc["light"], self.desc["wattage"]
+        if getattr(sc, "n_textures", 0):
+            fused = False
         if environment is not None and environment is not False:
             if fused:
                 raise ValueError("render_specular: an environment needs fused=False (mr_trace_level keeps no hit records)")

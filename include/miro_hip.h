@@ -139,7 +139,8 @@ mr_status mr_scene_create(int32_t device, mr_scene **out);
 mr_status mr_scene_destroy(mr_scene *scene);
 /* copies the arrays; triangles are appended in order (assignment2.cpp:449-461) */
 mr_status mr_scene_add_mesh(mr_scene *scene, const mr_mesh_desc *mesh);
-/* TriangleMesh::load(file, ctm) (TriangleMeshLoad.cpp:63-311); ctm = 16 floats row-major or NULL */
+/* TriangleMesh::load(file, ctm) (TriangleMeshLoad.cpp:63-311); ctm = 16 floats row-major or NULL.  `vt` records and the
+ * texture indices of v/t and v/t/n face corners are kept (see mr_scene_set_texcoords). */
 mr_status mr_scene_add_obj(mr_scene *scene, const char *path, const float *ctm16, uint32_t *n_triangles_out);
 /* TriangleMesh::createSingleTriangle + setV1..3/setN1..3 (TriangleMeshLoad.cpp:15-56) */
 mr_status mr_scene_add_triangle(mr_scene *scene, const float v[9], const float n[9]);
@@ -498,6 +499,81 @@ mr_status mr_scene_get_environment(const mr_scene *scene, uint32_t which, uint32
 mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
                                const uint32_t *d_pixels, const uint8_t *d_lowres, uint64_t n, uint32_t spp, uint32_t flags,
                                float *d_rgb, float *d_ray_rgb, uint64_t *d_counts, void *stream);
+
+/* ---- textured Phong materials: TexturedPhong (Texture.cpp:509-527), UV mapping, checker and image textures ------------------
+ * Phong::shade takes its diffuse colour from the material: diffuseColor = diffuse2D(hit.object->toUVCoordinates(hit.P))
+ * (Phong.cpp:51-56).  For a plain Phong that is m_diffuse; for a TexturedPhong it is Texture::lookup2D at the object's UV
+ * coordinates, and the light's diffuse term is max(0, nDotL * falloff * wattage) * diffuseColor * m_diffuse (Phong.cpp:146); the
+ * highlight does not see the texture.  A scene may carry up to MR_MAX_TEXTURES 2-D textures and a material may name one;
+ * mr_shade_lights and mr_shade_accumulate then run their textured kernels (csrc/mr_textures.hip).  A scene without a texture
+ * table is untouched: the same kernels, the same bits.
+ *
+ * UV coordinates of a hit (csrc/mr_uv.h), every operation fp32 in the reference's order:
+ *   plane     (P.x, P.z)  (Plane.cpp:50-60; also Object's default, Object.h:37)
+ *   sphere    dir = normalize(P - centre); u = atan2(dir.x, dir.z) / (2 PI) + 0.5; v = max(-1, min(1, asin(dir.y))) / PI + 0.5
+ *             (Sphere.cpp:83-95).  The clamp is on the ANGLE, to +-1 radian: v stays inside about [0.18, 0.82] -- reproduced, not
+ *             repaired.  atan2 / asin are those of miro_math.h; `+ 0.5` is a double addition rounded to float.
+ *   triangle  (0, 0) when its mesh has no texture coordinates; otherwise Triangle.cpp:172-222: one axis is dropped by the rule
+ *             normal.x > normal.z -> (i, j) = (2, 1), else normal.y > normal.z -> (0, 2), else (0, 1) on the signed,
+ *             un-normalised cross(B-A, C-A); beta = max(detPC / detBC, 0), gamma = max(detBP / detBC, 0),
+ *             alpha = max(1 - (beta + gamma), 0) with std::max(a, b) = a < b ? b : a (a NaN quotient stays: a degenerate
+ *             projection, detBC == 0, propagates); uv = alpha * tA + beta * tB + gamma * tC, summed left to right.
+ *
+ * mr_scene_set_texcoords -- TriangleMesh::m_texCoords / m_texCoordIndices for the whole scene: n_texcoords uv pairs and three
+ * indices per object in addObject order (spheres included; their entries are ignored), MR_NO_TEXCOORD in all three = this
+ * triangle's mesh has none.  Replaces an earlier table (also the one mr_scene_add_obj made from `vt` records and v/t, v/t/n
+ * face corners, which needs no call); n_texcoords == 0 clears it.  Before or after mr_bvh_build, like mr_scene_set_materials;
+ * objects added afterwards have none.  Errors (MR_ERR_INVALID, the earlier table stays): NULL scene, NULL arrays, a non-finite
+ * coordinate, an index >= n_texcoords, MR_NO_TEXCOORD in some but not all of an object's three.
+ * mr_scene_get_texcoords -- the table back: *n_texcoords, 2 * n_texcoords floats and 3 indices per object (any may be NULL).
+ *
+ * mr_scene_set_textures -- host only (works on a host_only scene), copies its inputs, replaces an earlier table;
+ * n_textures == 0 clears it.  The device copy is made by the first shading call after a change, on that call's stream.
+ * material_texture: one texture id per material of mr_scene_set_materials' table (MR_NO_TEXTURE = plain Phong), or NULL (no
+ * material names a texture).  A material that names a texture is a TexturedPhong: its m_diffuse becomes what the Phong
+ * constructor's clamps make of kd = 1 (Texture.cpp:513-514, Phong.cpp:24-31), clamp(1 - ks - kt, 0, 1) per channel -- the call
+ * writes that into the stored material record WHATEVER `diffuse` the caller put in mr_material, and clearing the table does not
+ * bring the old value back (set the materials again).  While a table exists mr_scene_set_materials is refused (MR_ERR_STATE:
+ * the table names materials by index): clear, set materials, set textures.
+ *   MR_TEX_CHECKER  CheckerBoardTexture (Texture.h:112-133): u' = |scale * u|, plus scale when u < 0, the same for v;
+ *                   ((int)u' + (int)v') % 2 == 0 ? color1 : color2.  Coordinates that are not finite, or whose scaled magnitude
+ *                   reaches 2^30, are undefined in the reference; here they are DEFINED as color1 and counted.
+ *   MR_TEX_IMAGE    LoadedTexture (Texture.cpp:23-28,131-185): W * H * 3 floats, row 0 = the bottom scanline (the environment's
+ *                   convention).  hdr = 1 is FIT_RGBF: m_maxIntensity is computed as the constructor does and
+ *                   tonemapValue = min(powf(f / max, 0.5f) * 1.5f, 1); hdr = 0 is FIT_BITMAP: pass channel / 255, tonemapValue
+ *                   is the identity.  Phong::shade calls lookup2D, the full-resolution image: no low-res copy is built (no
+ *                   24-texel minimum).  The bilinear lookup is mr_shade_environment's (wrapped indices, the error term taken
+ *                   from the wrapped index: u == 1 extrapolates).  A lookup that leaves the image in the reference (negative or
+ *                   non-finite u / v, an index beyond int) is DEFINED as 0 and counted -- for every negative coordinate,
+ *                   the sliver -1 / W < u < 0 included, where the reference's truncation happens to stay on texel 0.
+ * Errors (MR_ERR_INVALID, the earlier table stays): NULL scene, n_textures > MR_MAX_TEXTURES, NULL list, unknown kind, non-zero
+ *   reserved word, non-finite field or pixel, W or H of 0 (or above 65536), NULL pixels, hdr > 1, a texture id >= n_textures, a
+ *   material_texture given without a material table.
+ *
+ * mr_hit_uv -- toUVCoordinates(hit.P) of n traced rays: d_uv receives 2n floats, (0, 0) for a miss.  d_rays may be NULL for
+ *   scenes of triangles only.  mr_texture_lookup -- lookup2D of texture `texture` at n coordinates (d_uv: 2n floats): d_rgb
+ *   receives 3n floats; d_counts (may be NULL): [0] += undefined lookups, not zeroed.  Both only enqueue on `stream`.
+ *
+ * Entry points that shade without the lookup refuse a scene with a texture table (MR_ERR_STATE, naming the batched calls):
+ * mr_render_direct, mr_shade_direct, mr_trace_level, and mr_trace_photons (its roulette reads diffuse2D, Scene.cpp:545-551). */
+enum { MR_TEX_CHECKER = 0, MR_TEX_IMAGE = 1 };
+#define MR_MAX_TEXTURES 16
+#define MR_NO_TEXTURE  0xFFFFFFFFu
+#define MR_NO_TEXCOORD 0xFFFFFFFFu
+typedef struct mr_texture_desc {
+    uint32_t kind;
+    float color1[3], color2[3], scale;                /* MR_TEX_CHECKER */
+    const float *pixels;                              /* MR_TEX_IMAGE: host, W*H*3 floats, row 0 = bottom */
+    uint32_t W, H, hdr;
+    uint32_t reserved[5];                             /* must be 0 */
+} mr_texture_desc;
+mr_status mr_scene_set_texcoords(mr_scene *scene, const float *texcoords, uint32_t n_texcoords, const uint32_t *tidx);
+mr_status mr_scene_get_texcoords(const mr_scene *scene, uint32_t *n_texcoords, float *texcoords, uint32_t *tidx);
+mr_status mr_scene_set_textures(mr_scene *scene, const mr_texture_desc *textures, uint32_t n_textures,
+                                const uint32_t *material_texture);
+mr_status mr_hit_uv(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, uint64_t n, float *d_uv, void *stream);
+mr_status mr_texture_lookup(mr_scene *scene, uint32_t texture, const float *d_uv, uint64_t n, float *d_rgb, uint64_t *d_counts,
+                            void *stream);
 
 /* sigmoid(6v-3) tone map + 8-bit quantisation (Scene.cpp:87-91,177-202; Image.cpp:44-50) */
 mr_status mr_tonemap(mr_scene *scene, const float *d_rgb, uint64_t n_values, uint8_t *d_out, void *stream);
