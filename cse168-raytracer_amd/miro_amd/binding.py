@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "mr_final_gather",
     "mr_trace_photons", "mr_trace_photons_timing",
     "mr_scene_set_lights", "mr_shade_lights",
+    "mr_gen_eye_rays_lens", "mr_square_light_tangents", "mr_shade_square_lights",
     "mr_scene_set_environment", "mr_scene_get_environment", "mr_shade_environment",
     "mr_scene_set_texcoords", "mr_scene_get_texcoords", "mr_scene_set_textures", "mr_hit_uv", "mr_texture_lookup",
     "mr_last_error", "mr_version",
@@ -143,6 +144,39 @@ def light_desc(light):
         ld.normal[:] = light["normal"]
         ld.radius = light["radius"]
     return ld
+
+
+class LensDesc(C.Structure):
+    """mr_lens_desc (miro_hip.h): DOF_APERTURE / DOF_FOCUS_PLANE of the thin-lens camera"""
+    _fields_ = [("aperture", C.c_float), ("focus_plane", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
+class SquareLightDesc(C.Structure):
+    """mr_square_light_desc (miro_hip.h): a SquareLight"""
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3), ("color", C.c_float * 3), ("wattage", C.c_float),
+                ("dimensions", C.c_float * 2), ("reserved", C.c_uint32 * 4)]
+
+
+def square_light_desc(light):
+    """A SquareLightDesc from a SquareLightDesc or from dict(position, normal, color, wattage, dimensions); color defaults
+    to white, the normal to SquareLight's (0, 1, 0)."""
+    if isinstance(light, SquareLightDesc):
+        return light
+    ld = SquareLightDesc()
+    ld.position[:] = light["position"]
+    ld.normal[:] = light.get("normal", (0.0, 1.0, 0.0))
+    ld.color[:] = light.get("color", (1.0, 1.0, 1.0))
+    ld.wattage = light["wattage"]
+    ld.dimensions[:] = light["dimensions"]
+    return ld
+
+
+def square_light_tangents(normal):
+    """(t1, t2) of getTangents(normal) as the library computes them on the host (mr_square_light_tangents), float32 numpy."""
+    n = np.ascontiguousarray(normal, dtype=np.float32)
+    t1, t2 = np.empty(3, np.float32), np.empty(3, np.float32)
+    _check(lib().mr_square_light_tangents(_f32p(n), _f32p(t1), _f32p(t2)))
+    return t1, t2
 
 
 class EnvironmentDesc(C.Structure):
@@ -245,6 +279,10 @@ def load_library(path=None):
     L.mr_trace_photons_timing.argtypes = [C.POINTER(C.c_double)] * 3
     L.mr_scene_set_lights.argtypes = [vp, C.POINTER(LightDesc), C.c_uint32]
     L.mr_shade_lights.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.mr_gen_eye_rays_lens.argtypes = L.mr_gen_eye_rays.argtypes + [C.POINTER(LensDesc), vp, vp, vp]
+    L.mr_square_light_tangents.argtypes = [f32p, f32p, f32p]
+    L.mr_shade_square_lights.argtypes = [vp, C.POINTER(SquareLightDesc), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
+                                         C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.mr_scene_set_environment.argtypes = [vp, C.POINTER(EnvironmentDesc)]
     L.mr_scene_get_environment.argtypes = [vp, C.c_uint32, u32p, u32p, f32p, f32p]
     L.mr_shade_environment.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -490,6 +528,19 @@ class Scene:
         _check(fn(self.h, C.byref(cam), W, H, y0, y1, spp, 1 if jitter else 0, seed, d_rays.data_ptr(), _stream_ptr(stream)))
         return (y1 - y0) * W * spp
 
+    def gen_eye_rays_lens(self, cam, W, H, d_rays, aperture, focus_plane, y0=0, y1=None, spp=1, jitter=False, seed=168,
+                          d_samples_in=None, d_samples_out=None, d_counts=None, stream=None):
+        """mr_gen_eye_rays_lens: Camera::eyeRay under -DDOF for rows [y0, y1), in mr_gen_eye_rays' ray order.  d_samples_in /
+        d_samples_out: 4 floats per ray (dx, dy, lx, ly), given / used; d_counts: [0] += rays, [1] += exhausted lens samples."""
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        y1 = H if y1 is None else y1
+        lens = LensDesc()
+        lens.aperture, lens.focus_plane = aperture, focus_plane
+        _check(self.L.mr_gen_eye_rays_lens(self.h, C.byref(cam), W, H, y0, y1, spp, 1 if jitter else 0, seed, d_rays.data_ptr(),
+                                           _stream_ptr(stream), C.byref(lens), ptr(d_samples_in), ptr(d_samples_out), ptr(d_counts)))
+        return (y1 - y0) * W * spp
+
     def untile_pixels(self, d_slots, d_image, W, rows, spp, channels=3, stream=None):
         """Scatter a tiled window's pixel slots to image order on the device (mr_untile_pixels)."""
         _check(self.L.mr_untile_pixels(self.h, d_slots.data_ptr(), d_image.data_ptr(), W, rows, spp, channels,
@@ -663,6 +714,21 @@ class Scene:
             return t.data_ptr() if t is not None else None
         _check(self.L.mr_shade_lights(self.h, d_rays.data_ptr(), d_hits.data_ptr(), ptr(d_weights), ptr(d_pixels), n, spp, flags,
                                       ptr(d_rgb), ptr(d_ray_rgb), ptr(d_counts), _stream_ptr(stream)))
+
+    def shade_square_lights(self, lights, samples, d_rays, d_hits, n, d_rgb=None, seed=168, d_weights=None, d_pixels=None,
+                            d_uv_in=None, spp=1, flags=0, d_ray_rgb=None, d_counts=None, stream=None):
+        """mr_shade_square_lights: Phong::shade over a list of SquareLights (SquareLightDesc objects or dicts, see
+        square_light_desc) with `samples` shadow rays per hit and light, in one launch; weight * L / spp is added to
+        d_rgb[pixel], the un-weighted L of every ray written to d_ray_rgb (either may be None, not both).  d_uv_in: the
+        caller's own pairs, 2 * n * len(lights) * samples floats."""
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        arr = (SquareLightDesc * max(len(lights), 1))()
+        for i, lt in enumerate(lights):
+            arr[i] = square_light_desc(lt)
+        _check(self.L.mr_shade_square_lights(self.h, arr, len(lights), samples, seed, d_rays.data_ptr(), d_hits.data_ptr(),
+                                             ptr(d_weights), ptr(d_pixels), ptr(d_uv_in), n, spp, flags, ptr(d_rgb), ptr(d_ray_rgb),
+                                             ptr(d_counts), _stream_ptr(stream)))
 
     def set_environment(self, bg_color=(0.0, 0.0, 0.0), pixels=None, rotation=(0.0, 0.0)):
         """mr_scene_set_environment: Scene::setBgColor, Scene::setEnvironment (pixels: a float image [H, W, 3], row 0 = the

@@ -171,10 +171,18 @@ class FrameRenderer:
     """All device buffers of one rank's share of a frame, resident for the lifetime of the object."""
 
     def __init__(self, scene, desc, W, H, spp=1, bands=None, jitter=None, seed=168, flags=0, device=None, rgb=None,
-                 tiled=None):
+                 tiled=None, lens=None, square_lights=None, square_samples=1):
+        """lens: dict(aperture, focus_plane) -- generate() then makes the eye rays of the thin-lens camera
+        (mr_gen_eye_rays_lens, Camera::eyeRay under -DDOF) in image order; not with tiled=True.
+        square_lights: a list of SquareLights (binding.SquareLightDesc objects or dicts) that every level of render_specular's
+        batched path shades IN ADDITION to its point light / light list, with square_samples shadow rays per hit and light
+        (mr_shade_square_lights; level l draws its pairs with seed + l).  Without either option nothing changes."""
         if isinstance(desc, str):
             desc = scenes.SCENES[desc]
         self.scene, self.desc, self.W, self.H, self.spp = scene, desc, W, H, spp
+        self.lens, self.square_lights, self.square_samples = lens, square_lights, square_samples
+        if lens is not None and tiled:
+            raise ValueError("FrameRenderer: lens eye rays come in image order only (tiled must be falsy)")
         self.bands = bands if bands is not None else [(0, H)]
         self.jitter = (spp > 1) if jitter is None else jitter
         self.seed, self.flags = seed, flags
@@ -221,8 +229,13 @@ class FrameRenderer:
         off = 0
         for y0, y1 in self.bands:
             k = (y1 - y0) * self.W * self.spp
-            self.scene.gen_eye_rays(self.cam, self.W, self.H, self.d_rays[off:off + k], y0=y0, y1=y1, spp=self.spp,
-                                    jitter=self.jitter, seed=self.seed, stream=stream, tiled=self.tiled)
+            if self.lens is not None:
+                self.scene.gen_eye_rays_lens(self.cam, self.W, self.H, self.d_rays[off:off + k], self.lens["aperture"],
+                                             self.lens["focus_plane"], y0=y0, y1=y1, spp=self.spp, jitter=self.jitter,
+                                             seed=self.seed, stream=stream)
+            else:
+                self.scene.gen_eye_rays(self.cam, self.W, self.H, self.d_rays[off:off + k], y0=y0, y1=y1, spp=self.spp,
+                                        jitter=self.jitter, seed=self.seed, stream=stream, tiled=self.tiled)
             off += k
 
     def trace_primary(self, stream=None):
@@ -344,6 +357,8 @@ class FrameRenderer:
             if fused:
                 raise ValueError("render_specular: a light list needs fused=False (mr_trace_level shades by one point light)")
             sc.set_lights(lights)
+        if self.square_lights and fused:
+            raise ValueError("render_specular: square lights need fused=False (mr_trace_level keeps no hit records)")
         # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
         # each other on torch's current stream, so `stream` must be that stream (or a torch Stream, made current here)
         if stream is not None and not isinstance(stream, torch.cuda.Stream):
@@ -421,6 +436,10 @@ class FrameRenderer:
                 sc.trace_indirect(sh_rays, cnt, n, sh_hits, fl, stream=stream)           # closest hit: the occluder matters
                 sc.shade_accumulate(rays, hits, weights, pixels, n, sh_rays, sh_hits, src, cnt, L, W, self.d_slots,
                                     spp=self.spp, stream=stream)
+            if self.square_lights:
+                sc.shade_square_lights(self.square_lights, self.square_samples, rays, hits, n, self.d_slots, seed=self.seed + level,
+                                       d_weights=weights, d_pixels=pixels, spp=self.spp,
+                                       flags=fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT), d_counts=cnt, stream=stream)
             n_shadow = int(cnt.item())
             per_level.append((n, n_shadow))
             if level == depth:

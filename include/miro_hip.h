@@ -432,6 +432,86 @@ mr_status mr_shade_lights(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d
                           const uint32_t *d_pixels, uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb,
                           uint64_t *d_counts, void *stream);
 
+/* ---- distribution effects: the thin-lens camera and the square area light (csrc/mr_distribution.hip) -----------------------
+ * Both draw random numbers per sample from the counter-based generator of the eye-ray jitter, H(x) = pcg32(x),
+ * u(h) = (h >> 8) / 2^24, and both accept the caller's own numbers instead.  No time has been measured for either.
+ *
+ * mr_gen_eye_rays_lens is Camera::eyeRay under -DDOF (Camera.cpp:135-160) with DOF_APERTURE / DOF_FOCUS_PLANE (Miro.h:18-19)
+ * as arguments; raytraceImage averages TRACE_SAMPLES such rays per pixel (Scene.cpp:126-139): that is spp.  Its first eleven
+ * arguments are mr_gen_eye_rays' (same window, same ray order ((y-y0)*W+x)*spp+s; there is no tiled form).  Per sample, every
+ * operation in fp32 and in the reference's order:
+ *   (lx, ly)    = sampleDisc(aperture) (Utility.h:82-95)
+ *   new_eye     = eye + (lx * uDir + ly * vDir)                                        (Camera.cpp:140)
+ *   new_viewDir = (eye + viewDir * focus_plane) - new_eye,  viewDir the unit view vector (Camera.cpp:142)
+ *   localw      = normalize(-new_viewDir)                                              (Camera.cpp:145)
+ *   dir         = normalize(uPos * uDir + vPos * vDir - localw)                        (Camera.cpp:157-160)
+ *   ray         = (new_eye, tMin 0, dir, MIRO_TMAX)
+ * uDir and vDir are those of the UNMOVED eye (Camera.cpp:146-147 are commented out in the reference): the quirk is
+ * reproduced, not repaired.  With aperture == 0 the origin is the eye, but localw is rebuilt from eye + viewDir * focus_plane
+ * and may differ from mr_gen_eye_rays' wDir in the last bit.
+ * Samples, d_samples_in == NULL: with h = H(H(H(seed) ^ pixel) + s) the per-sample hash of mr_gen_eye_rays (pixel = y*W+x),
+ *   dx = u(H(h)), dy = u(H(h ^ 0x68bc21eb)) exactly as there (0.5, 0.5 when jitter == 0), so the
+ *   pixel jitter of a seed is unchanged; the lens pair of rejection round r = 0 ... 31 is
+ *     x = (2 u(H(h ^ (0x4c454e53 + 2r))) - 1) * aperture,  y = (2 u(H(h ^ (0x4c454e53 + 2r + 1))) - 1) * aperture,
+ *   accepted unless x*x + y*y > aperture*aperture (Utility.h:86-89).  The reference's loop is unbounded; here a sample that
+ *   is rejected 32 times (probability (1 - PI/4)^32 = 4e-22) is (0, 0) and counted in d_counts[1].
+ * d_samples_in (may be NULL): 4 floats per ray, dx, dy, lx, ly, used as they are (jitter and seed are then not read): for
+ *   callers with their own stratified sampler.  d_samples_out (may be NULL): 4 floats per ray, the values used.
+ * d_counts (may be NULL): [0] += rays written, [1] += samples that exhausted the 32 rounds; not zeroed by the call.
+ * The call only enqueues one kernel on `stream`.
+ * Errors (MR_ERR_INVALID, before any device call): NULL scene / cam / d_rays / lens, a non-zero reserved word, a non-finite or
+ *   negative aperture, a non-finite or non-positive focus_plane, a bad window, d_rays or a sample buffer not 16-byte aligned.
+ *
+ * mr_shade_square_lights is Phong::shade (Phong.cpp:66-157) for n traced rays over a list of SquareLights (SquareLight.h:6-58
+ * on PointLight.h:8-59) with `samples` shadow rays per hit and light (Phong.cpp:71-78; the reference ships samples = 1 and
+ * keeps 49 in a comment).  Per ray with a hit, L = 0; for every light in list order and i = 0 ... samples-1:
+ *   origin = samplePhotonOrigin(i, samples) (SquareLight.h:23-39): sideLength = sqrt((float)samples), du = dimensions[0] /
+ *     sideLength, dv likewise, sx = i % int(sideLength), sy = i / int(sideLength),
+ *     u = du*r0 + sx*du - dimensions[0]/2.0f, v = dv*r1 + sy*dv - dimensions[1]/2.0f, origin = position + u*t1 + v*t2 with
+ *     (t1, t2) = getTangents(normal) (Utility.h:25-31; SquareLight::preCalc), computed on the host: mr_square_light_tangents
+ *     returns them.  The normal only orients the rectangle: a SquareLight shades like a point light at `origin`.
+ *   l = origin - P (PointLight::getLightDirection); then the point light's arm of Phong.cpp:85-156: shadow ray from
+ *     P + l*epsilon along l/|l| with tMax = |l|, closest hit, the occluder rule of :99-113 (opaque: the sample is skipped,
+ *     refractive: scaled by dot(N, l), skipped if negative or < epsilon), falloff = 1/(4 PI^2 |l|^2), and
+ *     L += color * (max(0, nDotL*falloff*wattage / (float)samples) * diffuse * diffuse) * scale, then
+ *     L += max(0, eDotr^500 * falloff*wattage / (float)samples) -- two additions per sample, as Phong.cpp:146,155 make them.
+ *   (mr_shade_lights adds a light's two terms to each other first; for the first sample of a ray the two orders give the same
+ *   bits, so dimensions = (0, 0), samples = 1 and one light is mr_shade_lights with one MR_LIGHT_POINT, bit for bit.)
+ * Then weight * L / spp is added to d_rgb[pixel] exactly as mr_shade_lights adds it; d_ray_rgb is the deterministic per-ray L.
+ * A sum over mixed light kinds takes one call per kind (mr_shade_lights for point and disc lights, this call for square
+ * lights), each adding into d_rgb: the float addition order then differs from that of the reference's single list.
+ * samples: a perfect square in {1, 4, 9, ..., 64}: for any other value int(sideLength)^2 != samples and the reference's cells
+ *   leave the rectangle (MR_ERR_INVALID).
+ * Random pairs (r0, r1), d_uv_in == NULL: h = H(H(H(seed ^ 0x73717561) ^ ray index) + 64*light + i), r0 = u(H(h)),
+ *   r1 = u(H(h ^ 0x68bc21eb)).  d_uv_in (may be NULL): 2 * n * n_lights * samples floats in [0, 1), the pair of ray k, light j,
+ *   sample i at 2 * ((k * n_lights + j) * samples + i); read for rays with a hit only.
+ * d_counts (may be NULL): [0] += shadow rays traced (= rays with a hit x lights x samples); not zeroed by the call.
+ * flags: those of mr_shade_lights; MR_TRACE_ANY is refused with MR_ERR_STATE when a material is refractive.
+ * Materials: the table of mr_scene_set_materials.  A scene with a texture table (mr_scene_set_textures) is REFUSED with
+ *   MR_ERR_STATE: this call shades without the texture lookup.
+ * The call only enqueues one kernel on `stream`.
+ * Errors: NULL scene, n_lights == 0 or > MR_MAX_LIGHTS, NULL list, non-zero reserved, a non-finite field, a zero normal,
+ *   a negative dimension, samples not such a square, NULL rays / hits, both outputs NULL, spp == 0, n >= 2^32, other flags,
+ *   misaligned buffers (rays / hits 16 bytes, counters / d_uv_in 8): MR_ERR_INVALID (before any device call, and before the
+ *   scene's state is looked at); a scene that is not built or was built host_only: MR_ERR_STATE. */
+typedef struct mr_lens_desc {                         /* Miro.h:18-19 */
+    float aperture, focus_plane;                      /* DOF_APERTURE (radius of the lens disc), DOF_FOCUS_PLANE */
+    uint32_t reserved[6];                             /* must be 0 */
+} mr_lens_desc;
+mr_status mr_gen_eye_rays_lens(mr_scene *scene, const mr_camera *cam, uint32_t W, uint32_t H,
+                               uint32_t y0, uint32_t y1, uint32_t spp, uint32_t jitter, uint32_t seed,
+                               mr_ray *d_rays, void *stream, const mr_lens_desc *lens, const float *d_samples_in,
+                               float *d_samples_out, uint64_t *d_counts);
+typedef struct mr_square_light_desc {                 /* SquareLight.h:6-58 on PointLight.h:8-59 */
+    float position[3], normal[3], color[3], wattage, dimensions[2];
+    uint32_t reserved[4];                             /* must be 0 */
+} mr_square_light_desc;
+mr_status mr_square_light_tangents(const float normal[3], float t1[3], float t2[3]);   /* getTangents (Utility.h:25-31) */
+mr_status mr_shade_square_lights(mr_scene *scene, const mr_square_light_desc *lights, uint32_t n_lights, uint32_t samples,
+                                 uint32_t seed, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
+                                 const uint32_t *d_pixels, const float *d_uv_in, uint64_t n, uint32_t spp, uint32_t flags,
+                                 float *d_rgb, float *d_ray_rgb, uint64_t *d_counts, void *stream);
+
 /* ---- the environment of rays that MISS: Scene::getEnvironmentMap (Scene.cpp:338-342,657-688) ------------------------------
  * Scene::traceScene ends a ray that leaves the scene with shadeResult = getEnvironmentMap(ray), which its parent multiplies by
  * the reflection / refraction factor like any child result.  getEnvironmentMap returns m_bgColor (Scene::setBgColor, default 0)
