@@ -406,6 +406,22 @@ mr_status refuse_textured(const mr_scene *s, const char *who) {
                               "mr_shade_accumulate", who);
 }
 
+// what mr_scene_set_lights and mr_shade_square_lights ask of light i of a list: reserved words 0; finite position, colour and
+// wattage; with `normal` (a light that has one) a finite normal that is not zero
+mr_status check_light(const char *who, uint32_t i, const uint32_t reserved[4], const float position[3], const float color[3], float wattage,
+                      const float *normal) {
+    for (int k = 0; k < 4; k++)
+        if (reserved[k] != 0) return fail(MR_ERR_INVALID, "%s: light %u: reserved must be 0", who, i);
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(position[c]) || !std::isfinite(color[c])) return fail(MR_ERR_INVALID, "%s: light %u: position and color must be finite", who, i);
+    if (!std::isfinite(wattage)) return fail(MR_ERR_INVALID, "%s: light %u: wattage must be finite", who, i);
+    if (!normal) return MR_OK;
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(normal[c])) return fail(MR_ERR_INVALID, "%s: light %u: the normal must be finite", who, i);
+    if (normal[0] == 0.0f && normal[1] == 0.0f && normal[2] == 0.0f) return fail(MR_ERR_INVALID, "%s: light %u: the normal is zero", who, i);
+    return MR_OK;
+}
+
 // LoadedTexture::LoadedTexture (Texture.cpp:30-92) for a FIT_RGBF image of W x H pixels: m_maxIntensity and the low-res image,
 // written behind the image's own records in e.rec
 void build_environment_image(HostEnvironment &e, const float *px) {
@@ -1017,11 +1033,9 @@ mr_status mr_scene_set_lights(mr_scene *s, const mr_light_desc *lights, uint32_t
     for (uint32_t i = 0; i < n_lights; i++) {
         const mr_light_desc &in = lights[i];
         if (in.kind != MR_LIGHT_POINT && in.kind != MR_LIGHT_DISC) return fail(MR_ERR_INVALID, "light %u: unknown kind %u", i, in.kind);
-        for (int k = 0; k < 4; k++)
-            if (in.reserved[k] != 0) return fail(MR_ERR_INVALID, "light %u: mr_light_desc.reserved must be 0", i);
-        for (int c = 0; c < 3; c++)
-            if (!std::isfinite(in.position[c]) || !std::isfinite(in.color[c])) return fail(MR_ERR_INVALID, "light %u: position and color must be finite", i);
-        if (!std::isfinite(in.wattage)) return fail(MR_ERR_INVALID, "light %u: wattage must be finite", i);
+        const mr_status st = check_light("mr_scene_set_lights", i, in.reserved, in.position, in.color, in.wattage,
+                                         in.kind == MR_LIGHT_DISC ? in.normal : nullptr);
+        if (st != MR_OK) return st;
         ShadeLight &o = list[i];
         o = ShadeLight();
         o.kind = in.kind;
@@ -1029,9 +1043,6 @@ mr_status mr_scene_set_lights(mr_scene *s, const mr_light_desc *lights, uint32_t
         o.wattage = in.wattage;
         if (in.kind == MR_LIGHT_DISC) {
             if (!(in.radius > 0.0f) || !std::isfinite(in.radius)) return fail(MR_ERR_INVALID, "light %u: a disc light's radius must be positive", i);
-            for (int c = 0; c < 3; c++)
-                if (!std::isfinite(in.normal[c])) return fail(MR_ERR_INVALID, "light %u: a disc light's normal must be finite", i);
-            if (in.normal[0] == 0.0f && in.normal[1] == 0.0f && in.normal[2] == 0.0f) return fail(MR_ERR_INVALID, "light %u: a disc light's normal is zero", i);
             for (int c = 0; c < 3; c++) o.normal[c] = in.normal[c];
             o.radius = in.radius;
         }
@@ -1065,6 +1076,69 @@ mr_status mr_shade_lights(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hit
     }
     return launch_shade_lights(s->dev, s->lights.data(), (uint32_t)s->lights.size(), d_rays, d_hits, d_weights, d_pixels, n, spp,
                                flags, d_rgb, d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_gen_eye_rays_lens(mr_scene *s, const mr_camera *cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp,
+                               uint32_t jitter, uint32_t seed, mr_ray *d_rays, void *stream, const mr_lens_desc *lens,
+                               const float *d_samples_in, float *d_samples_out, uint64_t *d_counts) {
+    if (!s || !cam || !d_rays) return fail(MR_ERR_INVALID, "NULL argument");
+    if (!lens) return fail(MR_ERR_INVALID, "mr_gen_eye_rays_lens: NULL lens");
+    for (int k = 0; k < 6; k++)
+        if (lens->reserved[k] != 0) return fail(MR_ERR_INVALID, "mr_gen_eye_rays_lens: mr_lens_desc.reserved must be 0");
+    if (!std::isfinite(lens->aperture) || lens->aperture < 0.0f) return fail(MR_ERR_INVALID, "mr_gen_eye_rays_lens: aperture must be finite and >= 0");
+    if (!std::isfinite(lens->focus_plane) || !(lens->focus_plane > 0.0f)) return fail(MR_ERR_INVALID, "mr_gen_eye_rays_lens: focus_plane must be finite and > 0");
+    if (W == 0 || H == 0 || spp == 0 || y1 < y0 || y1 > H) return fail(MR_ERR_INVALID, "bad image window");
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_samples_in) & 15) ||
+        (reinterpret_cast<uintptr_t>(d_samples_out) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7))
+        return fail(MR_ERR_INVALID, "d_rays and the sample buffers must be 16-byte aligned, counters 8-byte aligned");
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    return launch_eye_rays_lens(*cam, W, H, y0, y1, spp, jitter, seed, *lens, d_samples_in, d_samples_out,
+                                reinterpret_cast<unsigned long long *>(d_counts), d_rays, static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_square_light_tangents(const float normal[3], float t1[3], float t2[3]) {
+    if (!normal || !t1 || !t2) return fail(MR_ERR_INVALID, "mr_square_light_tangents: NULL argument");
+    tangents_of(normal, t1, t2);
+    return MR_OK;
+}
+
+// the argument errors come before the scene's state here: a bad call is MR_ERR_INVALID on any scene
+mr_status mr_shade_square_lights(mr_scene *s, const mr_square_light_desc *lights, uint32_t n_lights, uint32_t samples, uint32_t seed,
+                                 const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels,
+                                 const float *d_uv_in, uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb,
+                                 uint64_t *d_counts, void *stream) {
+    const char *who = "mr_shade_square_lights";
+    if (!s) return fail(MR_ERR_INVALID, "%s: NULL scene", who);
+    if (n_lights == 0 || n_lights > MR_MAX_LIGHTS) return fail(MR_ERR_INVALID, "%s: %u lights, at least 1 and at most %u", who, n_lights, (unsigned)MR_MAX_LIGHTS);
+    if (!lights) return fail(MR_ERR_INVALID, "%s: NULL list of %u lights", who, n_lights);
+    uint32_t side = 0;
+    while (side < 8 && side * side < samples) side++;
+    if (samples == 0 || side * side != samples)
+        return fail(MR_ERR_INVALID, "%s: samples = %u is not a perfect square in 1 ... 64 (SquareLight.h:27-33 subdivides the rectangle "
+                                    "into int(sqrt(samples))^2 cells)", who, samples);
+    mr_status st;
+    for (uint32_t i = 0; i < n_lights; i++) {
+        const mr_square_light_desc &in = lights[i];
+        if ((st = check_light(who, i, in.reserved, in.position, in.color, in.wattage, in.normal)) != MR_OK) return st;
+        for (int k = 0; k < 2; k++)
+            if (!std::isfinite(in.dimensions[k]) || in.dimensions[k] < 0.0f)
+                return fail(MR_ERR_INVALID, "%s: light %u: dimensions must be finite and >= 0", who, i);
+    }
+    if (!d_rays || !d_hits || (!d_rgb && !d_ray_rgb)) return fail(MR_ERR_INVALID, "%s: NULL argument", who);
+    if (spp == 0) return fail(MR_ERR_INVALID, "%s: spp is 0", who);
+    if (n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32-1 rays per batch (the sample keys hold the ray index in 32 bits)", who);
+    if (flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT | MR_TRACE_ANY))
+        return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_TRACE_ANY only", who);
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_uv_in) & 7) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3))
+        return fail(MR_ERR_INVALID, "%s: ray / hit buffers must be 16-byte aligned, counters and d_uv_in 8-byte aligned", who);
+    if ((st = require_device(s)) != MR_OK) return st;
+    if ((st = refuse_textured(s, who)) != MR_OK) return st;
+    if ((flags & MR_TRACE_ANY) && s->dev.refractive)
+        return fail(MR_ERR_STATE, "%s: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)", who);
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    return launch_shade_square_lights(s->dev, lights, n_lights, side, seed, d_rays, d_hits, d_weights, d_pixels, d_uv_in, n, spp, flags, d_rgb,
+                                      d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_scene_set_environment(mr_scene *s, const mr_environment_desc *env) {

@@ -25,22 +25,21 @@ struct EyeFrame {
     unsigned long long n;        // samples in the window = rows * W * spp
 };
 
-// y0/y1: contiguous window.  For banded windows call set_bands() afterwards.
+// y0/y1: contiguous window.  For banded windows call set_bands() afterwards.  view_dir (optional): m_viewDir, normalised
+// once -- f.w is its negative normalised again, which is not the same bits.
 inline EyeFrame make_eye_frame(const mr_camera &cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp,
-                               uint32_t jitter, uint32_t seed, bool tiled) {
+                               uint32_t jitter, uint32_t seed, bool tiled, float *view_dir = nullptr) {
     auto unit3 = [](float *a) {
         const float len = sqrtf((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
         const float inv = 1.0f / len;
         a[0] *= inv; a[1] *= inv; a[2] *= inv;
-    };
-    auto cross3 = [](const float *a, const float *b, float *o) {
-        o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
     };
     EyeFrame f;
     float up[3] = {cam.up[0], cam.up[1], cam.up[2]};
     unit3(up);
     float view[3] = {cam.lookat[0] - cam.eye[0], cam.lookat[1] - cam.eye[1], cam.lookat[2] - cam.eye[2]};
     unit3(view);
+    if (view_dir) { view_dir[0] = view[0]; view_dir[1] = view[1]; view_dir[2] = view[2]; }
     f.w[0] = -view[0]; f.w[1] = -view[1]; f.w[2] = -view[2];
     unit3(f.w);
     cross3(up, f.w, f.u);
@@ -57,22 +56,12 @@ inline EyeFrame make_eye_frame(const mr_camera &cam, uint32_t W, uint32_t H, uin
     f.rows = y1 - y0;
     f.band_rows = f.rows ? f.rows : 1; f.band_rank = 0; f.band_world = 1;
     f.tiled = tiled && (f.tile.th > 1 || f.tile.tw > 1) ? 1u : 0u;
-    {   // host copy of pcg_hash
-        uint32_t state = seed * 747796405u + 2891336453u;
-        uint32_t word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
-        f.hbase = (word >> 22u) ^ word;
-    }
+    f.hbase = pcg32(seed);
     f.n = (unsigned long long)(y1 - y0) * W * spp;
     return f;
 }
 
 #if defined(__HIPCC__)
-__device__ __forceinline__ uint32_t eye_pcg(uint32_t x) {
-    const uint32_t state = x * 747796405u + 2891336453u;
-    const uint32_t word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
-    return (word >> 22u) ^ word;
-}
-
 // sample k of the window -> pixel (x, window row, image row y) and sample number
 __device__ __forceinline__ void eye_sample_of(const EyeFrame &f, unsigned long long k, uint32_t &x, uint32_t &row, uint32_t &y,
                                               uint32_t &sm) {
@@ -85,24 +74,38 @@ __device__ __forceinline__ void eye_sample_of(const EyeFrame &f, unsigned long l
                           : ((row / f.band_rows) * f.band_world + f.band_rank) * f.band_rows + row % f.band_rows;
 }
 
-// Camera::eyeRay for sample `sm` of pixel (x, y): a = (eye, tMin = 0), b = (direction, tMax = MIRO_TMAX)
-__device__ __forceinline__ void eye_ray_of(const EyeFrame &f, uint32_t x, uint32_t y, uint32_t sm, float4 &a, float4 &b) {
-    float dx = 0.5f, dy = 0.5f;
-    if (f.jitter) {
-        const uint32_t pix = y * f.W + x;
-        const uint32_t h = eye_pcg(eye_pcg(f.hbase ^ pix) + sm);
-        dx = (float)(eye_pcg(h) >> 8) * (1.0f / 16777216.0f);
-        dy = (float)(eye_pcg(h ^ 0x68bc21ebu) >> 8) * (1.0f / 16777216.0f);
-    }
-    const float up = f.left + (f.right - f.left) * (((float)x + dx) / (float)f.W);
-    const float vp = f.bottom + (f.top - f.bottom) * (((float)y + dy) / (float)f.H);
-    float ddx = (up * f.u[0] + vp * f.v[0]) - f.w[0];
-    float ddy = (up * f.u[1] + vp * f.v[1]) - f.w[1];
-    float ddz = (up * f.u[2] + vp * f.v[2]) - f.w[2];
+// Camera::eyeRay (Camera.cpp:127-160) in the pieces its plain and its thin-lens form share:
+// the key of sample `sm` of pixel (x, y), from which the sample's random numbers are drawn
+__device__ __forceinline__ uint32_t eye_sample_key(const EyeFrame &f, uint32_t x, uint32_t y, uint32_t sm) {
+    return pcg32(pcg32(f.hbase ^ (y * f.W + x)) + sm);
+}
+// ... its offset inside the pixel
+__device__ __forceinline__ void eye_jitter_of(uint32_t key, float &dx, float &dy) {
+    dx = unit01(pcg32(key));
+    dy = unit01(pcg32(key ^ 0x68bc21ebu));
+}
+// ... the film coordinates of pixel (x, y) at offset (dx, dy) (Camera.cpp:157-158)
+__device__ __forceinline__ void eye_film_of(const EyeFrame &f, uint32_t x, uint32_t y, float dx, float dy, float &up, float &vp) {
+    up = f.left + (f.right - f.left) * (((float)x + dx) / (float)f.W);
+    vp = f.bottom + (f.top - f.bottom) * (((float)y + dy) / (float)f.H);
+}
+// ... and the ray's second half: (up * uDir + vp * vDir - w) normalised (:160), tMax = MIRO_TMAX
+__device__ __forceinline__ float4 eye_direction_of(const EyeFrame &f, float up, float vp, const float w[3]) {
+    const float ddx = (up * f.u[0] + vp * f.v[0]) - w[0];
+    const float ddy = (up * f.u[1] + vp * f.v[1]) - w[1];
+    const float ddz = (up * f.u[2] + vp * f.v[2]) - w[2];
     const float len = sqrtf((ddx * ddx + ddy * ddy) + ddz * ddz);
     const float inv = 1.0f / len;
+    return make_float4(ddx * inv, ddy * inv, ddz * inv, 1e12f);
+}
+
+// Camera::eyeRay for sample `sm` of pixel (x, y): a = (eye, tMin = 0), b = (direction, tMax = MIRO_TMAX)
+__device__ __forceinline__ void eye_ray_of(const EyeFrame &f, uint32_t x, uint32_t y, uint32_t sm, float4 &a, float4 &b) {
+    float dx = 0.5f, dy = 0.5f, up, vp;
+    if (f.jitter) eye_jitter_of(eye_sample_key(f, x, y, sm), dx, dy);
+    eye_film_of(f, x, y, dx, dy, up, vp);
     a = make_float4(f.eye[0], f.eye[1], f.eye[2], 0.0f);
-    b = make_float4(ddx * inv, ddy * inv, ddz * inv, 1e12f);     // MIRO_TMAX
+    b = eye_direction_of(f, up, vp, f.w);
 }
 #endif
 

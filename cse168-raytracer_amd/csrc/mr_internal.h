@@ -26,6 +26,32 @@ mr_status fail(mr_status code, const char *fmt, ...);
     } while (0)
 
 // ---------------------------------------------------------------------------------------
+// small arithmetic that host and device code share, each written once so that every user gets the same bits
+// ---------------------------------------------------------------------------------------
+// the counter-based random numbers of the eye-ray jitter, the path and photon lobes, the lens and the square light:
+// H(x) = pcg32(x), u(h) = unit01(h) = (h >> 8) / 2^24
+__host__ __device__ __forceinline__ uint32_t pcg32(uint32_t x) {
+    const uint32_t state = x * 747796405u + 2891336453u;
+    const uint32_t word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
+    return (word >> 22u) ^ word;
+}
+__host__ __device__ __forceinline__ float unit01(uint32_t h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }
+
+__host__ __device__ __forceinline__ void cross3(const float a[3], const float b[3], float o[3]) {      // Vector3.h cross()
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+// getTangents (Utility.h:25-31): alignHemisphereToVector, DirectionalAreaLight and SquareLight::preCalc all call it.  The
+// result is built in locals and copied out: inlined into align_to_vector this is the code that function had of its own.
+__host__ __device__ __forceinline__ void tangents_of(const float v[3], float t1[3], float t2[3]) {
+    const float ez[3] = {0.f, 0.f, 1.f}, ey[3] = {0.f, 1.f, 0.f};
+    float a[3], b[3];
+    cross3(ez, v, a);
+    if ((double)((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]) < 1e-6) cross3(ey, v, a);     // float < double literal
+    cross3(a, v, b);
+    for (int c = 0; c < 3; c++) { t1[c] = a[c]; t2[c] = b[c]; }
+}
+
+// ---------------------------------------------------------------------------------------
 // host tree, DFS pre-order (what BVH::build produces, BVH.h:29-63)
 // ---------------------------------------------------------------------------------------
 struct HostNode {
@@ -233,6 +259,16 @@ mr_status launch_shade_lights(const DeviceScene &ds, const ShadeLight *lights, u
                               const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels, unsigned long long n,
                               uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts,
                               hipStream_t stream);
+
+// the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
+// square light, side * side shadow rays per hit and light
+mr_status launch_eye_rays_lens(const mr_camera &cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp, uint32_t jitter,
+                               uint32_t seed, const mr_lens_desc &lens, const float *d_samples_in, float *d_samples_out,
+                               unsigned long long *d_counts, mr_ray *d_rays, hipStream_t stream);
+mr_status launch_shade_square_lights(const DeviceScene &ds, const mr_square_light_desc *lights, uint32_t n_lights, uint32_t side,
+                                     uint32_t seed, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
+                                     const uint32_t *d_pixels, const float *d_uv_in, unsigned long long n, uint32_t spp, uint32_t flags,
+                                     float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts, hipStream_t stream);
 
 // 2-D textures of TexturedPhong materials (mr_textures.hip; Texture.h:112-133, Texture.cpp:23-28,131-185, Phong.cpp:51-56).  The
 // host copy is one blob as the device holds it: three float4 per texture (TexParams below), then the texels of the

@@ -48,9 +48,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
 template <int VAR, bool ANY>
 mr_status launch_lights_t(const LightsArgs &a, hipStream_t stream) {
     size_t lds = 0;
-    const mr_status st = stack_lds(&shade_lights_kernel<VAR, ANY>, a.tp.stack_depth, kStackLdsShared, lds);
+    const mr_status st = stack_lds(&shade_lights_kernel<VAR, ANY>, a.s.tp.stack_depth, kStackLdsShared, lds);
     if (st != MR_OK) return st;
-    hipLaunchKernelGGL((shade_lights_kernel<VAR, ANY>), dim3(trace_grid(a.tp.n)), dim3(kTraceBlock), lds, stream, a);
+    hipLaunchKernelGGL((shade_lights_kernel<VAR, ANY>), dim3(trace_grid(a.s.tp.n)), dim3(kTraceBlock), lds, stream, a);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;
 }

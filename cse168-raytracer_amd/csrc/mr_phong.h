@@ -7,6 +7,8 @@
 //                    refractive occluder -> dot(N, l) (0 if negative or < epsilon), no occluder -> 1
 //   phong_terms      diffuse term and highlight of a hit (Phong.cpp:116-156) for a material record and a point light;
 //                    disc_terms: for a DirectionalAreaLight; highlight_of is the one highlight (:149-156) of all of them
+//                    `samples`, where a caller gives it, is the number of shadow rays the light's wattage is divided among
+//                    (a SquareLight, Phong.cpp:146 / :154); the callers without it divide by a literal 1, which is no operation
 //   phong_combine    the two terms and the light scale put together
 //   phong_direct     direct light of an unoccluded hit on the frame's uniform material, with the normal normalised as
 //                    Scene::trace leaves it (Scene.cpp:262): phong_terms + phong_combine
@@ -85,12 +87,13 @@ __device__ __forceinline__ float light_scale_of(const rec::MeshMat &m, const flo
 
 // The specular highlight (Phong.cpp:149-156).  l: the normalised direction to the light, N normalised, (dx, dy, dz) the
 // direction of the ray that produced the hit, f2 the light's falloff factor.
-__device__ __forceinline__ float highlight_of(const float l[3], const float N[3], float dx, float dy, float dz, float f2, float wattage) {
+__device__ __forceinline__ float highlight_of(const float l[3], const float N[3], float dx, float dy, float dz, float f2, float wattage,
+                                              float samples = 1.0f) {
     const float two = 2 * ((l[0] * N[0] + l[1] * N[1]) + l[2] * N[2]);
     const float rx = -l[0] + two * N[0], ry = -l[1] + two * N[1], rz = -l[2] + two * N[2];
     float e = (-dx * rx + -dy * ry) + -dz * rz;
     e = powf(fmaxf(0.0f, fminf(1.0f, e)), 500.0f);
-    return fmaxf(0.0f, e * f2 * wattage);
+    return fmaxf(0.0f, e * f2 * wattage / samples);                // :154
 }
 // Phong.cpp:146-156 once the light has given l, nDotL and its falloff factor f2: diffuse[c] (to be multiplied by the light
 // scale, :146) and the highlight (added unscaled; 0 for a material of infinite shininess)
@@ -98,10 +101,10 @@ __device__ __forceinline__ float highlight_of(const float l[3], const float N[3]
 // plain Phong (Phong::diffuse2D), which is the second form.  The highlight does not see it.
 __device__ __forceinline__ void lit_terms(const float color[3], float wattage, const float *mt, const float *dc, const float N[3],
                                           const float l[3], float nDotL, float f2, float dx, float dy, float dz, float diffuse[3],
-                                          float &highlight) {
-    const float diff = fmaxf(0.0f, nDotL * f2 * wattage);
+                                          float &highlight, float samples = 1.0f) {
+    const float diff = fmaxf(0.0f, nDotL * f2 * wattage / samples);
     for (int c = 0; c < 3; c++) diffuse[c] = color[c] * (diff * dc[c] * mt[c]);               // :146
-    highlight = mt[9] < __builtin_huge_valf() ? highlight_of(l, N, dx, dy, dz, f2, wattage) : 0.0f;
+    highlight = mt[9] < __builtin_huge_valf() ? highlight_of(l, N, dx, dy, dz, f2, wattage, samples) : 0.0f;
 }
 __device__ __forceinline__ void lit_terms(const float color[3], float wattage, const float *mt, const float N[3], const float l[3],
                                           float nDotL, float f2, float dx, float dy, float dz, float diffuse[3], float &highlight) {
@@ -114,18 +117,19 @@ __device__ __forceinline__ void lit_terms(const float color[3], float wattage, c
 // (dx, dy, dz) the direction of the ray that produced the hit.
 __device__ __forceinline__ void phong_terms(const float L[3], const float color[3], float wattage, const float *mt, const float *dc,
                                             const float P[3], const float N[3], float dx, float dy, float dz, float diffuse[3],
-                                            float &highlight) {
+                                            float &highlight, float samples = 1.0f) {
     float l[3] = {L[0] - P[0], L[1] - P[1], L[2] - P[2]};
     const float falloff = (l[0] * l[0] + l[1] * l[1]) + l[2] * l[2];
     const float inv = 1.0f / sqrtf(falloff);
     l[0] *= inv; l[1] *= inv; l[2] *= inv;
     const float nDotL = (N[0] * l[0] + N[1] * l[1]) + N[2] * l[2];
     const float f2 = 1.0f / (falloff * 4.0f * kPhongPI * kPhongPI);                           // :140
-    lit_terms(color, wattage, mt, dc, N, l, nDotL, f2, dx, dy, dz, diffuse, highlight);
+    lit_terms(color, wattage, mt, dc, N, l, nDotL, f2, dx, dy, dz, diffuse, highlight, samples);
 }
 __device__ __forceinline__ void phong_terms(const float L[3], const float color[3], float wattage, const float *mt, const float P[3],
-                                            const float N[3], float dx, float dy, float dz, float diffuse[3], float &highlight) {
-    phong_terms(L, color, wattage, mt, mt, P, N, dx, dy, dz, diffuse, highlight);
+                                            const float N[3], float dx, float dy, float dz, float diffuse[3], float &highlight,
+                                            float samples = 1.0f) {
+    phong_terms(L, color, wattage, mt, mt, P, N, dx, dy, dz, diffuse, highlight, samples);
 }
 __device__ __forceinline__ void phong_terms(const LightArgs &a, const float *mt, const float *dc, const float P[3], const float N[3],
                                             float dx, float dy, float dz, float diffuse[3], float &highlight) {
@@ -153,6 +157,9 @@ __device__ __forceinline__ bool disc_terms(const ShadeLight &lt, const float *mt
     return disc_terms(lt, mt, mt, P, N, l, dx, dy, dz, diffuse, highlight);
 }
 
+// The light-list kernels of point and disc lights add a light's two terms to L at once, L += diffuse * scale + highlight.
+// Phong.cpp:146 and :155 add them one after the other, L += diffuse * scale; L += highlight, and so does the square-light
+// kernel (mr_distribution.hip).  Once L != 0 the two forms round differently; each kernel family keeps its own.
 __device__ __forceinline__ void phong_combine(const float diffuse[3], float highlight, float scale, float out[3]) {
     if (scale == 0.0f) { out[0] = 0.f; out[1] = 0.f; out[2] = 0.f; return; }
     for (int c = 0; c < 3; c++) out[c] = diffuse[c] * scale + highlight;

@@ -27,10 +27,6 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-void cross3(const float a[3], const float b[3], float o[3]) {
-    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 struct Buffers : PhotonRoundBuffers {
     ~Buffers() {
         (void)hipFree(slots); (void)hipFree(compact); (void)hipFree(words); (void)hipFree(offsets); (void)hipFree(next); (void)hipFree(header);
@@ -79,10 +75,7 @@ mr_status mr_trace_photons(mr_scene *s, mr_photon_map *map, const mr_photon_trac
     const uint32_t max_depth = desc->max_depth ? desc->max_depth : 5u;          // TRACE_DEPTH_PHOTONS (Miro.h:14)
     PhotonWalkLight wl;
     {
-        const float ez[3] = {0.f, 0.f, 1.f}, ey[3] = {0.f, 1.f, 0.f};
-        cross3(ez, lt.normal, wl.t1);                                            // getTangents (Utility.h:25-31)
-        if ((double)((wl.t1[0] * wl.t1[0] + wl.t1[1] * wl.t1[1]) + wl.t1[2] * wl.t1[2]) < 1e-6) cross3(ey, lt.normal, wl.t1);
-        cross3(wl.t1, lt.normal, wl.t2);
+        tangents_of(lt.normal, wl.t1, wl.t2);                                    // getTangents (Utility.h:25-31)
         float k = kPI * lt.radius * lt.radius;                                   // Scene.cpp:384
         if (desc->caustic) k = k / 10.f;                                         // :446
         for (int c = 0; c < 3; c++) {

@@ -16,7 +16,7 @@
 // Each emission owns max_depth record slots (a photon stores at most once per hit from its second hit on, and walks
 // max_depth + 1 segments) and one packed word: stores | segments << 8.
 //
-// Random numbers: the counter-based generator of the eye-ray jitter (pcg32 / unit01, mr_recursion.h).  Keys are documented
+// Random numbers: the counter-based generator of the eye-ray jitter (pcg32 / unit01, mr_internal.h).  Keys are documented
 // next to mr_trace_photons in miro_hip.h.
 #include <hip/hip_runtime.h>
 

@@ -5,8 +5,8 @@
 //   ChildGen<PATH>       Ray::reflect / getReflectionCoefficient / refract (Ray.h:143-243, Scene.cpp:302-336), or their
 //                        PATH_TRACING build plus Ray::random (Ray.h:124-158,235-239)
 //   write_children       wave64 ballot compaction of the children, one atomic per workgroup (workgroup_reserve)
-//   pcg32 / unit01       the counter-based random numbers
-// The hit point, the normal and the material of a hit are mr_surface.h (rec::MeshMat), Phong::shade is mr_phong.h.
+// The counter-based random numbers (pcg32 / unit01) and getTangents are mr_internal.h.  The hit point, the normal and the
+// material of a hit are mr_surface.h (rec::MeshMat), Phong::shade is mr_phong.h.
 // Device code only.
 #pragma once
 
@@ -71,27 +71,13 @@ __device__ __forceinline__ void reflect_dir(const float d[3], const float N[3], 
     r[0] *= inv; r[1] *= inv; r[2] *= inv;
 }
 
-__host__ __device__ __forceinline__ uint32_t pcg32(uint32_t x) {
-    const uint32_t state = x * 747796405u + 2891336453u;
-    const uint32_t word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
-    return (word >> 22u) ^ word;
-}
-__device__ __forceinline__ float unit01(uint32_t h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }
-
-__device__ __forceinline__ void cross3(const float a[3], const float b[3], float o[3]) {
-    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 // Ray::alignToVector (Ray.h:86-91): direction = alignHemisphereToVector(v, theta, phi) (Utility.h:34-50), origin = P +
 // epsilon * direction
 __device__ __forceinline__ void align_to_vector(const float v[3], const float P[3], float theta, float phi, float org[3], float dir[3]) {
     const float sp = mm_sinf(phi), cp = mm_cosf(phi), st = mm_sinf(theta), ct = mm_cosf(theta);
     const float u1 = sp * ct, u2 = sp * st, u3 = cp;
-    const float ez[3] = {0.f, 0.f, 1.f}, ey[3] = {0.f, 1.f, 0.f};
     float t1[3], t2[3];
-    cross3(ez, v, t1);
-    if ((double)((t1[0] * t1[0] + t1[1] * t1[1]) + t1[2] * t1[2]) < 1e-6) cross3(ey, v, t1);     // float < double literal
-    cross3(t1, v, t2);
+    tangents_of(v, t1, t2);
     for (int c = 0; c < 3; c++) dir[c] = (t1[c] * u1 + t2[c] * u2) + v[c] * u3;
     const float inv = 1.0f / sqrtf((dir[0] * dir[0] + dir[1] * dir[1]) + dir[2] * dir[2]);
     for (int c = 0; c < 3; c++) { dir[c] *= inv; org[c] = P[c] + dir[c] * kEps; }

@@ -11,16 +11,18 @@ compares generated eye rays by their bytes, so there is no tolerance to fall bac
 tolerance tests/test_lights.py applies to mr_shade_lights against its checker (rtol 1e-5, atol 1e-7 x max: powf on the device
 vs pow in the checker needs it)."""
 import ctypes as C
-import json
 import math
 import os
 import re
+import sys
 import subprocess
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_budget  # noqa: E402
 F = np.float32
 EPS = F(1e-4)                                                   # Miro.h:9
 PI = F(3.1415926535897932384626433832795028841972)              # Miro.h:10
@@ -451,33 +453,13 @@ def test_no_lens_sample_of_the_gpu_input_exhausts_the_rounds():
         assert (lx * lx + ly * ly <= F(APERTURE) * F(APERTURE)).all() and np.abs(lx).max() > 0.5 * APERTURE
 
 
-def _distribution_kernels():
-    pat = re.compile(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Dynamic Stack: (\w+).*?"
-                     r"Occupancy \[waves/SIMD\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", re.S)
-    path = os.path.join(ROOT, "cse168-raytracer_amd", "build", "mr_distribution.remarks.txt")
-    assert os.path.exists(path), "build the library first (__graft_entry__.build())"
-    return {"mr_distribution:" + name: {"vgprs": int(v), "scratch_bytes_per_lane": int(sc), "dynamic_stack": dyn == "True",
-                                        "waves_per_simd": int(occ), "sgprs_spilled": int(ss), "vgprs_spilled": int(vs)}
-            for name, v, sc, dyn, occ, ss, vs in pat.findall(open(path).read())}
-
-
 def test_distribution_kernels_stay_inside_the_verified_envelope():
     """Every kernel of mr_distribution.hip: no dynamic stack; no more spilled VGPRs, no more scratch per lane and no fewer waves
     per SIMD than BOTH its own record (tests/golden/kernel_budget_distribution.json, written from the build whose GPU tests were
     green) AND the worst value among the kernels of tests/golden/kernel_budget.json."""
-    cur = _distribution_kernels()
+    cur = kernel_budget.unit_kernels("mr_distribution")
     assert len(cur) == 13 and sum("shade_square_lights_kernel" in k for k in cur) == 12 and sum("eye_rays_lens_kernel" in k for k in cur) == 1
-    old = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_budget.json")))["kernels"]
-    worst = dict(vgprs_spilled=max(v["vgprs_spilled"] for v in old.values()), scratch=max(v["scratch_bytes_per_lane"] for v in old.values()),
-                 waves=min(v["waves_per_simd"] for v in old.values()))
-    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_budget_distribution.json")))["kernels"]
-    assert not sorted(set(cur) - set(rec)), "kernels without a verified record"
-    for name, c in cur.items():
-        r = rec[name]
-        assert not c["dynamic_stack"], name
-        assert c["vgprs_spilled"] <= min(r["vgprs_spilled"], worst["vgprs_spilled"]), (name, c, r)
-        assert c["scratch_bytes_per_lane"] <= min(r["scratch_bytes_per_lane"], worst["scratch"]), (name, c, r)
-        assert c["waves_per_simd"] >= max(r["waves_per_simd"], worst["waves"]), (name, c, r)
+    kernel_budget.assert_inside_envelope(cur, "kernel_budget_distribution.json")
 
 
 # ---- on the MI355X: the lens ---------------------------------------------------------------------------------------------

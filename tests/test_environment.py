@@ -7,15 +7,17 @@ numpy's double functions rounded to float, which the first test shows to be mm_a
 for bit.  PARITY UNPINNED: the reference cannot be built here and publishes no numbers for its environment; the checker is a
 restatement written from the cited lines."""
 import ctypes as C
-import json
 import os
 import re
+import sys
 import subprocess
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_budget  # noqa: E402
 F = np.float32
 PI = F(3.1415926535897932384626433832795028841972)              # Miro.h:10
 MISS = 0xFFFFFFFF
@@ -328,34 +330,14 @@ def test_restatement_self_checks(miro):
     assert val.std() > 100 * RTOL * val.mean()                                         # the image varies far above the tolerance
 
 
-def _environment_kernels():
-    pat = re.compile(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Dynamic Stack: (\w+).*?"
-                     r"Occupancy \[waves/SIMD\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", re.S)
-    path = os.path.join(ROOT, "cse168-raytracer_amd", "build", "mr_environment.remarks.txt")
-    assert os.path.exists(path), "build the library first (__graft_entry__.build())"
-    return {"mr_environment:" + name: {"vgprs": int(v), "scratch_bytes_per_lane": int(sc), "dynamic_stack": dyn == "True",
-                                       "waves_per_simd": int(occ), "sgprs_spilled": int(ss), "vgprs_spilled": int(vs)}
-            for name, v, sc, dyn, occ, ss, vs in pat.findall(open(path).read())}
-
-
 def test_environment_kernels_stay_inside_the_verified_envelope():
     """Every kernel of mr_environment.hip: no dynamic stack; no more spilled VGPRs, no more scratch per lane and no fewer waves
     per SIMD than BOTH its own record (tests/golden/kernel_budget_environment.json, written from the build whose GPU tests were
     green) AND the worst value among the kernels of tests/golden/kernel_budget.json.  The unit's remarks live in
     build/mr_environment.remarks.txt, which test_build_budget.py does not read."""
-    cur = _environment_kernels()
+    cur = kernel_budget.unit_kernels("mr_environment")
     assert len(cur) == 8 and all("shade_environment_kernel" in k for k in cur)
-    old = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_budget.json")))["kernels"]
-    worst = dict(vgprs_spilled=max(v["vgprs_spilled"] for v in old.values()), scratch=max(v["scratch_bytes_per_lane"] for v in old.values()),
-                 waves=min(v["waves_per_simd"] for v in old.values()))
-    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_budget_environment.json")))["kernels"]
-    assert not sorted(set(cur) - set(rec)), "kernels without a verified record"
-    for name, c in cur.items():
-        r = rec[name]
-        assert not c["dynamic_stack"], name
-        assert c["vgprs_spilled"] <= min(r["vgprs_spilled"], worst["vgprs_spilled"]), (name, c, r)
-        assert c["scratch_bytes_per_lane"] <= min(r["scratch_bytes_per_lane"], worst["scratch"]), (name, c, r)
-        assert c["waves_per_simd"] >= max(r["waves_per_simd"], worst["waves"]), (name, c, r)
+    kernel_budget.assert_inside_envelope(cur, "kernel_budget_environment.json")
 
 
 def build_shim_environment(tmp_path, miro):

@@ -9,15 +9,17 @@ checker is a restatement written from the cited lines of the reference.
 The point light is checked against the product's own batched chain (mr_gen_shadow_rays -> mr_trace_indirect ->
 mr_shade_accumulate), which tests/test_specular.py holds to the oracle: one point light must give the chain's bits."""
 import ctypes as C
-import json
 import os
 import re
+import sys
 import subprocess
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_budget  # noqa: E402
 F = np.float32
 EPS = F(1e-4)                                                   # Miro.h:9
 PI = F(3.1415926535897932384626433832795028841972)              # Miro.h:10
@@ -229,35 +231,15 @@ def test_scene_table_carries_the_light_lists():
     assert two["objects"] == scenes.SCENES["photon_room"]["objects"]
 
 
-def _lights_kernels():
-    pat = re.compile(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Dynamic Stack: (\w+).*?"
-                     r"Occupancy \[waves/SIMD\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", re.S)
-    path = os.path.join(ROOT, "cse168-raytracer_amd", "build", "mr_lights.remarks.txt")
-    assert os.path.exists(path), "build the library first (__graft_entry__.build())"
-    return {"mr_lights:" + name: {"vgprs": int(v), "scratch_bytes_per_lane": int(sc), "dynamic_stack": dyn == "True", "waves_per_simd": int(occ),
-                                  "sgprs_spilled": int(ss), "vgprs_spilled": int(vs)}
-            for name, v, sc, dyn, occ, ss, vs in pat.findall(open(path).read())}
-
-
 def test_lights_kernels_stay_inside_the_verified_envelope():
     """Every kernel of mr_lights.hip: no dynamic stack; no more spilled VGPRs, no more scratch per lane and no fewer waves per
     SIMD than BOTH its own record (tests/golden/kernel_budget_lights.json, written from the build whose GPU tests were green)
     AND the worst value among the kernels of tests/golden/kernel_budget.json.  The unit's remarks live in
     build/mr_lights.remarks.txt, which test_build_budget.py does not read."""
-    cur = _lights_kernels()
+    cur = kernel_budget.unit_kernels("mr_lights")
     assert len(cur) >= 6 and all("shade_lights_kernel" in k for k in cur)
     assert not any("trace_kernel" in k or "frame_kernel" in k for k in cur)
-    old = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_budget.json")))["kernels"]
-    worst = dict(vgprs_spilled=max(v["vgprs_spilled"] for v in old.values()), scratch=max(v["scratch_bytes_per_lane"] for v in old.values()),
-                 waves=min(v["waves_per_simd"] for v in old.values()))
-    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_budget_lights.json")))["kernels"]
-    assert not sorted(set(cur) - set(rec)), "kernels without a verified record"
-    for name, c in cur.items():
-        r = rec[name]
-        assert not c["dynamic_stack"], name
-        assert c["vgprs_spilled"] <= min(r["vgprs_spilled"], worst["vgprs_spilled"]), (name, c, r)
-        assert c["scratch_bytes_per_lane"] <= min(r["scratch_bytes_per_lane"], worst["scratch"]), (name, c, r)
-        assert c["waves_per_simd"] >= max(r["waves_per_simd"], worst["waves"]), (name, c, r)
+    kernel_budget.assert_inside_envelope(cur, "kernel_budget_lights.json")
 
 
 def test_restatement_leaves_few_rays_out_and_takes_every_branch(oracle):

@@ -7,12 +7,14 @@ Texture.cpp:23-28,161-185, TriangleMeshLoad.cpp:81-111,154-158,198-250.  The hit
 tests/test_objects.py and tests/test_gpu_parity.py hold to the oracle.  The shading tests lean on the UNTEXTURED kernels of the
 same calls (tests/test_lights.py ties them to the oracle): with A = the untextured result for Phong(kd = 1, ks, kt) and B the one
 for kd = 0 (the highlights alone), the textured result is (A - B) * tex / m + B per ray and channel, m = clamp(1 - ks - kt)."""
-import json
 import os
-import re
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import kernel_budget  # noqa: E402
 
 F = np.float32
 PI = F(3.1415926535897932384626433832795028841972)
@@ -290,24 +292,12 @@ def test_texture_kernels_stay_inside_the_verified_envelope():
     read): no dynamic stack; no more spilled VGPRs, no more scratch per lane and no fewer waves per SIMD than its record in
     tests/golden/kernel_budget_textures.json, written from the build whose GPU tests were green.  The textured light-list
     kernels keep their sibling's amdgpu_waves_per_eu(6, 8) contract: at least 6 waves per SIMD, in all 12 variants."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pat = re.compile(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Dynamic Stack: (\w+).*?"
-                     r"Occupancy \[waves/SIMD\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", re.S)
-    path = os.path.join(root, "cse168-raytracer_amd", "build", "mr_textures.remarks.txt")
-    assert os.path.exists(path), "build the library first (__graft_entry__.build())"
-    cur = {"mr_textures:" + name: dict(scratch=int(sc), dynamic=dyn == "True", waves=int(occ), spilled=int(vs))
-           for name, v, sc, dyn, occ, ss, vs in pat.findall(open(path).read())}
-    rec = json.load(open(os.path.join(root, "tests", "golden", "kernel_budget_textures.json")))["kernels"]
-    assert not sorted(set(cur) - set(rec)), "kernels without a verified record"
+    cur = kernel_budget.unit_kernels("mr_textures")
     lights = [k for k in cur if "shade_lights_tex_kernel" in k]
     assert len(lights) == 12 and len(cur) == 15
-    for name, c in cur.items():
-        r = rec[name]
-        assert not c["dynamic"], name
-        assert c["spilled"] <= r["vgprs_spilled"] and c["scratch"] <= r["scratch_bytes_per_lane"], (name, c, r)
-        assert c["waves"] >= r["waves_per_simd"], (name, c, r)
-        if name in lights:
-            assert c["waves"] >= 6, (name, c)
+    kernel_budget.assert_inside_envelope(cur, "kernel_budget_textures.json", also_main=False)
+    for name in lights:
+        assert cur[name]["waves_per_simd"] >= 6, (name, cur[name])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

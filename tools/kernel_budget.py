@@ -14,15 +14,44 @@ PAT = re.compile(r"Function Name: (\S+).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?Scr
 MANIFEST = os.path.join(ROOT, "tests", "golden", "kernel_budget.json")
 
 
+def _records(path, unit):
+    return {"%s:%s" % (unit, name): {"vgprs": int(vgprs), "scratch_bytes_per_lane": int(scratch), "dynamic_stack": dyn == "True",
+                                     "waves_per_simd": int(occ), "sgprs_spilled": int(sspill), "vgprs_spilled": int(vspill)}
+            for name, sgprs, vgprs, scratch, dyn, occ, sspill, vspill in PAT.findall(open(path).read())}
+
+
 def current(build_dir=None):
     build_dir = build_dir or os.path.join(ROOT, "cse168-raytracer_amd", "build")
     out = {}
     for f in sorted(glob.glob(os.path.join(build_dir, "*.resource-usage.txt"))):
-        unit = os.path.basename(f).replace(".resource-usage.txt", "")
-        for name, sgprs, vgprs, scratch, dyn, occ, sspill, vspill in PAT.findall(open(f).read()):
-            out["%s:%s" % (unit, name)] = {"vgprs": int(vgprs), "scratch_bytes_per_lane": int(scratch), "dynamic_stack": dyn == "True",
-                                           "waves_per_simd": int(occ), "sgprs_spilled": int(sspill), "vgprs_spilled": int(vspill)}
+        out.update(_records(f, os.path.basename(f).replace(".resource-usage.txt", "")))
     return out
+
+
+def unit_kernels(unit, build_dir=None):
+    """The kernels of a unit whose remarks the Makefile keeps out of *.resource-usage.txt (REMARK_UNITS): build/<unit>.remarks.txt"""
+    path = os.path.join(build_dir or os.path.join(ROOT, "cse168-raytracer_amd", "build"), unit + ".remarks.txt")
+    assert os.path.exists(path), "build the library first (__graft_entry__.build())"
+    return _records(path, unit)
+
+
+def assert_inside_envelope(cur, record, also_main=True):
+    """Every kernel of `cur`: known to tests/golden/<record>; no dynamic stack; no more spilled VGPRs, no more scratch per lane
+    and no fewer waves per SIMD than its own record -- and, with also_main, than the worst value among the kernels of
+    tests/golden/kernel_budget.json as well."""
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", record)))["kernels"]
+    assert not sorted(set(cur) - set(rec)), "kernels without a verified record"
+    worst = dict(vgprs_spilled=float("inf"), scratch=float("inf"), waves=0)
+    if also_main:
+        old = json.load(open(MANIFEST))["kernels"].values()
+        worst = dict(vgprs_spilled=max(v["vgprs_spilled"] for v in old), scratch=max(v["scratch_bytes_per_lane"] for v in old),
+                     waves=min(v["waves_per_simd"] for v in old))
+    for name, c in cur.items():
+        r = rec[name]
+        assert not c["dynamic_stack"], name
+        assert c["vgprs_spilled"] <= min(r["vgprs_spilled"], worst["vgprs_spilled"]), (name, c, r)
+        assert c["scratch_bytes_per_lane"] <= min(r["scratch_bytes_per_lane"], worst["scratch"]), (name, c, r)
+        assert c["waves_per_simd"] >= max(r["waves_per_simd"], worst["waves"]), (name, c, r)
 
 
 if __name__ == "__main__":
