@@ -163,6 +163,10 @@ inline FrameShape frame_schedule(unsigned long long chunks) {
 // end time (100 MHz constant clock), the CU it ran on and its XCD -- where the launch's idle VALU cycles sit
 __device__ unsigned long long g_wg_times[4 * 131072];
 #endif
+#if defined(MIRO_RUN_COUNTS)
+// measurement build only (mr_traverse.h: Stats): wave-level node visits summed over every launch since the last reading
+__device__ unsigned long long g_run_counts[3];
+#endif
 // kEyeRel (VAR kTraceEyeRel, the default traversal of triangle-only scenes, every SHADOW / MAT form): the primary ray is traced on the
 // eye-relative tables from a zero origin (trace_ray's REL), the shadow ray on the scene's own.  Every primary ray starts at
 // the eye, so the origin's share of each slab and triangle test is the same for all of them: computed once per eye by a build
@@ -176,6 +180,12 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
     const unsigned long long wg_t0 = wall_clock64();
 #endif
     constexpr bool kEyeRel = VAR == kTraceEyeRel;
+    // both traces keep wave-uniform node visits on the scalar side (uniform_run, mr_traverse.h: in the octant loops with the
+    // three-pair guard).  The frame kernel alone asks for it -- at 64 samples per pixel its waves are single pixels; the batched
+    // and level kernels keep the code they were verified with -- and only in its eye-relative, uniform-material forms: with
+    // per-object materials or objects in the scene the run's scalar registers push the kernel out of its recorded
+    // scratch / spill envelope (tests/golden/kernel_budget.json).
+    constexpr bool kRun = kEyeRel && !MAT;
     if (kEyeRel && a.build) {
         eye_tables(a);
         return;
@@ -258,7 +268,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
                     tp.root_lo[k] = kernarg_now<float>(offsetof(FrameArgs, rel_root_lo) + 4 * k);
                     tp.root_hi[k] = kernarg_now<float>(offsetof(FrameArgs, rel_root_hi) + 4 * k);
                 }
-                trace_ray<true, false, false, VAR, kEyeRel>(tp, r, rb.w, live, L, plane_hit, s_stack, tid, st);
+                trace_ray<true, false, false, VAR, kEyeRel, kRun>(tp, r, rb.w, live, L, plane_hit, s_stack, tid, st);
             } else {
                 trace_ray<true, false, false, VAR>(a.tp, r, rb.w, live, L, plane_hit, s_stack, tid, st);
             }
@@ -301,7 +311,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
             ray_setup(r, sa, sb);
             Lane L;
             int plane_hit;
-            trace_ray<true, SHADOW == 1, false, VAR>(a.tp, r, sb.w, hit, L, plane_hit, s_stack, tid, st);
+            trace_ray<true, SHADOW == 1, false, VAR, false, kRun>(a.tp, r, sb.w, hit, L, plane_hit, s_stack, tid, st);
             mr_hit hs = make_hit<kObj>(a.tp, L, plane_hit, sb.w);
             if (!hit) { hs.t = 0.0f; hs.prim = MR_MISS; hs.beta = 0.0f; hs.gamma = 0.0f; }
             if (a.shadow_hits && live) reinterpret_cast<float4 *>(a.shadow_hits)[idx] = *reinterpret_cast<const float4 *>(&hs);
@@ -361,6 +371,12 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
             if (blockIdx.x == 0) atomicAdd(&a.counts[0], n);
         }
     }
+#if defined(MIRO_RUN_COUNTS)
+    {
+        const unsigned mine[3] = {st.node_steps, st.run_visits, st.run_splits};
+        workgroup_add<kTraceBlock, 3>(mine, g_run_counts);
+    }
+#endif
 #if defined(MIRO_WG_TIMES) && MIRO_TRACE_BLOCK == 256
     if (tid == 0 && blockIdx.x < 131072u) {
         g_wg_times[4 * blockIdx.x] = wg_t0;
@@ -370,6 +386,23 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
     }
 #endif
 }
+#if defined(MIRO_RUN_COUNTS)
+}  // namespace
+}  // namespace mr
+#if MIRO_TRACE_BLOCK == 256
+#define MR_RUN_COUNTS_ENTRY mr_debug_run_counts_b256
+#else
+#define MR_RUN_COUNTS_ENTRY mr_debug_run_counts_b128
+#endif
+// {node visits, visits inside a run, runs ended by a split decision} of this unit's launches; reading resets them
+extern "C" int MR_RUN_COUNTS_ENTRY(unsigned long long *out) {
+    const unsigned long long zero[3] = {0ull, 0ull, 0ull};
+    const int e = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mr::g_run_counts), sizeof(zero), 0, hipMemcpyDeviceToHost);
+    return e ? e : (int)hipMemcpyToSymbol(HIP_SYMBOL(mr::g_run_counts), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
+}
+namespace mr {
+namespace {
+#endif
 #if defined(MIRO_WG_TIMES) && MIRO_TRACE_BLOCK == 256
 }  // namespace
 }  // namespace mr

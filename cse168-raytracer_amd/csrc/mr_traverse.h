@@ -50,7 +50,20 @@ __device__ __forceinline__ unsigned xcd_block_id() {
 constexpr float kEps = 1e-4f;        // Miro.h:9
 constexpr float kInf = __builtin_huge_valf();
 
+#ifdef MIRO_RUN_COUNTS
+// measurement build only (make VARIANT=_runc FRAME_DEFS=-DMIRO_RUN_COUNTS; tools/run_counts.py): wave-level node visits of the
+// fused frame kernel -- those taken outside uniform_run, those inside it, and those at which a run ended on a split decision.
+// One lane of the wave counts each event, so the sum over lanes is the number of wave-visits.
+struct Stats { unsigned long long box, tri; unsigned node_steps, run_visits, run_splits; };
+__device__ __forceinline__ void run_count_once(unsigned &c) {
+    const int lane = (int)__lane_id();
+    if (__builtin_amdgcn_readfirstlane(lane) == lane) c++;
+}
+#define MR_RUN_COUNT(field) run_count_once(field)
+#else
 struct Stats { unsigned long long box, tri; };
+#define MR_RUN_COUNT(field) ((void)0)      /* the counters are fields of the counting build's Stats only */
+#endif
 
 // ---------------------------------------------------------------------------------------------------
 // slab test of one box.  EXACT keeps the reference's predicate structure literally (BVH.cpp:599-608):
@@ -408,10 +421,79 @@ __device__ __forceinline__ void node_decide(float mn0, float mx0, float mn1, flo
     }
 }
 
+// The uniform run (octant loops with the three-pair guard, SLAB 6, of the fused frame kernel): entered by node_step once its test
+// has found every active lane of the wave at the node `cur`; from there `cur` is a SCALAR for as long as the lanes also take the
+// same decision.  At 64 samples per pixel a wave is one pixel -- 64 jittered rays through it, or 64 shadow rays from one patch
+// of surface to one light -- and what node_step pays per visit for lanes that may part at any moment (v_readfirstlane + v_cmp +
+// branch to find the wave at one node again, the exec-mask nest of node_decide, the child references moved to VGPRs and selected
+// per lane for L.cur and the push) is then spent on finding out what the compare masks already say: all active lanes hit both
+// children with the same near one, all hit only child 0, all only child 1, or none hits either.  In the first three cases the
+// next node is the scalar child reference and the far one, if any, is pushed from one v_mov; the loop goes on without touching
+// L.cur.  Otherwise -- a split decision, a pop (the lanes' stacks are their own: nothing says the popped values are equal), a leaf,
+// an irregular node -- L.cur is written per lane exactly as node_decide writes it and the run ends: node_step's own test starts
+// the next one.  Same bits: every floating-point instruction of a visit is the one node_step issues (the same load_node_scalar,
+// node_slabs_guarded -- its wave-wide exact-quotient recomputation included -- and, for irregular nodes, node_slabs<3>) on the
+// same operands; every lane keeps its own stack, pushes what node_decide would have pushed and visits the nodes in the same
+// order -- a wave in the run is a wave for which node_step's test would have succeeded at every visit.  Nothing is shared between
+// the lanes but the knowledge that their values are equal, so leaving the run needs no recovery step.
+template <bool EXACT, int OCT>
+__device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, Stats &st, int cur) {
+    const unsigned long long m_all = __builtin_amdgcn_ballot_w64(true);
+    float mn0, mx0, mn1, mx1, k0, k1;
+    int node, ref0, ref1;
+    bool regular;
+    // One loop exit, one scalar test for it: `cur` is the next node while the lanes agree, a leaf reference when they agree on a
+    // leaf, and kDone -- which is no child reference -- when the visit of `node` has to be finished behind the loop (pop, split
+    // decision, irregular node).
+    do {
+        node = cur;
+        const v16f v = load_node_scalar(p.nodes, node);
+        const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
+        const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
+        ref0 = __float_as_int(v[12]); ref1 = __float_as_int(v[13]);
+        regular = __float_as_int(v[14]) == 0;
+        MR_RUN_COUNT(st.run_visits);
+        cur = kDone;
+        if (regular) {
+            k0 = 0.0f; k1 = 0.0f;
+            node_slabs_guarded<EXACT, false, 6, OCT>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
+            // node_decide's comparisons (its SAFE form) as lane masks: out = the lanes whose ray misses the child
+            const unsigned long long out0 = (__builtin_amdgcn_ballot_w64(mn0 > k0) | __builtin_amdgcn_ballot_w64(mx0 < r.tmin)) & m_all;
+            const unsigned long long out1 = (__builtin_amdgcn_ballot_w64(mn1 > k1) | __builtin_amdgcn_ballot_w64(mx1 < r.tmin)) & m_all;
+            if ((out0 | out1) == 0ull) {                              // every lane hits both: near child first, ties -> child 0
+                const unsigned long long one_first = __builtin_amdgcn_ballot_w64(mn0 > mn1);
+                if (one_first == 0ull) { stack_push(L, s_stack, ref1); cur = ref0; }
+                else if (one_first == m_all) { stack_push(L, s_stack, ref0); cur = ref1; }
+            } else if ((out0 | (out1 ^ m_all)) == 0ull) {             // every lane hits child 0 only
+                cur = ref0;
+            } else if ((out1 | (out0 ^ m_all)) == 0ull) {             // every lane hits child 1 only
+                cur = ref1;
+            }
+        }
+    } while (cur >= 0);
+    if (cur != kDone) {                                // a leaf: the wave's leaf_step finds it uniform by its own test
+        L.cur = cur;
+    } else if (!regular) {                             // the reference's own divisions, decided lane by lane
+        // (the record is loaded a second time on purpose: kept live across the loop's exit its twelve corners cost the hot loop
+        // scalar registers it spills for, and irregular nodes are rare -- a frame whose eye is irregular, where every visit comes
+        // this way, pays the run's entry and two loads per visit and is slower than before)
+        const v16f v = load_node_scalar(p.nodes, node);
+        const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
+        const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
+        node_slabs<EXACT, false, 3>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
+        node_decide<false, false>(mn0, mx0, mn1, mx1, ref0, ref1, r, L, s_stack, st);
+    } else {                                           // no child hit in some lanes or all (pop), or the lanes part
+        if (((unsigned long long)__builtin_amdgcn_ballot_w64((mn0 > k0) || (mx0 < r.tmin)) &
+             (unsigned long long)__builtin_amdgcn_ballot_w64((mn1 > k1) || (mx1 < r.tmin))) != m_all) MR_RUN_COUNT(st.run_splits);
+        node_decide<false, true, true>(mn0, mx0, mn1, mx1, ref0, ref1, r, L, s_stack, st, k0, k1);
+    }
+}
+
 // SLAB: 0 = select form (the reference's NaN semantics) on (corner - o) * (1/d), 1 = min/max on the same products,
 //       2 = lean fma form, 3 = select form on the reference's true quotients (corner - o) / d
 // SCALAR: try the wave-uniform scalar-load path first
-template <bool EXACT, bool STATS, int SLAB, bool SCALAR = false, int OCT = 8>
+// RUN: ... and stay on the scalar side while the lanes decide alike (uniform_run; the octant loops of the fused frame kernel)
+template <bool EXACT, bool STATS, int SLAB, bool SCALAR = false, int OCT = 8, bool RUN = false>
 __device__ __forceinline__ void node_step(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, int tid, Stats &st) {
     float mn0, mx0, mn1, mx1;
     constexpr bool kSafe = SLAB == 1 || SLAB == 2 || SLAB == 4 || SLAB == 5 || SLAB == 6;
@@ -419,6 +501,11 @@ __device__ __forceinline__ void node_step(const TraceParams &p, const RayRegs &r
     if (SCALAR) {
         const int cur0 = __builtin_amdgcn_readfirstlane(L.cur);
         if (__all(L.cur == cur0)) {
+            if (RUN && SLAB == 6 && OCT < 8 && !STATS) {
+                uniform_run<EXACT, OCT>(p, r, L, s_stack, st, cur0);
+                return;
+            }
+            MR_RUN_COUNT(st.node_steps);
             const v16f v = load_node_scalar(p.nodes, cur0);
             const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
             const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
@@ -434,6 +521,7 @@ __device__ __forceinline__ void node_step(const TraceParams &p, const RayRegs &r
         }
     }
     // ---- inner node: test both children (BVH.cpp:593-624)
+    MR_RUN_COUNT(st.node_steps);
     const float4 *nd = p.nodes + 4 * (size_t)L.cur;
     const float4 q0 = nd[0], q1 = nd[1], q2 = nd[2];
     const int4 q3 = *reinterpret_cast<const int4 *>(nd + 3);
@@ -684,7 +772,7 @@ __device__ __forceinline__ void tri_step(const TraceParams &p, const RayRegs &r,
 //         long as its slowest lane's search for a leaf (incoherent batches: 14 of 64 lanes active per VALU
 //         instruction, profiles/r02_before_random); with the vote at least half of the unfinished lanes are active in every step.  The order of
 //         every lane's own steps -- and so its hit record -- is the same in all three modes.
-template <bool EXACT, bool ANY, bool STATS, int SLAB, int MODE, bool SCALAR, bool OBJ = false, int OCT = 8, bool REL = false>
+template <bool EXACT, bool ANY, bool STATS, int SLAB, int MODE, bool SCALAR, bool OBJ = false, int OCT = 8, bool REL = false, bool RUN = false>
 __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, int tid, Stats &st) {
     if (MODE == 2) {
         L.lpos = 0; L.lend = 0;
@@ -700,7 +788,7 @@ __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r,
         }
     } else if (MODE == 1) {
         while (__any(L.have())) {
-            while (L.cur >= 0) node_step<EXACT, STATS, SLAB, SCALAR, OCT>(p, r, L, s_stack, tid, st);
+            while (L.cur >= 0) node_step<EXACT, STATS, SLAB, SCALAR, OCT, RUN>(p, r, L, s_stack, tid, st);
             if (L.have()) leaf_step<EXACT, ANY, STATS, SCALAR, OBJ, REL>(p, r, L, s_stack, tid, st);
         }
     } else {
@@ -723,7 +811,7 @@ __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r,
 //     travels in the node flags: an irregular eye marks every node irregular, so every visit divides (SLAB 3) as the
 //     scene's tables would have had it do.  Default traversal of triangle-only scenes only.
 // ---------------------------------------------------------------------------------------------------
-template <bool EXACT, bool ANY, bool STATS, int VAR, bool REL = false>
+template <bool EXACT, bool ANY, bool STATS, int VAR, bool REL = false, bool RUN = false>
 __device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r_in, float tmax0, bool live, Lane &L,
                                           int &plane_hit, int *s_stack, int tid, Stats &st) {
     static_assert(!REL || ((VAR & kVarStrict) && !(VAR & kVarObjects) && !STATS), "eye-relative tables: default traversal, triangles only");
@@ -766,14 +854,14 @@ __device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r
             if (__all(!live || oct == oct0) && (kOctSlab != 6 || __all(!live || r.tmin == 0.0f))) {
                 done_oct = true;
                 switch (oct0) {
-                    case 0: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 0, REL>(p, r, L, s_stack, tid, st); break;
-                    case 1: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 1, REL>(p, r, L, s_stack, tid, st); break;
-                    case 2: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 2, REL>(p, r, L, s_stack, tid, st); break;
-                    case 3: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 3, REL>(p, r, L, s_stack, tid, st); break;
-                    case 4: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 4, REL>(p, r, L, s_stack, tid, st); break;
-                    case 5: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 5, REL>(p, r, L, s_stack, tid, st); break;
-                    case 6: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 6, REL>(p, r, L, s_stack, tid, st); break;
-                    default: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 7, REL>(p, r, L, s_stack, tid, st); break;
+                    case 0: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 0, REL, RUN>(p, r, L, s_stack, tid, st); break;
+                    case 1: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 1, REL, RUN>(p, r, L, s_stack, tid, st); break;
+                    case 2: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 2, REL, RUN>(p, r, L, s_stack, tid, st); break;
+                    case 3: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 3, REL, RUN>(p, r, L, s_stack, tid, st); break;
+                    case 4: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 4, REL, RUN>(p, r, L, s_stack, tid, st); break;
+                    case 5: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 5, REL, RUN>(p, r, L, s_stack, tid, st); break;
+                    case 6: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 6, REL, RUN>(p, r, L, s_stack, tid, st); break;
+                    default: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 7, REL, RUN>(p, r, L, s_stack, tid, st); break;
                 }
             }
         }
