@@ -171,11 +171,15 @@ __global__ __launch_bounds__(64 * kOrderWaves) void octant_order_kernel(const mr
 // ---------------------------------------------------------------------------------------------------
 constexpr unsigned long long kPoolChunk = 1024;
 
-// VOTE: the voting control flow of traverse() MODE 2 (one node step or one triangle test per iteration, whichever more
+// VOTE: the voting control flow of traverse(), kFlowVote (one node step or one triangle test per iteration, whichever more
 // lanes need) instead of while-while.
 template <bool EXACT, bool ANY, bool QUOT, int REFILL_MIN, bool VOTE = false>
 __global__ __launch_bounds__(kTraceBlock) void trace_persistent_kernel(TraceParams p, unsigned long long *next_ray) {
     extern __shared__ int s_stack[];
+    // a wave whose armed rays are all safe_lane, and any other wave (the reference's arithmetic; on products it loads its nodes per lane)
+    constexpr int kSafeSlab = QUOT ? kSlabCorrection : kSlabMinMax, kAnySlab = QUOT ? kSlabQuotient : kSlabSelect;
+    using Safe = Walk<EXACT, ANY, false, kSafeSlab, VOTE ? kFlowVote : kFlowWhileWhile, true, false, kNoOct, false, false>;
+    using Any = walk_scalar<walk_slab<Safe, kAnySlab>, QUOT>;
     const int tid = threadIdx.x, lane = tid & 63;
     Stats st = {0ull, 0ull};
     unsigned long long n_rays = p.n;
@@ -250,20 +254,20 @@ __global__ __launch_bounds__(kTraceBlock) void trace_persistent_kernel(TracePara
             const bool want_node = L.cur >= 0, want_tri = L.cur < 0 && L.cur != kDone;
             if (__popcll(__ballot(want_node)) >= __popcll(__ballot(want_tri))) {
                 if (want_node) {
-                    if (wave_safe) node_step<EXACT, false, QUOT ? 4 : 1, true>(p, r, L, s_stack, tid, st);
-                    else node_step<EXACT, false, QUOT ? 3 : 0, QUOT>(p, r, L, s_stack, tid, st);
+                    if (wave_safe) node_step<Safe>(p, r, L, s_stack, tid, st);
+                    else node_step<Any>(p, r, L, s_stack, tid, st);
                 }
             } else if (want_tri) {
-                tri_step<EXACT, ANY, false, true, false>(p, r, L, s_stack, st);
+                tri_step<Safe>(p, r, L, s_stack, st);
             }
             continue;
         }
         if (wave_safe) {
-            while (L.cur >= 0) node_step<EXACT, false, QUOT ? 4 : 1, true>(p, r, L, s_stack, tid, st);
+            while (L.cur >= 0) node_step<Safe>(p, r, L, s_stack, tid, st);
         } else {
-            while (L.cur >= 0) node_step<EXACT, false, QUOT ? 3 : 0, QUOT>(p, r, L, s_stack, tid, st);
+            while (L.cur >= 0) node_step<Any>(p, r, L, s_stack, tid, st);
         }
-        if (L.have()) leaf_step<EXACT, ANY, false, true>(p, r, L, s_stack, tid, st);
+        if (L.have()) leaf_step<Safe>(p, r, L, s_stack, tid, st);
     }
 }
 

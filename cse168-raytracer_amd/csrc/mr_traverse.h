@@ -65,6 +65,47 @@ struct Stats { unsigned long long box, tri; };
 #define MR_RUN_COUNT(field) ((void)0)      /* the counters are fields of the counting build's Stats only */
 #endif
 
+// The integer codes of a walk (values as ever: the profile logs print the numbers) and the type that carries them.
+// Slab form: how a node visit computes and compares the entry / exit distances of its two child boxes.
+constexpr int kSlabSelect     = 0;   // the reference's select chains (slab_axis: a NaN falls through every comparison) on the products (corner - o) * (1/d)
+constexpr int kSlabMinMax     = 1;   // min/max on the same products (slab_box_minmax): the same decisions for rays that cannot produce a NaN
+constexpr int kSlabLean       = 2;   // lean fma form (slab_box_lean, MR_MATH_FAST): distances that differ from the products by rounding
+constexpr int kSlabQuotient   = 3;   // select chains on the reference's true quotients (corner - o) / d: the reference's own arithmetic
+constexpr int kSlabCorrection = 4;   // min/max on products with one correction step (exact_quot): the quotients without a division, regular rays in regular nodes
+constexpr int kSlabGuarded    = 5;   // guarded products: plain products where they provably decide as the quotients do, kSlabCorrection where not (node_slabs_guarded)
+constexpr int kSlabGuardedT0  = 6;   // ... for waves whose rays all have tMin == 0 (the octant loops): three pairs to guard instead of five
+constexpr bool slab_guarded(int s) { return s == kSlabGuarded || s == kSlabGuardedT0; }
+constexpr bool slab_nan_free(int s) { return s == kSlabMinMax || s == kSlabLean || s == kSlabCorrection || slab_guarded(s); }   // no distance is a NaN: node_decide's SAFE form
+constexpr bool slab_divides_irregular(int s) { return s == kSlabCorrection || slab_guarded(s); }   // an irregular node takes kSlabQuotient instead
+constexpr bool slab_has_octant_body(int s) { return s == kSlabMinMax || s == kSlabLean || s == kSlabCorrection; }   // slab_box_oct
+constexpr bool slab_needs_tmin0(int s) { return s == kSlabGuardedT0; }
+// Control flow of traverse().  The order of every lane's own steps -- and so its hit record -- is the same in all three.
+constexpr int kFlowLane       = 0;   // one step of whatever the lane needs per iteration (the reference's control flow, lane by lane)
+constexpr int kFlowWhileWhile = 1;   // "while-while": lanes run inner nodes until each holds a leaf (or is done), then the wave does the leaves
+// voting: every iteration the wave counts the lanes that need a node step and those that need a triangle test and runs the step the
+// majority needs; the others wait one round.  In while-while a wave's node loop lasts as long as its slowest lane's search for a leaf
+// (incoherent batches: 14 of 64 lanes active per VALU instruction, profiles/r02_before_random); with the vote at least half of the
+// unfinished lanes are active in every step.
+constexpr int kFlowVote       = 2;
+constexpr int kNoOct = 8;            // octant of a walk whose wave's rays share none (0..7, bit k set: direction component k is negative)
+constexpr bool is_octant(int oct) { return oct != kNoOct; }
+
+// One walk: what traverse, node_step, leaf_step, tri_step, node_slabs, node_slabs_guarded and uniform_run are instantiated on.
+//   scalar: try the wave-uniform scalar-load path first (nodes and leaves)     obj: leaves may hold spheres     rel: eye-relative tables
+//   run: ... and stay on the scalar side while the lanes decide alike (uniform_run; the octant loops of the fused frame kernel)
+template <bool EXACT, bool ANY, bool STATS, int SLAB, int FLOW, bool SCALAR, bool OBJ, int OCT, bool REL, bool RUN>
+struct Walk {
+    static constexpr bool exact = EXACT, any = ANY, stats = STATS, scalar = SCALAR, obj = OBJ, rel = REL, run = RUN;
+    static constexpr int slab = SLAB, flow = FLOW, oct = OCT;
+};
+// the walk W with one thing changed
+template <typename W, int S, int F = W::flow> using walk_slab = Walk<W::exact, W::any, W::stats, S, F, W::scalar, W::obj, W::oct, W::rel, W::run>;
+template <typename W, int O> using walk_oct = Walk<W::exact, W::any, W::stats, W::slab, W::flow, W::scalar, W::obj, O, W::rel, W::run>;
+template <typename W, bool S> using walk_scalar = Walk<W::exact, W::any, W::stats, W::slab, W::flow, S, W::obj, W::oct, W::rel, W::run>;
+template <typename W, bool R> using walk_run = Walk<W::exact, W::any, W::stats, W::slab, W::flow, W::scalar, W::obj, W::oct, W::rel, R>;
+// the visit of an irregular node: the reference's own divisions, with no octant body
+template <typename W> using walk_divide = walk_oct<walk_slab<W, kSlabQuotient>, kNoOct>;
+
 // ---------------------------------------------------------------------------------------------------
 // slab test of one box.  EXACT keeps the reference's predicate structure literally (BVH.cpp:599-608):
 // NaNs (0 * inf when the origin sits on a slab plane of an axis the ray does not move along) fall
@@ -190,13 +231,16 @@ __device__ __forceinline__ void slab_box_oct(float lox, float hix, float loy, fl
     const float nx = (OCT & 1) ? hix : lox, fx = (OCT & 1) ? lox : hix;
     const float ny = (OCT & 2) ? hiy : loy, fy = (OCT & 2) ? loy : hiy;
     const float nz = (OCT & 4) ? hiz : loz, fz = (OCT & 4) ? loz : hiz;
-    if (SLAB == 4) {
+    switch (SLAB) {      // the forms of slab_has_octant_body
+    case kSlabCorrection:
         mn = vmax3(exact_quot(nx - r.ox, r.dx, r.ix), exact_quot(ny - r.oy, r.dy, r.iy), exact_quot(nz - r.oz, r.dz, r.iz));
         mx = vmin3(exact_quot(fx - r.ox, r.dx, r.ix), exact_quot(fy - r.oy, r.dy, r.iy), exact_quot(fz - r.oz, r.dz, r.iz));
-    } else if (SLAB == 2) {
+        break;
+    case kSlabLean:
         mn = vmax3(fmaf(nx, r.ix, r.nox), fmaf(ny, r.iy, r.noy), fmaf(nz, r.iz, r.noz));
         mx = vmin3(fmaf(fx, r.ix, r.nox), fmaf(fy, r.iy, r.noy), fmaf(fz, r.iz, r.noz));
-    } else {
+        break;
+    default:             // kSlabMinMax
         mn = vmax3((nx - r.ox) * r.ix, (ny - r.oy) * r.iy, (nz - r.oz) * r.iz);
         mx = vmin3((fx - r.ox) * r.ix, (fy - r.oy) * r.iy, (fz - r.oz) * r.iz);
     }
@@ -382,10 +426,10 @@ __device__ __forceinline__ v16f load_node_scalar(const float4 *nodes, int cur_un
     return v;
 }
 
-template <bool EXACT, bool STATS, int SLAB, int OCT = 8>
+template <typename W>
 __device__ __forceinline__ void node_slabs(const float4 q0, const float4 q1, const float4 q2, const RayRegs &r,
                                            float &mn0, float &mx0, float &mn1, float &mx1);
-template <bool EXACT, bool STATS, int SLAB, int OCT = 8>
+template <typename W>
 __device__ __forceinline__ void node_slabs_guarded(const float4 q0, const float4 q1, const float4 q2, const RayRegs &r, float best_t,
                                                    float &mn0, float &mx0, float &mn1, float &mx1, float &k0, float &k1);
 
@@ -421,7 +465,7 @@ __device__ __forceinline__ void node_decide(float mn0, float mx0, float mn1, flo
     }
 }
 
-// The uniform run (octant loops with the three-pair guard, SLAB 6, of the fused frame kernel): entered by node_step once its test
+// The uniform run (octant loops with the three-pair guard, kSlabGuardedT0, of the fused frame kernel): entered by node_step once its test
 // has found every active lane of the wave at the node `cur`; from there `cur` is a SCALAR for as long as the lanes also take the
 // same decision.  At 64 samples per pixel a wave is one pixel -- 64 jittered rays through it, or 64 shadow rays from one patch
 // of surface to one light -- and what node_step pays per visit for lanes that may part at any moment (v_readfirstlane + v_cmp +
@@ -432,11 +476,11 @@ __device__ __forceinline__ void node_decide(float mn0, float mx0, float mn1, flo
 // L.cur.  Otherwise -- a split decision, a pop (the lanes' stacks are their own: nothing says the popped values are equal), a leaf,
 // an irregular node -- L.cur is written per lane exactly as node_decide writes it and the run ends: node_step's own test starts
 // the next one.  Same bits: every floating-point instruction of a visit is the one node_step issues (the same load_node_scalar,
-// node_slabs_guarded -- its wave-wide exact-quotient recomputation included -- and, for irregular nodes, node_slabs<3>) on the
+// node_slabs_guarded -- its wave-wide exact-quotient recomputation included -- and, for irregular nodes, walk_divide) on the
 // same operands; every lane keeps its own stack, pushes what node_decide would have pushed and visits the nodes in the same
 // order -- a wave in the run is a wave for which node_step's test would have succeeded at every visit.  Nothing is shared between
 // the lanes but the knowledge that their values are equal, so leaving the run needs no recovery step.
-template <bool EXACT, int OCT>
+template <typename W>
 __device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, Stats &st, int cur) {
     const unsigned long long m_all = __builtin_amdgcn_ballot_w64(true);
     float mn0, mx0, mn1, mx1, k0, k1;
@@ -456,7 +500,7 @@ __device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs 
         cur = kDone;
         if (regular) {
             k0 = 0.0f; k1 = 0.0f;
-            node_slabs_guarded<EXACT, false, 6, OCT>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
+            node_slabs_guarded<W>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
             // node_decide's comparisons (its SAFE form) as lane masks: out = the lanes whose ray misses the child
             const unsigned long long out0 = (__builtin_amdgcn_ballot_w64(mn0 > k0) | __builtin_amdgcn_ballot_w64(mx0 < r.tmin)) & m_all;
             const unsigned long long out1 = (__builtin_amdgcn_ballot_w64(mn1 > k1) | __builtin_amdgcn_ballot_w64(mx1 < r.tmin)) & m_all;
@@ -480,7 +524,7 @@ __device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs 
         const v16f v = load_node_scalar(p.nodes, node);
         const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
         const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
-        node_slabs<EXACT, false, 3>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
+        node_slabs<walk_divide<W>>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
         node_decide<false, false>(mn0, mx0, mn1, mx1, ref0, ref1, r, L, s_stack, st);
     } else {                                           // no child hit in some lanes or all (pop), or the lanes part
         if (((unsigned long long)__builtin_amdgcn_ballot_w64((mn0 > k0) || (mx0 < r.tmin)) &
@@ -489,34 +533,30 @@ __device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs 
     }
 }
 
-// SLAB: 0 = select form (the reference's NaN semantics) on (corner - o) * (1/d), 1 = min/max on the same products,
-//       2 = lean fma form, 3 = select form on the reference's true quotients (corner - o) / d
-// SCALAR: try the wave-uniform scalar-load path first
-// RUN: ... and stay on the scalar side while the lanes decide alike (uniform_run; the octant loops of the fused frame kernel)
-template <bool EXACT, bool STATS, int SLAB, bool SCALAR = false, int OCT = 8, bool RUN = false>
+// one inner node (W::slab, W::scalar, W::oct, W::run: the slab forms and Walk at the top of this file)
+template <typename W>
 __device__ __forceinline__ void node_step(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, int tid, Stats &st) {
     float mn0, mx0, mn1, mx1;
-    constexpr bool kSafe = SLAB == 1 || SLAB == 2 || SLAB == 4 || SLAB == 5 || SLAB == 6;
-    constexpr bool kGuarded = SLAB == 5 || SLAB == 6;
-    if (SCALAR) {
+    constexpr bool kStats = W::stats, kSafe = slab_nan_free(W::slab), kGuarded = slab_guarded(W::slab);
+    if (W::scalar) {
         const int cur0 = __builtin_amdgcn_readfirstlane(L.cur);
         if (__all(L.cur == cur0)) {
-            if (RUN && SLAB == 6 && OCT < 8 && !STATS) {
-                uniform_run<EXACT, OCT>(p, r, L, s_stack, st, cur0);
+            if (W::run && slab_needs_tmin0(W::slab) && is_octant(W::oct) && !kStats) {
+                uniform_run<W>(p, r, L, s_stack, st, cur0);
                 return;
             }
             MR_RUN_COUNT(st.node_steps);
             const v16f v = load_node_scalar(p.nodes, cur0);
             const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
             const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
-            if ((SLAB == 4 || kGuarded) && __float_as_int(v[14]) != 0) {   // irregular node (wave-uniform): the reference's own divisions
-                node_slabs<EXACT, STATS, 3>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
-                node_decide<STATS, false>(mn0, mx0, mn1, mx1, __float_as_int(v[12]), __float_as_int(v[13]), r, L, s_stack, st);
+            if (slab_divides_irregular(W::slab) && __float_as_int(v[14]) != 0) {   // irregular node (wave-uniform): the reference's own divisions
+                node_slabs<walk_divide<W>>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
+                node_decide<kStats, false>(mn0, mx0, mn1, mx1, __float_as_int(v[12]), __float_as_int(v[13]), r, L, s_stack, st);
                 return;
             }
             float k0 = 0.0f, k1 = 0.0f;
-            node_slabs_guarded<EXACT, STATS, SLAB, OCT>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
-            node_decide<STATS, kSafe, kGuarded>(mn0, mx0, mn1, mx1, __float_as_int(v[12]), __float_as_int(v[13]), r, L, s_stack, st, k0, k1);
+            node_slabs_guarded<W>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
+            node_decide<kStats, kSafe, kGuarded>(mn0, mx0, mn1, mx1, __float_as_int(v[12]), __float_as_int(v[13]), r, L, s_stack, st, k0, k1);
             return;
         }
     }
@@ -525,44 +565,45 @@ __device__ __forceinline__ void node_step(const TraceParams &p, const RayRegs &r
     const float4 *nd = p.nodes + 4 * (size_t)L.cur;
     const float4 q0 = nd[0], q1 = nd[1], q2 = nd[2];
     const int4 q3 = *reinterpret_cast<const int4 *>(nd + 3);
-    if ((SLAB == 4 || kGuarded) && q3.z != 0) {
-        node_slabs<EXACT, STATS, 3>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
-        node_decide<STATS, false>(mn0, mx0, mn1, mx1, q3.x, q3.y, r, L, s_stack, st);
+    if (slab_divides_irregular(W::slab) && q3.z != 0) {
+        node_slabs<walk_divide<W>>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
+        node_decide<kStats, false>(mn0, mx0, mn1, mx1, q3.x, q3.y, r, L, s_stack, st);
         return;
     }
     float k0 = 0.0f, k1 = 0.0f;
-    node_slabs_guarded<EXACT, STATS, SLAB, OCT>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
-    node_decide<STATS, kSafe, kGuarded>(mn0, mx0, mn1, mx1, q3.x, q3.y, r, L, s_stack, st, k0, k1);
+    node_slabs_guarded<W>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
+    node_decide<kStats, kSafe, kGuarded>(mn0, mx0, mn1, mx1, q3.x, q3.y, r, L, s_stack, st, k0, k1);
 }
 
-template <bool EXACT, bool STATS, int SLAB, int OCT>
+template <typename W>
 __device__ __forceinline__ void node_slabs(const float4 q0, const float4 q1, const float4 q2, const RayRegs &r,
                                            float &mn0, float &mx0, float &mn1, float &mx1) {
-    if (OCT < 8 && (SLAB == 1 || SLAB == 2 || SLAB == 4)) {
-        slab_box_oct<OCT, SLAB>(q0.x, q0.y, q0.z, q0.w, q2.x, q2.y, r, mn0, mx0);
-        slab_box_oct<OCT, SLAB>(q1.x, q1.y, q1.z, q1.w, q2.z, q2.w, r, mn1, mx1);
-    } else if (SLAB == 2) {
+    constexpr bool kQuot = W::slab == kSlabQuotient;
+    if (is_octant(W::oct) && slab_has_octant_body(W::slab)) {
+        slab_box_oct<W::oct, W::slab>(q0.x, q0.y, q0.z, q0.w, q2.x, q2.y, r, mn0, mx0);
+        slab_box_oct<W::oct, W::slab>(q1.x, q1.y, q1.z, q1.w, q2.z, q2.w, r, mn1, mx1);
+    } else if (W::slab == kSlabLean) {
         slab_box_lean(q0.x, q0.y, q0.z, q0.w, q2.x, q2.y, r, mn0, mx0);
         slab_box_lean(q1.x, q1.y, q1.z, q1.w, q2.z, q2.w, r, mn1, mx1);
-    } else if (SLAB == 4) {
+    } else if (W::slab == kSlabCorrection) {
         slab_box_exactq(q0.x, q0.y, q0.z, q0.w, q2.x, q2.y, r, mn0, mx0);
         slab_box_exactq(q1.x, q1.y, q1.z, q1.w, q2.z, q2.w, r, mn1, mx1);
-    } else if (EXACT && (SLAB == 0 || SLAB == 3)) {
+    } else if (W::exact && !slab_nan_free(W::slab)) {          // kSlabSelect, kSlabQuotient
         mn0 = -kInf; mx0 = kInf; mn1 = -kInf; mx1 = kInf;
-        slab_axis<SLAB == 3>(q0.x, q0.y, r.ox, r.dx, r.ix, mn0, mx0);
-        slab_axis<SLAB == 3>(q0.z, q0.w, r.oy, r.dy, r.iy, mn0, mx0);
-        slab_axis<SLAB == 3>(q2.x, q2.y, r.oz, r.dz, r.iz, mn0, mx0);
-        slab_axis<SLAB == 3>(q1.x, q1.y, r.ox, r.dx, r.ix, mn1, mx1);
-        slab_axis<SLAB == 3>(q1.z, q1.w, r.oy, r.dy, r.iy, mn1, mx1);
-        slab_axis<SLAB == 3>(q2.z, q2.w, r.oz, r.dz, r.iz, mn1, mx1);
+        slab_axis<kQuot>(q0.x, q0.y, r.ox, r.dx, r.ix, mn0, mx0);
+        slab_axis<kQuot>(q0.z, q0.w, r.oy, r.dy, r.iy, mn0, mx0);
+        slab_axis<kQuot>(q2.x, q2.y, r.oz, r.dz, r.iz, mn0, mx0);
+        slab_axis<kQuot>(q1.x, q1.y, r.ox, r.dx, r.ix, mn1, mx1);
+        slab_axis<kQuot>(q1.z, q1.w, r.oy, r.dy, r.iy, mn1, mx1);
+        slab_axis<kQuot>(q2.z, q2.w, r.oz, r.dz, r.iz, mn1, mx1);
     } else {
         slab_box_minmax(q0.x, q0.y, q0.z, q0.w, q2.x, q2.y, r, mn0, mx0);
         slab_box_minmax(q1.x, q1.y, q1.z, q1.w, q2.z, q2.w, r, mn1, mx1);
     }
 }
 
-// SLAB 5, "guarded products": the slab distances of a regular ray in a regular node as products (corner - o) * RN(1/d)
-// -- 24 VALU fewer per two-child visit than the correction steps of SLAB 4 -- whenever the decisions taken from them are
+// kSlabGuarded (5), "guarded products": the slab distances of a regular ray in a regular node as products (corner - o) * RN(1/d)
+// -- 24 VALU fewer per two-child visit than the correction steps of kSlabCorrection (4) -- whenever the decisions taken from them are
 // PROVABLY the ones the reference's quotients give, and the quotients themselves otherwise.
 //   * q~ = RN(a * RN(1/d)) = (a/d)(1+e), |e| <= 2^-23 + 2^-48, against q = RN(a/d) = (a/d)(1+e'), |e'| <= 2^-24 (no
 //     under- or overflow: lane_is_regular, regular nodes): q~ and q are less than 4 ulps apart, have the same sign, and
@@ -573,21 +614,21 @@ __device__ __forceinline__ void node_slabs(const float4 q0, const float4 q1, con
 //     distance of two floats of one sign is the difference of their bit patterns (v_sad_u32); patterns of opposite sign
 //     are 2^31 apart, and there the comparison is decided by the signs, which are exact.
 //   * so: if in every lane all five pairs are more than 16 patterns apart (margin of two), the product decisions stand;
-//     if any lane has a closer pair the whole wave recomputes the node with exact quotients (SLAB 4) -- about one visit
+//     if any lane has a closer pair the whole wave recomputes the node with exact quotients (kSlabCorrection) -- about one visit
 //     in a few thousand.
-// Same hits, same visiting order, same bits as SLAB 4 (tests: test_gpu_parity, the fuzz campaigns run both).
-template <bool EXACT, bool STATS, int SLAB, int OCT>
+// Same hits, same visiting order, same bits as kSlabCorrection (tests: test_gpu_parity, the fuzz campaigns run both).
+template <typename W>
 __device__ __forceinline__ void node_slabs_guarded(const float4 q0, const float4 q1, const float4 q2, const RayRegs &r, float best_t,
                                                    float &mn0, float &mx0, float &mn1, float &mx1, float &k0, float &k1) {
-    if (SLAB != 5 && SLAB != 6) {
-        node_slabs<EXACT, STATS, SLAB, OCT>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
+    if (!slab_guarded(W::slab)) {
+        node_slabs<W>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
         return;
     }
-    node_slabs<EXACT, STATS, 1, OCT>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
+    node_slabs<walk_slab<W, kSlabMinMax>>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
     // k = minNum(exit, best_t) of both children and the smallest of the pattern distances, in ONE asm block (separate
     // asm statements are fenced by hazard no-ops: three s_nop per visit when the two v_min stood alone)
     unsigned near, t0, t1;
-    if (SLAB == 6) {
+    if (slab_needs_tmin0(W::slab)) {
         // tMin == 0 in every lane of the wave (camera, shadow and bounce rays: all of them): "exit < tMin" is a SIGN test,
         // and a product and its quotient have the same sign and are zero together -- that comparison needs no guard.
         // Three pairs are left: entry against min(exit, best) for each child, entry against entry.
@@ -603,7 +644,7 @@ __device__ __forceinline__ void node_slabs_guarded(const float4 q0, const float4
             : "v"(mn0), "v"(r.tmin), "v"(mn1), "v"(mx0), "v"(mx1), "v"(best_t));
     }
     if (__any(near <= 16u)) {
-        node_slabs<EXACT, STATS, 4, OCT>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
+        node_slabs<walk_slab<W, kSlabCorrection>>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
         k0 = vmin2(mx0, best_t); k1 = vmin2(mx1, best_t);
     }
 }
@@ -644,8 +685,9 @@ __device__ __forceinline__ void load_tri(const float4 *tr, float4 &q0, float4 &q
     else q2 = tr[2];
 }
 
-template <bool EXACT, bool ANY, bool STATS, bool SCALAR = false, bool OBJ = false, bool REL = false>
+template <typename W>
 __device__ __forceinline__ void leaf_step(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, int tid, Stats &st) {
+    constexpr bool EXACT = W::exact, ANY = W::any, STATS = W::stats, SCALAR = W::scalar, OBJ = W::obj, REL = W::rel;
     // ---- leaf (BVH.cpp:493-509)
     const unsigned bits = ~(unsigned)L.cur;
     const unsigned first = bits >> kLeafCountBits;
@@ -704,8 +746,9 @@ __device__ __forceinline__ void leaf_step(const TraceParams &p, const RayRegs &r
 // One triangle of the lane's current leaf (voting traversal): the leaf is decoded on its first step, popped after its
 // last.  Same tests in the same order with the same running best_t as leaf_step.  When every participating lane is at
 // the start of the same leaf, the whole leaf goes through the scalar cache in this one step (the coherent case).
-template <bool EXACT, bool ANY, bool STATS, bool SCALAR, bool OBJ, bool REL = false>
+template <typename W>
 __device__ __forceinline__ void tri_step(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, Stats &st) {
+    constexpr bool EXACT = W::exact, ANY = W::any, STATS = W::stats, SCALAR = W::scalar, OBJ = W::obj, REL = W::rel;
     bool done = false;
     if (SCALAR) {
         const int cur0 = __builtin_amdgcn_readfirstlane(L.cur);
@@ -765,39 +808,91 @@ __device__ __forceinline__ void tri_step(const TraceParams &p, const RayRegs &r,
     }
 }
 
-// MODE 0: one step of whatever the lane needs per iteration (the reference's control flow, lane by lane)
-// MODE 1: "while-while": lanes run inner nodes until each holds a leaf (or is done), then the wave does the leaves
-// MODE 2: voting: every iteration the wave counts the lanes that need a node step and those that need a triangle test
-//         and runs the step the majority needs; the others wait one round.  In while-while a wave's node loop lasts as
-//         long as its slowest lane's search for a leaf (incoherent batches: 14 of 64 lanes active per VALU
-//         instruction, profiles/r02_before_random); with the vote at least half of the unfinished lanes are active in every step.  The order of
-//         every lane's own steps -- and so its hit record -- is the same in all three modes.
-template <bool EXACT, bool ANY, bool STATS, int SLAB, int MODE, bool SCALAR, bool OBJ = false, int OCT = 8, bool REL = false, bool RUN = false>
+// the walk W in its control flow (kFlowLane / kFlowWhileWhile / kFlowVote)
+template <typename W>
 __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, int tid, Stats &st) {
-    if (MODE == 2) {
+    if (W::flow == kFlowVote) {
+        using Node = walk_run<W, false>;                       // the voting flow takes no uniform run
         L.lpos = 0; L.lend = 0;
         while (true) {
             const bool want_node = L.cur >= 0, want_tri = L.cur < 0 && L.cur != kDone;
             const unsigned long long m_node = __ballot(want_node), m_tri = __ballot(want_tri);
             if ((m_node | m_tri) == 0ull) break;
             if (__popcll(m_node) >= __popcll(m_tri)) {
-                if (want_node) node_step<EXACT, STATS, SLAB, SCALAR, OCT>(p, r, L, s_stack, tid, st);
+                if (want_node) node_step<Node>(p, r, L, s_stack, tid, st);
             } else {
-                if (want_tri) tri_step<EXACT, ANY, STATS, SCALAR, OBJ, REL>(p, r, L, s_stack, st);
+                if (want_tri) tri_step<W>(p, r, L, s_stack, st);
             }
         }
-    } else if (MODE == 1) {
+    } else if (W::flow == kFlowWhileWhile) {
         while (__any(L.have())) {
-            while (L.cur >= 0) node_step<EXACT, STATS, SLAB, SCALAR, OCT, RUN>(p, r, L, s_stack, tid, st);
-            if (L.have()) leaf_step<EXACT, ANY, STATS, SCALAR, OBJ, REL>(p, r, L, s_stack, tid, st);
+            while (L.cur >= 0) node_step<W>(p, r, L, s_stack, tid, st);
+            if (L.have()) leaf_step<W>(p, r, L, s_stack, tid, st);
         }
     } else {
+        // the per-lane flow has neither octant bodies nor the uniform run, and loads its leaves per lane
+        using Node = walk_run<walk_oct<W, kNoOct>, false>;
+        using Leaf = walk_scalar<W, false>;
         while (L.have()) {
-            if (L.cur >= 0) node_step<EXACT, STATS, SLAB, SCALAR>(p, r, L, s_stack, tid, st);
-            else leaf_step<EXACT, ANY, STATS, false, OBJ, REL>(p, r, L, s_stack, tid, st);
+            if (L.cur >= 0) node_step<Node>(p, r, L, s_stack, tid, st);
+            else leaf_step<Leaf>(p, r, L, s_stack, tid, st);
         }
     }
 }
+
+// What trace_ray does with a variant (the kVar... bits of mr_launch.h): the slab form and control flow of each of its four paths,
+// kNoPath where the variant has none.
+//   oct       a good wave whose live rays share an octant (kVarOctant)
+//   good      a good wave without one: NaN-free rays for the product variants (kVarMinMax), regular rays for the quotients (kVarStrict)
+//   fallback  any other wave of such a variant: the reference's own arithmetic
+//   plain     variants that do not sort their waves: counting runs (STATS) and those with neither bit
+struct PathPlan { int slab, flow; };
+struct TracePlan {
+    PathPlan oct, good, fallback, plain;
+    bool strict, scalar, obj;      // the root test, the fallback and the plain path divide; kVarScalar; kVarObjects
+};
+constexpr PathPlan kNoPath = {-1, -1};
+constexpr bool operator==(PathPlan a, PathPlan b) { return a.slab == b.slab && a.flow == b.flow; }
+constexpr bool operator==(TracePlan a, TracePlan b) {
+    return a.oct == b.oct && a.good == b.good && a.fallback == b.fallback && a.plain == b.plain && a.strict == b.strict && a.scalar == b.scalar && a.obj == b.obj;
+}
+constexpr bool has_path(PathPlan a) { return !(a == kNoPath); }
+constexpr TracePlan trace_plan(int var, bool stats) {
+    const bool strict = stats || (var & kVarStrict), minmax = !strict && (var & kVarMinMax), sorts = minmax || (strict && !stats);
+    const int flow = (var & kVarVote) ? kFlowVote : ((var & kVarWhileWhile) ? kFlowWhileWhile : kFlowLane);
+    const int safe = (var & kVarLeanFma) ? kSlabLean : kSlabMinMax;            // for waves whose rays cannot produce a NaN
+    const int exact = (var & kVarGuarded) ? kSlabGuarded : kSlabCorrection;    // guarded products instead of the correction steps
+    const int good = minmax ? safe : exact;
+    TracePlan P = {kNoPath, kNoPath, kNoPath, kNoPath, strict, (var & kVarScalar) != 0, (var & kVarObjects) != 0};
+    if (!sorts) { P.plain = {strict ? kSlabQuotient : kSlabSelect, flow}; return P; }
+    // the octant loops' guard assumes tMin == 0 (node_slabs_guarded)
+    if (var & kVarOctant) P.oct = {good == kSlabGuarded ? kSlabGuardedT0 : good, flow};
+    // A wave of regular rays that point into several octants is an incoherent one: bound by its record fetches, it gains nothing
+    // from the guarded products and would pay for their wave-wide branch -- the correction steps alone there.
+    // kVarMixedVote: ... and the voting control flow suits it better (random rays 3.86 -> 4.09 Grays/s, the atrium's bounce
+    // rays 4.96 -> 5.31, 1-spp shadow rays in image order 3.73 -> 4.31 without the caller's MR_TRACE_INCOHERENT hint)
+    if (minmax) P.good = {safe, flow};
+    else P.good = {kSlabCorrection, ((var & kVarMixedVote) && flow == kFlowWhileWhile) ? kFlowVote : flow};
+    P.fallback = {minmax ? kSlabSelect : kSlabQuotient, flow};
+    return P;
+}
+// every variant mr_launch.h names, as launched (STATS: MR_COUNT_STATS)                  oct                                 good                                fallback                          plain                      strict scalar obj
+static_assert(trace_plan(kTraceExact, false) ==           TracePlan{{kSlabGuardedT0, kFlowWhileWhile},  {kSlabCorrection, kFlowVote},       {kSlabQuotient, kFlowWhileWhile}, kNoPath,                     true,  true,  false});
+static_assert(trace_plan(kTraceEyeRel, false) ==          TracePlan{{kSlabGuardedT0, kFlowWhileWhile},  {kSlabCorrection, kFlowWhileWhile}, {kSlabQuotient, kFlowWhileWhile}, kNoPath,                     true,  true,  false});
+static_assert(trace_plan(kTraceExactObj, false) ==        TracePlan{{kSlabGuardedT0, kFlowWhileWhile},  {kSlabCorrection, kFlowWhileWhile}, {kSlabQuotient, kFlowWhileWhile}, kNoPath,                     true,  true,  true});
+static_assert(trace_plan(kTraceCorrection, false) ==      TracePlan{{kSlabCorrection, kFlowWhileWhile}, {kSlabCorrection, kFlowWhileWhile}, {kSlabQuotient, kFlowWhileWhile}, kNoPath,                     true,  true,  false});
+static_assert(trace_plan(kTraceProduct, false) ==         TracePlan{{kSlabMinMax, kFlowWhileWhile},     {kSlabMinMax, kFlowWhileWhile},     {kSlabSelect, kFlowWhileWhile},   kNoPath,                     false, true,  false});
+static_assert(trace_plan(kTraceProductObj, false) ==      TracePlan{kNoPath,                            {kSlabMinMax, kFlowWhileWhile},     {kSlabSelect, kFlowWhileWhile},   kNoPath,                     false, true,  true});
+static_assert(trace_plan(kTraceDevProduct, false) ==      TracePlan{kNoPath,                            {kSlabMinMax, kFlowWhileWhile},     {kSlabSelect, kFlowWhileWhile},   kNoPath,                     false, true,  false});
+static_assert(trace_plan(kTraceFast, false) ==            TracePlan{kNoPath,                            {kSlabLean, kFlowWhileWhile},       {kSlabSelect, kFlowWhileWhile},   kNoPath,                     false, true,  false});
+static_assert(trace_plan(kTraceVote, false) ==            TracePlan{kNoPath,                            {kSlabCorrection, kFlowVote},       {kSlabQuotient, kFlowVote},       kNoPath,                     true,  true,  false});
+static_assert(trace_plan(kTraceVoteObj, false) ==         TracePlan{kNoPath,                            {kSlabCorrection, kFlowVote},       {kSlabQuotient, kFlowVote},       kNoPath,                     true,  true,  true});
+static_assert(trace_plan(kTraceVoteProduct, false) ==     TracePlan{kNoPath,                            {kSlabMinMax, kFlowVote},           {kSlabSelect, kFlowVote},         kNoPath,                     false, true,  false});
+static_assert(trace_plan(kTraceVoteProductObj, false) ==  TracePlan{kNoPath,                            {kSlabMinMax, kFlowVote},           {kSlabSelect, kFlowVote},         kNoPath,                     false, true,  true});
+static_assert(trace_plan(kTracePlain, false) ==           TracePlan{kNoPath,                            kNoPath,                            kNoPath,                          {kSlabSelect, kFlowLane},    false, false, false});
+static_assert(trace_plan(kTracePlainObj, false) ==        TracePlan{kNoPath,                            kNoPath,                            kNoPath,                          {kSlabSelect, kFlowLane},    false, false, true});
+static_assert(trace_plan(kTracePlain, true) ==            TracePlan{kNoPath,                            kNoPath,                            kNoPath,                          {kSlabQuotient, kFlowLane},  true,  false, false});
+static_assert(trace_plan(kTracePlainObj, true) ==         TracePlan{kNoPath,                            kNoPath,                            kNoPath,                          {kSlabQuotient, kFlowLane},  true,  false, true});
 
 // ---------------------------------------------------------------------------------------------------
 // One ray per lane from the root test to the unbounded-object scan: Scene::trace (Scene.cpp:214-230) ->
@@ -808,7 +903,7 @@ __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r,
 //     eye, triangle records of tri_test_rel -- and every ray starts at the eye: the origin is taken as the constant 0, so the
 //     slab distances (corner - o) / d become (corner - eye) / d on the stored differences with no subtraction left, the
 //     same operands and the same bits as on the scene's own tables.  The eye's own regularity (lane_is_regular sees 0 here)
-//     travels in the node flags: an irregular eye marks every node irregular, so every visit divides (SLAB 3) as the
+//     travels in the node flags: an irregular eye marks every node irregular, so every visit divides (kSlabQuotient) as the
 //     scene's tables would have had it do.  Default traversal of triangle-only scenes only.
 // ---------------------------------------------------------------------------------------------------
 template <bool EXACT, bool ANY, bool STATS, int VAR, bool REL = false, bool RUN = false>
@@ -817,13 +912,12 @@ __device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r
     static_assert(!REL || ((VAR & kVarStrict) && !(VAR & kVarObjects) && !STATS), "eye-relative tables: default traversal, triangles only");
     RayRegs r = r_in;
     if (REL) { r.ox = 0.0f; r.oy = 0.0f; r.oz = 0.0f; }
-    constexpr bool kStrict = STATS || (VAR & kVarStrict);
-    constexpr int kBaseSlab = kStrict ? 3 : 0;
-    constexpr bool kMinMax = !kStrict && (VAR & kVarMinMax);
-    constexpr int kWW = (VAR & kVarVote) ? 2 : ((VAR & kVarWhileWhile) ? 1 : 0);   // control flow of traverse()
-    constexpr int kSafeSlab = (VAR & kVarLeanFma) ? 2 : 1;      // slab form for waves whose rays cannot produce a NaN
-    constexpr bool kScalar = (VAR & kVarScalar) != 0;          // wave-uniform nodes through the scalar cache
-    constexpr bool kObj = (VAR & kVarObjects) != 0;            // the scene holds spheres and / or planes
+    constexpr TracePlan P = trace_plan(VAR, STATS);
+    // what the walks of all four paths share; each path adds its slab form and control flow
+    using Base = Walk<EXACT, ANY, STATS, kSlabSelect, kFlowLane, P.scalar, P.obj, kNoOct, REL, false>;
+    // the fallback and the plain path take the scalar loads only where they divide: on kSlabSelect (the NaN-unsafe wave of a
+    // kVarMinMax variant, the plain path without kVarStrict) every node and leaf is loaded per lane
+    using Other = walk_scalar<Base, P.scalar && P.strict>;
 
     L.best_t = tmax0;                             // minHit.t = tMax (BVH.cpp:444)
     L.best_b = 0.0f; L.best_g = 0.0f;
@@ -831,66 +925,52 @@ __device__ __forceinline__ void trace_ray(const TraceParams &p, const RayRegs &r
     stack_reset(L, s_stack, tid);                 // this lane's LDS stack: the kDone sentinel only
     {   // BVH::intersect root test (BVH.cpp:447-466)
         float mn = -kInf, mx = kInf;
-        slab_axis<kStrict>(p.root_lo[0], p.root_hi[0], r.ox, r.dx, r.ix, mn, mx);
-        slab_axis<kStrict>(p.root_lo[1], p.root_hi[1], r.oy, r.dy, r.iy, mn, mx);
-        slab_axis<kStrict>(p.root_lo[2], p.root_hi[2], r.oz, r.dz, r.iz, mn, mx);
+        slab_axis<P.strict>(p.root_lo[0], p.root_hi[0], r.ox, r.dx, r.ix, mn, mx);
+        slab_axis<P.strict>(p.root_lo[1], p.root_hi[1], r.oy, r.dy, r.iy, mn, mx);
+        slab_axis<P.strict>(p.root_lo[2], p.root_hi[2], r.oz, r.dz, r.iz, mn, mx);
         if (STATS && live) st.box++;
         L.cur = (live && !((mn > mx) || (mn > tmax0) || (mx < r.tmin))) ? p.root_ref : kDone;
     }
 
+    // a good wave: NaN-free rays for the product forms (a slab product (corner - o) * (1/d) can only be NaN as 0*inf or inf*0 or from a
+    // non-finite origin: with o, d and 1/d all finite in every lane the select form and the min/max form decide identically), regular
+    // rays for the default trace (the quotients' decisions from guarded products or from the correction steps -- then the lanes'
+    // quotients are NaN-free too and the min/max form decides like the select form)
+    const bool good_wave = !has_path(P.good) ? false : (P.strict ? __all(lane_is_regular(r) || !live) : __all(lane_is_nan_free(r) || !live));
     // kVarOctant: when the wave's live rays all point into one octant the slab tests take their near / far corners by
     // position (slab_box_oct): eight copies of the loop, chosen once per ray batch of the wave
-    constexpr bool kOct = (VAR & kVarOctant) != 0;
-    constexpr int kExactSlab = (VAR & kVarGuarded) ? 5 : 4;   // guarded products (node_slabs_guarded) instead of the correction steps
-    constexpr int kGoodSlab = kMinMax ? kSafeSlab : kExactSlab;
-    constexpr int kOctSlab = kGoodSlab == 5 ? 6 : kGoodSlab;     // the octant loops' guard assumes tMin == 0 (node_slabs_guarded)
-    const bool good_wave = kMinMax ? __all(lane_is_nan_free(r) || !live) : ((kStrict && !STATS) ? __all(lane_is_regular(r) || !live) : false);
     bool done_oct = false;
-    if (kOct && (kMinMax || (kStrict && !STATS)) && good_wave) {
-        const unsigned long long m_live = __ballot(live);
-        if (m_live) {
-            const int oct = octant_of(r);
-            const int oct0 = __builtin_amdgcn_readlane(oct, __ffsll((long long)m_live) - 1);
-            if (__all(!live || oct == oct0) && (kOctSlab != 6 || __all(!live || r.tmin == 0.0f))) {
-                done_oct = true;
-                switch (oct0) {
-                    case 0: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 0, REL, RUN>(p, r, L, s_stack, tid, st); break;
-                    case 1: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 1, REL, RUN>(p, r, L, s_stack, tid, st); break;
-                    case 2: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 2, REL, RUN>(p, r, L, s_stack, tid, st); break;
-                    case 3: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 3, REL, RUN>(p, r, L, s_stack, tid, st); break;
-                    case 4: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 4, REL, RUN>(p, r, L, s_stack, tid, st); break;
-                    case 5: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 5, REL, RUN>(p, r, L, s_stack, tid, st); break;
-                    case 6: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 6, REL, RUN>(p, r, L, s_stack, tid, st); break;
-                    default: traverse<EXACT, ANY, STATS, kOctSlab, kWW, kScalar, kObj, 7, REL, RUN>(p, r, L, s_stack, tid, st); break;
+    if constexpr (has_path(P.oct)) {
+        if (good_wave) {
+            const unsigned long long m_live = __ballot(live);
+            if (m_live) {
+                const int oct = octant_of(r);
+                const int oct0 = __builtin_amdgcn_readlane(oct, __ffsll((long long)m_live) - 1);
+                if (__all(!live || oct == oct0) && (!slab_needs_tmin0(P.oct.slab) || __all(!live || r.tmin == 0.0f))) {
+                    done_oct = true;
+                    using Oct = walk_run<walk_slab<Base, P.oct.slab, P.oct.flow>, RUN>;
+#define MR_OCT_CASE(LABEL, O) LABEL: traverse<walk_oct<Oct, O>>(p, r, L, s_stack, tid, st); break;
+                    switch (oct0) {
+                        MR_OCT_CASE(case 0, 0) MR_OCT_CASE(case 1, 1) MR_OCT_CASE(case 2, 2) MR_OCT_CASE(case 3, 3)
+                        MR_OCT_CASE(case 4, 4) MR_OCT_CASE(case 5, 5) MR_OCT_CASE(case 6, 6) MR_OCT_CASE(default, 7)
+                    }
+#undef MR_OCT_CASE
                 }
             }
         }
     }
     if (done_oct) {
-    } else if (kMinMax) {
-        // a slab product (corner - o) * (1/d) can only be NaN as 0*inf or inf*0 or from a non-finite origin:
-        // with o, d and 1/d all finite in every lane the select form and the min/max form decide identically
-        if (good_wave) traverse<EXACT, ANY, STATS, kSafeSlab, kWW, kScalar, kObj>(p, r, L, s_stack, tid, st);
-        else traverse<EXACT, ANY, STATS, 0, kWW, false, kObj>(p, r, L, s_stack, tid, st);
-    } else if (kStrict && !STATS) {
-        // the default trace: where every lane's ray is regular, the quotients' decisions from guarded products (kVarGuarded)
-        // or from the correction steps (then the lanes' quotients are NaN-free too and the min/max form decides like the
-        // select form); the reference's own divisions otherwise
-        // (a wave whose rays point into several octants is an incoherent one: bound by its record fetches, it gains nothing
-        // from the guarded products and would pay for their wave-wide branch -- the correction steps alone here)
-        // kVarMixedVote: ... and the voting control flow suits it better (random rays 3.86 -> 4.09 Grays/s, the atrium's bounce
-        // rays 4.96 -> 5.31, 1-spp shadow rays in image order 3.73 -> 4.31 without the caller's MR_TRACE_INCOHERENT hint)
-        constexpr int kMixedFlow = ((VAR & kVarMixedVote) && kWW == 1) ? 2 : kWW;
-        if (good_wave) traverse<EXACT, ANY, STATS, 4, kMixedFlow, kScalar, kObj, 8, REL>(p, r, L, s_stack, tid, st);
-        else traverse<EXACT, ANY, STATS, 3, kWW, kScalar, kObj, 8, REL>(p, r, L, s_stack, tid, st);
+    } else if constexpr (has_path(P.good)) {
+        if (good_wave) traverse<walk_slab<Base, P.good.slab, P.good.flow>>(p, r, L, s_stack, tid, st);
+        else traverse<walk_slab<Other, P.fallback.slab, P.fallback.flow>>(p, r, L, s_stack, tid, st);
     } else {
-        traverse<EXACT, ANY, STATS, kBaseSlab, kWW, kStrict && kScalar, kObj>(p, r, L, s_stack, tid, st);
+        traverse<walk_slab<Other, P.plain.slab, P.plain.flow>>(p, r, L, s_stack, tid, st);
     }
 
     // Scene::trace's scan of the unbounded objects (Scene.cpp:220-230): every plane is tested against the
     // caller's tMin / tMax (Plane.cpp:33-48) and kept when nothing was hit yet or it is strictly nearer
     plane_hit = -1;
-    if (kObj && live && !(ANY && L.best_pos >= 0)) {
+    if (P.obj && live && !(ANY && L.best_pos >= 0)) {
         for (uint32_t k = 0; k < p.n_planes; k++) {
             const float4 pn = p.planes[2 * k], po = p.planes[2 * k + 1];
             const float ndotd = (pn.x * r.dx + pn.y * r.dy) + pn.z * r.dz;
