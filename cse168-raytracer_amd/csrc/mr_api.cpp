@@ -422,6 +422,13 @@ mr_status check_light(const char *who, uint32_t i, const uint32_t reserved[4], c
     return MR_OK;
 }
 
+// what the entry points that compute a hit's colour or normal themselves answer on a scene with a STONE or STEM texture
+mr_status refuse_procedural(const mr_scene *s, const char *who, const char *instead) {
+    if (!s->tex.procedural) return MR_OK;
+    return fail(MR_ERR_STATE, "%s: the scene's texture table holds a STONE or STEM texture, whose colour and bump-mapped normal come from "
+                              "the surface pass: call mr_hit_surface, then %s", who, instead);
+}
+
 // LoadedTexture::LoadedTexture (Texture.cpp:30-92) for a FIT_RGBF image of W x H pixels: m_maxIntensity and the low-res image,
 // written behind the image's own records in e.rec
 void build_environment_image(HostEnvironment &e, const float *px) {
@@ -939,6 +946,17 @@ mr_status mr_scene_set_materials(mr_scene *s, const mr_material *mats, uint32_t 
     return MR_OK;
 }
 
+// the scene's per-ray light-scale buffer, grown to n floats
+static mr_status reserve_light_scale(mr_scene *s, uint64_t n) {
+    if (n <= s->light_scale_cap) return MR_OK;
+    (void)hipFree(s->d_light_scale);
+    s->d_light_scale = nullptr;
+    s->light_scale_cap = 0;
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&s->d_light_scale), n * sizeof(float)));
+    s->light_scale_cap = n;
+    return MR_OK;
+}
+
 mr_status mr_shade_accumulate(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
                               const uint32_t *d_pixels, uint64_t n, const mr_ray *d_shadow_rays, const mr_hit *d_shadow_hits,
                               const uint32_t *d_shadow_src, const uint64_t *d_shadow_count, const mr_light *light, uint32_t spp,
@@ -948,14 +966,9 @@ mr_status mr_shade_accumulate(mr_scene *s, const mr_ray *d_rays, const mr_hit *d
     if (!d_rays || !d_hits || !d_shadow_rays || !d_shadow_hits || !d_shadow_src || !d_shadow_count || !light || !d_rgb)
         return fail(MR_ERR_INVALID, "NULL argument");
     if (spp == 0) return fail(MR_ERR_INVALID, "spp is 0");
+    if ((st = refuse_procedural(s, "mr_shade_accumulate", "mr_shade_accumulate_surface")) != MR_OK) return st;
     MR_HIP_CHECK(hipSetDevice(s->device));
-    if (n > s->light_scale_cap) {
-        (void)hipFree(s->d_light_scale);
-        s->d_light_scale = nullptr;
-        s->light_scale_cap = 0;
-        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&s->d_light_scale), n * sizeof(float)));
-        s->light_scale_cap = n;
-    }
+    if ((st = reserve_light_scale(s, n)) != MR_OK) return st;
     TexParams tex;
     const bool textured = !s->tex.blob.empty();
     if (textured && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
@@ -989,6 +1002,10 @@ mr_status mr_gen_path_rays(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hi
     if (n / spp > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "too many rays for 32-bit ray ids");
     if (kinds == 0 || (kinds & ~7u)) return fail(MR_ERR_INVALID, "kinds must be a combination of MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE");
     if (out_capacity == 0 && n > 0) return fail(MR_ERR_INVALID, "mr_gen_path_rays: out_capacity is 0 (room for 4n rays always suffices)");
+    if ((kinds & 4u) && s->tex.procedural)        // MR_PATH_DIFFUSE: Ray::random bounces about N, which no generator bumps
+        return fail(MR_ERR_STATE, "mr_gen_path_rays: MR_PATH_DIFFUSE on a scene whose texture table holds a STONE or STEM texture (Ray::random "
+                                  "bounces about the un-bumped N here; mr_hit_surface and the _surface calls shade such a scene, no generator "
+                                  "reads their normal)");
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_path_rays(s->dev, d_rays, d_hits, d_weights, d_pixels, d_ids, n, spp, seed, bounce, kinds, d_out_rays,
                             d_out_weights, d_out_pixels, d_out_ids, reinterpret_cast<unsigned long long *>(d_count), out_capacity,
@@ -1066,6 +1083,7 @@ mr_status mr_shade_lights(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hit
     if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
         (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3))
         return fail(MR_ERR_INVALID, "ray / hit buffers must be 16-byte aligned, counters 8-byte aligned");
+    if ((st = refuse_procedural(s, "mr_shade_lights", "mr_shade_lights_surface")) != MR_OK) return st;
     MR_HIP_CHECK(hipSetDevice(s->device));
     if (!s->tex.blob.empty()) {
         TexParams tex;
@@ -1133,6 +1151,7 @@ mr_status mr_shade_square_lights(mr_scene *s, const mr_square_light_desc *lights
         (reinterpret_cast<uintptr_t>(d_uv_in) & 7) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3))
         return fail(MR_ERR_INVALID, "%s: ray / hit buffers must be 16-byte aligned, counters and d_uv_in 8-byte aligned", who);
     if ((st = require_device(s)) != MR_OK) return st;
+    if ((st = refuse_procedural(s, who, "mr_shade_lights_surface (a point or disc light list; no _surface form shades square lights)")) != MR_OK) return st;
     if ((st = refuse_textured(s, who)) != MR_OK) return st;
     if ((flags & MR_TRACE_ANY) && s->dev.refractive)
         return fail(MR_ERR_STATE, "%s: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)", who);
@@ -1280,13 +1299,16 @@ mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, ui
     size_t texels = 0;
     for (uint32_t i = 0; i < n_textures; i++) {
         const mr_texture_desc &in = textures[i];
-        if (in.kind != MR_TEX_CHECKER && in.kind != MR_TEX_IMAGE) return fail(MR_ERR_INVALID, "texture %u: unknown kind %u", i, in.kind);
+        if (in.kind > MR_TEX_STEM) return fail(MR_ERR_INVALID, "texture %u: unknown kind %u", i, in.kind);
         for (int k = 0; k < 5; k++)
             if (in.reserved[k] != 0) return fail(MR_ERR_INVALID, "texture %u: mr_texture_desc.reserved must be 0", i);
         if (in.kind == MR_TEX_CHECKER) {
             for (int c = 0; c < 3; c++)
                 if (!std::isfinite(in.color1[c]) || !std::isfinite(in.color2[c])) return fail(MR_ERR_INVALID, "texture %u: the checker's colours must be finite", i);
             if (!std::isfinite(in.scale)) return fail(MR_ERR_INVALID, "texture %u: the checker's scale must be finite", i);
+        } else if (in.kind == MR_TEX_STONE || in.kind == MR_TEX_STEM) {
+            if (!std::isfinite(in.scale)) return fail(MR_ERR_INVALID, "texture %u: the %s texture's scale must be finite", i, in.kind == MR_TEX_STONE ? "stone" : "stem");
+            h.procedural = true;
         } else {
             if (in.W == 0 || in.H == 0 || !in.pixels) return fail(MR_ERR_INVALID, "texture %u: an image needs pixels and W, H > 0", i);
             if (in.W > 65536u || in.H > 65536u) return fail(MR_ERR_INVALID, "texture %u: image of %u x %u pixels, at most 65536 each way", i, in.W, in.H);
@@ -1302,6 +1324,17 @@ mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, ui
         for (uint32_t i = 0; i < n_mats; i++)
             if (material_texture[i] != kNoTexture && material_texture[i] >= n_textures)
                 return fail(MR_ERR_INVALID, "material %u names texture %u of %u", i, material_texture[i], n_textures);
+    // a bump-mapped material is diffuse only, as the reference's own are (assignment1.cpp:232,313): the reflect / refract
+    // generators and the light through a refractive occluder (Phong.cpp:99-113) work on the un-bumped N
+    if (material_texture)
+        for (uint32_t i = 0; i < n_mats; i++) {
+            if (material_texture[i] == kNoTexture || textures[material_texture[i]].kind != MR_TEX_STONE) continue;
+            const float *o = &s->materials[11 * (size_t)i];
+            for (int c = 3; c < 9; c++)
+                if (o[c] != 0.0f)
+                    return fail(MR_ERR_INVALID, "material %u names the STONE texture %u and has a non-zero ks or kt: a bump-mapped "
+                                                "material must be diffuse only", i, material_texture[i]);
+        }
 
     h.texel_base = 3 * (size_t)n_textures;
     h.mat_base = h.texel_base + texels;
@@ -1315,6 +1348,11 @@ mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, ui
             q[0] = make_float4(bits(MR_TEX_CHECKER), 0.f, 0.f, 0.f);
             q[1] = make_float4(in.color1[0], in.color1[1], in.color1[2], in.scale);
             q[2] = make_float4(in.color2[0], in.color2[1], in.color2[2], 0.f);
+            continue;
+        }
+        if (in.kind == MR_TEX_STONE || in.kind == MR_TEX_STEM) {                  // the scale where a checker's is
+            q[0] = make_float4(bits(in.kind), 0.f, 0.f, 0.f);
+            q[1] = make_float4(0.f, 0.f, 0.f, in.scale);
             continue;
         }
         float max_intensity = -1e15;                                              // Texture.cpp:34,41-50
@@ -1373,7 +1411,93 @@ mr_status mr_texture_lookup(mr_scene *s, uint32_t texture, const float *d_uv, ui
     MR_HIP_CHECK(hipSetDevice(s->device));
     TexParams tex;
     if ((st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+    uint32_t kind;
+    memcpy(&kind, &s->tex.blob[3 * (size_t)texture].x, sizeof(kind));
+    if (kind == MR_TEX_STONE || kind == MR_TEX_STEM)
+        return launch_texture_lookup_proc(tex, texture, d_uv, n, d_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
     return launch_texture_lookup(tex, texture, d_uv, n, d_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_hit_surface(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, uint64_t n, float *d_color, float *d_normal,
+                         uint64_t *d_counts, void *stream) {
+    mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (!d_hits || !d_color || !d_normal) return fail(MR_ERR_INVALID, "mr_hit_surface: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_color) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_normal) & 3) || (reinterpret_cast<uintptr_t>(d_counts) & 7))
+        return fail(MR_ERR_INVALID, "mr_hit_surface: ray / hit buffers must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned");
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    TexParams tex;
+    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
+    if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+    return launch_hit_surface(s->dev, tex, d_rays, d_hits, n, d_color, d_normal, reinterpret_cast<unsigned long long *>(d_counts),
+                              static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_shade_lights_surface(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color, const float *d_normal,
+                                  const float *d_weights, const uint32_t *d_pixels, uint64_t n, uint32_t spp, uint32_t flags,
+                                  float *d_rgb, float *d_ray_rgb, uint64_t *d_counts, void *stream) {
+    const char *who = "mr_shade_lights_surface";
+    mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (s->lights.empty()) return fail(MR_ERR_STATE, "%s: the scene has no lights (mr_scene_set_lights)", who);
+    if (!d_rays || !d_hits || !d_color || !d_normal || (!d_rgb && !d_ray_rgb)) return fail(MR_ERR_INVALID, "%s: NULL argument", who);
+    if (spp == 0) return fail(MR_ERR_INVALID, "%s: spp is 0", who);
+    if (n / spp > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: too many pixels", who);
+    if (flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT | MR_TRACE_ANY))
+        return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_TRACE_ANY only", who);
+    if ((flags & MR_TRACE_ANY) && s->dev.refractive)
+        return fail(MR_ERR_STATE, "%s: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)", who);
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_color) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_normal) & 3))
+        return fail(MR_ERR_INVALID, "%s: ray / hit buffers must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned", who);
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    return launch_shade_lights_surf(s->dev, s->lights.data(), (uint32_t)s->lights.size(), d_rays, d_hits, d_color, d_normal, d_weights, d_pixels,
+                                    n, spp, flags, d_rgb, d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts),
+                                    static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_shade_accumulate_surface(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color, const float *d_normal,
+                                      const float *d_weights, const uint32_t *d_pixels, uint64_t n, const mr_ray *d_shadow_rays,
+                                      const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src, const uint64_t *d_shadow_count,
+                                      const mr_light *light, uint32_t spp, float *d_rgb, void *stream) {
+    mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (!d_rays || !d_hits || !d_color || !d_normal || !d_shadow_rays || !d_shadow_hits || !d_shadow_src || !d_shadow_count || !light || !d_rgb)
+        return fail(MR_ERR_INVALID, "mr_shade_accumulate_surface: NULL argument");
+    if (spp == 0) return fail(MR_ERR_INVALID, "mr_shade_accumulate_surface: spp is 0");
+    if ((reinterpret_cast<uintptr_t>(d_color) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3))
+        return fail(MR_ERR_INVALID, "mr_shade_accumulate_surface: float buffers must be 4-byte aligned");
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    if ((st = reserve_light_scale(s, n)) != MR_OK) return st;
+    const hipStream_t q = static_cast<hipStream_t>(stream);
+    if ((st = launch_light_scale(s->dev, d_shadow_rays, d_shadow_hits, d_shadow_src, reinterpret_cast<const unsigned long long *>(d_shadow_count),
+                                 n, s->d_light_scale, q)) != MR_OK)
+        return st;
+    return launch_shade_accumulate_surf(s->dev, d_rays, d_hits, d_color, d_normal, d_weights, d_pixels, n, s->d_light_scale, *light, spp, d_rgb, q);
+}
+
+mr_status mr_texture_bump_height(mr_scene *s, uint32_t texture, const float *d_uv, uint64_t n, float *d_height, void *stream) {
+    mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (s->tex.blob.empty()) return fail(MR_ERR_STATE, "mr_texture_bump_height: the scene has no textures (mr_scene_set_textures)");
+    if (texture >= s->tex.n_textures) return fail(MR_ERR_INVALID, "mr_texture_bump_height: texture %u of %u", texture, s->tex.n_textures);
+    if (!d_uv || !d_height) return fail(MR_ERR_INVALID, "mr_texture_bump_height: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_uv) & 3) || (reinterpret_cast<uintptr_t>(d_height) & 3))
+        return fail(MR_ERR_INVALID, "mr_texture_bump_height: float buffers must be 4-byte aligned");
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    uint32_t kind;
+    memcpy(&kind, &s->tex.blob[3 * (size_t)texture].x, sizeof(kind));
+    return launch_bump_height(kind == MR_TEX_STONE, s->tex.blob[3 * (size_t)texture + 1].w, d_uv, n, d_height, static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_noise_probe(uint32_t which, const float *d_in, uint64_t n, float *d_out, void *stream) {
+    if (which != MR_NOISE_PERLIN && which != MR_NOISE_WORLEY2) return fail(MR_ERR_INVALID, "mr_noise_probe: which must be MR_NOISE_PERLIN or MR_NOISE_WORLEY2");
+    if (!d_in || !d_out) return fail(MR_ERR_INVALID, "mr_noise_probe: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
+        return fail(MR_ERR_INVALID, "mr_noise_probe: buffers must be 4-byte aligned");
+    return launch_noise_probe(which, d_in, n, d_out, static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_tonemap(mr_scene *s, const float *d_rgb, uint64_t n_values, uint8_t *d_out, void *stream) {

@@ -197,6 +197,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATH ? M
 
 }  // namespace
 
+mr_status launch_light_scale(const DeviceScene &ds, const mr_ray *d_shadow_rays, const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src,
+                             const unsigned long long *d_shadow_count, unsigned long long n, float *d_light_scale, hipStream_t stream) {
+    if (n == 0) return MR_OK;
+    hipLaunchKernelGGL(light_scale_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, mesh_of(ds), d_shadow_rays, d_shadow_hits,
+                       d_shadow_src, d_shadow_count, n, d_light_scale);
+    MR_HIP_CHECK(hipGetLastError());
+    return MR_OK;
+}
+
 mr_status launch_shade_accumulate(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
                                   const uint32_t *d_pixels, unsigned long long n, const mr_ray *d_shadow_rays,
                                   const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src,
@@ -204,9 +213,8 @@ mr_status launch_shade_accumulate(const DeviceScene &ds, const mr_ray *d_rays, c
                                   uint32_t spp, float *d_rgb, const TexParams *tex, hipStream_t stream) {
     if (n == 0) return MR_OK;
     const MeshMat m = mesh_of(ds);
-    hipLaunchKernelGGL(light_scale_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, m, d_shadow_rays, d_shadow_hits,
-                       d_shadow_src, d_shadow_count, n, d_light_scale);
-    MR_HIP_CHECK(hipGetLastError());
+    const mr_status st = launch_light_scale(ds, d_shadow_rays, d_shadow_hits, d_shadow_src, d_shadow_count, n, d_light_scale, stream);
+    if (st != MR_OK) return st;
     if (tex) return launch_shade_accumulate_tex(ds, *tex, d_rays, d_hits, d_weights, d_pixels, n, d_light_scale, light, spp, d_rgb, stream);
     AccumArgs a;
     a.m = m; a.rays = d_rays; a.hits = d_hits; a.weights = d_weights; a.pixels = d_pixels; a.light_scale = d_light_scale;

@@ -277,9 +277,11 @@ struct HostTextures {
     uint32_t n_textures = 0, n_materials = 0;
     size_t texel_base = 0, mat_base = 0;       // offsets into blob, in float4
     std::vector<float4> blob;                  // empty: the scene has no texture table
+    bool procedural = false;                   // some texture is a STONE or a STEM: only the _surface calls shade such a scene
 };
 struct TexParams {                             // the table as the kernels take it
     const float4 *recs;                        // 3 per texture: (kind, W, H, first texel as bits) (color1 | max_intensity, hdr) (color2)
+                                               // STONE / STEM: (kind, 0, 0, 0) (0, 0, 0, scale) (0): scale where a checker's is
     const float4 *texels;
     const uint32_t *mat_tex;                   // per material: texture id or kNoTexture
     const float *texcoords;                    // the scene's texture coordinates (mr_uv.h), nullptr: none
@@ -298,6 +300,26 @@ mr_status launch_hit_uv(const DeviceScene &ds, const mr_ray *d_rays, const mr_hi
                         hipStream_t stream);
 mr_status launch_texture_lookup(const TexParams &tex, uint32_t texture, const float *d_uv, unsigned long long n, float *d_rgb,
                                 unsigned long long *d_counts, hipStream_t stream);
+
+// Procedural textures and bump-mapped normals (mr_procedural.hip): the per-hit surface pass, the light-list and accumulate
+// kernels that read its two buffers, and the inspection kernels.  launch_hit_surface takes a TexParams whose recs / mat_tex
+// are nullptr for a scene without a texture table.
+mr_status launch_hit_surface(const DeviceScene &ds, const TexParams &tex, const mr_ray *d_rays, const mr_hit *d_hits, unsigned long long n,
+                             float *d_color, float *d_normal, unsigned long long *d_counts, hipStream_t stream);
+mr_status launch_shade_lights_surf(const DeviceScene &ds, const ShadeLight *lights, uint32_t n_lights, const mr_ray *d_rays,
+                                   const mr_hit *d_hits, const float *d_color, const float *d_normal, const float *d_weights,
+                                   const uint32_t *d_pixels, unsigned long long n, uint32_t spp, uint32_t flags, float *d_rgb,
+                                   float *d_ray_rgb, unsigned long long *d_counts, hipStream_t stream);
+mr_status launch_shade_accumulate_surf(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color,
+                                       const float *d_normal, const float *d_weights, const uint32_t *d_pixels, unsigned long long n,
+                                       const float *d_light_scale, const mr_light &light, uint32_t spp, float *d_rgb, hipStream_t stream);
+mr_status launch_texture_lookup_proc(const TexParams &tex, uint32_t texture, const float *d_uv, unsigned long long n, float *d_rgb,
+                                     unsigned long long *d_counts, hipStream_t stream);
+mr_status launch_bump_height(bool stone, float scale, const float *d_uv, unsigned long long n, float *d_height, hipStream_t stream);
+mr_status launch_noise_probe(uint32_t which, const float *d_in, unsigned long long n, float *d_out, hipStream_t stream);
+// the first half of launch_shade_accumulate (mr_bounce.hip): Phong.cpp:97-113's light scale per ray from the traced shadow rays
+mr_status launch_light_scale(const DeviceScene &ds, const mr_ray *d_shadow_rays, const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src,
+                             const unsigned long long *d_shadow_count, unsigned long long n, float *d_light_scale, hipStream_t stream);
 
 // The environment of rays that miss (mr_environment.hip; Scene::getEnvironmentMap, Scene.cpp:657-688).  The host copy is what
 // mr_scene_set_environment made of the caller's image (LoadedTexture::LoadedTexture, Texture.cpp:30-92); the device copy holds

@@ -1,0 +1,391 @@
+// mr_procedural.hip -- the reference's procedural textures and the bump mapping of Scene::trace: StemTexture::lookup2D
+// (Texture.h:192-212), StoneTexture::lookup2D and ::bumpHeight2D (Texture.cpp:358-440) over the noise of mr_noise.h, and the
+// normal as Scene.cpp:234-263 leaves it.
+//
+//   procedural_surface_kernel      per hit of a traced batch: diffuseColor (Phong.cpp:51-56) and the bumped, normalised normal,
+//                                  into two per-ray buffers of three floats each (mr_hit_surface)
+//   shade_lights_surf_kernel       shade_lights_kernel (mr_lights.hip) reading that colour and normal instead of computing them
+//   shade_accumulate_surf_kernel   shade_accumulate_kernel (mr_bounce.hip), the same way
+//   texture_lookup_proc_kernel     lookup2D of a STONE / STEM texture for a batch of coordinates (mr_texture_lookup)
+//   bump_height_kernel             bumpHeight2D of one texture for a batch of coordinates (mr_texture_bump_height)
+//   noise_probe_kernel             PerlinNoise::noise / WorleyNoise::noise2D of order 3 themselves (mr_noise_probe)
+//
+// Why a pass of its own: a stone hit costs five three-point Worley searches and up to 5 + 4 * 7 Perlin evaluations.  The
+// textured light-list kernel already spills in its worst variant; the surface pass has no traversal, so it
+// keeps everything in registers, and the shading kernels that follow it are the light-list and accumulate kernels with two
+// loads in place of the normal and the colour.  The two shading bodies are written out here, not added as one more switch to
+// mr_lights_body.h / mr_accumulate_body.h: the existing kernels keep their recorded register figures that way (see the note
+// on by-value arguments in mr_lights_body.h).  They share every piece around the changed lines with those bodies.
+//
+// powf and exp are the double series of miro_math.h rounded once (mm_powf, mm_exp); the reference calls libm's, which a
+// host restatement can call too -- tests/test_procedural.py measures the distance.  pow(f1f0, 2) (Texture.cpp:424) is
+// std::pow(float, int) of the C++03 library the reference was written for, which returns float (only then does the std::min
+// next to it compile): the float product f1f0 * f1f0.
+#include <hip/hip_runtime.h>
+
+#include "mr_accumulate_body.h"
+#include "mr_internal.h"
+#include "mr_launch.h"
+#include "mr_lights_body.h"
+#include "mr_noise.h"
+#include "mr_texture.h"
+#include "mr_uv.h"
+
+namespace mr {
+namespace {
+
+enum : uint32_t { kTexStone = 2u, kTexStem = 3u };                      // MR_TEX_STONE, MR_TEX_STEM
+
+// StemTexture::lookup2D (Texture.h:192-212)
+__device__ __forceinline__ void stem_color(const NoiseTables &nt, float scale, float cu, float cv, float rgb[3], bool &ok) {
+    const float u = cu * scale, v = cv * scale;
+    const Worley3 w = worley2(nt, u, v, ok);
+    const float noise = turbulence(nt, u, v, 10, 1.5f, 0.8f, 10, ok);
+    const float cells = w.F0 - w.F1;
+    rgb[0] = 0.0f;
+    rgb[1] = (float)(0.5 + 0.5 * (double)(noise + 1.0f) / (double)2.0f - 0.3 * (double)cells);                  // :211
+    rgb[2] = 0.0f;
+}
+
+// (1 - pow(f[1] - f[0], 0.8f)) * 1.5 (Texture.cpp:370,409)
+__device__ __forceinline__ float stone_outline(const Worley3 &w) {
+    return (float)((double)(1 - mm_powf(w.F1 - w.F0, 0.8f)) * 1.5);
+}
+
+// StoneTexture::bumpHeight2D (Texture.cpp:358-393).  The two branches differ in the parameters of one generateNoise call.
+__device__ __forceinline__ float stone_height(const NoiseTables &nt, float scale, float cu, float cv, bool &ok) {
+    const float u = cu * scale, v = cv * scale;
+    const float height_factor = (float)0.3;
+    const Worley3 w = worley2(nt, u, v, ok);
+    float f1f0 = stone_outline(w);
+    f1f0 *= -1.f;
+    // exp of an argument beyond +-700 (only a search that found fewer than two points gets there) gives the same float
+    // height as the bound itself: 1 or 0
+    double z = -20.0 * ((double)(w.F1 - w.F0) - 0.3);                                                           // :372
+    z = z < -700.0 ? -700.0 : (z > 700.0 ? 700.0 : z);
+    const float height = (float)(1.0 / (1.0 + mm_exp(z)));
+    const bool inside = (double)f1f0 > -1.1;                                                                    // :373
+    const float turb = turbulence(nt, u, v, inside ? 0.5f : 1.0f, 2, 0.5f, inside ? (int)(w.I0 % 3u) + 5 : 3, ok);   // :376,381
+    const float t = (float)((double)(turb / (inside ? 5.0f : 10.0f)) + 0.5);
+    return (inside ? 0.8f : 1.0f) * t + height_factor * height;                                                 // :377,391
+}
+
+// StoneTexture::lookup2D (Texture.cpp:396-440)
+__device__ __forceinline__ void stone_color(const NoiseTables &nt, float scale, float cu, float cv, float rgb[3], bool &ok) {
+    const float u = cu * scale, v = cv * scale;
+    const Worley3 w = worley2(nt, u, v, ok);
+    const float f1f0 = stone_outline(w);
+    float base = uv_min(uv_max(mm_powf((w.F2 - w.F1 + w.F0), 0.1f) - f1f0, 0.f), 0.5f);                         // :412
+    const float id10 = (float)(w.I0 % 10u), id5 = (float)(w.I0 % 5u);
+    base = (float)((double)base * ((double)(id10 / 20) + 0.5));                                                 // :415
+    const float turb = turbulence(nt, u, v, 3, 2, 0.8f, 5, ok);
+    base = uv_max(0.0f, base);
+    base = (float)((double)base + 0.8 * (double)fabsf(turb));                                                   // :420
+    if ((double)f1f0 > 1.1) {
+        const float edges = uv_min(f1f0 * f1f0 - 1.f, 0.75f);                                                   // :424
+        rgb[0] = rgb[1] = rgb[2] = (float)((double)edges + 0.25 * (double)fabsf(turb));
+    } else {
+        rgb[0] = base + id10 / 10;                                                                              // :430-432
+        rgb[1] = base + (id10 / 10) * 0.5f;
+        rgb[2] = base + (id5 / 5) * 0.25f;
+    }
+}
+
+// the bump mapping of Scene::trace (Scene.cpp:235-261) on the normal N as intersect() left it; the caller normalises (:262)
+__device__ __forceinline__ void bump_normal(const NoiseTables &nt, float scale, float u, float v, float N[3], bool &ok) {
+    const float delta = (float)0.0001;
+    float u1 = 0.f, u2 = 0.f, v1 = 0.f, v2 = 0.f;
+#pragma unroll 1
+    for (int s = 0; s < 4; s++) {                                        // :243-246
+        const float h = stone_height(nt, scale, s == 0 ? u - delta : (s == 1 ? u + delta : u),
+                                     s == 2 ? v - delta : (s == 3 ? v + delta : v), ok);
+        if (s == 0) u1 = h;
+        if (s == 1) u2 = h;
+        if (s == 2) v1 = h;
+        if (s == 3) v2 = h;
+    }
+    const float dx = (u2 - u1) / (2 * delta), dy = (v2 - v1) / (2 * delta);                                     // :249-250
+    const float n0 = N[0], n1 = N[1], n2 = N[2];
+    int m = 0;                                                                                                  // :255-257
+    float nm = n0;
+    if (n1 > n0) { m = 1; nm = n1; }
+    if (n2 > nm) m = 2;
+    const float r[3] = {m == 2 ? -n2 : 0.f, m == 0 ? -n0 : 0.f, m == 1 ? -n1 : 0.f};                            // :258
+    const float t1[3] = {n1 * r[2] - n2 * r[1], n2 * r[0] - n0 * r[2], n0 * r[1] - n1 * r[0]};                  // :260
+    const float c1[3] = {n1 * t1[2] - n2 * t1[1], n2 * t1[0] - n0 * t1[2], n0 * t1[1] - n1 * t1[0]};
+    const float c2[3] = {n1 * c1[2] - n2 * c1[1], n2 * c1[0] - n0 * c1[2], n0 * c1[1] - n1 * c1[0]};
+    for (int c = 0; c < 3; c++) N[c] = N[c] + (c1[c] * dx - c2[c] * dy);                                        // :261
+}
+
+struct SurfaceArgs {
+    rec::MeshMat m;
+    TexParams t;                 // recs / mat_tex nullptr: the scene has no texture table
+    const mr_ray *rays;
+    const mr_hit *hits;
+    unsigned long long n;
+    float *color, *normal;       // three floats per ray each; a ray that missed keeps what the buffers held
+    unsigned long long *counts;  // optional: [0] += lookups the reference leaves undefined
+};
+
+__global__ __launch_bounds__(kBlock) void procedural_surface_kernel(SurfaceArgs a) {
+    __shared__ uint32_t s_tab[128];
+    const NoiseTables nt = stage_noise_tables(s_tab);
+    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
+    unsigned my_undefined = 0;
+    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < a.n; k += stride) {
+        const float4 h = reinterpret_cast<const float4 *>(a.hits)[k];
+        const uint32_t prim = __float_as_uint(h.y);
+        if (prim == MR_MISS) continue;
+        float P[3], N[3], col[3];
+        surface<true>(a.m.s, a.rays, k, h.x, prim, h.z, h.w, P, N);
+        const uint32_t mid = material_id(a.m.s, a.m.prim_mat, prim);
+        const uint32_t tex = a.t.mat_tex ? a.t.mat_tex[mid] : kNoTexture;
+        bool ok = true;
+        if (tex == kNoTexture) {
+            const float *mt = a.m.mats + 11 * (size_t)mid;
+            col[0] = mt[0]; col[1] = mt[1]; col[2] = mt[2];
+        } else {
+            const UvPtrs um = {a.m.s, a.t.texcoords, a.t.ti};
+            float u, v;
+            uv_of(um, prim, P, u, v);
+            const float4 q0 = a.t.recs[3 * (size_t)tex];
+            const uint32_t kind = __float_as_uint(q0.x);
+            // the noise is behind this branch: a wave none of whose hits lies on a procedural material skips it whole
+            if (kind == kTexStone || kind == kTexStem) {
+                const float scale = a.t.recs[3 * (size_t)tex + 1].w;
+                if (kind == kTexStem) {
+                    stem_color(nt, scale, u, v, col, ok);
+                } else {
+                    stone_color(nt, scale, u, v, col, ok);
+                    bump_normal(nt, scale, u, v, N, ok);
+                }
+            } else {
+                ok = texture_color(a.t, tex, u, v, col);
+            }
+        }
+        normalize3(N);                                                   // Scene.cpp:262
+        if (!ok) my_undefined++;
+        a.color[3 * k] = col[0]; a.color[3 * k + 1] = col[1]; a.color[3 * k + 2] = col[2];
+        a.normal[3 * k] = N[0]; a.normal[3 * k + 1] = N[1]; a.normal[3 * k + 2] = N[2];
+    }
+    if (a.counts) workgroup_add<kBlock>(my_undefined, &a.counts[0]);
+}
+
+__global__ __launch_bounds__(kBlock) void texture_lookup_proc_kernel(TexParams t, uint32_t id, const float *uv, unsigned long long n,
+                                                                     float *rgb, unsigned long long *counts) {
+    __shared__ uint32_t s_tab[128];
+    const NoiseTables nt = stage_noise_tables(s_tab);
+    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
+    const bool stem = __float_as_uint(t.recs[3 * (size_t)id].x) == kTexStem;
+    const float scale = t.recs[3 * (size_t)id + 1].w;
+    unsigned my_undefined = 0;
+    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += stride) {
+        float c[3];
+        bool ok = true;
+        if (stem) stem_color(nt, scale, uv[2 * k], uv[2 * k + 1], c, ok);
+        else stone_color(nt, scale, uv[2 * k], uv[2 * k + 1], c, ok);
+        if (!ok) my_undefined++;
+        rgb[3 * k] = c[0]; rgb[3 * k + 1] = c[1]; rgb[3 * k + 2] = c[2];
+    }
+    if (counts) workgroup_add<kBlock>(my_undefined, &counts[0]);
+}
+
+// stone: the texture is a StoneTexture; every other kind's bumpHeight2D is 0 (Texture.h:63,191)
+__global__ __launch_bounds__(kBlock) void bump_height_kernel(bool stone, float scale, const float *uv, unsigned long long n, float *height) {
+    __shared__ uint32_t s_tab[128];
+    const NoiseTables nt = stage_noise_tables(s_tab);
+    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
+    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += stride) {
+        bool ok = true;
+        height[k] = stone ? stone_height(nt, scale, uv[2 * k], uv[2 * k + 1], ok) : 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void noise_probe_kernel(uint32_t which, const float *in, unsigned long long n, float *out) {
+    __shared__ uint32_t s_tab[128];
+    const NoiseTables nt = stage_noise_tables(s_tab);
+    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
+    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += stride) {
+        bool ok = true;
+        if (which == MR_NOISE_PERLIN) {
+            out[k] = perlin_noise(nt, in[3 * k], in[3 * k + 1], in[3 * k + 2], ok);
+        } else {
+            const Worley3 w = worley2(nt, in[2 * k], in[2 * k + 1], ok);
+            float *o = out + 6 * k;
+            o[0] = w.F0; o[1] = w.F1; o[2] = w.F2;
+            o[3] = __uint_as_float(w.I0); o[4] = __uint_as_float(w.I1); o[5] = __uint_as_float(w.I2);
+        }
+    }
+}
+
+// shade_lights_body (mr_lights_body.h) with the hit's diffuseColor and N read from the surface pass's buffers
+template <int VAR, bool ANY>
+__device__ __forceinline__ void shade_lights_surf_body(const LightsArgs a, const float *color, const float *normal) {
+    using namespace rec;
+    extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
+    const int tid = threadIdx.x;
+    const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
+    const unsigned long long n = a.s.tp.n;
+    const unsigned long long n_round = whole_workgroups(n);
+    Stats st = {0ull, 0ull};
+    unsigned my_shadow_rays = 0;
+
+    for (unsigned long long k = (unsigned long long)xcd_block_id() * kTraceBlock + tid; k < n_round; k += stride) {
+        const bool live = k < n;
+        const float4 h = hit_record_of(a.s, k, live);
+        const bool hit = __float_as_uint(h.y) != MR_MISS;              // a miss contributes nothing (m_bgColor = 0)
+        float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 1.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
+        const float *mt = a.s.m.mats;
+        float col[3] = {0.f, 0.f, 0.f};                                // diffuseColor
+        if (hit) {
+            shade_point_of(a.s, k, h, P, N, d, mt);
+            for (int c = 0; c < 3; c++) { col[c] = color[3 * k + c]; N[c] = normal[3 * k + c]; }
+            my_shadow_rays += a.s.n_lights;
+        }
+
+        float L[3] = {0.f, 0.f, 0.f};
+        for (uint32_t li = 0; li < a.s.n_lights; li++) {               // Phong.cpp:63, wave-uniform
+            const ShadeLight &lt = a.lights[li];
+            float4 sh;
+            {
+                float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(1.f, 1.f, 1.f, -1.f);
+                if (hit) shadow_ray_for(lt, P, sa, sb);
+                const mr_hit hs = trace_hit<true, ANY, false, VAR>(a.s.tp, sa, sb, sb.w, hit, s_stack, tid, st);
+                sh = *reinterpret_cast<const float4 *>(&hs);
+            }
+            if (hit) {
+                float4 sa, sb;
+                shadow_ray_for(lt, P, sa, sb);                         // rebuilt rather than kept across the traversal
+                const float scale = light_scale_of(a.s.m, sa, sb, sh);
+                float diffuse[3] = {0.f, 0.f, 0.f}, highlight = 0.0f, out[3] = {0.f, 0.f, 0.f};
+                bool lit = scale != 0.0f;                              // Phong.cpp:100-111: the light is skipped
+                if (lit) {
+                    if (lt.kind == MR_LIGHT_DISC) {
+                        const float l[3] = {sb.x, sb.y, sb.z};
+                        lit = disc_terms(lt, mt, col, P, N, l, d[0], d[1], d[2], diffuse, highlight);
+                    } else {
+                        phong_terms(lt.position, lt.color, lt.wattage, mt, col, P, N, d[0], d[1], d[2], diffuse, highlight);
+                    }
+                }
+                if (lit) phong_combine(diffuse, highlight, scale, out);
+                L[0] += out[0]; L[1] += out[1]; L[2] += out[2];
+            }
+        }
+        store_shaded(a.s, k, live, hit, L);
+    }
+
+    if (a.s.counts) workgroup_add<kTraceBlock>(my_shadow_rays, &a.s.counts[0]);
+}
+
+template <int VAR, bool ANY>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void shade_lights_surf_kernel(LightsArgs a, const float *color,
+                                                                                                                  const float *normal) {
+    shade_lights_surf_body<VAR, ANY>(a, color, normal);
+}
+
+// shade_accumulate_body (mr_accumulate_body.h), the same way
+__global__ __launch_bounds__(kBlock) void shade_accumulate_surf_kernel(AccumArgs a, const float *color, const float *normal) {
+    using namespace rec;
+    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
+    const unsigned long long n_round = (a.n + 63ull) & ~63ull;                            // whole waves: accumulate_runs shuffles
+    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < n_round; k += stride) {
+        float v[3] = {0.f, 0.f, 0.f};
+        uint32_t pix = 0xFFFFFFFFu;
+        if (k < a.n) {
+            pix = pixel_of(a.pixels, k, a.spp);
+            const float4 h = reinterpret_cast<const float4 *>(a.hits)[k];
+            const uint32_t prim = __float_as_uint(h.y);
+            const float scale = prim != MR_MISS ? a.light_scale[k] : 0.0f;                // a miss: m_bgColor = 0 contributes nothing
+            if (scale != 0.0f) {
+                float P[3], N[3], diffuse[3], highlight, out[3];
+                surface<false>(a.m.s, a.rays, k, h.x, prim, h.z, h.w, P, N);
+                const float4 rb = reinterpret_cast<const float4 *>(a.rays)[2 * k + 1];
+                const float *mt = material_of(a.m, prim);
+                float col[3];
+                for (int c = 0; c < 3; c++) { col[c] = color[3 * k + c]; N[c] = normal[3 * k + c]; }
+                phong_terms(a.lt, mt, col, P, N, rb.x, rb.y, rb.z, diffuse, highlight);
+                phong_combine(diffuse, highlight, scale, out);
+                float w[3];
+                weight_of(a.weights, k, w);
+                for (int c = 0; c < 3; c++) v[c] = out[c] * w[c] * a.inv_spp;
+            }
+        }
+        accumulate_runs(a.rgb, pix, v[0], v[1], v[2]);
+    }
+}
+
+template <int VAR, bool ANY>
+mr_status launch_lights_surf_t(const LightsArgs &a, const float *color, const float *normal, hipStream_t stream) {
+    size_t lds = 0;
+    const mr_status st = stack_lds(&shade_lights_surf_kernel<VAR, ANY>, a.s.tp.stack_depth, kStackLdsShared, lds);
+    if (st != MR_OK) return st;
+    hipLaunchKernelGGL((shade_lights_surf_kernel<VAR, ANY>), dim3(trace_grid(a.s.tp.n)), dim3(kTraceBlock), lds, stream, a, color, normal);
+    MR_HIP_CHECK(hipGetLastError());
+    return MR_OK;
+}
+
+template <int VAR>
+mr_status launch_lights_surf_a(const LightsArgs &a, const float *color, const float *normal, bool any, hipStream_t stream) {
+    return any ? launch_lights_surf_t<VAR, true>(a, color, normal, stream) : launch_lights_surf_t<VAR, false>(a, color, normal, stream);
+}
+
+}  // namespace
+
+mr_status launch_hit_surface(const DeviceScene &ds, const TexParams &tex, const mr_ray *d_rays, const mr_hit *d_hits, unsigned long long n,
+                             float *d_color, float *d_normal, unsigned long long *d_counts, hipStream_t stream) {
+    if (n == 0) return MR_OK;
+    if ((ds.spheres || ds.planes) && !d_rays)
+        return fail(MR_ERR_INVALID, "the scene holds spheres / planes: their hit point is o + t*d, d_rays is required");
+    SurfaceArgs a;
+    a.m = rec::mesh_of(ds); a.t = tex; a.rays = d_rays; a.hits = d_hits; a.n = n; a.color = d_color; a.normal = d_normal; a.counts = d_counts;
+    hipLaunchKernelGGL(procedural_surface_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
+    MR_HIP_CHECK(hipGetLastError());
+    return MR_OK;
+}
+
+mr_status launch_shade_lights_surf(const DeviceScene &ds, const ShadeLight *lights, uint32_t n_lights, const mr_ray *d_rays,
+                                   const mr_hit *d_hits, const float *d_color, const float *d_normal, const float *d_weights,
+                                   const uint32_t *d_pixels, unsigned long long n, uint32_t spp, uint32_t flags, float *d_rgb,
+                                   float *d_ray_rgb, unsigned long long *d_counts, hipStream_t stream) {
+    if (n == 0) return MR_OK;
+    const LightsArgs a = lights_args_of(ds, lights, n_lights, d_rays, d_hits, d_weights, d_pixels, n, spp, d_rgb, d_ray_rgb, d_counts);
+    const bool any = flags & MR_TRACE_ANY;
+    return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT,
+                              [&](auto var) { return launch_lights_surf_a<decltype(var)::value>(a, d_color, d_normal, any, stream); });
+}
+
+mr_status launch_shade_accumulate_surf(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color,
+                                       const float *d_normal, const float *d_weights, const uint32_t *d_pixels, unsigned long long n,
+                                       const float *d_light_scale, const mr_light &light, uint32_t spp, float *d_rgb, hipStream_t stream) {
+    if (n == 0) return MR_OK;
+    AccumArgs a;
+    a.m = rec::mesh_of(ds); a.rays = d_rays; a.hits = d_hits; a.weights = d_weights; a.pixels = d_pixels; a.light_scale = d_light_scale;
+    a.lt = light_args_of(light); a.spp = spp; a.inv_spp = 1.0f / (float)spp; a.n = n; a.rgb = d_rgb;
+    hipLaunchKernelGGL(shade_accumulate_surf_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, a, d_color, d_normal);
+    MR_HIP_CHECK(hipGetLastError());
+    return MR_OK;
+}
+
+mr_status launch_texture_lookup_proc(const TexParams &tex, uint32_t texture, const float *d_uv, unsigned long long n, float *d_rgb,
+                                     unsigned long long *d_counts, hipStream_t stream) {
+    if (n == 0) return MR_OK;
+    hipLaunchKernelGGL(texture_lookup_proc_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, tex, texture, d_uv, n, d_rgb, d_counts);
+    MR_HIP_CHECK(hipGetLastError());
+    return MR_OK;
+}
+
+mr_status launch_bump_height(bool stone, float scale, const float *d_uv, unsigned long long n, float *d_height, hipStream_t stream) {
+    if (n == 0) return MR_OK;
+    hipLaunchKernelGGL(bump_height_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, stone, scale, d_uv, n, d_height);
+    MR_HIP_CHECK(hipGetLastError());
+    return MR_OK;
+}
+
+mr_status launch_noise_probe(uint32_t which, const float *d_in, unsigned long long n, float *d_out, hipStream_t stream) {
+    if (n == 0) return MR_OK;
+    hipLaunchKernelGGL(noise_probe_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, which, d_in, n, d_out);
+    MR_HIP_CHECK(hipGetLastError());
+    return MR_OK;
+}
+
+}  // namespace mr

@@ -35,7 +35,8 @@ MR_ENV_LOWRES = 1 << 16
 MR_LIGHT_POINT, MR_LIGHT_DISC = 0, 1
 MR_MAX_LIGHTS = 8
 
-MR_TEX_CHECKER, MR_TEX_IMAGE = 0, 1
+MR_TEX_CHECKER, MR_TEX_IMAGE, MR_TEX_STONE, MR_TEX_STEM = 0, 1, 2, 3
+MR_NOISE_PERLIN, MR_NOISE_WORLEY2 = 0, 1
 MR_MAX_TEXTURES = 16
 MR_NO_TEXTURE = MR_NO_TEXCOORD = 0xFFFFFFFF
 
@@ -58,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "mr_gen_eye_rays_lens", "mr_square_light_tangents", "mr_shade_square_lights",
     "mr_scene_set_environment", "mr_scene_get_environment", "mr_shade_environment",
     "mr_scene_set_texcoords", "mr_scene_get_texcoords", "mr_scene_set_textures", "mr_hit_uv", "mr_texture_lookup",
+    "mr_hit_surface", "mr_shade_lights_surface", "mr_shade_accumulate_surface", "mr_texture_bump_height", "mr_noise_probe",
     "mr_last_error", "mr_version",
 ]
 
@@ -186,7 +188,7 @@ class EnvironmentDesc(C.Structure):
 
 
 class TextureDesc(C.Structure):
-    """mr_texture_desc (miro_hip.h): a CheckerBoardTexture or a LoadedTexture"""
+    """mr_texture_desc (miro_hip.h): a CheckerBoardTexture, a LoadedTexture, a StoneTexture or a StemTexture"""
     _fields_ = [("kind", C.c_uint32), ("color1", C.c_float * 3), ("color2", C.c_float * 3), ("scale", C.c_float),
                 ("pixels", C.POINTER(C.c_float)), ("W", C.c_uint32), ("H", C.c_uint32), ("hdr", C.c_uint32),
                 ("reserved", C.c_uint32 * 5)]
@@ -291,6 +293,11 @@ def load_library(path=None):
     L.mr_scene_set_textures.argtypes = [vp, C.POINTER(TextureDesc), C.c_uint32, u32p]
     L.mr_hit_uv.argtypes = [vp, vp, vp, C.c_uint64, vp, vp]
     L.mr_texture_lookup.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
+    L.mr_hit_surface.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp, vp]
+    L.mr_shade_lights_surface.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.mr_shade_accumulate_surface.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(Light), C.c_uint32, vp, vp]
+    L.mr_texture_bump_height.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp]
+    L.mr_noise_probe.argtypes = [C.c_uint32, vp, C.c_uint64, vp, vp]
     L.mr_photon_map_create.argtypes = [C.c_int32, C.c_uint32, C.POINTER(vp)]
     L.mr_photon_map_destroy.argtypes = [vp]
     L.mr_photon_map_store.argtypes = [vp, C.c_uint32, f32p, f32p, f32p]
@@ -794,7 +801,8 @@ class Scene:
 
     def set_textures(self, textures, material_texture=None):
         """mr_scene_set_textures.  textures: TextureDesc objects or dicts -- dict(color1, color2, scale) is a checker,
-        dict(pixels [H, W, 3] float32 with row 0 = the bottom scanline, hdr) an image; an empty list clears the table.
+        dict(pixels [H, W, 3] float32 with row 0 = the bottom scanline, hdr) an image, dict(stone=scale) a StoneTexture,
+        dict(stem=scale) a StemTexture; an empty list clears the table.
         material_texture: a texture id per material (MR_NO_TEXTURE = plain Phong).  A material that names a texture becomes a
         TexturedPhong: its stored diffuse is replaced by clamp(1 - ks - kt), see miro_hip.h."""
         arr = (TextureDesc * max(len(textures), 1))()
@@ -809,6 +817,9 @@ class Scene:
                 keep.append(px)
                 arr[i].kind, arr[i].H, arr[i].W, arr[i].hdr = MR_TEX_IMAGE, px.shape[0], px.shape[1], int(t.get("hdr", 0))
                 arr[i].pixels = _f32p(px)
+            elif "stone" in t or "stem" in t:
+                arr[i].kind = MR_TEX_STONE if "stone" in t else MR_TEX_STEM
+                arr[i].scale = t["stone"] if "stone" in t else t["stem"]
             else:
                 arr[i].kind = MR_TEX_CHECKER
                 arr[i].color1[:] = t.get("color1", (1.0, 1.0, 1.0))
@@ -819,6 +830,7 @@ class Scene:
             mt = np.ascontiguousarray(material_texture, dtype=np.uint32)
         _check(self.L.mr_scene_set_textures(self.h, arr, len(textures), _u32p(mt) if mt is not None else None))
         self.n_textures = len(textures)
+        self.procedural = any(arr[i].kind in (MR_TEX_STONE, MR_TEX_STEM) for i in range(len(textures)))
 
     def hit_uv(self, d_rays, d_hits, n, d_uv, stream=None):
         """mr_hit_uv: Object::toUVCoordinates(hit.P) of n traced rays into d_uv [n, 2] ((0, 0) for a miss)"""
@@ -831,8 +843,48 @@ class Scene:
         _check(self.L.mr_texture_lookup(self.h, texture, d_uv.data_ptr(), n, d_rgb.data_ptr(),
                                         d_counts.data_ptr() if d_counts is not None else None, _stream_ptr(stream)))
 
+    def hit_surface(self, d_rays, d_hits, n, d_color, d_normal, d_counts=None, stream=None):
+        """mr_hit_surface: for every ray that hit, diffuseColor (Phong.cpp:51-56; every texture kind) into d_color [n, 3] and
+        the normal as Scene::trace leaves it (bump-mapped on a STONE material, normalised; Scene.cpp:234-263) into d_normal
+        [n, 3]; a miss leaves its rows untouched.  d_counts[0] += the hits whose lookup the reference leaves undefined."""
+        _check(self.L.mr_hit_surface(self.h, d_rays.data_ptr() if d_rays is not None else None, d_hits.data_ptr(), n,
+                                     d_color.data_ptr(), d_normal.data_ptr(), d_counts.data_ptr() if d_counts is not None else None,
+                                     _stream_ptr(stream)))
+
+    def shade_lights_surface(self, d_rays, d_hits, d_color, d_normal, n, d_rgb=None, d_weights=None, d_pixels=None, spp=1, flags=0,
+                             d_ray_rgb=None, d_counts=None, stream=None):
+        """mr_shade_lights_surface: shade_lights with the hit's diffuse colour and normal read from hit_surface's buffers"""
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        _check(self.L.mr_shade_lights_surface(self.h, d_rays.data_ptr(), d_hits.data_ptr(), d_color.data_ptr(), d_normal.data_ptr(),
+                                              ptr(d_weights), ptr(d_pixels), n, spp, flags, ptr(d_rgb), ptr(d_ray_rgb), ptr(d_counts),
+                                              _stream_ptr(stream)))
+
+    def shade_accumulate_surface(self, d_rays, d_hits, d_color, d_normal, d_weights, d_pixels, n, d_shadow_rays, d_shadow_hits,
+                                 d_shadow_src, d_shadow_count, light_pos, wattage, d_rgb, spp=1, color=(1.0, 1.0, 1.0), stream=None):
+        """mr_shade_accumulate_surface: shade_accumulate with the hit's diffuse colour and normal read from hit_surface's buffers"""
+        lt = Light()
+        lt.position[:] = light_pos
+        lt.color[:] = color
+        lt.wattage = wattage
+        _check(self.L.mr_shade_accumulate_surface(self.h, d_rays.data_ptr(), d_hits.data_ptr(), d_color.data_ptr(), d_normal.data_ptr(),
+                                                  d_weights.data_ptr() if d_weights is not None else None,
+                                                  d_pixels.data_ptr() if d_pixels is not None else None, n,
+                                                  d_shadow_rays.data_ptr(), d_shadow_hits.data_ptr(), d_shadow_src.data_ptr(),
+                                                  d_shadow_count.data_ptr(), C.byref(lt), spp, d_rgb.data_ptr(), _stream_ptr(stream)))
+
+    def texture_bump_height(self, texture, d_uv, n, d_height, stream=None):
+        """mr_texture_bump_height: Texture::bumpHeight2D of texture `texture` at d_uv [n, 2] into d_height [n] (0 unless STONE)"""
+        _check(self.L.mr_texture_bump_height(self.h, texture, d_uv.data_ptr(), n, d_height.data_ptr(), _stream_ptr(stream)))
+
     def tonemap(self, d_rgb, n_values, d_out, stream=None):
         _check(self.L.mr_tonemap(self.h, d_rgb.data_ptr(), n_values, d_out.data_ptr(), _stream_ptr(stream)))
+
+
+def noise_probe(which, d_in, n, d_out, stream=None):
+    """mr_noise_probe: MR_NOISE_PERLIN -- d_in [n, 3] -> d_out [n]; MR_NOISE_WORLEY2 -- d_in [n, 2] -> d_out [n, 6] words, F[3] as
+    float32 then ID[3] as uint32 (view the tensor's last three columns as int32)"""
+    _check(lib().mr_noise_probe(which, d_in.data_ptr(), n, d_out.data_ptr(), _stream_ptr(stream)))
 
 
 class PhotonMap:

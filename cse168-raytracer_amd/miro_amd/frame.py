@@ -334,10 +334,18 @@ class FrameRenderer:
         is worth 0 and no launch is added.
         A scene with a texture table (Scene.set_textures) takes the batched path for every level, whatever `fused` says
         (fused="auto" included): mr_trace_level shades without the texture lookup and refuses such a scene; the batched
-        path's mr_shade_accumulate / mr_shade_lights look the diffuse colour up (Phong.cpp:51-56)."""
+        path's mr_shade_accumulate / mr_shade_lights look the diffuse colour up (Phong.cpp:51-56).
+        A scene whose table holds a procedural texture (a StoneTexture or a StemTexture) adds one launch per level: trace ->
+        mr_hit_surface (diffuse colour and bump-mapped normal of every hit into two [n, 3] buffers sized to the level's queue)
+        -> mr_shade_lights_surface (light list) or the shadow batch and mr_shade_accumulate_surface (single light) -> the
+        generators.  Square lights and MR_PATH_DIFFUSE children are refused on such a scene (no _surface form; Ray::random
+        bounces about the normal)."""
         sc, L, W = self.scene, self.desc["light"], self.desc["wattage"]
         if getattr(sc, "n_textures", 0):
             fused = False
+        surface = bool(getattr(sc, "procedural", False))
+        if surface and self.square_lights:
+            raise ValueError("render_specular: square lights on a scene with a procedural texture (no _surface form shades them)")
         if environment is not None and environment is not False:
             if fused:
                 raise ValueError("render_specular: an environment needs fused=False (mr_trace_level keeps no hit records)")
@@ -428,14 +436,26 @@ class FrameRenderer:
             if environment:
                 sc.shade_environment(rays, hits, n, self.d_slots, d_weights=weights, d_pixels=pixels, spp=self.spp,
                                      flags=env_lowres if level > 0 else 0, stream=stream)
+            if surface:
+                color, normal = torch.empty((n, 3), **f32), torch.empty((n, 3), **f32)
+                sc.hit_surface(rays, hits, n, color, normal, stream=stream)
             if lights is not None:
-                sc.shade_lights(rays, hits, n, self.d_slots, d_weights=weights, d_pixels=pixels, spp=self.spp,
-                                flags=fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT), d_counts=cnt, stream=stream)
+                lfl = fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT)
+                if surface:
+                    sc.shade_lights_surface(rays, hits, color, normal, n, self.d_slots, d_weights=weights, d_pixels=pixels,
+                                            spp=self.spp, flags=lfl, d_counts=cnt, stream=stream)
+                else:
+                    sc.shade_lights(rays, hits, n, self.d_slots, d_weights=weights, d_pixels=pixels, spp=self.spp, flags=lfl,
+                                    d_counts=cnt, stream=stream)
             else:
                 sc.gen_shadow_rays(rays, hits, n, L, sh_rays, src, cnt, stream=stream)
                 sc.trace_indirect(sh_rays, cnt, n, sh_hits, fl, stream=stream)           # closest hit: the occluder matters
-                sc.shade_accumulate(rays, hits, weights, pixels, n, sh_rays, sh_hits, src, cnt, L, W, self.d_slots,
-                                    spp=self.spp, stream=stream)
+                if surface:
+                    sc.shade_accumulate_surface(rays, hits, color, normal, weights, pixels, n, sh_rays, sh_hits, src, cnt, L, W,
+                                                self.d_slots, spp=self.spp, stream=stream)
+                else:
+                    sc.shade_accumulate(rays, hits, weights, pixels, n, sh_rays, sh_hits, src, cnt, L, W, self.d_slots,
+                                        spp=self.spp, stream=stream)
             if self.square_lights:
                 sc.shade_square_lights(self.square_lights, self.square_samples, rays, hits, n, self.d_slots, seed=self.seed + level,
                                        d_weights=weights, d_pixels=pixels, spp=self.spp,

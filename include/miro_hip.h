@@ -238,7 +238,8 @@ mr_status mr_gen_shadow_rays(mr_scene *scene, const mr_ray *d_rays, const mr_hit
                              void *stream);
 /* HitInfo::P and ::N as the object's intersect() leaves them (Triangle.cpp:160,162; Sphere.cpp:61-63;
  * Plane.cpp:42-44), device buffers of 3 floats per ray (either may be NULL).  d_rays (the rays the hits belong
- * to) may be NULL for scenes of triangles only. */
+ * to) may be NULL for scenes of triangles only.  On a scene with a STONE texture this stays the un-bumped, un-normalised
+ * normal; mr_hit_surface gives the normal Scene::trace hands on (Scene.cpp:234-263). */
 mr_status mr_hit_attrs(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, uint64_t n, float *d_P, float *d_N,
                        void *stream);
 
@@ -626,23 +627,61 @@ mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_h
  *                   from the wrapped index: u == 1 extrapolates).  A lookup that leaves the image in the reference (negative or
  *                   non-finite u / v, an index beyond int) is DEFINED as 0 and counted -- for every negative coordinate,
  *                   the sliver -1 / W < u < 0 included, where the reference's truncation happens to stay on texel 0.
+ *   MR_TEX_STONE    StoneTexture(scale) (Texture.h:101-110, Texture.cpp:358-440): flagstones from WorleyNoise::noise2D of order 3
+ *                   with Perlin turbulence, and the one texture whose bumpHeight2D is not 0 -- Scene::trace bump-maps the normal
+ *                   of a hit on it (Scene.cpp:234-263).  Only `scale` is read.  A material that names one must have ks = kt = 0,
+ *                   as the reference's own uses have (assignment1.cpp:232,313): no reflected or refracted ray and no light
+ *                   through a refractive occluder (Phong.cpp:99-113 reads the occluder's N) ever needs a bumped normal.
+ *   MR_TEX_STEM     StemTexture(scale) (Texture.h:184-213): green from the same two noises; bump height 0.  Only `scale` is read.
+ *                   The two noises are pure functions over two fixed tables (csrc/mr_noise.h), pinned to values recorded from
+ *                   the reference's own lib/src/Perlin.cpp and lib/src/Worley.cpp (tests/golden/noise_kat.npz).  A coordinate
+ *                   that is NaN or reaches 2^30 after scaling fails int(floor()) there: DEFINED as noise 0 here and counted.
+ *                   powf / exp are the series of miro_math.h, where the reference calls libm; pow(f1f0, 2) (Texture.cpp:424)
+ *                   is the float product of the C++03 std::pow(float, int).
  * Errors (MR_ERR_INVALID, the earlier table stays): NULL scene, n_textures > MR_MAX_TEXTURES, NULL list, unknown kind, non-zero
  *   reserved word, non-finite field or pixel, W or H of 0 (or above 65536), NULL pixels, hdr > 1, a texture id >= n_textures, a
- *   material_texture given without a material table.
+ *   material_texture given without a material table, a STONE texture named by a material with a non-zero ks or kt.
  *
  * mr_hit_uv -- toUVCoordinates(hit.P) of n traced rays: d_uv receives 2n floats, (0, 0) for a miss.  d_rays may be NULL for
  *   scenes of triangles only.  mr_texture_lookup -- lookup2D of texture `texture` at n coordinates (d_uv: 2n floats): d_rgb
  *   receives 3n floats; d_counts (may be NULL): [0] += undefined lookups, not zeroed.  Both only enqueue on `stream`.
  *
+ *   mr_texture_lookup serves all four kinds.
+ *
  * Entry points that shade without the lookup refuse a scene with a texture table (MR_ERR_STATE, naming the batched calls):
- * mr_render_direct, mr_shade_direct, mr_trace_level, and mr_trace_photons (its roulette reads diffuse2D, Scene.cpp:545-551). */
-enum { MR_TEX_CHECKER = 0, MR_TEX_IMAGE = 1 };
+ * mr_render_direct, mr_shade_direct, mr_trace_level, and mr_trace_photons (its roulette reads diffuse2D, Scene.cpp:545-551).
+ *
+ * ---- procedural textures and bump-mapped normals: a per-hit surface pass (csrc/mr_procedural.hip) ----
+ * A STONE or STEM lookup is too heavy to sit inside a kernel that also traverses (five Worley searches and up to 33 Perlin
+ * evaluations per stone hit), so a scene whose table holds one is shaded in two steps: mr_hit_surface, then a _surface call.
+ * mr_hit_surface -- for every ray of a traced batch that hit: d_color[3k..] = diffuseColor of Phong.cpp:51-56 (m_diffuse of a
+ *   plain Phong, Texture::lookup2D at Object::toUVCoordinates(hit.P) of a TexturedPhong, all four kinds) and d_normal[3k..] =
+ *   HitInfo::N as Scene::trace leaves it (Scene.cpp:234-263): on a STONE material four bumpHeight2D samples at (u -+ delta, v),
+ *   (u, v -+ delta) with delta = (float)0.0001, dx and dy by central differences, randomVec by the largest component of N, t1 =
+ *   cross(N, randomVec), N += dx * cross(N, t1) - dy * cross(N, cross(N, t1)), then normalize(); on every other material the
+ *   normalisation alone (the zero perturbation is skipped).  A ray that missed leaves its six floats untouched.  Works on any
+ *   scene, with or without a texture table.  d_counts (may be NULL): [0] += hits whose lookup the reference leaves undefined,
+ *   not zeroed.  d_rays may be NULL for scenes of triangles only.
+ * mr_shade_lights_surface, mr_shade_accumulate_surface -- mr_shade_lights (Phong.cpp:44-150 over the light list) and
+ *   mr_shade_accumulate with the hit's diffuseColor and N read from d_color / d_normal (24 bytes per ray) instead of computed;
+ *   every other argument, check and output is the plain call's.  They look nothing up, so they run on any scene.
+ * mr_texture_bump_height -- Texture::bumpHeight2D (Texture.h:63; StoneTexture's: Texture.cpp:358-393) of texture `texture` at n
+ *   coordinates (d_uv: 2n floats) into d_height (n floats): 0 for every kind but STONE.
+ * mr_noise_probe -- the noise functions themselves, needs no scene: MR_NOISE_PERLIN reads xyz triples (3n floats) and writes
+ *   PerlinNoise::noise (Perlin.h:16-51), n floats; MR_NOISE_WORLEY2 reads xy pairs (2n floats) and writes, per point, F[3] as
+ *   floats then ID[3] as uint32 of WorleyNoise::noise2D(at, 3, ...) (Worley.cpp:95-173), 6n words.  Runs on the current device.
+ * All five only enqueue on `stream`.
+ *
+ * On a scene whose table holds a STONE or STEM texture the calls that would compute the colour or the normal themselves
+ * return MR_ERR_STATE with a message naming the _surface calls: mr_shade_lights, mr_shade_accumulate, mr_shade_square_lights,
+ * and mr_gen_path_rays with MR_PATH_DIFFUSE (Ray::random bounces about N).  A scene without them runs the kernels it ran before. */
+enum { MR_TEX_CHECKER = 0, MR_TEX_IMAGE = 1, MR_TEX_STONE = 2, MR_TEX_STEM = 3 };
 #define MR_MAX_TEXTURES 16
 #define MR_NO_TEXTURE  0xFFFFFFFFu
 #define MR_NO_TEXCOORD 0xFFFFFFFFu
 typedef struct mr_texture_desc {
     uint32_t kind;
-    float color1[3], color2[3], scale;                /* MR_TEX_CHECKER */
+    float color1[3], color2[3], scale;                /* MR_TEX_CHECKER; MR_TEX_STONE and MR_TEX_STEM read scale alone */
     const float *pixels;                              /* MR_TEX_IMAGE: host, W*H*3 floats, row 0 = bottom */
     uint32_t W, H, hdr;
     uint32_t reserved[5];                             /* must be 0 */
@@ -654,6 +693,18 @@ mr_status mr_scene_set_textures(mr_scene *scene, const mr_texture_desc *textures
 mr_status mr_hit_uv(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, uint64_t n, float *d_uv, void *stream);
 mr_status mr_texture_lookup(mr_scene *scene, uint32_t texture, const float *d_uv, uint64_t n, float *d_rgb, uint64_t *d_counts,
                             void *stream);
+enum { MR_NOISE_PERLIN = 0, MR_NOISE_WORLEY2 = 1 };
+mr_status mr_hit_surface(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, uint64_t n, float *d_color, float *d_normal,
+                         uint64_t *d_counts, void *stream);
+mr_status mr_shade_lights_surface(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color,
+                                  const float *d_normal, const float *d_weights, const uint32_t *d_pixels, uint64_t n, uint32_t spp,
+                                  uint32_t flags, float *d_rgb, float *d_ray_rgb, uint64_t *d_counts, void *stream);
+mr_status mr_shade_accumulate_surface(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color,
+                                      const float *d_normal, const float *d_weights, const uint32_t *d_pixels, uint64_t n,
+                                      const mr_ray *d_shadow_rays, const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src,
+                                      const uint64_t *d_shadow_count, const mr_light *light, uint32_t spp, float *d_rgb, void *stream);
+mr_status mr_texture_bump_height(mr_scene *scene, uint32_t texture, const float *d_uv, uint64_t n, float *d_height, void *stream);
+mr_status mr_noise_probe(uint32_t which, const float *d_in, uint64_t n, float *d_out, void *stream);
 
 /* sigmoid(6v-3) tone map + 8-bit quantisation (Scene.cpp:87-91,177-202; Image.cpp:44-50) */
 mr_status mr_tonemap(mr_scene *scene, const float *d_rgb, uint64_t n_values, uint8_t *d_out, void *stream);

@@ -225,5 +225,12 @@ MM_FN float mm_powf01(float x, float y) {
     if (x == 0.0f) return 0.0f;
     return (float)mm_exp((double)y * mm_log((double)x));
 }
+/* powf(x, y) for finite x >= 0, above 1 too, and 0 < y <= 1 (StoneTexture's pow(f[1] - f[0], 0.8f) and pow(f[2] - f[1] + f[0],
+ * 0.1f), Texture.cpp:370,409,412: distances between feature points); powf(0, y) = 0, NaN for a negative or NaN x, as libm */
+MM_FN float mm_powf(float x, float y) {
+    if (x == 0.0f) return 0.0f;
+    if (!(x > 0.0f)) { uint32_t q = 0x7fc00000u; float f; memcpy(&f, &q, 4); return f; }
+    return (float)mm_exp((double)y * mm_log((double)x));
+}
 
 #endif /* MIRO_MATH_H */
