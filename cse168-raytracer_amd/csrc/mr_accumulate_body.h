@@ -1,6 +1,11 @@
 // mr_accumulate_body.h -- the body of shade_accumulate_kernel (mr_bounce.hip, where the kernel is described) as a
 // __device__ template: its textured form (mr_textures.hip) is the same code with the hit's diffuseColor looked up first
-// (Phong.cpp:51-56; diffuse_color_of).  Arguments by value, as in mr_lights_body.h.  Included by the .hip units that instantiate it (everything here is local to its unit).
+// (Phong.cpp:51-56; diffuse_color_of), its surface-pass form (mr_procedural.hip) the same code with the colour and the normal
+// loaded from the pass's two buffers.  SRC is the ColorSource of mr_texture.h, and the arguments are taken by value, as in
+// mr_lights_body.h.  Every source calls surface_point: the surface-pass form needs P alone, but P is the same fp32 operations
+// in the same order whether surface_od is asked for N or not (no contraction in these units), and the N it would compute is
+// overwritten from the buffer before anything reads it, so no code is generated for it.  Included by the .hip units that
+// instantiate it (everything here is local to its unit).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,8 +34,19 @@ struct AccumArgs {
     float *rgb;
 };
 
-template <bool TEX>
-__device__ __forceinline__ void shade_accumulate_body(const AccumArgs a, const TexParams t) {
+// what launch_shade_accumulate and its textured and surface-pass forms fill in the same way
+inline AccumArgs accum_args_of(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
+                               const uint32_t *d_pixels, unsigned long long n, const float *d_light_scale, const mr_light &light,
+                               uint32_t spp, float *d_rgb) {
+    AccumArgs a;
+    a.m = rec::mesh_of(ds); a.rays = d_rays; a.hits = d_hits; a.weights = d_weights; a.pixels = d_pixels; a.light_scale = d_light_scale;
+    a.lt = light_args_of(light); a.spp = spp; a.inv_spp = 1.0f / (float)spp; a.n = n; a.rgb = d_rgb;
+    return a;
+}
+
+// t: read by kColorTexture only; color, normal: three floats per ray each, read by kColorSurface only
+template <int SRC>
+__device__ __forceinline__ void shade_accumulate_body(const AccumArgs a, const TexParams t, const float *color, const float *normal) {
     using namespace rec;
     const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
     const unsigned long long n_round = (a.n + 63ull) & ~63ull;                            // whole waves: accumulate_runs shuffles
@@ -48,8 +64,10 @@ __device__ __forceinline__ void shade_accumulate_body(const AccumArgs a, const T
                 const float4 rb = reinterpret_cast<const float4 *>(a.rays)[2 * k + 1];
                 const float *mt = material_of(a.m, prim);
                 float col[3] = {0.f, 0.f, 0.f};
-                if (TEX) diffuse_color_of(a.m, t, material_id(a.m.s, a.m.prim_mat, prim), prim, P, col);
-                phong_terms(a.lt, mt, TEX ? col : mt, P, N, rb.x, rb.y, rb.z, diffuse, highlight);
+                if (SRC == kColorTexture) diffuse_color_of(a.m, t, material_id(a.m.s, a.m.prim_mat, prim), prim, P, col);
+                if (SRC == kColorSurface)
+                    for (int c = 0; c < 3; c++) { col[c] = color[3 * k + c]; N[c] = normal[3 * k + c]; }
+                phong_terms(a.lt, mt, SRC == kColorMaterial ? mt : col, P, N, rb.x, rb.y, rb.z, diffuse, highlight);
                 phong_combine(diffuse, highlight, scale, out);
                 float w[3];
                 weight_of(a.weights, k, w);

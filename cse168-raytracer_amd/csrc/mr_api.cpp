@@ -957,15 +957,26 @@ static mr_status reserve_light_scale(mr_scene *s, uint64_t n) {
     return MR_OK;
 }
 
+// what mr_shade_accumulate and mr_shade_accumulate_surface ask first, in this order.  surface_null: one of the buffers that the
+// _surface call takes besides is NULL
+static mr_status check_shade_accumulate(const char *who, mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, bool surface_null,
+                                        const mr_ray *d_shadow_rays, const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src,
+                                        const uint64_t *d_shadow_count, const mr_light *light, uint32_t spp, const float *d_rgb) {
+    const mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (!d_rays || !d_hits || surface_null || !d_shadow_rays || !d_shadow_hits || !d_shadow_src || !d_shadow_count || !light || !d_rgb)
+        return fail(MR_ERR_INVALID, "%s: NULL argument", who);
+    if (spp == 0) return fail(MR_ERR_INVALID, "%s: spp is 0", who);
+    return MR_OK;
+}
+
 mr_status mr_shade_accumulate(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
                               const uint32_t *d_pixels, uint64_t n, const mr_ray *d_shadow_rays, const mr_hit *d_shadow_hits,
                               const uint32_t *d_shadow_src, const uint64_t *d_shadow_count, const mr_light *light, uint32_t spp,
                               float *d_rgb, void *stream) {
-    mr_status st = require_device(s);
+    mr_status st = check_shade_accumulate("mr_shade_accumulate", s, d_rays, d_hits, false, d_shadow_rays, d_shadow_hits, d_shadow_src,
+                                          d_shadow_count, light, spp, d_rgb);
     if (st != MR_OK) return st;
-    if (!d_rays || !d_hits || !d_shadow_rays || !d_shadow_hits || !d_shadow_src || !d_shadow_count || !light || !d_rgb)
-        return fail(MR_ERR_INVALID, "NULL argument");
-    if (spp == 0) return fail(MR_ERR_INVALID, "spp is 0");
     if ((st = refuse_procedural(s, "mr_shade_accumulate", "mr_shade_accumulate_surface")) != MR_OK) return st;
     MR_HIP_CHECK(hipSetDevice(s->device));
     if ((st = reserve_light_scale(s, n)) != MR_OK) return st;
@@ -1068,21 +1079,31 @@ mr_status mr_scene_set_lights(mr_scene *s, const mr_light_desc *lights, uint32_t
     return MR_OK;
 }
 
+// what mr_shade_lights and mr_shade_lights_surface ask of the scene and of their arguments, in this order.  surface_null /
+// surface_misaligned: one of the buffers that the _surface call takes besides is
+static mr_status check_shade_lights(const char *who, mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, bool surface_null,
+                                    bool surface_misaligned, uint64_t n, uint32_t spp, uint32_t flags, const float *d_rgb,
+                                    const float *d_ray_rgb, const uint64_t *d_counts) {
+    const mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (s->lights.empty()) return fail(MR_ERR_STATE, "%s: the scene has no lights (mr_scene_set_lights)", who);
+    if (!d_rays || !d_hits || surface_null || (!d_rgb && !d_ray_rgb)) return fail(MR_ERR_INVALID, "%s: NULL argument", who);
+    if (spp == 0) return fail(MR_ERR_INVALID, "%s: spp is 0", who);
+    if (n / spp > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: too many pixels", who);
+    if (flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT | MR_TRACE_ANY))
+        return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_TRACE_ANY only", who);
+    if ((flags & MR_TRACE_ANY) && s->dev.refractive)
+        return fail(MR_ERR_STATE, "%s: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)", who);
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3) || surface_misaligned)
+        return fail(MR_ERR_INVALID, "%s: ray / hit buffers must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned", who);
+    return MR_OK;
+}
+
 mr_status mr_shade_lights(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels,
                           uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb, uint64_t *d_counts, void *stream) {
-    mr_status st = require_device(s);
+    mr_status st = check_shade_lights("mr_shade_lights", s, d_rays, d_hits, false, false, n, spp, flags, d_rgb, d_ray_rgb, d_counts);
     if (st != MR_OK) return st;
-    if (s->lights.empty()) return fail(MR_ERR_STATE, "mr_shade_lights: the scene has no lights (mr_scene_set_lights)");
-    if (!d_rays || !d_hits || (!d_rgb && !d_ray_rgb)) return fail(MR_ERR_INVALID, "NULL argument");
-    if (spp == 0) return fail(MR_ERR_INVALID, "spp is 0");
-    if (n / spp > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "too many pixels");
-    if (flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT | MR_TRACE_ANY))
-        return fail(MR_ERR_INVALID, "mr_shade_lights: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_TRACE_ANY only");
-    if ((flags & MR_TRACE_ANY) && s->dev.refractive)
-        return fail(MR_ERR_STATE, "mr_shade_lights: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)");
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
-        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3))
-        return fail(MR_ERR_INVALID, "ray / hit buffers must be 16-byte aligned, counters 8-byte aligned");
     if ((st = refuse_procedural(s, "mr_shade_lights", "mr_shade_lights_surface")) != MR_OK) return st;
     MR_HIP_CHECK(hipSetDevice(s->device));
     if (!s->tex.blob.empty()) {
@@ -1437,21 +1458,10 @@ mr_status mr_hit_surface(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits
 mr_status mr_shade_lights_surface(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color, const float *d_normal,
                                   const float *d_weights, const uint32_t *d_pixels, uint64_t n, uint32_t spp, uint32_t flags,
                                   float *d_rgb, float *d_ray_rgb, uint64_t *d_counts, void *stream) {
-    const char *who = "mr_shade_lights_surface";
-    mr_status st = require_device(s);
+    const mr_status st = check_shade_lights("mr_shade_lights_surface", s, d_rays, d_hits, !d_color || !d_normal,
+                                            (reinterpret_cast<uintptr_t>(d_color) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3), n, spp,
+                                            flags, d_rgb, d_ray_rgb, d_counts);
     if (st != MR_OK) return st;
-    if (s->lights.empty()) return fail(MR_ERR_STATE, "%s: the scene has no lights (mr_scene_set_lights)", who);
-    if (!d_rays || !d_hits || !d_color || !d_normal || (!d_rgb && !d_ray_rgb)) return fail(MR_ERR_INVALID, "%s: NULL argument", who);
-    if (spp == 0) return fail(MR_ERR_INVALID, "%s: spp is 0", who);
-    if (n / spp > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: too many pixels", who);
-    if (flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT | MR_TRACE_ANY))
-        return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_TRACE_ANY only", who);
-    if ((flags & MR_TRACE_ANY) && s->dev.refractive)
-        return fail(MR_ERR_STATE, "%s: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)", who);
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
-        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_color) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_normal) & 3))
-        return fail(MR_ERR_INVALID, "%s: ray / hit buffers must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned", who);
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_shade_lights_surf(s->dev, s->lights.data(), (uint32_t)s->lights.size(), d_rays, d_hits, d_color, d_normal, d_weights, d_pixels,
                                     n, spp, flags, d_rgb, d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts),
@@ -1462,11 +1472,9 @@ mr_status mr_shade_accumulate_surface(mr_scene *s, const mr_ray *d_rays, const m
                                       const float *d_weights, const uint32_t *d_pixels, uint64_t n, const mr_ray *d_shadow_rays,
                                       const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src, const uint64_t *d_shadow_count,
                                       const mr_light *light, uint32_t spp, float *d_rgb, void *stream) {
-    mr_status st = require_device(s);
+    mr_status st = check_shade_accumulate("mr_shade_accumulate_surface", s, d_rays, d_hits, !d_color || !d_normal, d_shadow_rays,
+                                          d_shadow_hits, d_shadow_src, d_shadow_count, light, spp, d_rgb);
     if (st != MR_OK) return st;
-    if (!d_rays || !d_hits || !d_color || !d_normal || !d_shadow_rays || !d_shadow_hits || !d_shadow_src || !d_shadow_count || !light || !d_rgb)
-        return fail(MR_ERR_INVALID, "mr_shade_accumulate_surface: NULL argument");
-    if (spp == 0) return fail(MR_ERR_INVALID, "mr_shade_accumulate_surface: spp is 0");
     if ((reinterpret_cast<uintptr_t>(d_color) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3))
         return fail(MR_ERR_INVALID, "mr_shade_accumulate_surface: float buffers must be 4-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));

@@ -38,9 +38,10 @@ __global__ __launch_bounds__(kBlock) void light_scale_kernel(MeshMat m, const mr
     }
 }
 
-// the body is shade_accumulate_body (mr_accumulate_body.h), which the textured form in mr_textures.hip shares
+// the body is shade_accumulate_body (mr_accumulate_body.h), which the textured form in mr_textures.hip and the surface-pass
+// form in mr_procedural.hip share
 __global__ __launch_bounds__(kBlock) void shade_accumulate_kernel(AccumArgs a) {
-    shade_accumulate_body<false>(a, TexParams());
+    shade_accumulate_body<kColorMaterial>(a, TexParams(), nullptr, nullptr);
 }
 
 struct BounceArgs {
@@ -212,13 +213,10 @@ mr_status launch_shade_accumulate(const DeviceScene &ds, const mr_ray *d_rays, c
                                   const unsigned long long *d_shadow_count, float *d_light_scale, const mr_light &light,
                                   uint32_t spp, float *d_rgb, const TexParams *tex, hipStream_t stream) {
     if (n == 0) return MR_OK;
-    const MeshMat m = mesh_of(ds);
     const mr_status st = launch_light_scale(ds, d_shadow_rays, d_shadow_hits, d_shadow_src, d_shadow_count, n, d_light_scale, stream);
     if (st != MR_OK) return st;
     if (tex) return launch_shade_accumulate_tex(ds, *tex, d_rays, d_hits, d_weights, d_pixels, n, d_light_scale, light, spp, d_rgb, stream);
-    AccumArgs a;
-    a.m = m; a.rays = d_rays; a.hits = d_hits; a.weights = d_weights; a.pixels = d_pixels; a.light_scale = d_light_scale;
-    a.lt = light_args_of(light); a.spp = spp; a.inv_spp = 1.0f / (float)spp; a.n = n; a.rgb = d_rgb;
+    const AccumArgs a = accum_args_of(ds, d_rays, d_hits, d_weights, d_pixels, n, d_light_scale, light, spp, d_rgb);
     hipLaunchKernelGGL(shade_accumulate_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;

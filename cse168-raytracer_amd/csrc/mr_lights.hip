@@ -39,25 +39,11 @@ using namespace rec;
 
 // VAR: the traversal variant of trace_ray (mr_traverse.h); ANY: the shadow rays stop at their first accepted hit (scenes
 // without a refractive material only: every occluder then scales the light to 0, whichever it is).  The body is
-// shade_lights_body (mr_lights_body.h), which the textured form in mr_textures.hip shares.
+// shade_lights_body (mr_lights_body.h), which the textured form in mr_textures.hip and the surface-pass form in
+// mr_procedural.hip share.
 template <int VAR, bool ANY>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void shade_lights_kernel(LightsArgs a) {
-    shade_lights_body<VAR, ANY, false>(a, TexParams());
-}
-
-template <int VAR, bool ANY>
-mr_status launch_lights_t(const LightsArgs &a, hipStream_t stream) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(&shade_lights_kernel<VAR, ANY>, a.s.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL((shade_lights_kernel<VAR, ANY>), dim3(trace_grid(a.s.tp.n)), dim3(kTraceBlock), lds, stream, a);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
-}
-
-template <int VAR>
-mr_status launch_lights_a(const LightsArgs &a, bool any, hipStream_t stream) {
-    return any ? launch_lights_t<VAR, true>(a, stream) : launch_lights_t<VAR, false>(a, stream);
+    shade_lights_body<VAR, ANY, kColorMaterial>(a, TexParams(), nullptr, nullptr);
 }
 
 }  // namespace
@@ -71,8 +57,10 @@ mr_status launch_shade_lights(const DeviceScene &ds, const ShadeLight *lights, u
 
     // the traversal variants of launch_level / launch_trace: the same hit records from each of them
     const bool any = flags & MR_TRACE_ANY;
-    return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT,
-                              [&](auto var) { return launch_lights_a<decltype(var)::value>(a, any, stream); });
+    return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT, [&](auto var) {
+        constexpr int VAR = decltype(var)::value;
+        return launch_lights(any ? &shade_lights_kernel<VAR, true> : &shade_lights_kernel<VAR, false>, a, stream);
+    });
 }
 
 }  // namespace mr

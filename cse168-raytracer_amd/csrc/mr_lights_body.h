@@ -1,10 +1,15 @@
 // mr_lights_body.h -- the body of shade_lights_kernel (mr_lights.hip, where the kernel is described) as a __device__
-// template, so that its textured form (mr_textures.hip) is the same code with one more step: TEX looks the hit's
-// diffuseColor up once per hit, before the light loop, as Phong.cpp:51-56 does, and keeps the colour (three registers)
-// across the shadow traversals.  Without TEX the colour is the material's own m_diffuse, read where it is used: the
-// untextured kernels are what they were -- the arguments are taken BY VALUE for that: through a reference to the kernel's
-// argument block the same body compiles to other register and scratch figures.  Included by the .hip units that instantiate
-// it (everything here is local to its unit).
+// template, so that its textured form (mr_textures.hip) and its surface-pass form (mr_procedural.hip) are the same code with
+// one more step.  SRC (ColorSource, mr_texture.h) says where the hit's diffuseColor comes from:
+//   kColorMaterial  the material's own m_diffuse, read where it is used
+//   kColorTexture   looked up once per hit, before the light loop, as Phong.cpp:51-56 does (diffuse_color_of)
+//   kColorSurface   loaded from the surface pass's colour buffer, and the hit's N from its normal buffer (Scene.cpp:234-263)
+// The last two keep the colour (three registers) across the shadow traversals.  The arguments are taken BY VALUE: through a
+// reference to the kernel's argument block the same body compiles to other register and scratch figures.  Measured when
+// kColorSurface joined the other two (hipcc, gfx950, the Makefile's flags): a source leaves the code of the other sources'
+// kernels alone -- the device assembly of mr_lights.hip, mr_textures.hip and mr_bounce.hip did not change by an instruction.
+// The launch plumbing of the three forms is launch_lights below.  Included by the .hip units that instantiate it (everything
+// here is local to its unit).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -86,8 +91,9 @@ struct LightsArgs {
     ShadeLight lights[MR_MAX_LIGHTS];
 };
 
-template <int VAR, bool ANY, bool TEX>
-__device__ __forceinline__ void shade_lights_body(const LightsArgs a, const TexParams t) {
+// t: read by kColorTexture only; color, normal: three floats per ray each, read by kColorSurface only
+template <int VAR, bool ANY, int SRC>
+__device__ __forceinline__ void shade_lights_body(const LightsArgs a, const TexParams t, const float *color, const float *normal) {
     using namespace rec;
     extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
     const int tid = threadIdx.x;
@@ -103,13 +109,15 @@ __device__ __forceinline__ void shade_lights_body(const LightsArgs a, const TexP
         const bool hit = __float_as_uint(h.y) != MR_MISS;              // a miss contributes nothing (m_bgColor = 0)
         float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 1.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
         const float *mt = a.s.m.mats;
-        float col[3] = {0.f, 0.f, 0.f};                                // TEX: diffuseColor
+        float col[3] = {0.f, 0.f, 0.f};                                // diffuseColor, unless the material's own
         if (hit) {
             shade_point_of(a.s, k, h, P, N, d, mt);
-            if (TEX) diffuse_color_of(a.s.m, t, material_id(a.s.m.s, a.s.m.prim_mat, __float_as_uint(h.y)), __float_as_uint(h.y), P, col);
+            if (SRC == kColorTexture) diffuse_color_of(a.s.m, t, material_id(a.s.m.s, a.s.m.prim_mat, __float_as_uint(h.y)), __float_as_uint(h.y), P, col);
+            if (SRC == kColorSurface)
+                for (int c = 0; c < 3; c++) { col[c] = color[3 * k + c]; N[c] = normal[3 * k + c]; }
             my_shadow_rays += a.s.n_lights;
         }
-        const float *dc = TEX ? col : mt;
+        const float *dc = SRC == kColorMaterial ? mt : col;
 
         float L[3] = {0.f, 0.f, 0.f};
         for (uint32_t li = 0; li < a.s.n_lights; li++) {               // Phong.cpp:63, wave-uniform
@@ -145,7 +153,7 @@ __device__ __forceinline__ void shade_lights_body(const LightsArgs a, const TexP
     if (a.s.counts) workgroup_add<kTraceBlock>(my_shadow_rays, &a.s.counts[0]);
 }
 
-// what launch_shade_lights and its textured form fill in the same way
+// what launch_shade_lights and its textured and surface-pass forms fill in the same way
 inline LightsArgs lights_args_of(const DeviceScene &ds, const ShadeLight *lights, uint32_t n_lights, const mr_ray *d_rays,
                                  const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels, unsigned long long n,
                                  uint32_t spp, float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts) {
@@ -153,6 +161,18 @@ inline LightsArgs lights_args_of(const DeviceScene &ds, const ShadeLight *lights
     fill_shade_args(a.s, ds, n_lights, d_rays, d_hits, d_weights, d_pixels, n, spp, d_rgb, d_ray_rgb, d_counts);
     for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = lights[i < n_lights ? i : 0];
     return a;
+}
+
+// ... and launch the same way: `kern` is the unit's own light-list kernel for the batch's traversal variant, `rest` its
+// arguments after the LightsArgs
+template <typename K, typename... Rest>
+mr_status launch_lights(K kern, const LightsArgs &a, hipStream_t stream, Rest... rest) {
+    size_t lds = 0;
+    const mr_status st = stack_lds(kern, a.s.tp.stack_depth, kStackLdsShared, lds);
+    if (st != MR_OK) return st;
+    hipLaunchKernelGGL(kern, dim3(trace_grid(a.s.tp.n)), dim3(kTraceBlock), lds, stream, a, rest...);
+    MR_HIP_CHECK(hipGetLastError());
+    return MR_OK;
 }
 
 }  // namespace

@@ -4,8 +4,9 @@
 //
 //   procedural_surface_kernel      per hit of a traced batch: diffuseColor (Phong.cpp:51-56) and the bumped, normalised normal,
 //                                  into two per-ray buffers of three floats each (mr_hit_surface)
-//   shade_lights_surf_kernel       shade_lights_kernel (mr_lights.hip) reading that colour and normal instead of computing them
-//   shade_accumulate_surf_kernel   shade_accumulate_kernel (mr_bounce.hip), the same way
+//   shade_lights_surf_kernel       shade_lights_kernel (mr_lights.hip) reading that colour and normal instead of computing
+//                                  them: shade_lights_body<.., kColorSurface>
+//   shade_accumulate_surf_kernel   shade_accumulate_kernel (mr_bounce.hip), the same way: shade_accumulate_body<kColorSurface>
 //   texture_lookup_proc_kernel     lookup2D of a STONE / STEM texture for a batch of coordinates (mr_texture_lookup)
 //   bump_height_kernel             bumpHeight2D of one texture for a batch of coordinates (mr_texture_bump_height)
 //   noise_probe_kernel             PerlinNoise::noise / WorleyNoise::noise2D of order 3 themselves (mr_noise_probe)
@@ -13,9 +14,8 @@
 // Why a pass of its own: a stone hit costs five three-point Worley searches and up to 5 + 4 * 7 Perlin evaluations.  The
 // textured light-list kernel already spills in its worst variant; the surface pass has no traversal, so it
 // keeps everything in registers, and the shading kernels that follow it are the light-list and accumulate kernels with two
-// loads in place of the normal and the colour.  The two shading bodies are written out here, not added as one more switch to
-// mr_lights_body.h / mr_accumulate_body.h: the existing kernels keep their recorded register figures that way (see the note
-// on by-value arguments in mr_lights_body.h).  They share every piece around the changed lines with those bodies.
+// loads in place of the normal and the colour: the shared bodies of mr_lights_body.h / mr_accumulate_body.h with the
+// kColorSurface source.
 //
 // powf and exp are the double series of miro_math.h rounded once (mm_powf, mm_exp); the reference calls libm's, which a
 // host restatement can call too -- tests/test_procedural.py measures the distance.  pow(f1f0, 2) (Texture.cpp:424) is
@@ -218,115 +218,16 @@ __global__ __launch_bounds__(kBlock) void noise_probe_kernel(uint32_t which, con
     }
 }
 
-// shade_lights_body (mr_lights_body.h) with the hit's diffuseColor and N read from the surface pass's buffers
-template <int VAR, bool ANY>
-__device__ __forceinline__ void shade_lights_surf_body(const LightsArgs a, const float *color, const float *normal) {
-    using namespace rec;
-    extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
-    const int tid = threadIdx.x;
-    const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
-    const unsigned long long n = a.s.tp.n;
-    const unsigned long long n_round = whole_workgroups(n);
-    Stats st = {0ull, 0ull};
-    unsigned my_shadow_rays = 0;
-
-    for (unsigned long long k = (unsigned long long)xcd_block_id() * kTraceBlock + tid; k < n_round; k += stride) {
-        const bool live = k < n;
-        const float4 h = hit_record_of(a.s, k, live);
-        const bool hit = __float_as_uint(h.y) != MR_MISS;              // a miss contributes nothing (m_bgColor = 0)
-        float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 1.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
-        const float *mt = a.s.m.mats;
-        float col[3] = {0.f, 0.f, 0.f};                                // diffuseColor
-        if (hit) {
-            shade_point_of(a.s, k, h, P, N, d, mt);
-            for (int c = 0; c < 3; c++) { col[c] = color[3 * k + c]; N[c] = normal[3 * k + c]; }
-            my_shadow_rays += a.s.n_lights;
-        }
-
-        float L[3] = {0.f, 0.f, 0.f};
-        for (uint32_t li = 0; li < a.s.n_lights; li++) {               // Phong.cpp:63, wave-uniform
-            const ShadeLight &lt = a.lights[li];
-            float4 sh;
-            {
-                float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(1.f, 1.f, 1.f, -1.f);
-                if (hit) shadow_ray_for(lt, P, sa, sb);
-                const mr_hit hs = trace_hit<true, ANY, false, VAR>(a.s.tp, sa, sb, sb.w, hit, s_stack, tid, st);
-                sh = *reinterpret_cast<const float4 *>(&hs);
-            }
-            if (hit) {
-                float4 sa, sb;
-                shadow_ray_for(lt, P, sa, sb);                         // rebuilt rather than kept across the traversal
-                const float scale = light_scale_of(a.s.m, sa, sb, sh);
-                float diffuse[3] = {0.f, 0.f, 0.f}, highlight = 0.0f, out[3] = {0.f, 0.f, 0.f};
-                bool lit = scale != 0.0f;                              // Phong.cpp:100-111: the light is skipped
-                if (lit) {
-                    if (lt.kind == MR_LIGHT_DISC) {
-                        const float l[3] = {sb.x, sb.y, sb.z};
-                        lit = disc_terms(lt, mt, col, P, N, l, d[0], d[1], d[2], diffuse, highlight);
-                    } else {
-                        phong_terms(lt.position, lt.color, lt.wattage, mt, col, P, N, d[0], d[1], d[2], diffuse, highlight);
-                    }
-                }
-                if (lit) phong_combine(diffuse, highlight, scale, out);
-                L[0] += out[0]; L[1] += out[1]; L[2] += out[2];
-            }
-        }
-        store_shaded(a.s, k, live, hit, L);
-    }
-
-    if (a.s.counts) workgroup_add<kTraceBlock>(my_shadow_rays, &a.s.counts[0]);
-}
-
+// shade_lights_body (mr_lights_body.h) and shade_accumulate_body (mr_accumulate_body.h) with the hit's diffuseColor and N read
+// from the surface pass's buffers
 template <int VAR, bool ANY>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void shade_lights_surf_kernel(LightsArgs a, const float *color,
                                                                                                                   const float *normal) {
-    shade_lights_surf_body<VAR, ANY>(a, color, normal);
+    shade_lights_body<VAR, ANY, kColorSurface>(a, TexParams(), color, normal);
 }
 
-// shade_accumulate_body (mr_accumulate_body.h), the same way
 __global__ __launch_bounds__(kBlock) void shade_accumulate_surf_kernel(AccumArgs a, const float *color, const float *normal) {
-    using namespace rec;
-    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
-    const unsigned long long n_round = (a.n + 63ull) & ~63ull;                            // whole waves: accumulate_runs shuffles
-    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < n_round; k += stride) {
-        float v[3] = {0.f, 0.f, 0.f};
-        uint32_t pix = 0xFFFFFFFFu;
-        if (k < a.n) {
-            pix = pixel_of(a.pixels, k, a.spp);
-            const float4 h = reinterpret_cast<const float4 *>(a.hits)[k];
-            const uint32_t prim = __float_as_uint(h.y);
-            const float scale = prim != MR_MISS ? a.light_scale[k] : 0.0f;                // a miss: m_bgColor = 0 contributes nothing
-            if (scale != 0.0f) {
-                float P[3], N[3], diffuse[3], highlight, out[3];
-                surface<false>(a.m.s, a.rays, k, h.x, prim, h.z, h.w, P, N);
-                const float4 rb = reinterpret_cast<const float4 *>(a.rays)[2 * k + 1];
-                const float *mt = material_of(a.m, prim);
-                float col[3];
-                for (int c = 0; c < 3; c++) { col[c] = color[3 * k + c]; N[c] = normal[3 * k + c]; }
-                phong_terms(a.lt, mt, col, P, N, rb.x, rb.y, rb.z, diffuse, highlight);
-                phong_combine(diffuse, highlight, scale, out);
-                float w[3];
-                weight_of(a.weights, k, w);
-                for (int c = 0; c < 3; c++) v[c] = out[c] * w[c] * a.inv_spp;
-            }
-        }
-        accumulate_runs(a.rgb, pix, v[0], v[1], v[2]);
-    }
-}
-
-template <int VAR, bool ANY>
-mr_status launch_lights_surf_t(const LightsArgs &a, const float *color, const float *normal, hipStream_t stream) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(&shade_lights_surf_kernel<VAR, ANY>, a.s.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL((shade_lights_surf_kernel<VAR, ANY>), dim3(trace_grid(a.s.tp.n)), dim3(kTraceBlock), lds, stream, a, color, normal);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
-}
-
-template <int VAR>
-mr_status launch_lights_surf_a(const LightsArgs &a, const float *color, const float *normal, bool any, hipStream_t stream) {
-    return any ? launch_lights_surf_t<VAR, true>(a, color, normal, stream) : launch_lights_surf_t<VAR, false>(a, color, normal, stream);
+    shade_accumulate_body<kColorSurface>(a, TexParams(), color, normal);
 }
 
 }  // namespace
@@ -350,17 +251,17 @@ mr_status launch_shade_lights_surf(const DeviceScene &ds, const ShadeLight *ligh
     if (n == 0) return MR_OK;
     const LightsArgs a = lights_args_of(ds, lights, n_lights, d_rays, d_hits, d_weights, d_pixels, n, spp, d_rgb, d_ray_rgb, d_counts);
     const bool any = flags & MR_TRACE_ANY;
-    return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT,
-                              [&](auto var) { return launch_lights_surf_a<decltype(var)::value>(a, d_color, d_normal, any, stream); });
+    return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT, [&](auto var) {
+        constexpr int VAR = decltype(var)::value;
+        return launch_lights(any ? &shade_lights_surf_kernel<VAR, true> : &shade_lights_surf_kernel<VAR, false>, a, stream, d_color, d_normal);
+    });
 }
 
 mr_status launch_shade_accumulate_surf(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color,
                                        const float *d_normal, const float *d_weights, const uint32_t *d_pixels, unsigned long long n,
                                        const float *d_light_scale, const mr_light &light, uint32_t spp, float *d_rgb, hipStream_t stream) {
     if (n == 0) return MR_OK;
-    AccumArgs a;
-    a.m = rec::mesh_of(ds); a.rays = d_rays; a.hits = d_hits; a.weights = d_weights; a.pixels = d_pixels; a.light_scale = d_light_scale;
-    a.lt = light_args_of(light); a.spp = spp; a.inv_spp = 1.0f / (float)spp; a.n = n; a.rgb = d_rgb;
+    const AccumArgs a = accum_args_of(ds, d_rays, d_hits, d_weights, d_pixels, n, d_light_scale, light, spp, d_rgb);
     hipLaunchKernelGGL(shade_accumulate_surf_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, a, d_color, d_normal);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;

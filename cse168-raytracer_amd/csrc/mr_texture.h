@@ -98,4 +98,11 @@ __device__ __forceinline__ void diffuse_color_of(const rec::MeshMat &m, const Te
     (void)texture_color(t, tex, u, v, col);
 }
 
+// Where a shading body (mr_lights_body.h, mr_accumulate_body.h) takes a hit's diffuseColor from; the last brings the normal too
+enum ColorSource : int {
+    kColorMaterial,   // the material's own m_diffuse, read where it is used
+    kColorTexture,    // diffuse_color_of above, once per hit
+    kColorSurface,    // the surface pass's two per-ray buffers (mr_hit_surface): the colour and the bump-mapped normal
+};
+
 }  // namespace mr

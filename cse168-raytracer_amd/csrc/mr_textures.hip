@@ -3,8 +3,8 @@
 //
 //   hit_uv_kernel                 toUVCoordinates(hit.P) of every ray of a traced batch (mr_hit_uv; mr_uv.h)
 //   texture_lookup_kernel         Texture::lookup2D of one texture for a batch of coordinates (mr_texture_lookup; mr_texture.h)
-//   shade_lights_tex_kernel       shade_lights_kernel (mr_lights.hip) with the lookup: shade_lights_body<.., TEX = true>
-//   shade_accumulate_tex_kernel   shade_accumulate_kernel (mr_bounce.hip) with the lookup: shade_accumulate_body<true>
+//   shade_lights_tex_kernel       shade_lights_kernel (mr_lights.hip) with the lookup: shade_lights_body<.., kColorTexture>
+//   shade_accumulate_tex_kernel   shade_accumulate_kernel (mr_bounce.hip) with the lookup: shade_accumulate_body<kColorTexture>
 //
 // The two shading kernels are chosen by the host when the scene has a texture table (mr_scene_set_textures); a scene without
 // one runs the untextured kernels under their own names.  A lane finds its material's texture id in the table's per-material
@@ -54,26 +54,11 @@ __global__ __launch_bounds__(kBlock) void texture_lookup_kernel(TexParams t, uin
 
 template <int VAR, bool ANY>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void shade_lights_tex_kernel(LightsArgs a, TexParams t) {
-    shade_lights_body<VAR, ANY, true>(a, t);
+    shade_lights_body<VAR, ANY, kColorTexture>(a, t, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(kBlock) void shade_accumulate_tex_kernel(AccumArgs a, TexParams t) {
-    shade_accumulate_body<true>(a, t);
-}
-
-template <int VAR, bool ANY>
-mr_status launch_lights_tex_t(const LightsArgs &a, const TexParams &t, hipStream_t stream) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(&shade_lights_tex_kernel<VAR, ANY>, a.s.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL((shade_lights_tex_kernel<VAR, ANY>), dim3(trace_grid(a.s.tp.n)), dim3(kTraceBlock), lds, stream, a, t);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
-}
-
-template <int VAR>
-mr_status launch_lights_tex_a(const LightsArgs &a, const TexParams &t, bool any, hipStream_t stream) {
-    return any ? launch_lights_tex_t<VAR, true>(a, t, stream) : launch_lights_tex_t<VAR, false>(a, t, stream);
+    shade_accumulate_body<kColorTexture>(a, t, nullptr, nullptr);
 }
 
 }  // namespace
@@ -85,8 +70,10 @@ mr_status launch_shade_lights_tex(const DeviceScene &ds, const TexParams &tex, c
     if (n == 0) return MR_OK;
     const LightsArgs a = lights_args_of(ds, lights, n_lights, d_rays, d_hits, d_weights, d_pixels, n, spp, d_rgb, d_ray_rgb, d_counts);
     const bool any = flags & MR_TRACE_ANY;
-    return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT,
-                              [&](auto var) { return launch_lights_tex_a<decltype(var)::value>(a, tex, any, stream); });
+    return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT, [&](auto var) {
+        constexpr int VAR = decltype(var)::value;
+        return launch_lights(any ? &shade_lights_tex_kernel<VAR, true> : &shade_lights_tex_kernel<VAR, false>, a, stream, tex);
+    });
 }
 
 mr_status launch_shade_accumulate_tex(const DeviceScene &ds, const TexParams &tex, const mr_ray *d_rays, const mr_hit *d_hits,
@@ -94,9 +81,7 @@ mr_status launch_shade_accumulate_tex(const DeviceScene &ds, const TexParams &te
                                       const float *d_light_scale, const mr_light &light, uint32_t spp, float *d_rgb,
                                       hipStream_t stream) {
     if (n == 0) return MR_OK;
-    AccumArgs a;
-    a.m = rec::mesh_of(ds); a.rays = d_rays; a.hits = d_hits; a.weights = d_weights; a.pixels = d_pixels; a.light_scale = d_light_scale;
-    a.lt = light_args_of(light); a.spp = spp; a.inv_spp = 1.0f / (float)spp; a.n = n; a.rgb = d_rgb;
+    const AccumArgs a = accum_args_of(ds, d_rays, d_hits, d_weights, d_pixels, n, d_light_scale, light, spp, d_rgb);
     hipLaunchKernelGGL(shade_accumulate_tex_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, a, tex);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;

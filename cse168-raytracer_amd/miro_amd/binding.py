@@ -385,6 +385,11 @@ def make_camera(eye, lookat, up, fov_deg):
     return cam
 
 
+def _ptr(t):
+    """the device address of an optional tensor argument: NULL for None"""
+    return t.data_ptr() if t is not None else None
+
+
 def _stream_ptr(stream):
     if stream is None:
         return None
@@ -688,9 +693,7 @@ class Scene:
         lt.position[:] = light_pos
         lt.color[:] = color
         lt.wattage = wattage
-        _check(self.L.mr_shade_accumulate(self.h, d_rays.data_ptr(), d_hits.data_ptr(),
-                                          d_weights.data_ptr() if d_weights is not None else None,
-                                          d_pixels.data_ptr() if d_pixels is not None else None, n,
+        _check(self.L.mr_shade_accumulate(self.h, d_rays.data_ptr(), d_hits.data_ptr(), _ptr(d_weights), _ptr(d_pixels), n,
                                           d_shadow_rays.data_ptr(), d_shadow_hits.data_ptr(), d_shadow_src.data_ptr(),
                                           d_shadow_count.data_ptr(), C.byref(lt), spp, d_rgb.data_ptr(), _stream_ptr(stream)))
 
@@ -717,10 +720,8 @@ class Scene:
                      d_counts=None, stream=None):
         """mr_shade_lights: Phong::shade over the scene's light list for n traced rays in one launch; weight * L / spp is added
         to d_rgb[pixel], the un-weighted L of every ray written to d_ray_rgb (either may be None, not both)."""
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-        _check(self.L.mr_shade_lights(self.h, d_rays.data_ptr(), d_hits.data_ptr(), ptr(d_weights), ptr(d_pixels), n, spp, flags,
-                                      ptr(d_rgb), ptr(d_ray_rgb), ptr(d_counts), _stream_ptr(stream)))
+        _check(self.L.mr_shade_lights(self.h, d_rays.data_ptr(), d_hits.data_ptr(), _ptr(d_weights), _ptr(d_pixels), n, spp, flags,
+                                      _ptr(d_rgb), _ptr(d_ray_rgb), _ptr(d_counts), _stream_ptr(stream)))
 
     def shade_square_lights(self, lights, samples, d_rays, d_hits, n, d_rgb=None, seed=168, d_weights=None, d_pixels=None,
                             d_uv_in=None, spp=1, flags=0, d_ray_rgb=None, d_counts=None, stream=None):
@@ -728,14 +729,12 @@ class Scene:
         square_light_desc) with `samples` shadow rays per hit and light, in one launch; weight * L / spp is added to
         d_rgb[pixel], the un-weighted L of every ray written to d_ray_rgb (either may be None, not both).  d_uv_in: the
         caller's own pairs, 2 * n * len(lights) * samples floats."""
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
         arr = (SquareLightDesc * max(len(lights), 1))()
         for i, lt in enumerate(lights):
             arr[i] = square_light_desc(lt)
         _check(self.L.mr_shade_square_lights(self.h, arr, len(lights), samples, seed, d_rays.data_ptr(), d_hits.data_ptr(),
-                                             ptr(d_weights), ptr(d_pixels), ptr(d_uv_in), n, spp, flags, ptr(d_rgb), ptr(d_ray_rgb),
-                                             ptr(d_counts), _stream_ptr(stream)))
+                                             _ptr(d_weights), _ptr(d_pixels), _ptr(d_uv_in), n, spp, flags, _ptr(d_rgb), _ptr(d_ray_rgb),
+                                             _ptr(d_counts), _stream_ptr(stream)))
 
     def set_environment(self, bg_color=(0.0, 0.0, 0.0), pixels=None, rotation=(0.0, 0.0)):
         """mr_scene_set_environment: Scene::setBgColor, Scene::setEnvironment (pixels: a float image [H, W, 3], row 0 = the
@@ -854,10 +853,8 @@ class Scene:
     def shade_lights_surface(self, d_rays, d_hits, d_color, d_normal, n, d_rgb=None, d_weights=None, d_pixels=None, spp=1, flags=0,
                              d_ray_rgb=None, d_counts=None, stream=None):
         """mr_shade_lights_surface: shade_lights with the hit's diffuse colour and normal read from hit_surface's buffers"""
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
         _check(self.L.mr_shade_lights_surface(self.h, d_rays.data_ptr(), d_hits.data_ptr(), d_color.data_ptr(), d_normal.data_ptr(),
-                                              ptr(d_weights), ptr(d_pixels), n, spp, flags, ptr(d_rgb), ptr(d_ray_rgb), ptr(d_counts),
+                                              _ptr(d_weights), _ptr(d_pixels), n, spp, flags, _ptr(d_rgb), _ptr(d_ray_rgb), _ptr(d_counts),
                                               _stream_ptr(stream)))
 
     def shade_accumulate_surface(self, d_rays, d_hits, d_color, d_normal, d_weights, d_pixels, n, d_shadow_rays, d_shadow_hits,
@@ -868,8 +865,7 @@ class Scene:
         lt.color[:] = color
         lt.wattage = wattage
         _check(self.L.mr_shade_accumulate_surface(self.h, d_rays.data_ptr(), d_hits.data_ptr(), d_color.data_ptr(), d_normal.data_ptr(),
-                                                  d_weights.data_ptr() if d_weights is not None else None,
-                                                  d_pixels.data_ptr() if d_pixels is not None else None, n,
+                                                  _ptr(d_weights), _ptr(d_pixels), n,
                                                   d_shadow_rays.data_ptr(), d_shadow_hits.data_ptr(), d_shadow_src.data_ptr(),
                                                   d_shadow_count.data_ptr(), C.byref(lt), spp, d_rgb.data_ptr(), _stream_ptr(stream)))
 
