@@ -422,11 +422,11 @@ mr_status check_light(const char *who, uint32_t i, const uint32_t reserved[4], c
     return MR_OK;
 }
 
-// what the entry points that compute a hit's colour or normal themselves answer on a scene with a STONE or STEM texture
+// what the entry points that compute a hit's colour or normal themselves answer on a scene with a procedural texture
 mr_status refuse_procedural(const mr_scene *s, const char *who, const char *instead) {
     if (!s->tex.procedural) return MR_OK;
-    return fail(MR_ERR_STATE, "%s: the scene's texture table holds a STONE or STEM texture, whose colour and bump-mapped normal come from "
-                              "the surface pass: call mr_hit_surface, then %s", who, instead);
+    return fail(MR_ERR_STATE, "%s: the scene's texture table holds a procedural texture (STONE, STEM, PETAL, LEAF or FLOWER_CENTER), whose "
+                              "colour and normal come from the surface pass: call mr_hit_surface, then %s", who, instead);
 }
 
 // LoadedTexture::LoadedTexture (Texture.cpp:30-92) for a FIT_RGBF image of W x H pixels: m_maxIntensity and the low-res image,
@@ -1014,9 +1014,9 @@ mr_status mr_gen_path_rays(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hi
     if (kinds == 0 || (kinds & ~7u)) return fail(MR_ERR_INVALID, "kinds must be a combination of MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE");
     if (out_capacity == 0 && n > 0) return fail(MR_ERR_INVALID, "mr_gen_path_rays: out_capacity is 0 (room for 4n rays always suffices)");
     if ((kinds & 4u) && s->tex.procedural)        // MR_PATH_DIFFUSE: Ray::random bounces about N, which no generator bumps
-        return fail(MR_ERR_STATE, "mr_gen_path_rays: MR_PATH_DIFFUSE on a scene whose texture table holds a STONE or STEM texture (Ray::random "
-                                  "bounces about the un-bumped N here; mr_hit_surface and the _surface calls shade such a scene, no generator "
-                                  "reads their normal)");
+        return fail(MR_ERR_STATE, "mr_gen_path_rays: MR_PATH_DIFFUSE on a scene whose texture table holds a procedural texture (STONE, STEM, "
+                                  "PETAL, LEAF or FLOWER_CENTER; Ray::random bounces about the un-bumped N here; mr_hit_surface and the "
+                                  "_surface calls shade such a scene, no generator reads their normal)");
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_path_rays(s->dev, d_rays, d_hits, d_weights, d_pixels, d_ids, n, spp, seed, bounce, kinds, d_out_rays,
                             d_out_weights, d_out_pixels, d_out_ids, reinterpret_cast<unsigned long long *>(d_count), out_capacity,
@@ -1320,7 +1320,7 @@ mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, ui
     size_t texels = 0;
     for (uint32_t i = 0; i < n_textures; i++) {
         const mr_texture_desc &in = textures[i];
-        if (in.kind > MR_TEX_STEM) return fail(MR_ERR_INVALID, "texture %u: unknown kind %u", i, in.kind);
+        if (in.kind > MR_TEX_FLOWER_CENTER) return fail(MR_ERR_INVALID, "texture %u: unknown kind %u", i, in.kind);
         for (int k = 0; k < 5; k++)
             if (in.reserved[k] != 0) return fail(MR_ERR_INVALID, "texture %u: mr_texture_desc.reserved must be 0", i);
         if (in.kind == MR_TEX_CHECKER) {
@@ -1330,6 +1330,14 @@ mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, ui
         } else if (in.kind == MR_TEX_STONE || in.kind == MR_TEX_STEM) {
             if (!std::isfinite(in.scale)) return fail(MR_ERR_INVALID, "texture %u: the %s texture's scale must be finite", i, in.kind == MR_TEX_STONE ? "stone" : "stem");
             h.procedural = true;
+        } else if (in.kind >= MR_TEX_PETAL) {                                    // the UVW kinds: pivot in color1, radius in color2[0]
+            if (in.kind != MR_TEX_LEAF && !(in.color2[0] > 0.0f && std::isfinite(in.color2[0])))
+                return fail(MR_ERR_INVALID, "texture %u: the radius (color2[0]) of a PETAL or FLOWER_CENTER texture must be finite and greater than 0", i);
+            for (int c = 0; c < 3; c++)
+                if (!std::isfinite(in.color1[c]) || !std::isfinite(in.color2[c])) return fail(MR_ERR_INVALID, "texture %u: the pivot (color1) and color2 must be finite", i);
+            if (!std::isfinite(in.scale)) return fail(MR_ERR_INVALID, "texture %u: the scale must be finite", i);
+            h.procedural = true;
+            h.solid = true;
         } else {
             if (in.W == 0 || in.H == 0 || !in.pixels) return fail(MR_ERR_INVALID, "texture %u: an image needs pixels and W, H > 0", i);
             if (in.W > 65536u || in.H > 65536u) return fail(MR_ERR_INVALID, "texture %u: image of %u x %u pixels, at most 65536 each way", i, in.W, in.H);
@@ -1374,6 +1382,12 @@ mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, ui
         if (in.kind == MR_TEX_STONE || in.kind == MR_TEX_STEM) {                  // the scale where a checker's is
             q[0] = make_float4(bits(in.kind), 0.f, 0.f, 0.f);
             q[1] = make_float4(0.f, 0.f, 0.f, in.scale);
+            continue;
+        }
+        if (in.kind >= MR_TEX_PETAL) {                                            // pivot and scale, then the radius
+            q[0] = make_float4(bits(in.kind), 0.f, 0.f, 0.f);
+            q[1] = make_float4(in.color1[0], in.color1[1], in.color1[2], in.scale);
+            q[2] = make_float4(in.color2[0], 0.f, 0.f, 0.f);
             continue;
         }
         float max_intensity = -1e15;                                              // Texture.cpp:34,41-50
@@ -1434,6 +1448,8 @@ mr_status mr_texture_lookup(mr_scene *s, uint32_t texture, const float *d_uv, ui
     if ((st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
     uint32_t kind;
     memcpy(&kind, &s->tex.blob[3 * (size_t)texture].x, sizeof(kind));
+    if (kind >= MR_TEX_PETAL)                  // lookup2D of a Texture3D is the base class's black (Texture.h:66): nobody wants that silently
+        return fail(MR_ERR_INVALID, "mr_texture_lookup: texture %u is a UVW texture (kind %u); mr_texture_lookup3 looks it up at points", texture, kind);
     if (kind == MR_TEX_STONE || kind == MR_TEX_STEM)
         return launch_texture_lookup_proc(tex, texture, d_uv, n, d_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
     return launch_texture_lookup(tex, texture, d_uv, n, d_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
@@ -1451,6 +1467,9 @@ mr_status mr_hit_surface(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits
     TexParams tex;
     tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
     if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+    if (s->tex.solid)
+        return launch_hit_surface_solid(s->dev, tex, d_rays, d_hits, n, d_color, d_normal, reinterpret_cast<unsigned long long *>(d_counts),
+                                        static_cast<hipStream_t>(stream));
     return launch_hit_surface(s->dev, tex, d_rays, d_hits, n, d_color, d_normal, reinterpret_cast<unsigned long long *>(d_counts),
                               static_cast<hipStream_t>(stream));
 }
@@ -1498,6 +1517,27 @@ mr_status mr_texture_bump_height(mr_scene *s, uint32_t texture, const float *d_u
     uint32_t kind;
     memcpy(&kind, &s->tex.blob[3 * (size_t)texture].x, sizeof(kind));
     return launch_bump_height(kind == MR_TEX_STONE, s->tex.blob[3 * (size_t)texture + 1].w, d_uv, n, d_height, static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_texture_lookup3(mr_scene *s, uint32_t texture, const float *d_p, uint64_t n, float *d_rgb, float *d_coords, uint64_t *d_counts,
+                             void *stream) {
+    mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (s->tex.blob.empty()) return fail(MR_ERR_STATE, "mr_texture_lookup3: the scene has no textures (mr_scene_set_textures)");
+    if (texture >= s->tex.n_textures) return fail(MR_ERR_INVALID, "mr_texture_lookup3: texture %u of %u", texture, s->tex.n_textures);
+    if (!d_p || !d_rgb) return fail(MR_ERR_INVALID, "mr_texture_lookup3: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_p) & 3) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_coords) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_counts) & 7))
+        return fail(MR_ERR_INVALID, "mr_texture_lookup3: float buffers must be 4-byte aligned, counters 8-byte aligned");
+    uint32_t kind;
+    memcpy(&kind, &s->tex.blob[3 * (size_t)texture].x, sizeof(kind));
+    if (kind < MR_TEX_PETAL)
+        return fail(MR_ERR_INVALID, "mr_texture_lookup3: texture %u is a UV texture (kind %u); mr_texture_lookup looks it up at coordinates", texture, kind);
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    TexParams tex;
+    if ((st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+    return launch_texture_lookup3(tex, texture, d_p, n, d_rgb, d_coords, reinterpret_cast<unsigned long long *>(d_counts),
+                                  static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_noise_probe(uint32_t which, const float *d_in, uint64_t n, float *d_out, void *stream) {

@@ -277,11 +277,13 @@ struct HostTextures {
     uint32_t n_textures = 0, n_materials = 0;
     size_t texel_base = 0, mat_base = 0;       // offsets into blob, in float4
     std::vector<float4> blob;                  // empty: the scene has no texture table
-    bool procedural = false;                   // some texture is a STONE or a STEM: only the _surface calls shade such a scene
+    bool procedural = false;                   // some texture is a STONE, a STEM or a UVW kind: only the _surface calls shade such a scene
+    bool solid = false;                        // some texture is a UVW kind (PETAL, LEAF, FLOWER_CENTER): mr_solid.hip's surface pass
 };
 struct TexParams {                             // the table as the kernels take it
     const float4 *recs;                        // 3 per texture: (kind, W, H, first texel as bits) (color1 | max_intensity, hdr) (color2)
                                                // STONE / STEM: (kind, 0, 0, 0) (0, 0, 0, scale) (0): scale where a checker's is
+                                               // PETAL / LEAF / FLOWER_CENTER: (kind, 0, 0, 0) (pivot, scale) (radius, 0, 0, 0)
     const float4 *texels;
     const uint32_t *mat_tex;                   // per material: texture id or kNoTexture
     const float *texcoords;                    // the scene's texture coordinates (mr_uv.h), nullptr: none
@@ -317,6 +319,11 @@ mr_status launch_texture_lookup_proc(const TexParams &tex, uint32_t texture, con
                                      unsigned long long *d_counts, hipStream_t stream);
 mr_status launch_bump_height(bool stone, float scale, const float *d_uv, unsigned long long n, float *d_height, hipStream_t stream);
 mr_status launch_noise_probe(uint32_t which, const float *d_in, unsigned long long n, float *d_out, hipStream_t stream);
+// UVW textures (mr_solid.hip): launch_hit_surface for a scene whose table holds one, and lookup3D of one of them at d_p
+mr_status launch_hit_surface_solid(const DeviceScene &ds, const TexParams &tex, const mr_ray *d_rays, const mr_hit *d_hits,
+                                   unsigned long long n, float *d_color, float *d_normal, unsigned long long *d_counts, hipStream_t stream);
+mr_status launch_texture_lookup3(const TexParams &tex, uint32_t texture, const float *d_p, unsigned long long n, float *d_rgb,
+                                 float *d_coords, unsigned long long *d_counts, hipStream_t stream);
 // the first half of launch_shade_accumulate (mr_bounce.hip): Phong.cpp:97-113's light scale per ray from the traced shadow rays
 mr_status launch_light_scale(const DeviceScene &ds, const mr_ray *d_shadow_rays, const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src,
                              const unsigned long long *d_shadow_count, unsigned long long n, float *d_light_scale, hipStream_t stream);

@@ -36,6 +36,7 @@ MR_LIGHT_POINT, MR_LIGHT_DISC = 0, 1
 MR_MAX_LIGHTS = 8
 
 MR_TEX_CHECKER, MR_TEX_IMAGE, MR_TEX_STONE, MR_TEX_STEM = 0, 1, 2, 3
+MR_TEX_PETAL, MR_TEX_LEAF, MR_TEX_FLOWER_CENTER = 4, 5, 6           # the UVW kinds: looked up at the hit point itself
 MR_NOISE_PERLIN, MR_NOISE_WORLEY2 = 0, 1
 MR_MAX_TEXTURES = 16
 MR_NO_TEXTURE = MR_NO_TEXCOORD = 0xFFFFFFFF
@@ -60,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "mr_scene_set_environment", "mr_scene_get_environment", "mr_shade_environment",
     "mr_scene_set_texcoords", "mr_scene_get_texcoords", "mr_scene_set_textures", "mr_hit_uv", "mr_texture_lookup",
     "mr_hit_surface", "mr_shade_lights_surface", "mr_shade_accumulate_surface", "mr_texture_bump_height", "mr_noise_probe",
+    "mr_texture_lookup3",
     "mr_last_error", "mr_version",
 ]
 
@@ -298,6 +300,7 @@ def load_library(path=None):
     L.mr_shade_accumulate_surface.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(Light), C.c_uint32, vp, vp]
     L.mr_texture_bump_height.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp]
     L.mr_noise_probe.argtypes = [C.c_uint32, vp, C.c_uint64, vp, vp]
+    L.mr_texture_lookup3.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp]
     L.mr_photon_map_create.argtypes = [C.c_int32, C.c_uint32, C.POINTER(vp)]
     L.mr_photon_map_destroy.argtypes = [vp]
     L.mr_photon_map_store.argtypes = [vp, C.c_uint32, f32p, f32p, f32p]
@@ -801,7 +804,8 @@ class Scene:
     def set_textures(self, textures, material_texture=None):
         """mr_scene_set_textures.  textures: TextureDesc objects or dicts -- dict(color1, color2, scale) is a checker,
         dict(pixels [H, W, 3] float32 with row 0 = the bottom scanline, hdr) an image, dict(stone=scale) a StoneTexture,
-        dict(stem=scale) a StemTexture; an empty list clears the table.
+        dict(stem=scale) a StemTexture; the UVW kinds dict(petal=(pivot, radius)) a PetalTexture, dict(leaf=scale) a LeafTexture,
+        dict(flower_center=(pivot, radius)) a FlowerCenterTexture; an empty list clears the table.
         material_texture: a texture id per material (MR_NO_TEXTURE = plain Phong).  A material that names a texture becomes a
         TexturedPhong: its stored diffuse is replaced by clamp(1 - ks - kt), see miro_hip.h."""
         arr = (TextureDesc * max(len(textures), 1))()
@@ -819,6 +823,14 @@ class Scene:
             elif "stone" in t or "stem" in t:
                 arr[i].kind = MR_TEX_STONE if "stone" in t else MR_TEX_STEM
                 arr[i].scale = t["stone"] if "stone" in t else t["stem"]
+            elif "petal" in t or "flower_center" in t:
+                arr[i].kind = MR_TEX_PETAL if "petal" in t else MR_TEX_FLOWER_CENTER
+                pivot, radius = t["petal"] if "petal" in t else t["flower_center"]
+                arr[i].color1[:] = pivot
+                arr[i].color2[0] = radius
+                arr[i].scale = 1.0
+            elif "leaf" in t:
+                arr[i].kind, arr[i].scale = MR_TEX_LEAF, t["leaf"]
             else:
                 arr[i].kind = MR_TEX_CHECKER
                 arr[i].color1[:] = t.get("color1", (1.0, 1.0, 1.0))
@@ -829,7 +841,7 @@ class Scene:
             mt = np.ascontiguousarray(material_texture, dtype=np.uint32)
         _check(self.L.mr_scene_set_textures(self.h, arr, len(textures), _u32p(mt) if mt is not None else None))
         self.n_textures = len(textures)
-        self.procedural = any(arr[i].kind in (MR_TEX_STONE, MR_TEX_STEM) for i in range(len(textures)))
+        self.procedural = any(arr[i].kind >= MR_TEX_STONE for i in range(len(textures)))
 
     def hit_uv(self, d_rays, d_hits, n, d_uv, stream=None):
         """mr_hit_uv: Object::toUVCoordinates(hit.P) of n traced rays into d_uv [n, 2] ((0, 0) for a miss)"""
@@ -842,10 +854,17 @@ class Scene:
         _check(self.L.mr_texture_lookup(self.h, texture, d_uv.data_ptr(), n, d_rgb.data_ptr(),
                                         d_counts.data_ptr() if d_counts is not None else None, _stream_ptr(stream)))
 
+    def texture_lookup3(self, texture, d_p, n, d_rgb, d_coords=None, d_counts=None, stream=None):
+        """mr_texture_lookup3: Texture::lookup3D of the UVW texture `texture` at the points d_p [n, 3] into d_rgb [n, 3]; d_coords
+        [n, 3] receives (u, v, dist) of a PETAL (not written for the other kinds); d_counts[0] += the lookups the reference
+        leaves undefined"""
+        _check(self.L.mr_texture_lookup3(self.h, texture, d_p.data_ptr(), n, d_rgb.data_ptr(), _ptr(d_coords), _ptr(d_counts),
+                                         _stream_ptr(stream)))
+
     def hit_surface(self, d_rays, d_hits, n, d_color, d_normal, d_counts=None, stream=None):
-        """mr_hit_surface: for every ray that hit, diffuseColor (Phong.cpp:51-56; every texture kind) into d_color [n, 3] and
-        the normal as Scene::trace leaves it (bump-mapped on a STONE material, normalised; Scene.cpp:234-263) into d_normal
-        [n, 3]; a miss leaves its rows untouched.  d_counts[0] += the hits whose lookup the reference leaves undefined."""
+        """mr_hit_surface: for every ray that hit, diffuseColor (Phong.cpp:51-56; every texture kind, a UVW kind at the hit point
+        itself) into d_color [n, 3] and the normal as Scene::trace leaves it (bump-mapped on a STONE material, normalised;
+        Scene.cpp:234-263) into d_normal [n, 3]; a miss leaves its rows untouched.  d_counts[0] += the hits whose lookup the reference leaves undefined."""
         _check(self.L.mr_hit_surface(self.h, d_rays.data_ptr() if d_rays is not None else None, d_hits.data_ptr(), n,
                                      d_color.data_ptr(), d_normal.data_ptr(), d_counts.data_ptr() if d_counts is not None else None,
                                      _stream_ptr(stream)))

@@ -335,7 +335,8 @@ class FrameRenderer:
         A scene with a texture table (Scene.set_textures) takes the batched path for every level, whatever `fused` says
         (fused="auto" included): mr_trace_level shades without the texture lookup and refuses such a scene; the batched
         path's mr_shade_accumulate / mr_shade_lights look the diffuse colour up (Phong.cpp:51-56).
-        A scene whose table holds a procedural texture (a StoneTexture or a StemTexture) adds one launch per level: trace ->
+        A scene whose table holds a procedural texture (a StoneTexture or a StemTexture, or one of the UVW kinds PetalTexture,
+        LeafTexture, FlowerCenterTexture, which are looked up at the hit point itself) adds one launch per level: trace ->
         mr_hit_surface (diffuse colour and bump-mapped normal of every hit into two [n, 3] buffers sized to the level's queue)
         -> mr_shade_lights_surface (light list) or the shadow batch and mr_shade_accumulate_surface (single light) -> the
         generators.  Square lights and MR_PATH_DIFFUSE children are refused on such a scene (no _surface form; Ray::random

@@ -214,6 +214,53 @@ SCENES["photon_room_two_lights"] = dict(
             dict(position=SCENES["photon_room"]["light"], color=(1.0, 1.0, 1.0), wattage=SCENES["photon_room"]["wattage"])])
 
 
+def flower_scene():
+    """makeTestPetalScene (assignment3.cpp:34-122), the reference's final scene: a flower under a DirectionalAreaLight(7) at
+    (50, 50, 40) facing the origin, wattage 4, camera (2, 4.4, 16.8) -> (3, 0, 4), fov 30.  Its four materials are
+    TexturedPhongs (:93-102): PetalTexture(pivot 0, radius 7) with ks = kt = 0, shininess 500, index 1.5 on models/Petals2.obj;
+    StemTexture(30) on Stem.obj; LeafTexture(scale 1) on Leaf.obj; FlowerCenterTexture(pivot (-0.1, -0.35, 0), radius 1.1).
+    The models are loaded with the identity, which is what addFlowerModel composes for position 0, rotation 0, scale 1.
+
+    What differs, because the reference tree does not hold it: FlowerCenter.obj and WaterDropsMany.obj are missing -- the centre
+    is a sphere of radius 1.1 at its texture's pivot, the drops are left out; gfx/forrest_salzburg02_big.hdr is missing -- a ray
+    that misses gets setBgColor(1) (:52).  The three models are stored xz-compressed (tests/golden/models/*.obj.xz, the
+    reference's files byte for byte); populate() unpacks them into the cache directory first.
+
+    Returns a description for populate() with, besides the usual keys, `textures` / `material_texture` for Scene.set_textures,
+    `lights` (the disc light) and `environment` (the arguments of Scene.set_environment); flower_setup() applies them."""
+    pos = np.asarray([50.0, 50.0, 40.0], np.float32)
+    nrm = -pos                                                   # :79-81: -position, normalize() = *= 1 / length
+    nrm = nrm * (np.float32(1) / np.sqrt(np.float32(np.float32(nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2])))
+    n_petals, n_stem, n_leaf = 14784, 1664, 6144                 # triangles of the three models
+    zero = (0.0, 0.0, 0.0)
+    centre = (-0.1, -0.35, 0.0)
+    return dict(
+        models=[("Petals2.obj.xz", None), ("Stem.obj.xz", None), ("Leaf.obj.xz", None)], floor=None,
+        objects=[("sphere", centre, 1.1)],
+        # (kd, ks, kt, shininess, index): TexturedPhong's defaults are ks = kt = 0, shininess 1, index 1 (Texture.h:305-309)
+        materials=[((1.0, 1.0, 1.0), zero, zero, 500.0, 1.5), ((1.0, 1.0, 1.0), zero, zero, 1.0, 1.0),
+                   ((1.0, 1.0, 1.0), zero, zero, 1.0, 1.0), ((1.0, 1.0, 1.0), zero, zero, 1.0, 1.0)],
+        prim_material=[0] * n_petals + [1] * n_stem + [2] * n_leaf + [3],
+        textures=[dict(petal=(zero, 7.0)), dict(stem=30.0), dict(leaf=1.0), dict(flower_center=(centre, 1.1))],
+        material_texture=[0, 1, 2, 3],
+        lights=[dict(position=tuple(float(c) for c in pos), normal=tuple(float(c) for c in nrm), color=(1.0, 1.0, 1.0), wattage=4.0,
+                     radius=7.0)],
+        environment=dict(bg_color=(1.0, 1.0, 1.0)),
+        eye=(2.0, 4.4, 16.8), lookat=(3.0, 0.0, 4.0), up=UP, fov=30.0, light=tuple(float(c) for c in pos), wattage=4.0)
+
+
+def flower_setup(scene, desc=None, leaf_size=4):
+    """populate() a miro_amd.Scene with flower_scene(), build it, and set its materials, textures, lights and environment"""
+    desc = desc or flower_scene()
+    populate(scene, desc)
+    scene.build(leaf_size)
+    scene.set_materials(desc["materials"], desc["prim_material"])
+    scene.set_textures(desc["textures"], desc["material_texture"])
+    scene.set_lights(desc["lights"])
+    scene.set_environment(**desc["environment"])
+    return desc
+
+
 def sponza_label():
     p = os.environ.get("MIRO_SPONZA_OBJ", "")
     return "sponza" if p and os.path.exists(p) else "sponza-standin"
@@ -224,12 +271,29 @@ def sponza_path(cache_dir=None):
     p = os.environ.get("MIRO_SPONZA_OBJ", "")
     if p and os.path.exists(p):
         return p
-    cache_dir = cache_dir or os.environ.get("MIRO_CACHE_DIR") or os.path.join("/tmp", "miro_amd_cache_%d" % os.getuid())
-    os.makedirs(cache_dir, exist_ok=True)
-    path = os.path.join(cache_dir, "atrium_standin_v3.obj")
+    path = os.path.join(_cache_dir(cache_dir), "atrium_standin_v3.obj")
     if not os.path.exists(path):
         tmp = path + ".%d.tmp" % os.getpid()
         write_obj(tmp, *atrium_mesh())
+        os.replace(tmp, path)
+    return path
+
+
+def _cache_dir(cache_dir=None):
+    cache_dir = cache_dir or os.environ.get("MIRO_CACHE_DIR") or os.path.join("/tmp", "miro_amd_cache_%d" % os.getuid())
+    os.makedirs(cache_dir, exist_ok=True)
+    return cache_dir
+
+
+def unpacked_model(name, cache_dir=None):
+    """Path of the OBJ that tests/golden/models/<name> (an .obj.xz) holds, unpacked into the cache directory once"""
+    import lzma
+    src = _model(name)
+    path = os.path.join(_cache_dir(cache_dir), "%s_%d" % (name[:-3], os.path.getsize(src)))
+    if not os.path.exists(path):
+        tmp = path + ".%d.tmp" % os.getpid()
+        with lzma.open(src, "rb") as fin, open(tmp, "wb") as fout:
+            fout.write(fin.read())
         os.replace(tmp, path)
     return path
 
@@ -240,7 +304,12 @@ def populate(scene, desc, cache_dir=None):
         desc = SCENES[desc]
     n = 0
     for name, ctm in desc["models"]:
-        path = sponza_path(cache_dir) if name == "@sponza" else (name if os.path.isabs(name) else _model(name))
+        if name == "@sponza":
+            path = sponza_path(cache_dir)
+        elif name.endswith(".xz"):
+            path = unpacked_model(name, cache_dir)
+        else:
+            path = name if os.path.isabs(name) else _model(name)
         n += scene.add_obj(path, ctm)
     if desc.get("floor") is not None:
         f = np.asarray(desc["floor"], np.float32).reshape(9)

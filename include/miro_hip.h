@@ -638,15 +638,43 @@ mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_h
  *                   that is NaN or reaches 2^30 after scaling fails int(floor()) there: DEFINED as noise 0 here and counted.
  *                   powf / exp are the series of miro_math.h, where the reference calls libm; pow(f1f0, 2) (Texture.cpp:424)
  *                   is the float product of the C++03 std::pow(float, int).
+ *   The three UVW kinds are the reference's Texture3D classes.  Phong::shade looks them up at the hit point itself,
+ *   diffuse3D(tex_coord3d_t(hit.P.x, hit.P.y, hit.P.z)) (Phong.cpp:53-56): no object mapping and no texture coordinates are
+ *   involved, and Scene::trace bump-maps UV materials only (Scene.cpp:238), so the normal stays the geometric one, normalised,
+ *   and ks / kt are not restricted.  They reuse the struct's fields: color1 = the pivot, color2[0] = the radius.
+ *   MR_TEX_PETAL    PetalTexture(pivot, radius, scale) (Texture.h:171-181, Texture.cpp:442-505): p = normalize(P - pivot), dist =
+ *                   |P - pivot| / radius, v = acos(-p.y) / PI, u = acos(p.x) / (2 PI), mirrored to 1 - u unless p.z < 0; two Perlin
+ *                   turbulences at (u, v / 4) (10 octaves) and (u, v) (25 octaves) blend a base and a tip colour with a highlight
+ *                   and a depression.  `scale` is not read (lookup3D never reads m_scale).
+ *   MR_TEX_LEAF     LeafTexture(pivot, direction, scale) (Texture.h:216-251): StemTexture::lookup2D's body at (P.x * scale,
+ *                   P.y * scale).  Only `scale` is read: pivot and direction are constructor arguments the lookup never uses.
+ *   MR_TEX_FLOWER_CENTER  FlowerCenterTexture(pivot, radius, scale) (Texture.h:253-277): fraction = clamp(powf(|P - pivot| /
+ *                   radius, 30), 0, 1) blends (0.31, 0.18) into (0.92, 0.71), blue 0.1f.  `scale` is not read.
+ *                   What counts as undefined in a PETAL lookup: its 25-octave turbulence reaches the frequency 4 * 3^24, about
+ *                   1.1e12, far beyond int(floor()).  An evaluation ALL of whose coordinates are whole numbers (every float from
+ *                   2^23 on is one, and z is 0) is +-0 in the reference whatever the conversion yields -- the fractions are 0, so
+ *                   every grad is +-0 and every lerp weight 0: it contributes 0 and is NOT counted.  An evaluation with a coordinate
+ *                   that is NaN or reaches 2^30 and another that is not whole is undefined there: noise 0 here, and counted (about
+ *                   0.4 % of the lookups at uniform (u, v)).  P == pivot gives NaN coordinates, an acos argument a rounding above 1
+ *                   gives NaN: both propagate as the reference's arithmetic has them and are counted by the same rule.  acos and
+ *                   powf are the series of miro_math.h.  CloudTexture is not a kind: it overloads lookup2D(const tex_coord3d_t &)
+ *                   instead of overriding lookup3D (Texture.h:152), so as a material it is the base class's black.
  * Errors (MR_ERR_INVALID, the earlier table stays): NULL scene, n_textures > MR_MAX_TEXTURES, NULL list, unknown kind, non-zero
- *   reserved word, non-finite field or pixel, W or H of 0 (or above 65536), NULL pixels, hdr > 1, a texture id >= n_textures, a
- *   material_texture given without a material table, a STONE texture named by a material with a non-zero ks or kt.
+ *   reserved word, non-finite field (also one the kind does not read) or pixel, W or H of 0 (or above 65536), NULL pixels,
+ *   hdr > 1, a texture id >= n_textures, a material_texture given without a material table, a STONE texture named by a material
+ *   with a non-zero ks or kt, a PETAL or FLOWER_CENTER texture whose radius is not finite and greater than 0.
  *
  * mr_hit_uv -- toUVCoordinates(hit.P) of n traced rays: d_uv receives 2n floats, (0, 0) for a miss.  d_rays may be NULL for
  *   scenes of triangles only.  mr_texture_lookup -- lookup2D of texture `texture` at n coordinates (d_uv: 2n floats): d_rgb
  *   receives 3n floats; d_counts (may be NULL): [0] += undefined lookups, not zeroed.  Both only enqueue on `stream`.
  *
- *   mr_texture_lookup serves all four kinds.
+ *   mr_texture_lookup serves the four UV kinds; on a UVW kind it returns MR_ERR_INVALID naming mr_texture_lookup3 (lookup2D of a
+ *   Texture3D is the base class's black, Texture.h:66).
+ * mr_texture_lookup3 -- Texture::lookup3D of the UVW texture `texture` at n points (d_p: 3n floats): d_rgb receives 3n floats.
+ *   d_coords (may be NULL): for a PETAL, (u, v, dist) of Texture.cpp:465-492 per point, 3n floats -- the coordinates the noise
+ *   is evaluated at and the blend factor; not written for the other two kinds.  d_counts (may be NULL): [0] += the lookups the
+ *   reference leaves undefined (above), not zeroed.  MR_ERR_INVALID naming mr_texture_lookup on a UV kind.  Only enqueues on
+ *   `stream`.
  *
  * Entry points that shade without the lookup refuse a scene with a texture table (MR_ERR_STATE, naming the batched calls):
  * mr_render_direct, mr_shade_direct, mr_trace_level, and mr_trace_photons (its roulette reads diffuse2D, Scene.cpp:545-551).
@@ -655,33 +683,38 @@ mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_h
  * A STONE or STEM lookup is too heavy to sit inside a kernel that also traverses (five Worley searches and up to 33 Perlin
  * evaluations per stone hit), so a scene whose table holds one is shaded in two steps: mr_hit_surface, then a _surface call.
  * mr_hit_surface -- for every ray of a traced batch that hit: d_color[3k..] = diffuseColor of Phong.cpp:51-56 (m_diffuse of a
- *   plain Phong, Texture::lookup2D at Object::toUVCoordinates(hit.P) of a TexturedPhong, all four kinds) and d_normal[3k..] =
+ *   plain Phong, Texture::lookup2D at Object::toUVCoordinates(hit.P) of a TexturedPhong with a UV texture, Texture::lookup3D at
+ *   hit.P itself with a UVW texture; all seven kinds in any mixture) and d_normal[3k..] =
  *   HitInfo::N as Scene::trace leaves it (Scene.cpp:234-263): on a STONE material four bumpHeight2D samples at (u -+ delta, v),
  *   (u, v -+ delta) with delta = (float)0.0001, dx and dy by central differences, randomVec by the largest component of N, t1 =
  *   cross(N, randomVec), N += dx * cross(N, t1) - dy * cross(N, cross(N, t1)), then normalize(); on every other material the
- *   normalisation alone (the zero perturbation is skipped).  A ray that missed leaves its six floats untouched.  Works on any
+ *   normalisation alone (the zero perturbation is skipped; a UVW material gets neither toUVCoordinates nor the bump).  A scene
+ *   whose table holds a UVW kind runs the pass of csrc/mr_solid.hip, every other scene the one it ran before.  A ray that missed leaves its six floats untouched.  Works on any
  *   scene, with or without a texture table.  d_counts (may be NULL): [0] += hits whose lookup the reference leaves undefined,
  *   not zeroed.  d_rays may be NULL for scenes of triangles only.
  * mr_shade_lights_surface, mr_shade_accumulate_surface -- mr_shade_lights (Phong.cpp:44-150 over the light list) and
  *   mr_shade_accumulate with the hit's diffuseColor and N read from d_color / d_normal (24 bytes per ray) instead of computed;
  *   every other argument, check and output is the plain call's.  They look nothing up, so they run on any scene.
  * mr_texture_bump_height -- Texture::bumpHeight2D (Texture.h:63; StoneTexture's: Texture.cpp:358-393) of texture `texture` at n
- *   coordinates (d_uv: 2n floats) into d_height (n floats): 0 for every kind but STONE.
+ *   coordinates (d_uv: 2n floats) into d_height (n floats): 0 for every kind but STONE, the UVW kinds included.
  * mr_noise_probe -- the noise functions themselves, needs no scene: MR_NOISE_PERLIN reads xyz triples (3n floats) and writes
  *   PerlinNoise::noise (Perlin.h:16-51), n floats; MR_NOISE_WORLEY2 reads xy pairs (2n floats) and writes, per point, F[3] as
  *   floats then ID[3] as uint32 of WorleyNoise::noise2D(at, 3, ...) (Worley.cpp:95-173), 6n words.  Runs on the current device.
  * All five only enqueue on `stream`.
  *
- * On a scene whose table holds a STONE or STEM texture the calls that would compute the colour or the normal themselves
+ * On a scene whose table holds a STONE, STEM or UVW texture the calls that would compute the colour or the normal themselves
  * return MR_ERR_STATE with a message naming the _surface calls: mr_shade_lights, mr_shade_accumulate, mr_shade_square_lights,
- * and mr_gen_path_rays with MR_PATH_DIFFUSE (Ray::random bounces about N).  A scene without them runs the kernels it ran before. */
-enum { MR_TEX_CHECKER = 0, MR_TEX_IMAGE = 1, MR_TEX_STONE = 2, MR_TEX_STEM = 3 };
+ * and mr_gen_path_rays with MR_PATH_DIFFUSE (Ray::random bounces about N).  The first three have no lookup3D; the last would be
+ * right on a UVW scene, whose normals nothing bumps, and is refused only to keep the single rule "a scene with a procedural
+ * texture goes through the surface pass".  A scene without them runs the kernels it ran before. */
+enum { MR_TEX_CHECKER = 0, MR_TEX_IMAGE = 1, MR_TEX_STONE = 2, MR_TEX_STEM = 3, MR_TEX_PETAL = 4, MR_TEX_LEAF = 5, MR_TEX_FLOWER_CENTER = 6 };
 #define MR_MAX_TEXTURES 16
 #define MR_NO_TEXTURE  0xFFFFFFFFu
 #define MR_NO_TEXCOORD 0xFFFFFFFFu
 typedef struct mr_texture_desc {
     uint32_t kind;
-    float color1[3], color2[3], scale;                /* MR_TEX_CHECKER; MR_TEX_STONE and MR_TEX_STEM read scale alone */
+    float color1[3], color2[3], scale;                /* MR_TEX_CHECKER; MR_TEX_STONE, MR_TEX_STEM and MR_TEX_LEAF read scale alone;
+                                                         MR_TEX_PETAL and MR_TEX_FLOWER_CENTER: color1 = pivot, color2[0] = radius */
     const float *pixels;                              /* MR_TEX_IMAGE: host, W*H*3 floats, row 0 = bottom */
     uint32_t W, H, hdr;
     uint32_t reserved[5];                             /* must be 0 */
@@ -693,6 +726,8 @@ mr_status mr_scene_set_textures(mr_scene *scene, const mr_texture_desc *textures
 mr_status mr_hit_uv(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, uint64_t n, float *d_uv, void *stream);
 mr_status mr_texture_lookup(mr_scene *scene, uint32_t texture, const float *d_uv, uint64_t n, float *d_rgb, uint64_t *d_counts,
                             void *stream);
+mr_status mr_texture_lookup3(mr_scene *scene, uint32_t texture, const float *d_p, uint64_t n, float *d_rgb, float *d_coords,
+                             uint64_t *d_counts, void *stream);
 enum { MR_NOISE_PERLIN = 0, MR_NOISE_WORLEY2 = 1 };
 mr_status mr_hit_surface(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, uint64_t n, float *d_color, float *d_normal,
                          uint64_t *d_counts, void *stream);

@@ -54,7 +54,20 @@ def assert_inside_envelope(cur, record, also_main=True):
         assert c["waves_per_simd"] >= max(r["waves_per_simd"], worst["waves"]), (name, c, r)
 
 
+def write_unit(unit):
+    """`--write-unit UNIT`: records the kernels of a REMARK_UNITS unit as tests/golden/kernel_budget_<UNIT minus "mr_">.json, under
+    the same condition as --write"""
+    cur = unit_kernels(unit)
+    path = os.path.join(ROOT, "tests", "golden", "kernel_budget_%s.json" % unit.replace("mr_", "", 1))
+    json.dump({"note": "recorded from a build whose GPU run of the unit's test file was green; regenerate with tools/kernel_budget.py "
+                       "--write-unit %s after re-verifying on the GPU" % unit, "kernels": cur}, open(path, "w"), indent=1, sort_keys=True)
+    print("wrote %d kernels to %s" % (len(cur), path))
+
+
 if __name__ == "__main__":
+    if "--write-unit" in sys.argv:
+        write_unit(sys.argv[sys.argv.index("--write-unit") + 1])
+        sys.exit(0)
     cur = current()
     if "--write" in sys.argv:
         json.dump({"note": "recorded from a build whose GPU suite was green; regenerate with tools/kernel_budget.py --write after "
