@@ -380,7 +380,10 @@ mr_status require_device(const mr_scene *s) {
     return MR_OK;
 }
 
+}  // namespace
+
 // the texture table on the device, uploaded on `stream` by the first shading call after a change; `p`: as the kernels take it
+// (declared in mr_internal.h: mr_trace_photons_surface in mr_photon_trace.cpp takes it too)
 mr_status texture_params(mr_scene *s, hipStream_t stream, TexParams &p) {
     const HostTextures &t = s->tex;
     if (s->tex_dirty) {
@@ -397,6 +400,8 @@ mr_status texture_params(mr_scene *s, hipStream_t stream, TexParams &p) {
     p.ti = s->dev.ti;
     return MR_OK;
 }
+
+namespace {
 
 // what the entry points that shade without the texture lookup answer on a scene with a texture table
 mr_status refuse_textured(const mr_scene *s, const char *who) {

@@ -396,6 +396,15 @@ constexpr uint32_t kPhotonMaxDepth = 32;
 // need: stores still missing to the target (> 0)
 mr_status launch_photon_round(const DeviceScene &ds, const PhotonWalkLight &lt, uint32_t seed, uint32_t caustic, uint32_t max_depth,
                               uint32_t first, uint32_t count, unsigned long long need, const PhotonRoundBuffers &b, hipStream_t stream);
+// the same round on the kernel of mr_photon_walk_surface.hip: the colour and the normal of every hit are the surface pass's
+// (tex: the scene's table, recs / mat_tex nullptr without one)
+mr_status launch_photon_round_surface(const DeviceScene &ds, const TexParams &tex, const PhotonWalkLight &lt, uint32_t seed, uint32_t caustic,
+                                      uint32_t max_depth, uint32_t first, uint32_t count, unsigned long long need, const PhotonRoundBuffers &b,
+                                      hipStream_t stream);
+// what follows either walk (mr_photon_walk.hip): photon_scan_kernel and photon_compact_kernel over the round's words and slots
+mr_status launch_photon_round_finish(uint32_t max_depth, uint32_t count, unsigned long long need, const PhotonRoundBuffers &b, hipStream_t stream);
+// the texture table on the device, uploaded on `stream` by the first call after a change (mr_api.cpp); `p`: as the kernels take it
+mr_status texture_params(mr_scene *s, hipStream_t stream, TexParams &p);
 // what mr_trace_photons needs to know of a map (the struct lives in mr_photon.cpp)
 int32_t photon_map_device(const mr_photon_map *m);
 bool photon_map_balanced(const mr_photon_map *m);

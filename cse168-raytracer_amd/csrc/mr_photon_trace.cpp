@@ -1,10 +1,14 @@
-// mr_photon_trace.cpp -- host side of mr_trace_photons: Scene::tracePhotons / traceCausticPhotons for one
-// DirectionalAreaLight (Scene.cpp:351-472).  The photons are walked on the device (mr_photon_walk.hip) in rounds of
+// mr_photon_trace.cpp -- host side of mr_trace_photons and mr_trace_photons_surface: Scene::tracePhotons /
+// traceCausticPhotons for one DirectionalAreaLight (Scene.cpp:351-472).  The photons are walked on the device
+// (mr_photon_walk.hip, or mr_photon_walk_surface.hip with the surface pass's colour and normal at every hit) in rounds of
 // emissions; after each round the host reads one small header, copies the round's compacted records and pushes them
 // through mr_photon_map_store, until the target is reached or max_emissions are spent; then scale_photon_power(1/emitted).
 //
 // The result does not depend on the round size: a round's header says how many of its emissions count (up to and including
 // the one whose stores reach the target), and only their records -- in emission order -- are taken.
+//
+// Both entry points run trace_photons below; they differ in the round launcher they hand it (and in what they ask of the
+// scene's texture table before).
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -45,31 +49,29 @@ mr_status allocate(Buffers &b, uint32_t capacity, uint32_t max_depth) {
     return MR_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-mr_status mr_trace_photons(mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, mr_photon_trace_result *result,
-                           mr_photon_record *d_records, uint64_t records_capacity, void *stream_) {
-    if (!s || !map || !desc) return fail(MR_ERR_INVALID, "mr_trace_photons: NULL scene, map or desc");
-    if (desc->max_emissions == 0) return fail(MR_ERR_INVALID, "mr_trace_photons: max_emissions is 0 (the hard stop is required)");
+// launch(light, max_depth, first, count, need, buffers): one round's walk and bookkeeping kernels on `stream`
+template <typename Launch>
+mr_status trace_photons(const char *who, bool surface, mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc,
+                        mr_photon_trace_result *result, mr_photon_record *d_records, uint64_t records_capacity, hipStream_t stream, Launch &&launch) {
+    if (!s || !map || !desc) return fail(MR_ERR_INVALID, "%s: NULL scene, map or desc", who);
+    if (desc->max_emissions == 0) return fail(MR_ERR_INVALID, "%s: max_emissions is 0 (the hard stop is required)", who);
     const mr_disc_light &lt = desc->light;
-    if (!(lt.radius > 0.0f) || !std::isfinite(lt.radius)) return fail(MR_ERR_INVALID, "mr_trace_photons: the light's radius must be positive");
-    if (lt.normal[0] == 0.0f && lt.normal[1] == 0.0f && lt.normal[2] == 0.0f) return fail(MR_ERR_INVALID, "mr_trace_photons: the light's normal is zero");
+    if (!(lt.radius > 0.0f) || !std::isfinite(lt.radius)) return fail(MR_ERR_INVALID, "%s: the light's radius must be positive", who);
+    if (lt.normal[0] == 0.0f && lt.normal[1] == 0.0f && lt.normal[2] == 0.0f) return fail(MR_ERR_INVALID, "%s: the light's normal is zero", who);
     for (int c = 0; c < 3; c++)
-        if (!std::isfinite(lt.normal[c]) || !std::isfinite(lt.position[c])) return fail(MR_ERR_INVALID, "mr_trace_photons: the light's position and normal must be finite");
-    if (desc->max_depth > kPhotonMaxDepth) return fail(MR_ERR_INVALID, "mr_trace_photons: max_depth is at most %u", kPhotonMaxDepth);
+        if (!std::isfinite(lt.normal[c]) || !std::isfinite(lt.position[c])) return fail(MR_ERR_INVALID, "%s: the light's position and normal must be finite", who);
+    if (desc->max_depth > kPhotonMaxDepth) return fail(MR_ERR_INVALID, "%s: max_depth is at most %u", who, kPhotonMaxDepth);
     for (int k = 0; k < 6; k++)
         if (desc->reserved[k] != 0) return fail(MR_ERR_INVALID, "mr_photon_trace_desc.reserved must be 0");
-    if (reinterpret_cast<uintptr_t>(d_records) & 3) return fail(MR_ERR_INVALID, "mr_trace_photons: d_records must be 4-byte aligned");
-    if (s->device != photon_map_device(map)) return fail(MR_ERR_INVALID, "mr_trace_photons: scene on device %d, photon map on device %d", s->device, photon_map_device(map));
+    if (reinterpret_cast<uintptr_t>(d_records) & 3) return fail(MR_ERR_INVALID, "%s: d_records must be 4-byte aligned", who);
+    if (s->device != photon_map_device(map)) return fail(MR_ERR_INVALID, "%s: scene on device %d, photon map on device %d", who, s->device, photon_map_device(map));
     if (!s->built) return fail(MR_ERR_STATE, "mr_bvh_build has not been called on this scene");
     if (!s->on_device) return fail(MR_ERR_STATE, "scene was built host_only: nothing is resident on a device and there is no CPU fallback");
-    if (!s->tex.blob.empty())                // the roulette reads diffuse2D (Scene.cpp:545-551); the walk has no texture lookup
-        return fail(MR_ERR_STATE, "mr_trace_photons: the scene has a texture table (mr_scene_set_textures) and the photon walk's roulette "
-                                  "has no texture lookup; trace photons before setting textures, or clear them (n_textures = 0)");
+    if (!surface && !s->tex.blob.empty())    // the roulette reads diffuse2D (Scene.cpp:545-551); the plain walk has no texture lookup
+        return fail(MR_ERR_STATE, "mr_trace_photons: the scene has a texture table (mr_scene_set_textures) and the plain photon walk's roulette "
+                                  "has no texture lookup; call mr_trace_photons_surface, whose walk looks textures up, or trace photons "
+                                  "before setting textures, or clear them (n_textures = 0)");
     if (photon_map_balanced(map)) return fail(MR_ERR_STATE, "photon map is immutable after mr_photon_map_balance");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     g_timing = Timing();
 
     const uint32_t max_depth = desc->max_depth ? desc->max_depth : 5u;          // TRACE_DEPTH_PHOTONS (Miro.h:14)
@@ -110,15 +112,14 @@ mr_status mr_trace_photons(mr_scene *s, mr_photon_map *map, const mr_photon_trac
             if (count > b.capacity) count = b.capacity;
             if (count > desc->max_emissions - res.emitted) count = desc->max_emissions - res.emitted;
             auto t0 = std::chrono::steady_clock::now();
-            st = launch_photon_round(s->dev, wl, desc->seed, desc->caustic ? 1u : 0u, max_depth, (uint32_t)res.emitted, (uint32_t)count,
-                                     desc->target - res.stored, b, stream);
+            st = launch(wl, max_depth, (uint32_t)res.emitted, (uint32_t)count, (unsigned long long)(desc->target - res.stored), b);
             if (st != MR_OK) return st;
             PhotonRoundHeader hdr;
             MR_HIP_CHECK(hipMemcpyAsync(&hdr, b.header, sizeof(hdr), hipMemcpyDeviceToHost, stream));
             MR_HIP_CHECK(hipStreamSynchronize(stream));
             g_timing.kernel_ms += ms_since(t0);
             if (hdr.emitted > count || hdr.stored > (uint64_t)count * max_depth)
-                return fail(MR_ERR_HIP, "mr_trace_photons: inconsistent round header (%u emissions of %llu)", hdr.emitted, (unsigned long long)count);
+                return fail(MR_ERR_HIP, "%s: inconsistent round header (%u emissions of %llu)", who, hdr.emitted, (unsigned long long)count);
 
             t0 = std::chrono::steady_clock::now();
             recs.resize(hdr.stored);
@@ -151,6 +152,36 @@ mr_status mr_trace_photons(mr_scene *s, mr_photon_map *map, const mr_photon_trac
     }
     if (result) *result = res;
     return MR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+mr_status mr_trace_photons(mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, mr_photon_trace_result *result,
+                           mr_photon_record *d_records, uint64_t records_capacity, void *stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return trace_photons("mr_trace_photons", false, s, map, desc, result, d_records, records_capacity, stream,
+                         [&](const PhotonWalkLight &wl, uint32_t max_depth, uint32_t first, uint32_t count, unsigned long long need, const PhotonRoundBuffers &b) {
+                             return launch_photon_round(s->dev, wl, desc->seed, desc->caustic ? 1u : 0u, max_depth, first, count, need, b, stream);
+                         });
+}
+
+mr_status mr_trace_photons_surface(mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, mr_photon_trace_result *result,
+                                   mr_photon_record *d_records, uint64_t records_capacity, void *stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    bool have_table = false;                 // the table is uploaded / refreshed by the first round, as mr_hit_surface does it
+    TexParams tex;
+    return trace_photons("mr_trace_photons_surface", true, s, map, desc, result, d_records, records_capacity, stream,
+                         [&](const PhotonWalkLight &wl, uint32_t max_depth, uint32_t first, uint32_t count, unsigned long long need, const PhotonRoundBuffers &b) {
+                             if (!have_table) {
+                                 tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
+                                 mr_status st = s->tex.blob.empty() ? MR_OK : texture_params(s, stream, tex);
+                                 if (st != MR_OK) return st;
+                                 have_table = true;
+                             }
+                             return launch_photon_round_surface(s->dev, tex, wl, desc->seed, desc->caustic ? 1u : 0u, max_depth, first, count, need, b, stream);
+                         });
 }
 
 mr_status mr_trace_photons_timing(double *kernel_ms, double *readback_ms, double *store_ms) {

@@ -64,6 +64,8 @@ EXPORTED_SYMBOLS = [
     "mr_texture_lookup3",
     "mr_last_error", "mr_version",
 ]
+# every symbol include/miro_hip_surface.h declares (entry points added after miro_hip.h's own list was held at 69 names)
+SURFACE_SYMBOLS = ["mr_trace_photons_surface"]
 
 
 class MiroError(RuntimeError):
@@ -280,6 +282,7 @@ def load_library(path=None):
     L.mr_trace_level.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mr_final_gather.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.mr_trace_photons.argtypes = [vp, vp, C.POINTER(PhotonTraceDesc), C.POINTER(PhotonTraceResult), vp, C.c_uint64, vp]
+    L.mr_trace_photons_surface.argtypes = L.mr_trace_photons.argtypes
     L.mr_trace_photons_timing.argtypes = [C.POINTER(C.c_double)] * 3
     L.mr_scene_set_lights.argtypes = [vp, C.POINTER(LightDesc), C.c_uint32]
     L.mr_shade_lights.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -311,7 +314,10 @@ def load_library(path=None):
     L.mr_irradiance_estimate.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, vp, vp, vp, vp]
     L.mr_photon_map_count_stats.argtypes = [vp, C.c_int32]
     L.mr_photon_map_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int32]
-    for name in EXPORTED_SYMBOLS:
+    for name in SURFACE_SYMBOLS:
+        if not hasattr(L, name):
+            raise OSError("%s does not export %s" % (path, name))
+    for name in EXPORTED_SYMBOLS + SURFACE_SYMBOLS:
         if hasattr(L, name) and getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = C.c_int32
     _lib = L
@@ -651,9 +657,10 @@ class Scene:
                                       _stream_ptr(stream)))
 
     def trace_photons(self, photon_map, light, target, max_emissions, caustic=False, seed=168, max_depth=0, round_emissions=0,
-                      d_records=None, records_capacity=None, stream=None):
+                      d_records=None, records_capacity=None, stream=None, surface=False):
         """mr_trace_photons: Scene::tracePhotons (caustic: traceCausticPhotons) for one disc light into `photon_map`, which
-        the caller balances afterwards.  light: dict with position, normal, color, wattage, radius.  d_records: optional
+        the caller balances afterwards.  surface=True: mr_trace_photons_surface, the walk whose roulette and diffuse bounce
+        read the surface pass's colour and normal -- the call for a scene with a texture table.  light: dict with position, normal, color, wattage, radius.  d_records: optional
         device tensor of PHOTON_RECORD_DTYPE-sized (48-byte) records.  Returns a dict: emitted, stored, segments, rounds and
         the wall time of the call's parts (kernel_ms, readback_ms, store_ms)."""
         desc = PhotonTraceDesc()
@@ -667,9 +674,9 @@ class Scene:
         res = PhotonTraceResult()
         if d_records is not None and records_capacity is None:
             records_capacity = d_records.numel() * d_records.element_size() // PHOTON_RECORD_DTYPE.itemsize
-        _check(self.L.mr_trace_photons(self.h, photon_map.h, C.byref(desc), C.byref(res),
-                                       d_records.data_ptr() if d_records is not None else None, records_capacity or 0,
-                                       _stream_ptr(stream)))
+        call = self.L.mr_trace_photons_surface if surface else self.L.mr_trace_photons
+        _check(call(self.h, photon_map.h, C.byref(desc), C.byref(res), d_records.data_ptr() if d_records is not None else None,
+                    records_capacity or 0, _stream_ptr(stream)))
         t = [C.c_double(), C.c_double(), C.c_double()]
         _check(self.L.mr_trace_photons_timing(*(C.byref(x) for x in t)))
         return dict(emitted=res.emitted, stored=res.stored, segments=res.segments, rounds=res.rounds,

@@ -261,6 +261,71 @@ def flower_setup(scene, desc=None, leaf_size=4):
     return desc
 
 
+# ---------------------------------------------------------------------------------------------
+# The photon_room geometry under textured material tables (mr_trace_photons_surface).  Objects of photon_room: triangles 0-1
+# the wall x = -2, 2-3 the wall x = 2, 4-5 the box's bottom (below the floor plane, never hit), 6-7 the ceiling, 8-9 the wall
+# z = -2, 10-11 the wall z = 2, then the glass sphere (12), the mirror sphere (13) and the floor plane.
+# ---------------------------------------------------------------------------------------------
+_NONE = 0xFFFFFFFF
+_WHITE, _ZERO = (1.0, 1.0, 1.0), (0.0, 0.0, 0.0)
+_GLASS, _MIRROR = SCENES["photon_room"]["materials"][2], SCENES["photon_room"]["materials"][3]
+_WALL = SCENES["photon_room"]["materials"][0]
+_TEXTURED = (_WHITE, _ZERO, _ZERO, _INF, 1.0)                    # a TexturedPhong: its kd is the lookup
+
+
+def _textured_room(materials, prim_material, floor_material, textures, material_texture, texcoord_walls):
+    base = SCENES["photon_room"]
+    objects = list(base["objects"])
+    objects[-1] = objects[-1][:3] + (floor_material,)
+    # A wall's quad a, b, c, d is the triangles (a, b, c) and (a, c, d) (_box_triangles), texture coordinates 0 ... 4 across it.
+    # A wall with texture coordinates is wound the other way round, (a, c, b) and (a, d, c): Triangle::toUVCoordinates picks its
+    # projection by the SIGNED components of cross(B - A, C - A) (Triangle.cpp:193-200), which _box_triangles points out of
+    # the room -- a negative largest component, for which the rule projects the triangle onto a line and (u, v) is NaN.
+    tidx = np.full((len(prim_material), 3), _NONE, np.uint32)
+    for first in texcoord_walls:
+        for k in (first, first + 1):
+            kind, v, n = objects[k]
+            objects[k] = (kind, tuple(v[0:3]) + tuple(v[6:9]) + tuple(v[3:6]), n)
+        tidx[first], tidx[first + 1] = (0, 2, 1), (0, 3, 2)
+    return dict(base, objects=objects, materials=materials, prim_material=prim_material, textures=textures,
+                material_texture=material_texture, texcoords=np.array([[0, 0], [4, 0], [4, 4], [0, 4]], np.float32), tidx=tidx)
+
+
+def photon_room_mixed():
+    """The room with every texture kind but STONE and IMAGE: material 0 PETAL (pivot at the room's centre) on the wall x = -2,
+    1 LEAF on the wall x = 2, 2 FLOWER_CENTER on the ceiling, 3 STEM on the wall z = -2 (the one with texture coordinates),
+    4 the plain wall material on the wall z = 2, 5 a CHECKER on the slightly glossy floor plane, 6 the glass and 7 the mirror
+    sphere, both plain."""
+    return _textured_room(
+        [_TEXTURED, _TEXTURED, _TEXTURED, _TEXTURED, _WALL, (_WHITE, (0.1, 0.1, 0.1), _ZERO, _INF, 1.0), _GLASS, _MIRROR],
+        [0, 0, 1, 1, 4, 4, 2, 2, 3, 3, 4, 4, 6, 7], 5,
+        [dict(petal=((0.0, 1.75, 0.0), 3.0)), dict(leaf=2.0), dict(flower_center=((0.0, 4.0, 0.0), 2.5)), dict(stem=7.5),
+         dict(color1=(0.9, 0.8, 0.7), color2=(0.3, 0.35, 0.4), scale=2.0)],
+        [0, 1, 2, 3, _NONE, 4, _NONE, _NONE], [8])
+
+
+def photon_room_stone():
+    """The room with bump-mapped surfaces: material 0 STONE of scale 3 on the floor plane, 1 STONE of scale 20 on the walls
+    x = -2 and z = -2 (with texture coordinates), both diffuse only; 2 the plain wall material, 3 glass, 4 mirror.
+    The stone walls are the two whose inward normals, (1, 0, 0) and (0, 0, 1), have a POSITIVE largest component: Scene::trace
+    picks its randomVec by the largest SIGNED component of N (Scene.cpp:249-256), so on the walls x = 2 and z = 2 -- normals
+    (-1, 0, 0) and (0, 0, -1), largest component 0 -- randomVec is the zero vector and the reference itself leaves N un-bumped.
+    (With _textured_room's winding of the walls that have texture coordinates, both rules are met on these two walls.)"""
+    return _textured_room([_TEXTURED, _TEXTURED, _WALL, _GLASS, _MIRROR], [1, 1, 2, 2, 2, 2, 2, 2, 1, 1, 2, 2, 3, 4], 0,
+                          [dict(stone=3.0), dict(stone=20.0)], [0, 1, _NONE, _NONE, _NONE], [0, 8])
+
+
+def textured_room_setup(scene, desc, leaf_size=4):
+    """populate() a miro_amd.Scene with photon_room_mixed() / photon_room_stone(), build it, and set its texture coordinates,
+    materials and textures"""
+    populate(scene, desc)
+    scene.build(leaf_size)
+    scene.set_texcoords(desc["texcoords"], desc["tidx"])
+    scene.set_materials(desc["materials"], desc["prim_material"])
+    scene.set_textures(desc["textures"], desc["material_texture"])
+    return desc
+
+
 def sponza_label():
     p = os.environ.get("MIRO_SPONZA_OBJ", "")
     return "sponza" if p and os.path.exists(p) else "sponza-standin"

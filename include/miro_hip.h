@@ -677,7 +677,8 @@ mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_h
  *   `stream`.
  *
  * Entry points that shade without the lookup refuse a scene with a texture table (MR_ERR_STATE, naming the batched calls):
- * mr_render_direct, mr_shade_direct, mr_trace_level, and mr_trace_photons (its roulette reads diffuse2D, Scene.cpp:545-551).
+ * mr_render_direct, mr_shade_direct, mr_trace_level, and mr_trace_photons (its roulette reads diffuse2D, Scene.cpp:545-551;
+ * mr_trace_photons_surface is the walk with the lookup).
  *
  * ---- procedural textures and bump-mapped normals: a per-hit surface pass (csrc/mr_procedural.hip) ----
  * A STONE or STEM lookup is too heavy to sit inside a kernel that also traverses (five Worley searches and up to 33 Perlin
@@ -824,7 +825,26 @@ mr_status mr_final_gather(mr_scene *scene, mr_photon_map *global_map, mr_photon_
  * The call synchronises `stream` (it copies the records into the map's host store) and returns when the map is filled.
  * Errors: NULL scene / map / desc, max_emissions == 0, radius <= 0, zero or non-finite normal, max_depth > 32, scene and map
  *   on different devices: MR_ERR_INVALID (before any device call); scene not built or host_only, map already balanced:
- *   MR_ERR_STATE. */
+ *   MR_ERR_STATE.
+ *
+ * mr_trace_photons_surface -- the same call on the walk of csrc/mr_photon_walk_surface.hip, which looks textures up: emission,
+ *   the keys of every draw, termination, records, independence from round_emissions and the errors are exactly those above.
+ *   At every hit the colour and the normal are what mr_hit_surface writes for that ray and hit (one device function serves
+ *   both): the colour is diffuseColor of Scene.cpp:545-549 for all seven texture kinds and for plain Phong, the normal is
+ *   HitInfo::N as Scene::trace leaves it -- bumped on a STONE material, only normalised everywhere else.
+ *     roulette       prob[0] = average(colour); prob[1], prob[2] add the averages of the material's ks and kt as above; the
+ *                    comparisons are the reference's, literally: rnd > prob[2], rnd < prob[0], rnd < prob[1], rnd < prob[2], so
+ *                    a zero, negative or NaN colour falls where those put it
+ *     diffuse event  Ray::random about that normal with the keys above; power = (colour * power) * (1 / prob[0])
+ *     specular       mirror, Fresnel and refraction use the same normal (a STONE material has ks = kt = 0, so a bumped normal
+ *                    only ever reaches Ray::random)
+ *     stored         hit.P, the incoming direction, the power before the bounce, as above
+ *   Lookups the reference leaves undefined (a petal's large octaves, texels outside an image) take the value the surface pass
+ *   defines and are not counted: a count over walked emissions would depend on the round size.
+ *   Works on any built, device-resident scene, with or without a texture table; without one, map, records and result are
+ *   byte-identical to mr_trace_photons'.  It uploads the table if it changed, as the shading calls do.
+ *   mr_trace_photons itself keeps refusing a scene with a texture table (MR_ERR_STATE, naming this call).
+ *   mr_trace_photons_timing serves both calls. */
 typedef struct mr_disc_light {                        /* DirectionalAreaLight.h:7-38 on SquareLight.h / PointLight.h */
     float position[3], normal[3], color[3], wattage, radius;
 } mr_disc_light;
@@ -849,7 +869,8 @@ typedef struct mr_photon_record {                     /* 48 bytes */
 mr_status mr_trace_photons(mr_scene *scene, mr_photon_map *map, const mr_photon_trace_desc *desc,
                            mr_photon_trace_result *result, mr_photon_record *d_records, uint64_t records_capacity,
                            void *stream);
-/* Where the calling thread's last mr_trace_photons spent its wall time, in milliseconds (any pointer may be NULL): the
+/* (the prototype of mr_trace_photons_surface -- the signature above -- is in miro_hip_surface.h, included below) */
+/* Where the calling thread's last mr_trace_photons / mr_trace_photons_surface spent its wall time, in milliseconds (any pointer may be NULL): the
  * device rounds (walk + bookkeeping kernels, including the wait for them), the copies of the records, the host store. */
 mr_status mr_trace_photons_timing(double *kernel_ms, double *readback_ms, double *store_ms);
 
@@ -859,4 +880,5 @@ const char *mr_version(void);
 #ifdef __cplusplus
 }
 #endif
+#include "miro_hip_surface.h"
 #endif /* MIRO_HIP_H */
