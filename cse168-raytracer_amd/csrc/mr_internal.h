@@ -183,6 +183,13 @@ mr_status launch_gather_queries(const DeviceScene &ds, const mr_ray *d_rays, con
                                 float *d_pos, float *d_nrm, hipStream_t stream);
 mr_status launch_gather_accumulate(const float *d_irr_a, const float *d_irr_b, unsigned long long n, uint32_t spp,
                                    float *d_rgb, hipStream_t stream);
+// the same term for any queue of the recursion (mr_gather_level.hip): d_normal NULL or the surface pass's normals; per-ray
+// weights and pixels; d_counts [0] += queries, [1] += rays
+mr_status launch_gather_level_queries(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_normal,
+                                      unsigned long long n, float *d_pos, float *d_nrm, unsigned long long *d_counts,
+                                      hipStream_t stream);
+mr_status launch_gather_level_accumulate(const float *d_irr_a, const float *d_irr_b, const float *d_weights, const uint32_t *d_pixels,
+                                         unsigned long long n, uint32_t spp, float *d_rgb, float *d_ray_rgb, hipStream_t stream);
 mr_status launch_tonemap(const float *d_rgb, unsigned long long n_values, uint8_t *d_out, hipStream_t stream);
 mr_status launch_deinterleave(const float *d_recv, float *d_full, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t world,
                               uint32_t shard_rows, uint32_t fpp, hipStream_t stream);

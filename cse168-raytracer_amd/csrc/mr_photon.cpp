@@ -371,4 +371,42 @@ mr_status mr_final_gather(mr_scene *s, mr_photon_map *global_map, mr_photon_map 
     return launch_gather_accumulate(d_irr[0], d_irr[1], n, spp, d_rgb, stream);
 }
 
+mr_status mr_gather_level(mr_scene *s, mr_photon_map *global_map, mr_photon_map *caustic_map, const mr_ray *d_rays,
+                          const mr_hit *d_hits, const float *d_normal, const float *d_weights, const uint32_t *d_pixels, uint64_t n,
+                          float max_dist, uint32_t nphotons, uint32_t spp, float *d_scratch, float *d_rgb, float *d_ray_rgb,
+                          uint64_t *d_counts, void *stream_v) {
+    if (!s || !d_rays || !d_hits || !d_scratch || (!d_rgb && !d_ray_rgb)) return fail(MR_ERR_INVALID, "mr_gather_level: NULL argument");
+    if (spp == 0) return fail(MR_ERR_INVALID, "mr_gather_level: spp is 0");
+    if (n / spp > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "mr_gather_level: too many pixels");
+    if (nphotons == 0 || nphotons > kKnnMaxK) return fail(MR_ERR_INVALID, "mr_gather_level: nphotons must be in [1, %d]", kKnnMaxK);
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_weights) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_pixels) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3) || (reinterpret_cast<uintptr_t>(d_scratch) & 3))
+        return fail(MR_ERR_INVALID, "mr_gather_level: ray / hit buffers must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned");
+    mr_photon_map *maps[2] = {global_map, caustic_map};
+    for (mr_photon_map *m : maps)
+        if (m && m->device != s->device) return fail(MR_ERR_INVALID, "mr_gather_level: photon map lives on device %d, the scene on %d", m->device, s->device);
+    if (!s->built) return fail(MR_ERR_STATE, "mr_gather_level: mr_bvh_build has not been called on this scene");
+    if (!s->on_device) return fail(MR_ERR_STATE, "mr_gather_level: scene was built host_only: nothing is resident on a device and there is no CPU fallback");
+    for (mr_photon_map *m : maps)
+        if (m && (!m->balanced || !m->on_device)) return fail(MR_ERR_STATE, "mr_gather_level: photon map is not balanced and resident on a device");
+    if (s->tex.procedural && !d_normal)
+        return fail(MR_ERR_STATE, "mr_gather_level: the scene's texture table holds a procedural texture (STONE, STEM, PETAL, LEAF or FLOWER_CENTER), "
+                                  "whose normal comes from the surface pass: call mr_hit_surface, then mr_gather_level with its normal buffer");
+    if (n == 0) return MR_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    float *d_pos = d_scratch, *d_nrm = d_scratch + 3 * n;
+    float *d_irr[2] = {d_scratch + 6 * n, d_scratch + 9 * n};
+    mr_status st = launch_gather_level_queries(s->dev, d_rays, d_hits, d_normal, n, d_pos, d_nrm, reinterpret_cast<unsigned long long *>(d_counts), stream);
+    if (st != MR_OK) return st;
+    for (int i = 0; i < 2; i++) {
+        if (!maps[i]) { d_irr[i] = nullptr; continue; }
+        st = launch_irradiance(maps[i]->dev, maps[i]->dev.work_counters + (maps[i]->next_counter.fetch_add(1) % kPhotonWorkCounters), d_pos, d_nrm, n, max_dist, nphotons, d_irr[i], nullptr, nullptr, maps[i]->d_stats, stream);
+        if (st != MR_OK) return st;
+    }
+    if (!d_irr[0] && !d_irr[1] && !d_ray_rgb) return MR_OK;      // no map: nothing to add
+    return launch_gather_level_accumulate(d_irr[0], d_irr[1], d_weights, d_pixels, n, spp, d_rgb, d_ray_rgb, stream);
+}
+
 }  // extern "C"

@@ -65,7 +65,7 @@ EXPORTED_SYMBOLS = [
     "mr_last_error", "mr_version",
 ]
 # every symbol include/miro_hip_surface.h declares (entry points added after miro_hip.h's own list was held at 69 names)
-SURFACE_SYMBOLS = ["mr_trace_photons_surface"]
+SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level"]
 
 
 class MiroError(RuntimeError):
@@ -283,6 +283,7 @@ def load_library(path=None):
     L.mr_final_gather.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.mr_trace_photons.argtypes = [vp, vp, C.POINTER(PhotonTraceDesc), C.POINTER(PhotonTraceResult), vp, C.c_uint64, vp]
     L.mr_trace_photons_surface.argtypes = L.mr_trace_photons.argtypes
+    L.mr_gather_level.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
     L.mr_trace_photons_timing.argtypes = [C.POINTER(C.c_double)] * 3
     L.mr_scene_set_lights.argtypes = [vp, C.POINTER(LightDesc), C.c_uint32]
     L.mr_shade_lights.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -655,6 +656,20 @@ class Scene:
                                       caustic_map.h if caustic_map is not None else None, d_rays.data_ptr(),
                                       d_hits.data_ptr(), n, max_dist, nphotons, spp, d_scratch.data_ptr(), d_rgb.data_ptr(),
                                       _stream_ptr(stream)))
+
+    def gather_level(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb=None, d_normal=None, d_weights=None,
+                     d_pixels=None, max_dist=1e10, nphotons=500, spp=1, d_ray_rgb=None, d_counts=None, stream=None):
+        """mr_gather_level: the photon-map term of Scene::traceScene (Scene.cpp:286-299) for any queue of the recursion.  For
+        every ray whose hit is diffuse, irradiance_estimate of the global and the caustic map (either may be None) at the hit
+        point; E = irradiance + caustic goes un-weighted to d_ray_rgb [n, 3] and weight * E / spp is added to the ray's pixel
+        of d_rgb (d_weights / d_pixels: the queue's, None = 1 and ray index / spp).  d_normal: None for the object's normal,
+        or hit_surface's [n, 3] buffer (required on a scene with a procedural texture).  d_scratch: 12 * n floats, whose
+        layout is documented (positions, normals with NaN = no query, the two estimates).  d_counts[0] += queries,
+        d_counts[1] += rays."""
+        _check(self.L.mr_gather_level(self.h, global_map.h if global_map is not None else None,
+                                      caustic_map.h if caustic_map is not None else None, _ptr(d_rays), _ptr(d_hits),
+                                      _ptr(d_normal), _ptr(d_weights), _ptr(d_pixels), n, max_dist, nphotons, spp, _ptr(d_scratch),
+                                      _ptr(d_rgb), _ptr(d_ray_rgb), _ptr(d_counts), _stream_ptr(stream)))
 
     def trace_photons(self, photon_map, light, target, max_emissions, caustic=False, seed=168, max_depth=0, round_emissions=0,
                       d_records=None, records_capacity=None, stream=None, surface=False):

@@ -304,7 +304,7 @@ class FrameRenderer:
         return g
 
     def render_specular(self, depth=10, stream=None, path_tracing=False, path_seed=168, path_kinds=None, fused=False,
-                        group_octants=False, lights=None, environment=None):
+                        group_octants=False, lights=None, environment=None, photon_maps=None, nphotons=500, max_dist=1e10):
         """Scene::traceScene with reflective / refractive materials (Scene.cpp:270-346) as wavefront bounces: every
         level traces its queue, shades it (weight x Phong::shade added to the ray's pixel), and emits the reflect /
         Fresnel / refract children of the next level by ballot compaction.  depth = TRACE_DEPTH (Miro.h:13): rays are
@@ -340,10 +340,23 @@ class FrameRenderer:
         mr_hit_surface (diffuse colour and bump-mapped normal of every hit into two [n, 3] buffers sized to the level's queue)
         -> mr_shade_lights_surface (light list) or the shadow batch and mr_shade_accumulate_surface (single light) -> the
         generators.  Square lights and MR_PATH_DIFFUSE children are refused on such a scene (no _surface form; Ray::random
-        bounces about the normal)."""
+        bounces about the normal).
+        photon_maps: (global, caustic) binding.PhotonMap objects, balanced and resident; either may be None.  The photon-map
+        term of Scene::traceScene (Scene.cpp:286-299) at EVERY level: after a level is traced and shaded and before its
+        children are generated, mr_gather_level runs on the level's queue with its weights and pixels -- irradiance_estimate of
+        both maps at every diffuse hit, weight x (irradiance + caustic) / spp added to the ray's pixel -- so a diffuse wall seen
+        in a mirror or through glass carries its indirect light and its caustics.  nphotons / max_dist: PHOTON_SAMPLES and
+        PHOTON_MAX_DIST (Miro.h:16-17).  On a scene with a procedural texture the queries take the normal buffer that
+        mr_hit_surface just filled (the bumped normal, Scene.cpp:290), otherwise the object's normal.  The scratch (12 floats per
+        ray) is allocated with the level's other buffers.  `fused` must be falsy: mr_trace_level keeps no hit records.  None: no
+        launch is added."""
         sc, L, W = self.scene, self.desc["light"], self.desc["wattage"]
         if getattr(sc, "n_textures", 0):
             fused = False
+        if photon_maps is not None:
+            if fused:
+                raise ValueError("render_specular: photon maps need fused=False (mr_trace_level keeps no hit records)")
+            global_map, caustic_map = photon_maps
         surface = bool(getattr(sc, "procedural", False))
         if surface and self.square_lights:
             raise ValueError("render_specular: square lights on a scene with a procedural texture (no _surface form shades them)")
@@ -375,7 +388,7 @@ class FrameRenderer:
         if stream is not None and stream != torch.cuda.current_stream(self.device):
             with torch.cuda.stream(stream):
                 return self.render_specular(depth, stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights,
-                                            environment or None)
+                                            environment or None, photon_maps, nphotons, max_dist)
         self.d_slots.zero_()
         if path_kinds is None:
             path_kinds = binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT
@@ -461,6 +474,10 @@ class FrameRenderer:
                 sc.shade_square_lights(self.square_lights, self.square_samples, rays, hits, n, self.d_slots, seed=self.seed + level,
                                        d_weights=weights, d_pixels=pixels, spp=self.spp,
                                        flags=fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT), d_counts=cnt, stream=stream)
+            if photon_maps is not None:
+                sc.gather_level(global_map, caustic_map, rays, hits, n, torch.empty(12 * n, **f32), self.d_slots,
+                                d_normal=normal if surface else None, d_weights=weights, d_pixels=pixels, max_dist=max_dist,
+                                nphotons=nphotons, spp=self.spp, stream=stream)
             n_shadow = int(cnt.item())
             per_level.append((n, n_shadow))
             if level == depth:

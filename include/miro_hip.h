@@ -783,6 +783,31 @@ mr_status mr_final_gather(mr_scene *scene, mr_photon_map *global_map, mr_photon_
                           const mr_hit *d_hits, uint64_t n, float max_dist, uint32_t nphotons, uint32_t spp,
                           float *d_scratch, float *d_rgb, void *stream);
 
+/* "mr_gather_level" (declared in miro_hip_surface.h): the same term for ANY queue of the recursion -- the eye rays, or the
+ * reflect / Fresnel / refract children of a later level (mr_gen_secondary_rays) -- so that the maps are read at every hit of
+ * Scene::traceScene, not at depth 0 only.  Per ray k of the n rays:
+ *   query      iff the ray hit and the hit's material is diffuse (Phong::isDiffuse, Phong.cpp:39-42: the clamped m_diffuse of
+ *              the material table, also for a TexturedPhong, as the reference tests it)
+ *   position   HitInfo::P
+ *   normal     d_normal == NULL: the object's normal, normalised (the bits mr_final_gather uses).  d_normal != NULL: three
+ *              floats per ray, the normal as Scene::trace hands it on -- the buffer mr_hit_surface writes, bumped on STONE --
+ *              read as it is for query rays and never for the others.  On a scene whose texture table holds a procedural
+ *              kind (STONE, STEM or a UVW kind) d_normal == NULL is refused: MR_ERR_STATE, call mr_hit_surface first.
+ *   value      E = irradiance + caustic, one float add per channel (Scene.cpp:298); with one map that map's estimate; with
+ *              none the call is valid and adds nothing.  0 for a ray that is no query.
+ * d_weights (rgb per ray, NULL = 1) and d_pixels (pixel per ray, NULL = k / spp) are the queue's, as in mr_shade_lights.
+ * Outputs: d_ray_rgb (may be NULL) receives E per ray, un-weighted; d_rgb (may be NULL when d_ray_rgb is given) has
+ * E[c] * weight[c] / spp ADDED to the ray's pixel with float atomics, runs of equal pixels summed inside the wave first: the
+ * order of the additions is not reproducible, as documented at mr_shade_lights.  d_counts (may be NULL, two uint64, not
+ * zeroed by the call): [0] += queries made, [1] += rays seen.
+ * d_scratch: 12 * n floats on the device; the layout is part of the contract (miro_hip_surface.h): positions, normals (NaN =
+ * no query), the global estimate, the caustic estimate, 3 n floats each, ray k at 3 k -- queries are not compacted.
+ * n need not be a multiple of spp; n == 0 is MR_OK and launches nothing.  nphotons in [1, 512].  With device buffers the call
+ * only enqueues on `stream` (the query kernel, one estimate per map, the accumulate kernel) and can be captured into a graph.
+ * Errors: a NULL scene / rays / hits / scratch or both outputs NULL, spp == 0 (or n / spp beyond 32 bits), nphotons out of range, misaligned buffers
+ * (rays / hits 16 bytes, counters 8, floats 4), a map on another device: MR_ERR_INVALID.  A scene that is not built or was
+ * built host_only, a map that is not balanced or not resident: MR_ERR_STATE. */
+
 /* ---- photon tracing: Scene::tracePhotons / traceCausticPhotons (Scene.cpp:351-472) for ONE DirectionalAreaLight ----------
  * Emits photons from the disc light and walks each with Scene::tracePhoton (Scene.cpp:529-655), as the serial (non-OpenMP)
  * build does, on the device: one lane per photon, emission -> Scene::trace -> roulette -> store / next segment, in one kernel

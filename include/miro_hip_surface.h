@@ -14,6 +14,14 @@ mr_status mr_trace_photons_surface(mr_scene *scene, mr_photon_map *map, const mr
                                    mr_photon_trace_result *result, mr_photon_record *d_records, uint64_t records_capacity,
                                    void *stream);
 
+/* the photon-map term of mr_final_gather for any queue of the recursion: see "mr_gather_level" in miro_hip.h.  d_scratch holds
+ * 12 n floats and its layout is part of the contract: [0, 3n) the query positions, [3n, 6n) the query normals (NaN = no query),
+ * [6n, 9n) the global map's estimate, [9n, 12n) the caustic map's; ray k's triple sits at 3k of each part (not compacted). */
+mr_status mr_gather_level(mr_scene *scene, mr_photon_map *global_map, mr_photon_map *caustic_map, const mr_ray *d_rays,
+                          const mr_hit *d_hits, const float *d_normal, const float *d_weights, const uint32_t *d_pixels, uint64_t n,
+                          float max_dist, uint32_t nphotons, uint32_t spp, float *d_scratch, float *d_rgb, float *d_ray_rgb,
+                          uint64_t *d_counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
