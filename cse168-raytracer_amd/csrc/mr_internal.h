@@ -415,6 +415,28 @@ mr_status texture_params(mr_scene *s, hipStream_t stream, TexParams &p);
 // what mr_trace_photons needs to know of a map (the struct lives in mr_photon.cpp)
 int32_t photon_map_device(const mr_photon_map *m);
 bool photon_map_balanced(const mr_photon_map *m);
+uint32_t photon_map_stored(const mr_photon_map *m);
+
+// the photon map built on the device (mr_photon_build.hip; mr_photon_map_build_device): store + scale + balance of one batch of
+// records on an empty map.  The workspace lives from _begin to _end; the stages run in the order declared.
+struct PhotonBuildStatus {            // what the store kernel leaves for the host: O(1)
+    uint32_t lo[3], hi[3];            // the bounding box as order-preserving keys (decoded by launch_photon_build_store)
+    uint32_t nonfinite, deferred;     // some position is not finite; photons whose direction bytes the host decides
+};
+struct PhotonBuildWork;
+// m: photons taken (after the cap); tables1024: the host's DirTables (costheta, sintheta, cosphi, sinphi)
+mr_status photon_build_begin(uint32_t m, const float *tables1024, PhotonBuildWork **out, hipStream_t stream);
+void photon_build_end(PhotonBuildWork *w);
+// the store kernel, then `status` and the box on the host (synchronises `stream`)
+mr_status launch_photon_build_store(PhotonBuildWork *w, const mr_photon_record *d_records, float scale, PhotonBuildStatus *status, float lo[3], float hi[3],
+                                    hipStream_t stream);
+// the deferred list on the device, status.deferred entries of (storage index as bits, dx, dy, dz); the host overwrites .y with
+// theta | phi << 8 (as bits) and copies the entries back before launch_photon_build_fix
+float4 *photon_build_deferred(PhotonBuildWork *w);
+mr_status launch_photon_build_fix(PhotonBuildWork *w, uint32_t count, hipStream_t stream);
+mr_status launch_photon_build_tree(PhotonBuildWork *w, hipStream_t stream);
+// dev.rec / power / boxes are allocated and n, half, layers, layer_base set; d_dir: 2 m bytes, the quantised directions in heap order
+mr_status launch_photon_build_pack(PhotonBuildWork *w, PhotonMapDev &dev, uint8_t *d_dir, hipStream_t stream);
 
 }  // namespace mr
 

@@ -9,6 +9,7 @@
 // under a total order (coordinate, then storage index), which yields the unique left-balanced tree; the device
 // gets three float4 planes in heap order (position+axis, de-quantised direction, power).
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -38,6 +39,15 @@ struct DirTables {
 };
 const DirTables &tables() { static DirTables t; return t; }
 
+// the two direction bytes of Photon_map::store (PhotonMap.cpp:268-283): the one place they are computed, for
+// mr_photon_map_store and for the photons mr_photon_map_build_device defers to the host
+inline void direction_bytes(float dx, float dy, float dz, uint8_t &theta_out, uint8_t &phi_out) {
+    const int theta = int(acos(dz) * (256.0 / M_PI));
+    theta_out = theta > 255 ? 255 : (uint8_t)theta;
+    const int phi = int(atan2(dy, dx) * (256.0 / (2.0 * M_PI)));
+    phi_out = phi > 255 ? 255 : (phi < 0 ? (uint8_t)(phi + 256) : (uint8_t)phi);
+}
+
 }  // namespace
 
 struct mr_photon_map {
@@ -55,7 +65,12 @@ struct mr_photon_map {
     PhotonMapDev dev;
     unsigned long long *d_stats = nullptr;   // work counters of the estimates (mr_photon_map_count_stats), else NULL
     std::atomic<uint32_t> next_counter{0};   // which of dev.work_counters the next estimate launch takes
-    uint32_t count() const { return (uint32_t)theta.size(); }
+    // a map built by mr_photon_map_build_device lives on the device alone: the vectors above stay empty, dev holds the planes and
+    // d_dir the quantised directions in heap order (theta, phi per photon), which mr_photon_map_export reads back
+    bool device_built = false;
+    uint32_t device_stored = 0;
+    uint8_t *d_dir = nullptr;
+    uint32_t count() const { return device_built ? device_stored : (uint32_t)theta.size(); }
 };
 
 namespace {
@@ -121,9 +136,10 @@ struct Balancer {
 };
 
 void release(mr_photon_map *m) {
-    (void)hipFree(m->dev.rec); (void)hipFree(m->dev.power); (void)hipFree(m->dev.boxes); (void)hipFree(m->dev.work_counters); (void)hipFree(m->d_stats);
+    (void)hipFree(m->dev.rec); (void)hipFree(m->dev.power); (void)hipFree(m->dev.boxes); (void)hipFree(m->dev.work_counters); (void)hipFree(m->d_stats); (void)hipFree(m->d_dir);
     m->dev = PhotonMapDev();
     m->d_stats = nullptr;
+    m->d_dir = nullptr;
     m->on_device = false;
 }
 
@@ -132,6 +148,7 @@ void release(mr_photon_map *m) {
 namespace mr {
 int32_t photon_map_device(const mr_photon_map *m) { return m->device; }
 bool photon_map_balanced(const mr_photon_map *m) { return m->balanced; }
+uint32_t photon_map_stored(const mr_photon_map *m) { return m->count(); }
 }  // namespace mr
 
 extern "C" {
@@ -167,10 +184,10 @@ mr_status mr_photon_map_store(mr_photon_map *m, uint32_t n, const float *power, 
             if (p > m->bbox_max[k]) m->bbox_max[k] = p;
             m->power.push_back(power[3 * (size_t)i + k]);
         }
-        const int theta = int(acos(dir[3 * (size_t)i + 2]) * (256.0 / M_PI));
-        m->theta.push_back(theta > 255 ? 255 : (uint8_t)theta);
-        const int phi = int(atan2(dir[3 * (size_t)i + 1], dir[3 * (size_t)i]) * (256.0 / (2.0 * M_PI)));
-        m->phi.push_back(phi > 255 ? 255 : (phi < 0 ? (uint8_t)(phi + 256) : (uint8_t)phi));
+        uint8_t theta, phi;
+        direction_bytes(dir[3 * (size_t)i], dir[3 * (size_t)i + 1], dir[3 * (size_t)i + 2], theta, phi);
+        m->theta.push_back(theta);
+        m->phi.push_back(phi);
     }
     return MR_OK;
 }
@@ -189,6 +206,7 @@ mr_status mr_photon_map_scale(mr_photon_map *m, float scale) {
 
 mr_status mr_photon_map_balance(mr_photon_map *m, uint32_t host_only) {
     if (!m) return fail(MR_ERR_INVALID, "photon map is NULL");
+    if (m->device_built) return MR_OK;       // mr_photon_map_build_device left it balanced and resident
     const uint32_t n = m->count();
     m->heap.assign(n, 0);
     m->plane.assign(n, 0);
@@ -281,6 +299,115 @@ mr_status mr_photon_map_balance(mr_photon_map *m, uint32_t host_only) {
     return MR_OK;
 }
 
+mr_status mr_photon_map_build_device(mr_photon_map *m, const mr_photon_record *d_records, uint64_t n, float scale,
+                                     mr_photon_build_result *result, void *stream_v) {
+    if (result) *result = mr_photon_build_result();
+    if (!m) return fail(MR_ERR_INVALID, "mr_photon_map_build_device: photon map is NULL");
+    if (n && !d_records) return fail(MR_ERR_INVALID, "mr_photon_map_build_device: records is NULL with n = %llu", (unsigned long long)n);
+    if (reinterpret_cast<uintptr_t>(d_records) & 3) return fail(MR_ERR_INVALID, "mr_photon_map_build_device: records must be 4-byte aligned");
+    if (n > (1ull << 24))
+        return fail(MR_ERR_INVALID, "mr_photon_map_build_device: n = %llu is above 2^24; store larger maps through the host path "
+                                    "(mr_photon_map_store, mr_photon_map_scale, mr_photon_map_balance)", (unsigned long long)n);
+    if (m->balanced) return fail(MR_ERR_STATE, "photon map is immutable after mr_photon_map_balance");
+    if (m->count() > 0) return fail(MR_ERR_STATE, "mr_photon_map_build_device: the map already holds %u photons; it builds an empty map", m->count());
+    int count = 0;
+    hipError_t e = hipGetDeviceCount(&count);
+    if (e != hipSuccess || count <= 0)
+        return fail(MR_ERR_HIP, "no HIP device available (%s); this library has no CPU fallback",
+                    e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
+    if (m->device >= count) return fail(MR_ERR_INVALID, "device %d out of range [0,%d)", m->device, count);
+    MR_HIP_CHECK(hipSetDevice(m->device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const uint32_t taken = (uint32_t)(n < m->max_photons ? n : m->max_photons);       // PhotonMap.cpp:260-261: silently full
+    mr_photon_build_result res = mr_photon_build_result();
+    res.stored = taken; res.dropped = n - taken;
+    const auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto ms = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+
+    struct Work {                                   // the workspace and, until the build succeeds, the map's new planes
+        PhotonBuildWork *w = nullptr;
+        PhotonMapDev dev;
+        uint8_t *d_dir = nullptr;
+        bool keep = false;
+        ~Work() {
+            photon_build_end(w);
+            if (!keep) { (void)hipFree(dev.rec); (void)hipFree(dev.power); (void)hipFree(dev.boxes); (void)hipFree(d_dir); }
+        }
+    } work;
+    const DirTables &t = tables();
+    static_assert(sizeof(DirTables) == 1024 * sizeof(float), "the four tables travel as one block");
+    mr_status st = photon_build_begin(taken, t.costheta, &work.w, stream);
+    if (st != MR_OK) return st;
+
+    // store: powers, box, direction bytes (the host's for the deferred photons), the non-finite flag
+    auto t0 = now();
+    PhotonBuildStatus status;
+    float lo[3], hi[3];
+    st = launch_photon_build_store(work.w, d_records, scale, &status, lo, hi, stream);
+    if (st != MR_OK) return st;
+    if (status.nonfinite) return fail(MR_ERR_INVALID, "mr_photon_map_build_device: a photon position is not finite; the map is left empty");
+    if (status.deferred > taken) return fail(MR_ERR_HIP, "mr_photon_map_build_device: inconsistent deferred count %u of %u", status.deferred, taken);
+    if (status.deferred) {
+        std::vector<float4> list(status.deferred);
+        float4 *d_list = photon_build_deferred(work.w);
+        MR_HIP_CHECK(hipMemcpyAsync(list.data(), d_list, list.size() * sizeof(float4), hipMemcpyDeviceToHost, stream));
+        MR_HIP_CHECK(hipStreamSynchronize(stream));
+        for (float4 &d : list) {
+            uint8_t theta, phi;
+            direction_bytes(d.y, d.z, d.w, theta, phi);
+            const uint32_t b = (uint32_t)theta | ((uint32_t)phi << 8);
+            memcpy(&d.y, &b, 4);
+        }
+        MR_HIP_CHECK(hipMemcpyAsync(d_list, list.data(), list.size() * sizeof(float4), hipMemcpyHostToDevice, stream));
+        st = launch_photon_build_fix(work.w, status.deferred, stream);
+        if (st != MR_OK) return st;
+        MR_HIP_CHECK(hipStreamSynchronize(stream));                 // `list` leaves scope
+    }
+    res.deferred = status.deferred;
+    res.store_ms = ms(t0);
+
+    // balance: three sorted lists, then one heap level per step
+    t0 = now();
+    st = launch_photon_build_tree(work.w, stream);
+    if (st != MR_OK) return st;
+    MR_HIP_CHECK(hipStreamSynchronize(stream));
+    res.balance_ms = ms(t0);
+
+    // pack: the planes in heap order and the block boxes, laid out as mr_photon_map_balance lays them out
+    t0 = now();
+    const size_t bytes = ((size_t)taken + 1) * sizeof(float4);
+    work.dev.n = (int32_t)taken;
+    work.dev.half = (int32_t)taken / 2 - 1;                         // half_stored_photons, PhotonMap.cpp:357
+    size_t total = 0;
+    for (uint64_t first = 1; first <= taken && work.dev.layers < 4; first <<= 6) { work.dev.layer_base[work.dev.layers++] = (int32_t)total; total += (size_t)first; }
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&work.dev.rec), 2 * bytes));
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&work.dev.power), bytes));
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&work.dev.boxes), 4 * std::max<size_t>(total, 1) * sizeof(float4)));
+    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&work.d_dir), std::max<size_t>(2 * (size_t)taken, 4)));
+    st = launch_photon_build_pack(work.w, work.dev, work.d_dir, stream);
+    if (st != MR_OK) return st;
+    MR_HIP_CHECK(hipStreamSynchronize(stream));
+    if (!m->dev.work_counters) {
+        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&m->dev.work_counters), kPhotonWorkCounters * sizeof(unsigned)));
+        MR_HIP_CHECK(hipMemset(m->dev.work_counters, 0, kPhotonWorkCounters * sizeof(unsigned)));
+    }
+    res.pack_ms = ms(t0);
+
+    work.dev.work_counters = m->dev.work_counters;
+    m->dev = work.dev;
+    m->d_dir = work.d_dir;
+    work.keep = true;
+    memcpy(m->bbox_min, lo, sizeof(lo));
+    memcpy(m->bbox_max, hi, sizeof(hi));
+    m->prev_scale = taken;
+    m->device_built = true;
+    m->device_stored = taken;
+    m->balanced = true;
+    m->on_device = true;
+    if (result) *result = res;
+    return MR_OK;
+}
+
 mr_status mr_photon_map_count(const mr_photon_map *m, uint32_t *stored) {
     if (!m || !stored) return fail(MR_ERR_INVALID, "NULL argument");
     *stored = m->count();
@@ -290,6 +417,25 @@ mr_status mr_photon_map_count(const mr_photon_map *m, uint32_t *stored) {
 mr_status mr_photon_map_export(const mr_photon_map *m, float *pos, int32_t *plane, uint8_t *theta_phi, float *power) {
     if (!m) return fail(MR_ERR_INVALID, "photon map is NULL");
     if (!m->balanced) return fail(MR_ERR_STATE, "mr_photon_map_balance has not been called");
+    if (m->device_built) {                    // the device arrays are all there is: read them back
+        const uint32_t n = m->count();
+        if (n == 0) return MR_OK;
+        std::vector<float4> rec(2 * (size_t)(n + 1)), pw((size_t)n + 1);
+        std::vector<uint8_t> tp(2 * (size_t)n);
+        MR_HIP_CHECK(hipSetDevice(m->device));
+        MR_HIP_CHECK(hipDeviceSynchronize());
+        MR_HIP_CHECK(hipMemcpy(rec.data(), m->dev.rec, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        MR_HIP_CHECK(hipMemcpy(pw.data(), m->dev.power, pw.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        MR_HIP_CHECK(hipMemcpy(tp.data(), m->d_dir, tp.size(), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n; i++) {
+            const float4 a = rec[2 * (size_t)(i + 1)], p = pw[(size_t)i + 1];
+            if (pos) { pos[3 * (size_t)i] = a.x; pos[3 * (size_t)i + 1] = a.y; pos[3 * (size_t)i + 2] = a.z; }
+            if (power) { power[3 * (size_t)i] = p.x; power[3 * (size_t)i + 1] = p.y; power[3 * (size_t)i + 2] = p.z; }
+            if (plane) memcpy(&plane[i], &a.w, 4);
+        }
+        if (theta_phi) memcpy(theta_phi, tp.data(), tp.size());
+        return MR_OK;
+    }
     for (uint32_t i = 0; i < m->count(); i++) {
         const uint32_t s = m->heap[i];
         for (int k = 0; k < 3; k++) {

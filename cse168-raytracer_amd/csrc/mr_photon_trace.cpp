@@ -49,10 +49,66 @@ mr_status allocate(Buffers &b, uint32_t capacity, uint32_t max_depth) {
     return MR_OK;
 }
 
+// Where a round's compacted records go -- the one thing mr_trace_photons_resident does differently.
+//   begin(desc, max_depth)                 before the first round
+//   copy(compact, n, at, stream)           enqueue the copy of the round's n records, the call's records [at, at + n)
+//   store(map)                             after that copy and the stream's synchronisation: hand them to the map
+//   finish(map, emitted, stored, stream)   after the last round
+// HostStore: to the host and through mr_photon_map_store, then scale_photon_power(1 / emitted); the caller balances.
+struct HostStore {
+    static constexpr bool kHost = true;
+    std::vector<mr_photon_record> recs;
+    std::vector<float> power, pos, dir;
+    mr_status begin(const mr_photon_trace_desc *, uint32_t) { return MR_OK; }
+    mr_status copy(const float4 *compact, uint64_t n, uint64_t, hipStream_t stream) {
+        recs.resize(n);
+        if (n) MR_HIP_CHECK(hipMemcpyAsync(recs.data(), compact, n * sizeof(mr_photon_record), hipMemcpyDeviceToHost, stream));
+        return MR_OK;
+    }
+    mr_status store(mr_photon_map *map) {
+        power.resize(3 * recs.size()); pos.resize(3 * recs.size()); dir.resize(3 * recs.size());
+        for (size_t i = 0; i < recs.size(); i++)
+            for (int c = 0; c < 3; c++) { power[3 * i + c] = recs[i].power[c]; pos[3 * i + c] = recs[i].pos[c]; dir[3 * i + c] = recs[i].dir[c]; }
+        for (size_t at = 0; at < recs.size(); at += 1u << 30) {       // mr_photon_map_store counts in 32 bits
+            const size_t n = recs.size() - at < (1u << 30) ? recs.size() - at : (1u << 30);
+            mr_status st = mr_photon_map_store(map, (uint32_t)n, power.data() + 3 * at, pos.data() + 3 * at, dir.data() + 3 * at);
+            if (st != MR_OK) return st;
+        }
+        return MR_OK;
+    }
+    mr_status finish(mr_photon_map *map, uint64_t emitted, uint64_t, hipStream_t) {
+        return emitted ? mr_photon_map_scale(map, 1.0f / (float)emitted) : MR_OK;      // Scene.cpp:402
+    }
+};
+// DeviceAppend: device to device onto a library-owned buffer of target + max_depth records (the last emission's records all
+// count), then mr_photon_map_build_device with the same scale; the map ends balanced and resident.
+struct DeviceAppend {
+    static constexpr bool kHost = false;
+    mr_photon_record *d_all = nullptr;
+    uint64_t capacity = 0;
+    mr_photon_build_result *build = nullptr;
+    ~DeviceAppend() { (void)hipFree(d_all); }
+    mr_status begin(const mr_photon_trace_desc *desc, uint32_t max_depth) {
+        capacity = (uint64_t)desc->target + max_depth;
+        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d_all), capacity * sizeof(mr_photon_record)));
+        return MR_OK;
+    }
+    mr_status copy(const float4 *compact, uint64_t n, uint64_t at, hipStream_t stream) {
+        if (at + n > capacity) return fail(MR_ERR_HIP, "mr_trace_photons_resident: %llu records overflow the buffer of %llu", (unsigned long long)(at + n), (unsigned long long)capacity);
+        if (n) MR_HIP_CHECK(hipMemcpyAsync(d_all + at, compact, n * sizeof(mr_photon_record), hipMemcpyDeviceToDevice, stream));
+        return MR_OK;
+    }
+    mr_status store(mr_photon_map *) { return MR_OK; }
+    mr_status finish(mr_photon_map *map, uint64_t emitted, uint64_t stored, hipStream_t stream) {
+        return mr_photon_map_build_device(map, d_all, stored, emitted ? 1.0f / (float)emitted : 1.0f, build, stream);
+    }
+};
+
 // launch(light, max_depth, first, count, need, buffers): one round's walk and bookkeeping kernels on `stream`
-template <typename Launch>
+template <typename Policy, typename Launch>
 mr_status trace_photons(const char *who, bool surface, mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc,
-                        mr_photon_trace_result *result, mr_photon_record *d_records, uint64_t records_capacity, hipStream_t stream, Launch &&launch) {
+                        mr_photon_trace_result *result, mr_photon_record *d_records, uint64_t records_capacity, hipStream_t stream, Policy &&policy,
+                        Launch &&launch) {
     if (!s || !map || !desc) return fail(MR_ERR_INVALID, "%s: NULL scene, map or desc", who);
     if (desc->max_emissions == 0) return fail(MR_ERR_INVALID, "%s: max_emissions is 0 (the hard stop is required)", who);
     const mr_disc_light &lt = desc->light;
@@ -72,6 +128,9 @@ mr_status trace_photons(const char *who, bool surface, mr_scene *s, mr_photon_ma
                                   "has no texture lookup; call mr_trace_photons_surface, whose walk looks textures up, or trace photons "
                                   "before setting textures, or clear them (n_textures = 0)");
     if (photon_map_balanced(map)) return fail(MR_ERR_STATE, "photon map is immutable after mr_photon_map_balance");
+    if (!policy.kHost && photon_map_stored(map) > 0)
+        return fail(MR_ERR_STATE, "%s: the map already holds %u photons; this call builds ONE empty map (trace several lights into one map with "
+                                  "mr_trace_photons and mr_photon_map_balance)", who, photon_map_stored(map));
     g_timing = Timing();
 
     const uint32_t max_depth = desc->max_depth ? desc->max_depth : 5u;          // TRACE_DEPTH_PHOTONS (Miro.h:14)
@@ -88,8 +147,8 @@ mr_status trace_photons(const char *who, bool surface, mr_scene *s, mr_photon_ma
     }
 
     mr_photon_trace_result res = {0, 0, 0, 0};
+    if (desc->target > 0 || !policy.kHost) MR_HIP_CHECK(hipSetDevice(s->device));
     if (desc->target > 0) {
-        MR_HIP_CHECK(hipSetDevice(s->device));
         uint64_t limit = kRoundRecords / max_depth;
         if (limit > (1u << 20)) limit = 1u << 20;
         // the first round: one emission per wanted photon (a photon stores less than once per emission in most rooms)
@@ -99,8 +158,8 @@ mr_status trace_photons(const char *who, bool surface, mr_scene *s, mr_photon_ma
         Buffers b;
         mr_status st = allocate(b, (uint32_t)round, max_depth);
         if (st != MR_OK) return st;
-        std::vector<mr_photon_record> recs;
-        std::vector<float> power, pos, dir;
+        st = policy.begin(desc, max_depth);
+        if (st != MR_OK) return st;
         bool reached = false;
         while (!reached && res.emitted < desc->max_emissions) {
             uint64_t count = round;
@@ -122,57 +181,48 @@ mr_status trace_photons(const char *who, bool surface, mr_scene *s, mr_photon_ma
                 return fail(MR_ERR_HIP, "%s: inconsistent round header (%u emissions of %llu)", who, hdr.emitted, (unsigned long long)count);
 
             t0 = std::chrono::steady_clock::now();
-            recs.resize(hdr.stored);
-            if (hdr.stored) MR_HIP_CHECK(hipMemcpyAsync(recs.data(), b.compact, hdr.stored * sizeof(mr_photon_record), hipMemcpyDeviceToHost, stream));
+            st = policy.copy(b.compact, hdr.stored, res.stored, stream);
+            if (st != MR_OK) return st;
             if (d_records && res.stored < records_capacity && hdr.stored) {
                 const uint64_t room = records_capacity - res.stored, n = hdr.stored < room ? hdr.stored : room;
                 MR_HIP_CHECK(hipMemcpyAsync(d_records + res.stored, b.compact, n * sizeof(mr_photon_record), hipMemcpyDeviceToDevice, stream));
             }
             MR_HIP_CHECK(hipStreamSynchronize(stream));
-            g_timing.readback_ms += ms_since(t0);
+            if (policy.kHost) g_timing.readback_ms += ms_since(t0);
 
             t0 = std::chrono::steady_clock::now();
-            power.resize(3 * recs.size()); pos.resize(3 * recs.size()); dir.resize(3 * recs.size());
-            for (size_t i = 0; i < recs.size(); i++)
-                for (int c = 0; c < 3; c++) { power[3 * i + c] = recs[i].power[c]; pos[3 * i + c] = recs[i].pos[c]; dir[3 * i + c] = recs[i].dir[c]; }
-            for (size_t at = 0; at < recs.size(); at += 1u << 30) {       // mr_photon_map_store counts in 32 bits
-                const size_t n = recs.size() - at < (1u << 30) ? recs.size() - at : (1u << 30);
-                st = mr_photon_map_store(map, (uint32_t)n, power.data() + 3 * at, pos.data() + 3 * at, dir.data() + 3 * at);
-                if (st != MR_OK) return st;
-            }
-            g_timing.store_ms += ms_since(t0);
+            st = policy.store(map);
+            if (st != MR_OK) return st;
+            if (policy.kHost) g_timing.store_ms += ms_since(t0);
 
             res.emitted += hdr.emitted; res.stored += hdr.stored; res.segments += hdr.segments; res.rounds++;
             reached = hdr.reached != 0;
         }
-        if (res.emitted) {
-            mr_status st2 = mr_photon_map_scale(map, 1.0f / (float)res.emitted);      // Scene.cpp:402
-            if (st2 != MR_OK) return st2;
-        }
+    }
+    if (desc->target > 0 || !policy.kHost) {
+        mr_status st2 = policy.finish(map, res.emitted, res.stored, stream);
+        if (st2 != MR_OK) return st2;
     }
     if (result) *result = res;
     return MR_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-mr_status mr_trace_photons(mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, mr_photon_trace_result *result,
-                           mr_photon_record *d_records, uint64_t records_capacity, void *stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    return trace_photons("mr_trace_photons", false, s, map, desc, result, d_records, records_capacity, stream,
+// the two walks behind one policy
+template <typename Policy>
+mr_status trace_plain(const char *who, mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, mr_photon_trace_result *result,
+                      mr_photon_record *d_records, uint64_t records_capacity, hipStream_t stream, Policy &&policy) {
+    return trace_photons(who, false, s, map, desc, result, d_records, records_capacity, stream, policy,
                          [&](const PhotonWalkLight &wl, uint32_t max_depth, uint32_t first, uint32_t count, unsigned long long need, const PhotonRoundBuffers &b) {
                              return launch_photon_round(s->dev, wl, desc->seed, desc->caustic ? 1u : 0u, max_depth, first, count, need, b, stream);
                          });
 }
 
-mr_status mr_trace_photons_surface(mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, mr_photon_trace_result *result,
-                                   mr_photon_record *d_records, uint64_t records_capacity, void *stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+template <typename Policy>
+mr_status trace_surface(const char *who, mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, mr_photon_trace_result *result,
+                        mr_photon_record *d_records, uint64_t records_capacity, hipStream_t stream, Policy &&policy) {
     bool have_table = false;                 // the table is uploaded / refreshed by the first round, as mr_hit_surface does it
     TexParams tex;
-    return trace_photons("mr_trace_photons_surface", true, s, map, desc, result, d_records, records_capacity, stream,
+    return trace_photons(who, true, s, map, desc, result, d_records, records_capacity, stream, policy,
                          [&](const PhotonWalkLight &wl, uint32_t max_depth, uint32_t first, uint32_t count, unsigned long long need, const PhotonRoundBuffers &b) {
                              if (!have_table) {
                                  tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
@@ -182,6 +232,32 @@ mr_status mr_trace_photons_surface(mr_scene *s, mr_photon_map *map, const mr_pho
                              }
                              return launch_photon_round_surface(s->dev, tex, wl, desc->seed, desc->caustic ? 1u : 0u, max_depth, first, count, need, b, stream);
                          });
+}
+
+}  // namespace
+
+extern "C" {
+
+mr_status mr_trace_photons(mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, mr_photon_trace_result *result,
+                           mr_photon_record *d_records, uint64_t records_capacity, void *stream_) {
+    return trace_plain("mr_trace_photons", s, map, desc, result, d_records, records_capacity, static_cast<hipStream_t>(stream_), HostStore());
+}
+
+mr_status mr_trace_photons_surface(mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, mr_photon_trace_result *result,
+                                   mr_photon_record *d_records, uint64_t records_capacity, void *stream_) {
+    return trace_surface("mr_trace_photons_surface", s, map, desc, result, d_records, records_capacity, static_cast<hipStream_t>(stream_), HostStore());
+}
+
+mr_status mr_trace_photons_resident(mr_scene *s, mr_photon_map *map, const mr_photon_trace_desc *desc, uint32_t surface,
+                                    mr_photon_trace_result *result, mr_photon_build_result *build, mr_photon_record *d_records,
+                                    uint64_t records_capacity, void *stream_) {
+    if (build) *build = mr_photon_build_result();
+    if (surface > 1) return fail(MR_ERR_INVALID, "mr_trace_photons_resident: surface is 0 (the walk of mr_trace_photons) or 1 (of mr_trace_photons_surface)");
+    DeviceAppend policy;
+    policy.build = build;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    return surface ? trace_surface("mr_trace_photons_resident", s, map, desc, result, d_records, records_capacity, stream, policy)
+                   : trace_plain("mr_trace_photons_resident", s, map, desc, result, d_records, records_capacity, stream, policy);
 }
 
 mr_status mr_trace_photons_timing(double *kernel_ms, double *readback_ms, double *store_ms) {

@@ -65,7 +65,7 @@ EXPORTED_SYMBOLS = [
     "mr_last_error", "mr_version",
 ]
 # every symbol include/miro_hip_surface.h declares (entry points added after miro_hip.h's own list was held at 69 names)
-SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level"]
+SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map_build_device", "mr_trace_photons_resident"]
 
 
 class MiroError(RuntimeError):
@@ -207,6 +207,14 @@ class PhotonTraceResult(C.Structure):
     _fields_ = [("emitted", C.c_uint64), ("stored", C.c_uint64), ("segments", C.c_uint64), ("rounds", C.c_uint64)]
 
 
+class PhotonBuildResult(C.Structure):
+    _fields_ = [("stored", C.c_uint64), ("dropped", C.c_uint64), ("deferred", C.c_uint64),
+                ("store_ms", C.c_double), ("balance_ms", C.c_double), ("pack_ms", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # mr_photon_record (miro_hip.h): the optional raw output of mr_trace_photons
 PHOTON_RECORD_DTYPE = np.dtype([("pos", "<f4", 3), ("dir", "<f4", 3), ("power", "<f4", 3),
                                 ("emission", "<u4"), ("depth", "<u4"), ("flags", "<u4")])
@@ -285,6 +293,9 @@ def load_library(path=None):
     L.mr_trace_photons_surface.argtypes = L.mr_trace_photons.argtypes
     L.mr_gather_level.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
     L.mr_trace_photons_timing.argtypes = [C.POINTER(C.c_double)] * 3
+    L.mr_photon_map_build_device.argtypes = [vp, vp, C.c_uint64, C.c_float, C.POINTER(PhotonBuildResult), vp]
+    L.mr_trace_photons_resident.argtypes = [vp, vp, C.POINTER(PhotonTraceDesc), C.c_uint32, C.POINTER(PhotonTraceResult),
+                                            C.POINTER(PhotonBuildResult), vp, C.c_uint64, vp]
     L.mr_scene_set_lights.argtypes = [vp, C.POINTER(LightDesc), C.c_uint32]
     L.mr_shade_lights.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.mr_gen_eye_rays_lens.argtypes = L.mr_gen_eye_rays.argtypes + [C.POINTER(LensDesc), vp, vp, vp]
@@ -672,12 +683,14 @@ class Scene:
                                       _ptr(d_rgb), _ptr(d_ray_rgb), _ptr(d_counts), _stream_ptr(stream)))
 
     def trace_photons(self, photon_map, light, target, max_emissions, caustic=False, seed=168, max_depth=0, round_emissions=0,
-                      d_records=None, records_capacity=None, stream=None, surface=False):
+                      d_records=None, records_capacity=None, stream=None, surface=False, resident=False):
         """mr_trace_photons: Scene::tracePhotons (caustic: traceCausticPhotons) for one disc light into `photon_map`, which
         the caller balances afterwards.  surface=True: mr_trace_photons_surface, the walk whose roulette and diffuse bounce
         read the surface pass's colour and normal -- the call for a scene with a texture table.  light: dict with position, normal, color, wattage, radius.  d_records: optional
         device tensor of PHOTON_RECORD_DTYPE-sized (48-byte) records.  Returns a dict: emitted, stored, segments, rounds and
-        the wall time of the call's parts (kernel_ms, readback_ms, store_ms)."""
+        the wall time of the call's parts (kernel_ms, readback_ms, store_ms).  resident=True: mr_trace_photons_resident -- the
+        records stay on the device and the call ends with the device build of `photon_map`, which must be empty and comes
+        back balanced and resident (no balance() afterwards); the dict then carries the build result under "build"."""
         desc = PhotonTraceDesc()
         desc.light.position[:] = light["position"]
         desc.light.normal[:] = light["normal"]
@@ -689,13 +702,31 @@ class Scene:
         res = PhotonTraceResult()
         if d_records is not None and records_capacity is None:
             records_capacity = d_records.numel() * d_records.element_size() // PHOTON_RECORD_DTYPE.itemsize
-        call = self.L.mr_trace_photons_surface if surface else self.L.mr_trace_photons
-        _check(call(self.h, photon_map.h, C.byref(desc), C.byref(res), d_records.data_ptr() if d_records is not None else None,
-                    records_capacity or 0, _stream_ptr(stream)))
+        build = PhotonBuildResult()
+        if resident:
+            _check(self.L.mr_trace_photons_resident(self.h, photon_map.h, C.byref(desc), 1 if surface else 0, C.byref(res), C.byref(build),
+                                                    _ptr(d_records), records_capacity or 0, _stream_ptr(stream)))
+        else:
+            call = self.L.mr_trace_photons_surface if surface else self.L.mr_trace_photons
+            _check(call(self.h, photon_map.h, C.byref(desc), C.byref(res), _ptr(d_records), records_capacity or 0, _stream_ptr(stream)))
         t = [C.c_double(), C.c_double(), C.c_double()]
         _check(self.L.mr_trace_photons_timing(*(C.byref(x) for x in t)))
-        return dict(emitted=res.emitted, stored=res.stored, segments=res.segments, rounds=res.rounds,
-                    kernel_ms=t[0].value, readback_ms=t[1].value, store_ms=t[2].value)
+        out = dict(emitted=res.emitted, stored=res.stored, segments=res.segments, rounds=res.rounds,
+                   kernel_ms=t[0].value, readback_ms=t[1].value, store_ms=t[2].value)
+        if resident:
+            out["build"] = build.as_dict()
+        return out
+
+    def photon_maps(self, light, target, max_emissions, surface=False, seed=168):
+        """(global, caustic): the two maps of one disc light (Scene::tracePhotons and traceCausticPhotons), each traced and
+        built the resident way -- balanced and resident, ready for render_specular(photon_maps=...).  `target` photons each;
+        a map holds at most target + 32 records (the last emission's all count)."""
+        maps = []
+        for caustic in (False, True):
+            m = PhotonMap(target + 32, device=self.device)
+            self.trace_photons(m, light, target, max_emissions, caustic=caustic, seed=seed, surface=surface, resident=True)
+            maps.append(m)
+        return tuple(maps)
 
     def set_materials(self, materials, prim_material=None):
         """materials: list of (diffuse, specular, transmission, shininess, refract_index) as Phong's constructor takes
@@ -952,6 +983,13 @@ class PhotonMap:
 
     def balance(self, host_only=False):
         _check(self.L.mr_photon_map_balance(self.h, 1 if host_only else 0))
+
+    def build_device(self, d_records, n, scale, stream=None):
+        """mr_photon_map_build_device: store + scale_photon_power(scale) + balance of the first n records of a device tensor of
+        PHOTON_RECORD_DTYPE-sized records, on the device, for an empty map.  Returns the build result as a dict."""
+        res = PhotonBuildResult()
+        _check(self.L.mr_photon_map_build_device(self.h, _ptr(d_records), n, scale, C.byref(res), _stream_ptr(stream)))
+        return res.as_dict()
 
     def count(self):
         n = C.c_uint32(0)

@@ -755,6 +755,13 @@ mr_status mr_photon_map_store(mr_photon_map *map, uint32_t n, const float *power
 mr_status mr_photon_map_scale(mr_photon_map *map, float scale);        /* scale_photon_power (:298-306) */
 /* Photon_map::balance (:314-359): left-balanced kd-tree in heap order; uploads unless host_only */
 mr_status mr_photon_map_balance(mr_photon_map *map, uint32_t host_only);
+/* "mr_photon_map_build_device" (declared in miro_hip_surface.h): store(n records) + scale_photon_power(scale) + balance() of an
+ * EMPTY map in one call, on the device, from a device array of mr_photon_record: hand-written kernels (csrc/mr_photon_build.hip)
+ * store the photons, sort three lists by (coordinate, storage index), build the left-balanced tree one heap level per step,
+ * and pack the planes and block boxes.  The map is then balanced and resident exactly as the three calls above would have left
+ * it -- same photon at every node, same split axes, direction bytes and powers, same boxes -- and mr_photon_map_store /
+ * _scale are refused as after mr_photon_map_balance (which itself is then a no-op).  mr_photon_map_export reads the device
+ * arrays back.  Opt-in: the three host calls are unchanged and remain the yardstick. */
 mr_status mr_photon_map_count(const mr_photon_map *map, uint32_t *stored);
 /* balanced tree in heap order (any pointer may be NULL): pos[3n], plane[n], theta_phi[2n] (quantised direction), power[3n] */
 mr_status mr_photon_map_export(const mr_photon_map *map, float *pos, int32_t *plane, uint8_t *theta_phi, float *power);
@@ -895,6 +902,11 @@ mr_status mr_trace_photons(mr_scene *scene, mr_photon_map *map, const mr_photon_
                            mr_photon_trace_result *result, mr_photon_record *d_records, uint64_t records_capacity,
                            void *stream);
 /* (the prototype of mr_trace_photons_surface -- the signature above -- is in miro_hip_surface.h, included below) */
+/* "mr_trace_photons_resident" (declared in miro_hip_surface.h): either walk with the records kept on the device -- appended
+ * round by round to a library-owned buffer instead of copied to the host -- and mr_photon_map_build_device(map, records,
+ * stored, 1 / emitted) at the end: the map comes back balanced and resident, byte-identical to mr_trace_photons (or _surface)
+ * + mr_photon_map_balance on the same desc.  One EMPTY map per call; several lights into one map stay with the host path.
+ * mr_trace_photons_timing reports readback_ms = store_ms = 0 for it. */
 /* Where the calling thread's last mr_trace_photons / mr_trace_photons_surface spent its wall time, in milliseconds (any pointer may be NULL): the
  * device rounds (walk + bookkeeping kernels, including the wait for them), the copies of the records, the host store. */
 mr_status mr_trace_photons_timing(double *kernel_ms, double *readback_ms, double *store_ms);

@@ -22,6 +22,33 @@ mr_status mr_gather_level(mr_scene *scene, mr_photon_map *global_map, mr_photon_
                           float max_dist, uint32_t nphotons, uint32_t spp, float *d_scratch, float *d_rgb, float *d_ray_rgb,
                           uint64_t *d_counts, void *stream);
 
+/* The photon map built on the device: see "mr_photon_map_build_device" in miro_hip.h.  store(n records) +
+ * scale_photon_power(scale) + balance() for an EMPTY, unbalanced map, from a device array of records (pos, dir and power are
+ * read, the other fields ignored), in the order given.  On return the map is balanced and resident, and answers every call as
+ * the map that the same records took through mr_photon_map_store / _scale / _balance; mr_photon_map_export reads the device
+ * arrays back.  The host reads O(1) data (counts, the box) and the list of deferred photons: those whose scaled angle
+ * acos(dz) * 256 / pi or atan2(dy, dx) * 256 / (2 pi) is not finite or lies within 2^-20 of a whole number get their two
+ * direction bytes from the host's own expression.  n is at most 2^24 (larger maps: the host path).
+ * Errors: NULL map, NULL records with n > 0, records not 4-byte aligned, n > 2^24, a non-finite position (found on the device;
+ * the map stays empty and usable): MR_ERR_INVALID.  A map that holds photons or is balanced: MR_ERR_STATE. */
+typedef struct mr_photon_build_result {
+    uint64_t stored;     /* photons in the map */
+    uint64_t dropped;    /* records beyond max_photons (PhotonMap.cpp:260-261) */
+    uint64_t deferred;   /* photons whose direction bytes the host decided */
+    double store_ms, balance_ms, pack_ms;   /* wall time of the three stages, stream synchronised between them */
+} mr_photon_build_result;
+mr_status mr_photon_map_build_device(mr_photon_map *map, const mr_photon_record *d_records, uint64_t n, float scale,
+                                     mr_photon_build_result *result, void *stream);
+
+/* mr_trace_photons (surface == 0) or mr_trace_photons_surface (surface == 1) whose records never leave the device: see
+ * "mr_trace_photons_resident" in miro_hip.h.  Rounds, termination, result, d_records and errors are those calls'; the records
+ * are appended to a library-owned device buffer and the call ends with mr_photon_map_build_device(map, records, stored,
+ * 1 / emitted) into `build` (may be NULL): the map is balanced and resident on return.  ONE map per call: the map must be
+ * empty (MR_ERR_STATE otherwise); several lights traced into one map stay with mr_trace_photons + mr_photon_map_balance. */
+mr_status mr_trace_photons_resident(mr_scene *scene, mr_photon_map *map, const mr_photon_trace_desc *desc, uint32_t surface,
+                                    mr_photon_trace_result *result, mr_photon_build_result *build,
+                                    mr_photon_record *d_records, uint64_t records_capacity, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
