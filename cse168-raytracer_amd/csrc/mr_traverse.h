@@ -480,56 +480,70 @@ __device__ __forceinline__ void node_decide(float mn0, float mx0, float mn1, flo
 // same operands; every lane keeps its own stack, pushes what node_decide would have pushed and visits the nodes in the same
 // order -- a wave in the run is a wave for which node_step's test would have succeeded at every visit.  Nothing is shared between
 // the lanes but the knowledge that their values are equal, so leaving the run needs no recovery step.
+// The scalar side of a visit in the run.  The run keeps its node as a BYTE offset into the table:
+// the scalar load adds a 32-bit offset register to its base itself, so one shift stands where a sign extension, a 64-bit shift
+// and a 64-bit add stood in front of every load.  Offsets stay below 2^31 -- the run is for node indices below kRunNodeLimit;
+// in a larger table the nodes beyond are visited lane by lane (node_step's per-lane visit, which is right for any node).
+constexpr unsigned kRunNodeLimit = 1u << 25;
+__device__ __forceinline__ v16f load_node_scalar_at(const float4 *nodes, unsigned off) {
+    v16f v;
+    asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(nodes), "s"(off) : "memory");
+    return v;
+}
+// How a run ends travels in `cur` itself: the loop keeps ONE exit and one scalar test for it.  `cur` is the next node while the
+// run goes on, and otherwise a child reference that is no node of the run (a leaf; an index of kRunNodeLimit or more) or one of
+// two values that are no reference at all: kDone when node_decide has to finish the visit lane by lane (pop, split decision),
+// kRunIrregular at an irregular node.  (Leaf references end at ~((2^27 - 2) << 4 | 15) = 0x80000010: mr_api.cpp refuses 2^27
+// records or more.)
+constexpr int kRunIrregular = kDone + 1;
+
 template <typename W>
 __device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, Stats &st, int cur) {
     const unsigned long long m_all = __builtin_amdgcn_ballot_w64(true);
-    float mn0, mx0, mn1, mx1, k0, k1;
-    int node, ref0, ref1;
-    bool regular;
-    // One loop exit, one scalar test for it: `cur` is the next node while the lanes agree, a leaf reference when they agree on a
-    // leaf, and kDone -- which is no child reference -- when the visit of `node` has to be finished behind the loop (pop, split
-    // decision, irregular node).
+    float mn0, mx0, mn1, mx1, k0, k1;        // (written by every visit that can reach node_decide<.., true, true> below)
+    int ref0, ref1;
+    unsigned off;
     do {
-        node = cur;
-        const v16f v = load_node_scalar(p.nodes, node);
+        off = (unsigned)cur << 6;
+        const v16f v = load_node_scalar_at(p.nodes, off);
         const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
         const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
         ref0 = __float_as_int(v[12]); ref1 = __float_as_int(v[13]);
-        regular = __float_as_int(v[14]) == 0;
         MR_RUN_COUNT(st.run_visits);
-        cur = kDone;
-        if (regular) {
+        cur = kRunIrregular;
+        if (__float_as_int(v[14]) == 0) {
+            cur = kDone;
             k0 = 0.0f; k1 = 0.0f;
             node_slabs_guarded<W>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
-            // node_decide's comparisons (its SAFE form) as lane masks: out = the lanes whose ray misses the child
-            const unsigned long long out0 = (__builtin_amdgcn_ballot_w64(mn0 > k0) | __builtin_amdgcn_ballot_w64(mx0 < r.tmin)) & m_all;
-            const unsigned long long out1 = (__builtin_amdgcn_ballot_w64(mn1 > k1) | __builtin_amdgcn_ballot_w64(mx1 < r.tmin)) & m_all;
+            // node_decide's comparisons (its SAFE form) as lane masks: out = the lanes whose ray misses the child.  A compare mask
+            // has zero bits for inactive lanes, so the masks need no and with m_all.
+            const unsigned long long out0 = __builtin_amdgcn_ballot_w64(mn0 > k0) | __builtin_amdgcn_ballot_w64(mx0 < r.tmin);
+            const unsigned long long out1 = __builtin_amdgcn_ballot_w64(mn1 > k1) | __builtin_amdgcn_ballot_w64(mx1 < r.tmin);
             if ((out0 | out1) == 0ull) {                              // every lane hits both: near child first, ties -> child 0
                 const unsigned long long one_first = __builtin_amdgcn_ballot_w64(mn0 > mn1);
-                if (one_first == 0ull) { stack_push(L, s_stack, ref1); cur = ref0; }
+                if (__builtin_expect(one_first == 0ull, 1)) { stack_push(L, s_stack, ref1); cur = ref0; }
                 else if (one_first == m_all) { stack_push(L, s_stack, ref0); cur = ref1; }
-            } else if ((out0 | (out1 ^ m_all)) == 0ull) {             // every lane hits child 0 only
-                cur = ref0;
-            } else if ((out1 | (out0 ^ m_all)) == 0ull) {             // every lane hits child 1 only
-                cur = ref1;
+            } else {                                                  // every lane hits child 0 only / child 1 only: no branch
+                const bool only0 = (out0 | (out1 ^ m_all)) == 0ull, only1 = (out1 | (out0 ^ m_all)) == 0ull;
+                cur = only0 ? ref0 : only1 ? ref1 : kDone;
             }
         }
-    } while (cur >= 0);
-    if (cur != kDone) {                                // a leaf: the wave's leaf_step finds it uniform by its own test
-        L.cur = cur;
-    } else if (!regular) {                             // the reference's own divisions, decided lane by lane
+    } while ((unsigned)cur < kRunNodeLimit);
+    if (cur == kDone) {                                // no child hit in some lanes or all (pop), or the lanes part
+        if (((unsigned long long)__builtin_amdgcn_ballot_w64((mn0 > k0) || (mx0 < r.tmin)) &
+             (unsigned long long)__builtin_amdgcn_ballot_w64((mn1 > k1) || (mx1 < r.tmin))) != m_all) MR_RUN_COUNT(st.run_splits);
+        node_decide<false, true, true>(mn0, mx0, mn1, mx1, ref0, ref1, r, L, s_stack, st, k0, k1);
+    } else if (cur == kRunIrregular) {                 // the reference's own divisions, decided lane by lane
         // (the record is loaded a second time on purpose: kept live across the loop's exit its twelve corners cost the hot loop
         // scalar registers it spills for, and irregular nodes are rare -- a frame whose eye is irregular, where every visit comes
         // this way, pays the run's entry and two loads per visit and is slower than before)
-        const v16f v = load_node_scalar(p.nodes, node);
+        const v16f v = load_node_scalar_at(p.nodes, off);
         const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
         const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
         node_slabs<walk_divide<W>>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
         node_decide<false, false>(mn0, mx0, mn1, mx1, ref0, ref1, r, L, s_stack, st);
-    } else {                                           // no child hit in some lanes or all (pop), or the lanes part
-        if (((unsigned long long)__builtin_amdgcn_ballot_w64((mn0 > k0) || (mx0 < r.tmin)) &
-             (unsigned long long)__builtin_amdgcn_ballot_w64((mn1 > k1) || (mx1 < r.tmin))) != m_all) MR_RUN_COUNT(st.run_splits);
-        node_decide<false, true, true>(mn0, mx0, mn1, mx1, ref0, ref1, r, L, s_stack, st, k0, k1);
+    } else {                                           // a leaf: the wave's leaf_step finds it uniform by its own test
+        L.cur = cur;
     }
 }
 
@@ -540,8 +554,10 @@ __device__ __forceinline__ void node_step(const TraceParams &p, const RayRegs &r
     constexpr bool kStats = W::stats, kSafe = slab_nan_free(W::slab), kGuarded = slab_guarded(W::slab);
     if (W::scalar) {
         const int cur0 = __builtin_amdgcn_readfirstlane(L.cur);
-        if (__all(L.cur == cur0)) {
-            if (W::run && slab_needs_tmin0(W::slab) && is_octant(W::oct) && !kStats) {
+        // (a wave of a run walk at a node beyond the run's offsets takes the per-lane visit below: it is correct for any node)
+        constexpr bool kRuns = W::run && slab_needs_tmin0(W::slab) && is_octant(W::oct) && !kStats;
+        if (__all(L.cur == cur0) && (!kRuns || (unsigned)cur0 < kRunNodeLimit)) {
+            if (kRuns) {
                 uniform_run<W>(p, r, L, s_stack, st, cur0);
                 return;
             }
@@ -643,7 +659,8 @@ __device__ __forceinline__ void node_slabs_guarded(const float4 q0, const float4
             : "=&v"(near), "=&v"(t0), "=&v"(t1), "=&v"(k0), "=&v"(k1)
             : "v"(mn0), "v"(r.tmin), "v"(mn1), "v"(mx0), "v"(mx1), "v"(best_t));
     }
-    if (__any(near <= 16u)) {
+    // (run walks say that the recomputation is rare: it is laid out behind the loop and the visit's own path falls through)
+    if (W::run ? __builtin_expect(__any(near <= 16u), 0) : __any(near <= 16u)) {
         node_slabs<walk_slab<W, kSlabCorrection>>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
         k0 = vmin2(mx0, best_t); k1 = vmin2(mx1, best_t);
     }
