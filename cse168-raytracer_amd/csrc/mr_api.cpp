@@ -25,6 +25,17 @@ mr_status fail(mr_status code, const char *fmt, ...) {
     return code;
 }
 
+mr_status select_device(int32_t device) {
+    int count = 0;
+    hipError_t e = hipGetDeviceCount(&count);
+    if (e != hipSuccess || count <= 0)
+        return fail(MR_ERR_HIP, "no HIP device available (%s); this library has no CPU fallback",
+                    e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
+    if (device >= count) return fail(MR_ERR_INVALID, "device %d out of range [0,%d)", device, count);
+    MR_HIP_CHECK(hipSetDevice(device));
+    return MR_OK;
+}
+
 namespace {
 
 template <typename T>
@@ -576,13 +587,8 @@ mr_status mr_bvh_build(mr_scene *s, const mr_build_opts *opts) {
     }
     const bool host_only = opts && opts->host_only;
     if (!host_only) {
-        int count = 0;
-        hipError_t e = hipGetDeviceCount(&count);
-        if (e != hipSuccess || count <= 0)
-            return fail(MR_ERR_HIP, "no HIP device available (%s); this library has no CPU fallback",
-                        e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
-        if (s->device >= count) return fail(MR_ERR_INVALID, "device %d out of range [0,%d)", s->device, count);
-        MR_HIP_CHECK(hipSetDevice(s->device));
+        mr_status st = select_device(s->device);
+        if (st != MR_OK) return st;
     }
     if (s->on_device) release_device(s);
     s->built = false;

@@ -1,11 +1,13 @@
 // mr_gather_level.hip -- the photon-map term of Scene::traceScene (Scene.cpp:286-299) for ANY queue of the recursion
 // (mr_gather_level): the eye rays, or the reflect / Fresnel / refract children of a later level with their path weights and
-// pixels.  Two streaming kernels, one lane per ray, around the k-NN estimates of mr_photon.hip (launch_irradiance):
+// pixels.  Two streaming kernels, one lane per ray, around the k-NN estimates of mr_photon.hip (launch_irradiance).  The
+// query kernel is the library's only one: mr_final_gather launches it too, without a normal buffer and without counts, and
+// then accumulates with its own kernel (gather_accumulate_kernel of mr_shade.hip: sample order, one float add per pixel).
 //
 //   gather_level_queries_kernel     hit point and normal of every ray whose hit has a diffuse material (Phong::isDiffuse,
 //                                   Phong.cpp:39-42), a NaN normal elsewhere ("no query": irradiance_kernel answers 0).  The
-//                                   normal is the object's, normalised (Scene.cpp:262) -- the bits gather_queries_kernel of
-//                                   mr_shade.hip writes -- or, given the surface pass's buffer, that buffer's (bumped on STONE):
+//                                   normal is the object's, normalised (Scene.cpp:262), or, given the surface pass's
+//                                   buffer, that buffer's (bumped on STONE):
 //                                   what Scene.cpp:290 hands to irradiance_estimate.  Queries stay in place, not compacted.
 //   gather_level_accumulate_kernel  E = irradiance + caustic per ray (Scene.cpp:298) to d_ray_rgb, and weight * E / spp to the
 //                                   ray's pixel in the expression shape of store_shaded (mr_lights_body.h).  Whole waves:

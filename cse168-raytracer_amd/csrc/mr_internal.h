@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <chrono>
 #include <mutex>
 #include <cstdint>
 #include <string>
@@ -24,6 +25,14 @@ mr_status fail(mr_status code, const char *fmt, ...);
             return mr::fail(MR_ERR_HIP, "%s failed: %s (%s:%d)", #expr,                 \
                             hipGetErrorString(e__), __FILE__, __LINE__);                \
     } while (0)
+// what every call does before its first device work: the two refusals below, then hipSetDevice
+//   MR_ERR_HIP      "no HIP device available (...); this library has no CPU fallback"
+//   MR_ERR_INVALID  "device %d out of range [0,%d)"
+mr_status select_device(int32_t device);
+
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // ---------------------------------------------------------------------------------------
 // small arithmetic that host and device code share, each written once so that every user gets the same bits
@@ -178,13 +187,13 @@ mr_status launch_shade(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit
                        const mr_hit *d_shadow_hits, const uint32_t *d_shadow_src, const unsigned long long *d_shadow_count,
                        uint8_t *d_occluded, const mr_light &light, const float diffuse[3], uint32_t spp, float *d_rgb,
                        hipStream_t stream);
-// final gather (Scene.cpp:285-299): queries of the diffuse hits (NaN normal elsewhere), then irradiance -> pixels
-mr_status launch_gather_queries(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, unsigned long long n,
-                                float *d_pos, float *d_nrm, hipStream_t stream);
+// The photon-map term (Scene.cpp:285-299).  One query kernel (mr_gather_level.hip) serves mr_final_gather and mr_gather_level:
+// hit point and normal of the diffuse hits, a NaN normal elsewhere; d_normal NULL or the surface pass's normals; d_counts NULL
+// or [0] += queries, [1] += rays.  Two accumulate kernels, because their sums round differently: mr_final_gather's
+// (mr_shade.hip) adds a pixel's samples in sample order and then one float to the pixel; mr_gather_level's takes per-ray
+// weights and pixels and adds wave runs with float atomics.
 mr_status launch_gather_accumulate(const float *d_irr_a, const float *d_irr_b, unsigned long long n, uint32_t spp,
                                    float *d_rgb, hipStream_t stream);
-// the same term for any queue of the recursion (mr_gather_level.hip): d_normal NULL or the surface pass's normals; per-ray
-// weights and pixels; d_counts [0] += queries, [1] += rays
 mr_status launch_gather_level_queries(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_normal,
                                       unsigned long long n, float *d_pos, float *d_nrm, unsigned long long *d_counts,
                                       hipStream_t stream);
@@ -373,6 +382,16 @@ struct PhotonMapDev {
     unsigned *work_counters = nullptr;
 };
 constexpr uint32_t kPhotonWorkCounters = 16;
+// n, half, layers and layer_base of a balanced map of n photons; returns the number of its block boxes (the boxes plane holds
+// four float4 for each, and for one when there is none)
+inline size_t photon_map_layout(PhotonMapDev &dev, uint32_t n) {
+    dev.n = (int32_t)n;
+    dev.half = (int32_t)n / 2 - 1;                                  // half_stored_photons, PhotonMap.cpp:357
+    dev.layers = 0;
+    size_t total = 0;
+    for (uint64_t first = 1; first <= n && dev.layers < 4; first <<= 6) { dev.layer_base[dev.layers++] = (int32_t)total; total += (size_t)first; }
+    return total;
+}
 constexpr int kKnnMaxK = 512;     // nphotons limit of the wave-cooperative k-NN (PHOTON_SAMPLES = 500)
 mr_status launch_irradiance(const PhotonMapDev &pm, unsigned *work_counter, const float *d_pos, const float *d_normal, unsigned long long nq,
                             float max_dist, uint32_t k, float *d_irrad, int32_t *d_found, float *d_r2, unsigned long long *d_stats,
@@ -435,7 +454,7 @@ mr_status launch_photon_build_store(PhotonBuildWork *w, const mr_photon_record *
 float4 *photon_build_deferred(PhotonBuildWork *w);
 mr_status launch_photon_build_fix(PhotonBuildWork *w, uint32_t count, hipStream_t stream);
 mr_status launch_photon_build_tree(PhotonBuildWork *w, hipStream_t stream);
-// dev.rec / power / boxes are allocated and n, half, layers, layer_base set; d_dir: 2 m bytes, the quantised directions in heap order
+// dev.rec / power / boxes are allocated for photon_map_layout(dev, m); d_dir: 2 m bytes, the quantised directions in heap order
 mr_status launch_photon_build_pack(PhotonBuildWork *w, PhotonMapDev &dev, uint8_t *d_dir, hipStream_t stream);
 
 }  // namespace mr

@@ -9,13 +9,12 @@
 // under a total order (coordinate, then storage index), which yields the unique left-balanced tree; the device
 // gets three float4 planes in heap order (position+axis, de-quantised direction, power).
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <new>
-#include <numeric>
 
 #include "mr_internal.h"
+#include "mr_photon_tree.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -42,10 +41,8 @@ const DirTables &tables() { static DirTables t; return t; }
 // the two direction bytes of Photon_map::store (PhotonMap.cpp:268-283): the one place they are computed, for
 // mr_photon_map_store and for the photons mr_photon_map_build_device defers to the host
 inline void direction_bytes(float dx, float dy, float dz, uint8_t &theta_out, uint8_t &phi_out) {
-    const int theta = int(acos(dz) * (256.0 / M_PI));
-    theta_out = theta > 255 ? 255 : (uint8_t)theta;
-    const int phi = int(atan2(dy, dx) * (256.0 / (2.0 * M_PI)));
-    phi_out = phi > 255 ? 255 : (phi < 0 ? (uint8_t)(phi + 256) : (uint8_t)phi);
+    theta_out = theta_byte(int(acos(dz) * (256.0 / M_PI)));
+    phi_out = phi_byte(int(atan2(dy, dx) * (256.0 / (2.0 * M_PI))));
 }
 
 }  // namespace
@@ -75,16 +72,6 @@ struct mr_photon_map {
 
 namespace {
 
-// the median rule of balance_segment (PhotonMap.cpp:421-430): left-balanced split of [start, end]
-inline int left_balanced_median(int start, int end) {
-    const int n = end - start + 1;
-    int median = 1;
-    while (4 * median <= n) median += median;
-    if (3 * median <= n) { median += median; median += start - 1; }
-    else median = end - median + 1;
-    return median;
-}
-
 struct Balancer {
     mr_photon_map &m;
     std::vector<uint32_t> org;      // permutation being partitioned, 1-based segment positions
@@ -92,17 +79,14 @@ struct Balancer {
 
     explicit Balancer(mr_photon_map &pm) : m(pm) {
         org.resize(m.count() + 1);
-        std::iota(org.begin(), org.end(), 0u);      // org[p] = storage index p-1 for p >= 1 (slot 0 unused)
-        for (uint32_t p = 1; p < org.size(); p++) org[p] = p - 1;
+        for (uint32_t p = 1; p < org.size(); p++) org[p] = p - 1;      // storage index p-1 for p >= 1 (slot 0 unused)
         memcpy(bmin, m.bbox_min, sizeof(bmin));
         memcpy(bmax, m.bbox_max, sizeof(bmax));
     }
 
     void segment(int index, int start, int end) {
         const int median = left_balanced_median(start, end);
-        int axis = 2;                                               // PhotonMap.cpp:436-441
-        if ((bmax[0] - bmin[0]) > (bmax[1] - bmin[1]) && (bmax[0] - bmin[0]) > (bmax[2] - bmin[2])) axis = 0;
-        else if ((bmax[1] - bmin[1]) > (bmax[2] - bmin[2])) axis = 1;
+        const int axis = split_axis(bmin, bmax);
         const float *pos = m.pos.data();
         std::nth_element(org.begin() + start, org.begin() + median, org.begin() + end + 1,
                          [pos, axis](uint32_t a, uint32_t b) {
@@ -141,6 +125,61 @@ void release(mr_photon_map *m) {
     m->d_stats = nullptr;
     m->d_dir = nullptr;
     m->on_device = false;
+}
+
+// The device planes of a balanced map of n photons, from their allocation to the end of the call that fills them: commit()
+// swaps them into the map; the destructor frees what the holder then holds -- the new planes of a call that failed, or the
+// planes the map had before.  The hand-out counters are allocated once per map, by the first holder that finds none.
+struct Planes {
+    PhotonMapDev dev;
+    uint8_t *d_dir = nullptr;
+    size_t box_records = 0;                   // float4 in dev.boxes
+    ~Planes() { (void)hipFree(dev.rec); (void)hipFree(dev.power); (void)hipFree(dev.boxes); (void)hipFree(dev.work_counters); (void)hipFree(d_dir); }
+    mr_status allocate(const mr_photon_map *m, uint32_t n, bool with_dir) {
+        box_records = 4 * std::max<size_t>(photon_map_layout(dev, n), 1);
+        const size_t bytes = ((size_t)n + 1) * sizeof(float4);      // 1-based, slot 0 unused
+        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dev.rec), 2 * bytes));
+        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dev.power), bytes));
+        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dev.boxes), box_records * sizeof(float4)));
+        if (with_dir) MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dir), std::max<size_t>(2 * (size_t)n, 4)));
+        if (!m->dev.work_counters) {
+            MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dev.work_counters), kPhotonWorkCounters * sizeof(unsigned)));
+            MR_HIP_CHECK(hipMemset(dev.work_counters, 0, kPhotonWorkCounters * sizeof(unsigned)));
+        }
+        return MR_OK;
+    }
+    void commit(mr_photon_map *m) {
+        if (m->dev.work_counters) std::swap(dev.work_counters, m->dev.work_counters);      // the map keeps its own
+        std::swap(dev, m->dev);
+        std::swap(d_dir, m->d_dir);
+        m->on_device = true;
+    }
+};
+
+// one k-NN estimate on a resident map: the launch takes the next of the map's hand-out counters and the map's statistics
+mr_status estimate(mr_photon_map *m, const float *d_pos, const float *d_normal, unsigned long long n_queries, float max_dist, uint32_t nphotons,
+                   float *d_irrad, int32_t *d_found, float *d_r2, hipStream_t stream) {
+    unsigned *counter = m->dev.work_counters + (m->next_counter.fetch_add(1) % kPhotonWorkCounters);
+    return launch_irradiance(m->dev, counter, d_pos, d_normal, n_queries, max_dist, nphotons, d_irrad, d_found, d_r2, m->d_stats, stream);
+}
+
+// What mr_final_gather and mr_gather_level do between their own checks and their own accumulate step.  d_scratch, in floats:
+// [0, 3n) positions, [3n, 6n) normals (NaN = no query), [6n, 9n) the global map's estimate, [9n, 12n) the caustic map's.
+// d_irr[i]: where map i's estimate is, NULL without that map.
+mr_status gather_estimates(mr_scene *s, mr_photon_map *const maps[2], const mr_ray *d_rays, const mr_hit *d_hits, const float *d_normal,
+                           uint64_t n, float max_dist, uint32_t nphotons, float *d_scratch, uint64_t *d_counts, hipStream_t stream,
+                           float *d_irr[2]) {
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    float *d_pos = d_scratch, *d_nrm = d_scratch + 3 * n;
+    mr_status st = launch_gather_level_queries(s->dev, d_rays, d_hits, d_normal, n, d_pos, d_nrm, reinterpret_cast<unsigned long long *>(d_counts), stream);
+    if (st != MR_OK) return st;
+    for (int i = 0; i < 2; i++) {
+        d_irr[i] = maps[i] ? d_scratch + (6 + 3 * i) * n : nullptr;
+        if (!maps[i]) continue;
+        st = estimate(maps[i], d_pos, d_nrm, n, max_dist, nphotons, d_irr[i], nullptr, nullptr, stream);
+        if (st != MR_OK) return st;
+    }
+    return MR_OK;
 }
 
 }  // namespace
@@ -218,14 +257,12 @@ mr_status mr_photon_map_balance(mr_photon_map *m, uint32_t host_only) {
     }
     m->balanced = true;
     if (host_only) return MR_OK;
-    int count = 0;
-    hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || count <= 0)
-        return fail(MR_ERR_HIP, "no HIP device available (%s); this library has no CPU fallback",
-                    e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
-    if (m->device >= count) return fail(MR_ERR_INVALID, "device %d out of range [0,%d)", m->device, count);
-    MR_HIP_CHECK(hipSetDevice(m->device));
+    mr_status st = select_device(m->device);
+    if (st != MR_OK) return st;
     if (m->on_device) release(m);
+    Planes planes;                            // the map takes them once every upload has succeeded
+    st = planes.allocate(m, n, false);
+    if (st != MR_OK) return st;
     // heap-ordered planes, 1-based (slot 0 unused) so that children of i are 2i, 2i+1
     std::vector<float4> a(n + 1), d(n + 1), p(n + 1);
     const DirTables &t = tables();
@@ -243,12 +280,8 @@ mr_status mr_photon_map_balance(mr_photon_map *m, uint32_t host_only) {
     const size_t bytes = (size_t)(n + 1) * sizeof(float4);
     std::vector<float4> rec(2 * (size_t)(n + 1));
     for (uint32_t i = 0; i <= n; i++) { rec[2 * (size_t)i] = a[i]; rec[2 * (size_t)i + 1] = d[i]; }
-    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&m->dev.rec), 2 * bytes));
-    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&m->dev.power), bytes));
-    MR_HIP_CHECK(hipMemcpy(m->dev.rec, rec.data(), 2 * bytes, hipMemcpyHostToDevice));
-    MR_HIP_CHECK(hipMemcpy(m->dev.power, p.data(), bytes, hipMemcpyHostToDevice));
-    m->dev.n = (int32_t)n;
-    m->dev.half = (int32_t)n / 2 - 1;                               // half_stored_photons, PhotonMap.cpp:357
+    MR_HIP_CHECK(hipMemcpy(planes.dev.rec, rec.data(), 2 * bytes, hipMemcpyHostToDevice));
+    MR_HIP_CHECK(hipMemcpy(planes.dev.power, p.data(), bytes, hipMemcpyHostToDevice));
     // block boxes: bounds of every subtree (bottom-up over the heap), then per block root its own six levels and its subtree
     {
         const float inf = INFINITY;
@@ -264,11 +297,8 @@ mr_status mr_photon_map_balance(mr_photon_map *m, uint32_t host_only) {
                 slo[3 * (size_t)j + c] = lo; shi[3 * (size_t)j + c] = hi;
             }
         }
-        int layers = 0;
-        size_t total = 0;
-        for (uint64_t first = 1; first <= n && layers < 4; first <<= 6) { m->dev.layer_base[layers++] = (int32_t)total; total += (size_t)first; }
-        m->dev.layers = layers;
-        std::vector<float4> boxes(4 * std::max<size_t>(total, 1), make_float4(inf, inf, inf, 0.f));
+        const int layers = planes.dev.layers;
+        std::vector<float4> boxes(planes.box_records, make_float4(inf, inf, inf, 0.f));
         for (size_t i = 0; i < boxes.size(); i += 2) boxes[i + 1] = make_float4(-inf, -inf, -inf, 0.f);
         uint64_t first = 1;
         for (int L = 0; L < layers; L++, first <<= 6) {
@@ -281,21 +311,16 @@ mr_status mr_photon_map_balance(mr_photon_map *m, uint32_t host_only) {
                         const float pj[3] = {a[j].x, a[j].y, a[j].z};
                         for (int c = 0; c < 3; c++) { lo[c] = std::min(lo[c], pj[c]); hi[c] = std::max(hi[c], pj[c]); }
                     }
-                float4 *b = &boxes[4 * ((size_t)m->dev.layer_base[L] + (size_t)(r - first))];
+                float4 *b = &boxes[4 * ((size_t)planes.dev.layer_base[L] + (size_t)(r - first))];
                 b[0] = make_float4(lo[0], lo[1], lo[2], 0.f);
                 b[1] = make_float4(hi[0], hi[1], hi[2], 0.f);
                 b[2] = make_float4(slo[3 * r], slo[3 * r + 1], slo[3 * r + 2], 0.f);
                 b[3] = make_float4(shi[3 * r], shi[3 * r + 1], shi[3 * r + 2], 0.f);
             }
         }
-        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&m->dev.boxes), boxes.size() * sizeof(float4)));
-        MR_HIP_CHECK(hipMemcpy(m->dev.boxes, boxes.data(), boxes.size() * sizeof(float4), hipMemcpyHostToDevice));
+        MR_HIP_CHECK(hipMemcpy(planes.dev.boxes, boxes.data(), boxes.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
-    if (!m->dev.work_counters) {
-        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&m->dev.work_counters), kPhotonWorkCounters * sizeof(unsigned)));
-        MR_HIP_CHECK(hipMemset(m->dev.work_counters, 0, kPhotonWorkCounters * sizeof(unsigned)));
-    }
-    m->on_device = true;
+    planes.commit(m);
     return MR_OK;
 }
 
@@ -310,37 +335,24 @@ mr_status mr_photon_map_build_device(mr_photon_map *m, const mr_photon_record *d
                                     "(mr_photon_map_store, mr_photon_map_scale, mr_photon_map_balance)", (unsigned long long)n);
     if (m->balanced) return fail(MR_ERR_STATE, "photon map is immutable after mr_photon_map_balance");
     if (m->count() > 0) return fail(MR_ERR_STATE, "mr_photon_map_build_device: the map already holds %u photons; it builds an empty map", m->count());
-    int count = 0;
-    hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || count <= 0)
-        return fail(MR_ERR_HIP, "no HIP device available (%s); this library has no CPU fallback",
-                    e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
-    if (m->device >= count) return fail(MR_ERR_INVALID, "device %d out of range [0,%d)", m->device, count);
-    MR_HIP_CHECK(hipSetDevice(m->device));
+    mr_status st = select_device(m->device);
+    if (st != MR_OK) return st;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const uint32_t taken = (uint32_t)(n < m->max_photons ? n : m->max_photons);       // PhotonMap.cpp:260-261: silently full
     mr_photon_build_result res = mr_photon_build_result();
     res.stored = taken; res.dropped = n - taken;
-    const auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto ms = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
 
-    struct Work {                                   // the workspace and, until the build succeeds, the map's new planes
+    struct Work {                                   // the workspace
         PhotonBuildWork *w = nullptr;
-        PhotonMapDev dev;
-        uint8_t *d_dir = nullptr;
-        bool keep = false;
-        ~Work() {
-            photon_build_end(w);
-            if (!keep) { (void)hipFree(dev.rec); (void)hipFree(dev.power); (void)hipFree(dev.boxes); (void)hipFree(d_dir); }
-        }
+        ~Work() { photon_build_end(w); }
     } work;
     const DirTables &t = tables();
     static_assert(sizeof(DirTables) == 1024 * sizeof(float), "the four tables travel as one block");
-    mr_status st = photon_build_begin(taken, t.costheta, &work.w, stream);
+    st = photon_build_begin(taken, t.costheta, &work.w, stream);
     if (st != MR_OK) return st;
 
     // store: powers, box, direction bytes (the host's for the deferred photons), the non-finite flag
-    auto t0 = now();
+    auto t0 = std::chrono::steady_clock::now();
     PhotonBuildStatus status;
     float lo[3], hi[3];
     st = launch_photon_build_store(work.w, d_records, scale, &status, lo, hi, stream);
@@ -364,46 +376,32 @@ mr_status mr_photon_map_build_device(mr_photon_map *m, const mr_photon_record *d
         MR_HIP_CHECK(hipStreamSynchronize(stream));                 // `list` leaves scope
     }
     res.deferred = status.deferred;
-    res.store_ms = ms(t0);
+    res.store_ms = ms_since(t0);
 
     // balance: three sorted lists, then one heap level per step
-    t0 = now();
+    t0 = std::chrono::steady_clock::now();
     st = launch_photon_build_tree(work.w, stream);
     if (st != MR_OK) return st;
     MR_HIP_CHECK(hipStreamSynchronize(stream));
-    res.balance_ms = ms(t0);
+    res.balance_ms = ms_since(t0);
 
     // pack: the planes in heap order and the block boxes, laid out as mr_photon_map_balance lays them out
-    t0 = now();
-    const size_t bytes = ((size_t)taken + 1) * sizeof(float4);
-    work.dev.n = (int32_t)taken;
-    work.dev.half = (int32_t)taken / 2 - 1;                         // half_stored_photons, PhotonMap.cpp:357
-    size_t total = 0;
-    for (uint64_t first = 1; first <= taken && work.dev.layers < 4; first <<= 6) { work.dev.layer_base[work.dev.layers++] = (int32_t)total; total += (size_t)first; }
-    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&work.dev.rec), 2 * bytes));
-    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&work.dev.power), bytes));
-    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&work.dev.boxes), 4 * std::max<size_t>(total, 1) * sizeof(float4)));
-    MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&work.d_dir), std::max<size_t>(2 * (size_t)taken, 4)));
-    st = launch_photon_build_pack(work.w, work.dev, work.d_dir, stream);
+    t0 = std::chrono::steady_clock::now();
+    Planes planes;                                  // the map takes them once the build has succeeded
+    st = planes.allocate(m, taken, true);
+    if (st != MR_OK) return st;
+    st = launch_photon_build_pack(work.w, planes.dev, planes.d_dir, stream);
     if (st != MR_OK) return st;
     MR_HIP_CHECK(hipStreamSynchronize(stream));
-    if (!m->dev.work_counters) {
-        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&m->dev.work_counters), kPhotonWorkCounters * sizeof(unsigned)));
-        MR_HIP_CHECK(hipMemset(m->dev.work_counters, 0, kPhotonWorkCounters * sizeof(unsigned)));
-    }
-    res.pack_ms = ms(t0);
+    res.pack_ms = ms_since(t0);
 
-    work.dev.work_counters = m->dev.work_counters;
-    m->dev = work.dev;
-    m->d_dir = work.d_dir;
-    work.keep = true;
+    planes.commit(m);
     memcpy(m->bbox_min, lo, sizeof(lo));
     memcpy(m->bbox_max, hi, sizeof(hi));
     m->prev_scale = taken;
     m->device_built = true;
     m->device_stored = taken;
     m->balanced = true;
-    m->on_device = true;
     if (result) *result = res;
     return MR_OK;
 }
@@ -458,8 +456,7 @@ mr_status mr_irradiance_estimate(mr_photon_map *m, const float *d_pos, const flo
     if (!d_pos || !d_normal || !d_irrad) return fail(MR_ERR_INVALID, "NULL argument");
     if (nphotons == 0 || nphotons > kKnnMaxK) return fail(MR_ERR_INVALID, "nphotons must be in [1, %d]", kKnnMaxK);
     MR_HIP_CHECK(hipSetDevice(m->device));
-    return launch_irradiance(m->dev, m->dev.work_counters + (m->next_counter.fetch_add(1) % kPhotonWorkCounters), d_pos, d_normal, n_queries, max_dist, nphotons, d_irrad, d_found, d_r2, m->d_stats,
-                             static_cast<hipStream_t>(stream));
+    return estimate(m, d_pos, d_normal, n_queries, max_dist, nphotons, d_irrad, d_found, d_r2, static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_photon_map_count_stats(mr_photon_map *m, int32_t enable) {
@@ -504,16 +501,9 @@ mr_status mr_final_gather(mr_scene *s, mr_photon_map *global_map, mr_photon_map 
     }
     if (n == 0) return MR_OK;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    MR_HIP_CHECK(hipSetDevice(s->device));
-    float *d_pos = d_scratch, *d_nrm = d_scratch + 3 * n;
-    float *d_irr[2] = {d_scratch + 6 * n, d_scratch + 9 * n};
-    mr_status st = launch_gather_queries(s->dev, d_rays, d_hits, n, d_pos, d_nrm, stream);
+    float *d_irr[2];
+    mr_status st = gather_estimates(s, maps, d_rays, d_hits, nullptr, n, max_dist, nphotons, d_scratch, nullptr, stream, d_irr);
     if (st != MR_OK) return st;
-    for (int i = 0; i < 2; i++) {
-        if (!maps[i]) { d_irr[i] = nullptr; continue; }
-        st = launch_irradiance(maps[i]->dev, maps[i]->dev.work_counters + (maps[i]->next_counter.fetch_add(1) % kPhotonWorkCounters), d_pos, d_nrm, n, max_dist, nphotons, d_irr[i], nullptr, nullptr, maps[i]->d_stats, stream);
-        if (st != MR_OK) return st;
-    }
     return launch_gather_accumulate(d_irr[0], d_irr[1], n, spp, d_rgb, stream);
 }
 
@@ -541,16 +531,9 @@ mr_status mr_gather_level(mr_scene *s, mr_photon_map *global_map, mr_photon_map 
                                   "whose normal comes from the surface pass: call mr_hit_surface, then mr_gather_level with its normal buffer");
     if (n == 0) return MR_OK;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    MR_HIP_CHECK(hipSetDevice(s->device));
-    float *d_pos = d_scratch, *d_nrm = d_scratch + 3 * n;
-    float *d_irr[2] = {d_scratch + 6 * n, d_scratch + 9 * n};
-    mr_status st = launch_gather_level_queries(s->dev, d_rays, d_hits, d_normal, n, d_pos, d_nrm, reinterpret_cast<unsigned long long *>(d_counts), stream);
+    float *d_irr[2];
+    mr_status st = gather_estimates(s, maps, d_rays, d_hits, d_normal, n, max_dist, nphotons, d_scratch, d_counts, stream, d_irr);
     if (st != MR_OK) return st;
-    for (int i = 0; i < 2; i++) {
-        if (!maps[i]) { d_irr[i] = nullptr; continue; }
-        st = launch_irradiance(maps[i]->dev, maps[i]->dev.work_counters + (maps[i]->next_counter.fetch_add(1) % kPhotonWorkCounters), d_pos, d_nrm, n, max_dist, nphotons, d_irr[i], nullptr, nullptr, maps[i]->d_stats, stream);
-        if (st != MR_OK) return st;
-    }
     if (!d_irr[0] && !d_irr[1] && !d_ray_rgb) return MR_OK;      // no map: nothing to add
     return launch_gather_level_accumulate(d_irr[0], d_irr[1], d_weights, d_pixels, n, spp, d_rgb, d_ray_rgb, stream);
 }

@@ -22,11 +22,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
 #include <new>
 
 #include "mr_internal.h"
 #include "mr_launch.h"
+#include "mr_photon_tree.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -47,15 +47,6 @@ struct BuildNode {
     int32_t pad[2];
 };
 static_assert(sizeof(BuildNode) == 64, "one node per 64 bytes");
-
-__device__ __forceinline__ uint32_t order_key(float f) {            // ascending uint32 <=> ascending float, -0 == +0
-    uint32_t b = __float_as_uint(f);
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_float(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
 
 // ---- store --------------------------------------------------------------------------------------------------------------
 // The scaled angle decides a byte on the device only when it is finite and farther than 2^-20 from every whole number.
@@ -89,8 +80,8 @@ __global__ __launch_bounds__(kBlock) void build_store_kernel(const float *record
             const double f = atan2((double)d[1], (double)d[0]) * (256.0 / (2.0 * M_PI));
             if (decided(t) && decided(f)) {
                 const int theta = int(t), phi = int(f);
-                dir[2 * (size_t)i] = theta > 255 ? 255 : (uint8_t)theta;
-                dir[2 * (size_t)i + 1] = phi > 255 ? 255 : (phi < 0 ? (uint8_t)(phi + 256) : (uint8_t)phi);
+                dir[2 * (size_t)i] = theta_byte(theta);
+                dir[2 * (size_t)i + 1] = phi_byte(phi);
             } else {
                 defer = true;
             }
@@ -243,16 +234,6 @@ __global__ __launch_bounds__(kBlock) void build_scan_sums_kernel(uint32_t *sums,
 }
 
 // ---- one level ------------------------------------------------------------------------------------------------------------
-// the median rule of balance_segment (PhotonMap.cpp:421-430), as left_balanced_median of mr_photon.cpp
-__device__ __forceinline__ int32_t left_balanced_median(int32_t start, int32_t end) {
-    const int32_t n = end - start + 1;
-    int32_t median = 1;
-    while (4 * median <= n) median += median;
-    if (3 * median <= n) { median += median; median += start - 1; }
-    else median = end - median + 1;
-    return median;
-}
-
 // nodes first ... last of one heap level
 __global__ __launch_bounds__(kBlock) void build_node_kernel(BuildNode *nodes, uint32_t first, uint32_t last, uint32_t m, const float *pos,
                                                             const uint32_t *lists, uint32_t *heap, int32_t *plane) {
@@ -265,10 +246,7 @@ __global__ __launch_bounds__(kBlock) void build_node_kernel(BuildNode *nodes, ui
         plane[h] = 0;
         return;
     }
-    const float *bmin = nd.lo, *bmax = nd.hi;
-    int axis = 2;                                                       // PhotonMap.cpp:436-441
-    if ((bmax[0] - bmin[0]) > (bmax[1] - bmin[1]) && (bmax[0] - bmin[0]) > (bmax[2] - bmin[2])) axis = 0;
-    else if ((bmax[1] - bmin[1]) > (bmax[2] - bmin[2])) axis = 1;
+    const int axis = split_axis(nd.lo, nd.hi);
     const int32_t median = left_balanced_median(nd.start, nd.end);
     const uint32_t photon = lists[(size_t)axis * m + median];
     if (photon >= m) return;                                            // never
@@ -489,9 +467,7 @@ mr_status photon_build_begin(uint32_t m, const float *tables1024, PhotonBuildWor
     *out = w;
     PhotonBuildStatus st;
     const float big = 1e8f;                                          // Photon_map's initial box (PhotonMap.cpp:36-38)
-    uint32_t kmax, kmin;
-    { uint32_t b; float f = big; memcpy(&b, &f, 4); kmax = b | 0x80000000u; f = -big; memcpy(&b, &f, 4); kmin = ~b; }
-    for (int c = 0; c < 3; c++) { st.lo[c] = kmax; st.hi[c] = kmin; }
+    for (int c = 0; c < 3; c++) { st.lo[c] = order_key(big); st.hi[c] = order_key(-big); }
     st.nonfinite = 0; st.deferred = 0;
     MR_HIP_CHECK(hipMemcpyAsync(w->status, &st, sizeof(st), hipMemcpyHostToDevice, stream));
     MR_HIP_CHECK(hipMemcpyAsync(w->tables, tables1024, 1024 * sizeof(float), hipMemcpyHostToDevice, stream));
@@ -515,11 +491,7 @@ mr_status launch_photon_build_store(PhotonBuildWork *w, const mr_photon_record *
     MR_HIP_CHECK(hipGetLastError());
     MR_HIP_CHECK(hipMemcpyAsync(status, w->status, sizeof(*status), hipMemcpyDeviceToHost, stream));
     MR_HIP_CHECK(hipStreamSynchronize(stream));
-    for (int c = 0; c < 3; c++) {
-        const uint32_t kl = status->lo[c], kh = status->hi[c];
-        const uint32_t bl = (kl & 0x80000000u) ? (kl & 0x7FFFFFFFu) : ~kl, bh = (kh & 0x80000000u) ? (kh & 0x7FFFFFFFu) : ~kh;
-        memcpy(&lo[c], &bl, 4); memcpy(&hi[c], &bh, 4);
-    }
+    for (int c = 0; c < 3; c++) { lo[c] = key_float(status->lo[c]); hi[c] = key_float(status->hi[c]); }
     return MR_OK;
 }
 
@@ -582,8 +554,7 @@ mr_status launch_photon_build_pack(PhotonBuildWork *w, PhotonMapDev &dev, uint8_
     BoxLayers bl = {};
     bl.layers = dev.layers;
     for (int l = 0; l < 4; l++) bl.base[l] = dev.layer_base[l];
-    uint64_t total = 0, first = 1;
-    for (int l = 0; l < dev.layers; l++, first <<= 6) total += first;
+    const size_t total = photon_map_layout(dev, m);                    // what the caller laid dev out with
     bl.total = (uint32_t)total;
     hipLaunchKernelGGL(build_boxes_kernel, dim3(blocks_of(total ? total : 1)), dim3(kBlock), 0, stream, dev.rec, w->sub, m, bl, dev.boxes);
     MR_HIP_CHECK(hipGetLastError());

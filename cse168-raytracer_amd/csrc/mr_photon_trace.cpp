@@ -27,10 +27,6 @@ constexpr uint64_t kRoundRecords = 5ull << 20;                        // record 
 struct Timing { double kernel_ms = 0, readback_ms = 0, store_ms = 0; };
 thread_local Timing g_timing;
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 struct Buffers : PhotonRoundBuffers {
     ~Buffers() {
         (void)hipFree(slots); (void)hipFree(compact); (void)hipFree(words); (void)hipFree(offsets); (void)hipFree(next); (void)hipFree(header);

@@ -4,6 +4,8 @@
 //                       (Phong.cpp:44-160), Scene::trace's normal normalisation (Scene.cpp:262),
 //                       the miss colour (Scene.cpp:340,685) and the per-pixel sample average
 //                       (Scene.cpp:126-139) into a linear float RGB buffer (tempImage, Scene.cpp:106)
+//   gather_accumulate   the last step of mr_final_gather: a pixel's photon-map terms summed in sample order (its queries
+//                       come from the query kernel of mr_gather_level.hip)
 //   tonemap             sigmoid(6v-3) and the 8-bit mapping (Scene.cpp:87-91,177-202; Image.cpp:44-50)
 // Floating point here is tolerance-parity (powf, expf differ from libm in the last ulps); the hot
 // path's bit-exactness is unaffected.
@@ -90,26 +92,10 @@ __global__ __launch_bounds__(kBlock) void shade_samples_kernel(ShadeArgs a, unsi
     }
 }
 
-// Queries of Scene::traceScene's photon-map term (Scene.cpp:285-292): hit point and the normalised normal of every
-// hit whose material is diffuse (Phong::isDiffuse, Phong.cpp:39-42); a NaN normal marks "no query".
-__global__ __launch_bounds__(kBlock) void gather_queries_kernel(SurfacePtrs m, const float *mats, const uint32_t *prim_mat,
-                                                                const mr_ray *rays, const mr_hit *hits, unsigned long long n,
-                                                                float *pos, float *nrm) {
-    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
-    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += stride) {
-        const float4 h = reinterpret_cast<const float4 *>(hits)[k];
-        const uint32_t prim = __float_as_uint(h.y);
-        float P[3] = {0.f, 0.f, 0.f}, N[3];
-        N[0] = N[1] = N[2] = __uint_as_float(0x7fc00000u);
-        if (prim != MR_MISS) {
-            const rec::MeshMat mm = {m, mats, prim_mat};
-            if (rec::any_pos(rec::material_of(mm, prim))) rec::surface_point(mm, rays, k, h, P, N);
-        }
-        for (int c = 0; c < 3; c++) { pos[3 * k + c] = P[c]; nrm[3 * k + c] = N[c]; }
-    }
-}
-
-// shadeResult += irradiance + caustic (Scene.cpp:298), averaged over the pixel's samples like the direct term
+// mr_final_gather's last step: shadeResult += irradiance + caustic (Scene.cpp:298), averaged over the pixel's samples like the
+// direct term -- one thread per pixel channel sums the samples in sample order and adds one float to the pixel.  (Its queries
+// come from gather_level_queries_kernel of mr_gather_level.hip, the one query kernel; mr_gather_level's own accumulate kernel
+// adds wave runs with float atomics, which rounds differently, so the two accumulate kernels stay apart.)
 __global__ __launch_bounds__(kBlock) void gather_accumulate_kernel(const float *irr_a, const float *irr_b, unsigned long long n_pixels,
                                                                    uint32_t spp, float *rgb) {
     const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
@@ -185,15 +171,6 @@ mr_status launch_shade(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit
         hipLaunchKernelGGL(shade_samples_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, a, n);
     else
         hipLaunchKernelGGL(shade_pixels_kernel, dim3(grid_for(a.n_pixels)), dim3(kBlock), 0, stream, a);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
-}
-
-mr_status launch_gather_queries(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, unsigned long long n,
-                                float *d_pos, float *d_nrm, hipStream_t stream) {
-    if (n == 0) return MR_OK;
-    hipLaunchKernelGGL(gather_queries_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, surface_ptrs(ds), ds.materials,
-                       ds.prim_material, d_rays, d_hits, n, d_pos, d_nrm);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;
 }

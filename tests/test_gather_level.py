@@ -495,3 +495,73 @@ def test_plain_equivalence_with_final_gather(oracle, miro):
     scene.gather_level(None, None, lv.rays, lv.hits, lv.n, scratch, a, max_dist=MAX_DIST, nphotons=K_GATHER)
     torch.cuda.synchronize()
     assert a.cpu().numpy().tobytes() == a_h.tobytes()
+
+
+# a triangle mesh (a diffuse quad, a glass triangle in front of it), a diffuse and a mirror sphere, a diffuse floor plane, open sky
+QUERY_SCENE = dict(
+    models=[], floor=None,
+    objects=[("tri", (-0.5, 0.0, 0.0, 0.5, 0.0, 0.0, 0.5, 1.0, 0.0), (0.0, 0.0, 1.0) * 3),
+             ("tri", (-0.5, 0.0, 0.0, 0.5, 1.0, 0.0, -0.5, 1.0, 0.0), (0.0, 0.0, 1.0) * 3),
+             ("tri", (-0.4, 0.0, 1.5, 0.4, 0.0, 1.5, 0.0, 0.6, 1.5), (0.0, 0.0, 1.0) * 3),
+             ("sphere", (-1.4, 0.6, 0.0), 0.6), ("sphere", (1.4, 0.6, 0.0), 0.6),
+             ("plane", (0.0, 1.0, 0.0), (0.0, 0.0, 0.0), 0)],
+    materials=[((0.7, 0.6, 0.5), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), float("inf"), 1.0),
+               ((0.0, 0.0, 0.0), (0.9, 0.9, 0.9), (0.0, 0.0, 0.0), float("inf"), 1.0),
+               ((0.0, 0.0, 0.0), (0.05, 0.05, 0.05), (0.9, 0.9, 0.9), float("inf"), 1.5)],
+    prim_material=[0, 0, 2, 0, 1],
+    eye=(0.0, 1.5, 6.0), lookat=(0.0, 0.5, 0.0), up=(0.0, 1.0, 0.0), fov=45.0)
+
+
+def query_kinds(desc, prim):
+    """per hit record: is it a query, and on which kind of object (0 triangle, 1 sphere, 2 plane; -1 miss)"""
+    prim = np.asarray(prim, np.uint32)
+    bounded = [o[0] for o in desc["objects"] if o[0] != "plane"]
+    is_sphere = np.array([k == "sphere" for k in bounded] + [False])
+    hit = prim != np.uint32(MISS)
+    plane = hit & ((prim & np.uint32(PLANE_BIT)) != 0)
+    kind = np.where(plane, 2, np.where(is_sphere[np.where(hit & ~plane, prim, len(bounded))], 1, 0))
+    return diffuse_hits(desc, prim), np.where(hit, kind, -1)
+
+
+@pytest.mark.gpu
+def test_final_gather_and_gather_level_build_the_same_queries(miro):
+    """mr_final_gather builds its queries with the kernel of mr_gather_level (d_normal = NULL): on one traced batch of 24 x 17 = 408
+    rays (one full workgroup, one partial one, the last wave partial) at one sample per pixel, the first 6 n floats of the scratch --
+    positions, then normals with NaN = no query -- are byte-equal after mr_final_gather and after mr_gather_level(d_normal =
+    d_weights = d_pixels = NULL).  The batch holds a query on a triangle, on a sphere and on a plane, a hit that is no query (mirror,
+    glass) and a miss."""
+    import torch
+    from miro_amd import scenes
+    desc, W, H = QUERY_SCENE, 24, 17
+    n = W * H
+    scene = miro.Scene(0)
+    scenes.populate(scene, desc)
+    scene.set_materials(desc["materials"], desc["prim_material"])
+    scene.build(4)
+    rays = torch.empty((n, 8), dtype=torch.float32, device="cuda")
+    hits = torch.empty((n, 4), dtype=torch.float32, device="cuda")
+    scene.gen_eye_rays(camera(miro, desc), W, H, rays)
+    scene.trace_device(rays, n, hits)
+    torch.cuda.synchronize()
+    prim = hits.cpu().numpy().view(miro.HIT_DTYPE).reshape(-1)["prim"]
+    query, kind = query_kinds(desc, prim)
+    print("%d rays: queries on triangles / spheres / planes %s, %d hits that are no query, %d misses"
+          % (n, [int((query & (kind == k)).sum()) for k in range(3)], (~query & (kind >= 0)).sum(), (kind < 0).sum()))
+    assert n == 408 and all((query & (kind == k)).any() for k in range(3)) and (~query & (kind >= 0)).any() and (kind < 0).any()
+    rng = np.random.RandomState(7)
+    g = miro.PhotonMap(200)
+    pos = (rng.rand(200, 3) * [4.0, 1.2, 2.0] - [2.0, 0.0, 0.5]).astype(F)
+    g.store(np.full((200, 3), 0.01, F), pos, np.tile(np.array([0.0, -1.0, 0.0], F), (200, 1)))
+    g.balance()
+    seen = []
+    for final in (True, False):
+        scratch = torch.full((12 * n,), -3.0, dtype=torch.float32, device="cuda")
+        rgb = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+        if final:
+            scene.final_gather(g, None, rays, hits, n, scratch, rgb, max_dist=1.0, nphotons=20)
+        else:
+            scene.gather_level(g, None, rays, hits, n, scratch, rgb, d_normal=None, d_weights=None, d_pixels=None, max_dist=1.0, nphotons=20)
+        torch.cuda.synchronize()
+        seen.append(scratch[:6 * n].cpu().numpy())
+    assert np.array_equal(np.isnan(seen[0].reshape(2, n, 3)[1]).all(axis=1), ~query)
+    assert seen[0].tobytes() == seen[1].tobytes()
