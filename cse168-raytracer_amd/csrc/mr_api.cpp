@@ -1348,7 +1348,6 @@ mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, ui
                 if (!std::isfinite(in.color1[c]) || !std::isfinite(in.color2[c])) return fail(MR_ERR_INVALID, "texture %u: the pivot (color1) and color2 must be finite", i);
             if (!std::isfinite(in.scale)) return fail(MR_ERR_INVALID, "texture %u: the scale must be finite", i);
             h.procedural = true;
-            h.solid = true;
         } else {
             if (in.W == 0 || in.H == 0 || !in.pixels) return fail(MR_ERR_INVALID, "texture %u: an image needs pixels and W, H > 0", i);
             if (in.W > 65536u || in.H > 65536u) return fail(MR_ERR_INVALID, "texture %u: image of %u x %u pixels, at most 65536 each way", i, in.W, in.H);
@@ -1478,9 +1477,6 @@ mr_status mr_hit_surface(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits
     TexParams tex;
     tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
     if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
-    if (s->tex.solid)
-        return launch_hit_surface_solid(s->dev, tex, d_rays, d_hits, n, d_color, d_normal, reinterpret_cast<unsigned long long *>(d_counts),
-                                        static_cast<hipStream_t>(stream));
     return launch_hit_surface(s->dev, tex, d_rays, d_hits, n, d_color, d_normal, reinterpret_cast<unsigned long long *>(d_counts),
                               static_cast<hipStream_t>(stream));
 }

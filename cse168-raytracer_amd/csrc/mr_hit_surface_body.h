@@ -1,20 +1,16 @@
 // mr_hit_surface_body.h -- diffuseColor (Phong.cpp:51-56; Scene.cpp:545-549 in the photon roulette) and HitInfo::N as
-// Scene::trace leaves it (Scene.cpp:234-263) for ONE hit, as a device function: what the loop of solid_surface_kernel
-// (mr_solid.hip) does per hit, for the photon walk of mr_photon_walk_surface.hip.
+// Scene::trace leaves it (Scene.cpp:234-263) for ONE hit, as a device function.  Two callers: the loop of hit_surface_kernel
+// (mr_procedural.hip; mr_hit_surface) and the photon walk of mr_photon_walk_surface.hip.
 //
 // The caller brings the hit point and the object's own normal (surface_od<true> of mr_surface.h); this function does the
 // material -> texture id step, reads the kind, maps the point with uv_of for the UV kinds only, looks the colour up in one of
 // the seven arms (or takes the plain material's kd), bump-maps the normal of a STONE hit and normalises.  The arms are the
-// shared functions of mr_texture.h, mr_procedural_body.h and mr_solid_body.h, in the surface pass's order, and every unit is
-// compiled with -ffp-contract=off: the colour and the normal are the bits mr_hit_surface writes for the same ray and hit
+// shared functions of mr_texture.h, mr_procedural_body.h and mr_solid_body.h, and every unit is compiled with
+// -ffp-contract=off: the photon walk's colour and normal are the bits mr_hit_surface writes for the same ray and hit
 // (tests/test_photon_walk_surface.py holds the two together).  The noise arms sit behind one branch: a wave none of whose
 // hits lies on a STONE / STEM / UVW material skips them whole.
 //
-// solid_surface_kernel keeps its own copy of these thirty lines: calling this function from it changed its code (DESIGN
-// section 5b), and its recorded build is the one verified on the GPU.
-//
-// t.mat_tex may be nullptr (a scene without a texture table: every hit is plain Phong), as in procedural_surface_kernel.
-// Device code only.
+// t.mat_tex may be nullptr (a scene without a texture table: every hit is plain Phong).  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>

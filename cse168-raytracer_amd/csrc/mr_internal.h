@@ -294,7 +294,6 @@ struct HostTextures {
     size_t texel_base = 0, mat_base = 0;       // offsets into blob, in float4
     std::vector<float4> blob;                  // empty: the scene has no texture table
     bool procedural = false;                   // some texture is a STONE, a STEM or a UVW kind: only the _surface calls shade such a scene
-    bool solid = false;                        // some texture is a UVW kind (PETAL, LEAF, FLOWER_CENTER): mr_solid.hip's surface pass
 };
 struct TexParams {                             // the table as the kernels take it
     const float4 *recs;                        // 3 per texture: (kind, W, H, first texel as bits) (color1 | max_intensity, hdr) (color2)
@@ -319,9 +318,10 @@ mr_status launch_hit_uv(const DeviceScene &ds, const mr_ray *d_rays, const mr_hi
 mr_status launch_texture_lookup(const TexParams &tex, uint32_t texture, const float *d_uv, unsigned long long n, float *d_rgb,
                                 unsigned long long *d_counts, hipStream_t stream);
 
-// Procedural textures and bump-mapped normals (mr_procedural.hip): the per-hit surface pass, the light-list and accumulate
-// kernels that read its two buffers, and the inspection kernels.  launch_hit_surface takes a TexParams whose recs / mat_tex
-// are nullptr for a scene without a texture table.
+// Procedural and UVW textures and bump-mapped normals (mr_procedural.hip): the per-hit surface pass of every scene, the
+// light-list and accumulate kernels that read its two buffers, and the inspection kernels (launch_texture_lookup3: lookup3D of
+// one UVW texture at d_p).  launch_hit_surface takes a TexParams whose recs / mat_tex are nullptr for a scene without a
+// texture table.
 mr_status launch_hit_surface(const DeviceScene &ds, const TexParams &tex, const mr_ray *d_rays, const mr_hit *d_hits, unsigned long long n,
                              float *d_color, float *d_normal, unsigned long long *d_counts, hipStream_t stream);
 mr_status launch_shade_lights_surf(const DeviceScene &ds, const ShadeLight *lights, uint32_t n_lights, const mr_ray *d_rays,
@@ -335,9 +335,6 @@ mr_status launch_texture_lookup_proc(const TexParams &tex, uint32_t texture, con
                                      unsigned long long *d_counts, hipStream_t stream);
 mr_status launch_bump_height(bool stone, float scale, const float *d_uv, unsigned long long n, float *d_height, hipStream_t stream);
 mr_status launch_noise_probe(uint32_t which, const float *d_in, unsigned long long n, float *d_out, hipStream_t stream);
-// UVW textures (mr_solid.hip): launch_hit_surface for a scene whose table holds one, and lookup3D of one of them at d_p
-mr_status launch_hit_surface_solid(const DeviceScene &ds, const TexParams &tex, const mr_ray *d_rays, const mr_hit *d_hits,
-                                   unsigned long long n, float *d_color, float *d_normal, unsigned long long *d_counts, hipStream_t stream);
 mr_status launch_texture_lookup3(const TexParams &tex, uint32_t texture, const float *d_p, unsigned long long n, float *d_rgb,
                                  float *d_coords, unsigned long long *d_counts, hipStream_t stream);
 // the first half of launch_shade_accumulate (mr_bounce.hip): Phong.cpp:97-113's light scale per ray from the traced shadow rays

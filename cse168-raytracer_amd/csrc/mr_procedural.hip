@@ -2,17 +2,20 @@
 // (Texture.h:192-212), StoneTexture::lookup2D and ::bumpHeight2D (Texture.cpp:358-440) over the noise of mr_noise.h, and the
 // normal as Scene.cpp:234-263 leaves it.
 //
-//   procedural_surface_kernel      per hit of a traced batch: diffuseColor (Phong.cpp:51-56) and the bumped, normalised normal,
-//                                  into two per-ray buffers of three floats each (mr_hit_surface)
+//   hit_surface_kernel             per hit of a traced batch: diffuseColor (Phong.cpp:51-56) and the bumped, normalised normal,
+//                                  into two per-ray buffers of three floats each (mr_hit_surface).  The one surface pass: every
+//                                  scene, all seven texture kinds in any mixture or no table at all; the per-hit step is
+//                                  hit_color_normal (mr_hit_surface_body.h), which the photon walk on textured scenes calls too
 //   shade_lights_surf_kernel       shade_lights_kernel (mr_lights.hip) reading that colour and normal instead of computing
 //                                  them: shade_lights_body<.., kColorSurface>
 //   shade_accumulate_surf_kernel   shade_accumulate_kernel (mr_bounce.hip), the same way: shade_accumulate_body<kColorSurface>
 //   texture_lookup_proc_kernel     lookup2D of a STONE / STEM texture for a batch of coordinates (mr_texture_lookup)
+//   texture_lookup3_kernel         lookup3D of one UVW texture (PETAL, LEAF, FLOWER_CENTER) for a batch of points
+//                                  (mr_texture_lookup3): the UVW inspection kernel lives here with the pass that serves its kinds
 //   bump_height_kernel             bumpHeight2D of one texture for a batch of coordinates (mr_texture_bump_height)
 //   noise_probe_kernel             PerlinNoise::noise / WorleyNoise::noise2D of order 3 themselves (mr_noise_probe)
 //
-// The lookups and the bump themselves are the device functions of mr_procedural_body.h, shared with mr_solid.hip, whose surface
-// pass serves the scenes that hold a UVW texture as well.
+// The lookups and the bump themselves are the device functions of mr_procedural_body.h, the UVW arms those of mr_solid_body.h.
 //
 // Why a pass of its own: a stone hit costs five three-point Worley searches and up to 5 + 4 * 7 Perlin evaluations.  The
 // textured light-list kernel already spills in its worst variant; the surface pass has no traversal, so it
@@ -27,13 +30,14 @@
 #include <hip/hip_runtime.h>
 
 #include "mr_accumulate_body.h"
+#include "mr_hit_surface_body.h"
 #include "mr_internal.h"
 #include "mr_launch.h"
 #include "mr_lights_body.h"
 #include "mr_noise.h"
 #include "mr_procedural_body.h"
+#include "mr_solid_body.h"
 #include "mr_texture.h"
-#include "mr_uv.h"
 
 namespace mr {
 namespace {
@@ -48,43 +52,28 @@ struct SurfaceArgs {
     unsigned long long *counts;  // optional: [0] += lookups the reference leaves undefined
 };
 
-__global__ __launch_bounds__(kBlock) void procedural_surface_kernel(SurfaceArgs a) {
+__global__ __launch_bounds__(kBlock) void hit_surface_kernel(SurfaceArgs a) {
     __shared__ uint32_t s_tab[128];
     const NoiseTables nt = stage_noise_tables(s_tab);
     const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
     unsigned my_undefined = 0;
+    // hit_color_normal's test of mat_tex, taken out of the loop: a scene without a texture table runs a call that is compiled
+    // knowing it, the plain arm alone (measured: DESIGN section 4)
+    const bool table = a.t.mat_tex != nullptr;
     for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < a.n; k += stride) {
         const float4 h = reinterpret_cast<const float4 *>(a.hits)[k];
         const uint32_t prim = __float_as_uint(h.y);
         if (prim == MR_MISS) continue;
         float P[3], N[3], col[3];
         surface<true>(a.m.s, a.rays, k, h.x, prim, h.z, h.w, P, N);
-        const uint32_t mid = material_id(a.m.s, a.m.prim_mat, prim);
-        const uint32_t tex = a.t.mat_tex ? a.t.mat_tex[mid] : kNoTexture;
         bool ok = true;
-        if (tex == kNoTexture) {
-            const float *mt = a.m.mats + 11 * (size_t)mid;
-            col[0] = mt[0]; col[1] = mt[1]; col[2] = mt[2];
+        if (table) {
+            hit_color_normal(a.m, a.t, nt, prim, P, N, col, ok);
         } else {
-            const UvPtrs um = {a.m.s, a.t.texcoords, a.t.ti};
-            float u, v;
-            uv_of(um, prim, P, u, v);
-            const float4 q0 = a.t.recs[3 * (size_t)tex];
-            const uint32_t kind = __float_as_uint(q0.x);
-            // the noise is behind this branch: a wave none of whose hits lies on a procedural material skips it whole
-            if (kind == kTexStone || kind == kTexStem) {
-                const float scale = a.t.recs[3 * (size_t)tex + 1].w;
-                if (kind == kTexStem) {
-                    stem_color(nt, scale, u, v, col, ok);
-                } else {
-                    stone_color(nt, scale, u, v, col, ok);
-                    bump_normal(nt, scale, u, v, N, ok);
-                }
-            } else {
-                ok = texture_color(a.t, tex, u, v, col);
-            }
+            TexParams t0 = a.t;
+            t0.mat_tex = nullptr;
+            hit_color_normal(a.m, t0, nt, prim, P, N, col, ok);
         }
-        normalize3(N);                                                   // Scene.cpp:262
         if (!ok) my_undefined++;
         a.color[3 * k] = col[0]; a.color[3 * k + 1] = col[1]; a.color[3 * k + 2] = col[2];
         a.normal[3 * k] = N[0]; a.normal[3 * k + 1] = N[1]; a.normal[3 * k + 2] = N[2];
@@ -107,6 +96,27 @@ __global__ __launch_bounds__(kBlock) void texture_lookup_proc_kernel(TexParams t
         else stone_color(nt, scale, uv[2 * k], uv[2 * k + 1], c, ok);
         if (!ok) my_undefined++;
         rgb[3 * k] = c[0]; rgb[3 * k + 1] = c[1]; rgb[3 * k + 2] = c[2];
+    }
+    if (counts) workgroup_add<kBlock>(my_undefined, &counts[0]);
+}
+
+// coords: optional, written for a PETAL alone
+__global__ __launch_bounds__(kBlock) void texture_lookup3_kernel(TexParams t, uint32_t id, const float *p, unsigned long long n, float *rgb,
+                                                                 float *coords, unsigned long long *counts) {
+    __shared__ uint32_t s_tab[128];
+    const NoiseTables nt = stage_noise_tables(s_tab);
+    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
+    const uint32_t kind = __float_as_uint(t.recs[3 * (size_t)id].x);
+    const float4 q1 = t.recs[3 * (size_t)id + 1], q2 = t.recs[3 * (size_t)id + 2];
+    unsigned my_undefined = 0;
+    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < n; k += stride) {
+        const float P[3] = {p[3 * k], p[3 * k + 1], p[3 * k + 2]};
+        float c[3], crd[3];
+        bool ok = true;
+        solid_color(nt, kind, q1, q2, P, c, crd, ok);
+        if (!ok) my_undefined++;
+        rgb[3 * k] = c[0]; rgb[3 * k + 1] = c[1]; rgb[3 * k + 2] = c[2];
+        if (coords && kind == kTexPetal) { coords[3 * k] = crd[0]; coords[3 * k + 1] = crd[1]; coords[3 * k + 2] = crd[2]; }
     }
     if (counts) workgroup_add<kBlock>(my_undefined, &counts[0]);
 }
@@ -160,7 +170,7 @@ mr_status launch_hit_surface(const DeviceScene &ds, const TexParams &tex, const 
         return fail(MR_ERR_INVALID, "the scene holds spheres / planes: their hit point is o + t*d, d_rays is required");
     SurfaceArgs a;
     a.m = rec::mesh_of(ds); a.t = tex; a.rays = d_rays; a.hits = d_hits; a.n = n; a.color = d_color; a.normal = d_normal; a.counts = d_counts;
-    hipLaunchKernelGGL(procedural_surface_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
+    hipLaunchKernelGGL(hit_surface_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;
 }
@@ -192,6 +202,14 @@ mr_status launch_texture_lookup_proc(const TexParams &tex, uint32_t texture, con
                                      unsigned long long *d_counts, hipStream_t stream) {
     if (n == 0) return MR_OK;
     hipLaunchKernelGGL(texture_lookup_proc_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, tex, texture, d_uv, n, d_rgb, d_counts);
+    MR_HIP_CHECK(hipGetLastError());
+    return MR_OK;
+}
+
+mr_status launch_texture_lookup3(const TexParams &tex, uint32_t texture, const float *d_p, unsigned long long n, float *d_rgb,
+                                 float *d_coords, unsigned long long *d_counts, hipStream_t stream) {
+    if (n == 0) return MR_OK;
+    hipLaunchKernelGGL(texture_lookup3_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, tex, texture, d_p, n, d_rgb, d_coords, d_counts);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;
 }

@@ -1,7 +1,8 @@
 // mr_procedural_body.h -- the 2-D procedural lookups and the bump mapping as device functions: StemTexture::lookup2D
 // (Texture.h:192-212), StoneTexture::lookup2D and ::bumpHeight2D (Texture.cpp:358-440) over the noise of mr_noise.h, and the
-// perturbation of Scene::trace (Scene.cpp:235-261).  Shared by the surface pass of mr_procedural.hip and the one of mr_solid.hip,
-// which adds the UVW kinds (mr_solid_body.h).  Device code only; the units that include this are compiled with -ffp-contract=off.
+// perturbation of Scene::trace (Scene.cpp:235-261).  Called by the inspection kernels of mr_procedural.hip and by
+// hit_color_normal (mr_hit_surface_body.h), next to the UVW kinds (mr_solid_body.h).  Device code only; the units that include
+// this are compiled with -ffp-contract=off.
 #pragma once
 
 #include <hip/hip_runtime.h>

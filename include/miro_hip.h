@@ -689,8 +689,8 @@ mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_h
  *   HitInfo::N as Scene::trace leaves it (Scene.cpp:234-263): on a STONE material four bumpHeight2D samples at (u -+ delta, v),
  *   (u, v -+ delta) with delta = (float)0.0001, dx and dy by central differences, randomVec by the largest component of N, t1 =
  *   cross(N, randomVec), N += dx * cross(N, t1) - dy * cross(N, cross(N, t1)), then normalize(); on every other material the
- *   normalisation alone (the zero perturbation is skipped; a UVW material gets neither toUVCoordinates nor the bump).  A scene
- *   whose table holds a UVW kind runs the pass of csrc/mr_solid.hip, every other scene the one it ran before.  A ray that missed leaves its six floats untouched.  Works on any
+ *   normalisation alone (the zero perturbation is skipped; a UVW material gets neither toUVCoordinates nor the bump).  One
+ *   kernel serves every scene (csrc/mr_procedural.hip).  A ray that missed leaves its six floats untouched.  Works on any
  *   scene, with or without a texture table.  d_counts (may be NULL): [0] += hits whose lookup the reference leaves undefined,
  *   not zeroed.  d_rays may be NULL for scenes of triangles only.
  * mr_shade_lights_surface, mr_shade_accumulate_surface -- mr_shade_lights (Phong.cpp:44-150 over the light list) and

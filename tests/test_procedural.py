@@ -361,15 +361,17 @@ def test_set_textures_refuses_bad_procedural_textures_and_keeps_the_earlier_tabl
 
 
 def test_procedural_kernels_stay_inside_the_verified_envelope():
-    """Every kernel of mr_procedural.hip (remarks in build/mr_procedural.remarks.txt): no dynamic stack; no more spilled VGPRs, no
-    more scratch per lane and no fewer waves per SIMD than BOTH its own record (tests/golden/kernel_budget_procedural.json, written
-    from the build whose GPU run of this file was green) AND the worst value among the kernels of tests/golden/kernel_budget.json.
-    The surface pass and the inspection kernels have no traversal: no scratch at all."""
+    """Every kernel of mr_procedural.hip (remarks in build/mr_procedural.remarks.txt), 18 of them: no dynamic stack; no more spilled
+    VGPRs, no more scratch per lane and no fewer waves per SIMD than BOTH its own record (tests/golden/kernel_budget_procedural.json,
+    written by tools/kernel_budget.py --write-unit mr_procedural from the build whose GPU run of this file, of
+    tests/test_solid_textures.py and of tests/test_photon_walk_surface.py was green) AND the worst value among the kernels of
+    tests/golden/kernel_budget.json.  The one surface pass (hit_surface_kernel, every scene's) and the inspection kernels, the
+    UVW one included, have no traversal: no scratch at all."""
     cur = kernel_budget.unit_kernels("mr_procedural")
     count = lambda word: sum(word in k for k in cur)                                         # noqa: E731
-    assert len(cur) == 17 and count("shade_lights_surf_kernel") == 12
-    for word in ("procedural_surface_kernel", "shade_accumulate_surf_kernel", "texture_lookup_proc_kernel", "bump_height_kernel",
-                 "noise_probe_kernel"):
+    assert len(cur) == 18 and count("shade_lights_surf_kernel") == 12
+    for word in ("hit_surface_kernel", "shade_accumulate_surf_kernel", "texture_lookup_proc_kernel", "texture_lookup3_kernel",
+                 "bump_height_kernel", "noise_probe_kernel"):
         assert count(word) == 1, word
         name = [k for k in cur if word in k][0]
         assert cur[name]["scratch_bytes_per_lane"] == 0 and cur[name]["vgprs_spilled"] == 0, (name, cur[name])
@@ -676,6 +678,84 @@ def test_bump_mapped_normals_from_the_devices_own_heights(miro, yard, traced):
     for which in (plain, check):
         assert normal[which].tobytes() == normalised(t.N[which]).tobytes()
     yard.untextured()
+
+
+class Plot:
+    """Two quads and a sphere: a checker (material 0) and an 8 x 8 seeded image (1) on the triangles of the first quad, stem (2) and
+    stone (3) on those of the second, plain Phong (4) on the sphere."""
+    V = np.array([[-3, -1.5, 0.25], [0, -1.5, 0.25], [0, 1.5, 0.25], [-3, 1.5, 0.25],
+                  [0.5, -1.5, -0.5], [3.5, -1.5, 0.5], [3.5, 1.5, 0.5], [0.5, 1.5, -0.5]], F)
+    NRM = np.array([[0.1, 0.2, 1]] * 4 + [[-0.3, 0.1, 1]] * 4, F)
+    T = np.array([[0, 0], [3, 0], [3, 3], [0, 3], [0.5, 0.25], [2.5, 0.25], [2.5, 2.25], [0.5, 2.25]], F)
+    IDX = np.array([[0, 1, 2], [0, 2, 3], [4, 5, 6], [4, 6, 7]], np.uint32)
+    CENTRE, RADIUS = (0.25, 0.0, 1.5), 0.75
+    MATERIALS = [((1, 1, 1), (0.25, 0, 0), (0, 0, 0), 500.0, 1.5), DIFFUSE, DIFFUSE, DIFFUSE, ((0.5, 0.25, 0.75), (0, 0, 0), (0, 0, 0), 1.0, 1.0)]
+    PRIM_MATERIAL = [0, 1, 2, 3, 4]
+    TABLE = [dict(color1=(1.0, 0.5, 0.25), color2=(0.125, 0.25, 0.5), scale=4.0),
+             dict(pixels=np.random.default_rng(47).random((8, 8, 3)).astype(F)), dict(stem=7.5), dict(stone=3.0)]
+    MATERIAL_TEXTURE = [0, 1, 2, 3, NONE]
+
+    def __init__(self, miro):
+        s = miro.Scene(0)
+        s.add_arrays(self.V, self.NRM, self.IDX, self.IDX)
+        s.add_sphere(self.CENTRE, self.RADIUS)
+        s.build(4)
+        ti = np.full((5, 3), NONE, np.uint32)
+        ti[:4] = self.IDX
+        s.set_texcoords(self.T, ti)
+        s.set_materials(self.MATERIALS, self.PRIM_MATERIAL)
+        s.set_textures(self.TABLE, self.MATERIAL_TEXTURE)
+        self.scene = s
+
+
+def plot_rays(miro, n, seed=43):
+    rng = np.random.default_rng(seed)
+    o = np.stack([rng.uniform(-2, 2, n), rng.uniform(-1, 1, n), rng.uniform(5, 7, n)], 1)
+    tgt = np.stack([rng.uniform(-3.6, 4.1, n), rng.uniform(-1.9, 1.9, n), np.zeros(n)], 1)
+    tgt[::8] = Plot.CENTRE + rng.uniform(-0.6, 0.6, (len(tgt[::8]), 3))
+    d = tgt - o
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    rays = np.zeros(n, miro.RAY_DTYPE)
+    for k, name in enumerate(("ox", "oy", "oz")):
+        rays[name] = o[:, k]
+    for k, name in enumerate(("dx", "dy", "dz")):
+        rays[name] = d[:, k]
+    rays["tmin"], rays["tmax"] = 1e-4, 1e30
+    return rays
+
+
+@pytest.mark.gpu
+def test_surface_pass_colours_are_the_2d_lookups_at_the_hits_own_uv(miro):
+    """The UV arms of the one surface kernel, held by something that is not the surface pass: 4 099 seeded rays (16 workgroups and
+    a 3-lane tail) on a scene whose table holds a CHECKER, an IMAGE, a STEM and a STONE next to a plain material.  The colour of
+    every textured hit is mr_texture_lookup of its texture at mr_hit_uv's (u, v), bit for bit; a plain hit's is the material's
+    kd; the normal of every hit that is not on the stone is the normalised mr_hit_attrs normal, byte for byte (the stone's bumped
+    normals are test_bump_mapped_normals_from_the_devices_own_heights'); rays that miss keep the fill value; the undefined count
+    is the sum of the lookups' counts."""
+    p = Plot(miro)
+    s = p.scene
+    t = Traced(miro, s, plot_rays(miro, N_BATCH))
+    color, normal, undefined = t.surface(s)
+    color, normal = color.cpu().numpy(), normal.cpu().numpy()
+    mat = np.where(t.hit, np.asarray(p.PRIM_MATERIAL)[np.minimum(t.prim, 4)], -1)
+    print("plot: hits per material %s, misses %d, undefined %d" % ([(mat == m).sum() for m in range(5)], (mat == -1).sum(), undefined))
+    for m in range(-1, 5):
+        assert (mat == m).sum() >= 100, m
+    miss = mat == -1
+    assert (color[miss] == 7.0).all() and (normal[miss] == 7.0).all()
+    looked_up_undefined = 0
+    for m, tex in enumerate(p.MATERIAL_TEXTURE[:4]):
+        which = mat == m
+        rgb, count = _lookup(s, tex, t.uv[which])
+        assert color[which].tobytes() == rgb.tobytes(), m
+        assert len(np.unique(rgb, axis=0)) > (1 if m == 0 else 20), m                    # a checker has two colours
+        looked_up_undefined += count
+    assert len(np.unique(color[mat == 0], axis=0)) == 2
+    assert (color[mat == 4] == np.array(p.MATERIALS[4][0], F)).all()
+    flat = t.hit & (mat != 3)
+    assert normal[flat].tobytes() == normalised(t.N[flat]).tobytes()
+    assert np.abs(normal[mat == 3] - normalised(t.N[mat == 3])).max() > 0.05            # the stone's bump is there
+    assert undefined == looked_up_undefined
 
 
 def _chain(scene, t, light, surface=None):

@@ -1,8 +1,9 @@
-"""Time of the surface pass (mr_hit_surface) over 2^20 hits of ONE material: an all-stone batch (procedural_surface_kernel of
-mr_procedural.hip: five Worley searches, up to 33 Perlin evaluations and the bump per hit) and an all-petal batch
-(solid_surface_kernel of mr_solid.hip: up to 35 Perlin evaluations per hit).  The scene is a floor plane under seeded rays that
-all hit it.  HIP events around windows of --calls back-to-back calls; one warm-up window per texture, then the two alternate for
---repeats timed windows each.  Prints one JSON line; needs the GPU (no fallback)."""
+"""Time of the surface pass (mr_hit_surface, hit_surface_kernel of mr_procedural.hip) over 2^20 hits of ONE material: an
+all-stone batch (five Worley searches, up to 33 Perlin evaluations and the bump per hit), an all-petal batch (up to 35 Perlin
+evaluations per hit) and a plain batch (no texture table: the material's kd and the normalised normal, the memory-bound path
+where the kernel's fixed overhead shows first).  The scene is a floor plane under seeded rays that all hit it.  HIP events
+around windows of --calls back-to-back calls; one warm-up window per row, then the rows alternate for --repeats timed windows
+each.  Prints one JSON line; needs the GPU (no fallback)."""
 import argparse
 import json
 import os
@@ -14,13 +15,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cse168-raytracer_amd"))
 
 NONE = 0xFFFFFFFF
-TEXTURES = dict(stone=dict(stone=3.0), petal=dict(petal=((0.0, -0.5, 0.0), 7.0)))
+TEXTURES = dict(stone=dict(stone=3.0), petal=dict(petal=((0.0, -0.5, 0.0), 7.0)), plain=None)   # None: no texture table
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hits", type=int, default=1 << 20)
-    ap.add_argument("--repeats", type=int, default=20, help="timed windows per texture, the two textures alternating")
+    ap.add_argument("--repeats", type=int, default=20, help="timed windows per row, the rows alternating")
     ap.add_argument("--calls", type=int, default=100, help="back-to-back calls per window")
     a = ap.parse_args()
     import torch
@@ -53,7 +54,10 @@ def main():
 
     def window(name):
         """milliseconds per call over a window of --calls back-to-back calls"""
-        s.set_textures([TEXTURES[name]], [0, NONE])
+        if TEXTURES[name] is None:
+            s.set_textures([])
+        else:
+            s.set_textures([TEXTURES[name]], [0, NONE])
         counts.zero_()
         s.hit_surface(d_rays, d_hits, n, color, normal, d_counts=counts)  # uploads the table; not timed
         torch.cuda.synchronize()
