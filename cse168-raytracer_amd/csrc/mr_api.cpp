@@ -1152,16 +1152,17 @@ mr_status mr_square_light_tangents(const float normal[3], float t1[3], float t2[
     return MR_OK;
 }
 
-// the argument errors come before the scene's state here: a bad call is MR_ERR_INVALID on any scene
-mr_status mr_shade_square_lights(mr_scene *s, const mr_square_light_desc *lights, uint32_t n_lights, uint32_t samples, uint32_t seed,
-                                 const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels,
-                                 const float *d_uv_in, uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb,
-                                 uint64_t *d_counts, void *stream) {
-    const char *who = "mr_shade_square_lights";
+// What mr_shade_square_lights and mr_shade_square_lights_surface ask, in this order; `side` is what they launch with.  The
+// argument errors come before the scene's state here: a bad call is MR_ERR_INVALID on any scene.  surface: the _surface call,
+// which takes d_color / d_normal besides and looks nothing up, so that a texture table is no reason to refuse.
+static mr_status check_shade_square_lights(const char *who, bool surface, mr_scene *s, const mr_square_light_desc *lights, uint32_t n_lights,
+                                           uint32_t samples, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color,
+                                           const float *d_normal, const float *d_uv_in, uint64_t n, uint32_t spp, uint32_t flags,
+                                           const float *d_rgb, const float *d_ray_rgb, const uint64_t *d_counts, uint32_t &side) {
     if (!s) return fail(MR_ERR_INVALID, "%s: NULL scene", who);
     if (n_lights == 0 || n_lights > MR_MAX_LIGHTS) return fail(MR_ERR_INVALID, "%s: %u lights, at least 1 and at most %u", who, n_lights, (unsigned)MR_MAX_LIGHTS);
     if (!lights) return fail(MR_ERR_INVALID, "%s: NULL list of %u lights", who, n_lights);
-    uint32_t side = 0;
+    side = 0;
     while (side < 8 && side * side < samples) side++;
     if (samples == 0 || side * side != samples)
         return fail(MR_ERR_INVALID, "%s: samples = %u is not a perfect square in 1 ... 64 (SquareLight.h:27-33 subdivides the rectangle "
@@ -1174,7 +1175,7 @@ mr_status mr_shade_square_lights(mr_scene *s, const mr_square_light_desc *lights
             if (!std::isfinite(in.dimensions[k]) || in.dimensions[k] < 0.0f)
                 return fail(MR_ERR_INVALID, "%s: light %u: dimensions must be finite and >= 0", who, i);
     }
-    if (!d_rays || !d_hits || (!d_rgb && !d_ray_rgb)) return fail(MR_ERR_INVALID, "%s: NULL argument", who);
+    if (!d_rays || !d_hits || (!d_rgb && !d_ray_rgb) || (surface && (!d_color || !d_normal))) return fail(MR_ERR_INVALID, "%s: NULL argument", who);
     if (spp == 0) return fail(MR_ERR_INVALID, "%s: spp is 0", who);
     if (n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32-1 rays per batch (the sample keys hold the ray index in 32 bits)", who);
     if (flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT | MR_TRACE_ANY))
@@ -1182,14 +1183,43 @@ mr_status mr_shade_square_lights(mr_scene *s, const mr_square_light_desc *lights
     if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
         (reinterpret_cast<uintptr_t>(d_uv_in) & 7) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3))
         return fail(MR_ERR_INVALID, "%s: ray / hit buffers must be 16-byte aligned, counters and d_uv_in 8-byte aligned", who);
+    if (surface && ((reinterpret_cast<uintptr_t>(d_color) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3)))
+        return fail(MR_ERR_INVALID, "%s: d_color and d_normal must be 4-byte aligned", who);
     if ((st = require_device(s)) != MR_OK) return st;
-    if ((st = refuse_procedural(s, who, "mr_shade_lights_surface (a point or disc light list; no _surface form shades square lights)")) != MR_OK) return st;
-    if ((st = refuse_textured(s, who)) != MR_OK) return st;
+    if (!surface) {
+        if ((st = refuse_procedural(s, who, "mr_shade_square_lights_surface")) != MR_OK) return st;
+        if ((st = refuse_textured(s, who)) != MR_OK) return st;
+    }
     if ((flags & MR_TRACE_ANY) && s->dev.refractive)
         return fail(MR_ERR_STATE, "%s: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)", who);
+    return MR_OK;
+}
+
+mr_status mr_shade_square_lights(mr_scene *s, const mr_square_light_desc *lights, uint32_t n_lights, uint32_t samples, uint32_t seed,
+                                 const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels,
+                                 const float *d_uv_in, uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb,
+                                 uint64_t *d_counts, void *stream) {
+    uint32_t side = 0;
+    const mr_status st = check_shade_square_lights("mr_shade_square_lights", false, s, lights, n_lights, samples, d_rays, d_hits, nullptr, nullptr,
+                                                   d_uv_in, n, spp, flags, d_rgb, d_ray_rgb, d_counts, side);
+    if (st != MR_OK) return st;
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_shade_square_lights(s->dev, lights, n_lights, side, seed, d_rays, d_hits, d_weights, d_pixels, d_uv_in, n, spp, flags, d_rgb,
                                       d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_shade_square_lights_surface(mr_scene *s, const mr_square_light_desc *lights, uint32_t n_lights, uint32_t samples, uint32_t seed,
+                                         const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color, const float *d_normal,
+                                         const float *d_weights, const uint32_t *d_pixels, const float *d_uv_in, uint64_t n, uint32_t spp,
+                                         uint32_t flags, float *d_rgb, float *d_ray_rgb, uint64_t *d_counts, void *stream) {
+    uint32_t side = 0;
+    const mr_status st = check_shade_square_lights("mr_shade_square_lights_surface", true, s, lights, n_lights, samples, d_rays, d_hits, d_color,
+                                                   d_normal, d_uv_in, n, spp, flags, d_rgb, d_ray_rgb, d_counts, side);
+    if (st != MR_OK) return st;
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    return launch_shade_square_lights_surface(s->dev, lights, n_lights, side, seed, d_rays, d_hits, d_color, d_normal, d_weights, d_pixels,
+                                              d_uv_in, n, spp, flags, d_rgb, d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts),
+                                              static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_scene_set_environment(mr_scene *s, const mr_environment_desc *env) {

@@ -4,7 +4,8 @@
 //   eye_rays_lens_kernel          Camera::eyeRay under -DDOF (Camera.cpp:135-160, Miro.h:18-19, sampleDisc Utility.h:82-95):
 //                                 mr_gen_eye_rays_lens.  One lane per sample, a store-bound kernel like eye_rays_kernel.
 //   shade_square_lights_kernel    Phong::shade (Phong.cpp:66-157) over a list of SquareLights (SquareLight.h:6-58), `samples`
-//                                 shadow rays per hit and light: mr_shade_square_lights.
+//                                 shadow rays per hit and light: mr_shade_square_lights.  Its body is the template of
+//                                 mr_square_body.h, which mr_square_surface.hip instantiates for mr_shade_square_lights_surface.
 //
 // The square-light kernel is shade_lights_kernel (mr_lights.hip) with one more loop, written from the same pieces
 // (mr_lights_body.h): a SquareLight is a PointLight whose origin is sampled (SquareLight.h:6-58), so a sample is
@@ -25,6 +26,7 @@
 #include "mr_internal.h"
 #include "mr_launch.h"
 #include "mr_lights_body.h"
+#include "mr_square_body.h"
 
 namespace mr {
 namespace {
@@ -84,109 +86,12 @@ __global__ __launch_bounds__(kBlock) void eye_rays_lens_kernel(EyeFrame f, LensA
 // ---------------------------------------------------------------------------------------------------------------------------
 // the square light
 // ---------------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kSquareDomain = 0x73717561u;       // "squa": the seed domain of the sample pairs
-
-// a SquareLight as the kernel takes it: tangents (getTangents, Utility.h:25-31) and cell sizes (SquareLight.h:27-29) from the host
-struct SquareLightRec {
-    float position[3], t1[3], t2[3], color[3], wattage;
-    float du, dv, half_u, half_v;    // m_dimensions / sideLength, m_dimensions / 2.0f
-};
-
-// ShadeArgs' fields (mr_lights_body.h: fill_shade_args and the shared pieces take either) with the kernel's own among them.  With
-// a ShadeArgs as member or base every variant reserves 32 B more scratch per lane, touched by nothing, and leaves the budget.
-struct SquareArgs {
-    TraceParams tp;
-    MeshMat m;
-    const mr_hit *hits;
-    const float *weights;
-    const uint32_t *pixels;
-    const float *uv_in;              // NULL: the counter generator; else 2 * n * n_lights * samples floats
-    uint32_t spp, n_lights, side, samples, hseed;
-    float inv_spp, fsamples;
-    float *rgb, *ray_rgb;
-    unsigned long long *counts;
-    SquareLightRec lights[MR_MAX_LIGHTS];
-};
-
-// samplePhotonOrigin(i, samples) for sample cell (sx, sy) of light li and ray k (SquareLight.h:23-39), and the shadow ray to it
-__device__ __forceinline__ void square_shadow_ray(const SquareArgs &a, const SquareLightRec &lt, unsigned long long k, uint32_t li,
-                                                  uint32_t sx, uint32_t sy, const float P[3], float origin[3], float4 &sa, float4 &sb) {
-    const uint32_t i = sy * a.side + sx;
-    float r0, r1;
-    if (a.uv_in) {
-        const float2 r = reinterpret_cast<const float2 *>(a.uv_in)[(k * a.n_lights + li) * a.samples + i];
-        r0 = r.x; r1 = r.y;
-    } else {
-        const uint32_t h = pcg32(pcg32(a.hseed ^ (uint32_t)k) + (li * 64u + i));
-        r0 = unit01(pcg32(h)); r1 = unit01(pcg32(h ^ 0x68bc21ebu));
-    }
-    const float u = ((lt.du * r0) + (float)sx * lt.du) - lt.half_u;                        // SquareLight.h:35-36
-    const float v = ((lt.dv * r1) + (float)sy * lt.dv) - lt.half_v;
-    for (int c = 0; c < 3; c++) origin[c] = (lt.position[c] + u * lt.t1[c]) + v * lt.t2[c];   // :38
-    shadow_ray_of(P, origin[0], origin[1], origin[2], sa, sb);
-}
-
+// The loop is shade_square_lights_body (mr_square_body.h, with SquareArgs, SquareLightRec and square_shadow_ray), which the
+// surface-pass form (mr_square_surface.hip) instantiates with kColorSurface; here the hit's N is computed and diffuseColor is
+// the material's own.
 template <int VAR, bool ANY>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void shade_square_lights_kernel(SquareArgs a) {
-    extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
-    const int tid = threadIdx.x;
-    const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
-    const unsigned long long n = a.tp.n;
-    const unsigned long long n_round = whole_workgroups(n);
-    Stats st = {0ull, 0ull};
-    unsigned my_shadow_rays = 0;
-
-    for (unsigned long long k = (unsigned long long)xcd_block_id() * kTraceBlock + tid; k < n_round; k += stride) {
-        const bool live = k < n;
-        const float4 h = hit_record_of(a, k, live);
-        const bool hit = __float_as_uint(h.y) != MR_MISS;              // a miss contributes nothing
-        float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 1.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
-        const float *mt = a.m.mats;
-        if (hit) {
-            shade_point_of(a, k, h, P, N, d, mt);
-            my_shadow_rays += a.n_lights * a.samples;
-        }
-
-        float L[3] = {0.f, 0.f, 0.f};
-        for (uint32_t li = 0; li < a.n_lights; li++) {               // Phong.cpp:63, wave-uniform
-            const SquareLightRec &lt = a.lights[li];
-            for (uint32_t sy = 0; sy < a.side; sy++)                   // :78, sample i = sy * side + sx (SquareLight.h:32-33)
-                for (uint32_t sx = 0; sx < a.side; sx++) {
-                    float4 sh;
-                    {
-                        float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(1.f, 1.f, 1.f, -1.f);
-                        float origin[3];
-                        if (hit) square_shadow_ray(a, lt, k, li, sx, sy, P, origin, sa, sb);                     // :80-92
-                        const mr_hit hs = trace_hit<true, ANY, false, VAR>(a.tp, sa, sb, sb.w, hit, s_stack, tid, st);   // :97
-                        sh = *reinterpret_cast<const float4 *>(&hs);
-                    }
-                    if (hit) {
-                        float origin[3]; float4 sa, sb;
-                        square_shadow_ray(a, lt, k, li, sx, sy, P, origin, sa, sb);   // rebuilt rather than kept across the traversal
-                        const float scale = light_scale_of(a.m, sa, sb, sh);        // :97-113
-                        if (scale != 0.0f) {                                          // otherwise `continue`: the sample is skipped
-                            float diffuse[3], highlight;
-                            phong_terms(origin, lt.color, lt.wattage, mt, P, N, d[0], d[1], d[2], diffuse, highlight, a.fsamples);
-                            for (int c = 0; c < 3; c++) L[c] += diffuse[c] * scale;                    // :146
-                            for (int c = 0; c < 3; c++) L[c] += highlight;                             // :155, one term after the other
-                        }
-                    }
-                }
-        }
-        store_shaded(a, k, live, hit, L);
-    }
-
-    if (a.counts) workgroup_add<kTraceBlock>(my_shadow_rays, &a.counts[0]);
-}
-
-template <int VAR, bool ANY>
-mr_status launch_square_t(const SquareArgs &a, hipStream_t stream) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(&shade_square_lights_kernel<VAR, ANY>, a.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL((shade_square_lights_kernel<VAR, ANY>), dim3(trace_grid(a.tp.n)), dim3(kTraceBlock), lds, stream, a);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
+    shade_square_lights_body<VAR, ANY, kColorMaterial>(a, nullptr, nullptr);
 }
 
 }  // namespace
@@ -210,24 +115,9 @@ mr_status launch_shade_square_lights(const DeviceScene &ds, const mr_square_ligh
                                      const uint32_t *d_pixels, const float *d_uv_in, unsigned long long n, uint32_t spp, uint32_t flags,
                                      float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts, hipStream_t stream) {
     if (n == 0) return MR_OK;
-    SquareArgs a;
-    fill_shade_args(a, ds, n_lights, d_rays, d_hits, d_weights, d_pixels, n, spp, d_rgb, d_ray_rgb, d_counts);
-    a.uv_in = d_uv_in;
-    a.side = side; a.samples = side * side; a.fsamples = (float)a.samples;
-    a.hseed = pcg32(seed ^ kSquareDomain);
-    for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) {
-        const mr_square_light_desc &in = lights[i < n_lights ? i : 0];
-        SquareLightRec &o = a.lights[i];
-        for (int c = 0; c < 3; c++) { o.position[c] = in.position[c]; o.color[c] = in.color[c]; }
-        o.wattage = in.wattage;
-        tangents_of(in.normal, o.t1, o.t2);                                      // SquareLight::preCalc
-        const float side_length = sqrtf(a.fsamples);                             // SquareLight.h:27-29
-        o.du = in.dimensions[0] / side_length; o.dv = in.dimensions[1] / side_length;
-        o.half_u = in.dimensions[0] / 2.0f; o.half_v = in.dimensions[1] / 2.0f;
-    }
-    return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT, [&](auto var) {
-        constexpr int V = decltype(var)::value;
-        return (flags & MR_TRACE_ANY) ? launch_square_t<V, true>(a, stream) : launch_square_t<V, false>(a, stream);
+    const SquareArgs a = square_args_of(ds, lights, n_lights, side, seed, d_rays, d_hits, d_weights, d_pixels, d_uv_in, n, spp, d_rgb, d_ray_rgb, d_counts);
+    return launch_square_variant(ds, flags, a, stream, [](auto var, auto any) {
+        return &shade_square_lights_kernel<decltype(var)::value, decltype(any)::value>;
     });
 }
 

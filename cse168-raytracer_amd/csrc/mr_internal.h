@@ -285,6 +285,12 @@ mr_status launch_shade_square_lights(const DeviceScene &ds, const mr_square_ligh
                                      uint32_t seed, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
                                      const uint32_t *d_pixels, const float *d_uv_in, unsigned long long n, uint32_t spp, uint32_t flags,
                                      float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts, hipStream_t stream);
+// ... with the hit's diffuse colour and normal read from the surface pass's buffers (mr_square_surface.hip)
+mr_status launch_shade_square_lights_surface(const DeviceScene &ds, const mr_square_light_desc *lights, uint32_t n_lights, uint32_t side,
+                                             uint32_t seed, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color,
+                                             const float *d_normal, const float *d_weights, const uint32_t *d_pixels, const float *d_uv_in,
+                                             unsigned long long n, uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb,
+                                             unsigned long long *d_counts, hipStream_t stream);
 
 // 2-D textures of TexturedPhong materials (mr_textures.hip; Texture.h:112-133, Texture.cpp:23-28,131-185, Phong.cpp:51-56).  The
 // host copy is one blob as the device holds it: three float4 per texture (TexParams below), then the texels of the

@@ -65,7 +65,8 @@ EXPORTED_SYMBOLS = [
     "mr_last_error", "mr_version",
 ]
 # every symbol include/miro_hip_surface.h declares (entry points added after miro_hip.h's own list was held at 69 names)
-SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map_build_device", "mr_trace_photons_resident"]
+SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map_build_device", "mr_trace_photons_resident",
+                   "mr_shade_square_lights_surface"]
 
 
 class MiroError(RuntimeError):
@@ -302,6 +303,8 @@ def load_library(path=None):
     L.mr_square_light_tangents.argtypes = [f32p, f32p, f32p]
     L.mr_shade_square_lights.argtypes = [vp, C.POINTER(SquareLightDesc), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
                                          C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.mr_shade_square_lights_surface.argtypes = [vp, C.POINTER(SquareLightDesc), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
+                                                 vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.mr_scene_set_environment.argtypes = [vp, C.POINTER(EnvironmentDesc)]
     L.mr_scene_get_environment.argtypes = [vp, C.c_uint32, u32p, u32p, f32p, f32p]
     L.mr_shade_environment.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -791,6 +794,17 @@ class Scene:
         _check(self.L.mr_shade_square_lights(self.h, arr, len(lights), samples, seed, d_rays.data_ptr(), d_hits.data_ptr(),
                                              _ptr(d_weights), _ptr(d_pixels), _ptr(d_uv_in), n, spp, flags, _ptr(d_rgb), _ptr(d_ray_rgb),
                                              _ptr(d_counts), _stream_ptr(stream)))
+
+    def shade_square_lights_surface(self, lights, samples, d_rays, d_hits, d_color, d_normal, n, d_rgb=None, seed=168, d_weights=None,
+                                    d_pixels=None, d_uv_in=None, spp=1, flags=0, d_ray_rgb=None, d_counts=None, stream=None):
+        """mr_shade_square_lights_surface: shade_square_lights with the hit's diffuse colour and normal read from hit_surface's
+        buffers; the call for a scene with a texture table (it runs on any scene).  The same seed gives the same pairs."""
+        arr = (SquareLightDesc * max(len(lights), 1))()
+        for i, lt in enumerate(lights):
+            arr[i] = square_light_desc(lt)
+        _check(self.L.mr_shade_square_lights_surface(self.h, arr, len(lights), samples, seed, d_rays.data_ptr(), d_hits.data_ptr(),
+                                                     _ptr(d_color), _ptr(d_normal), _ptr(d_weights), _ptr(d_pixels), _ptr(d_uv_in), n,
+                                                     spp, flags, _ptr(d_rgb), _ptr(d_ray_rgb), _ptr(d_counts), _stream_ptr(stream)))
 
     def set_environment(self, bg_color=(0.0, 0.0, 0.0), pixels=None, rotation=(0.0, 0.0)):
         """mr_scene_set_environment: Scene::setBgColor, Scene::setEnvironment (pixels: a float image [H, W, 3], row 0 = the

@@ -176,7 +176,8 @@ class FrameRenderer:
         (mr_gen_eye_rays_lens, Camera::eyeRay under -DDOF) in image order; not with tiled=True.
         square_lights: a list of SquareLights (binding.SquareLightDesc objects or dicts) that every level of render_specular's
         batched path shades IN ADDITION to its point light / light list, with square_samples shadow rays per hit and light
-        (mr_shade_square_lights; level l draws its pairs with seed + l).  Without either option nothing changes."""
+        (mr_shade_square_lights; level l draws its pairs with seed + l; on a scene with a texture table, procedural or not,
+        mr_hit_surface and mr_shade_square_lights_surface with the same seeds).  Without either option nothing changes."""
         if isinstance(desc, str):
             desc = scenes.SCENES[desc]
         self.scene, self.desc, self.W, self.H, self.spp = scene, desc, W, H, spp
@@ -339,8 +340,11 @@ class FrameRenderer:
         LeafTexture, FlowerCenterTexture, which are looked up at the hit point itself) adds one launch per level: trace ->
         mr_hit_surface (diffuse colour and bump-mapped normal of every hit into two [n, 3] buffers sized to the level's queue)
         -> mr_shade_lights_surface (light list) or the shadow batch and mr_shade_accumulate_surface (single light) -> the
-        generators.  Square lights and MR_PATH_DIFFUSE children are refused on such a scene (no _surface form; Ray::random
-        bounces about the normal).
+        generators.  MR_PATH_DIFFUSE children are refused on such a scene (Ray::random bounces about the normal).
+        Square lights (FrameRenderer(square_lights=...)) on a scene with any texture table, checker and image textures included,
+        are shaded by mr_shade_square_lights_surface(seed + level) from the level's colour and normal buffers; where the table
+        holds no procedural texture, mr_hit_surface is launched for them alone and the other calls of the level stay the
+        textured ones.  On a scene without a table it is mr_shade_square_lights, as before, and no surface pass.
         photon_maps: (global, caustic) binding.PhotonMap objects, balanced and resident; either may be None.  The photon-map
         term of Scene::traceScene (Scene.cpp:286-299) at EVERY level: after a level is traced and shaded and before its
         children are generated, mr_gather_level runs on the level's queue with its weights and pixels -- irradiance_estimate of
@@ -358,8 +362,8 @@ class FrameRenderer:
                 raise ValueError("render_specular: photon maps need fused=False (mr_trace_level keeps no hit records)")
             global_map, caustic_map = photon_maps
         surface = bool(getattr(sc, "procedural", False))
-        if surface and self.square_lights:
-            raise ValueError("render_specular: square lights on a scene with a procedural texture (no _surface form shades them)")
+        # square lights on a texture table of any kind read the surface pass's buffers (mr_shade_square_lights refuses the table)
+        square_surface = bool(self.square_lights) and bool(getattr(sc, "n_textures", 0))
         if environment is not None and environment is not False:
             if fused:
                 raise ValueError("render_specular: an environment needs fused=False (mr_trace_level keeps no hit records)")
@@ -450,7 +454,7 @@ class FrameRenderer:
             if environment:
                 sc.shade_environment(rays, hits, n, self.d_slots, d_weights=weights, d_pixels=pixels, spp=self.spp,
                                      flags=env_lowres if level > 0 else 0, stream=stream)
-            if surface:
+            if surface or square_surface:
                 color, normal = torch.empty((n, 3), **f32), torch.empty((n, 3), **f32)
                 sc.hit_surface(rays, hits, n, color, normal, stream=stream)
             if lights is not None:
@@ -470,7 +474,12 @@ class FrameRenderer:
                 else:
                     sc.shade_accumulate(rays, hits, weights, pixels, n, sh_rays, sh_hits, src, cnt, L, W, self.d_slots,
                                         spp=self.spp, stream=stream)
-            if self.square_lights:
+            if square_surface:
+                sc.shade_square_lights_surface(self.square_lights, self.square_samples, rays, hits, color, normal, n, self.d_slots,
+                                               seed=self.seed + level, d_weights=weights, d_pixels=pixels, spp=self.spp,
+                                               flags=fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT), d_counts=cnt,
+                                               stream=stream)
+            elif self.square_lights:
                 sc.shade_square_lights(self.square_lights, self.square_samples, rays, hits, n, self.d_slots, seed=self.seed + level,
                                        d_weights=weights, d_pixels=pixels, spp=self.spp,
                                        flags=fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT), d_counts=cnt, stream=stream)

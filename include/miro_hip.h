@@ -489,7 +489,14 @@ mr_status mr_shade_lights(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d
  * d_counts (may be NULL): [0] += shadow rays traced (= rays with a hit x lights x samples); not zeroed by the call.
  * flags: those of mr_shade_lights; MR_TRACE_ANY is refused with MR_ERR_STATE when a material is refractive.
  * Materials: the table of mr_scene_set_materials.  A scene with a texture table (mr_scene_set_textures) is REFUSED with
- *   MR_ERR_STATE: this call shades without the texture lookup.
+ *   MR_ERR_STATE: this call shades without the texture lookup.  "mr_shade_square_lights_surface" (declared in
+ *   miro_hip_surface.h) is the call for such a scene: the same arguments with d_color / d_normal, the two buffers of
+ *   mr_hit_surface, after d_hits.  The hit's diffuseColor (the first factor of Phong.cpp:146; the second stays the material's
+ *   m_diffuse) and its N (Phong.cpp:139,151) are read from them, for rays with a hit only; P is rebuilt from ray and hit, the
+ *   occluder rule of :99-113 keeps the occluder's own normal.  Every other argument, check, random pair (the same seed, ray,
+ *   light and sample give the same pair), output and error is this call's, but: NULL or not 4-byte aligned d_color / d_normal
+ *   are MR_ERR_INVALID, and no texture table is refused -- it looks nothing up and runs on any built scene
+ *   (csrc/mr_square_surface.hip).
  * The call only enqueues one kernel on `stream`.
  * Errors: NULL scene, n_lights == 0 or > MR_MAX_LIGHTS, NULL list, non-zero reserved, a non-finite field, a zero normal,
  *   a negative dimension, samples not such a square, NULL rays / hits, both outputs NULL, spp == 0, n >= 2^32, other flags,
@@ -696,15 +703,19 @@ mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_h
  * mr_shade_lights_surface, mr_shade_accumulate_surface -- mr_shade_lights (Phong.cpp:44-150 over the light list) and
  *   mr_shade_accumulate with the hit's diffuseColor and N read from d_color / d_normal (24 bytes per ray) instead of computed;
  *   every other argument, check and output is the plain call's.  They look nothing up, so they run on any scene.
+ * mr_shade_square_lights_surface (declared in miro_hip_surface.h; csrc/mr_square_surface.hip) -- mr_shade_square_lights the same
+ *   way: d_color / d_normal follow d_hits, soft shadows on a stone floor or on the flower.  Documented with
+ *   mr_shade_square_lights above.
  * mr_texture_bump_height -- Texture::bumpHeight2D (Texture.h:63; StoneTexture's: Texture.cpp:358-393) of texture `texture` at n
  *   coordinates (d_uv: 2n floats) into d_height (n floats): 0 for every kind but STONE, the UVW kinds included.
  * mr_noise_probe -- the noise functions themselves, needs no scene: MR_NOISE_PERLIN reads xyz triples (3n floats) and writes
  *   PerlinNoise::noise (Perlin.h:16-51), n floats; MR_NOISE_WORLEY2 reads xy pairs (2n floats) and writes, per point, F[3] as
  *   floats then ID[3] as uint32 of WorleyNoise::noise2D(at, 3, ...) (Worley.cpp:95-173), 6n words.  Runs on the current device.
- * All five only enqueue on `stream`.
+ * All six only enqueue on `stream`.
  *
  * On a scene whose table holds a STONE, STEM or UVW texture the calls that would compute the colour or the normal themselves
- * return MR_ERR_STATE with a message naming the _surface calls: mr_shade_lights, mr_shade_accumulate, mr_shade_square_lights,
+ * return MR_ERR_STATE with a message naming the _surface calls: mr_shade_lights, mr_shade_accumulate, mr_shade_square_lights
+ * (which refuses every texture table, checker and image included: mr_shade_square_lights_surface is its form for all of them),
  * and mr_gen_path_rays with MR_PATH_DIFFUSE (Ray::random bounces about N).  The first three have no lookup3D; the last would be
  * right on a UVW scene, whose normals nothing bumps, and is refused only to keep the single rule "a scene with a procedural
  * texture goes through the surface pass".  A scene without them runs the kernels it ran before. */

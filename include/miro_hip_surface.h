@@ -49,6 +49,15 @@ mr_status mr_trace_photons_resident(mr_scene *scene, mr_photon_map *map, const m
                                     mr_photon_trace_result *result, mr_photon_build_result *build,
                                     mr_photon_record *d_records, uint64_t records_capacity, void *stream);
 
+/* mr_shade_square_lights with the hit's diffuse colour and normal read from mr_hit_surface's buffers, for a scene with a texture
+ * table (any scene will do): see "mr_shade_square_lights_surface" in miro_hip.h.  d_color / d_normal: 3 n floats each, 4-byte
+ * aligned, read for rays with a hit only. */
+mr_status mr_shade_square_lights_surface(mr_scene *scene, const mr_square_light_desc *lights, uint32_t n_lights, uint32_t samples,
+                                         uint32_t seed, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color,
+                                         const float *d_normal, const float *d_weights, const uint32_t *d_pixels,
+                                         const float *d_uv_in, uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb,
+                                         float *d_ray_rgb, uint64_t *d_counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
