@@ -1013,25 +1013,55 @@ mr_status mr_gen_secondary_rays(mr_scene *s, const mr_ray *d_rays, const mr_hit 
                                  reinterpret_cast<unsigned long long *>(d_count), out_capacity, d_out_octants, static_cast<hipStream_t>(stream));
 }
 
+// What mr_gen_path_rays and mr_gen_path_rays_surface ask, in this order.  surface: the _surface call, which takes d_color /
+// d_normal besides and reads every hit's N from the second, so that a procedural texture is no reason to refuse.
+static mr_status check_gen_path_rays(const char *who, bool surface, mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits,
+                                     const float *d_color, const float *d_normal, uint64_t n, uint32_t spp, uint32_t kinds,
+                                     const mr_ray *d_out_rays, const float *d_out_weights, const uint32_t *d_out_pixels,
+                                     const uint64_t *d_count, uint64_t out_capacity) {
+    const mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (!d_rays || !d_hits || !d_out_rays || !d_out_weights || !d_out_pixels || !d_count) return fail(MR_ERR_INVALID, "NULL argument");
+    if (surface && !d_color) return fail(MR_ERR_INVALID, "%s: d_color is NULL", who);
+    if (surface && !d_normal) return fail(MR_ERR_INVALID, "%s: d_normal is NULL", who);
+    if (surface && (reinterpret_cast<uintptr_t>(d_color) & 3)) return fail(MR_ERR_INVALID, "%s: d_color must be 4-byte aligned", who);
+    if (surface && (reinterpret_cast<uintptr_t>(d_normal) & 3)) return fail(MR_ERR_INVALID, "%s: d_normal must be 4-byte aligned", who);
+    if (spp == 0) return fail(MR_ERR_INVALID, "spp is 0");
+    if (n / spp > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "too many rays for 32-bit ray ids");
+    if (kinds == 0 || (kinds & ~7u)) return fail(MR_ERR_INVALID, "kinds must be a combination of MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE");
+    if (out_capacity == 0 && n > 0) return fail(MR_ERR_INVALID, "%s: out_capacity is 0 (room for 4n rays always suffices)", who);
+    if (!surface && (kinds & 4u) && s->tex.procedural)        // MR_PATH_DIFFUSE: Ray::random bounces about N, which this call does not bump
+        return fail(MR_ERR_STATE, "%s: MR_PATH_DIFFUSE on a scene whose texture table holds a procedural texture (STONE, STEM, "
+                                  "PETAL, LEAF or FLOWER_CENTER; Ray::random bounces about the un-bumped N here; mr_gen_path_rays_surface "
+                                  "reads mr_hit_surface's normal and colour)", who);
+    return MR_OK;
+}
+
 mr_status mr_gen_path_rays(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
                            const uint32_t *d_pixels, const uint32_t *d_ids, uint64_t n, uint32_t spp, uint32_t seed,
                            uint32_t bounce, uint32_t kinds, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
                            uint32_t *d_out_ids, uint64_t *d_count, uint64_t out_capacity, uint8_t *d_out_octants, void *stream) {
-    mr_status st = require_device(s);
+    const mr_status st = check_gen_path_rays("mr_gen_path_rays", false, s, d_rays, d_hits, nullptr, nullptr, n, spp, kinds, d_out_rays,
+                                             d_out_weights, d_out_pixels, d_count, out_capacity);
     if (st != MR_OK) return st;
-    if (!d_rays || !d_hits || !d_out_rays || !d_out_weights || !d_out_pixels || !d_count) return fail(MR_ERR_INVALID, "NULL argument");
-    if (spp == 0) return fail(MR_ERR_INVALID, "spp is 0");
-    if (n / spp > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "too many rays for 32-bit ray ids");
-    if (kinds == 0 || (kinds & ~7u)) return fail(MR_ERR_INVALID, "kinds must be a combination of MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE");
-    if (out_capacity == 0 && n > 0) return fail(MR_ERR_INVALID, "mr_gen_path_rays: out_capacity is 0 (room for 4n rays always suffices)");
-    if ((kinds & 4u) && s->tex.procedural)        // MR_PATH_DIFFUSE: Ray::random bounces about N, which no generator bumps
-        return fail(MR_ERR_STATE, "mr_gen_path_rays: MR_PATH_DIFFUSE on a scene whose texture table holds a procedural texture (STONE, STEM, "
-                                  "PETAL, LEAF or FLOWER_CENTER; Ray::random bounces about the un-bumped N here; mr_hit_surface and the "
-                                  "_surface calls shade such a scene, no generator reads their normal)");
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_path_rays(s->dev, d_rays, d_hits, d_weights, d_pixels, d_ids, n, spp, seed, bounce, kinds, d_out_rays,
                             d_out_weights, d_out_pixels, d_out_ids, reinterpret_cast<unsigned long long *>(d_count), out_capacity,
                             d_out_octants, static_cast<hipStream_t>(stream));
+}
+
+mr_status mr_gen_path_rays_surface(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color, const float *d_normal,
+                                   const float *d_weights, const uint32_t *d_pixels, const uint32_t *d_ids, uint64_t n, uint32_t spp,
+                                   uint32_t seed, uint32_t bounce, uint32_t kinds, mr_ray *d_out_rays, float *d_out_weights,
+                                   uint32_t *d_out_pixels, uint32_t *d_out_ids, uint64_t *d_count, uint64_t out_capacity,
+                                   uint8_t *d_out_octants, void *stream) {
+    const mr_status st = check_gen_path_rays("mr_gen_path_rays_surface", true, s, d_rays, d_hits, d_color, d_normal, n, spp, kinds,
+                                             d_out_rays, d_out_weights, d_out_pixels, d_count, out_capacity);
+    if (st != MR_OK) return st;
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    return launch_path_rays_surface(s->dev, d_rays, d_hits, d_color, d_normal, d_weights, d_pixels, d_ids, n, spp, seed, bounce, kinds,
+                                    d_out_rays, d_out_weights, d_out_pixels, d_out_ids, reinterpret_cast<unsigned long long *>(d_count),
+                                    out_capacity, d_out_octants, static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_trace_level(mr_scene *s, const mr_level_desc *level, const mr_ray *d_rays, const float *d_weights,

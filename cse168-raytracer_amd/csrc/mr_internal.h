@@ -259,6 +259,12 @@ mr_status launch_path_rays(const DeviceScene &ds, const mr_ray *d_rays, const mr
                            const uint32_t *d_pixels, const uint32_t *d_ids, unsigned long long n, uint32_t spp, uint32_t seed,
                            uint32_t bounce, uint32_t kinds, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
                            uint32_t *d_out_ids, unsigned long long *d_count, unsigned long long out_capacity, uint8_t *d_out_octants, hipStream_t stream);
+// ... with every hit's N and the diffuse child's colour read from the surface pass's buffers (mr_path_surface.hip)
+mr_status launch_path_rays_surface(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color,
+                                   const float *d_normal, const float *d_weights, const uint32_t *d_pixels, const uint32_t *d_ids,
+                                   unsigned long long n, uint32_t spp, uint32_t seed, uint32_t bounce, uint32_t kinds, mr_ray *d_out_rays,
+                                   float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_count,
+                                   unsigned long long out_capacity, uint8_t *d_out_octants, hipStream_t stream);
 
 mr_status launch_level(const DeviceScene &ds, const mr_level_desc &ld, const mr_ray *d_rays, const float *d_weights,
                        const uint32_t *d_pixels, const uint32_t *d_ids, unsigned long long n, float *d_rgb, mr_ray *d_out_rays,

@@ -66,7 +66,7 @@ EXPORTED_SYMBOLS = [
 ]
 # every symbol include/miro_hip_surface.h declares (entry points added after miro_hip.h's own list was held at 69 names)
 SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map_build_device", "mr_trace_photons_resident",
-                   "mr_shade_square_lights_surface"]
+                   "mr_shade_square_lights_surface", "mr_gen_path_rays_surface"]
 
 
 class MiroError(RuntimeError):
@@ -305,6 +305,8 @@ def load_library(path=None):
                                          C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.mr_shade_square_lights_surface.argtypes = [vp, C.POINTER(SquareLightDesc), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                                  vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.mr_gen_path_rays_surface.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp,
+                                           vp, vp, C.c_uint64, vp, vp]
     L.mr_scene_set_environment.argtypes = [vp, C.POINTER(EnvironmentDesc)]
     L.mr_scene_get_environment.argtypes = [vp, C.c_uint32, u32p, u32p, f32p, f32p]
     L.mr_shade_environment.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -617,6 +619,21 @@ class Scene:
                                        n, spp, seed, bounce, kinds, d_out_rays.data_ptr(), d_out_weights.data_ptr(),
                                        d_out_pixels.data_ptr(), ptr(d_out_ids), d_count.data_ptr(), out_capacity, ptr(d_out_octants),
                                        _stream_ptr(stream)))
+
+    def gen_path_rays_surface(self, d_rays, d_hits, d_color, d_normal, d_weights, d_pixels, d_ids, n, d_out_rays, d_out_weights,
+                              d_out_pixels, d_out_ids, d_count, spp=1, seed=168, bounce=0,
+                              kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE, stream=None, out_capacity=None, d_out_octants=None):
+        """mr_gen_path_rays_surface: gen_path_rays with every hit's normal and the diffuse child's colour read from hit_surface's
+        two [n, 3] buffers: the children bounce about the normal that Scene::trace hands on (bumped on a stone material) and
+        the diffuse child carries weight x diffuseColor (Phong.cpp:51-56).  Runs on any scene, textured or not."""
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        if out_capacity is None:
+            out_capacity = min(t.shape[0] for t in (d_out_rays, d_out_weights, d_out_pixels, d_out_ids) if t is not None)
+        _check(self.L.mr_gen_path_rays_surface(self.h, d_rays.data_ptr(), d_hits.data_ptr(), ptr(d_color), ptr(d_normal), ptr(d_weights),
+                                               ptr(d_pixels), ptr(d_ids), n, spp, seed, bounce, kinds, d_out_rays.data_ptr(),
+                                               d_out_weights.data_ptr(), d_out_pixels.data_ptr(), ptr(d_out_ids), d_count.data_ptr(),
+                                               out_capacity, ptr(d_out_octants), _stream_ptr(stream)))
 
     def trace_level(self, d_rays, d_weights, d_pixels, d_ids, n, d_rgb, light_pos, wattage, children=MR_LEVEL_LAST, d_out_rays=None,
                     d_out_weights=None, d_out_pixels=None, d_out_ids=None, d_out_count=None, d_counts=None, spp=1, flags=0,

@@ -305,7 +305,8 @@ class FrameRenderer:
         return g
 
     def render_specular(self, depth=10, stream=None, path_tracing=False, path_seed=168, path_kinds=None, fused=False,
-                        group_octants=False, lights=None, environment=None, photon_maps=None, nphotons=500, max_dist=1e10):
+                        group_octants=False, lights=None, environment=None, photon_maps=None, nphotons=500, max_dist=1e10,
+                        surface_children=None):
         """Scene::traceScene with reflective / refractive materials (Scene.cpp:270-346) as wavefront bounces: every
         level traces its queue, shades it (weight x Phong::shade added to the ray's pixel), and emits the reflect /
         Fresnel / refract children of the next level by ballot compaction.  depth = TRACE_DEPTH (Miro.h:13): rays are
@@ -340,7 +341,14 @@ class FrameRenderer:
         LeafTexture, FlowerCenterTexture, which are looked up at the hit point itself) adds one launch per level: trace ->
         mr_hit_surface (diffuse colour and bump-mapped normal of every hit into two [n, 3] buffers sized to the level's queue)
         -> mr_shade_lights_surface (light list) or the shadow batch and mr_shade_accumulate_surface (single light) -> the
-        generators.  MR_PATH_DIFFUSE children are refused on such a scene (Ray::random bounces about the normal).
+        generators.
+        surface_children: under path_tracing, a level's children come from mr_gen_path_rays_surface, which reads the level's
+        colour and normal buffers: every child bounces about the normal Scene::trace hands on (the bumped one on stone) and the
+        diffuse child carries weight x diffuseColor, the looked-up colour (Phong.cpp:51-56), not the material's m_diffuse.  None:
+        on a scene with a procedural texture, and only there.  True: on any scene; a level whose surface pass does not run
+        already gets it (mr_hit_surface works with or without a table), and `fused` must be falsy on a scene without a table.
+        False: mr_gen_path_rays everywhere, which refuses MR_PATH_DIFFUSE on a scene with a procedural texture (ValueError here,
+        before any launch).  Without path_tracing it has no effect: the non-path generators emit no diffuse child.
         Square lights (FrameRenderer(square_lights=...)) on a scene with any texture table, checker and image textures included,
         are shaded by mr_shade_square_lights_surface(seed + level) from the level's colour and normal buffers; where the table
         holds no procedural texture, mr_hit_surface is launched for them alone and the other calls of the level stay the
@@ -364,6 +372,14 @@ class FrameRenderer:
         surface = bool(getattr(sc, "procedural", False))
         # square lights on a texture table of any kind read the surface pass's buffers (mr_shade_square_lights refuses the table)
         square_surface = bool(self.square_lights) and bool(getattr(sc, "n_textures", 0))
+        if surface_children is None:
+            surface_children = surface
+        elif not surface_children and surface and path_tracing and path_kinds is not None and path_kinds & binding.MR_PATH_DIFFUSE:
+            raise ValueError("render_specular: surface_children=False with MR_PATH_DIFFUSE on a scene with a procedural texture "
+                             "(mr_gen_path_rays bounces about the un-bumped normal and refuses the scene)")
+        surface_children = bool(surface_children) and path_tracing
+        if surface_children and fused:
+            raise ValueError("render_specular: surface_children needs fused=False (mr_trace_level keeps no hit records)")
         if environment is not None and environment is not False:
             if fused:
                 raise ValueError("render_specular: an environment needs fused=False (mr_trace_level keeps no hit records)")
@@ -392,7 +408,7 @@ class FrameRenderer:
         if stream is not None and stream != torch.cuda.current_stream(self.device):
             with torch.cuda.stream(stream):
                 return self.render_specular(depth, stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights,
-                                            environment or None, photon_maps, nphotons, max_dist)
+                                            environment or None, photon_maps, nphotons, max_dist, surface_children)
         self.d_slots.zero_()
         if path_kinds is None:
             path_kinds = binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT
@@ -454,7 +470,7 @@ class FrameRenderer:
             if environment:
                 sc.shade_environment(rays, hits, n, self.d_slots, d_weights=weights, d_pixels=pixels, spp=self.spp,
                                      flags=env_lowres if level > 0 else 0, stream=stream)
-            if surface or square_surface:
+            if surface or square_surface or (surface_children and level < depth):
                 color, normal = torch.empty((n, 3), **f32), torch.empty((n, 3), **f32)
                 sc.hit_surface(rays, hits, n, color, normal, stream=stream)
             if lights is not None:
@@ -498,8 +514,13 @@ class FrameRenderer:
             out_oct = torch.empty(fan * n, dtype=torch.uint8, device=self.device) if group_octants else None
             if path_tracing:
                 out_ids = torch.empty(fan * n, dtype=torch.int32, device=self.device)
-                sc.gen_path_rays(rays, hits, weights, pixels, ids, n, out_rays, out_w, out_pix, out_ids, cnt2, spp=self.spp,
-                                 seed=path_seed, bounce=level, kinds=path_kinds, stream=stream, d_out_octants=out_oct)
+                if surface_children:
+                    sc.gen_path_rays_surface(rays, hits, color, normal, weights, pixels, ids, n, out_rays, out_w, out_pix, out_ids, cnt2,
+                                             spp=self.spp, seed=path_seed, bounce=level, kinds=path_kinds, stream=stream,
+                                             d_out_octants=out_oct)
+                else:
+                    sc.gen_path_rays(rays, hits, weights, pixels, ids, n, out_rays, out_w, out_pix, out_ids, cnt2, spp=self.spp,
+                                     seed=path_seed, bounce=level, kinds=path_kinds, stream=stream, d_out_octants=out_oct)
             else:
                 sc.gen_secondary_rays(rays, hits, weights, pixels, n, out_rays, out_w, out_pix, cnt2, spp=self.spp, stream=stream,
                                       d_out_octants=out_oct)

@@ -345,7 +345,16 @@ mr_status mr_gen_secondary_rays(mr_scene *scene, const mr_ray *d_rays, const mr_
  * (seed, ray id, bounce, child kind).  kinds selects the children: MR_PATH_MIRROR | MR_PATH_REFRACT (Scene.cpp:302-336)
  * | MR_PATH_DIFFUSE (an extension: traceScene at HEAD never calls Ray::random); up to four children per ray (room for
  * 4n).  d_ids (NULL = ray index) are stable ray ids, d_out_ids (may be NULL) receives the children's.  out_capacity as
- * in mr_gen_secondary_rays (4n always suffices; n when kinds == MR_PATH_DIFFUSE). */
+ * in mr_gen_secondary_rays (4n always suffices; n when kinds == MR_PATH_DIFFUSE).
+ * mr_gen_path_rays_surface (declared in miro_hip_surface.h; csrc/mr_path_surface.hip) is the same call with d_color / d_normal
+ * after d_hits, the two buffers of mr_hit_surface (3 n floats each, 4-byte aligned, read for rays with a hit only): every child
+ * -- Ray::reflect, the Fresnel term, Ray::refract, Ray::random -- takes hit.N from d_normal, the normal as Scene::trace hands
+ * it on (Scene.cpp:234-263, bumped on a STONE material), and the diffuse child carries weight * d_color, the diffuseColor of
+ * Phong.cpp:51-56 that Scene::tracePhoton carries on (Scene.cpp:545-553, :608), instead of weight * m_diffuse.  WHICH children
+ * a hit has stays the material's (isDiffuse / isReflective / isRefractive): a diffuse child whose colour is 0 is emitted with
+ * weight 0.  Every other argument, check, key, child id and capacity rule is mr_gen_path_rays'; NULL or misaligned d_color /
+ * d_normal: MR_ERR_INVALID.  It looks nothing up and refuses no texture table; on a scene without one the children are
+ * mr_gen_path_rays' bit for bit. */
 enum { MR_PATH_MIRROR = 1u, MR_PATH_REFRACT = 2u, MR_PATH_DIFFUSE = 4u };
 mr_status mr_gen_path_rays(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
                            const uint32_t *d_pixels, const uint32_t *d_ids, uint64_t n, uint32_t spp, uint32_t seed,
@@ -714,11 +723,13 @@ mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_h
  * All six only enqueue on `stream`.
  *
  * On a scene whose table holds a STONE, STEM or UVW texture the calls that would compute the colour or the normal themselves
- * return MR_ERR_STATE with a message naming the _surface calls: mr_shade_lights, mr_shade_accumulate, mr_shade_square_lights
+ * return MR_ERR_STATE with a message naming their _surface form: mr_shade_lights, mr_shade_accumulate, mr_shade_square_lights
  * (which refuses every texture table, checker and image included: mr_shade_square_lights_surface is its form for all of them),
- * and mr_gen_path_rays with MR_PATH_DIFFUSE (Ray::random bounces about N).  The first three have no lookup3D; the last would be
- * right on a UVW scene, whose normals nothing bumps, and is refused only to keep the single rule "a scene with a procedural
- * texture goes through the surface pass".  A scene without them runs the kernels it ran before. */
+ * and mr_gen_path_rays with MR_PATH_DIFFUSE (Ray::random bounces about N; mr_gen_path_rays_surface is its form).  The first
+ * three have no lookup3D; the last would bounce about the right normal on a UVW scene, whose normals nothing bumps, but would
+ * still carry m_diffuse instead of the looked-up colour.  A scene without them runs the kernels it ran before.  Still without a
+ * surface form: mr_gen_secondary_rays needs none (no diffuse child; a STONE material has ks = kt = 0), and mr_trace_level
+ * refuses every texture table. */
 enum { MR_TEX_CHECKER = 0, MR_TEX_IMAGE = 1, MR_TEX_STONE = 2, MR_TEX_STEM = 3, MR_TEX_PETAL = 4, MR_TEX_LEAF = 5, MR_TEX_FLOWER_CENTER = 6 };
 #define MR_MAX_TEXTURES 16
 #define MR_NO_TEXTURE  0xFFFFFFFFu

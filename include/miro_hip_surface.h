@@ -58,6 +58,15 @@ mr_status mr_shade_square_lights_surface(mr_scene *scene, const mr_square_light_
                                          const float *d_uv_in, uint64_t n, uint32_t spp, uint32_t flags, float *d_rgb,
                                          float *d_ray_rgb, uint64_t *d_counts, void *stream);
 
+/* mr_gen_path_rays with every hit's normal and the diffuse child's colour read from mr_hit_surface's buffers, for a scene with a
+ * texture table (any scene will do): see "mr_gen_path_rays_surface" in miro_hip.h.  d_color / d_normal: 3 n floats each, 4-byte
+ * aligned, read for rays with a hit only. */
+mr_status mr_gen_path_rays_surface(mr_scene *scene, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_color,
+                                   const float *d_normal, const float *d_weights, const uint32_t *d_pixels, const uint32_t *d_ids,
+                                   uint64_t n, uint32_t spp, uint32_t seed, uint32_t bounce, uint32_t kinds, mr_ray *d_out_rays,
+                                   float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, uint64_t *d_count,
+                                   uint64_t out_capacity, uint8_t *d_out_octants, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
