@@ -1,6 +1,7 @@
 // mr_api.cpp -- the extern "C" boundary declared in include/miro_hip.h.
-// Scene assembly and BVH::build run on the host; mr_bvh_build flattens the tree into the device
-// layout of mr_internal.h and uploads it once; mr_trace only moves rays/hits and launches.
+// Scene assembly runs on the host, BVH::build on the host (mr_build.cpp) or, opt-in, on the device (mr_bvh_build.hip);
+// mr_bvh_build flattens the tree into the device layout of mr_internal.h and uploads it once; mr_trace only moves
+// rays/hits and launches.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -578,14 +579,21 @@ mr_status mr_scene_add_plane(mr_scene *s, const float normal[3], const float ori
     return MR_OK;
 }
 
+// where the calling thread's last mr_bvh_build spent its time (mr_bvh_build_timing)
+struct BuildTiming { uint32_t builder_used = MR_BUILD_REFERENCE; double prims_ms = 0.0, levels_ms = 0.0, finish_ms = 0.0, upload_ms = 0.0; };
+static thread_local BuildTiming g_build_timing;
+
 mr_status mr_bvh_build(mr_scene *s, const mr_build_opts *opts) {
     if (!s) return fail(MR_ERR_INVALID, "scene is NULL");
-    uint32_t leaf = 4;
+    uint32_t leaf = 4, builder = MR_BUILD_REFERENCE;
+    const bool host_only = opts && opts->host_only;
     if (opts) {
-        if (opts->builder != MR_BUILD_REFERENCE) return fail(MR_ERR_INVALID, "unknown builder %u", opts->builder);
+        builder = opts->builder;
+        if (builder != MR_BUILD_REFERENCE && builder != MR_BUILD_REFERENCE_DEVICE) return fail(MR_ERR_INVALID, "unknown builder %u", builder);
+        if (builder == MR_BUILD_REFERENCE_DEVICE && host_only)
+            return fail(MR_ERR_INVALID, "builder MR_BUILD_REFERENCE_DEVICE builds on a device: host_only must be 0 with it");
         if (opts->leaf_size) leaf = opts->leaf_size;
     }
-    const bool host_only = opts && opts->host_only;
     if (!host_only) {
         mr_status st = select_device(s->device);
         if (st != MR_OK) return st;
@@ -593,16 +601,43 @@ mr_status mr_bvh_build(mr_scene *s, const mr_build_opts *opts) {
     if (s->on_device) release_device(s);
     s->built = false;
     s->on_device = false;
-    mr_status st = build_reference_tree(s->mesh, leaf, s->tree);
-    if (st != MR_OK) return st;
+    BuildTiming timing;
+    mr_status st = MR_OK;
+    bool on_host = builder == MR_BUILD_REFERENCE;
+    if (!on_host) {
+        BvhBuildPhases ph;
+        st = build_reference_tree_device(s->mesh, leaf, s->tree, ph, on_host);      // on_host: a non-finite coordinate
+        if (st != MR_OK) return st;
+        timing.builder_used = MR_BUILD_REFERENCE_DEVICE;
+        timing.prims_ms = ph.prims_ms; timing.levels_ms = ph.levels_ms; timing.finish_ms = ph.finish_ms;
+    }
+    if (on_host) {
+        const auto t0 = std::chrono::steady_clock::now();
+        st = build_reference_tree(s->mesh, leaf, s->tree);
+        if (st != MR_OK) return st;
+        timing.builder_used = MR_BUILD_REFERENCE;
+        timing.levels_ms = ms_since(t0);
+    }
+    g_build_timing = timing;
     s->built = true;
     if (host_only) return MR_OK;
     const uint32_t layout = opts ? opts->layout : 0u;
     if ((layout & 15u) > MR_LAYOUT_TREELETS || (layout & ~(uint32_t)(15u | MR_LAYOUT_ALIGN_LEAVES)))
         return fail(MR_ERR_INVALID, "unknown layout %u", layout);
+    const auto t0 = std::chrono::steady_clock::now();
     st = flatten_and_upload(s, layout);
     if (st != MR_OK) { release_device(s); return st; }
+    g_build_timing.upload_ms = ms_since(t0);
     s->on_device = true;
+    return MR_OK;
+}
+
+mr_status mr_bvh_build_timing(uint32_t *builder_used, double *prims_ms, double *levels_ms, double *finish_ms, double *upload_ms) {
+    if (builder_used) *builder_used = g_build_timing.builder_used;
+    if (prims_ms) *prims_ms = g_build_timing.prims_ms;
+    if (levels_ms) *levels_ms = g_build_timing.levels_ms;
+    if (finish_ms) *finish_ms = g_build_timing.finish_ms;
+    if (upload_ms) *upload_ms = g_build_timing.upload_ms;
     return MR_OK;
 }
 

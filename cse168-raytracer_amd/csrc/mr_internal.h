@@ -107,6 +107,12 @@ struct HostMesh {
 mr_status load_obj(const char *path, const float *ctm16, HostMesh &mesh, uint32_t *n_tris);
 // BVH::build semantics (BVH.cpp:60-339): identical tree to the reference's
 mr_status build_reference_tree(const HostMesh &mesh, uint32_t leaf_size, HostTree &tree);
+// the same tree built by kernels (mr_bvh_build.hip; MR_BUILD_REFERENCE_DEVICE), on the current device.  The temporaries are
+// freed before it returns.  nonfinite: some coordinate is not finite, found by the object-table kernel -- the tree is not built
+// (MR_OK) and the caller builds it on the host.  phases: wall time of the object table (uploads of the raw mesh included), of
+// the launches of the 33 depths, and of the numbering and the download.
+struct BvhBuildPhases { double prims_ms = 0.0, levels_ms = 0.0, finish_ms = 0.0; };
+mr_status build_reference_tree_device(const HostMesh &mesh, uint32_t leaf_size, HostTree &tree, BvhBuildPhases &phases, bool &nonfinite);
 
 // ---------------------------------------------------------------------------------------
 // device layout (see DESIGN.md "Data layout in HBM")

@@ -28,6 +28,7 @@ MR_ORDER_GIVEN = 0x80000000
 
 MR_PATH_MIRROR, MR_PATH_REFRACT, MR_PATH_DIFFUSE = 1, 2, 4
 MR_LEVEL_LAST, MR_LEVEL_SPECULAR, MR_LEVEL_PATH = 0, 1, 2
+MR_BUILD_REFERENCE, MR_BUILD_REFERENCE_DEVICE = 0, 1             # mr_build_opts.builder: on the host / the same tree by kernels
 MR_LAYOUT_DFS, MR_LAYOUT_PAIRS, MR_LAYOUT_TREELETS, MR_LAYOUT_ALIGN_LEAVES = 0, 1, 2, 16
 
 MR_ENV_LOWRES = 1 << 16
@@ -66,7 +67,7 @@ EXPORTED_SYMBOLS = [
 ]
 # every symbol include/miro_hip_surface.h declares (entry points added after miro_hip.h's own list was held at 69 names)
 SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map_build_device", "mr_trace_photons_resident",
-                   "mr_shade_square_lights_surface", "mr_gen_path_rays_surface"]
+                   "mr_shade_square_lights_surface", "mr_gen_path_rays_surface", "mr_bvh_build_timing"]
 
 
 class MiroError(RuntimeError):
@@ -294,6 +295,7 @@ def load_library(path=None):
     L.mr_trace_photons_surface.argtypes = L.mr_trace_photons.argtypes
     L.mr_gather_level.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
     L.mr_trace_photons_timing.argtypes = [C.POINTER(C.c_double)] * 3
+    L.mr_bvh_build_timing.argtypes = [u32p] + [C.POINTER(C.c_double)] * 4
     L.mr_photon_map_build_device.argtypes = [vp, vp, C.c_uint64, C.c_float, C.POINTER(PhotonBuildResult), vp]
     L.mr_trace_photons_resident.argtypes = [vp, vp, C.POINTER(PhotonTraceDesc), C.c_uint32, C.POINTER(PhotonTraceResult),
                                             C.POINTER(PhotonBuildResult), vp, C.c_uint64, vp]
@@ -483,17 +485,25 @@ class Scene:
         return len(vi)
 
     # ---- Scene::preCalc -> BVH::build (Scene.cpp:72)
-    def build(self, leaf_size=4, host_only=False, layout=None):
-        """layout: MR_LAYOUT_* (storage order of the device records; default from MIRO_LAYOUT for A/B probes, else 0)"""
+    def build(self, leaf_size=4, host_only=False, layout=None, builder=None):
+        """layout: MR_LAYOUT_* (storage order of the device records; default from MIRO_LAYOUT for A/B probes, else 0)
+        builder: MR_BUILD_REFERENCE (default) or MR_BUILD_REFERENCE_DEVICE -- the same tree, built by kernels"""
         o = BuildOpts()
         o.leaf_size = leaf_size
-        o.builder = 0
+        o.builder = MR_BUILD_REFERENCE if builder is None else builder
         o.host_only = 1 if host_only else 0
         o.layout = int(os.environ.get("MIRO_LAYOUT", "0")) if layout is None else layout
         _check(self.L.mr_bvh_build(self.h, C.byref(o)))
         return self.info()
 
     preCalc = build
+
+    def build_timing(self):
+        """mr_bvh_build_timing: the builder that produced the tree of this thread's last build and the milliseconds of its phases"""
+        b = C.c_uint32()
+        t = [C.c_double() for _ in range(4)]
+        _check(self.L.mr_bvh_build_timing(C.byref(b), *(C.byref(x) for x in t)))
+        return dict(builder=b.value, prims_ms=t[0].value, levels_ms=t[1].value, finish_ms=t[2].value, upload_ms=t[3].value)
 
     def info(self):
         i = SceneInfo()

@@ -61,14 +61,21 @@ typedef struct mr_mesh_desc {
 
 typedef struct mr_build_opts {
     uint32_t leaf_size;     /* OBJECTS_PER_LEAF (BVH.h:59,61): 4 = scalar reference build (default when 0) */
-    uint32_t builder;       /* MR_BUILD_REFERENCE (0): the reference's binary-search split, identical tree */
+    uint32_t builder;       /* MR_BUILD_REFERENCE (0): the reference's binary-search split, identical tree, built on the host.
+                               MR_BUILD_REFERENCE_DEVICE (1): the identical tree -- nodes, padded corners, child links, depths and
+                               leaf order bit for bit -- built by kernels (csrc/mr_bvh_build.hip), one launch per depth.  It needs a
+                               device: with host_only = 1 the call fails with MR_ERR_INVALID (before any device call; the message
+                               names host_only).  A scene with a non-finite coordinate is built on the host instead (MR_OK);
+                               "mr_bvh_build_timing" (declared in miro_hip_surface.h) tells which builder produced the tree and
+                               where the calling thread's last mr_bvh_build spent its wall time.  Any other value: MR_ERR_INVALID,
+                               "unknown builder" */
     uint32_t host_only;     /* 1: build the tree on the host and skip the device upload (tree inspection,
                                CPU-only tooling); mr_trace on such a scene fails with MR_ERR_STATE */
     uint32_t layout;        /* storage order of the device records (MR_LAYOUT_*): a permutation of where the same nodes and
                                triangles live in HBM -- references, visiting order and hit records are unaffected */
     uint32_t reserved[4];
 } mr_build_opts;
-enum { MR_BUILD_REFERENCE = 0 };
+enum { MR_BUILD_REFERENCE = 0, MR_BUILD_REFERENCE_DEVICE = 1 };
 enum {
     MR_LAYOUT_DFS      = 0,   /* inner nodes in depth-first pre-order (a node's first inner child is its neighbour) */
     MR_LAYOUT_PAIRS    = 1,   /* pre-order, padded so that a node and its first inner child always share one 128-byte line */

@@ -67,6 +67,15 @@ mr_status mr_gen_path_rays_surface(mr_scene *scene, const mr_ray *d_rays, const 
                                    float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, uint64_t *d_count,
                                    uint64_t out_capacity, uint8_t *d_out_octants, void *stream);
 
+/* Where the calling thread's last mr_bvh_build spent its wall time, in milliseconds (thread-local; any pointer may be NULL): see
+ * mr_build_opts.builder in miro_hip.h.  builder_used: the builder that really produced the tree -- MR_BUILD_REFERENCE for a
+ * scene that MR_BUILD_REFERENCE_DEVICE handed to the host because of a non-finite coordinate.
+ *   prims_ms   device builder: upload of the raw mesh arrays and the object-table kernel (0 for the host builder)
+ *   levels_ms  device builder: the launches of the tree's depths with their read-backs; host builder: the whole recursion
+ *   finish_ms  device builder: subtree sizes, pre-order numbering and the download of the tree (0 for the host builder)
+ *   upload_ms  either: flattening the tree into the device layout and uploading it (0 with host_only) */
+mr_status mr_bvh_build_timing(uint32_t *builder_used, double *prims_ms, double *levels_ms, double *finish_ms, double *upload_ms);
+
 #ifdef __cplusplus
 }
 #endif
