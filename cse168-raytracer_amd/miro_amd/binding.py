@@ -418,6 +418,23 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def _light(position, color, wattage):
+    """an mr_light: the single point light of the calls that take one"""
+    lt = Light()
+    lt.position[:] = position
+    lt.color[:] = color
+    lt.wattage = wattage
+    return lt
+
+
+def _square_lights(lights):
+    """the mr_square_light_desc array of a list of SquareLightDesc objects or dicts (see square_light_desc)"""
+    arr = (SquareLightDesc * max(len(lights), 1))()
+    for i, lt in enumerate(lights):
+        arr[i] = square_light_desc(lt)
+    return arr
+
+
 def _stream_ptr(stream):
     if stream is None:
         return None
@@ -433,6 +450,7 @@ class Scene:
         _check(self.L.mr_scene_create(device, C.byref(self.h)))
         self.device = device
         self.n_textures = 0            # textures of the last set_textures (FrameRenderer.render_specular reads it)
+        self.procedural = False        # whether one of them is procedural (a stone, stem or UVW kind), likewise
 
     def close(self):
         if getattr(self, "h", None):
@@ -554,14 +572,13 @@ class Scene:
         """mr_trace_grouped: a bounce queue traced with its rays grouped by direction octant inside chunks of 2^chunk_log2
         (d_order: int32 / uint32 tensor of n entries, written by the call unless chunk_log2 holds MR_ORDER_GIVEN); the hit
         buffer is mr_trace's.  d_octants: the generator's octant bytes (uint8 per ray), cheaper to order from than the rays."""
-        _check(self.L.mr_trace_grouped(self.h, d_rays.data_ptr(), d_octants.data_ptr() if d_octants is not None else None, n,
-                                       d_hits.data_ptr(), d_order.data_ptr(), chunk_log2, flags, _stream_ptr(stream)))
+        _check(self.L.mr_trace_grouped(self.h, d_rays.data_ptr(), _ptr(d_octants), n, d_hits.data_ptr(), d_order.data_ptr(),
+                                       chunk_log2, flags, _stream_ptr(stream)))
 
     def order_by_octant(self, d_rays, n, d_order, chunk_log2=0, stream=None, d_octants=None):
         """mr_order_by_octant: the ray order alone (for trace_level(d_order=...) or trace_grouped(chunk_log2 | MR_ORDER_GIVEN))"""
-        _check(self.L.mr_order_by_octant(self.h, d_rays.data_ptr() if d_rays is not None else None,
-                                         d_octants.data_ptr() if d_octants is not None else None, n, chunk_log2,
-                                         d_order.data_ptr(), _stream_ptr(stream)))
+        _check(self.L.mr_order_by_octant(self.h, _ptr(d_rays), _ptr(d_octants), n, chunk_log2, d_order.data_ptr(),
+                                         _stream_ptr(stream)))
 
     def stats(self, reset=True):
         a, b = C.c_uint64(0), C.c_uint64(0)
@@ -580,13 +597,11 @@ class Scene:
                           d_samples_in=None, d_samples_out=None, d_counts=None, stream=None):
         """mr_gen_eye_rays_lens: Camera::eyeRay under -DDOF for rows [y0, y1), in mr_gen_eye_rays' ray order.  d_samples_in /
         d_samples_out: 4 floats per ray (dx, dy, lx, ly), given / used; d_counts: [0] += rays, [1] += exhausted lens samples."""
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
         y1 = H if y1 is None else y1
         lens = LensDesc()
         lens.aperture, lens.focus_plane = aperture, focus_plane
         _check(self.L.mr_gen_eye_rays_lens(self.h, C.byref(cam), W, H, y0, y1, spp, 1 if jitter else 0, seed, d_rays.data_ptr(),
-                                           _stream_ptr(stream), C.byref(lens), ptr(d_samples_in), ptr(d_samples_out), ptr(d_counts)))
+                                           _stream_ptr(stream), C.byref(lens), _ptr(d_samples_in), _ptr(d_samples_out), _ptr(d_counts)))
         return (y1 - y0) * W * spp
 
     def untile_pixels(self, d_slots, d_image, W, rows, spp, channels=3, stream=None):
@@ -596,21 +611,15 @@ class Scene:
 
     def gen_shadow_rays(self, d_rays, d_hits, n, light, d_out, d_src, d_count, stream=None):
         l = np.ascontiguousarray(light, dtype=np.float32)
-        _check(self.L.mr_gen_shadow_rays(self.h, d_rays.data_ptr() if d_rays is not None else None, d_hits.data_ptr(), n,
-                                         _f32p(l), d_out.data_ptr(), d_src.data_ptr() if d_src is not None else None,
+        _check(self.L.mr_gen_shadow_rays(self.h, _ptr(d_rays), d_hits.data_ptr(), n, _f32p(l), d_out.data_ptr(), _ptr(d_src),
                                          d_count.data_ptr(), _stream_ptr(stream)))
 
     def hit_attrs(self, d_hits, n, d_P, d_N, stream=None, d_rays=None):
-        _check(self.L.mr_hit_attrs(self.h, d_rays.data_ptr() if d_rays is not None else None, d_hits.data_ptr(), n,
-                                   d_P.data_ptr() if d_P is not None else None,
-                                   d_N.data_ptr() if d_N is not None else None, _stream_ptr(stream)))
+        _check(self.L.mr_hit_attrs(self.h, _ptr(d_rays), d_hits.data_ptr(), n, _ptr(d_P), _ptr(d_N), _stream_ptr(stream)))
 
     def shade_direct(self, d_rays, d_hits, n, d_shadow_hits, d_shadow_src, d_shadow_count, light_pos, wattage,
                      d_rgb, spp=1, color=(1.0, 1.0, 1.0), diffuse=(1.0, 1.0, 1.0), stream=None):
-        lt = Light()
-        lt.position[:] = light_pos
-        lt.color[:] = color
-        lt.wattage = wattage
+        lt = _light(light_pos, color, wattage)
         df = np.ascontiguousarray(diffuse, dtype=np.float32)
         _check(self.L.mr_shade_direct(self.h, d_rays.data_ptr(), d_hits.data_ptr(), n, d_shadow_hits.data_ptr(),
                                       d_shadow_src.data_ptr(), d_shadow_count.data_ptr(), C.byref(lt), _f32p(df), spp,
@@ -621,13 +630,11 @@ class Scene:
                       out_capacity=None, d_out_octants=None):
         """mr_gen_path_rays: the PATH_TRACING generators (Ray.h:124-158,235-239): up to 4 children per hit.
         out_capacity: rays the output tensors hold (default: the shortest of them)"""
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
         if out_capacity is None:
             out_capacity = min(t.shape[0] for t in (d_out_rays, d_out_weights, d_out_pixels, d_out_ids) if t is not None)
-        _check(self.L.mr_gen_path_rays(self.h, d_rays.data_ptr(), d_hits.data_ptr(), ptr(d_weights), ptr(d_pixels), ptr(d_ids),
+        _check(self.L.mr_gen_path_rays(self.h, d_rays.data_ptr(), d_hits.data_ptr(), _ptr(d_weights), _ptr(d_pixels), _ptr(d_ids),
                                        n, spp, seed, bounce, kinds, d_out_rays.data_ptr(), d_out_weights.data_ptr(),
-                                       d_out_pixels.data_ptr(), ptr(d_out_ids), d_count.data_ptr(), out_capacity, ptr(d_out_octants),
+                                       d_out_pixels.data_ptr(), _ptr(d_out_ids), d_count.data_ptr(), out_capacity, _ptr(d_out_octants),
                                        _stream_ptr(stream)))
 
     def gen_path_rays_surface(self, d_rays, d_hits, d_color, d_normal, d_weights, d_pixels, d_ids, n, d_out_rays, d_out_weights,
@@ -636,14 +643,12 @@ class Scene:
         """mr_gen_path_rays_surface: gen_path_rays with every hit's normal and the diffuse child's colour read from hit_surface's
         two [n, 3] buffers: the children bounce about the normal that Scene::trace hands on (bumped on a stone material) and
         the diffuse child carries weight x diffuseColor (Phong.cpp:51-56).  Runs on any scene, textured or not."""
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
         if out_capacity is None:
             out_capacity = min(t.shape[0] for t in (d_out_rays, d_out_weights, d_out_pixels, d_out_ids) if t is not None)
-        _check(self.L.mr_gen_path_rays_surface(self.h, d_rays.data_ptr(), d_hits.data_ptr(), ptr(d_color), ptr(d_normal), ptr(d_weights),
-                                               ptr(d_pixels), ptr(d_ids), n, spp, seed, bounce, kinds, d_out_rays.data_ptr(),
-                                               d_out_weights.data_ptr(), d_out_pixels.data_ptr(), ptr(d_out_ids), d_count.data_ptr(),
-                                               out_capacity, ptr(d_out_octants), _stream_ptr(stream)))
+        _check(self.L.mr_gen_path_rays_surface(self.h, d_rays.data_ptr(), d_hits.data_ptr(), _ptr(d_color), _ptr(d_normal), _ptr(d_weights),
+                                               _ptr(d_pixels), _ptr(d_ids), n, spp, seed, bounce, kinds, d_out_rays.data_ptr(),
+                                               d_out_weights.data_ptr(), d_out_pixels.data_ptr(), _ptr(d_out_ids), d_count.data_ptr(),
+                                               out_capacity, _ptr(d_out_octants), _stream_ptr(stream)))
 
     def trace_level(self, d_rays, d_weights, d_pixels, d_ids, n, d_rgb, light_pos, wattage, children=MR_LEVEL_LAST, d_out_rays=None,
                     d_out_weights=None, d_out_pixels=None, d_out_ids=None, d_out_count=None, d_counts=None, spp=1, flags=0,
@@ -651,8 +656,6 @@ class Scene:
                     d_out_octants=None, d_order=None):
         """mr_trace_level: trace -> shadow ray -> trace -> Phong::shade x weight -> pixel, and the next level's queue, in
         one launch (Scene.cpp:270-346)"""
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
         ld = LevelDesc()
         ld.light.position[:] = light_pos
         ld.light.color[:] = color
@@ -662,10 +665,10 @@ class Scene:
             outs = [t for t in (d_out_rays, d_out_weights, d_out_pixels, d_out_ids) if t is not None]
             out_capacity = min(t.shape[0] for t in outs) if outs else 0
         ld.out_capacity_lo, ld.out_capacity_hi = out_capacity & 0xFFFFFFFF, out_capacity >> 32
-        ld.d_out_octants, ld.d_order = ptr(d_out_octants), ptr(d_order)
-        _check(self.L.mr_trace_level(self.h, C.byref(ld), d_rays.data_ptr(), ptr(d_weights), ptr(d_pixels), ptr(d_ids), n,
-                                     d_rgb.data_ptr(), ptr(d_out_rays), ptr(d_out_weights), ptr(d_out_pixels), ptr(d_out_ids),
-                                     ptr(d_out_count), ptr(d_counts), _stream_ptr(stream)))
+        ld.d_out_octants, ld.d_order = _ptr(d_out_octants), _ptr(d_order)
+        _check(self.L.mr_trace_level(self.h, C.byref(ld), d_rays.data_ptr(), _ptr(d_weights), _ptr(d_pixels), _ptr(d_ids), n,
+                                     d_rgb.data_ptr(), _ptr(d_out_rays), _ptr(d_out_weights), _ptr(d_out_pixels), _ptr(d_out_ids),
+                                     _ptr(d_out_count), _ptr(d_counts), _stream_ptr(stream)))
 
     def deinterleave_bands(self, d_recv, d_full, W, H, band_rows, world, shard_rows, floats_per_pixel=3, stream=None):
         _check(self.L.mr_deinterleave_bands(self.h, d_recv.data_ptr(), d_full.data_ptr(), W, H, band_rows, world, shard_rows,
@@ -685,10 +688,8 @@ class Scene:
         fd.light.color[:] = color
         fd.light.wattage = wattage
         fd.diffuse[:] = diffuse
-        _check(self.L.mr_render_direct(self.h, C.byref(fd), d_rgb.data_ptr(),
-                                       d_hits.data_ptr() if d_hits is not None else None,
-                                       d_shadow_hits.data_ptr() if d_shadow_hits is not None else None,
-                                       d_counts.data_ptr() if d_counts is not None else None, _stream_ptr(stream)))
+        _check(self.L.mr_render_direct(self.h, C.byref(fd), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_shadow_hits), _ptr(d_counts),
+                                       _stream_ptr(stream)))
 
     def final_gather(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb, max_dist=1e10, nphotons=500,
                      spp=1, stream=None):
@@ -775,10 +776,7 @@ class Scene:
 
     def shade_accumulate(self, d_rays, d_hits, d_weights, d_pixels, n, d_shadow_rays, d_shadow_hits, d_shadow_src,
                          d_shadow_count, light_pos, wattage, d_rgb, spp=1, color=(1.0, 1.0, 1.0), stream=None):
-        lt = Light()
-        lt.position[:] = light_pos
-        lt.color[:] = color
-        lt.wattage = wattage
+        lt = _light(light_pos, color, wattage)
         _check(self.L.mr_shade_accumulate(self.h, d_rays.data_ptr(), d_hits.data_ptr(), _ptr(d_weights), _ptr(d_pixels), n,
                                           d_shadow_rays.data_ptr(), d_shadow_hits.data_ptr(), d_shadow_src.data_ptr(),
                                           d_shadow_count.data_ptr(), C.byref(lt), spp, d_rgb.data_ptr(), _stream_ptr(stream)))
@@ -787,12 +785,9 @@ class Scene:
                            spp=1, stream=None, out_capacity=None, d_out_octants=None):
         if out_capacity is None:
             out_capacity = min(t.shape[0] for t in (d_out_rays, d_out_weights, d_out_pixels))
-        _check(self.L.mr_gen_secondary_rays(self.h, d_rays.data_ptr(), d_hits.data_ptr(),
-                                            d_weights.data_ptr() if d_weights is not None else None,
-                                            d_pixels.data_ptr() if d_pixels is not None else None, n, spp,
+        _check(self.L.mr_gen_secondary_rays(self.h, d_rays.data_ptr(), d_hits.data_ptr(), _ptr(d_weights), _ptr(d_pixels), n, spp,
                                             d_out_rays.data_ptr(), d_out_weights.data_ptr(), d_out_pixels.data_ptr(),
-                                            d_count.data_ptr(), out_capacity,
-                                            d_out_octants.data_ptr() if d_out_octants is not None else None, _stream_ptr(stream)))
+                                            d_count.data_ptr(), out_capacity, _ptr(d_out_octants), _stream_ptr(stream)))
 
     def set_lights(self, lights):
         """mr_scene_set_lights: Scene::addLight for the whole list (replaces an earlier one; an empty list clears it).
@@ -815,9 +810,7 @@ class Scene:
         square_light_desc) with `samples` shadow rays per hit and light, in one launch; weight * L / spp is added to
         d_rgb[pixel], the un-weighted L of every ray written to d_ray_rgb (either may be None, not both).  d_uv_in: the
         caller's own pairs, 2 * n * len(lights) * samples floats."""
-        arr = (SquareLightDesc * max(len(lights), 1))()
-        for i, lt in enumerate(lights):
-            arr[i] = square_light_desc(lt)
+        arr = _square_lights(lights)
         _check(self.L.mr_shade_square_lights(self.h, arr, len(lights), samples, seed, d_rays.data_ptr(), d_hits.data_ptr(),
                                              _ptr(d_weights), _ptr(d_pixels), _ptr(d_uv_in), n, spp, flags, _ptr(d_rgb), _ptr(d_ray_rgb),
                                              _ptr(d_counts), _stream_ptr(stream)))
@@ -826,9 +819,7 @@ class Scene:
                                     d_pixels=None, d_uv_in=None, spp=1, flags=0, d_ray_rgb=None, d_counts=None, stream=None):
         """mr_shade_square_lights_surface: shade_square_lights with the hit's diffuse colour and normal read from hit_surface's
         buffers; the call for a scene with a texture table (it runs on any scene).  The same seed gives the same pairs."""
-        arr = (SquareLightDesc * max(len(lights), 1))()
-        for i, lt in enumerate(lights):
-            arr[i] = square_light_desc(lt)
+        arr = _square_lights(lights)
         _check(self.L.mr_shade_square_lights_surface(self.h, arr, len(lights), samples, seed, d_rays.data_ptr(), d_hits.data_ptr(),
                                                      _ptr(d_color), _ptr(d_normal), _ptr(d_weights), _ptr(d_pixels), _ptr(d_uv_in), n,
                                                      spp, flags, _ptr(d_rgb), _ptr(d_ray_rgb), _ptr(d_counts), _stream_ptr(stream)))
@@ -869,10 +860,8 @@ class Scene:
         """mr_shade_environment: Scene::getEnvironmentMap for every ray of a traced batch that missed; weight * value / spp is
         added to d_rgb[pixel], the un-weighted value of every ray written to d_ray_rgb (either may be None, not both).
         d_lowres: uint8 per ray, non-zero = the low-res image (ray.isDiffuse); flags: MR_ENV_LOWRES for all rays."""
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-        _check(self.L.mr_shade_environment(self.h, d_rays.data_ptr(), d_hits.data_ptr(), ptr(d_weights), ptr(d_pixels), ptr(d_lowres),
-                                           n, spp, flags, ptr(d_rgb), ptr(d_ray_rgb), ptr(d_counts), _stream_ptr(stream)))
+        _check(self.L.mr_shade_environment(self.h, d_rays.data_ptr(), d_hits.data_ptr(), _ptr(d_weights), _ptr(d_pixels), _ptr(d_lowres),
+                                           n, spp, flags, _ptr(d_rgb), _ptr(d_ray_rgb), _ptr(d_counts), _stream_ptr(stream)))
 
     def set_texcoords(self, texcoords, tidx):
         """mr_scene_set_texcoords: texcoords [n, 2] float32 and tidx [objects, 3] uint32 in addObject order (MR_NO_TEXCOORD in
@@ -939,14 +928,12 @@ class Scene:
 
     def hit_uv(self, d_rays, d_hits, n, d_uv, stream=None):
         """mr_hit_uv: Object::toUVCoordinates(hit.P) of n traced rays into d_uv [n, 2] ((0, 0) for a miss)"""
-        _check(self.L.mr_hit_uv(self.h, d_rays.data_ptr() if d_rays is not None else None, d_hits.data_ptr(), n, d_uv.data_ptr(),
-                                _stream_ptr(stream)))
+        _check(self.L.mr_hit_uv(self.h, _ptr(d_rays), d_hits.data_ptr(), n, d_uv.data_ptr(), _stream_ptr(stream)))
 
     def texture_lookup(self, texture, d_uv, n, d_rgb, d_counts=None, stream=None):
         """mr_texture_lookup: Texture::lookup2D of texture `texture` at d_uv [n, 2] into d_rgb [n, 3]; d_counts[0] += the
         lookups the reference leaves undefined"""
-        _check(self.L.mr_texture_lookup(self.h, texture, d_uv.data_ptr(), n, d_rgb.data_ptr(),
-                                        d_counts.data_ptr() if d_counts is not None else None, _stream_ptr(stream)))
+        _check(self.L.mr_texture_lookup(self.h, texture, d_uv.data_ptr(), n, d_rgb.data_ptr(), _ptr(d_counts), _stream_ptr(stream)))
 
     def texture_lookup3(self, texture, d_p, n, d_rgb, d_coords=None, d_counts=None, stream=None):
         """mr_texture_lookup3: Texture::lookup3D of the UVW texture `texture` at the points d_p [n, 3] into d_rgb [n, 3]; d_coords
@@ -959,9 +946,8 @@ class Scene:
         """mr_hit_surface: for every ray that hit, diffuseColor (Phong.cpp:51-56; every texture kind, a UVW kind at the hit point
         itself) into d_color [n, 3] and the normal as Scene::trace leaves it (bump-mapped on a STONE material, normalised;
         Scene.cpp:234-263) into d_normal [n, 3]; a miss leaves its rows untouched.  d_counts[0] += the hits whose lookup the reference leaves undefined."""
-        _check(self.L.mr_hit_surface(self.h, d_rays.data_ptr() if d_rays is not None else None, d_hits.data_ptr(), n,
-                                     d_color.data_ptr(), d_normal.data_ptr(), d_counts.data_ptr() if d_counts is not None else None,
-                                     _stream_ptr(stream)))
+        _check(self.L.mr_hit_surface(self.h, _ptr(d_rays), d_hits.data_ptr(), n, d_color.data_ptr(), d_normal.data_ptr(),
+                                     _ptr(d_counts), _stream_ptr(stream)))
 
     def shade_lights_surface(self, d_rays, d_hits, d_color, d_normal, n, d_rgb=None, d_weights=None, d_pixels=None, spp=1, flags=0,
                              d_ray_rgb=None, d_counts=None, stream=None):
@@ -973,10 +959,7 @@ class Scene:
     def shade_accumulate_surface(self, d_rays, d_hits, d_color, d_normal, d_weights, d_pixels, n, d_shadow_rays, d_shadow_hits,
                                  d_shadow_src, d_shadow_count, light_pos, wattage, d_rgb, spp=1, color=(1.0, 1.0, 1.0), stream=None):
         """mr_shade_accumulate_surface: shade_accumulate with the hit's diffuse colour and normal read from hit_surface's buffers"""
-        lt = Light()
-        lt.position[:] = light_pos
-        lt.color[:] = color
-        lt.wattage = wattage
+        lt = _light(light_pos, color, wattage)
         _check(self.L.mr_shade_accumulate_surface(self.h, d_rays.data_ptr(), d_hits.data_ptr(), d_color.data_ptr(), d_normal.data_ptr(),
                                                   _ptr(d_weights), _ptr(d_pixels), n,
                                                   d_shadow_rays.data_ptr(), d_shadow_hits.data_ptr(), d_shadow_src.data_ptr(),
@@ -1050,8 +1033,7 @@ class PhotonMap:
                             stream=None):
         """Device tensors: d_pos / d_normal [n,3] float32, d_irrad [n,3]; optional d_found int32 [n], d_r2 float32 [n]."""
         _check(self.L.mr_irradiance_estimate(self.h, d_pos.data_ptr(), d_normal.data_ptr(), n, max_dist, nphotons,
-                                             d_irrad.data_ptr(), d_found.data_ptr() if d_found is not None else None,
-                                             d_r2.data_ptr() if d_r2 is not None else None, _stream_ptr(stream)))
+                                             d_irrad.data_ptr(), _ptr(d_found), _ptr(d_r2), _stream_ptr(stream)))
 
     STAT_NAMES = ("queries", "blocks", "records_searched", "tightenings", "records_prepass", "repeated_searches", "boxes_measured",
                   "candidates", "expansions", "unused9", "unguessed", "unused11")

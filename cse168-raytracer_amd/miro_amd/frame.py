@@ -5,6 +5,9 @@ framebuffer gather used on a multi-GPU node.
 This replaces the reference's per-pixel recursion (Scene::raytraceImage, Scene.cpp:93-212) by batches;
 torch supplies device memory, streams and torch.distributed (backend "nccl" = RCCL) only.
 """
+import collections
+import contextlib
+
 import numpy as np
 import torch
 
@@ -167,6 +170,49 @@ class FusedFrame:
         return int(c[0]) // max(steps, 1), int(c[1]) // max(steps, 1)
 
 
+class Queue(collections.namedtuple("Queue", "rays weights pixels ids octs n")):
+    """One level's rays in render_specular: weights and pixels (None: the eye rays, weight 1 and pixel = ray index // spp),
+    the path tracer's ray ids and the octant bytes (None where the plan has none), and the number of rays."""
+    __slots__ = ()
+
+    def first(self, n):
+        """the leading n rays of freshly generated children"""
+        rays, weights, pixels, ids, octs, _ = self
+        return Queue(rays[:n], weights[:n], pixels[:n], ids if ids is None else ids[:n], octs if octs is None else octs[:n], n)
+
+
+NO_QUEUE = Queue(None, None, None, None, None, 0)
+
+
+class LevelPlan(collections.namedtuple("LevelPlan", (
+        "stream", "flags", "fused", "path_tracing", "path_kinds", "fan", "path_seed", "group_octants", "lights", "environment",
+        "env_lowres", "surface", "square", "square_lights", "surface_children", "photon_maps", "nphotons", "max_dist"))):
+    """What FrameRenderer.render_specular decides once per call, from its arguments and the scene's state (_resolve):
+    stream: the torch Stream of every launch, None for the current one; flags: the renderer's trace flags;
+    fused: False / True / "auto", already False on a scene with a texture table;
+    path_tracing, path_kinds (never None), fan (children per ray, at most), path_seed, group_octants: as given;
+    lights: the scene's light list shades, not the description's point light; environment: misses are shaded, after the
+    first level with env_lowres (MR_ENV_LOWRES or 0);
+    surface: the scene has a procedural texture, so shading reads the surface pass's colour and normal;
+    square: None, "plain" (mr_shade_square_lights) or "surface" (any texture table), for square_lights;
+    surface_children: the path tracer's children come from mr_gen_path_rays_surface;
+    photon_maps: None or (global, caustic), gathered with nphotons / max_dist."""
+    __slots__ = ()
+
+    def surface_pass(self, last):
+        """does a level run mr_hit_surface: for its shading, for its square lights, or for its children (not the last level's)"""
+        return self.surface or self.square == "surface" or (self.surface_children and not last)
+
+    def level_flags(self, level, grouped=False):
+        """The flag words of a level: (trace batches, shading calls, mr_trace_level / mr_trace_grouped).  Bounce queues are
+        compacted in wave order, not in image order: from the first bounce on they carry the MR_TRACE_INCOHERENT hint (voting
+        control flow; the same hit records), except where the level works through an octant order (`grouped`)."""
+        hint = binding.MR_TRACE_INCOHERENT if level > 0 else 0
+        trace = self.flags | hint
+        return (trace, trace & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT),
+                (self.flags & binding.MR_MATH_PRODUCT) | (0 if grouped else hint))
+
+
 class FrameRenderer:
     """All device buffers of one rank's share of a frame, resident for the lifetime of the object."""
 
@@ -199,6 +245,7 @@ class FrameRenderer:
         self.d_shadow_hits = torch.empty((n, 4), **f32)
         self.d_src = torch.empty(n, dtype=torch.int32, device=self.device)
         self.d_count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.d_gather = None                            # final_gather's scratch, allocated on first use
         # rgb: an external [n_pixels, 3] buffer to shade into (FrameGather.local on a multi-GPU node)
         self.d_rgb = torch.zeros((max(self.n_pixels, 1), 3), **f32) if rgb is None else rgb
         self.cam = binding.make_camera(desc["eye"], desc["lookat"], desc["up"], desc["fov"])
@@ -272,7 +319,7 @@ class FrameRenderer:
         frame, added to d_rgb after `step()`.  The scratch (48 B per ray) is allocated on first use."""
         if self.n == 0:
             return
-        if getattr(self, "d_gather", None) is None:
+        if self.d_gather is None:
             self.d_gather = torch.empty(12 * self.n, dtype=torch.float32, device=self.device)
         self.scene.final_gather(global_map, caustic_map, self.d_rays, self.d_hits, self.n, self.d_gather, self.d_slots,
                                 max_dist=max_dist, nphotons=nphotons, spp=self.spp, stream=stream)
@@ -362,16 +409,37 @@ class FrameRenderer:
         mr_hit_surface just filled (the bumped normal, Scene.cpp:290), otherwise the object's normal.  The scratch (12 floats per
         ray) is allocated with the level's other buffers.  `fused` must be falsy: mr_trace_level keeps no hit records.  None: no
         launch is added."""
-        sc, L, W = self.scene, self.desc["light"], self.desc["wattage"]
-        if getattr(sc, "n_textures", 0):
+        plan = self._resolve(stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights, environment, photon_maps,
+                             nphotons, max_dist, surface_children)
+        # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
+        # each other on torch's current stream, so a torch Stream is made current here
+        with contextlib.nullcontext() if stream is None else torch.cuda.stream(stream):
+            self.d_slots.zero_()
+            queue = Queue(self.d_rays, None, None, None, None, self.n)      # the eye rays, in image order
+            per_level = []
+            for level in range(depth + 1):
+                if queue.n == 0:
+                    break
+                one_launch = plan.fused is True or (plan.fused == "auto" and
+                                                    (level == 0 or per_level[-1][1] >= 0.9 * per_level[-1][0]))
+                counts, queue = (self._level_fused if one_launch else self._level_batched)(plan, queue, level, level == depth)
+                per_level.append(counts)
+            self._untile(stream)
+        return per_level
+
+    def _resolve(self, stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights, environment, photon_maps,
+                 nphotons, max_dist, surface_children):
+        """render_specular's arguments and the scene's state as a LevelPlan: every check, and the two scene setters
+        (set_environment, set_lights) between them"""
+        sc = self.scene
+        if sc.n_textures:
             fused = False
         if photon_maps is not None:
             if fused:
                 raise ValueError("render_specular: photon maps need fused=False (mr_trace_level keeps no hit records)")
             global_map, caustic_map = photon_maps
-        surface = bool(getattr(sc, "procedural", False))
-        # square lights on a texture table of any kind read the surface pass's buffers (mr_shade_square_lights refuses the table)
-        square_surface = bool(self.square_lights) and bool(getattr(sc, "n_textures", 0))
+            photon_maps = (global_map, caustic_map)
+        surface = bool(sc.procedural)
         if surface_children is None:
             surface_children = surface
         elif not surface_children and surface and path_tracing and path_kinds is not None and path_kinds & binding.MR_PATH_DIFFUSE:
@@ -380,6 +448,7 @@ class FrameRenderer:
         surface_children = bool(surface_children) and path_tracing
         if surface_children and fused:
             raise ValueError("render_specular: surface_children needs fused=False (mr_trace_level keeps no hit records)")
+        env_lowres = 0
         if environment is not None and environment is not False:
             if fused:
                 raise ValueError("render_specular: an environment needs fused=False (mr_trace_level keeps no hit records)")
@@ -391,7 +460,8 @@ class FrameRenderer:
             if has_image and diffuse_children and kinds != binding.MR_PATH_DIFFUSE:
                 raise ValueError("render_specular: an environment image with MR_PATH_DIFFUSE mixed with other kinds "
                                  "(the queue does not record which child came from Ray::random)")
-            env_lowres = binding.MR_ENV_LOWRES if diffuse_children and kinds == binding.MR_PATH_DIFFUSE else 0
+            if diffuse_children and kinds == binding.MR_PATH_DIFFUSE:
+                env_lowres = binding.MR_ENV_LOWRES
             environment = True
         else:
             environment = False
@@ -401,136 +471,125 @@ class FrameRenderer:
             sc.set_lights(lights)
         if self.square_lights and fused:
             raise ValueError("render_specular: square lights need fused=False (mr_trace_level keeps no hit records)")
-        # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
-        # each other on torch's current stream, so `stream` must be that stream (or a torch Stream, made current here)
         if stream is not None and not isinstance(stream, torch.cuda.Stream):
             raise TypeError("render_specular: pass a torch.cuda.Stream (or None for the current stream), not a raw handle")
-        if stream is not None and stream != torch.cuda.current_stream(self.device):
-            with torch.cuda.stream(stream):
-                return self.render_specular(depth, stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights,
-                                            environment or None, photon_maps, nphotons, max_dist, surface_children)
-        self.d_slots.zero_()
-        if path_kinds is None:
-            path_kinds = binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT
-        fan = 4 if path_tracing else 3                  # children per ray, at most
-        ids = None
-        octs = None                                     # octant bytes of the current queue (None: the eye rays, in image order)
-        rays, weights, pixels, n = self.d_rays, None, None, self.n
-        per_level = []
+        # square lights on a texture table of any kind read the surface pass's buffers (mr_shade_square_lights refuses the table)
+        square = None if not self.square_lights else "surface" if sc.n_textures else "plain"
+        return LevelPlan(stream=stream, flags=self.flags, fused=fused, path_tracing=path_tracing,
+                         path_kinds=binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT if path_kinds is None else path_kinds,
+                         fan=4 if path_tracing else 3, path_seed=path_seed, group_octants=group_octants, lights=lights is not None,
+                         environment=environment, env_lowres=env_lowres, surface=surface, square=square,
+                         square_lights=self.square_lights, surface_children=surface_children, photon_maps=photon_maps,
+                         nphotons=nphotons, max_dist=max_dist)
+
+    def _children(self, plan, n):
+        """The buffers for the children of a level of n rays, at most plan.fan each: ids under path tracing only, octant bytes
+        with group_octants only."""
+        m, dev = plan.fan * n, self.device
+        return Queue(torch.empty((m, 8), dtype=torch.float32, device=dev), torch.empty((m, 3), dtype=torch.float32, device=dev),
+                     torch.empty(m, dtype=torch.int32, device=dev),
+                     torch.empty(m, dtype=torch.int32, device=dev) if plan.path_tracing else None,
+                     torch.empty(m, dtype=torch.uint8, device=dev) if plan.group_octants else None, m)
+
+    def _level_fused(self, plan, q, level, last):
+        """One level as ONE launch of mr_trace_level; returns (rays, shadow rays) and the next queue (None after the last)."""
+        sc, n = self.scene, q.n
+        order = None
+        if q.octs is not None:                          # grouped waves share a direction sign: the default control flow
+            order = torch.empty(n, dtype=torch.int32, device=self.device)
+            sc.order_by_octant(q.rays, n, order, d_octants=q.octs, stream=plan.stream)
+        cnts = torch.zeros(3, dtype=torch.int64, device=self.device)        # rays, shadow rays, children
+        out = NO_QUEUE if last else self._children(plan, n)
+        children = binding.MR_LEVEL_LAST if last else (binding.MR_LEVEL_PATH if plan.path_tracing else binding.MR_LEVEL_SPECULAR)
+        sc.trace_level(q.rays, q.weights, q.pixels, q.ids, n, self.d_slots, self.desc["light"], self.desc["wattage"],
+                       children=children, d_out_rays=out.rays, d_out_weights=out.weights, d_out_pixels=out.pixels, d_out_ids=out.ids,
+                       d_out_count=None if last else cnts[2:], d_counts=cnts[:2], spp=self.spp,
+                       flags=plan.level_flags(level, order is not None)[2], seed=plan.path_seed, bounce=level, kinds=plan.path_kinds,
+                       stream=plan.stream, d_out_octants=out.octs, d_order=order)
+        host = cnts.tolist()
+        return (n, host[1]), None if last else out.first(host[2])
+
+    def _level_batched(self, plan, q, level, last):
+        """One level as separate launches: trace, environment, surface pass, shade, photon term, children -- whichever of
+        them the plan asks for; returns (rays, shadow rays) and the next queue (None after the last)."""
+        sc, n, stream = self.scene, q.n, plan.stream
         f32 = dict(dtype=torch.float32, device=self.device)
-        for level in range(depth + 1):
-            if n == 0:
-                break
-            if fused is True or (fused == "auto" and (level == 0 or per_level[-1][1] >= 0.9 * per_level[-1][0])):
-                last = level == depth
-                order = None
-                if octs is not None:                    # grouped waves share a direction sign: the default control flow
-                    order = torch.empty(n, dtype=torch.int32, device=self.device)
-                    sc.order_by_octant(rays, n, order, d_octants=octs, stream=stream)
-                fl = (self.flags & binding.MR_MATH_PRODUCT) | (binding.MR_TRACE_INCOHERENT if level > 0 and order is None else 0)
-                cnts = torch.zeros(3, dtype=torch.int64, device=self.device)        # rays, shadow rays, children
-                out_rays = out_w = out_pix = out_ids = out_oct = None
-                if not last:
-                    out_rays = torch.empty((fan * n, 8), **f32)
-                    out_w = torch.empty((fan * n, 3), **f32)
-                    out_pix = torch.empty(fan * n, dtype=torch.int32, device=self.device)
-                    if path_tracing:
-                        out_ids = torch.empty(fan * n, dtype=torch.int32, device=self.device)
-                    if group_octants:
-                        out_oct = torch.empty(fan * n, dtype=torch.uint8, device=self.device)
-                children = binding.MR_LEVEL_LAST if last else (binding.MR_LEVEL_PATH if path_tracing else binding.MR_LEVEL_SPECULAR)
-                sc.trace_level(rays, weights, pixels, ids, n, self.d_slots, L, W, children=children, d_out_rays=out_rays,
-                               d_out_weights=out_w, d_out_pixels=out_pix, d_out_ids=out_ids,
-                               d_out_count=None if last else cnts[2:], d_counts=cnts[:2], spp=self.spp, flags=fl, seed=path_seed,
-                               bounce=level, kinds=path_kinds, stream=stream, d_out_octants=out_oct, d_order=order)
-                host = cnts.tolist()
-                per_level.append((n, host[1]))
-                if last:
-                    break
-                n = host[2]
-                rays, weights, pixels = out_rays[:n], out_w[:n], out_pix[:n]
-                octs = out_oct[:n] if out_oct is not None else None
-                if path_tracing:
-                    ids = out_ids[:n]
-                continue
-            hits = torch.empty((n, 4), **f32) if lights is None or level > 0 else self.d_hits
-            if lights is None:
-                sh_rays = torch.empty((n, 8), **f32)
-                sh_hits = torch.empty((n, 4), **f32)
-                src = torch.empty(n, dtype=torch.int32, device=self.device)
-            cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
-            # bounce queues are compacted in wave order, not in image order: from the first bounce on the batches carry the
-            # MR_TRACE_INCOHERENT hint (voting control flow; the same hit records)
-            fl = self.flags | (binding.MR_TRACE_INCOHERENT if level > 0 else 0)
-            if octs is not None:
-                order = torch.empty(n, dtype=torch.int32, device=self.device)
-                sc.trace_grouped(rays, n, hits, order, self.flags & binding.MR_MATH_PRODUCT, d_octants=octs, stream=stream)
+        hits = self.d_hits if plan.lights and level == 0 else torch.empty((n, 4), **f32)
+        trace_flags, _, grouped_flags = plan.level_flags(level, q.octs is not None)
+        if q.octs is not None:
+            order = torch.empty(n, dtype=torch.int32, device=self.device)
+            sc.trace_grouped(q.rays, n, hits, order, grouped_flags, d_octants=q.octs, stream=stream)
+        else:
+            sc.trace_device(q.rays, n, hits, trace_flags, stream=stream)
+        if plan.environment:
+            sc.shade_environment(q.rays, hits, n, self.d_slots, d_weights=q.weights, d_pixels=q.pixels, spp=self.spp,
+                                 flags=plan.env_lowres if level > 0 else 0, stream=stream)
+        color = normal = None
+        if plan.surface_pass(last):
+            color, normal = torch.empty((n, 3), **f32), torch.empty((n, 3), **f32)
+            sc.hit_surface(q.rays, hits, n, color, normal, stream=stream)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._shade(plan, q, hits, color, normal, cnt, level)
+        if plan.photon_maps is not None:
+            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), self.d_slots,
+                            d_normal=normal if plan.surface else None, d_weights=q.weights, d_pixels=q.pixels,
+                            max_dist=plan.max_dist, nphotons=plan.nphotons, spp=self.spp, stream=stream)
+        counts = (n, int(cnt.item()))
+        return counts, None if last else self._generate(plan, q, hits, color, normal, level)
+
+    def _shade(self, plan, q, hits, color, normal, cnt, level):
+        """A batched level's direct light, weight x Phong::shade added to the ray's pixel: the scene's light list in one launch,
+        or the description's point light through a shadow batch; then the renderer's square lights.  Each from the surface
+        pass's colour and normal where the plan says so.  cnt[0]: the level's shadow rays."""
+        sc, n, stream = self.scene, q.n, plan.stream
+        L, W = self.desc["light"], self.desc["wattage"]
+        trace_flags, shade_flags, _ = plan.level_flags(level)
+        if plan.lights:
+            if plan.surface:
+                sc.shade_lights_surface(q.rays, hits, color, normal, n, self.d_slots, d_weights=q.weights, d_pixels=q.pixels,
+                                        spp=self.spp, flags=shade_flags, d_counts=cnt, stream=stream)
             else:
-                sc.trace_device(rays, n, hits, fl, stream=stream)
-            if environment:
-                sc.shade_environment(rays, hits, n, self.d_slots, d_weights=weights, d_pixels=pixels, spp=self.spp,
-                                     flags=env_lowres if level > 0 else 0, stream=stream)
-            if surface or square_surface or (surface_children and level < depth):
-                color, normal = torch.empty((n, 3), **f32), torch.empty((n, 3), **f32)
-                sc.hit_surface(rays, hits, n, color, normal, stream=stream)
-            if lights is not None:
-                lfl = fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT)
-                if surface:
-                    sc.shade_lights_surface(rays, hits, color, normal, n, self.d_slots, d_weights=weights, d_pixels=pixels,
-                                            spp=self.spp, flags=lfl, d_counts=cnt, stream=stream)
-                else:
-                    sc.shade_lights(rays, hits, n, self.d_slots, d_weights=weights, d_pixels=pixels, spp=self.spp, flags=lfl,
-                                    d_counts=cnt, stream=stream)
+                sc.shade_lights(q.rays, hits, n, self.d_slots, d_weights=q.weights, d_pixels=q.pixels, spp=self.spp,
+                                flags=shade_flags, d_counts=cnt, stream=stream)
+        else:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            sh_rays, sh_hits = torch.empty((n, 8), **f32), torch.empty((n, 4), **f32)
+            src = torch.empty(n, dtype=torch.int32, device=self.device)
+            sc.gen_shadow_rays(q.rays, hits, n, L, sh_rays, src, cnt, stream=stream)
+            sc.trace_indirect(sh_rays, cnt, n, sh_hits, trace_flags, stream=stream)         # closest hit: the occluder matters
+            if plan.surface:
+                sc.shade_accumulate_surface(q.rays, hits, color, normal, q.weights, q.pixels, n, sh_rays, sh_hits, src, cnt, L, W,
+                                            self.d_slots, spp=self.spp, stream=stream)
             else:
-                sc.gen_shadow_rays(rays, hits, n, L, sh_rays, src, cnt, stream=stream)
-                sc.trace_indirect(sh_rays, cnt, n, sh_hits, fl, stream=stream)           # closest hit: the occluder matters
-                if surface:
-                    sc.shade_accumulate_surface(rays, hits, color, normal, weights, pixels, n, sh_rays, sh_hits, src, cnt, L, W,
-                                                self.d_slots, spp=self.spp, stream=stream)
-                else:
-                    sc.shade_accumulate(rays, hits, weights, pixels, n, sh_rays, sh_hits, src, cnt, L, W, self.d_slots,
-                                        spp=self.spp, stream=stream)
-            if square_surface:
-                sc.shade_square_lights_surface(self.square_lights, self.square_samples, rays, hits, color, normal, n, self.d_slots,
-                                               seed=self.seed + level, d_weights=weights, d_pixels=pixels, spp=self.spp,
-                                               flags=fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT), d_counts=cnt,
-                                               stream=stream)
-            elif self.square_lights:
-                sc.shade_square_lights(self.square_lights, self.square_samples, rays, hits, n, self.d_slots, seed=self.seed + level,
-                                       d_weights=weights, d_pixels=pixels, spp=self.spp,
-                                       flags=fl & (binding.MR_MATH_PRODUCT | binding.MR_TRACE_INCOHERENT), d_counts=cnt, stream=stream)
-            if photon_maps is not None:
-                sc.gather_level(global_map, caustic_map, rays, hits, n, torch.empty(12 * n, **f32), self.d_slots,
-                                d_normal=normal if surface else None, d_weights=weights, d_pixels=pixels, max_dist=max_dist,
-                                nphotons=nphotons, spp=self.spp, stream=stream)
-            n_shadow = int(cnt.item())
-            per_level.append((n, n_shadow))
-            if level == depth:
-                break
-            out_rays = torch.empty((fan * n, 8), **f32)
-            out_w = torch.empty((fan * n, 3), **f32)
-            out_pix = torch.empty(fan * n, dtype=torch.int32, device=self.device)
-            cnt2 = torch.zeros(1, dtype=torch.int64, device=self.device)
-            out_oct = torch.empty(fan * n, dtype=torch.uint8, device=self.device) if group_octants else None
-            if path_tracing:
-                out_ids = torch.empty(fan * n, dtype=torch.int32, device=self.device)
-                if surface_children:
-                    sc.gen_path_rays_surface(rays, hits, color, normal, weights, pixels, ids, n, out_rays, out_w, out_pix, out_ids, cnt2,
-                                             spp=self.spp, seed=path_seed, bounce=level, kinds=path_kinds, stream=stream,
-                                             d_out_octants=out_oct)
-                else:
-                    sc.gen_path_rays(rays, hits, weights, pixels, ids, n, out_rays, out_w, out_pix, out_ids, cnt2, spp=self.spp,
-                                     seed=path_seed, bounce=level, kinds=path_kinds, stream=stream, d_out_octants=out_oct)
-            else:
-                sc.gen_secondary_rays(rays, hits, weights, pixels, n, out_rays, out_w, out_pix, cnt2, spp=self.spp, stream=stream,
-                                      d_out_octants=out_oct)
-            n = int(cnt2.item())
-            rays, weights, pixels = out_rays[:n], out_w[:n], out_pix[:n]
-            octs = out_oct[:n] if out_oct is not None else None
-            if path_tracing:
-                ids = out_ids[:n]
-        self._untile(stream)
-        return per_level
+                sc.shade_accumulate(q.rays, hits, q.weights, q.pixels, n, sh_rays, sh_hits, src, cnt, L, W, self.d_slots,
+                                    spp=self.spp, stream=stream)
+        if plan.square == "surface":
+            sc.shade_square_lights_surface(plan.square_lights, self.square_samples, q.rays, hits, color, normal, n, self.d_slots,
+                                           seed=self.seed + level, d_weights=q.weights, d_pixels=q.pixels, spp=self.spp,
+                                           flags=shade_flags, d_counts=cnt, stream=stream)
+        elif plan.square == "plain":
+            sc.shade_square_lights(plan.square_lights, self.square_samples, q.rays, hits, n, self.d_slots, seed=self.seed + level,
+                                   d_weights=q.weights, d_pixels=q.pixels, spp=self.spp, flags=shade_flags, d_counts=cnt,
+                                   stream=stream)
+
+    def _generate(self, plan, q, hits, color, normal, level):
+        """The next level's queue by ballot compaction: the path-tracing generators (from the surface buffers where the plan
+        says so) or the reflect / Fresnel / refract children."""
+        sc, n = self.scene, q.n
+        out = self._children(plan, n)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if not plan.path_tracing:
+            sc.gen_secondary_rays(q.rays, hits, q.weights, q.pixels, n, out.rays, out.weights, out.pixels, cnt, spp=self.spp,
+                                  stream=plan.stream, d_out_octants=out.octs)
+        elif plan.surface_children:
+            sc.gen_path_rays_surface(q.rays, hits, color, normal, q.weights, q.pixels, q.ids, n, out.rays, out.weights, out.pixels,
+                                     out.ids, cnt, spp=self.spp, seed=plan.path_seed, bounce=level, kinds=plan.path_kinds,
+                                     stream=plan.stream, d_out_octants=out.octs)
+        else:
+            sc.gen_path_rays(q.rays, hits, q.weights, q.pixels, q.ids, n, out.rays, out.weights, out.pixels, out.ids, cnt,
+                             spp=self.spp, seed=plan.path_seed, bounce=level, kinds=plan.path_kinds, stream=plan.stream,
+                             d_out_octants=out.octs)
+        return out.first(int(cnt.item()))
 
     def ray_counts(self):
         """(primary, shadow) of the last step -- synchronises the whole device (the step may have run on any stream)."""
