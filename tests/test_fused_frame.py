@@ -183,9 +183,12 @@ def test_fused_frame_full_size_properties(miro, spp):
                                      (1920, 1080, 16), (2048, 1100, 8), (1920, 135, 64), (1000, 961, 16)])
 def test_large_frame_schedule_renders_every_chunk_once(miro, W, H, spp):
     """Frames of 60 000 chunks or more are launched with the schedule of frame_schedule() (mr_frame.hip): body workgroups striding
-    over their chunks, and a tail that the last workgroups pull chunk by chunk from a counter (re-armed by its last reader: the
-    frame is rendered three times here).  The picture is the one narrow windows give -- those are below the threshold and take
-    the plain strided schedule.  Sizes: the threshold exactly, ragged last chunks, 8 / 16 / 32 chunks per body workgroup."""
+    over their chunks, and a tail that the last workgroups pull chunk by chunk from a counter.  The frame is rendered three
+    times here, but each launch takes the next of the scene's 64 counters and every test builds its own scene, so the three
+    launches read three counters that nothing has used before: the re-arming by a tail's last reader is NOT what this test
+    sees -- tests/test_frame_large.py launches until the ring has wrapped, and replays a captured launch after it has.  The
+    picture is the one narrow windows give -- those are below the threshold and take the plain strided schedule.  Sizes: the
+    threshold exactly, ragged last chunks, 8 / 16 / 32 chunks per body workgroup."""
     name = "bunny"
     d = scenes.SCENES[name]
     sc = product_scene(miro, name)
