@@ -165,7 +165,7 @@ __device__ unsigned long long g_wg_times[4 * 131072];
 #endif
 #if defined(MIRO_RUN_COUNTS)
 // measurement build only (mr_traverse.h: Stats): wave-level node visits summed over every launch since the last reading
-__device__ unsigned long long g_run_counts[3];
+__device__ unsigned long long g_run_counts[kRunCounters];
 #endif
 // kEyeRel (VAR kTraceEyeRel, the default traversal of triangle-only scenes, every SHADOW / MAT form): the primary ray is traced on the
 // eye-relative tables from a zero origin (trace_ray's REL), the shadow ray on the scene's own.  Every primary ray starts at
@@ -373,8 +373,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
     }
 #if defined(MIRO_RUN_COUNTS)
     {
-        const unsigned mine[3] = {st.node_steps, st.run_visits, st.run_splits};
-        workgroup_add<kTraceBlock, 3>(mine, g_run_counts);
+        const unsigned mine[kRunCounters] = {st.node_steps, st.run_visits, st.run_splits, st.walks, st.walks_whole, st.end_leaf, st.end_pop,
+                                             st.end_irregular, st.end_far_node, st.end_done, st.walk_leaves, st.pops_agree, st.pops_differ};
+        workgroup_add<kTraceBlock, kRunCounters>(mine, g_run_counts);
     }
 #endif
 #if defined(MIRO_WG_TIMES) && MIRO_TRACE_BLOCK == 256
@@ -394,9 +395,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
 #else
 #define MR_RUN_COUNTS_ENTRY mr_debug_run_counts_b128
 #endif
-// {node visits, visits inside a run, runs ended by a split decision} of this unit's launches; reading resets them
+// the kRunCounters counters of mr_traverse.h (Stats, in its order) summed over this unit's launches; reading resets them
 extern "C" int MR_RUN_COUNTS_ENTRY(unsigned long long *out) {
-    const unsigned long long zero[3] = {0ull, 0ull, 0ull};
+    const unsigned long long zero[mr::kRunCounters] = {};
     const int e = (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mr::g_run_counts), sizeof(zero), 0, hipMemcpyDeviceToHost);
     return e ? e : (int)hipMemcpyToSymbol(HIP_SYMBOL(mr::g_run_counts), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
 }

@@ -54,7 +54,16 @@ constexpr float kInf = __builtin_huge_valf();
 // measurement build only (make VARIANT=_runc FRAME_DEFS=-DMIRO_RUN_COUNTS; tools/run_counts.py): wave-level node visits of the
 // fused frame kernel -- those taken outside uniform_run, those inside it, and those at which a run ended on a split decision.
 // One lane of the wave counts each event, so the sum over lanes is the number of wave-visits.
-struct Stats { unsigned long long box, tri; unsigned node_steps, run_visits, run_splits; };
+// ... and how the uniform walks go: walks entered, those of them whose lanes are all the lanes of
+// the wave that still have work ("whole"), how a walk ends besides a split decision -- at a leaf it may not take, at a pop it
+// may not take, at an irregular node, at a node of kRunNodeLimit or more, with every lane done --, the leaves taken inside a
+// walk, and the pops inside a walk after which the lanes hold one value / different values.
+constexpr int kRunCounters = 13;
+struct Stats {
+    unsigned long long box, tri;
+    unsigned node_steps, run_visits, run_splits;
+    unsigned walks, walks_whole, end_leaf, end_pop, end_irregular, end_far_node, end_done, walk_leaves, pops_agree, pops_differ;
+};
 __device__ __forceinline__ void run_count_once(unsigned &c) {
     const int lane = (int)__lane_id();
     if (__builtin_amdgcn_readfirstlane(lane) == lane) c++;
@@ -473,9 +482,9 @@ __device__ __forceinline__ void node_decide(float mn0, float mx0, float mn1, flo
 // per lane for L.cur and the push) is then spent on finding out what the compare masks already say: all active lanes hit both
 // children with the same near one, all hit only child 0, all only child 1, or none hits either.  In the first three cases the
 // next node is the scalar child reference and the far one, if any, is pushed from one v_mov; the loop goes on without touching
-// L.cur.  Otherwise -- a split decision, a pop (the lanes' stacks are their own: nothing says the popped values are equal), a leaf,
-// an irregular node -- L.cur is written per lane exactly as node_decide writes it and the run ends: node_step's own test starts
-// the next one.  Same bits: every floating-point instruction of a visit is the one node_step issues (the same load_node_scalar,
+// L.cur.  Otherwise -- a split decision, an irregular node, and for a run that holds only SOME of the wave's working lanes
+// (uniform_run) a pop or a leaf too -- L.cur is written per lane exactly as node_decide writes it and the run ends: node_step's
+// own test starts the next one.  A run that holds ALL of them goes on through pops and leaves (uniform_walk, below).  Same bits: every floating-point instruction of a visit is the one node_step issues (the same load_node_scalar,
 // node_slabs_guarded -- its wave-wide exact-quotient recomputation included -- and, for irregular nodes, walk_divide) on the
 // same operands; every lane keeps its own stack, pushes what node_decide would have pushed and visits the nodes in the same
 // order -- a wave in the run is a wave for which node_step's test would have succeeded at every visit.  Nothing is shared between
@@ -490,12 +499,36 @@ __device__ __forceinline__ v16f load_node_scalar_at(const float4 *nodes, unsigne
     asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(nodes), "s"(off) : "memory");
     return v;
 }
-// How a run ends travels in `cur` itself: the loop keeps ONE exit and one scalar test for it.  `cur` is the next node while the
-// run goes on, and otherwise a child reference that is no node of the run (a leaf; an index of kRunNodeLimit or more) or one of
-// two values that are no reference at all: kDone when node_decide has to finish the visit lane by lane (pop, split decision),
-// kRunIrregular at an irregular node.  (Leaf references end at ~((2^27 - 2) << 4 | 15) = 0x80000010: mr_api.cpp refuses 2^27
-// records or more.)
+// How a descent ends travels in `cur` itself: the loop of visits keeps ONE exit and one scalar test for it.  `cur` is the next node
+// while the descent goes on, and otherwise a child reference that is no node of the run (a leaf; an index of kRunNodeLimit or more)
+// or one of the values below that are no reference at all.  (Leaf references end at ~((2^27 - 2) << 4 | 15) = 0x80000010:
+// mr_api.cpp refuses 2^27 records or more.)
+//
+// The uniform walk (uniform_walk): the run of a wave whose lanes at the node are ALL its lanes that
+// still have work (m_have, traverse's own ballot of L.have()).  It does not end at a leaf or a pop:
+//   * `cur` a leaf reference (closest-hit walks): the uniform leaf loop runs in place -- leaf_step's scalar arm: the same
+//     load_tri_uniform, object_test, triangle order, strict-less replacement and running best_t, the leaf_cnt_ext lookup for the
+//     extended count -- and then the lanes pop;
+//   * no lane hits a child: the lanes pop;
+//   * a pop: every lane pops ITS OWN stack; one v_readfirstlane and one compare say whether the values are equal.
+//     Equal: `cur` is that value (kDone: the wave has finished).  Not equal: the walk ends with L.cur as popped.
+// A run that holds a subset of the working lanes is uniform_run, unchanged: the others wait at their leaves, and going on without
+// them would undo the while-while grouping (1-spp frames).  An any-hit walk ends at every leaf (a lane that is done leaves the wave's
+// working set there) and takes the pops.  Same bits: every floating-point instruction is one node_step / leaf_step issue on the
+// same operands, every lane visits the same nodes and triangles in the same order with its own stack and its own best_t -- a wave
+// in the walk is one for which node_step's and leaf_step's uniformity tests would have succeeded at every step; the only new
+// knowledge used is that the popped values are equal.
+// Shape: the visits of a descent keep the run's own loop and foot; the pop and the leaves sit behind it.  Nothing of a visit is
+// carried out of that loop (child references and distances would be alive across the leaves: a spilled sixteen-register tuple,
+// six vector registers), so a visit that node_decide has to finish is computed again behind the loops.
 constexpr int kRunIrregular = kDone + 1;
+constexpr int kWalkDecide = kDone + 2;       // node_decide has to finish the visit lane by lane (split decision)
+constexpr int kWalkParted = kDone + 3;       // the lanes popped different values
+constexpr int kWalkPop = kDone + 4;          // (inside the walk only) no lane hits a child
+constexpr int kWalkFirstLeaf = kDone + 16;   // the smallest leaf reference (above)
+
+template <bool REL>
+__device__ __forceinline__ void load_tri_uniform(const float4 *tris, unsigned pos_uniform, float4 &q0, float4 &q1, float4 &q2);
 
 template <typename W>
 __device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, Stats &st, int cur) {
@@ -503,12 +536,15 @@ __device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs 
     float mn0, mx0, mn1, mx1, k0, k1;        // (written by every visit that can reach node_decide<.., true, true> below)
     int ref0, ref1;
     unsigned off;
+    MR_RUN_COUNT(st.walks);
     do {
         off = (unsigned)cur << 6;
         const v16f v = load_node_scalar_at(p.nodes, off);
         const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
         const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
-        ref0 = __float_as_int(v[12]); ref1 = __float_as_int(v[13]);
+        // (moved out of the record's sixteen-register tuple by hand: as parts of it they keep the whole tuple alive to the loop's exit
+        // and beyond, and next to the walk's loops the tuple is then spilled -- 64 bytes of scratch per lane)
+        asm("s_mov_b32 %0, %2\n\ts_mov_b32 %1, %3" : "=&s"(ref0), "=&s"(ref1) : "s"(__float_as_int(v[12])), "s"(__float_as_int(v[13])));
         MR_RUN_COUNT(st.run_visits);
         cur = kRunIrregular;
         if (__float_as_int(v[14]) == 0) {
@@ -532,8 +568,10 @@ __device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs 
     if (cur == kDone) {                                // no child hit in some lanes or all (pop), or the lanes part
         if (((unsigned long long)__builtin_amdgcn_ballot_w64((mn0 > k0) || (mx0 < r.tmin)) &
              (unsigned long long)__builtin_amdgcn_ballot_w64((mn1 > k1) || (mx1 < r.tmin))) != m_all) MR_RUN_COUNT(st.run_splits);
+        else MR_RUN_COUNT(st.end_pop);
         node_decide<false, true, true>(mn0, mx0, mn1, mx1, ref0, ref1, r, L, s_stack, st, k0, k1);
     } else if (cur == kRunIrregular) {                 // the reference's own divisions, decided lane by lane
+        MR_RUN_COUNT(st.end_irregular);
         // (the record is loaded a second time on purpose: kept live across the loop's exit its twelve corners cost the hot loop
         // scalar registers it spills for, and irregular nodes are rare -- a frame whose eye is irregular, where every visit comes
         // this way, pays the run's entry and two loads per visit and is slower than before)
@@ -544,36 +582,159 @@ __device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs 
         node_decide<false, false>(mn0, mx0, mn1, mx1, ref0, ref1, r, L, s_stack, st);
     } else {                                           // a leaf: the wave's leaf_step finds it uniform by its own test
         L.cur = cur;
+#ifdef MIRO_RUN_COUNTS
+        if (cur < 0) MR_RUN_COUNT(st.end_leaf);
+        else MR_RUN_COUNT(st.end_far_node);
+#endif
     }
 }
 
-// one inner node (W::slab, W::scalar, W::oct, W::run: the slab forms and Walk at the top of this file)
 template <typename W>
-__device__ __forceinline__ void node_step(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, int tid, Stats &st) {
+__device__ __forceinline__ void uniform_walk(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, Stats &st, int cur) {
+    const unsigned long long m_all = __builtin_amdgcn_ballot_w64(true);
+    // the leaves a walk takes: every leaf reference in a closest-hit walk, none in an any-hit one -- [kWalkFirstLeaf, 0) as one unsigned test
+    constexpr unsigned leaf_span = W::any ? 0u : 0u - (unsigned)kWalkFirstLeaf;
+    unsigned off;
+    // each lane pops its own stack (kDone at the bottom): `cur` is the popped value when the lanes agree on it.  (The popped values live
+    // for this test only: when they differ the slot is given back and popped again behind the loop -- L.cur carried round the loop
+    // is a register of every visit.)
+    auto pop_uniform = [&]() {
+        const int mine = stack_pop(L, s_stack);
+        cur = __builtin_amdgcn_readfirstlane(mine);
+        if (__builtin_amdgcn_ballot_w64(mine == cur) != m_all) { cur = kWalkParted; L.sp += kStackStride; MR_RUN_COUNT(st.pops_differ); }
+        else MR_RUN_COUNT(st.pops_agree);
+    };
+    MR_RUN_COUNT(st.walks);
+    MR_RUN_COUNT(st.walks_whole);
+    // The shape is a plain loop nest, so that best_t / best_b / best_g / best_pos stay in their registers from the walk's entry to its
+    // exit: the visits of a descent -- the run's loop as it was, one scalar test at its foot --, behind them the pop and the leaves
+    // that follow, each with its pop; in a leaf its triangles.
+    for (;;) {
+      do {      // (the descent)
+        off = (unsigned)cur << 6;
+        const v16f v = load_node_scalar_at(p.nodes, off);
+        const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
+        const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
+        const int ref0 = __float_as_int(v[12]), ref1 = __float_as_int(v[13]);
+        MR_RUN_COUNT(st.run_visits);
+        cur = kRunIrregular;
+        if (__float_as_int(v[14]) == 0) {
+            cur = kWalkDecide;
+            float mn0, mx0, mn1, mx1, k0 = 0.0f, k1 = 0.0f;
+            node_slabs_guarded<W>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
+            // node_decide's comparisons (its SAFE form) as lane masks: out = the lanes whose ray misses the child.  A compare mask
+            // has zero bits for inactive lanes, so the masks need no and with m_all.
+            const unsigned long long out0 = __builtin_amdgcn_ballot_w64(mn0 > k0) | __builtin_amdgcn_ballot_w64(mx0 < r.tmin);
+            const unsigned long long out1 = __builtin_amdgcn_ballot_w64(mn1 > k1) | __builtin_amdgcn_ballot_w64(mx1 < r.tmin);
+            if ((out0 | out1) == 0ull) {                              // every lane hits both: near child first, ties -> child 0
+                const unsigned long long one_first = __builtin_amdgcn_ballot_w64(mn0 > mn1);
+                if (__builtin_expect(one_first == 0ull, 1)) { stack_push(L, s_stack, ref1); cur = ref0; }
+                else if (one_first == m_all) { stack_push(L, s_stack, ref0); cur = ref1; }
+            } else {                                                  // every lane hits child 0 only / child 1 only: no branch
+                const bool only0 = (out0 | (out1 ^ m_all)) == 0ull, only1 = (out1 | (out0 ^ m_all)) == 0ull;
+                cur = only0 ? ref0 : only1 ? ref1 : (out0 & out1) == m_all ? kWalkPop : kWalkDecide;
+            }
+        }
+      } while ((unsigned)cur < kRunNodeLimit);
+        if (cur == kWalkPop) pop_uniform();                           // no lane hits a child
+        while ((unsigned)cur - (unsigned)kWalkFirstLeaf < leaf_span) {
+            // a leaf, every lane of the walk in it (leaf_step's scalar arm)
+            const unsigned bits = ~(unsigned)cur;
+            const unsigned first0 = bits >> kLeafCountBits;
+            unsigned cnt0 = bits & kLeafCountMask;
+            if (cnt0 == kLeafCountMask) cnt0 = p.leaf_cnt_ext[first0];
+            MR_RUN_COUNT(st.walk_leaves);
+            for (unsigned k = 0; k < cnt0; k++) {
+                float4 t0, t1, t2;
+                load_tri_uniform<W::rel>(p.tris, first0 + k, t0, t1, t2);
+                float t, b, g;
+                const bool ok = object_test<W::exact, W::obj, W::rel>(t0, t1, t2, r, L.best_t, t, b, g);
+                if (ok && t < L.best_t) {             // strict-less replacement (BVH.cpp:500)
+                    L.best_t = t; L.best_b = b; L.best_g = g; L.best_pos = (int)(first0 + k);
+                }
+            }
+            pop_uniform();
+        }
+        if ((unsigned)cur >= kRunNodeLimit) break;
+    }
+    if (cur == kWalkParted) {                          // the lanes part at a pop
+        L.cur = stack_pop(L, s_stack);
+    } else if (cur == kWalkDecide) {                   // the lanes part: no child hit in some, a child in others, or another near one
+        // node_step's visit of a node the wave shares, decided lane by lane.  (The record is loaded and the distances are computed a
+        // second time on purpose, as below: six distances alive across the loop's exit are alive across its leaves.)
+        const v16f v = load_node_scalar_at(p.nodes, off);
+        const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
+        const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
+        float mn0, mx0, mn1, mx1, k0 = 0.0f, k1 = 0.0f;
+        node_slabs_guarded<W>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
+#ifdef MIRO_RUN_COUNTS
+        if (((unsigned long long)__builtin_amdgcn_ballot_w64((mn0 > k0) || (mx0 < r.tmin)) &
+             (unsigned long long)__builtin_amdgcn_ballot_w64((mn1 > k1) || (mx1 < r.tmin))) != m_all) MR_RUN_COUNT(st.run_splits);
+        else MR_RUN_COUNT(st.end_pop);
+#endif
+        node_decide<false, true, true>(mn0, mx0, mn1, mx1, __float_as_int(v[12]), __float_as_int(v[13]), r, L, s_stack, st, k0, k1);
+    } else if (cur == kRunIrregular) {                 // the reference's own divisions, decided lane by lane
+        MR_RUN_COUNT(st.end_irregular);
+        // (the record is loaded a second time on purpose: kept live across the loop's exit its twelve corners -- or just its two child
+        // references: they are part of the sixteen-register tuple -- cost the hot loop scalar registers it spills for, and irregular
+        // nodes are rare -- a frame whose eye is irregular, where every visit comes this way, pays the run's entry and two loads per
+        // visit and is slower than before)
+        const v16f v = load_node_scalar_at(p.nodes, off);
+        const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
+        const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
+        float mn0, mx0, mn1, mx1;
+        node_slabs<walk_divide<W>>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
+        node_decide<false, false>(mn0, mx0, mn1, mx1, __float_as_int(v[12]), __float_as_int(v[13]), r, L, s_stack, st);
+    } else {                                         // kDone: every lane popped its sentinel.  A leaf the walk may not take (the
+        L.cur = cur;                                   // wave's leaf_step finds it uniform by its own test), a node of kRunNodeLimit or more
+#ifdef MIRO_RUN_COUNTS
+        if (cur == kDone) MR_RUN_COUNT(st.end_done);
+        else if (cur < 0) MR_RUN_COUNT(st.end_leaf);
+        else MR_RUN_COUNT(st.end_far_node);
+#endif
+    }
+}
+
+// the walks that take the uniform run: the octant loops with the three-pair guard, without counters
+template <typename W> constexpr bool walk_runs() { return W::run && slab_needs_tmin0(W::slab) && is_octant(W::oct) && !W::stats; }
+
+// one inner node (W::slab, W::scalar, W::oct, W::run: the slab forms and Walk at the top of this file)
+// m_have (run walks): the lanes of the wave that had work when traverse last looked
+template <typename W>
+__device__ __forceinline__ void node_step(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, int tid, Stats &st,
+                                          unsigned long long m_have = 0ull) {
     float mn0, mx0, mn1, mx1;
     constexpr bool kStats = W::stats, kSafe = slab_nan_free(W::slab), kGuarded = slab_guarded(W::slab);
     if (W::scalar) {
         const int cur0 = __builtin_amdgcn_readfirstlane(L.cur);
         // (a wave of a run walk at a node beyond the run's offsets takes the per-lane visit below: it is correct for any node)
-        constexpr bool kRuns = W::run && slab_needs_tmin0(W::slab) && is_octant(W::oct) && !kStats;
+        constexpr bool kRuns = walk_runs<W>();
         if (__all(L.cur == cur0) && (!kRuns || (unsigned)cur0 < kRunNodeLimit)) {
             if (kRuns) {
-                uniform_run<W>(p, r, L, s_stack, st, cur0);
+                // The lanes the walk leaves at inner nodes take the per-lane visit below at once, as traverse's node loop would have
+                // them do next.  (If-then and fall through, not if-else: laid out after the walk as its else branch, the per-lane visit
+                // keeps the values L had BEFORE the walk alive all through it -- best_t / best_b / best_g / best_pos twice.)
+                if ((unsigned long long)__builtin_amdgcn_ballot_w64(true) != m_have) {      // a subset of the working lanes: the run
+                    uniform_run<W>(p, r, L, s_stack, st, cur0);
+                    return;
+                }
+                uniform_walk<W>(p, r, L, s_stack, st, cur0);
+                if (L.cur < 0) return;
+            } else {
+                MR_RUN_COUNT(st.node_steps);
+                const v16f v = load_node_scalar(p.nodes, cur0);
+                const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
+                const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
+                if (slab_divides_irregular(W::slab) && __float_as_int(v[14]) != 0) {   // irregular node (wave-uniform): the reference's own divisions
+                    node_slabs<walk_divide<W>>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
+                    node_decide<kStats, false>(mn0, mx0, mn1, mx1, __float_as_int(v[12]), __float_as_int(v[13]), r, L, s_stack, st);
+                    return;
+                }
+                float k0 = 0.0f, k1 = 0.0f;
+                node_slabs_guarded<W>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
+                node_decide<kStats, kSafe, kGuarded>(mn0, mx0, mn1, mx1, __float_as_int(v[12]), __float_as_int(v[13]), r, L, s_stack, st, k0, k1);
                 return;
             }
-            MR_RUN_COUNT(st.node_steps);
-            const v16f v = load_node_scalar(p.nodes, cur0);
-            const float4 q0 = make_float4(v[0], v[1], v[2], v[3]), q1 = make_float4(v[4], v[5], v[6], v[7]);
-            const float4 q2 = make_float4(v[8], v[9], v[10], v[11]);
-            if (slab_divides_irregular(W::slab) && __float_as_int(v[14]) != 0) {   // irregular node (wave-uniform): the reference's own divisions
-                node_slabs<walk_divide<W>>(q0, q1, q2, r, mn0, mx0, mn1, mx1);
-                node_decide<kStats, false>(mn0, mx0, mn1, mx1, __float_as_int(v[12]), __float_as_int(v[13]), r, L, s_stack, st);
-                return;
-            }
-            float k0 = 0.0f, k1 = 0.0f;
-            node_slabs_guarded<W>(q0, q1, q2, r, L.best_t, mn0, mx0, mn1, mx1, k0, k1);
-            node_decide<kStats, kSafe, kGuarded>(mn0, mx0, mn1, mx1, __float_as_int(v[12]), __float_as_int(v[13]), r, L, s_stack, st, k0, k1);
-            return;
         }
     }
     // ---- inner node: test both children (BVH.cpp:593-624)
@@ -840,6 +1001,13 @@ __device__ __forceinline__ void traverse(const TraceParams &p, const RayRegs &r,
             } else {
                 if (want_tri) tri_step<W>(p, r, L, s_stack, st);
             }
+        }
+    } else if (W::flow == kFlowWhileWhile && walk_runs<W>()) {
+        // the lanes with work, handed down: a run that holds them all is a whole walk (uniform_run)
+        unsigned long long m_have;
+        while ((m_have = __builtin_amdgcn_ballot_w64(L.have())) != 0ull) {
+            while (L.cur >= 0) node_step<W>(p, r, L, s_stack, tid, st, m_have);
+            if (L.have()) leaf_step<W>(p, r, L, s_stack, tid, st);
         }
     } else if (W::flow == kFlowWhileWhile) {
         while (__any(L.have())) {

@@ -2,7 +2,8 @@
     make -C cse168-raytracer_amd VARIANT=_runc FRAME_DEFS=-DMIRO_RUN_COUNTS
     MIRO_LIB=cse168-raytracer_amd/lib_runc/libmiro_hip.so python tools/run_counts.py
 Prints, for one frame, the wave-level node visits, those taken inside uniform_run (mr_traverse.h) and the runs that ended on a
-split decision."""
+split decision, and how the uniform walks go: how many hold every working lane of their wave, the
+leaves and pops they take, and how they end (item 23)."""
 import argparse
 import ctypes as C
 import os
@@ -17,6 +18,11 @@ import torch  # noqa: E402
 import miro_amd  # noqa: E402
 from miro_amd import binding, scenes  # noqa: E402
 from miro_amd import frame as mframe  # noqa: E402
+
+
+# Stats of the counting build (mr_traverse.h), in its order
+COUNTERS = ("node_steps", "run_visits", "run_splits", "walks", "walks_whole", "end_leaf", "end_pop", "end_irregular", "end_far_node",
+            "end_done", "walk_leaves", "pops_agree", "pops_differ")
 
 
 def main():
@@ -36,15 +42,27 @@ def main():
     fr = mframe.FusedFrame(sc, d, a.w, a.h, spp=a.spp)
     fr.step()
     torch.cuda.synchronize()
-    tot = np.zeros(3, np.uint64)
+    tot = np.zeros(len(COUNTERS), np.uint64)
     for entry in ("mr_debug_run_counts_b256", "mr_debug_run_counts_b128"):
-        buf = np.zeros(3, np.uint64)
+        buf = np.zeros(len(COUNTERS), np.uint64)
         rc = getattr(L, entry)(buf.ctypes.data_as(C.c_void_p))
         assert rc == 0, rc
         tot += buf
-    steps, run, splits = (int(v) for v in tot)
+    c = dict(zip(COUNTERS, (int(v) for v in tot)))
+    steps, run, splits = c["node_steps"], c["run_visits"], c["run_splits"]
     print("%s %dx%dx%d: %d wave-level node visits, %d of them (%.1f %%) inside runs; %d runs (%.2f %% of the run visits) ended on a split decision" % (
         a.scene, a.w, a.h, a.spp, steps + run, run, 100.0 * run / max(steps + run, 1), splits, 100.0 * splits / max(run, 1)))
+    # the uniform walk.  A walk is what a run was, carried on through the leaves and pops it may take:
+    # each leaf taken and each pop taken with one value popped is a place where the run before ended and the next one began.
+    walks = max(c["walks"], 1)
+    print("  %d walks, %d of them (%.1f %%) whole; inside walks: %d leaves, %d pops with one value, %d pops with several" % (
+        c["walks"], c["walks_whole"], 100.0 * c["walks_whole"] / walks, c["walk_leaves"], c["pops_agree"], c["pops_differ"]))
+    print("  walks ended: %d split decision, %d lanes parted at a pop, %d every lane done, %d at a leaf they may not take, "
+          "%d at a pop they may not take, %d irregular node, %d node beyond the run's offsets" % (
+              splits, c["pops_differ"], c["end_done"], c["end_leaf"], c["end_pop"], c["end_irregular"], c["end_far_node"]))
+    taken = c["walk_leaves"] + c["pops_agree"] - c["end_done"]
+    print("  run boundaries of the walk-less kernel: %d; carried through by the walk: %d (%.1f %%)" % (
+        c["walks"] + taken, taken, 100.0 * taken / max(c["walks"] + taken, 1)))
 
 
 if __name__ == "__main__":
