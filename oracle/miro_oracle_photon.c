@@ -6,8 +6,11 @@
  * max_dist = PHOTON_MAX_DIST = 1e10 and nphotons = PHOTON_SAMPLES = 500 (Miro.h:16-17).
  * TEST INFRASTRUCTURE ONLY (see miro_oracle.h).
  *
- * PARITY UNPINNED: the reference holds no fixture or known answer for its photon map and cannot be built here;
- * this file is a line-by-line-faithful restatement checked only for self-consistency (brute-force k-NN).
+ * PARITY: pinned to the reference's own PhotonMap.cpp on every map WITHOUT A TIED MEDIAN (no node with a child has another
+ * photon in its subtree with the same pos[plane]): tests/test_photon_reference.py compares tree, found, dist2[0] and the
+ * irradiance bit for bit with tests/golden/photon_ref/, which oracle/_ref/photon_ref wrote (the reference's file compiled
+ * unchanged, oracle/ref_photon_driver.cpp).  NOT pinned: maps with a tied median, where median_split below selects by
+ * (coordinate, address) and the reference's Sedgewick partition does not (measured in DESIGN.md "Oracle").
  *
  * Quirks kept on purpose:
  *   - a node descends only if index < stored/2 - 1 (:160,:357), so the last three heap slots are never visited;
@@ -180,15 +183,17 @@ static inline void photon_dir(const orc_pmap *m, const photon *p, float *d)
     d[2] = m->costheta[p->theta];
 }
 
-/* max-heap on dist2[1..n]: move the hole at `at` down until (d, id) fits */
-static void sift_down(nearest *np, int at, float d, int id)
+/* max-heap on dist2[1..n]: move the hole at `at` down until (d, id) fits.  The reference stops at a child of the SAME distance
+ * while it builds the heap (:210, `>=`) and passes it while it inserts (:230, `>`): with equal distances in the heap that decides
+ * which photon sits at the root, and with it which of them the next insertion drops. */
+static void sift_down(nearest *np, int at, float d, int id, int pass_equal)
 {
     const int n = np->found;
     for (;;) {
         int c = 2 * at;
         if (c > n) break;
         if (c < n && np->dist2[c] < np->dist2[c + 1]) c++;
-        if (!(np->dist2[c] > d)) break;
+        if (pass_equal ? d > np->dist2[c] : d >= np->dist2[c]) break;
         np->dist2[at] = np->dist2[c];
         np->index[at] = np->index[c];
         at = c;
@@ -207,10 +212,10 @@ static void offer(nearest *np, float d, int id)
         return;
     }
     if (!np->heaped) {                               /* :197-217: heapify once, on the first overflow */
-        for (int k = np->found >> 1; k >= 1; k--) sift_down(np, k, np->dist2[k], np->index[k]);
+        for (int k = np->found >> 1; k >= 1; k--) sift_down(np, k, np->dist2[k], np->index[k], 0);
         np->heaped = 1;
     }
-    sift_down(np, 1, d, id);                         /* :222-238: replace the farthest */
+    sift_down(np, 1, d, id, 1);                       /* :222-238: replace the farthest */
     np->dist2[0] = np->dist2[1];                     /* :240: the radius shrinks only from now on */
 }
 

@@ -2,15 +2,16 @@
 tree bit for bit, and the oracle's kd-tree search equals brute force.  GPU: the wave-cooperative k-NN kernel
 against the oracle's restated irradiance_estimate.
 
-PARITY UNPINNED: the reference holds no photon-map fixture and cannot be built here, so these tests pin the HIP
-path to the restatement (oracle/miro_oracle_photon.c) only.
+PARITY: these tests pin the HIP path to the restatement (oracle/miro_oracle_photon.c).  The restatement itself, the host
+balance, the device build and the kernel are pinned to the reference's own PhotonMap.cpp in tests/test_photon_reference.py,
+exactly, on maps without a tied median; with a tied median the reference's tree is not reproduced (strict xfails there).
 
 This file stops at 200 000 photons (three layers of blocks) and 3 840 queries per launch (batches of 16 only).  The other
 regimes of the kernel are in tests/test_photon_regimes.py: maps with a fourth layer of blocks, launches of more than 102 400
 queries (batches of 64, the seam, the hand-out counter's re-arm), the counting instantiation behind count_stats(), device-built
 maps searched with equal work counters, launches of 1 ... 65 queries and of none, the empty map.  What stays unpinned in both
-files: which of two photons at exactly the same distance is dropped, the -0 / +0 identity of box corners, and the oracle being
-a restatement."""
+files: which of two photons at exactly the same distance is dropped, the -0 / +0 identity of box corners, and the reference's
+tree on maps with a tied median."""
 import numpy as np
 import pytest
 
@@ -292,6 +293,6 @@ def test_photon_search_fuzz(oracle, miro, seed):
     reference's 1e10, photon positions on a coarse grid (exact distance ties, coincident photons, duplicates) or generic, clustered
     or spread; queries on photons, between them, far outside the map, in runs of neighbours (the guessed radius) and scattered
     (its fallback).  `found` and the radius np.dist2[0] must be the oracle's on every query; powers are uniform, so the irradiance
-    does not depend on which of several photons at exactly the same distance is kept (PARITY UNPINNED like the rest of this file:
-    the oracle is a restatement)."""
+    does not depend on which of several photons at exactly the same distance is kept (on the gridded maps the oracle's tree is not
+    the reference's: tied medians, tests/test_photon_reference.py)."""
     photon_fuzz_case(oracle, miro, seed)

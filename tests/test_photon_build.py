@@ -5,7 +5,8 @@ mr_photon_map_balance -- which this feature leaves as it was.  A device-built ma
 arrays of export() (which, on such a map, reads the device arrays back) are compared with np.array_equal on their integer
 views, and count().  On tie-free inputs the oracle's PhotonMap is compared as well, as tests/test_photon.py's
 test_balance_identical compares it (plane on the nodes that descend).  On tied inputs only the host path is the yardstick:
-nobody has established the oracle's tie order.  No test asserts a speed."""
+with a tied median neither it nor the oracle gives the reference's tree (tests/test_photon_reference.py pins both builders to
+the reference's own PhotonMap.cpp on maps without one, and measures the rest).  No test asserts a speed."""
 import os
 import re
 import sys

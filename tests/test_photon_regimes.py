@@ -8,14 +8,14 @@ and test_gather_level.py do not enter:
   D  device-built maps searched like host-built ones WITH EQUAL WORK COUNTERS, which is what observes their boxes
   E  launches of fewer queries than a workgroup has waves, no query at all, and the map of no photons
 
-The yardstick of A, B and E is the oracle's PhotonMap.irradiance_estimate (a restatement: PARITY UNPINNED like the rest of the photon
-tests), of D the library's own host path, of C the plain kernel on the same map, which A and B tie to the oracle.  `found` must be
+The yardstick of A, B and E is the oracle's PhotonMap.irradiance_estimate (a restatement, itself pinned to the reference's own
+PhotonMap.cpp on maps without a tied median: tests/test_photon_reference.py), of D the library's own host path, of C the plain kernel on the same map, which A and B tie to the oracle.  `found` must be
 np.array_equal and the radius equal on its uint32 view in every comparison; the irradiance within 1e-5 of the largest expected
 value (test_irradiance_estimate_matches_oracle's figure for summation order) with the same finiteness pattern.
 
 Positions are tie-free (random, every coordinate distinct on its axis) wherever powers are non-uniform, powers uniform wherever
 positions are tied: which of two photons at exactly the same distance is dropped is not reproduced (csrc/mr_photon.hip's header).
-Not pinned here either: the -0 / +0 identity of box corners, the tree and tie order of the reference's own PhotonMap.cpp.  No test
+Not pinned here either: the -0 / +0 identity of box corners, the reference's tree on maps with a tied median.  No test
 asserts a speed."""
 import numpy as np
 import pytest
