@@ -1193,6 +1193,32 @@ mr_status mr_shade_lights(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hit
                                flags, d_rgb, d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
+// mr_render_direct's window over mr_shade_lights' light list, in one launch (mr_frame_lights.hip).  What the arguments alone can
+// get wrong is answered first, before any device call and before the scene's state is read; then the scene's state.
+mr_status mr_render_lights(mr_scene *s, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
+                           uint64_t *d_counts, void *stream) {
+    if (!s || !frame || !d_rgb) return fail(MR_ERR_INVALID, "mr_render_lights: NULL argument");
+    if (frame->W == 0 || frame->H == 0) return fail(MR_ERR_INVALID, "mr_render_lights: empty image");
+    mr_frame_desc fd = *frame;
+    if (fd.band_world <= 1) { fd.band_world = 1; fd.band_rank = 0; if (fd.band_rows == 0) fd.band_rows = 1; }
+    mr_status st = check_frame_lights(fd);
+    if (st != MR_OK) return st;
+    if ((reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_sample_rgb) & 3))
+        return fail(MR_ERR_INVALID, "mr_render_lights: the hit buffer must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned");
+    if ((st = require_device(s)) != MR_OK) return st;
+    if (s->lights.empty()) return fail(MR_ERR_STATE, "mr_render_lights: the scene has no lights (mr_scene_set_lights)");
+    if (!s->tex.blob.empty())
+        return fail(MR_ERR_STATE, "mr_render_lights: the scene has a texture table (mr_scene_set_textures) and this call shades without "
+                                  "the lookup; use the batched calls mr_trace -> mr_shade_lights, or mr_trace -> mr_hit_surface -> "
+                                  "mr_shade_lights_surface");
+    if ((fd.flags & MR_TRACE_ANY) && s->dev.refractive)
+        return fail(MR_ERR_STATE, "mr_render_lights: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)");
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    return launch_frame_lights(s->dev, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
+                               reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+}
+
 mr_status mr_gen_eye_rays_lens(mr_scene *s, const mr_camera *cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp,
                                uint32_t jitter, uint32_t seed, mr_ray *d_rays, void *stream, const mr_lens_desc *lens,
                                const float *d_samples_in, float *d_samples_out, uint64_t *d_counts) {

@@ -287,6 +287,12 @@ mr_status launch_shade_lights(const DeviceScene &ds, const ShadeLight *lights, u
                               const mr_hit *d_hits, const float *d_weights, const uint32_t *d_pixels, unsigned long long n,
                               uint32_t spp, uint32_t flags, float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts,
                               hipStream_t stream);
+// the fused frame over the light list (mr_frame_lights.hip, mr_render_lights).  fd: band_world >= 1 (as mr_render_direct hands it
+// to launch_frame).  check_frame_lights: what the descriptor alone can get wrong (spp, bands, rows, size, flags), without a
+// device call or a look at any scene; launch_frame_lights: one kernel on `stream`, none for an empty window
+mr_status check_frame_lights(const mr_frame_desc &fd);
+mr_status launch_frame_lights(const DeviceScene &ds, const ShadeLight *lights, uint32_t n_lights, const mr_frame_desc &fd, float *d_rgb,
+                              mr_hit *d_hits, float *d_sample_rgb, unsigned long long *d_counts, hipStream_t stream);
 
 // the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
 // square light, side * side shadow rays per hit and light

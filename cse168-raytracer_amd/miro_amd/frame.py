@@ -125,14 +125,23 @@ def gather_framebuffer(local_rgb, H, W, band, rank, world, group=None, dst=0):
 class FusedFrame:
     """One rank's share of a direct-light frame rendered by mr_render_direct: a single launch per step, no ray buffers.
     Resident: the float framebuffer shard (12 B per pixel) and, when `keep_hits`, the two hit-record buffers
-    (16 + 16 B per sample) that parity tests compare with the batched pipeline's."""
+    (16 + 16 B per sample) that parity tests compare with the batched pipeline's.  With `lights` the launch is
+    mr_render_lights: the frame over a light list, and `keep_hits` keeps the primary records only."""
 
     def __init__(self, scene, desc, W, H, spp=1, band=None, rank=0, world=1, jitter=None, seed=168, flags=0, rgb=None,
-                 tiled=None, keep_hits=False, any_shadow=False, no_shadows=False):
+                 tiled=None, keep_hits=False, any_shadow=False, no_shadows=False, lights=None):
         """no_shadows: MR_FRAME_NO_SHADOWS, the reference's -DDISABLE_SHADOWS build (primary rays only, BASELINE config 2).
-        A scene with a material table (Scene.set_materials) is shaded with its per-object materials (Phong.cpp:99-156)."""
+        A scene with a material table (Scene.set_materials) is shaded with its per-object materials (Phong.cpp:99-156).
+        lights: a list for Scene.set_lights (point and disc lights), set once here; step() then renders with
+        Scene.render_lights instead of the description's one point light (any_shadow: MR_TRACE_ANY for the shadow rays;
+        no_shadows is not available there).  None: nothing changes."""
         if isinstance(desc, str):
             desc = scenes.SCENES[desc]
+        if lights is not None and no_shadows:
+            raise ValueError("FusedFrame: no_shadows is not available with a light list (mr_render_lights always traces shadow rays)")
+        self.lights = None if lights is None else list(lights)
+        if self.lights is not None:
+            scene.set_lights(self.lights)
         self.scene, self.desc, self.W, self.H, self.spp = scene, desc, W, H, spp
         self.jitter = (spp > 1) if jitter is None else jitter
         self.seed = seed
@@ -148,7 +157,7 @@ class FusedFrame:
         if self.d_rgb.numel() < 3 * self.n_pixels or self.d_rgb.dtype != torch.float32 or not self.d_rgb.is_contiguous():
             raise ValueError("rgb must be a contiguous float32 buffer of at least %d x 3 values" % self.n_pixels)
         self.d_hits = torch.empty((max(self.n, 1), 4), **f32) if keep_hits else None
-        self.d_shadow_hits = torch.empty((max(self.n, 1), 4), **f32) if keep_hits else None
+        self.d_shadow_hits = torch.empty((max(self.n, 1), 4), **f32) if keep_hits and self.lights is None else None
         self.d_counts = torch.zeros(2, dtype=torch.int64, device=self.device)
         self.cam = binding.make_camera(desc["eye"], desc["lookat"], desc["up"], desc["fov"])
 
@@ -158,6 +167,11 @@ class FusedFrame:
 
     def step(self, stream=None):
         if self.n == 0:
+            return
+        if self.lights is not None:
+            self.scene.render_lights(self.cam, self.W, self.H, self.d_rgb, bands=self.bands, spp=self.spp, jitter=self.jitter,
+                                     seed=self.seed, tiled=self.tiled, flags=self.flags, d_hits=self.d_hits, d_counts=self.d_counts,
+                                     stream=stream)
             return
         self.scene.render_direct(self.cam, self.W, self.H, self.d_rgb, self.desc["light"], self.desc["wattage"],
                                  bands=self.bands, spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled,

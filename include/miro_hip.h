@@ -303,6 +303,9 @@ typedef struct mr_frame_desc {
  * every replay. */
 mr_status mr_render_direct(mr_scene *scene, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, mr_hit *d_shadow_hits,
                            uint64_t *d_counts, void *stream);
+/* "mr_render_lights" (declared, with its whole contract, in miro_hip_surface.h): this frame over the scene's light list
+ * (mr_scene_set_lights: point and disc lights) and its material table instead of `light` / `diffuse`, bit for bit
+ * mr_gen_eye_rays[_tiled] -> mr_trace -> mr_shade_lights; one launch, no counters, no eye-relative tables. */
 
 /* ---- multi-GPU frames: image rows dealt to the devices in interleaved bands -------------------
  * Bands of band_rows rows are dealt round-robin: band b (rows [b*band_rows, ...)) belongs to rank b % world and is that

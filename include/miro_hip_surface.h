@@ -76,6 +76,33 @@ mr_status mr_gen_path_rays_surface(mr_scene *scene, const mr_ray *d_rays, const 
  *   upload_ms  either: flattening the tree into the device layout and uploading it (0 with host_only) */
 mr_status mr_bvh_build_timing(uint32_t *builder_used, double *prims_ms, double *levels_ms, double *finish_ms, double *upload_ms);
 
+/* ---- the whole direct-light frame step over the scene's LIGHT LIST in ONE launch ----------------------------------------
+ * mr_render_direct's frame with Phong::shade's loop over Scene::lights() (Phong.cpp:59-63) in the place of its one point
+ * light: for every sample Camera::eyeRay -> Scene::trace -> for every light of mr_scene_set_lights, in list order, the shadow
+ * ray, Scene::trace, the occluder's light scale and the light's terms added to L (from 0; a miss contributes 0) -> the pixel's
+ * mean.  The same hit records, per-sample L and pixels, bit for bit, as the batched
+ *   mr_gen_eye_rays[_tiled] -> mr_trace -> mr_shade_lights(d_ray_rgb) [-> pairwise mean over each pixel's samples]
+ * on the same scene, camera, seed and sample order, without the ray, hit and per-ray colour buffers (60 bytes per sample).
+ * Window: mr_render_direct's in every respect -- rows [y0,y1) or one rank's interleaved bands, spp a power of two <= 64,
+ *   jitter, seed, tiled.  frame->light and frame->diffuse are NOT read.
+ * Lights: the scene's list (point and disc lights, at most MR_MAX_LIGHTS).  Materials: the table of mr_scene_set_materials,
+ *   or the white Lambert without one -- what mr_shade_lights uses.
+ * d_rgb: rows*W*3 floats, window rows in band order, image order inside a row.  Optional device outputs (NULL to skip):
+ *   d_hits        rows*W*spp records in sample order (the tiled order with frame->tiled), 16-byte aligned
+ *   d_sample_rgb  3 floats per sample in d_hits' order: the sample's un-weighted L (0 for a miss)
+ *   d_counts      [0] += samples, [1] += shadow rays = samples with a hit x lights (8-byte aligned, not zeroed by the call)
+ * flags: MR_MATH_PRODUCT, MR_TRACE_INCOHERENT (both kinds of ray), MR_TRACE_ANY (shadow rays only).
+ * Launches: with device buffers the call enqueues ONE kernel on `stream` and can be captured into a graph; it allocates
+ *   nothing and uses none of the scene's hand-out counters or eye-relative tables, so calls on one scene may overlap freely.
+ * Errors, in this order.  MR_ERR_INVALID, before any device call and before the scene's state is read: NULL scene / frame /
+ *   d_rgb; W or H of 0; spp not a power of two <= 64; a bad band description; rows outside the image; window too large; any
+ *   other flag, MR_FRAME_NO_SHADOWS included; d_hits not 16-byte aligned (d_counts 8, the float buffers 4).  MR_ERR_STATE: a
+ *   scene that is not built or was built host_only; a scene without lights; a scene with a texture table (use mr_trace ->
+ *   mr_shade_lights, or mr_hit_surface -> mr_shade_lights_surface); MR_TRACE_ANY with a refractive material.  An empty window
+ *   (y0 == y1, or a rank without bands) is MR_OK with no launch. */
+mr_status mr_render_lights(mr_scene *scene, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
+                           uint64_t *d_counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
