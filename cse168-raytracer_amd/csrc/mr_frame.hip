@@ -374,7 +374,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
 #if defined(MIRO_RUN_COUNTS)
     {
         const unsigned mine[kRunCounters] = {st.node_steps, st.run_visits, st.run_splits, st.walks, st.walks_whole, st.end_leaf, st.end_pop,
-                                             st.end_irregular, st.end_far_node, st.end_done, st.walk_leaves, st.pops_agree, st.pops_differ};
+                                             st.end_irregular, st.end_far_node, st.end_done, st.walk_leaves, st.pops_agree, st.pops_differ, st.tri_uniform, st.tri_skipped};
         workgroup_add<kTraceBlock, kRunCounters>(mine, g_run_counts);
     }
 #endif

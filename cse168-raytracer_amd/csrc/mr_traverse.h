@@ -58,11 +58,14 @@ constexpr float kInf = __builtin_huge_valf();
 // the wave that still have work ("whole"), how a walk ends besides a split decision -- at a leaf it may not take, at a pop it
 // may not take, at an irregular node, at a node of kRunNodeLimit or more, with every lane done --, the leaves taken inside a
 // walk, and the pops inside a walk after which the lanes hold one value / different values.
-constexpr int kRunCounters = 13;
+// ... and the triangle tests of the uniform leaf loops that carry the rejection guard (item 24): wave-level tests, and those of
+// them the guard skipped.
+constexpr int kRunCounters = 15;
 struct Stats {
     unsigned long long box, tri;
     unsigned node_steps, run_visits, run_splits;
     unsigned walks, walks_whole, end_leaf, end_pop, end_irregular, end_far_node, end_done, walk_leaves, pops_agree, pops_differ;
+    unsigned tri_uniform, tri_skipped;
 };
 __device__ __forceinline__ void run_count_once(unsigned &c) {
     const int lane = (int)__lane_id();
@@ -391,6 +394,70 @@ __device__ __forceinline__ bool object_test(const float4 q0, const float4 q1, co
     return tri_test<EXACT>(q0, q1, q2, r, tmax, t, beta, gamma);
 }
 
+// The rejection guard of the uniform leaf loops.  In a uniform leaf the whole wave tests ONE
+// triangle, and most of those tests end with every lane rejecting it: two or three IEEE division sequences (11 VALU each, one of
+// them a quarter-rate v_rcp_f32) and the reject test computed for nothing.  A lane is SURE of the reference's rejection when, for the
+// numerator nb of beta (or ng of gamma),
+//     nb * k < -|ddotn|      with k = 2^13 carrying the sign bit of ddotn.
+//   * Scaling by a power of two is exact (a denormal scaled UP stays exact); if nb * k overflows it is +-inf of the product's
+//     sign, which keeps the inequality because |ddotn| is finite wherever the compare can hold (ddotn = +-inf: nothing is below
+//     -inf, the lane is not sure) -- and |nb| * 2^13 >= 2^128 > |ddotn| then holds in the reals too.
+//   * k has ddotn's sign, so nb * k = 2^13 * nb * sgn(ddotn): the compare says nb * sgn(ddotn) * 2^13 < -|ddotn|, that is
+//     nb / ddotn < -2^-13 in the reals for ddotn != 0.  The sign bit is read as a bit, which is what IEEE division does with
+//     +-0: for ddotn = +0 the lane is sure iff nb < 0 and the reference's quotient is -inf; for ddotn = -0 iff nb > 0, again -inf;
+//     nb = +-0 over ddotn = +-0 is NaN in the reference and 0 < -0 is false here.
+//   * Rounding is monotone and 2^-13 is a float: the real quotient below -2^-13 rounds to a quotient <= -2^-13 < -1e-4f = -kEps
+//     (2^-13 = 1.2207e-4), so the reference's `beta < -epsilon` (Triangle.cpp:158) rejects the triangle.
+//   * A NaN operand fails every compare: the lane is not sure.
+// When every lane that takes part is sure the test is skipped: a rejected test writes nothing, so hit records and pixels keep
+// their bits.  Otherwise the wave runs the test as it was -- the same quotients of the same operands, the same reject test.
+// Cost: v_and + v_or for k, two v_mul, and the two compares as the compiler emits them -- one v_min and one v_cmp with source
+// modifiers (minNum keeps the number when one product is a NaN: the same decision) --, one scalar compare of the mask with exec, a branch.
+__device__ __forceinline__ bool tri_surely_rejects(float nb, float ng, float ddotn) {
+    // 2^13 with ddotn's sign.  (Two VOP2 instructions that carry their constants as literals: written as an and-or the constant
+    // is moved to a vector register of its own in front of the frame's loop, alive through the whole kernel.)
+    float k;
+    asm("v_and_b32 %0, 0x80000000, %1\n\tv_or_b32 %0, 0x46000000, %0" : "=v"(k) : "v"(ddotn));
+    const float lim = -__builtin_fabsf(ddotn);
+    return (nb * k < lim) || (ng * k < lim);
+}
+
+// the exact triangle test of a uniform leaf behind that guard: ddotn and the numerators of beta and gamma by today's operations
+// (tri_test<true> / tri_test_rel: for the scene's own records that includes p, u and w), the guard, and -- unless every lane is
+// sure -- the three divisions and the reject test on those operands.  False for a skipped test, t / beta / gamma unwritten.
+template <bool REL>
+__device__ __forceinline__ bool tri_test_guarded(const float4 q0, const float4 q1, const float4 q2, const RayRegs &r, float tmax,
+                                                 float &t, float &beta, float &gamma, Stats &st) {
+    float ddotn, pn, nb, ng;
+    if (REL) {
+        ddotn = (r.mx_ * q0.x + r.my_ * q0.y) + r.mz_ * q0.z;
+        nb = (r.mx_ * q1.x + r.my_ * q1.y) + r.mz_ * q1.z;
+        ng = (r.mx_ * q1.w + r.my_ * q2.x) + r.mz_ * q2.y;
+        pn = q0.w;
+    } else {
+        const float3 p = tri_p(q0, r.ox, r.oy, r.oz);
+        ddotn = (r.mx_ * q2.y + r.my_ * q2.z) + r.mz_ * q2.w;
+        pn = tri_pn(p, q2);
+        const float3 u = tri_u(p, q1, q2);
+        nb = (r.mx_ * u.x + r.my_ * u.y) + r.mz_ * u.z;
+        const float3 w = tri_w(p, q0, q1);
+        ng = (r.mx_ * w.x + r.my_ * w.y) + r.mz_ * w.z;
+    }
+    MR_RUN_COUNT(st.tri_uniform);
+    if (__builtin_amdgcn_ballot_w64(tri_surely_rejects(nb, ng, ddotn)) == __builtin_amdgcn_ballot_w64(true)) {
+        MR_RUN_COUNT(st.tri_skipped);
+        return false;
+    }
+    // Triangle.cpp:158's reject test in its own order of comparisons, t divided only for the lanes that beta and gamma let through
+    // (what the compiler makes of tri_test's `||` chain by itself; behind the guard's branch it has to be told)
+    beta = nb / ddotn;
+    gamma = ng / ddotn;
+    if ((beta < -kEps) || (gamma < -kEps) || (beta + gamma > 1 + kEps)) return false;
+    asm("" : "+v"(ddotn));      // (an empty statement the division depends on: it is not computed ahead of the branch for every lane)
+    t = pn / ddotn;
+    return !((t < r.tmin) || (t > tmax));
+}
+
 // ---------------------------------------------------------------------------------------------------
 // closest-hit / any-hit traversal, one ray per lane (its slab forms and control flows: the kVar... bits of mr_launch.h)
 // ---------------------------------------------------------------------------------------------------
@@ -530,6 +597,23 @@ constexpr int kWalkFirstLeaf = kDone + 16;   // the smallest leaf reference (abo
 template <bool REL>
 __device__ __forceinline__ void load_tri_uniform(const float4 *tris, unsigned pos_uniform, float4 &q0, float4 &q1, float4 &q2);
 
+// the walks whose uniform leaf loops carry the rejection guard (tri_test_guarded): those that take the uniform run -- the octant
+// loops of the fused frame kernel's eye-relative, uniform-material forms, both traces; exact triangle records only
+template <typename W> constexpr bool walk_guards_tris() {
+    return W::run && slab_needs_tmin0(W::slab) && is_octant(W::oct) && !W::stats && W::exact && !W::obj;
+}
+// the object test of a uniform leaf: behind the guard in those walks, object_test as ever in all others.
+// IN_WALK: the leaf loop of uniform_walk (else leaf_step's scalar arm).  The walk's loop carries the guard on the eye-relative
+// tables only: with it in the shadow trace's walk as well -- numerators first or beta before w, the divisions in any order or
+// chained one behind the other -- frame_kernel<794, 0, false> spills 6 vector registers / 28 bytes of scratch against the 4 / 20
+// of tests/golden/kernel_budget.json, so that loop keeps today's code.
+template <typename W, bool IN_WALK = false>
+__device__ __forceinline__ bool uniform_object_test(const float4 q0, const float4 q1, const float4 q2, const RayRegs &r, float tmax,
+                                                    float &t, float &beta, float &gamma, Stats &st) {
+    if constexpr (walk_guards_tris<W>() && (W::rel || !IN_WALK)) return tri_test_guarded<W::rel>(q0, q1, q2, r, tmax, t, beta, gamma, st);
+    else return object_test<W::exact, W::obj, W::rel>(q0, q1, q2, r, tmax, t, beta, gamma);
+}
+
 template <typename W>
 __device__ __forceinline__ void uniform_run(const TraceParams &p, const RayRegs &r, Lane &L, int *s_stack, Stats &st, int cur) {
     const unsigned long long m_all = __builtin_amdgcn_ballot_w64(true);
@@ -648,7 +732,7 @@ __device__ __forceinline__ void uniform_walk(const TraceParams &p, const RayRegs
                 float4 t0, t1, t2;
                 load_tri_uniform<W::rel>(p.tris, first0 + k, t0, t1, t2);
                 float t, b, g;
-                const bool ok = object_test<W::exact, W::obj, W::rel>(t0, t1, t2, r, L.best_t, t, b, g);
+                const bool ok = uniform_object_test<W, true>(t0, t1, t2, r, L.best_t, t, b, g, st);
                 if (ok && t < L.best_t) {             // strict-less replacement (BVH.cpp:500)
                     L.best_t = t; L.best_b = b; L.best_g = g; L.best_pos = (int)(first0 + k);
                 }
@@ -884,7 +968,7 @@ __device__ __forceinline__ void leaf_step(const TraceParams &p, const RayRegs &r
                 load_tri_uniform<REL>(p.tris, first0 + k, q0, q1, q2);
                 if (!(ANY && done)) {
                     float t, b, g;
-                    const bool ok = object_test<EXACT, OBJ, REL>(q0, q1, q2, r, L.best_t, t, b, g);
+                    const bool ok = uniform_object_test<W>(q0, q1, q2, r, L.best_t, t, b, g, st);
                     if (ok && t < L.best_t) {
                         L.best_t = t; L.best_b = b; L.best_g = g; L.best_pos = (int)(first0 + k);
                         if (ANY) done = true;

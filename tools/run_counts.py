@@ -3,7 +3,8 @@
     MIRO_LIB=cse168-raytracer_amd/lib_runc/libmiro_hip.so python tools/run_counts.py
 Prints, for one frame, the wave-level node visits, those taken inside uniform_run (mr_traverse.h) and the runs that ended on a
 split decision, and how the uniform walks go: how many hold every working lane of their wave, the
-leaves and pops they take, and how they end (item 23)."""
+leaves and pops they take, and how they end (item 23); and the wave-level triangle tests of the uniform leaf loops that carry the
+rejection guard, with those the guard skipped (item 24)."""
 import argparse
 import ctypes as C
 import os
@@ -22,7 +23,7 @@ from miro_amd import frame as mframe  # noqa: E402
 
 # Stats of the counting build (mr_traverse.h), in its order
 COUNTERS = ("node_steps", "run_visits", "run_splits", "walks", "walks_whole", "end_leaf", "end_pop", "end_irregular", "end_far_node",
-            "end_done", "walk_leaves", "pops_agree", "pops_differ")
+            "end_done", "walk_leaves", "pops_agree", "pops_differ", "tri_uniform", "tri_skipped")
 
 
 def main():
@@ -63,6 +64,11 @@ def main():
     taken = c["walk_leaves"] + c["pops_agree"] - c["end_done"]
     print("  run boundaries of the walk-less kernel: %d; carried through by the walk: %d (%.1f %%)" % (
         c["walks"] + taken, taken, 100.0 * taken / max(c["walks"] + taken, 1)))
+    # the rejection guard of the uniform leaf loops (item 24): eye rays in the walk's leaf loop and in leaf_step's scalar arm, shadow
+    # rays in leaf_step's scalar arm
+    waves = a.w * a.h * a.spp / 64.0
+    print("  guarded wave-level triangle tests: %d (%.2f per 64 samples), %d of them (%.1f %%) skipped by the guard" % (
+        c["tri_uniform"], c["tri_uniform"] / waves, c["tri_skipped"], 100.0 * c["tri_skipped"] / max(c["tri_uniform"], 1)))
 
 
 if __name__ == "__main__":
