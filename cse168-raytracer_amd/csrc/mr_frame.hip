@@ -298,12 +298,13 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
                 for (int k = 0; k < 3; k++) { la.L[k] = a.lt.L[k]; la.color[k] = a.lt.color[k]; }
                 la.wattage = a.lt.wattage;
                 rec::surface_point_od(mm, ox, oy, oz, rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
-                phong_terms(la, rec::material_of(mm, h.prim), P, N, rb.x, rb.y, rb.z, c, highlight);
+                phong_terms<true>(la, rec::material_of(mm, h.prim), P, N, rb.x, rb.y, rb.z, c, highlight);
             } else {
                 surface_od<true>(a.m, ox, oy, oz, rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
             }
             if (SHADOW != 2) shadow_ray_of(P, a.lt.L[0], a.lt.L[1], a.lt.L[2], sa, sb);
-            if (!MAT) phong_direct(a.lt, P, N, rb.x, rb.y, rb.z, c);                            // Phong.cpp:116-156
+            // <true>: no powf for a highlight the whole wave gets as exact zero (highlight_of's ZERO_GUARD, mr_phong.h)
+            if (!MAT) phong_direct<true>(a.lt, P, N, rb.x, rb.y, rb.z, c);                      // Phong.cpp:116-156
             if (SHADOW != 2) my_shadow_rays++;
         }
         if (SHADOW != 2) {

@@ -87,24 +87,46 @@ __device__ __forceinline__ float light_scale_of(const rec::MeshMat &m, const flo
 
 // The specular highlight (Phong.cpp:149-156).  l: the normalised direction to the light, N normalised, (dx, dy, dz) the
 // direction of the ray that produced the hit, f2 the light's falloff factor.
+//
+// ZERO_GUARD (the fused frame): powf(x, 500.0f) is some 125 VALU instructions, and for nearly every
+// sample its result is exactly +0 -- x^500 is below half the smallest denormal, 2^-150, for x < 2^-0.3 = 0.8123, that is
+// outside a cone of 36 degrees around the mirror direction.  A lane is SURE of the zero when its clamped e is below
+// kHighlightZeroBelow; when every lane that is here is sure, e = +0 is written without the call.
+//   * The constant: tools/pow_zero_probe.hip runs this device's powf(x, 500.0f) -- through highlight_pow below, the very call of
+//     this function -- on every float of [0, 1] and prints the largest X with a bitwise +0 for every float of [0, X]
+//     (profiles/pow_zero_probe.log: X = 0x1.a0733cp-1 = 0.8133792).  0.75 is below it; 0.75^500 = 2^-207.5 lies 57 binades
+//     under the rounding boundary, so the last bits of powf's log2 and exp2 have no say.
+//   * The clamp comes first, as it always did: a negative e and -0 are +0 after fmaxf, and 0^500 = +0 is in the probe's range.
+//   * A NaN e leaves the clamp as 1 (fminf and fmaxf return their other operand), 1 < 0.75 is false: never sure.
+//   * Inactive lanes: the ballot of the compare holds no bit of a lane that is not here, and is compared with the ballot of
+//     `true`, the mask of the lanes that are (inside the caller's `if (hit)`, and `if (shininess < inf)` where that is a branch).
+//     A lane without a hit neither blocks the skip nor receives a value.
+//   * Otherwise the whole wave calls powf on the same operand as without the guard.  What follows (:154) is the same
+//     instructions on +0 either way.
+constexpr float kHighlightZeroBelow = 0.75f;
+__device__ __forceinline__ float highlight_pow(float e) { return powf(e, 500.0f); }
+template <bool ZERO_GUARD = false>
 __device__ __forceinline__ float highlight_of(const float l[3], const float N[3], float dx, float dy, float dz, float f2, float wattage,
                                               float samples = 1.0f) {
     const float two = 2 * ((l[0] * N[0] + l[1] * N[1]) + l[2] * N[2]);
     const float rx = -l[0] + two * N[0], ry = -l[1] + two * N[1], rz = -l[2] + two * N[2];
     float e = (-dx * rx + -dy * ry) + -dz * rz;
-    e = powf(fmaxf(0.0f, fminf(1.0f, e)), 500.0f);
+    e = fmaxf(0.0f, fminf(1.0f, e));
+    if (ZERO_GUARD && __builtin_amdgcn_ballot_w64(e < kHighlightZeroBelow) == __builtin_amdgcn_ballot_w64(true)) e = 0.0f;
+    else e = highlight_pow(e);
     return fmaxf(0.0f, e * f2 * wattage / samples);                // :154
 }
 // Phong.cpp:146-156 once the light has given l, nDotL and its falloff factor f2: diffuse[c] (to be multiplied by the light
 // scale, :146) and the highlight (added unscaled; 0 for a material of infinite shininess)
 // dc: the hit's diffuseColor (Phong.cpp:51-56) -- the texture's colour for a TexturedPhong (mr_texture.h), m_diffuse itself for a
 // plain Phong (Phong::diffuse2D), which is the second form.  The highlight does not see it.
+template <bool ZERO_GUARD = false>
 __device__ __forceinline__ void lit_terms(const float color[3], float wattage, const float *mt, const float *dc, const float N[3],
                                           const float l[3], float nDotL, float f2, float dx, float dy, float dz, float diffuse[3],
                                           float &highlight, float samples = 1.0f) {
     const float diff = fmaxf(0.0f, nDotL * f2 * wattage / samples);
     for (int c = 0; c < 3; c++) diffuse[c] = color[c] * (diff * dc[c] * mt[c]);               // :146
-    highlight = mt[9] < __builtin_huge_valf() ? highlight_of(l, N, dx, dy, dz, f2, wattage, samples) : 0.0f;
+    highlight = mt[9] < __builtin_huge_valf() ? highlight_of<ZERO_GUARD>(l, N, dx, dy, dz, f2, wattage, samples) : 0.0f;
 }
 __device__ __forceinline__ void lit_terms(const float color[3], float wattage, const float *mt, const float N[3], const float l[3],
                                           float nDotL, float f2, float dx, float dy, float dz, float diffuse[3], float &highlight) {
@@ -115,6 +137,7 @@ __device__ __forceinline__ void lit_terms(const float color[3], float wattage, c
 // of a hit with light scale s != 0 is diffuse[c] * s + highlight, and 0 for s == 0 (Phong.cpp:100-103 skips the light).
 // mt: the hit's material record, dc its diffuseColor (lit_terms; the forms without dc are a plain Phong's); N normalised;
 // (dx, dy, dz) the direction of the ray that produced the hit.
+template <bool ZERO_GUARD = false>
 __device__ __forceinline__ void phong_terms(const float L[3], const float color[3], float wattage, const float *mt, const float *dc,
                                             const float P[3], const float N[3], float dx, float dy, float dz, float diffuse[3],
                                             float &highlight, float samples = 1.0f) {
@@ -124,20 +147,22 @@ __device__ __forceinline__ void phong_terms(const float L[3], const float color[
     l[0] *= inv; l[1] *= inv; l[2] *= inv;
     const float nDotL = (N[0] * l[0] + N[1] * l[1]) + N[2] * l[2];
     const float f2 = 1.0f / (falloff * 4.0f * kPhongPI * kPhongPI);                           // :140
-    lit_terms(color, wattage, mt, dc, N, l, nDotL, f2, dx, dy, dz, diffuse, highlight, samples);
+    lit_terms<ZERO_GUARD>(color, wattage, mt, dc, N, l, nDotL, f2, dx, dy, dz, diffuse, highlight, samples);
 }
+template <bool ZERO_GUARD = false>
 __device__ __forceinline__ void phong_terms(const float L[3], const float color[3], float wattage, const float *mt, const float P[3],
                                             const float N[3], float dx, float dy, float dz, float diffuse[3], float &highlight,
                                             float samples = 1.0f) {
-    phong_terms(L, color, wattage, mt, mt, P, N, dx, dy, dz, diffuse, highlight, samples);
+    phong_terms<ZERO_GUARD>(L, color, wattage, mt, mt, P, N, dx, dy, dz, diffuse, highlight, samples);
 }
 __device__ __forceinline__ void phong_terms(const LightArgs &a, const float *mt, const float *dc, const float P[3], const float N[3],
                                             float dx, float dy, float dz, float diffuse[3], float &highlight) {
     phong_terms(a.L, a.color, a.wattage, mt, dc, P, N, dx, dy, dz, diffuse, highlight);
 }
+template <bool ZERO_GUARD = false>
 __device__ __forceinline__ void phong_terms(const LightArgs &a, const float *mt, const float P[3], const float N[3], float dx,
                                             float dy, float dz, float diffuse[3], float &highlight) {
-    phong_terms(a.L, a.color, a.wattage, mt, mt, P, N, dx, dy, dz, diffuse, highlight);
+    phong_terms<ZERO_GUARD>(a.L, a.color, a.wattage, mt, mt, P, N, dx, dy, dz, diffuse, highlight);
 }
 // Phong.cpp:121-136 for a DirectionalAreaLight.  l: the normalised direction (the shadow ray's).  Returns false when the hit
 // lies outside the disc's cylinder (:133, the light is skipped); otherwise lit_terms with nDotL = dot(N, -normal) on the
@@ -167,12 +192,13 @@ __device__ __forceinline__ void phong_combine(const float diffuse[3], float high
 
 // The uniform-material callers' form: N is the un-normalised HitInfo::N and is normalised in place; the material is Phong's
 // default but for its diffuse colour (shininess 1 < infinity: the highlight is on), the light is not occluded.
+template <bool ZERO_GUARD = false>
 __device__ __forceinline__ void phong_direct(const DirectLight &a, const float P[3], float N[3], float dx, float dy, float dz,
                                              float out[3]) {
     normalize3(N);                                                 // Scene.cpp:262
     const float mt[11] = {a.diffuse[0], a.diffuse[1], a.diffuse[2], 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.0f, 1.0f};
     float diffuse[3], highlight;
-    phong_terms(a.L, a.color, a.wattage, mt, P, N, dx, dy, dz, diffuse, highlight);
+    phong_terms<ZERO_GUARD>(a.L, a.color, a.wattage, mt, P, N, dx, dy, dz, diffuse, highlight);
     phong_combine(diffuse, highlight, 1.0f, out);
 }
 
