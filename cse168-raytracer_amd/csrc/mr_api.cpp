@@ -1195,28 +1195,59 @@ mr_status mr_shade_lights(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hit
 
 // mr_render_direct's window over mr_shade_lights' light list, in one launch (mr_frame_lights.hip).  What the arguments alone can
 // get wrong is answered first, before any device call and before the scene's state is read; then the scene's state.
-mr_status mr_render_lights(mr_scene *s, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
-                           uint64_t *d_counts, void *stream) {
-    if (!s || !frame || !d_rgb) return fail(MR_ERR_INVALID, "mr_render_lights: NULL argument");
-    if (frame->W == 0 || frame->H == 0) return fail(MR_ERR_INVALID, "mr_render_lights: empty image");
-    mr_frame_desc fd = *frame;
+// What mr_render_lights and mr_render_lights_surface ask of their arguments and of the scene, in this order; `fd`: the
+// descriptor as the launchers take it (band_world >= 1).  surface_misaligned: one of the buffers that the _surface call takes
+// besides is; refuse_table: the call shades without the lookup.
+static mr_status check_render_lights(const char *who, mr_scene *s, const mr_frame_desc *frame, mr_frame_desc &fd, const float *d_rgb,
+                                     const mr_hit *d_hits, const float *d_sample_rgb, bool surface_misaligned, const uint64_t *d_counts,
+                                     bool refuse_table) {
+    if (!s || !frame || !d_rgb) return fail(MR_ERR_INVALID, "%s: NULL argument", who);
+    if (frame->W == 0 || frame->H == 0) return fail(MR_ERR_INVALID, "%s: empty image", who);
+    fd = *frame;
     if (fd.band_world <= 1) { fd.band_world = 1; fd.band_rank = 0; if (fd.band_rows == 0) fd.band_rows = 1; }
-    mr_status st = check_frame_lights(fd);
+    mr_status st = check_frame_lights(who, fd);
     if (st != MR_OK) return st;
     if ((reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
-        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_sample_rgb) & 3))
-        return fail(MR_ERR_INVALID, "mr_render_lights: the hit buffer must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned");
+        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_sample_rgb) & 3) || surface_misaligned)
+        return fail(MR_ERR_INVALID, "%s: the hit buffer must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned", who);
     if ((st = require_device(s)) != MR_OK) return st;
-    if (s->lights.empty()) return fail(MR_ERR_STATE, "mr_render_lights: the scene has no lights (mr_scene_set_lights)");
-    if (!s->tex.blob.empty())
-        return fail(MR_ERR_STATE, "mr_render_lights: the scene has a texture table (mr_scene_set_textures) and this call shades without "
+    if (s->lights.empty()) return fail(MR_ERR_STATE, "%s: the scene has no lights (mr_scene_set_lights)", who);
+    if (refuse_table && !s->tex.blob.empty())
+        return fail(MR_ERR_STATE, "%s: the scene has a texture table (mr_scene_set_textures) and this call shades without "
                                   "the lookup; use the batched calls mr_trace -> mr_shade_lights, or mr_trace -> mr_hit_surface -> "
-                                  "mr_shade_lights_surface");
+                                  "mr_shade_lights_surface", who);
     if ((fd.flags & MR_TRACE_ANY) && s->dev.refractive)
-        return fail(MR_ERR_STATE, "mr_render_lights: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)");
+        return fail(MR_ERR_STATE, "%s: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)", who);
+    return MR_OK;
+}
+
+mr_status mr_render_lights(mr_scene *s, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
+                           uint64_t *d_counts, void *stream) {
+    mr_frame_desc fd;
+    const mr_status st = check_render_lights("mr_render_lights", s, frame, fd, d_rgb, d_hits, d_sample_rgb, false, d_counts, true);
+    if (st != MR_OK) return st;
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_frame_lights(s->dev, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
                                reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+}
+
+// ... on any scene: with a texture table every hit's diffuse colour and normal are hit_color_normal's (mr_frame_lights_surface.hip).
+// The first call after mr_scene_set_textures uploads the table (texture_params: an allocation and a copy) and must lie outside a
+// stream capture; after it the call is one kernel on `stream`.
+mr_status mr_render_lights_surface(mr_scene *s, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
+                                   float *d_sample_color, float *d_sample_normal, uint64_t *d_counts, void *stream) {
+    mr_frame_desc fd;
+    mr_status st = check_render_lights("mr_render_lights_surface", s, frame, fd, d_rgb, d_hits, d_sample_rgb,
+                                       (reinterpret_cast<uintptr_t>(d_sample_color) & 3) || (reinterpret_cast<uintptr_t>(d_sample_normal) & 3),
+                                       d_counts, false);
+    if (st != MR_OK) return st;
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    TexParams tex;
+    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
+    if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+    return launch_frame_lights_surface(s->dev, tex, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
+                                       d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts),
+                                       static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_gen_eye_rays_lens(mr_scene *s, const mr_camera *cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp,

@@ -24,10 +24,12 @@
 // NOT here, on purpose: mr_frame.hip's eye-relative tables, its uniform-run scalar walk, its pulled tail with the counter
 // ring and its 128-lane build.  Each was tuned on the single-light kernel against that kernel's register envelope; this
 // kernel takes the plain grid-stride loop of the batched kernels (trace_grid workgroups, xcd_block_id) until it has been
-// measured.  mr_frame.hip itself is untouched: the window arithmetic of its launcher is written again below.
+// measured.  mr_frame.hip itself is untouched: the window arithmetic of its launcher is written again in mr_frame_window.h,
+// which the textured form of this frame (mr_frame_lights_surface.hip) reads too.
 #include <hip/hip_runtime.h>
 
 #include "mr_eye.h"
+#include "mr_frame_window.h"
 #include "mr_internal.h"
 #include "mr_launch.h"
 #include "mr_phong.h"
@@ -158,52 +160,21 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(fra
     }
 }
 
-// The window of a frame descriptor: mr_frame.hip's reading of it (MR_FRAME_ENTRY), in its wording.  `fd` has band_world >= 1.
-// Reads nothing but the descriptor.
-mr_status window_of(const mr_frame_desc &fd, EyeFrame &eye) {
-    const uint32_t spp = fd.spp;
-    if (spp == 0 || spp > 64 || (spp & (spp - 1)))
-        return fail(MR_ERR_INVALID, "mr_render_lights: spp must be a power of two <= 64 (got %u); use the batched pipeline", spp);
-    if (fd.band_world == 0 || fd.band_rank >= fd.band_world || fd.band_rows == 0)
-        return fail(MR_ERR_INVALID, "mr_render_lights: bad band description (%u rows, rank %u of %u)", fd.band_rows, fd.band_rank, fd.band_world);
-    uint32_t rows = 0;
-    if (fd.band_world == 1) {
-        if (fd.y1 > fd.H || fd.y0 > fd.y1) return fail(MR_ERR_INVALID, "mr_render_lights: rows [%u,%u) outside the image", fd.y0, fd.y1);
-        rows = fd.y1 - fd.y0;
-    } else {
-        const uint32_t nb = (fd.H + fd.band_rows - 1) / fd.band_rows;
-        for (uint32_t b = fd.band_rank; b < nb; b += fd.band_world) {
-            const uint32_t y0 = b * fd.band_rows, y1 = y0 + fd.band_rows < fd.H ? y0 + fd.band_rows : fd.H;
-            rows += y1 - y0;
-        }
-    }
-    eye = make_eye_frame(fd.camera, fd.W, fd.H, fd.band_world == 1 ? fd.y0 : 0, fd.band_world == 1 ? fd.y1 : rows, spp, fd.jitter, fd.seed,
-                         fd.tiled != 0);
-    eye.rows = rows;
-    eye.n = (unsigned long long)rows * fd.W * spp;
-    if (fd.band_world > 1) {
-        // (a ragged last band only ever is the LAST window row group of its owner: eye_sample_of's row formula holds for it)
-        eye.y0 = 0; eye.band_rows = fd.band_rows; eye.band_rank = fd.band_rank; eye.band_world = fd.band_world;
-    }
-    if (eye.n >= (1ull << 32) * spp) return fail(MR_ERR_INVALID, "mr_render_lights: window too large");
-    return MR_OK;
-}
-
 }  // namespace
 
-mr_status check_frame_lights(const mr_frame_desc &fd) {
+mr_status check_frame_lights(const char *who, const mr_frame_desc &fd) {
     EyeFrame eye;
-    const mr_status st = window_of(fd, eye);
+    const mr_status st = frame_window_of(who, fd, eye);
     if (st != MR_OK) return st;
     if (fd.flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT | MR_TRACE_ANY))
-        return fail(MR_ERR_INVALID, "mr_render_lights: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_TRACE_ANY only");
+        return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_TRACE_ANY only", who);
     return MR_OK;
 }
 
 mr_status launch_frame_lights(const DeviceScene &ds, const ShadeLight *lights, uint32_t n_lights, const mr_frame_desc &fd, float *d_rgb,
                               mr_hit *d_hits, float *d_sample_rgb, unsigned long long *d_counts, hipStream_t stream) {
     FrameLightsArgs a;
-    const mr_status st = window_of(fd, a.eye);
+    const mr_status st = frame_window_of("mr_render_lights", fd, a.eye);
     if (st != MR_OK) return st;
     if (a.eye.n == 0) return MR_OK;
     a.tp = scene_trace_params(ds);

@@ -289,10 +289,18 @@ mr_status launch_shade_lights(const DeviceScene &ds, const ShadeLight *lights, u
                               hipStream_t stream);
 // the fused frame over the light list (mr_frame_lights.hip, mr_render_lights).  fd: band_world >= 1 (as mr_render_direct hands it
 // to launch_frame).  check_frame_lights: what the descriptor alone can get wrong (spp, bands, rows, size, flags), without a
-// device call or a look at any scene; launch_frame_lights: one kernel on `stream`, none for an empty window
-mr_status check_frame_lights(const mr_frame_desc &fd);
+// device call or a look at any scene, `who` the entry point its messages name; launch_frame_lights: one kernel on `stream`,
+// none for an empty window
+mr_status check_frame_lights(const char *who, const mr_frame_desc &fd);
 mr_status launch_frame_lights(const DeviceScene &ds, const ShadeLight *lights, uint32_t n_lights, const mr_frame_desc &fd, float *d_rgb,
                               mr_hit *d_hits, float *d_sample_rgb, unsigned long long *d_counts, hipStream_t stream);
+// ... on any scene (mr_frame_lights_surface.hip, mr_render_lights_surface): every hit's diffuse colour and normal from
+// hit_color_normal between the primary trace and the light loop.  tex: as mr_hit_surface hands it to launch_hit_surface
+// (recs / mat_tex nullptr without a texture table); d_sample_color / d_sample_normal optional; d_counts: three words
+struct TexParams;
+mr_status launch_frame_lights_surface(const DeviceScene &ds, const TexParams &tex, const ShadeLight *lights, uint32_t n_lights,
+                                      const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color,
+                                      float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream);
 
 // the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
 // square light, side * side shadow rays per hit and light

@@ -67,7 +67,8 @@ EXPORTED_SYMBOLS = [
 ]
 # every symbol include/miro_hip_surface.h declares (entry points added after miro_hip.h's own list was held at 69 names)
 SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map_build_device", "mr_trace_photons_resident",
-                   "mr_shade_square_lights_surface", "mr_gen_path_rays_surface", "mr_bvh_build_timing", "mr_render_lights"]
+                   "mr_shade_square_lights_surface", "mr_gen_path_rays_surface", "mr_bvh_build_timing", "mr_render_lights",
+                   "mr_render_lights_surface"]
 
 
 class MiroError(RuntimeError):
@@ -285,6 +286,7 @@ def load_library(path=None):
     L.mr_deinterleave_bands.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.mr_render_direct.argtypes = [vp, C.POINTER(FrameDesc), vp, vp, vp, vp, vp]
     L.mr_render_lights.argtypes = [vp, C.POINTER(FrameDesc), vp, vp, vp, vp, vp]
+    L.mr_render_lights_surface.argtypes = [vp, C.POINTER(FrameDesc), vp, vp, vp, vp, vp, vp, vp]
     L.mr_tonemap.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.mr_scene_set_materials.argtypes = [vp, C.POINTER(Material), C.c_uint32, u32p]
     L.mr_shade_accumulate.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(Light), C.c_uint32, vp, vp]
@@ -704,6 +706,22 @@ class Scene:
         fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
         _check(self.L.mr_render_lights(self.h, C.byref(fd), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb), _ptr(d_counts),
                                        _stream_ptr(stream)))
+
+    def render_lights_surface(self, cam, W, H, d_rgb, y0=0, y1=None, bands=None, spp=1, jitter=False, seed=168, tiled=False, flags=0,
+                              d_hits=None, d_sample_rgb=None, d_sample_color=None, d_sample_normal=None, d_counts=None, stream=None):
+        """mr_render_lights_surface: render_lights on any scene -- with a texture table (set_textures) every hit's diffuse colour
+        and normal are hit_surface's (every texture kind, the bump-mapped normal of a STONE material), looked up between the
+        primary trace and the light loop of the same launch.  d_sample_color / d_sample_normal [n, 3]: what hit_surface writes
+        for each sample (a miss leaves its row untouched).  d_counts: THREE words, [0] += samples, [1] += shadow rays,
+        [2] += hits whose lookup the reference leaves undefined.  A miss contributes 0: set_environment is not applied.  The
+        first call after set_textures uploads the table and must lie outside a graph capture."""
+        fd = FrameDesc()
+        fd.camera = cam
+        fd.W, fd.H, fd.y0, fd.y1 = W, H, y0, H if y1 is None else y1
+        fd.band_rows, fd.band_rank, fd.band_world = bands if bands is not None else (1, 0, 1)
+        fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
+        _check(self.L.mr_render_lights_surface(self.h, C.byref(fd), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb),
+                                               _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_counts), _stream_ptr(stream)))
 
     def final_gather(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb, max_dist=1e10, nphotons=500,
                      spp=1, stream=None):

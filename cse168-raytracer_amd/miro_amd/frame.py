@@ -126,7 +126,10 @@ class FusedFrame:
     """One rank's share of a direct-light frame rendered by mr_render_direct: a single launch per step, no ray buffers.
     Resident: the float framebuffer shard (12 B per pixel) and, when `keep_hits`, the two hit-record buffers
     (16 + 16 B per sample) that parity tests compare with the batched pipeline's.  With `lights` the launch is
-    mr_render_lights: the frame over a light list, and `keep_hits` keeps the primary records only."""
+    mr_render_lights: the frame over a light list, and `keep_hits` keeps the primary records only.  On a scene with a texture
+    table (Scene.n_textures at step()) that launch is mr_render_lights_surface: the same frame with every hit's looked-up colour
+    and bump-mapped normal.  A sample that misses contributes 0 in both: the scene's environment (set_environment) is not
+    applied -- mr_shade_environment needs the ray and hit buffers and stays with the batched route (FrameRenderer)."""
 
     def __init__(self, scene, desc, W, H, spp=1, band=None, rank=0, world=1, jitter=None, seed=168, flags=0, rgb=None,
                  tiled=None, keep_hits=False, any_shadow=False, no_shadows=False, lights=None):
@@ -158,7 +161,9 @@ class FusedFrame:
             raise ValueError("rgb must be a contiguous float32 buffer of at least %d x 3 values" % self.n_pixels)
         self.d_hits = torch.empty((max(self.n, 1), 4), **f32) if keep_hits else None
         self.d_shadow_hits = torch.empty((max(self.n, 1), 4), **f32) if keep_hits and self.lights is None else None
-        self.d_counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+        # primary rays, shadow rays and, with a light list, undefined lookups (mr_render_direct's counters stay two words: the
+        # tests of its counter ring compare the whole tensor)
+        self.d_counts = torch.zeros(2 if self.lights is None else 3, dtype=torch.int64, device=self.device)
         self.cam = binding.make_camera(desc["eye"], desc["lookat"], desc["up"], desc["fov"])
 
     def bytes_resident(self):
@@ -169,9 +174,9 @@ class FusedFrame:
         if self.n == 0:
             return
         if self.lights is not None:
-            self.scene.render_lights(self.cam, self.W, self.H, self.d_rgb, bands=self.bands, spp=self.spp, jitter=self.jitter,
-                                     seed=self.seed, tiled=self.tiled, flags=self.flags, d_hits=self.d_hits, d_counts=self.d_counts,
-                                     stream=stream)
+            render = self.scene.render_lights_surface if self.scene.n_textures else self.scene.render_lights
+            render(self.cam, self.W, self.H, self.d_rgb, bands=self.bands, spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled,
+                   flags=self.flags, d_hits=self.d_hits, d_counts=self.d_counts, stream=stream)
             return
         self.scene.render_direct(self.cam, self.W, self.H, self.d_rgb, self.desc["light"], self.desc["wattage"],
                                  bands=self.bands, spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled,
@@ -182,6 +187,11 @@ class FusedFrame:
         """(primary, shadow) rays per step, from the device counters accumulated over `steps` steps -- synchronises."""
         c = self.d_counts.cpu().numpy()
         return int(c[0]) // max(steps, 1), int(c[1]) // max(steps, 1)
+
+    def undefined_lookups(self, steps=1):
+        """Hits whose texture lookup the reference leaves undefined, per step (mr_render_lights_surface's d_counts[2]; 0 for every
+        other launch of this class) -- synchronises."""
+        return int(self.d_counts.cpu().numpy()[2]) // max(steps, 1) if self.lights is not None else 0
 
 
 class Queue(collections.namedtuple("Queue", "rays weights pixels ids octs n")):

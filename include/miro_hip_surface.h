@@ -103,6 +103,32 @@ mr_status mr_bvh_build_timing(uint32_t *builder_used, double *prims_ms, double *
 mr_status mr_render_lights(mr_scene *scene, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
                            uint64_t *d_counts, void *stream);
 
+/* ---- ... on ANY scene, textured ones included -------------------------------------------------------------------------
+ * mr_render_lights with the surface pass's step between the primary trace and the light loop: with a texture table
+ * (mr_scene_set_textures) every hit's diffuseColor (Phong.cpp:51-56, all seven kinds in any mixture) and the normal Scene::trace
+ * hands on (bump-mapped on a STONE material, normalised; Scene.cpp:234-263) are what mr_hit_surface computes for that ray and
+ * hit; the colour goes where the material's diffuse went, the normal everywhere N goes; the occluder's light scale still reads
+ * the occluder's own geometric normal.  The same hit records, per-sample colour, normal and L and pixels, bit for bit, as the batched
+ *   mr_gen_eye_rays[_tiled] -> mr_trace -> mr_hit_surface -> mr_shade_lights_surface(d_ray_rgb) [-> pairwise mean over each
+ *   pixel's samples]
+ * on the same scene, camera, seed and sample order, without its ray, hit, colour, normal and per-ray L buffers (84 bytes per
+ * sample).  Without a texture table the call renders what mr_render_lights renders, bit for bit.
+ * Window, lights, materials, flags, d_rgb, d_hits, d_sample_rgb: mr_render_lights' in every respect.  Besides (NULL to skip):
+ *   d_sample_color   3 floats per sample in d_hits' order, 4-byte aligned: what mr_hit_surface writes to d_color for that ray
+ *   d_sample_normal  likewise, its d_normal.  A sample that missed leaves its row of both untouched, as there.
+ *   d_counts         THREE words: [0] += samples, [1] += shadow rays, [2] += hits whose lookup the reference leaves undefined
+ *                    (mr_hit_surface's d_counts[0] on the same batch); 8-byte aligned, not zeroed by the call
+ * A sample that misses contributes 0, as in mr_render_lights: the environment of mr_scene_set_environment is NOT applied
+ *   (mr_shade_environment needs the ray and hit buffers and stays with the batched route).
+ * Launches: with a texture table that is already on the device the call enqueues ONE kernel on `stream` and can be captured
+ *   into a graph.  The first call after mr_scene_set_textures uploads the table on `stream` -- an allocation and a copy -- and
+ *   must lie outside a capture (every other call that reads the table uploads it too).
+ * Errors: mr_render_lights', in its order, without the refusal of a texture table; d_sample_color / d_sample_normal not 4-byte
+ *   aligned is MR_ERR_INVALID with the other alignments.  MR_TRACE_ANY with a refractive material and a scene without lights
+ *   stay MR_ERR_STATE. */
+mr_status mr_render_lights_surface(mr_scene *scene, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
+                                   float *d_sample_color, float *d_sample_normal, uint64_t *d_counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
