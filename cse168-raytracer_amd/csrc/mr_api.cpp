@@ -1193,6 +1193,29 @@ mr_status mr_shade_lights(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hit
                                flags, d_rgb, d_ray_rgb, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
+// the environment on the device, its texel records uploaded on `stream` by the first call after a change (e.rec stays until the
+// next change); `p`: as the kernels take it.  For mr_shade_environment and mr_render_lights_environment, as texture_params is
+// for the calls that read the texture table
+static mr_status environment_params(mr_scene *s, hipStream_t stream, EnvParams &p) {
+    const HostEnvironment &e = s->env;
+    if (s->env_dirty) {
+        (void)hipFree(s->d_env);
+        s->d_env = nullptr;
+        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&s->d_env), e.rec.size() * sizeof(float)));
+        MR_HIP_CHECK(hipMemcpyAsync(s->d_env, e.rec.data(), e.rec.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        s->env_dirty = false;
+    }
+    p = EnvParams{};
+    if (e.W) {
+        p.full = s->d_env; p.low = s->d_env + (size_t)e.W * e.H;
+        p.W = e.W; p.H = e.H; p.lw = e.lw; p.lh = e.lh;
+        p.max_intensity = e.max_intensity;
+    }
+    p.rot[0] = e.rot[0]; p.rot[1] = e.rot[1];
+    for (int c = 0; c < 3; c++) p.bg[c] = e.bg[c];
+    return MR_OK;
+}
+
 // mr_render_direct's window over mr_shade_lights' light list, in one launch (mr_frame_lights.hip).  What the arguments alone can
 // get wrong is answered first, before any device call and before the scene's state is read; then the scene's state.
 // What mr_render_lights and mr_render_lights_surface ask of their arguments and of the scene, in this order; `fd`: the
@@ -1248,6 +1271,27 @@ mr_status mr_render_lights_surface(mr_scene *s, const mr_frame_desc *frame, floa
     return launch_frame_lights_surface(s->dev, tex, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
                                        d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts),
                                        static_cast<hipStream_t>(stream));
+}
+
+// ... and a live sample whose primary ray misses is worth the scene's environment (mr_frame_lights_env.hip).  The first call after
+// mr_scene_set_environment with an image uploads it (environment_params: an allocation and a copy), as the first call after
+// mr_scene_set_textures uploads the table; both must lie outside a stream capture.  After them the call is one kernel on `stream`.
+mr_status mr_render_lights_environment(mr_scene *s, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
+                                       float *d_sample_color, float *d_sample_normal, uint64_t *d_counts, void *stream) {
+    mr_frame_desc fd;
+    mr_status st = check_render_lights("mr_render_lights_environment", s, frame, fd, d_rgb, d_hits, d_sample_rgb,
+                                       (reinterpret_cast<uintptr_t>(d_sample_color) & 3) || (reinterpret_cast<uintptr_t>(d_sample_normal) & 3),
+                                       d_counts, false);
+    if (st != MR_OK) return st;
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    TexParams tex;
+    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
+    if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+    EnvParams env;
+    if ((st = environment_params(s, static_cast<hipStream_t>(stream), env)) != MR_OK) return st;
+    return launch_frame_lights_env(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
+                                   d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts),
+                                   static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_gen_eye_rays_lens(mr_scene *s, const mr_camera *cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp,
@@ -1409,22 +1453,8 @@ mr_status mr_shade_environment(mr_scene *s, const mr_ray *d_rays, const mr_hit *
         (reinterpret_cast<uintptr_t>(d_pixels) & 3))
         return fail(MR_ERR_INVALID, "ray / hit buffers must be 16-byte aligned, counters 8-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
-    const HostEnvironment &e = s->env;
-    if (s->env_dirty) {                        // the texel records, on this call's stream (e.rec stays until the next change)
-        (void)hipFree(s->d_env);
-        s->d_env = nullptr;
-        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&s->d_env), e.rec.size() * sizeof(float)));
-        MR_HIP_CHECK(hipMemcpyAsync(s->d_env, e.rec.data(), e.rec.size() * sizeof(float), hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
-        s->env_dirty = false;
-    }
-    EnvParams p = {};
-    if (e.W) {
-        p.full = s->d_env; p.low = s->d_env + (size_t)e.W * e.H;
-        p.W = e.W; p.H = e.H; p.lw = e.lw; p.lh = e.lh;
-        p.max_intensity = e.max_intensity;
-    }
-    p.rot[0] = e.rot[0]; p.rot[1] = e.rot[1];
-    for (int c = 0; c < 3; c++) p.bg[c] = e.bg[c];
+    EnvParams p;
+    if ((st = environment_params(s, static_cast<hipStream_t>(stream), p)) != MR_OK) return st;
     return launch_shade_environment(p, d_rays, d_hits, d_weights, d_pixels, d_lowres, n, spp, flags, d_rgb, d_ray_rgb,
                                     reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }

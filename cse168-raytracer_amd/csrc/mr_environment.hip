@@ -14,7 +14,8 @@
 // a loop over the lanes).  The grid of the image variants is held to 8 workgroups per CU so that this copy stays small
 // beside the batch.
 //
-// The arithmetic of the lookup is the reference's (the bilinear part is mr_texture.h, shared with the material textures),
+// The arithmetic of the lookup is the reference's (mr_environment_body.h, shared with the fused frame of
+// mr_frame_lights_env.hip; the bilinear part is mr_texture.h, shared with the material textures),
 // operation for operation in fp32 (this unit is compiled with
 // -ffp-contract=off like the rest), on mm_atan2f / mm_asinf of miro_math.h: texture coordinates are the same bits as a host
 // restatement's.  powf is the device library's (the tolerance of the shaded value, as in mr_lights.hip).
@@ -24,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "miro_math.h"
+#include "mr_environment_body.h"
 #include "mr_internal.h"
 #include "mr_launch.h"
 #include "mr_recursion.h"
@@ -32,8 +34,6 @@
 
 namespace mr {
 namespace {
-
-using rec::kPI;
 
 struct EnvArgs {
     EnvParams env;
@@ -50,19 +50,6 @@ struct EnvArgs {
     float *ray_rgb;               // may be NULL: the un-weighted value of every ray
     unsigned long long *counts;   // optional: [0] += misses, [1] += undefined lookups
 };
-
-// Scene.cpp:664-676: the texture coordinates of a direction
-__device__ __forceinline__ void env_coords(const float rot[2], float dx, float dy, float dz, float &u, float &v) {
-    float phi = mm_atan2f(dx, dz) + rot[0] + kPI;                       // :665
-    float theta = mm_asinf(dy) + rot[1];                                // :666
-    if (theta > kPI / 2.0f) {                                           // :667-671
-        phi += kPI;
-        theta -= 2.0f * (theta - kPI / 2.0f);
-    }
-    if (phi > 2.0f * kPI) phi -= (2.0f * kPI);                          // :672
-    u = phi / (2.0f * kPI);                                             // :675
-    v = (float)((double)(theta / kPI) + 0.5);                           // :676 (0.5 is a double)
-}
 
 template <bool IMAGE, bool WEIGHTS, bool PIXELS>
 __global__ __launch_bounds__(kBlock) void shade_environment_kernel(EnvArgs a) {
@@ -97,11 +84,9 @@ __global__ __launch_bounds__(kBlock) void shade_environment_kernel(EnvArgs a) {
                 const float4 rb = a.rays[2 * k + 1];
                 const bool low = a.all_lowres || (a.lowres && a.lowres[k]);                // ray.isDiffuse (:678-681)
                 const int w = low ? (int)a.env.lw : (int)a.env.W, h = low ? (int)a.env.lh : (int)a.env.H;
-                float u, v, xe = 0.f, ye = 0.f;
+                float xe = 0.f, ye = 0.f;
                 int x1 = 0, x2 = 0, y1 = 0, y2 = 0;
-                env_coords(a.env.rot, rb.x, rb.y, rb.z, u, v);
-                const bool okx = bilinear_axis(w, u, x1, x2, xe), oky = bilinear_axis(h, v, y1, y2, ye);
-                if (okx && oky) {
+                if (env_texels(a.env.rot, w, h, rb.x, rb.y, rb.z, x1, x2, y1, y2, xe, ye)) {
                     float4 p11, p21, p12, p22;
                     if (low) {
                         p11 = s_low[y1 * w + x1]; p21 = s_low[y1 * w + x2]; p12 = s_low[y2 * w + x1]; p22 = s_low[y2 * w + x2];
@@ -109,9 +94,7 @@ __global__ __launch_bounds__(kBlock) void shade_environment_kernel(EnvArgs a) {
                         const float4 *r1 = a.env.full + (size_t)y1 * w, *r2 = a.env.full + (size_t)y2 * w;
                         p11 = r1[x1]; p21 = r1[x2]; p12 = r2[x1]; p22 = r2[x2];
                     }
-                    val[0] = bilinear_blend(p11.x, p21.x, p12.x, p22.x, xe, ye, a.env.max_intensity);
-                    val[1] = bilinear_blend(p11.y, p21.y, p12.y, p22.y, xe, ye, a.env.max_intensity);
-                    val[2] = bilinear_blend(p11.z, p21.z, p12.z, p22.z, xe, ye, a.env.max_intensity);
+                    env_blend(p11, p21, p12, p22, xe, ye, a.env.max_intensity, val);
                 } else {
                     my_undefined++;
                 }

@@ -23,8 +23,9 @@
 // (photon_walk_surface_kernel does the same).  hit_color_normal's test of mat_tex is taken out of the loop as
 // hit_surface_kernel takes it out: without a texture table the plain arm alone runs, and the frame is mr_render_lights'.
 //
-// A miss contributes 0 (m_bgColor = 0), as in mr_render_lights: the environment (mr_shade_environment) needs the ray and hit
-// buffers and stays with the batched route.
+// A miss contributes 0 (m_bgColor = 0), as in mr_render_lights.  The frame that gives a miss the scene's environment is
+// mr_frame_lights_env.hip (mr_render_lights_environment): the per-sample body of both is one template,
+// frame_lights_surface_body<VAR, ANY, ENV> of mr_frame_lights_surface_body.h, instantiated here with ENV = false.
 //
 // Waves per SIMD, spilled VGPRs and scratch bytes per lane of the 12 kernels (hipcc, gfx950, the Makefile's flags); the
 // envelope is the worst kernel of tests/golden/kernel_budget.json, 30 spilled VGPRs / 108 bytes / 4 waves, and every variant
@@ -46,36 +47,10 @@
 // chain: DESIGN section 5c, profiles/frame_lights_surface_ab.log.
 #include <hip/hip_runtime.h>
 
-#include "mr_eye.h"
-#include "mr_frame_window.h"
-#include "mr_hit_surface_body.h"
-#include "mr_internal.h"
-#include "mr_launch.h"
-#include "mr_noise.h"
-#include "mr_phong.h"
-#include "mr_surface.h"
-#include "mr_tile.h"
-#include "mr_traverse.h"
+#include "mr_frame_lights_surface_body.h"
 
 namespace mr {
 namespace {
-
-using namespace rec;
-
-struct FrameLightsSurfaceArgs {
-    EyeFrame eye;
-    TraceParams tp;              // scene arrays, root box; rays / hits / n unused
-    MeshMat m;
-    TexParams t;                 // recs / mat_tex nullptr: the scene has no texture table
-    mr_hit *hits;                // optional: primary hit record of sample k
-    float *sample_rgb;           // optional: the un-weighted L of sample k (0 for a miss)
-    float *sample_color;         // optional: diffuseColor of sample k's hit; a miss keeps what the buffer held
-    float *sample_normal;        // optional: the normal Scene::trace hands on for sample k's hit; likewise
-    float *rgb;                  // [rows * W][3], window rows in band order, image order inside a row
-    unsigned long long *counts;  // optional: [0] += primary rays, [1] += shadow rays, [2] += hits whose lookup is undefined
-    uint32_t n_lights;
-    ShadeLight lights[MR_MAX_LIGHTS];
-};
 
 // MIRO_FRAME_LIGHTS_SURFACE_WAVES (A/B builds) sets one value for every variant.
 #ifdef MIRO_FRAME_LIGHTS_SURFACE_WAVES
@@ -84,120 +59,14 @@ constexpr int frame_lights_surface_waves(int) { return MIRO_FRAME_LIGHTS_SURFACE
 constexpr int frame_lights_surface_waves(int var) { return var == kTraceProduct || var == kTraceVote || var == kTraceVoteProduct ? 5 : 4; }
 #endif
 
-// VAR, ANY: as in frame_lights_kernel.  The arguments are taken BY VALUE (mr_lights_body.h says why).
+// VAR, ANY: as in frame_lights_kernel.  The arguments are taken BY VALUE (mr_lights_body.h says why).  The body is
+// frame_lights_surface_body<VAR, ANY, false> (mr_frame_lights_surface_body.h): no environment.
 template <int VAR, bool ANY>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(frame_lights_surface_waves(VAR), 8))) void frame_lights_surface_kernel(
     const FrameLightsSurfaceArgs a) {
     extern __shared__ int s_stack[];                  // [stack_depth][kTraceBlock]
     __shared__ uint32_t s_tab[128];
-    const NoiseTables nt = stage_noise_tables(s_tab);
-    const int tid = threadIdx.x;
-    const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
-    const unsigned long long n = a.eye.n;
-    const unsigned long long n_round = whole_workgroups(n);
-    const uint32_t spp = a.eye.spp;
-    const bool table = a.t.mat_tex != nullptr;        // wave-uniform, out of the loop (hit_surface_kernel)
-    Stats st = {0ull, 0ull};
-    unsigned my_shadow_rays = 0, my_undefined = 0;
-
-    // whole workgroups run every iteration (n_round): the traversals and the butterfly are called by whole waves
-    for (unsigned long long idx = (unsigned long long)xcd_block_id() * kTraceBlock + tid; idx < n_round; idx += stride) {
-        const bool live = idx < n;
-        uint32_t x = 0, row = 0, y = 0, sm = 0;
-        float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = make_float4(1.f, 1.f, 1.f, -1.f);
-        if (live) {
-            eye_sample_of(a.eye, idx, x, row, y, sm);
-            eye_ray_of(a.eye, x, y, sm, ra, rb);
-        }
-        // ---- primary ray: a closest hit; a lane past the end of the window gets the miss record
-        const mr_hit h = trace_hit<true, false, false, VAR>(a.tp, ra, rb, rb.w, live, s_stack, tid, st);
-        if (a.hits && live) reinterpret_cast<float4 *>(a.hits)[idx] = *reinterpret_cast<const float4 *>(&h);
-
-        // ---- HitInfo::P, the normal as Scene::trace leaves it and diffuseColor: the surface pass's step for this hit
-        const bool hit = live && h.prim != MR_MISS;
-        float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 1.f, 0.f}, col[3] = {0.f, 0.f, 0.f};
-        const float *mt = a.m.mats;
-        if (hit) {
-            // the ray's origin is the eye (a hit lane is a live one): read from the arguments, uniform, where it is used
-            surface_od<true>(a.m.s, a.eye.eye[0], a.eye.eye[1], a.eye.eye[2], rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
-            bool ok = true;
-            if (table) {
-                hit_color_normal(a.m, a.t, nt, h.prim, P, N, col, ok);
-            } else {
-                TexParams t0 = a.t;
-                t0.mat_tex = nullptr;
-                hit_color_normal(a.m, t0, nt, h.prim, P, N, col, ok);
-            }
-            if (!ok) my_undefined++;
-            if (a.sample_color) { a.sample_color[3 * idx] = col[0]; a.sample_color[3 * idx + 1] = col[1]; a.sample_color[3 * idx + 2] = col[2]; }
-            if (a.sample_normal) { a.sample_normal[3 * idx] = N[0]; a.sample_normal[3 * idx + 1] = N[1]; a.sample_normal[3 * idx + 2] = N[2]; }
-            mt = material_of(a.m, h.prim);
-            my_shadow_rays += a.n_lights;
-        }
-        // the eye ray's direction, computed again: cheaper than three registers live across the lookup
-        float d[3] = {0.f, 0.f, 0.f};
-        if (hit) {
-            eye_sample_of(a.eye, idx, x, row, y, sm);
-            eye_ray_of(a.eye, x, y, sm, ra, rb);
-            d[0] = rb.x; d[1] = rb.y; d[2] = rb.z;
-        }
-
-        // ---- Phong::shade over the light list (shade_lights_body with kColorSurface); a miss contributes nothing (m_bgColor = 0)
-        float L[3] = {0.f, 0.f, 0.f};
-        for (uint32_t li = 0; li < a.n_lights; li++) {                 // Phong.cpp:63, wave-uniform
-            const ShadeLight &lt = a.lights[li];
-            float4 sh;
-            {
-                float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(1.f, 1.f, 1.f, -1.f);
-                if (hit) shadow_ray_for(lt, P, sa, sb);
-                const mr_hit hs = trace_hit<true, ANY, false, VAR>(a.tp, sa, sb, sb.w, hit, s_stack, tid, st);
-                sh = *reinterpret_cast<const float4 *>(&hs);
-            }
-            if (hit) {
-                float4 sa, sb;
-                shadow_ray_for(lt, P, sa, sb);                         // rebuilt rather than kept across the traversal
-                const float scale = light_scale_of(a.m, sa, sb, sh);
-                float diffuse[3] = {0.f, 0.f, 0.f}, highlight = 0.0f, out[3] = {0.f, 0.f, 0.f};
-                bool lit = scale != 0.0f;                              // Phong.cpp:100-111: the light is skipped
-                if (lit) {
-                    if (lt.kind == MR_LIGHT_DISC) {
-                        const float l[3] = {sb.x, sb.y, sb.z};
-                        lit = disc_terms(lt, mt, col, P, N, l, d[0], d[1], d[2], diffuse, highlight);
-                    } else {
-                        phong_terms(lt.position, lt.color, lt.wattage, mt, col, P, N, d[0], d[1], d[2], diffuse, highlight);
-                    }
-                }
-                if (lit) phong_combine(diffuse, highlight, scale, out);
-                L[0] += out[0]; L[1] += out[1]; L[2] += out[2];
-            }
-        }
-        if (a.sample_rgb && live) { a.sample_rgb[3 * idx] = L[0]; a.sample_rgb[3 * idx + 1] = L[1]; a.sample_rgb[3 * idx + 2] = L[2]; }
-
-        // ---- the pixel's mean (Scene.cpp:126-139), as frame_kernel forms it: spp is a power of two <= 64 (checked by the
-        // host), a pixel's samples are `spp` consecutive, aligned lanes; the summation tree depends on the sample index only
-        for (uint32_t off = 1; off < spp; off <<= 1) {
-            L[0] += __shfl_xor(L[0], (int)off, 64);
-            L[1] += __shfl_xor(L[1], (int)off, 64);
-            L[2] += __shfl_xor(L[2], (int)off, 64);
-        }
-        if (live) eye_sample_of(a.eye, idx, x, row, y, sm);      // recomputed: cheaper than live registers across the traversals
-        if (live && sm == 0) {
-            if (spp > 1) {
-                const float inv_spp = 1.0f / (float)spp;
-                L[0] *= inv_spp; L[1] *= inv_spp; L[2] *= inv_spp;
-            }
-            float *o = a.rgb + 3 * ((size_t)row * a.eye.W + x);
-            o[0] = L[0]; o[1] = L[1]; o[2] = L[2];
-        }
-    }
-
-    // rays traced and undefined lookups.  Per-lane counts: one atomic per workgroup each; primary rays: the launch's sample
-    // count, added once.
-    if (a.counts) {
-        workgroup_add<kTraceBlock>(my_shadow_rays, &a.counts[1]);
-        workgroup_add<kTraceBlock>(my_undefined, &a.counts[2]);
-        if (blockIdx.x == 0 && tid == 0) atomicAdd(&a.counts[0], n);
-    }
+    frame_lights_surface_body<VAR, ANY, false>(a, EnvParams{}, s_stack, s_tab);
 }
 
 }  // namespace
@@ -206,17 +75,10 @@ mr_status launch_frame_lights_surface(const DeviceScene &ds, const TexParams &te
                                       const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color,
                                       float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream) {
     FrameLightsSurfaceArgs a;
-    const mr_status st = frame_window_of("mr_render_lights_surface", fd, a.eye);
+    const mr_status st = fill_frame_lights_surface_args(a, "mr_render_lights_surface", ds, tex, lights, n_lights, fd, d_rgb, d_hits, d_sample_rgb,
+                                                        d_sample_color, d_sample_normal, d_counts);
     if (st != MR_OK) return st;
     if (a.eye.n == 0) return MR_OK;
-    a.tp = scene_trace_params(ds);
-    a.tp.n = a.eye.n;
-    a.m = mesh_of(ds);
-    a.t = tex;
-    a.hits = d_hits; a.sample_rgb = d_sample_rgb; a.sample_color = d_sample_color; a.sample_normal = d_sample_normal;
-    a.rgb = d_rgb; a.counts = d_counts;
-    a.n_lights = n_lights;
-    for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = lights[i < n_lights ? i : 0];
 
     // the traversal variants of launch_frame_lights: the same hit records from each of them
     const bool any = fd.flags & MR_TRACE_ANY;

@@ -1,0 +1,201 @@
+// mr_frame_lights_surface_body.h -- the body of frame_lights_surface_kernel (mr_frame_lights_surface.hip, where the kernel and
+// its register figures are described) as a __device__ template, so that the frame that gives a ray that misses the scene's
+// environment (mr_frame_lights_env.hip, mr_render_lights_environment) is the same code with one more step.  ENV says what a
+// live sample whose primary ray misses is worth:
+//   false  0 (m_bgColor = 0): mr_render_lights_surface
+//   true   Scene::getEnvironmentMap(ray) (Scene.cpp:338-342, 657-688): bg_color, or the lookup of the full-resolution image at
+//          the eye ray's direction (env_lookup_full, mr_environment_body.h; an eye ray is never isDiffuse, so the low-res copy
+//          is not read).  The value is the sample's L: it goes to d_sample_rgb and into the pixel's butterfly as a hit's L does.
+// The lookup lies between the primary traversal and the shadow traversals, on the lanes that missed, and writes into L, which
+// is live across the light loop anyway; the eye ray's direction is computed again for it, as the hit arm computes it again.
+// Colour or image is a wave-uniform branch on env.full.  Two counters more: live samples that missed, undefined lookups.
+// With ENV false nothing of `env` is read and the code is the kernel's as it stood (the figures of
+// tests/golden/kernel_budget_frame_lights_surface.json hold).  The arguments are taken BY VALUE (mr_lights_body.h says why).
+// Included by the .hip units that instantiate it (everything here is local to its unit).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "mr_environment_body.h"
+#include "mr_eye.h"
+#include "mr_frame_window.h"
+#include "mr_hit_surface_body.h"
+#include "mr_internal.h"
+#include "mr_launch.h"
+#include "mr_noise.h"
+#include "mr_phong.h"
+#include "mr_surface.h"
+#include "mr_tile.h"
+#include "mr_traverse.h"
+
+namespace mr {
+namespace {
+
+using namespace rec;
+
+struct FrameLightsSurfaceArgs {
+    EyeFrame eye;
+    TraceParams tp;              // scene arrays, root box; rays / hits / n unused
+    MeshMat m;
+    TexParams t;                 // recs / mat_tex nullptr: the scene has no texture table
+    mr_hit *hits;                // optional: primary hit record of sample k
+    float *sample_rgb;           // optional: the un-weighted L of sample k (a miss: 0, or the environment's value with ENV)
+    float *sample_color;         // optional: diffuseColor of sample k's hit; a miss keeps what the buffer held
+    float *sample_normal;        // optional: the normal Scene::trace hands on for sample k's hit; likewise
+    float *rgb;                  // [rows * W][3], window rows in band order, image order inside a row
+    unsigned long long *counts;  // optional: [0] += primary rays, [1] += shadow rays, [2] += hits whose lookup is undefined;
+                                 // with ENV besides [3] += live samples that missed, [4] += undefined environment lookups
+    uint32_t n_lights;
+    ShadeLight lights[MR_MAX_LIGHTS];
+};
+
+// what launch_frame_lights_surface and launch_frame_lights_env put into the block; `who`: the entry point the window's messages name
+inline mr_status fill_frame_lights_surface_args(FrameLightsSurfaceArgs &a, const char *who, const DeviceScene &ds, const TexParams &tex,
+                                                const ShadeLight *lights, uint32_t n_lights, const mr_frame_desc &fd, float *d_rgb,
+                                                mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color, float *d_sample_normal,
+                                                unsigned long long *d_counts) {
+    const mr_status st = frame_window_of(who, fd, a.eye);
+    if (st != MR_OK) return st;
+    a.tp = scene_trace_params(ds);
+    a.tp.n = a.eye.n;
+    a.m = mesh_of(ds);
+    a.t = tex;
+    a.hits = d_hits; a.sample_rgb = d_sample_rgb; a.sample_color = d_sample_color; a.sample_normal = d_sample_normal;
+    a.rgb = d_rgb; a.counts = d_counts;
+    a.n_lights = n_lights;
+    for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = lights[i < n_lights ? i : 0];
+    return MR_OK;
+}
+
+// VAR, ANY: as in frame_lights_kernel.  s_stack: the workgroup's dynamic LDS, [stack_depth][kTraceBlock]; s_tab: 128 words of
+// static LDS for the two noise tables.
+template <int VAR, bool ANY, bool ENV>
+__device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfaceArgs a, const EnvParams env, int *s_stack, uint32_t (&s_tab)[128]) {
+    const NoiseTables nt = stage_noise_tables(s_tab);
+    const int tid = threadIdx.x;
+    const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
+    const unsigned long long n = a.eye.n;
+    const unsigned long long n_round = whole_workgroups(n);
+    const uint32_t spp = a.eye.spp;
+    const bool table = a.t.mat_tex != nullptr;        // wave-uniform, out of the loop (hit_surface_kernel)
+    Stats st = {0ull, 0ull};
+    unsigned my_shadow_rays = 0, my_undefined = 0, my_misses = 0, my_env_undefined = 0;
+
+    // whole workgroups run every iteration (n_round): the traversals and the butterfly are called by whole waves
+    for (unsigned long long idx = (unsigned long long)xcd_block_id() * kTraceBlock + tid; idx < n_round; idx += stride) {
+        const bool live = idx < n;
+        uint32_t x = 0, row = 0, y = 0, sm = 0;
+        float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = make_float4(1.f, 1.f, 1.f, -1.f);
+        if (live) {
+            eye_sample_of(a.eye, idx, x, row, y, sm);
+            eye_ray_of(a.eye, x, y, sm, ra, rb);
+        }
+        // ---- primary ray: a closest hit; a lane past the end of the window gets the miss record
+        const mr_hit h = trace_hit<true, false, false, VAR>(a.tp, ra, rb, rb.w, live, s_stack, tid, st);
+        if (a.hits && live) reinterpret_cast<float4 *>(a.hits)[idx] = *reinterpret_cast<const float4 *>(&h);
+
+        // ---- HitInfo::P, the normal as Scene::trace leaves it and diffuseColor: the surface pass's step for this hit
+        const bool hit = live && h.prim != MR_MISS;
+        float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 1.f, 0.f}, col[3] = {0.f, 0.f, 0.f};
+        const float *mt = a.m.mats;
+        if (hit) {
+            // the ray's origin is the eye (a hit lane is a live one): read from the arguments, uniform, where it is used
+            surface_od<true>(a.m.s, a.eye.eye[0], a.eye.eye[1], a.eye.eye[2], rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
+            bool ok = true;
+            if (table) {
+                hit_color_normal(a.m, a.t, nt, h.prim, P, N, col, ok);
+            } else {
+                TexParams t0 = a.t;
+                t0.mat_tex = nullptr;
+                hit_color_normal(a.m, t0, nt, h.prim, P, N, col, ok);
+            }
+            if (!ok) my_undefined++;
+            if (a.sample_color) { a.sample_color[3 * idx] = col[0]; a.sample_color[3 * idx + 1] = col[1]; a.sample_color[3 * idx + 2] = col[2]; }
+            if (a.sample_normal) { a.sample_normal[3 * idx] = N[0]; a.sample_normal[3 * idx + 1] = N[1]; a.sample_normal[3 * idx + 2] = N[2]; }
+            mt = material_of(a.m, h.prim);
+            my_shadow_rays += a.n_lights;
+        }
+        // the eye ray's direction, computed again: cheaper than three registers live across the lookup.  With ENV a live lane
+        // that missed needs it too (a lane past the end of the window is no miss)
+        float d[3] = {0.f, 0.f, 0.f};
+        if (ENV ? live : hit) {
+            eye_sample_of(a.eye, idx, x, row, y, sm);
+            eye_ray_of(a.eye, x, y, sm, ra, rb);
+            d[0] = rb.x; d[1] = rb.y; d[2] = rb.z;
+        }
+
+        // ---- Phong::shade over the light list (shade_lights_body with kColorSurface); a miss contributes nothing (m_bgColor = 0)
+        // or, with ENV, what Scene::traceScene returns for it (Scene.cpp:338-342)
+        float L[3] = {0.f, 0.f, 0.f};
+        if (ENV) {
+            if (live && !hit) {
+                my_misses++;
+                if (env.full) {                                        // wave-uniform
+                    if (!env_lookup_full(env, d[0], d[1], d[2], L)) my_env_undefined++;
+                } else {
+                    L[0] = env.bg[0]; L[1] = env.bg[1]; L[2] = env.bg[2];                      // Scene.cpp:685
+                }
+            }
+        }
+        for (uint32_t li = 0; li < a.n_lights; li++) {                 // Phong.cpp:63, wave-uniform
+            const ShadeLight &lt = a.lights[li];
+            float4 sh;
+            {
+                float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(1.f, 1.f, 1.f, -1.f);
+                if (hit) shadow_ray_for(lt, P, sa, sb);
+                const mr_hit hs = trace_hit<true, ANY, false, VAR>(a.tp, sa, sb, sb.w, hit, s_stack, tid, st);
+                sh = *reinterpret_cast<const float4 *>(&hs);
+            }
+            if (hit) {
+                float4 sa, sb;
+                shadow_ray_for(lt, P, sa, sb);                         // rebuilt rather than kept across the traversal
+                const float scale = light_scale_of(a.m, sa, sb, sh);
+                float diffuse[3] = {0.f, 0.f, 0.f}, highlight = 0.0f, out[3] = {0.f, 0.f, 0.f};
+                bool lit = scale != 0.0f;                              // Phong.cpp:100-111: the light is skipped
+                if (lit) {
+                    if (lt.kind == MR_LIGHT_DISC) {
+                        const float l[3] = {sb.x, sb.y, sb.z};
+                        lit = disc_terms(lt, mt, col, P, N, l, d[0], d[1], d[2], diffuse, highlight);
+                    } else {
+                        phong_terms(lt.position, lt.color, lt.wattage, mt, col, P, N, d[0], d[1], d[2], diffuse, highlight);
+                    }
+                }
+                if (lit) phong_combine(diffuse, highlight, scale, out);
+                L[0] += out[0]; L[1] += out[1]; L[2] += out[2];
+            }
+        }
+        if (a.sample_rgb && live) { a.sample_rgb[3 * idx] = L[0]; a.sample_rgb[3 * idx + 1] = L[1]; a.sample_rgb[3 * idx + 2] = L[2]; }
+
+        // ---- the pixel's mean (Scene.cpp:126-139), as frame_kernel forms it: spp is a power of two <= 64 (checked by the
+        // host), a pixel's samples are `spp` consecutive, aligned lanes; the summation tree depends on the sample index only
+        for (uint32_t off = 1; off < spp; off <<= 1) {
+            L[0] += __shfl_xor(L[0], (int)off, 64);
+            L[1] += __shfl_xor(L[1], (int)off, 64);
+            L[2] += __shfl_xor(L[2], (int)off, 64);
+        }
+        if (live) eye_sample_of(a.eye, idx, x, row, y, sm);      // recomputed: cheaper than live registers across the traversals
+        if (live && sm == 0) {
+            if (spp > 1) {
+                const float inv_spp = 1.0f / (float)spp;
+                L[0] *= inv_spp; L[1] *= inv_spp; L[2] *= inv_spp;
+            }
+            float *o = a.rgb + 3 * ((size_t)row * a.eye.W + x);
+            o[0] = L[0]; o[1] = L[1]; o[2] = L[2];
+        }
+    }
+
+    // rays traced, undefined lookups and misses.  Per-lane counts: one atomic per workgroup each; primary rays: the launch's
+    // sample count, added once.
+    if (a.counts) {
+        workgroup_add<kTraceBlock>(my_shadow_rays, &a.counts[1]);
+        workgroup_add<kTraceBlock>(my_undefined, &a.counts[2]);
+        if (ENV) {
+            workgroup_add<kTraceBlock>(my_misses, &a.counts[3]);
+            workgroup_add<kTraceBlock>(my_env_undefined, &a.counts[4]);
+        }
+        if (blockIdx.x == 0 && tid == 0) atomicAdd(&a.counts[0], n);
+    }
+}
+
+}  // namespace
+}  // namespace mr

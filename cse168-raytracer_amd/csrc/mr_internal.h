@@ -301,6 +301,12 @@ struct TexParams;
 mr_status launch_frame_lights_surface(const DeviceScene &ds, const TexParams &tex, const ShadeLight *lights, uint32_t n_lights,
                                       const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color,
                                       float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream);
+// ... with the environment for rays that miss (mr_frame_lights_env.hip, mr_render_lights_environment): a live sample whose
+// primary ray misses is worth env.bg, or the lookup of the full image (env.full); d_counts: five words
+struct EnvParams;
+mr_status launch_frame_lights_env(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
+                                  uint32_t n_lights, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
+                                  float *d_sample_color, float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream);
 
 // the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
 // square light, side * side shadow rays per hit and light

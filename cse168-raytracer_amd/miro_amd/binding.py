@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = [
 SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map_build_device", "mr_trace_photons_resident",
                    "mr_shade_square_lights_surface", "mr_gen_path_rays_surface", "mr_bvh_build_timing", "mr_render_lights",
                    "mr_render_lights_surface"]
+# every symbol include/miro_hip_frame.h declares (fused frame calls added after that list was held at 9 names)
+FRAME_SYMBOLS = ["mr_render_lights_environment"]
 
 
 class MiroError(RuntimeError):
@@ -287,6 +289,7 @@ def load_library(path=None):
     L.mr_render_direct.argtypes = [vp, C.POINTER(FrameDesc), vp, vp, vp, vp, vp]
     L.mr_render_lights.argtypes = [vp, C.POINTER(FrameDesc), vp, vp, vp, vp, vp]
     L.mr_render_lights_surface.argtypes = [vp, C.POINTER(FrameDesc), vp, vp, vp, vp, vp, vp, vp]
+    L.mr_render_lights_environment.argtypes = L.mr_render_lights_surface.argtypes
     L.mr_tonemap.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.mr_scene_set_materials.argtypes = [vp, C.POINTER(Material), C.c_uint32, u32p]
     L.mr_shade_accumulate.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(Light), C.c_uint32, vp, vp]
@@ -336,10 +339,10 @@ def load_library(path=None):
     L.mr_irradiance_estimate.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, vp, vp, vp, vp]
     L.mr_photon_map_count_stats.argtypes = [vp, C.c_int32]
     L.mr_photon_map_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int32]
-    for name in SURFACE_SYMBOLS:
+    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS:
         if not hasattr(L, name):
             raise OSError("%s does not export %s" % (path, name))
-    for name in EXPORTED_SYMBOLS + SURFACE_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS:
         if hasattr(L, name) and getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = C.c_int32
     _lib = L
@@ -713,8 +716,9 @@ class Scene:
         and normal are hit_surface's (every texture kind, the bump-mapped normal of a STONE material), looked up between the
         primary trace and the light loop of the same launch.  d_sample_color / d_sample_normal [n, 3]: what hit_surface writes
         for each sample (a miss leaves its row untouched).  d_counts: THREE words, [0] += samples, [1] += shadow rays,
-        [2] += hits whose lookup the reference leaves undefined.  A miss contributes 0: set_environment is not applied.  The
-        first call after set_textures uploads the table and must lie outside a graph capture."""
+        [2] += hits whose lookup the reference leaves undefined.  A miss contributes 0: set_environment is not applied
+        (render_lights_environment applies it).  The first call after set_textures uploads the table and must lie outside a
+        graph capture."""
         fd = FrameDesc()
         fd.camera = cam
         fd.W, fd.H, fd.y0, fd.y1 = W, H, y0, H if y1 is None else y1
@@ -722,6 +726,21 @@ class Scene:
         fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
         _check(self.L.mr_render_lights_surface(self.h, C.byref(fd), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb),
                                                _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_counts), _stream_ptr(stream)))
+
+    def render_lights_environment(self, cam, W, H, d_rgb, y0=0, y1=None, bands=None, spp=1, jitter=False, seed=168, tiled=False, flags=0,
+                                  d_hits=None, d_sample_rgb=None, d_sample_color=None, d_sample_normal=None, d_counts=None, stream=None):
+        """mr_render_lights_environment: render_lights_surface with the scene's environment (set_environment) for rays that miss
+        -- a live sample whose primary ray misses is worth bg_color, or the lookup of the full-resolution image at the eye ray's
+        direction; the value is the sample's L (d_sample_rgb, the pixel's mean).  d_counts: FIVE words, [0..2] as in
+        render_lights_surface, [3] += samples that missed, [4] += environment lookups the reference leaves undefined.  The first
+        call after set_environment with an image uploads it and must lie outside a graph capture, like the texture table."""
+        fd = FrameDesc()
+        fd.camera = cam
+        fd.W, fd.H, fd.y0, fd.y1 = W, H, y0, H if y1 is None else y1
+        fd.band_rows, fd.band_rank, fd.band_world = bands if bands is not None else (1, 0, 1)
+        fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
+        _check(self.L.mr_render_lights_environment(self.h, C.byref(fd), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb),
+                                                   _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_counts), _stream_ptr(stream)))
 
     def final_gather(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb, max_dist=1e10, nphotons=500,
                      spp=1, stream=None):

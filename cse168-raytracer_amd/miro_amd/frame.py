@@ -129,22 +129,35 @@ class FusedFrame:
     mr_render_lights: the frame over a light list, and `keep_hits` keeps the primary records only.  On a scene with a texture
     table (Scene.n_textures at step()) that launch is mr_render_lights_surface: the same frame with every hit's looked-up colour
     and bump-mapped normal.  A sample that misses contributes 0 in both: the scene's environment (set_environment) is not
-    applied -- mr_shade_environment needs the ray and hit buffers and stays with the batched route (FrameRenderer)."""
+    applied.  With `lights` and `environment` the launch is mr_render_lights_environment on any scene: that frame with the
+    environment's value -- bg_color, or the lookup of the full-resolution image -- as the L of every sample that misses, the
+    level-0 image of Scene::raytraceImage with its background, still one launch and no ray buffers; d_counts then has five
+    words (environment_counts())."""
 
     def __init__(self, scene, desc, W, H, spp=1, band=None, rank=0, world=1, jitter=None, seed=168, flags=0, rgb=None,
-                 tiled=None, keep_hits=False, any_shadow=False, no_shadows=False, lights=None):
+                 tiled=None, keep_hits=False, any_shadow=False, no_shadows=False, lights=None, environment=None):
         """no_shadows: MR_FRAME_NO_SHADOWS, the reference's -DDISABLE_SHADOWS build (primary rays only, BASELINE config 2).
         A scene with a material table (Scene.set_materials) is shaded with its per-object materials (Phong.cpp:99-156).
         lights: a list for Scene.set_lights (point and disc lights), set once here; step() then renders with
         Scene.render_lights instead of the description's one point light (any_shadow: MR_TRACE_ANY for the shadow rays;
-        no_shadows is not available there).  None: nothing changes."""
+        no_shadows is not available there).  None: nothing changes.
+        environment (with `lights` only): True -- misses are shaded with the scene's environment as it is set; a dict -- the
+        arguments of Scene.set_environment, applied once here; step() then renders with Scene.render_lights_environment.
+        None: nothing changes."""
         if isinstance(desc, str):
             desc = scenes.SCENES[desc]
         if lights is not None and no_shadows:
             raise ValueError("FusedFrame: no_shadows is not available with a light list (mr_render_lights always traces shadow rays)")
+        if environment is not None and environment is not True and not isinstance(environment, dict):
+            raise ValueError("FusedFrame: environment is None, True or a dict of Scene.set_environment's arguments")
+        if environment is not None and lights is None:
+            raise ValueError("FusedFrame: environment needs a light list (mr_render_direct has no environment)")
         self.lights = None if lights is None else list(lights)
         if self.lights is not None:
             scene.set_lights(self.lights)
+        self.environment = environment is not None
+        if isinstance(environment, dict):
+            scene.set_environment(**environment)
         self.scene, self.desc, self.W, self.H, self.spp = scene, desc, W, H, spp
         self.jitter = (spp > 1) if jitter is None else jitter
         self.seed = seed
@@ -162,8 +175,8 @@ class FusedFrame:
         self.d_hits = torch.empty((max(self.n, 1), 4), **f32) if keep_hits else None
         self.d_shadow_hits = torch.empty((max(self.n, 1), 4), **f32) if keep_hits and self.lights is None else None
         # primary rays, shadow rays and, with a light list, undefined lookups (mr_render_direct's counters stay two words: the
-        # tests of its counter ring compare the whole tensor)
-        self.d_counts = torch.zeros(2 if self.lights is None else 3, dtype=torch.int64, device=self.device)
+        # tests of its counter ring compare the whole tensor); with an environment besides misses and undefined environment lookups
+        self.d_counts = torch.zeros(2 if self.lights is None else 5 if self.environment else 3, dtype=torch.int64, device=self.device)
         self.cam = binding.make_camera(desc["eye"], desc["lookat"], desc["up"], desc["fov"])
 
     def bytes_resident(self):
@@ -175,6 +188,8 @@ class FusedFrame:
             return
         if self.lights is not None:
             render = self.scene.render_lights_surface if self.scene.n_textures else self.scene.render_lights
+            if self.environment:
+                render = self.scene.render_lights_environment
             render(self.cam, self.W, self.H, self.d_rgb, bands=self.bands, spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled,
                    flags=self.flags, d_hits=self.d_hits, d_counts=self.d_counts, stream=stream)
             return
@@ -192,6 +207,14 @@ class FusedFrame:
         """Hits whose texture lookup the reference leaves undefined, per step (mr_render_lights_surface's d_counts[2]; 0 for every
         other launch of this class) -- synchronises."""
         return int(self.d_counts.cpu().numpy()[2]) // max(steps, 1) if self.lights is not None else 0
+
+    def environment_counts(self, steps=1):
+        """(misses, undefined environment lookups) per step: mr_render_lights_environment's d_counts[3] and [4]; (0, 0) for
+        every other launch of this class -- synchronises."""
+        if not self.environment:
+            return 0, 0
+        c = self.d_counts.cpu().numpy()
+        return int(c[3]) // max(steps, 1), int(c[4]) // max(steps, 1)
 
 
 class Queue(collections.namedtuple("Queue", "rays weights pixels ids octs n")):

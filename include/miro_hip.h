@@ -305,7 +305,10 @@ mr_status mr_render_direct(mr_scene *scene, const mr_frame_desc *frame, float *d
                            uint64_t *d_counts, void *stream);
 /* "mr_render_lights" (declared, with its whole contract, in miro_hip_surface.h): this frame over the scene's light list
  * (mr_scene_set_lights: point and disc lights) and its material table instead of `light` / `diffuse`, bit for bit
- * mr_gen_eye_rays[_tiled] -> mr_trace -> mr_shade_lights; one launch, no counters, no eye-relative tables. */
+ * mr_gen_eye_rays[_tiled] -> mr_trace -> mr_shade_lights; one launch, no counters, no eye-relative tables.
+ * "mr_render_lights_surface" (miro_hip_surface.h) is that frame on any scene, textured ones included, and
+ * "mr_render_lights_environment" (declared, with its whole contract, in miro_hip_frame.h) the frame that gives a ray that
+ * misses the environment of mr_scene_set_environment: the level-0 image of Scene::raytraceImage, background included. */
 
 /* ---- multi-GPU frames: image rows dealt to the devices in interleaved bands -------------------
  * Bands of band_rows rows are dealt round-robin: band b (rows [b*band_rows, ...)) belongs to rank b % world and is that
@@ -950,4 +953,5 @@ const char *mr_version(void);
 }
 #endif
 #include "miro_hip_surface.h"
+#include "miro_hip_frame.h"
 #endif /* MIRO_HIP_H */

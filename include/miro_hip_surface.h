@@ -119,7 +119,7 @@ mr_status mr_render_lights(mr_scene *scene, const mr_frame_desc *frame, float *d
  *   d_counts         THREE words: [0] += samples, [1] += shadow rays, [2] += hits whose lookup the reference leaves undefined
  *                    (mr_hit_surface's d_counts[0] on the same batch); 8-byte aligned, not zeroed by the call
  * A sample that misses contributes 0, as in mr_render_lights: the environment of mr_scene_set_environment is NOT applied
- *   (mr_shade_environment needs the ray and hit buffers and stays with the batched route).
+ *   (mr_render_lights_environment, declared in miro_hip_frame.h, is this call with it applied).
  * Launches: with a texture table that is already on the device the call enqueues ONE kernel on `stream` and can be captured
  *   into a graph.  The first call after mr_scene_set_textures uploads the table on `stream` -- an allocation and a copy -- and
  *   must lie outside a capture (every other call that reads the table uploads it too).
