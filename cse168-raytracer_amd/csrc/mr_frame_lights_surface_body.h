@@ -22,6 +22,7 @@
 #include "mr_hit_surface_body.h"
 #include "mr_internal.h"
 #include "mr_launch.h"
+#include "mr_light_loop.h"
 #include "mr_noise.h"
 #include "mr_phong.h"
 #include "mr_surface.h"
@@ -124,7 +125,7 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
             d[0] = rb.x; d[1] = rb.y; d[2] = rb.z;
         }
 
-        // ---- Phong::shade over the light list (shade_lights_body with kColorSurface); a miss contributes nothing (m_bgColor = 0)
+        // ---- Phong::shade over the light list (shade_light_list, mr_light_loop.h: shade_lights_body's loop with kColorSurface); a miss contributes nothing (m_bgColor = 0)
         // or, with ENV, what Scene::traceScene returns for it (Scene.cpp:338-342)
         float L[3] = {0.f, 0.f, 0.f};
         if (ENV) {
@@ -137,33 +138,7 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
                 }
             }
         }
-        for (uint32_t li = 0; li < a.n_lights; li++) {                 // Phong.cpp:63, wave-uniform
-            const ShadeLight &lt = a.lights[li];
-            float4 sh;
-            {
-                float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(1.f, 1.f, 1.f, -1.f);
-                if (hit) shadow_ray_for(lt, P, sa, sb);
-                const mr_hit hs = trace_hit<true, ANY, false, VAR>(a.tp, sa, sb, sb.w, hit, s_stack, tid, st);
-                sh = *reinterpret_cast<const float4 *>(&hs);
-            }
-            if (hit) {
-                float4 sa, sb;
-                shadow_ray_for(lt, P, sa, sb);                         // rebuilt rather than kept across the traversal
-                const float scale = light_scale_of(a.m, sa, sb, sh);
-                float diffuse[3] = {0.f, 0.f, 0.f}, highlight = 0.0f, out[3] = {0.f, 0.f, 0.f};
-                bool lit = scale != 0.0f;                              // Phong.cpp:100-111: the light is skipped
-                if (lit) {
-                    if (lt.kind == MR_LIGHT_DISC) {
-                        const float l[3] = {sb.x, sb.y, sb.z};
-                        lit = disc_terms(lt, mt, col, P, N, l, d[0], d[1], d[2], diffuse, highlight);
-                    } else {
-                        phong_terms(lt.position, lt.color, lt.wattage, mt, col, P, N, d[0], d[1], d[2], diffuse, highlight);
-                    }
-                }
-                if (lit) phong_combine(diffuse, highlight, scale, out);
-                L[0] += out[0]; L[1] += out[1]; L[2] += out[2];
-            }
-        }
+        shade_light_list<VAR, ANY>(a.tp, a.m, a.lights, a.n_lights, hit, P, N, mt, col, d, s_stack, tid, st, L);
         if (a.sample_rgb && live) { a.sample_rgb[3 * idx] = L[0]; a.sample_rgb[3 * idx + 1] = L[1]; a.sample_rgb[3 * idx + 2] = L[2]; }
 
         // ---- the pixel's mean (Scene.cpp:126-139), as frame_kernel forms it: spp is a power of two <= 64 (checked by the

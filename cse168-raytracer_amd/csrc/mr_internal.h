@@ -307,6 +307,14 @@ struct EnvParams;
 mr_status launch_frame_lights_env(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
                                   uint32_t n_lights, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
                                   float *d_sample_color, float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream);
+// one level of the recursion over the light list on any scene (mr_level_lights.hip, mr_trace_level_lights): launch_level's queues
+// with that frame's texture table, environment (read with ld.environment only) and optional per-ray outputs; d_out_count is
+// zeroed on `stream` on a level with children (a one-word kernel), then one kernel (none for n == 0); d_counts: five words
+mr_status launch_level_lights(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
+                              uint32_t n_lights, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
+                              const uint32_t *d_pixels, unsigned long long n, float *d_rgb, mr_hit *d_hits, float *d_ray_rgb,
+                              float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
+                              unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
 
 // the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
 // square light, side * side shadow rays per hit and light

@@ -70,7 +70,7 @@ SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map
                    "mr_shade_square_lights_surface", "mr_gen_path_rays_surface", "mr_bvh_build_timing", "mr_render_lights",
                    "mr_render_lights_surface"]
 # every symbol include/miro_hip_frame.h declares (fused frame calls added after that list was held at 9 names)
-FRAME_SYMBOLS = ["mr_render_lights_environment"]
+FRAME_SYMBOLS = ["mr_render_lights_environment", "mr_trace_level_lights"]
 
 
 class MiroError(RuntimeError):
@@ -121,6 +121,13 @@ class LevelDesc(C.Structure):
                 ("path_kinds", C.c_uint32), ("seed", C.c_uint32), ("bounce", C.c_uint32),
                 ("out_capacity_lo", C.c_uint32), ("out_capacity_hi", C.c_uint32), ("reserved", C.c_uint32),
                 ("d_out_octants", C.c_void_p), ("d_order", C.c_void_p)]
+
+
+class LevelLightsDesc(C.Structure):
+    """mr_level_lights_desc (miro_hip_frame.h): one level of traceScene's recursion for mr_trace_level_lights"""
+    _fields_ = [("spp", C.c_uint32), ("flags", C.c_uint32), ("children", C.c_uint32), ("environment", C.c_uint32),
+                ("out_capacity_lo", C.c_uint32), ("out_capacity_hi", C.c_uint32), ("reserved", C.c_uint32 * 6),
+                ("d_out_octants", C.c_void_p)]
 
 
 class Material(C.Structure):
@@ -296,6 +303,7 @@ def load_library(path=None):
     L.mr_gen_secondary_rays.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, vp]
     L.mr_gen_path_rays.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
     L.mr_trace_level.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mr_trace_level_lights.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mr_final_gather.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.mr_trace_photons.argtypes = [vp, vp, C.POINTER(PhotonTraceDesc), C.POINTER(PhotonTraceResult), vp, C.c_uint64, vp]
     L.mr_trace_photons_surface.argtypes = L.mr_trace_photons.argtypes
@@ -675,6 +683,29 @@ class Scene:
         _check(self.L.mr_trace_level(self.h, C.byref(ld), d_rays.data_ptr(), _ptr(d_weights), _ptr(d_pixels), _ptr(d_ids), n,
                                      d_rgb.data_ptr(), _ptr(d_out_rays), _ptr(d_out_weights), _ptr(d_out_pixels), _ptr(d_out_ids),
                                      _ptr(d_out_count), _ptr(d_counts), _stream_ptr(stream)))
+
+    def trace_level_lights(self, d_rays, d_weights, d_pixels, n, d_rgb, children=MR_LEVEL_LAST, environment=False, d_hits=None,
+                           d_ray_rgb=None, d_color=None, d_normal=None, d_out_rays=None, d_out_weights=None, d_out_pixels=None,
+                           d_out_count=None, d_counts=None, spp=1, flags=0, stream=None, out_capacity=None, d_out_octants=None):
+        """mr_trace_level_lights: one level of the recursion in one launch on any scene -- trace -> a miss: the scene's
+        environment (environment=True) or 0 -> a hit: hit_surface's colour and normal with the texture table or none, then per
+        light of set_lights the shadow ray, its trace and the Phong terms -> weight x L / spp added to the ray's pixel of d_rgb
+        (None when d_ray_rgb is given) -> with children=MR_LEVEL_SPECULAR the reflect / Fresnel / refract children into the output
+        queue.  d_hits [n, 4], d_ray_rgb / d_color / d_normal [n, 3]: optional per-ray outputs (a miss leaves its colour and normal
+        rows untouched).  d_counts: FIVE words, [0] += rays, [1] += shadow rays, [2] += undefined texture lookups, [3] += misses,
+        [4] += undefined environment lookups.  The first call after set_textures / set_environment uploads and must lie outside a
+        graph capture."""
+        ld = LevelLightsDesc()
+        ld.spp, ld.flags, ld.children, ld.environment = spp, flags, children, 1 if environment else 0
+        if out_capacity is None:
+            outs = [t for t in (d_out_rays, d_out_weights, d_out_pixels) if t is not None]
+            out_capacity = min(t.shape[0] for t in outs) if outs else 0
+        ld.out_capacity_lo, ld.out_capacity_hi = out_capacity & 0xFFFFFFFF, out_capacity >> 32
+        ld.d_out_octants = _ptr(d_out_octants)
+        _check(self.L.mr_trace_level_lights(self.h, C.byref(ld), d_rays.data_ptr(), _ptr(d_weights), _ptr(d_pixels), n, _ptr(d_rgb),
+                                            _ptr(d_hits), _ptr(d_ray_rgb), _ptr(d_color), _ptr(d_normal), _ptr(d_out_rays),
+                                            _ptr(d_out_weights), _ptr(d_out_pixels), _ptr(d_out_count), _ptr(d_counts),
+                                            _stream_ptr(stream)))
 
     def deinterleave_bands(self, d_recv, d_full, W, H, band_rows, world, shard_rows, floats_per_pixel=3, stream=None):
         _check(self.L.mr_deinterleave_bands(self.h, d_recv.data_ptr(), d_full.data_ptr(), W, H, band_rows, world, shard_rows,

@@ -236,7 +236,8 @@ class LevelPlan(collections.namedtuple("LevelPlan", (
         "env_lowres", "surface", "square", "square_lights", "surface_children", "photon_maps", "nphotons", "max_dist"))):
     """What FrameRenderer.render_specular decides once per call, from its arguments and the scene's state (_resolve):
     stream: the torch Stream of every launch, None for the current one; flags: the renderer's trace flags;
-    fused: False / True / "auto", already False on a scene with a texture table;
+    fused: False / True / "auto", already False on a scene with a texture table, or "lights" (every level is one
+    mr_trace_level_lights, on any scene);
     path_tracing, path_kinds (never None), fan (children per ray, at most), path_seed, group_octants: as given;
     lights: the scene's light list shades, not the description's point light; environment: misses are shaded, after the
     first level with env_lowres (MR_ENV_LOWRES or 0);
@@ -455,7 +456,15 @@ class FrameRenderer:
         PHOTON_MAX_DIST (Miro.h:16-17).  On a scene with a procedural texture the queries take the normal buffer that
         mr_hit_surface just filled (the bumped normal, Scene.cpp:290), otherwise the object's normal.  The scratch (12 floats per
         ray) is allocated with the level's other buffers.  `fused` must be falsy: mr_trace_level keeps no hit records.  None: no
-        launch is added."""
+        launch is added.
+        fused="lights": every level is ONE launch of mr_trace_level_lights on ANY scene -- trace, the environment of a miss, the
+        surface step (texture table or none, bumped normal), the loop over the light list, weight x L to the pixel, the specular
+        children -- where the batched path runs trace -> mr_shade_environment -> mr_hit_surface -> mr_shade_lights[_surface] ->
+        mr_gen_secondary_rays.  It needs lights=[...], takes environment= in every form and photon_maps= (the launch then also
+        writes the level's hit records, and bumped normals on a procedural scene, and mr_gather_level follows it), and raises
+        ValueError with path_tracing, square lights, group_octants or surface_children=True.  The same rays, children and counts;
+        the pixel sums differ by the order of the float atomics.  Opt-in: fused="auto" never chooses it (a level whose rays rarely
+        hit runs its light loop at that lane utilisation; DESIGN section 5c has the times)."""
         plan = self._resolve(stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights, environment, photon_maps,
                              nphotons, max_dist, surface_children)
         # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
@@ -469,7 +478,8 @@ class FrameRenderer:
                     break
                 one_launch = plan.fused is True or (plan.fused == "auto" and
                                                     (level == 0 or per_level[-1][1] >= 0.9 * per_level[-1][0]))
-                counts, queue = (self._level_fused if one_launch else self._level_batched)(plan, queue, level, level == depth)
+                step = self._level_lights if plan.fused == "lights" else self._level_fused if one_launch else self._level_batched
+                counts, queue = step(plan, queue, level, level == depth)
                 per_level.append(counts)
             self._untile(stream)
         return per_level
@@ -479,6 +489,17 @@ class FrameRenderer:
         """render_specular's arguments and the scene's state as a LevelPlan: every check, and the two scene setters
         (set_environment, set_lights) between them"""
         sc = self.scene
+        level_lights = isinstance(fused, str) and fused == "lights"
+        if level_lights:
+            if lights is None:
+                raise ValueError("render_specular: fused=\"lights\" needs lights=[...] (mr_trace_level_lights shades by the scene's light list)")
+            refused = [("path_tracing", path_tracing), ("square lights", self.square_lights), ("group_octants", group_octants),
+                       ("surface_children=True", surface_children is True)]
+            for what, given in refused:
+                if given:
+                    raise ValueError("render_specular: %s needs the batched path, not fused=\"lights\" (mr_trace_level_lights emits the "
+                                     "specular children and shades point and disc lights only)" % what)
+            fused = False                       # the checks below speak of mr_trace_level; the plan carries "lights"
         if sc.n_textures:
             fused = False
         if photon_maps is not None:
@@ -522,7 +543,7 @@ class FrameRenderer:
             raise TypeError("render_specular: pass a torch.cuda.Stream (or None for the current stream), not a raw handle")
         # square lights on a texture table of any kind read the surface pass's buffers (mr_shade_square_lights refuses the table)
         square = None if not self.square_lights else "surface" if sc.n_textures else "plain"
-        return LevelPlan(stream=stream, flags=self.flags, fused=fused, path_tracing=path_tracing,
+        return LevelPlan(stream=stream, flags=self.flags, fused="lights" if level_lights else fused, path_tracing=path_tracing,
                          path_kinds=binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT if path_kinds is None else path_kinds,
                          fan=4 if path_tracing else 3, path_seed=path_seed, group_octants=group_octants, lights=lights is not None,
                          environment=environment, env_lowres=env_lowres, surface=surface, square=square,
@@ -555,6 +576,29 @@ class FrameRenderer:
                        stream=plan.stream, d_out_octants=out.octs, d_order=order)
         host = cnts.tolist()
         return (n, host[1]), None if last else out.first(host[2])
+
+    def _level_lights(self, plan, q, level, last):
+        """One level as ONE launch of mr_trace_level_lights (then mr_gather_level, with photon maps); returns (rays, shadow rays)
+        and the next queue (None after the last)."""
+        sc, n, stream = self.scene, q.n, plan.stream
+        f32 = dict(dtype=torch.float32, device=self.device)
+        hits = normal = None
+        if plan.photon_maps is not None:                # the photon term reads the level's hit records (and bumped normals)
+            hits = self.d_hits if level == 0 else torch.empty((n, 4), **f32)
+            normal = torch.empty((n, 3), **f32) if plan.surface else None
+        cnts = torch.zeros(6, dtype=torch.int64, device=self.device)        # the call's five counters, children
+        out = NO_QUEUE if last else self._children(plan, n)
+        sc.trace_level_lights(q.rays, q.weights, q.pixels, n, self.d_slots,
+                              children=binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_SPECULAR, environment=plan.environment,
+                              d_hits=hits, d_normal=normal, d_out_rays=out.rays, d_out_weights=out.weights, d_out_pixels=out.pixels,
+                              d_out_count=None if last else cnts[5:], d_counts=cnts[:5], spp=self.spp,
+                              flags=plan.level_flags(level)[2], stream=stream)
+        if plan.photon_maps is not None:
+            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), self.d_slots,
+                            d_normal=normal, d_weights=q.weights, d_pixels=q.pixels, max_dist=plan.max_dist,
+                            nphotons=plan.nphotons, spp=self.spp, stream=stream)
+        host = cnts.tolist()
+        return (n, host[1]), None if last else out.first(host[5])
 
     def _level_batched(self, plan, q, level, last):
         """One level as separate launches: trace, environment, surface pass, shade, photon term, children -- whichever of

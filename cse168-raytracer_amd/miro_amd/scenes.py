@@ -214,7 +214,14 @@ SCENES["photon_room_two_lights"] = dict(
             dict(position=SCENES["photon_room"]["light"], color=(1.0, 1.0, 1.0), wattage=SCENES["photon_room"]["wattage"])])
 
 
-def flower_scene():
+# flower_scene(drops=True): centres of the glass spheres of radius 0.3 that stand in for WaterDropsMany.obj, each resting on a petal
+# where the scene's camera sees it (a point of Petals2.obj plus 0.3 along the petal's normal towards the camera)
+_DROP_RADIUS = 0.3
+_DROPS = [(3.22, 0.34, 4.84), (1.23, 0.5, 5.34), (-0.87, 0.31, 5.75), (4.34, 0.02, 2.96), (-2.25, 0.54, 3.86), (-1.57, 0.54, -0.36),
+          (4.67, 1.25, 0.9), (1.26, 0.66, 0.48)]
+
+
+def flower_scene(drops=False):
     """makeTestPetalScene (assignment3.cpp:34-122), the reference's final scene: a flower under a DirectionalAreaLight(7) at
     (50, 50, 40) facing the origin, wattage 4, camera (2, 4.4, 16.8) -> (3, 0, 4), fov 30.  Its four materials are
     TexturedPhongs (:93-102): PetalTexture(pivot 0, radius 7) with ks = kt = 0, shininess 500, index 1.5 on models/Petals2.obj;
@@ -225,6 +232,9 @@ def flower_scene():
     is a sphere of radius 1.1 at its texture's pivot, the drops are left out; gfx/forrest_salzburg02_big.hdr is missing -- a ray
     that misses gets setBgColor(1) (:52).  The three models are stored xz-compressed (tests/golden/models/*.obj.xz, the
     reference's files byte for byte); populate() unpacks them into the cache directory first.
+    drops=True: eight glass spheres of radius 0.3 on the petals stand in for the drops, with the reference's water material (:105:
+    Phong(kd 1, ks 0, kt 1, shininess 250, index 1.33)) as a fifth, untextured material -- the scene then has refractive objects and
+    every level of the recursion has children.  The default leaves them out, as before.
 
     Returns a description for populate() with, besides the usual keys, `textures` / `material_texture` for Scene.set_textures,
     `lights` (the disc light) and `environment` (the arguments of Scene.set_environment); flower_setup() applies them."""
@@ -234,15 +244,17 @@ def flower_scene():
     n_petals, n_stem, n_leaf = 14784, 1664, 6144                 # triangles of the three models
     zero = (0.0, 0.0, 0.0)
     centre = (-0.1, -0.35, 0.0)
+    water = [((1.0, 1.0, 1.0), zero, (1.0, 1.0, 1.0), 250.0, 1.33)] if drops else []
+    n_drops = len(_DROPS) if drops else 0
     return dict(
         models=[("Petals2.obj.xz", None), ("Stem.obj.xz", None), ("Leaf.obj.xz", None)], floor=None,
-        objects=[("sphere", centre, 1.1)],
+        objects=[("sphere", centre, 1.1)] + [("sphere", c, _DROP_RADIUS) for c in _DROPS[:n_drops]],
         # (kd, ks, kt, shininess, index): TexturedPhong's defaults are ks = kt = 0, shininess 1, index 1 (Texture.h:305-309)
         materials=[((1.0, 1.0, 1.0), zero, zero, 500.0, 1.5), ((1.0, 1.0, 1.0), zero, zero, 1.0, 1.0),
-                   ((1.0, 1.0, 1.0), zero, zero, 1.0, 1.0), ((1.0, 1.0, 1.0), zero, zero, 1.0, 1.0)],
-        prim_material=[0] * n_petals + [1] * n_stem + [2] * n_leaf + [3],
+                   ((1.0, 1.0, 1.0), zero, zero, 1.0, 1.0), ((1.0, 1.0, 1.0), zero, zero, 1.0, 1.0)] + water,
+        prim_material=[0] * n_petals + [1] * n_stem + [2] * n_leaf + [3] + [4] * n_drops,
         textures=[dict(petal=(zero, 7.0)), dict(stem=30.0), dict(leaf=1.0), dict(flower_center=(centre, 1.1))],
-        material_texture=[0, 1, 2, 3],
+        material_texture=[0, 1, 2, 3] + [_NONE] * len(water),
         lights=[dict(position=tuple(float(c) for c in pos), normal=tuple(float(c) for c in nrm), color=(1.0, 1.0, 1.0), wattage=4.0,
                      radius=7.0)],
         environment=dict(bg_color=(1.0, 1.0, 1.0)),

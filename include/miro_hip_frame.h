@@ -39,6 +39,54 @@ mr_status mr_render_lights_environment(mr_scene *scene, const mr_frame_desc *fra
                                        float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, uint64_t *d_counts,
                                        void *stream);
 
+/* ---- ONE level of Scene::traceScene's recursion in ONE launch on any scene: light list, texture table, environment ----------
+ * mr_trace_level (miro_hip.h) shades a queue by one point light with the plain material table.  This call takes the same queue
+ * -- d_rays, optional d_weights (NULL: 1) and d_pixels (NULL: ray index / spp), n rays -- and handles ray k in one lane:
+ *   1. Scene::trace, closest hit; d_hits[k], if given, is that record.
+ *   2. A miss: L = Scene::getEnvironmentMap(ray) of mr_scene_set_environment with environment == 1 -- bg_color, or the lookup of
+ *      the FULL-RESOLUTION image at the ray's direction (a specular child is never isDiffuse) -- otherwise 0.  A lookup the
+ *      reference leaves undefined is 0 and counted.
+ *   3. A hit: the per-hit step of mr_hit_surface with the scene's texture table or none (all seven texture kinds, the bumped
+ *      normal on stone); rows k of d_color / d_normal, if given, receive it.  A miss leaves its rows untouched.
+ *   4. A hit: for every light of mr_scene_set_lights in list order the shadow ray, its closest-hit trace, the light scale and the
+ *      point or disc terms, summed into L -- mr_shade_lights_surface's loop.
+ *   5. d_ray_rgb[k] = L, if given; weight * L / spp is added to d_rgb[pixel]: one add per ray, hit or miss (float atomics; rays
+ *      of one pixel in adjacent lanes are summed in the wave first).  d_rgb may be NULL when d_ray_rgb is given.
+ *   6. With children == MR_LEVEL_SPECULAR the reflect / Fresnel / refract children of mr_gen_secondary_rays go to the output
+ *      queue: about the normal and with the material that generator uses, not the bumped normal.  Capacity rule, d_out_count
+ *      (zeroed by the call, then += children, stored or not) and d_out_octants are mr_trace_level's.
+ * d_counts: FIVE words, 8-byte aligned, not zeroed by the call: [0] += rays, [1] += shadow rays (hits x lights), [2] +=
+ *   undefined texture lookups, [3] += misses, [4] += undefined environment lookups.
+ * flags: MR_MATH_PRODUCT, MR_TRACE_INCOHERENT only.  n == 0 is MR_OK and launches nothing, after zeroing d_out_count on a level
+ *   with children.
+ * The first call after mr_scene_set_textures or mr_scene_set_environment uploads (mr_render_lights_environment's rule) and must
+ *   lie outside a stream capture; after that the call is the zeroing of d_out_count (with children; a one-word kernel, so that a
+ *   graph replays it as written) plus one kernel and can be captured.
+ *
+ * The contract.  Per ray, the outputs are those of the batched
+ *   mr_trace -> mr_hit_surface -> mr_shade_lights_surface(d_ray_rgb) || mr_shade_environment(flags 0, d_ray_rgb)
+ *   -> mr_gen_secondary_rays
+ * on the same queue, bit for bit: hit records, colour, normal, L (the light chain's row where the ray hit, the environment
+ * chain's where it missed), the counters; the children are the same set in another order; d_rgb differs by the order of the
+ * float atomics.
+ * Errors.  MR_ERR_INVALID from the arguments alone, before the scene's state is read and before any device call: NULL scene /
+ *   level / d_rays; d_rgb and d_ray_rgb both NULL; spp == 0; other flags; children == MR_LEVEL_PATH (the path-traced generators
+ *   stay batched: mr_gen_path_rays[_surface]); non-zero reserved words; children without an output queue or capacity;
+ *   misalignment (rays and out rays 16 bytes, counters 8, float and index buffers 4).  MR_ERR_STATE: a scene that is unbuilt,
+ *   built host_only, or has no lights.  Square lights and the thin lens are not part of this call. */
+typedef struct mr_level_lights_desc {
+    uint32_t spp, flags, children;       /* children: MR_LEVEL_LAST or MR_LEVEL_SPECULAR */
+    uint32_t environment;                /* 0: a miss is worth 0.  1: Scene::getEnvironmentMap of mr_scene_set_environment */
+    uint32_t out_capacity_lo, out_capacity_hi;
+    uint32_t reserved[6];                /* must be 0 */
+    uint8_t *d_out_octants;              /* may be NULL, as in mr_level_desc */
+} mr_level_lights_desc;
+mr_status mr_trace_level_lights(mr_scene *scene, const mr_level_lights_desc *level, const mr_ray *d_rays,
+                                const float *d_weights, const uint32_t *d_pixels, uint64_t n, float *d_rgb,
+                                mr_hit *d_hits, float *d_ray_rgb, float *d_color, float *d_normal,
+                                mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
+                                uint64_t *d_out_count, uint64_t *d_counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
