@@ -1294,6 +1294,44 @@ mr_status mr_render_lights_environment(mr_scene *s, const mr_frame_desc *frame, 
                                    static_cast<hipStream_t>(stream));
 }
 
+// what mr_trace_level_lights and mr_trace_level_lights_path ask of their queues after the descriptor's own words, in this order:
+// the output queue and its capacity on a level with children (fan: children per ray at most), the ray count, the alignments.
+// more_misaligned: one of the buffers that the _path call takes besides is
+static mr_status check_level_lights_queue(const char *who, bool children, unsigned fan, uint32_t capacity_lo, uint32_t capacity_hi,
+                                          const mr_ray *d_rays, const float *d_weights, const uint32_t *d_pixels, uint64_t n,
+                                          const float *d_rgb, const mr_hit *d_hits, const float *d_ray_rgb, const float *d_color,
+                                          const float *d_normal, const mr_ray *d_out_rays, const float *d_out_weights,
+                                          const uint32_t *d_out_pixels, const uint64_t *d_out_count, const uint64_t *d_counts,
+                                          bool more_misaligned) {
+    if (children && (!d_out_rays || !d_out_weights || !d_out_pixels || !d_out_count))
+        return fail(MR_ERR_INVALID, "%s: a level with children needs the output queue", who);
+    if (children && n > 0 && capacity_lo == 0 && capacity_hi == 0)
+        return fail(MR_ERR_INVALID, "%s: out_capacity is 0 (room for %un rays always suffices)", who, fan);
+    if (n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 rays per call", who);
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_out_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) ||
+        (reinterpret_cast<uintptr_t>(d_out_count) & 7) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_weights) & 3) || (reinterpret_cast<uintptr_t>(d_pixels) & 3) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_color) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_out_weights) & 3) || (reinterpret_cast<uintptr_t>(d_out_pixels) & 3) || more_misaligned)
+        return fail(MR_ERR_INVALID, "%s: ray queues and the hit buffer must be 16-byte aligned, counters 8-byte, float and index buffers "
+                                    "4-byte aligned", who);
+    return MR_OK;
+}
+
+// ... and of the scene, after the arguments: built on a device, with lights; then the two uploads of
+// mr_render_lights_environment (texture table; environment image with `environment`), each only after a change
+static mr_status level_lights_params(const char *who, mr_scene *s, bool environment, hipStream_t stream, TexParams &tex, EnvParams &env) {
+    mr_status st = require_device(s);
+    if (st != MR_OK) return st;
+    if (s->lights.empty()) return fail(MR_ERR_STATE, "%s: the scene has no lights (mr_scene_set_lights)", who);
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
+    if (!s->tex.blob.empty() && (st = texture_params(s, stream, tex)) != MR_OK) return st;
+    env = EnvParams{};
+    if (environment && (st = environment_params(s, stream, env)) != MR_OK) return st;
+    return MR_OK;
+}
+
 // One level of the recursion over the light list on any scene, in one launch (mr_level_lights.hip).  What the arguments alone can
 // get wrong is answered first, before any device call and before the scene's state is read; then the scene's state; then the two
 // uploads of mr_render_lights_environment (texture table, environment image: outside a stream capture), each only after a change.
@@ -1315,31 +1353,53 @@ mr_status mr_trace_level_lights(mr_scene *s, const mr_level_lights_desc *level, 
     if (level->environment > 1) return fail(MR_ERR_INVALID, "%s: environment must be 0 or 1", who);
     for (int k = 0; k < 6; k++)
         if (level->reserved[k] != 0) return fail(MR_ERR_INVALID, "%s: mr_level_lights_desc.reserved must be 0", who);
-    if (level->children != MR_LEVEL_LAST && (!d_out_rays || !d_out_weights || !d_out_pixels || !d_out_count))
-        return fail(MR_ERR_INVALID, "%s: a level with children needs the output queue", who);
-    if (level->children != MR_LEVEL_LAST && n > 0 && level->out_capacity_lo == 0 && level->out_capacity_hi == 0)
-        return fail(MR_ERR_INVALID, "%s: out_capacity is 0 (room for 3n rays always suffices)", who);
-    if (n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 rays per call", who);
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_out_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_out_count) & 7) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
-        (reinterpret_cast<uintptr_t>(d_weights) & 3) || (reinterpret_cast<uintptr_t>(d_pixels) & 3) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_color) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_out_weights) & 3) || (reinterpret_cast<uintptr_t>(d_out_pixels) & 3))
-        return fail(MR_ERR_INVALID, "%s: ray queues and the hit buffer must be 16-byte aligned, counters 8-byte, float and index buffers "
-                                    "4-byte aligned", who);
-    mr_status st = require_device(s);
+    mr_status st = check_level_lights_queue(who, level->children != MR_LEVEL_LAST, 3u, level->out_capacity_lo, level->out_capacity_hi, d_rays,
+                                            d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights,
+                                            d_out_pixels, d_out_count, d_counts, false);
     if (st != MR_OK) return st;
-    if (s->lights.empty()) return fail(MR_ERR_STATE, "%s: the scene has no lights (mr_scene_set_lights)", who);
-    MR_HIP_CHECK(hipSetDevice(s->device));
     TexParams tex;
-    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
-    if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
-    EnvParams env = EnvParams{};
-    if (level->environment && (st = environment_params(s, static_cast<hipStream_t>(stream), env)) != MR_OK) return st;
+    EnvParams env;
+    if ((st = level_lights_params(who, s, level->environment != 0, static_cast<hipStream_t>(stream), tex, env)) != MR_OK) return st;
     return launch_level_lights(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), *level, d_rays, d_weights, d_pixels, n,
                                d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights, d_out_pixels,
                                reinterpret_cast<unsigned long long *>(d_out_count), reinterpret_cast<unsigned long long *>(d_counts),
                                static_cast<hipStream_t>(stream));
+}
+
+// ... of a PATH_TRACING build (mr_level_lights_path.hip): the children of mr_gen_path_rays_surface, ids, the low-res byte.  The
+// checks, their order and the uploads are mr_trace_level_lights', under this call's name; the two byte masks take any address.
+mr_status mr_trace_level_lights_path(mr_scene *s, const mr_level_lights_path_desc *level, const mr_ray *d_rays, const float *d_weights,
+                                     const uint32_t *d_pixels, const uint32_t *d_ids, uint64_t n, float *d_rgb, mr_hit *d_hits,
+                                     float *d_ray_rgb, float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights,
+                                     uint32_t *d_out_pixels, uint32_t *d_out_ids, uint64_t *d_out_count, uint64_t *d_counts,
+                                     void *stream) {
+    const char *who = "mr_trace_level_lights_path";
+    if (!s || !level || !d_rays) return fail(MR_ERR_INVALID, "%s: NULL argument (scene, level and d_rays are required)", who);
+    if (!d_rgb && !d_ray_rgb) return fail(MR_ERR_INVALID, "%s: NULL argument (d_rgb and d_ray_rgb are both NULL)", who);
+    if (level->spp == 0) return fail(MR_ERR_INVALID, "%s: spp is 0", who);
+    if (level->flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT | MR_ENV_LOWRES))
+        return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_ENV_LOWRES only", who);
+    if (level->children == MR_LEVEL_SPECULAR)
+        return fail(MR_ERR_INVALID, "%s: children == MR_LEVEL_SPECULAR: the specular children are mr_trace_level_lights'", who);
+    if (level->children != MR_LEVEL_LAST && level->children != MR_LEVEL_PATH)
+        return fail(MR_ERR_INVALID, "%s: children must be MR_LEVEL_LAST or MR_LEVEL_PATH", who);
+    if (level->environment > 1) return fail(MR_ERR_INVALID, "%s: environment must be 0 or 1", who);
+    if (level->children == MR_LEVEL_PATH && (level->path_kinds == 0 || (level->path_kinds & ~7u)))
+        return fail(MR_ERR_INVALID, "%s: path_kinds must be a combination of MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE", who);
+    for (int k = 0; k < 5; k++)
+        if (level->reserved[k] != 0) return fail(MR_ERR_INVALID, "%s: mr_level_lights_path_desc.reserved must be 0", who);
+    mr_status st = check_level_lights_queue(who, level->children != MR_LEVEL_LAST, 4u, level->out_capacity_lo, level->out_capacity_hi, d_rays,
+                                            d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights,
+                                            d_out_pixels, d_out_count, d_counts,
+                                            (reinterpret_cast<uintptr_t>(d_ids) & 3) || (reinterpret_cast<uintptr_t>(d_out_ids) & 3));
+    if (st != MR_OK) return st;
+    TexParams tex;
+    EnvParams env;
+    if ((st = level_lights_params(who, s, level->environment != 0, static_cast<hipStream_t>(stream), tex, env)) != MR_OK) return st;
+    return launch_level_lights_path(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), *level, d_rays, d_weights, d_pixels,
+                                    d_ids, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights, d_out_pixels,
+                                    d_out_ids, reinterpret_cast<unsigned long long *>(d_out_count),
+                                    reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_gen_eye_rays_lens(mr_scene *s, const mr_camera *cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp,

@@ -315,6 +315,15 @@ mr_status launch_level_lights(const DeviceScene &ds, const TexParams &tex, const
                               const uint32_t *d_pixels, unsigned long long n, float *d_rgb, mr_hit *d_hits, float *d_ray_rgb,
                               float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
                               unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
+// ... of a PATH_TRACING build (mr_level_lights_path.hip, mr_trace_level_lights_path): the same level with the children of
+// mr_gen_path_rays_surface (ids in and out, ld.path_kinds / seed / bounce), the low-res environment image for the rays that
+// ld.d_lowres or MR_ENV_LOWRES names, and ld.d_out_lowres for the next level
+mr_status launch_level_lights_path(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
+                                   uint32_t n_lights, const mr_level_lights_path_desc &ld, const mr_ray *d_rays, const float *d_weights,
+                                   const uint32_t *d_pixels, const uint32_t *d_ids, unsigned long long n, float *d_rgb, mr_hit *d_hits,
+                                   float *d_ray_rgb, float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights,
+                                   uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_out_count,
+                                   unsigned long long *d_counts, hipStream_t stream);
 
 // the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
 // square light, side * side shadow rays per hit and light

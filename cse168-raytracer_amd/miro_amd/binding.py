@@ -70,7 +70,7 @@ SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map
                    "mr_shade_square_lights_surface", "mr_gen_path_rays_surface", "mr_bvh_build_timing", "mr_render_lights",
                    "mr_render_lights_surface"]
 # every symbol include/miro_hip_frame.h declares (fused frame calls added after that list was held at 9 names)
-FRAME_SYMBOLS = ["mr_render_lights_environment", "mr_trace_level_lights"]
+FRAME_SYMBOLS = ["mr_render_lights_environment", "mr_trace_level_lights", "mr_trace_level_lights_path"]
 
 
 class MiroError(RuntimeError):
@@ -128,6 +128,14 @@ class LevelLightsDesc(C.Structure):
     _fields_ = [("spp", C.c_uint32), ("flags", C.c_uint32), ("children", C.c_uint32), ("environment", C.c_uint32),
                 ("out_capacity_lo", C.c_uint32), ("out_capacity_hi", C.c_uint32), ("reserved", C.c_uint32 * 6),
                 ("d_out_octants", C.c_void_p)]
+
+
+class LevelLightsPathDesc(C.Structure):
+    """mr_level_lights_path_desc (miro_hip_frame.h): one level of a PATH_TRACING build's recursion for mr_trace_level_lights_path"""
+    _fields_ = [("spp", C.c_uint32), ("flags", C.c_uint32), ("children", C.c_uint32), ("environment", C.c_uint32),
+                ("path_kinds", C.c_uint32), ("seed", C.c_uint32), ("bounce", C.c_uint32),
+                ("out_capacity_lo", C.c_uint32), ("out_capacity_hi", C.c_uint32), ("reserved", C.c_uint32 * 5),
+                ("d_out_octants", C.c_void_p), ("d_lowres", C.c_void_p), ("d_out_lowres", C.c_void_p)]
 
 
 class Material(C.Structure):
@@ -304,6 +312,7 @@ def load_library(path=None):
     L.mr_gen_path_rays.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
     L.mr_trace_level.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mr_trace_level_lights.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mr_trace_level_lights_path.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mr_final_gather.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.mr_trace_photons.argtypes = [vp, vp, C.POINTER(PhotonTraceDesc), C.POINTER(PhotonTraceResult), vp, C.c_uint64, vp]
     L.mr_trace_photons_surface.argtypes = L.mr_trace_photons.argtypes
@@ -706,6 +715,30 @@ class Scene:
                                             _ptr(d_hits), _ptr(d_ray_rgb), _ptr(d_color), _ptr(d_normal), _ptr(d_out_rays),
                                             _ptr(d_out_weights), _ptr(d_out_pixels), _ptr(d_out_count), _ptr(d_counts),
                                             _stream_ptr(stream)))
+
+    def trace_level_lights_path(self, d_rays, d_weights, d_pixels, d_ids, n, d_rgb, children=MR_LEVEL_LAST, environment=False,
+                                d_hits=None, d_ray_rgb=None, d_color=None, d_normal=None, d_out_rays=None, d_out_weights=None,
+                                d_out_pixels=None, d_out_ids=None, d_out_count=None, d_counts=None, spp=1, flags=0, seed=168, bounce=0,
+                                kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE, stream=None, out_capacity=None,
+                                d_out_octants=None, d_lowres=None, d_out_lowres=None):
+        """mr_trace_level_lights_path: trace_level_lights for a PATH_TRACING build -- the same per-ray steps, then with
+        children=MR_LEVEL_PATH the children of gen_path_rays_surface (kinds, seed, bounce; d_ids / d_out_ids: the path tracer's ray
+        ids, None: the ray's index) about the bumped normal and with the looked-up colour, in the same launch.  d_lowres: uint8 per
+        ray, non-zero = the ray was made by Ray::random and a miss reads the low-res environment image (flags: MR_ENV_LOWRES for
+        all rays); d_out_lowres: uint8 per stored child, 1 for the diffuse child -- the next level's d_lowres.  d_counts: FIVE
+        words, as in trace_level_lights."""
+        ld = LevelLightsPathDesc()
+        ld.spp, ld.flags, ld.children, ld.environment = spp, flags, children, 1 if environment else 0
+        ld.path_kinds, ld.seed, ld.bounce = kinds, seed, bounce
+        if out_capacity is None:
+            outs = [t for t in (d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_lowres) if t is not None]
+            out_capacity = min(t.shape[0] for t in outs) if outs else 0
+        ld.out_capacity_lo, ld.out_capacity_hi = out_capacity & 0xFFFFFFFF, out_capacity >> 32
+        ld.d_out_octants, ld.d_lowres, ld.d_out_lowres = _ptr(d_out_octants), _ptr(d_lowres), _ptr(d_out_lowres)
+        _check(self.L.mr_trace_level_lights_path(self.h, C.byref(ld), d_rays.data_ptr(), _ptr(d_weights), _ptr(d_pixels), _ptr(d_ids), n,
+                                                 _ptr(d_rgb), _ptr(d_hits), _ptr(d_ray_rgb), _ptr(d_color), _ptr(d_normal),
+                                                 _ptr(d_out_rays), _ptr(d_out_weights), _ptr(d_out_pixels), _ptr(d_out_ids),
+                                                 _ptr(d_out_count), _ptr(d_counts), _stream_ptr(stream)))
 
     def deinterleave_bands(self, d_recv, d_full, W, H, band_rows, world, shard_rows, floats_per_pixel=3, stream=None):
         _check(self.L.mr_deinterleave_bands(self.h, d_recv.data_ptr(), d_full.data_ptr(), W, H, band_rows, world, shard_rows,

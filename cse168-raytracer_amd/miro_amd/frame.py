@@ -217,15 +217,17 @@ class FusedFrame:
         return int(c[3]) // max(steps, 1), int(c[4]) // max(steps, 1)
 
 
-class Queue(collections.namedtuple("Queue", "rays weights pixels ids octs n")):
+class Queue(collections.namedtuple("Queue", "rays weights pixels ids octs n low", defaults=(None,))):
     """One level's rays in render_specular: weights and pixels (None: the eye rays, weight 1 and pixel = ray index // spp),
-    the path tracer's ray ids and the octant bytes (None where the plan has none), and the number of rays."""
+    the path tracer's ray ids and the octant bytes (None where the plan has none), the number of rays, and (fused="lights_path"
+    only) one byte per ray that is non-zero for a ray made by Ray::random."""
     __slots__ = ()
 
     def first(self, n):
         """the leading n rays of freshly generated children"""
-        rays, weights, pixels, ids, octs, _ = self
-        return Queue(rays[:n], weights[:n], pixels[:n], ids if ids is None else ids[:n], octs if octs is None else octs[:n], n)
+        rays, weights, pixels, ids, octs, _, low = self
+        return Queue(rays[:n], weights[:n], pixels[:n], ids if ids is None else ids[:n], octs if octs is None else octs[:n], n,
+                     low if low is None else low[:n])
 
 
 NO_QUEUE = Queue(None, None, None, None, None, 0)
@@ -237,7 +239,7 @@ class LevelPlan(collections.namedtuple("LevelPlan", (
     """What FrameRenderer.render_specular decides once per call, from its arguments and the scene's state (_resolve):
     stream: the torch Stream of every launch, None for the current one; flags: the renderer's trace flags;
     fused: False / True / "auto", already False on a scene with a texture table, or "lights" (every level is one
-    mr_trace_level_lights, on any scene);
+    mr_trace_level_lights, on any scene) or "lights_path" (every level is one mr_trace_level_lights_path: path tracing);
     path_tracing, path_kinds (never None), fan (children per ray, at most), path_seed, group_octants: as given;
     lights: the scene's light list shades, not the description's point light; environment: misses are shaded, after the
     first level with env_lowres (MR_ENV_LOWRES or 0);
@@ -464,7 +466,14 @@ class FrameRenderer:
         writes the level's hit records, and bumped normals on a procedural scene, and mr_gather_level follows it), and raises
         ValueError with path_tracing, square lights, group_octants or surface_children=True.  The same rays, children and counts;
         the pixel sums differ by the order of the float atomics.  Opt-in: fused="auto" never chooses it (a level whose rays rarely
-        hit runs its light loop at that lane utilisation; DESIGN section 5c has the times)."""
+        hit runs its light loop at that lane utilisation; DESIGN section 5c has the times).
+        fused="lights_path": the same for a PATH_TRACING build: every level is ONE launch of mr_trace_level_lights_path, whose
+        children are those of mr_gen_path_rays_surface (about the bumped normal, the diffuse child with the looked-up colour) --
+        the batched path with surface_children=True.  It needs lights=[...] and path_tracing=True, takes environment=,
+        photon_maps=, path_seed and path_kinds, and raises ValueError with square lights, group_octants or surface_children=False.
+        Its queues carry the ray ids and, with an environment, one byte per ray that marks the children of Ray::random: a miss
+        of such a ray reads the low-res image, so an environment IMAGE with MR_PATH_DIFFUSE mixed with other kinds is accepted
+        on this route.  Opt-in as well."""
         plan = self._resolve(stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights, environment, photon_maps,
                              nphotons, max_dist, surface_children)
         # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
@@ -478,7 +487,8 @@ class FrameRenderer:
                     break
                 one_launch = plan.fused is True or (plan.fused == "auto" and
                                                     (level == 0 or per_level[-1][1] >= 0.9 * per_level[-1][0]))
-                step = self._level_lights if plan.fused == "lights" else self._level_fused if one_launch else self._level_batched
+                step = self._level_lights if plan.fused == "lights" else self._level_lights_path if plan.fused == "lights_path" else \
+                    self._level_fused if one_launch else self._level_batched
                 counts, queue = step(plan, queue, level, level == depth)
                 per_level.append(counts)
             self._untile(stream)
@@ -490,6 +500,21 @@ class FrameRenderer:
         (set_environment, set_lights) between them"""
         sc = self.scene
         level_lights = isinstance(fused, str) and fused == "lights"
+        level_path = isinstance(fused, str) and fused == "lights_path"
+        if level_path:
+            if lights is None:
+                raise ValueError("render_specular: fused=\"lights_path\" needs lights=[...] (mr_trace_level_lights_path shades by the "
+                                 "scene's light list)")
+            if not path_tracing:
+                raise ValueError("render_specular: fused=\"lights_path\" needs path_tracing=True (the specular children are "
+                                 "fused=\"lights\")")
+            refused = [("square lights", self.square_lights), ("group_octants", group_octants),
+                       ("surface_children=False", surface_children is False)]
+            for what, given in refused:
+                if given:
+                    raise ValueError("render_specular: %s needs the batched path, not fused=\"lights_path\" (mr_trace_level_lights_path "
+                                     "emits the children of mr_gen_path_rays_surface and shades point and disc lights only)" % what)
+            fused = False                       # the checks below speak of mr_trace_level; the plan carries "lights_path"
         if level_lights:
             if lights is None:
                 raise ValueError("render_specular: fused=\"lights\" needs lights=[...] (mr_trace_level_lights shades by the scene's light list)")
@@ -525,7 +550,7 @@ class FrameRenderer:
             has_image = sc.get_environment(0)[0] is not None
             kinds = binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT if path_kinds is None else path_kinds
             diffuse_children = path_tracing and bool(kinds & binding.MR_PATH_DIFFUSE)
-            if has_image and diffuse_children and kinds != binding.MR_PATH_DIFFUSE:
+            if has_image and diffuse_children and kinds != binding.MR_PATH_DIFFUSE and not level_path:
                 raise ValueError("render_specular: an environment image with MR_PATH_DIFFUSE mixed with other kinds "
                                  "(the queue does not record which child came from Ray::random)")
             if diffuse_children and kinds == binding.MR_PATH_DIFFUSE:
@@ -543,7 +568,8 @@ class FrameRenderer:
             raise TypeError("render_specular: pass a torch.cuda.Stream (or None for the current stream), not a raw handle")
         # square lights on a texture table of any kind read the surface pass's buffers (mr_shade_square_lights refuses the table)
         square = None if not self.square_lights else "surface" if sc.n_textures else "plain"
-        return LevelPlan(stream=stream, flags=self.flags, fused="lights" if level_lights else fused, path_tracing=path_tracing,
+        return LevelPlan(stream=stream, flags=self.flags, fused="lights" if level_lights else "lights_path" if level_path else fused,
+                         path_tracing=path_tracing,
                          path_kinds=binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT if path_kinds is None else path_kinds,
                          fan=4 if path_tracing else 3, path_seed=path_seed, group_octants=group_octants, lights=lights is not None,
                          environment=environment, env_lowres=env_lowres, surface=surface, square=square,
@@ -593,6 +619,32 @@ class FrameRenderer:
                               d_hits=hits, d_normal=normal, d_out_rays=out.rays, d_out_weights=out.weights, d_out_pixels=out.pixels,
                               d_out_count=None if last else cnts[5:], d_counts=cnts[:5], spp=self.spp,
                               flags=plan.level_flags(level)[2], stream=stream)
+        if plan.photon_maps is not None:
+            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), self.d_slots,
+                            d_normal=normal, d_weights=q.weights, d_pixels=q.pixels, max_dist=plan.max_dist,
+                            nphotons=plan.nphotons, spp=self.spp, stream=stream)
+        host = cnts.tolist()
+        return (n, host[1]), None if last else out.first(host[5])
+
+    def _level_lights_path(self, plan, q, level, last):
+        """One level as ONE launch of mr_trace_level_lights_path (then mr_gather_level, with photon maps); returns (rays, shadow
+        rays) and the next queue (None after the last).  With an environment the children carry their low-res byte."""
+        sc, n, stream = self.scene, q.n, plan.stream
+        f32 = dict(dtype=torch.float32, device=self.device)
+        hits = normal = None
+        if plan.photon_maps is not None:                # the photon term reads the level's hit records (and bumped normals)
+            hits = self.d_hits if level == 0 else torch.empty((n, 4), **f32)
+            normal = torch.empty((n, 3), **f32) if plan.surface else None
+        cnts = torch.zeros(6, dtype=torch.int64, device=self.device)        # the call's five counters, children
+        out = NO_QUEUE if last else self._children(plan, n)
+        if not last and plan.environment:
+            out = out._replace(low=torch.empty(out.n, dtype=torch.uint8, device=self.device))
+        sc.trace_level_lights_path(q.rays, q.weights, q.pixels, q.ids, n, self.d_slots,
+                                   children=binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_PATH, environment=plan.environment,
+                                   d_hits=hits, d_normal=normal, d_out_rays=out.rays, d_out_weights=out.weights,
+                                   d_out_pixels=out.pixels, d_out_ids=out.ids, d_out_count=None if last else cnts[5:],
+                                   d_counts=cnts[:5], spp=self.spp, flags=plan.level_flags(level)[2], seed=plan.path_seed, bounce=level,
+                                   kinds=plan.path_kinds, stream=stream, d_lowres=q.low, d_out_lowres=out.low)
         if plan.photon_maps is not None:
             sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), self.d_slots,
                             d_normal=normal, d_weights=q.weights, d_pixels=q.pixels, max_dist=plan.max_dist,

@@ -87,6 +87,60 @@ mr_status mr_trace_level_lights(mr_scene *scene, const mr_level_lights_desc *lev
                                 mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
                                 uint64_t *d_out_count, uint64_t *d_counts, void *stream);
 
+/* ---- ... of a PATH_TRACING build: the same level with the path tracer's children and the low-res environment image ----------
+ * mr_trace_level_lights stops at the specular children.  This call takes its queue plus what the path tracer's queues carry --
+ * d_ids, stable ray ids (NULL: the ray's index, as in mr_gen_path_rays), and one byte per ray that says whether Ray::random made
+ * it (level->d_lowres, optional) -- and handles ray k in one lane:
+ *   1. Scene::trace, closest hit; d_hits[k], if given, is that record.
+ *   2. A miss: L = Scene::getEnvironmentMap(ray) with environment == 1 -- bg_color, or LoadedTexture::lookup of the image at the
+ *      ray's direction: the FULL-RESOLUTION image, or lowresLookup2D of its low-res copy for a ray that is isDiffuse
+ *      (Scene.cpp:678-681): d_lowres[k] != 0, or every ray of the queue with MR_ENV_LOWRES -- otherwise 0.  A lookup the
+ *      reference leaves undefined is 0 and counted, in either image.
+ *   3. - 5. as in mr_trace_level_lights: the surface step (rows k of d_color / d_normal, if given), the loop over the light list,
+ *      d_ray_rgb[k] = L, weight * L / spp added to d_rgb[pixel].
+ *   6. With children == MR_LEVEL_PATH the children of mr_gen_path_rays_surface go to the output queue: of the kinds in path_kinds
+ *      (MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE) that the hit's MATERIAL has, lobe-sampled with the random numbers of
+ *      (seed, ray id, bounce, kind), every one about the normal of step 3 -- the bumped one on stone -- and the diffuse child with
+ *      weight x the looked-up colour of step 3.  d_out_ids (optional) receives the child ids mr_gen_path_rays derives;
+ *      d_out_lowres (optional), one byte per STORED child, is 1 for the child of Ray::random and 0 otherwise: the next level's
+ *      d_lowres.  Capacity rule (a child whose slot lies beyond out_capacity is counted, not stored: none of its outputs is
+ *      written), d_out_count (zeroed by the call, then += children, stored or not) and d_out_octants are mr_trace_level's.
+ * d_counts: FIVE words as in mr_trace_level_lights: [0] += rays, [1] += shadow rays, [2] += undefined texture lookups,
+ *   [3] += misses, [4] += undefined environment lookups.
+ * flags: MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_ENV_LOWRES only.  n == 0 is MR_OK and launches nothing, after zeroing
+ *   d_out_count on a level with children.
+ * Uploads and graph capture: mr_trace_level_lights' rule -- after the first call the call is the zeroing of d_out_count (with
+ *   children; a one-word kernel) plus one kernel.
+ *
+ * The contract.  Per ray, on the same queue, seed, bounce and kinds, the outputs are those of the batched
+ *   mr_trace -> mr_hit_surface -> mr_shade_lights_surface(d_ray_rgb) || mr_shade_environment(d_ray_rgb, the same flags and
+ *   d_lowres) -> mr_gen_path_rays_surface(that chain's colour and normal)
+ * bit for bit: hit records, colour, normal, L (the light chain's row where the ray hit, the environment chain's where it
+ * missed), the five counters; the children are the same set -- ray, weight, pixel, id and octant of every child id -- in another
+ * order, d_out_count is equal; d_rgb differs by the order of the float atomics.  On a scene without a texture table and with
+ * path_kinds = MR_PATH_MIRROR | MR_PATH_REFRACT the children are mr_gen_path_rays' set.
+ * Errors.  MR_ERR_INVALID from the arguments alone, before the scene's state is read and before any device call: NULL scene /
+ *   level / d_rays; d_rgb and d_ray_rgb both NULL; spp == 0; other flags; children == MR_LEVEL_SPECULAR (those are
+ *   mr_trace_level_lights') or unknown; environment > 1; with children, path_kinds 0 or with unknown bits; non-zero reserved
+ *   words; children without an output queue or capacity; misalignment (rays and out rays 16 bytes, counters 8, float, index and
+ *   id buffers 4; the byte masks and octants may lie anywhere).  MR_ERR_STATE: a scene that is unbuilt, built host_only, or has
+ *   no lights.  Square lights and the thin lens are not part of this call. */
+typedef struct mr_level_lights_path_desc {
+    uint32_t spp, flags, children;       /* children: MR_LEVEL_LAST or MR_LEVEL_PATH */
+    uint32_t environment;                /* 0: a miss is worth 0.  1: Scene::getEnvironmentMap of mr_scene_set_environment */
+    uint32_t path_kinds, seed, bounce;   /* as in mr_gen_path_rays; read with children == MR_LEVEL_PATH */
+    uint32_t out_capacity_lo, out_capacity_hi;
+    uint32_t reserved[5];                /* must be 0 */
+    uint8_t *d_out_octants;              /* may be NULL, as in mr_level_desc */
+    const uint8_t *d_lowres;             /* may be NULL: per ray, non-zero = the ray is isDiffuse */
+    uint8_t *d_out_lowres;               /* may be NULL: per stored child, 1 = made by Ray::random */
+} mr_level_lights_path_desc;
+mr_status mr_trace_level_lights_path(mr_scene *scene, const mr_level_lights_path_desc *level, const mr_ray *d_rays,
+                                     const float *d_weights, const uint32_t *d_pixels, const uint32_t *d_ids, uint64_t n,
+                                     float *d_rgb, mr_hit *d_hits, float *d_ray_rgb, float *d_color, float *d_normal,
+                                     mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids,
+                                     uint64_t *d_out_count, uint64_t *d_counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
