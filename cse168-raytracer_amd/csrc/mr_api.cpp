@@ -1221,9 +1221,10 @@ static mr_status environment_params(mr_scene *s, hipStream_t stream, EnvParams &
 // What mr_render_lights and mr_render_lights_surface ask of their arguments and of the scene, in this order; `fd`: the
 // descriptor as the launchers take it (band_world >= 1).  surface_misaligned: one of the buffers that the _surface call takes
 // besides is; refuse_table: the call shades without the lookup.
-static mr_status check_render_lights(const char *who, mr_scene *s, const mr_frame_desc *frame, mr_frame_desc &fd, const float *d_rgb,
-                                     const mr_hit *d_hits, const float *d_sample_rgb, bool surface_misaligned, const uint64_t *d_counts,
-                                     bool refuse_table) {
+// (the two halves: what the arguments alone can get wrong; then the scene's state.  mr_render_level_lights puts its own
+// argument checks between them)
+static mr_status check_render_lights_args(const char *who, mr_scene *s, const mr_frame_desc *frame, mr_frame_desc &fd, const float *d_rgb,
+                                          const mr_hit *d_hits, const float *d_sample_rgb, bool surface_misaligned, const uint64_t *d_counts) {
     if (!s || !frame || !d_rgb) return fail(MR_ERR_INVALID, "%s: NULL argument", who);
     if (frame->W == 0 || frame->H == 0) return fail(MR_ERR_INVALID, "%s: empty image", who);
     fd = *frame;
@@ -1233,7 +1234,11 @@ static mr_status check_render_lights(const char *who, mr_scene *s, const mr_fram
     if ((reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
         (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_sample_rgb) & 3) || surface_misaligned)
         return fail(MR_ERR_INVALID, "%s: the hit buffer must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned", who);
-    if ((st = require_device(s)) != MR_OK) return st;
+    return MR_OK;
+}
+static mr_status check_render_lights_state(const char *who, mr_scene *s, const mr_frame_desc &fd, bool refuse_table) {
+    const mr_status st = require_device(s);
+    if (st != MR_OK) return st;
     if (s->lights.empty()) return fail(MR_ERR_STATE, "%s: the scene has no lights (mr_scene_set_lights)", who);
     if (refuse_table && !s->tex.blob.empty())
         return fail(MR_ERR_STATE, "%s: the scene has a texture table (mr_scene_set_textures) and this call shades without "
@@ -1242,6 +1247,12 @@ static mr_status check_render_lights(const char *who, mr_scene *s, const mr_fram
     if ((fd.flags & MR_TRACE_ANY) && s->dev.refractive)
         return fail(MR_ERR_STATE, "%s: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)", who);
     return MR_OK;
+}
+static mr_status check_render_lights(const char *who, mr_scene *s, const mr_frame_desc *frame, mr_frame_desc &fd, const float *d_rgb,
+                                     const mr_hit *d_hits, const float *d_sample_rgb, bool surface_misaligned, const uint64_t *d_counts,
+                                     bool refuse_table) {
+    const mr_status st = check_render_lights_args(who, s, frame, fd, d_rgb, d_hits, d_sample_rgb, surface_misaligned, d_counts);
+    return st != MR_OK ? st : check_render_lights_state(who, s, fd, refuse_table);
 }
 
 mr_status mr_render_lights(mr_scene *s, const mr_frame_desc *frame, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
@@ -1400,6 +1411,63 @@ mr_status mr_trace_level_lights_path(mr_scene *s, const mr_level_lights_path_des
                                     d_ids, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights, d_out_pixels,
                                     d_out_ids, reinterpret_cast<unsigned long long *>(d_out_count),
                                     reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+}
+
+// The level-0 frame that also emits the rays of level 1 (mr_frame_level_lights.hip).  The frame call's argument checks under this
+// call's name, then the level calls' in their order, all before the scene's state is read; then the state and the uploads of
+// mr_render_lights_environment.  MR_LEVEL_LAST is that frame itself.
+mr_status mr_render_level_lights(mr_scene *s, const mr_frame_desc *frame, const mr_frame_level_desc *level, float *d_rgb, mr_hit *d_hits,
+                                 float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, mr_ray *d_out_rays,
+                                 float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, uint64_t *d_out_count,
+                                 uint64_t *d_counts, void *stream) {
+    const char *who = "mr_render_level_lights";
+    mr_frame_desc fd;
+    mr_status st = check_render_lights_args(who, s, frame, fd, d_rgb, d_hits, d_sample_rgb,
+                                            (reinterpret_cast<uintptr_t>(d_sample_color) & 3) || (reinterpret_cast<uintptr_t>(d_sample_normal) & 3),
+                                            d_counts);
+    if (st != MR_OK) return st;
+    if (!level) return fail(MR_ERR_INVALID, "%s: NULL argument (level)", who);
+    if (fd.flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT))
+        return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT only (the shadow rays are closest-hit, as in "
+                                    "mr_trace_level_lights)", who);
+    if (level->children != MR_LEVEL_LAST && level->children != MR_LEVEL_SPECULAR && level->children != MR_LEVEL_PATH)
+        return fail(MR_ERR_INVALID, "%s: children must be MR_LEVEL_LAST, MR_LEVEL_SPECULAR or MR_LEVEL_PATH", who);
+    if (level->environment > 1) return fail(MR_ERR_INVALID, "%s: environment must be 0 or 1", who);
+    if (level->children == MR_LEVEL_PATH && (level->path_kinds == 0 || (level->path_kinds & ~7u)))
+        return fail(MR_ERR_INVALID, "%s: path_kinds must be a combination of MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE", who);
+    for (int k = 0; k < 6; k++)
+        if (level->reserved[k] != 0) return fail(MR_ERR_INVALID, "%s: mr_frame_level_desc.reserved must be 0", who);
+    const bool children = level->children != MR_LEVEL_LAST;
+    if (children) {
+        if (!d_out_rays || !d_out_weights || !d_out_pixels || !d_out_count)
+            return fail(MR_ERR_INVALID, "%s: a frame with children needs the output queue", who);
+        unsigned long long n = 0;
+        if ((st = frame_level_lights_samples(who, fd, n)) != MR_OK) return st;
+        if (n > 0 && level->out_capacity_lo == 0 && level->out_capacity_hi == 0)
+            return fail(MR_ERR_INVALID, "%s: out_capacity is 0 (room for %u rays per sample always suffices)", who,
+                        level->children == MR_LEVEL_PATH ? 4u : 3u);
+        if (n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 samples per call with children", who);
+        if ((reinterpret_cast<uintptr_t>(d_out_rays) & 15) || (reinterpret_cast<uintptr_t>(d_out_count) & 7) ||
+            (reinterpret_cast<uintptr_t>(d_out_weights) & 3) || (reinterpret_cast<uintptr_t>(d_out_pixels) & 3) ||
+            (reinterpret_cast<uintptr_t>(d_out_ids) & 3))
+            return fail(MR_ERR_INVALID, "%s: the output rays must be 16-byte aligned, d_out_count 8-byte, weights, pixels and ids "
+                                        "4-byte aligned", who);
+    }
+    if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    TexParams tex;
+    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
+    if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+    EnvParams env = EnvParams{};
+    if (level->environment && (st = environment_params(s, static_cast<hipStream_t>(stream), env)) != MR_OK) return st;
+    if (!children)
+        return launch_frame_lights_env(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
+                                       d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts),
+                                       static_cast<hipStream_t>(stream));
+    return launch_frame_level_lights(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), fd, *level, d_rgb, d_hits,
+                                     d_sample_rgb, d_sample_color, d_sample_normal, d_out_rays, d_out_weights, d_out_pixels, d_out_ids,
+                                     reinterpret_cast<unsigned long long *>(d_out_count), reinterpret_cast<unsigned long long *>(d_counts),
+                                     static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_gen_eye_rays_lens(mr_scene *s, const mr_camera *cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp,
@@ -1654,7 +1722,10 @@ mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, ui
             if (material_texture[i] != kNoTexture && material_texture[i] >= n_textures)
                 return fail(MR_ERR_INVALID, "material %u names texture %u of %u", i, material_texture[i], n_textures);
     // a bump-mapped material is diffuse only, as the reference's own are (assignment1.cpp:232,313): the reflect / refract
-    // generators and the light through a refractive occluder (Phong.cpp:99-113) work on the un-bumped N
+    // generators and the light through a refractive occluder (Phong.cpp:99-113) work on the un-bumped N.
+    // mr_render_level_lights RESTS on this rule (and on mr_scene_set_materials being refused while a table is set): its specular
+    // children bounce about the normal of the surface step, which is the object's own on every material but STONE
+    // (mr_frame_lights_surface_body.h, the children step).  Whoever relaxes the rule gives that kernel the hit record back.
     if (material_texture)
         for (uint32_t i = 0; i < n_mats; i++) {
             if (material_texture[i] == kNoTexture || textures[material_texture[i]].kind != MR_TEX_STONE) continue;

@@ -11,6 +11,18 @@
 // Colour or image is a wave-uniform branch on env.full.  Two counters more: live samples that missed, undefined lookups.
 // With ENV false nothing of `env` is read and the code is the kernel's as it stood (the figures of
 // tests/golden/kernel_budget_frame_lights_surface.json hold).  The arguments are taken BY VALUE (mr_lights_body.h says why).
+// CHILDREN says whether the frame, being level 0 of Scene::traceScene's recursion, also emits the rays of level 1
+// (mr_frame_level_lights.hip, mr_render_level_lights):
+//   0  none: the two frames above; nothing of FrameChildArgs is read and the code is what it was (their records hold)
+//   1  the reflect / Fresnel / refract children of mr_level_lights.hip's last step: rec::ChildGen<false>, rec::write_children,
+//      about the object's own normal -- which is taken from the surface step, not computed again from the hit record: the step
+//      bumps the normal on a STONE material only, and such a material has no specular child (the children step says on what
+//      that rests)
+//   2  the PATH_TRACING children of mr_level_lights_path.hip's last step: rec::ChildGen<true> about the normal of the surface
+//      step (the bumped one on stone), the diffuse child with the looked-up colour, write_children_col -- the bumped normal and
+//      the colour are the light loop's own
+// In both the ray's origin is the eye, its path weight 1, its pixel row * W + x of this call's d_rgb, and (2) its id the sample
+// index in the launch's own order.  The step stands between the surface step and the light loop, where all it reads is at hand.
 // Included by the .hip units that instantiate it (everything here is local to its unit).
 #pragma once
 
@@ -20,11 +32,13 @@
 #include "mr_eye.h"
 #include "mr_frame_window.h"
 #include "mr_hit_surface_body.h"
+#include "mr_children_col.h"
 #include "mr_internal.h"
 #include "mr_launch.h"
 #include "mr_light_loop.h"
 #include "mr_noise.h"
 #include "mr_phong.h"
+#include "mr_recursion.h"
 #include "mr_surface.h"
 #include "mr_tile.h"
 #include "mr_traverse.h"
@@ -68,10 +82,18 @@ inline mr_status fill_frame_lights_surface_args(FrameLightsSurfaceArgs &a, const
     return MR_OK;
 }
 
+// the queue of level 1 (CHILDREN != 0)
+struct FrameChildArgs {
+    ChildQueue out;
+    uint8_t *out_lowres;         // CHILDREN == 2, optional: per stored child, 1 for the child of Ray::random (kind 3), 0 otherwise
+    uint32_t kinds, hbase;       // CHILDREN == 2: MR_PATH_* wanted, pcg32(path seed)
+};
+
 // VAR, ANY: as in frame_lights_kernel.  s_stack: the workgroup's dynamic LDS, [stack_depth][kTraceBlock]; s_tab: 128 words of
 // static LDS for the two noise tables.
-template <int VAR, bool ANY, bool ENV>
-__device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfaceArgs a, const EnvParams env, int *s_stack, uint32_t (&s_tab)[128]) {
+template <int VAR, bool ANY, bool ENV, int CHILDREN>
+__device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfaceArgs a, const EnvParams env, const FrameChildArgs &ch, int *s_stack,
+                                                          uint32_t (&s_tab)[128]) {
     const NoiseTables nt = stage_noise_tables(s_tab);
     const int tid = threadIdx.x;
     const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
@@ -82,7 +104,8 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
     Stats st = {0ull, 0ull};
     unsigned my_shadow_rays = 0, my_undefined = 0, my_misses = 0, my_env_undefined = 0;
 
-    // whole workgroups run every iteration (n_round): the traversals and the butterfly are called by whole waves
+    // whole workgroups run every iteration (n_round): the traversals, the butterfly and (CHILDREN) write_children are called
+    // by whole waves
     for (unsigned long long idx = (unsigned long long)xcd_block_id() * kTraceBlock + tid; idx < n_round; idx += stride) {
         const bool live = idx < n;
         uint32_t x = 0, row = 0, y = 0, sm = 0;
@@ -123,6 +146,42 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
             eye_sample_of(a.eye, idx, x, row, y, sm);
             eye_ray_of(a.eye, x, y, sm, ra, rb);
             d[0] = rb.x; d[1] = rb.y; d[2] = rb.z;
+        }
+
+        // ---- the rays of level 1 (Scene.cpp:302-336): the last step of level_lights_kernel / level_lights_path_kernel for a ray
+        // that starts at the eye with weight 1.  It stands HERE, before the light loop, not after the pixel's mean where the level
+        // kernels have it: everything it reads is at hand (x and row are the sample's, computed just above), the children are a
+        // set whose order is not part of the contract, and nothing of it -- the queue's arguments, the generators' state -- then
+        // lives across the shadow traversals, where the registers are scarcest.  A lane past the end of the window has no pixel
+        // and no children
+        if (CHILDREN != 0) {
+            const uint32_t pix = (ENV ? live : hit) ? row * a.eye.W + x : 0xFFFFFFFFu;
+            ChildGen<CHILDREN == 2> g;
+            bool emit[4] = {false, false, false, false};
+            if (hit) {
+                g.mt = mt;
+                const bool refl = any_pos(g.mt + 3) && (CHILDREN == 1 || (ch.kinds & 1u));
+                const bool refr = any_pos(g.mt + 6) && (CHILDREN == 1 || (ch.kinds & 2u));
+                const bool diff = CHILDREN == 2 && any_pos(g.mt) && (ch.kinds & 4u);
+                if (refl || refr || diff) {
+                    // The hit point and the normal of the surface step, not rebuilt from the hit record.  P is surface_od's for this very ray and record: the bits
+                    // surface_point_od(eye, d, h) gives the level kernels.  N is normalize3 of surface_od's normal, bumped before
+                    // on a STONE material only (hit_color_normal): what CHILDREN == 2 asks for; and for CHILDREN == 1, whose
+                    // children bounce about the object's own normal, the same bits wherever a child exists -- a material that
+                    // names a STONE texture has ks = kt = 0 (mr_scene_set_textures refuses any other, and mr_scene_set_materials
+                    // is refused while a table is set; both in mr_api.cpp, which names this dependence), and on every other hit
+                    // N is surface_point_od's normalize3 of the same three values.
+                    for (int c = 0; c < 3; c++) { g.P[c] = P[c]; g.N[c] = N[c]; }
+                    g.d[0] = d[0]; g.d[1] = d[1]; g.d[2] = d[2];
+                    g.w0[0] = 1.f; g.w0[1] = 1.f; g.w0[2] = 1.f;
+                    if (CHILDREN == 2) g.hray = pcg32(ch.hbase ^ (uint32_t)idx);               // bounce 0
+                    g.plan(refl, refr, diff, emit);
+                }
+            }
+            if constexpr (CHILDREN == 2)
+                write_children_col<kTraceBlock>(ch.out, ch.out_lowres, g, col, emit, pix, (uint32_t)idx);
+            else
+                write_children<kTraceBlock, false>(ch.out, g, emit, pix, 0u);
         }
 
         // ---- Phong::shade over the light list (shade_light_list, mr_light_loop.h: shade_lights_body's loop with kColorSurface); a miss contributes nothing (m_bgColor = 0)
@@ -170,6 +229,13 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
         }
         if (blockIdx.x == 0 && tid == 0) atomicAdd(&a.counts[0], n);
     }
+}
+
+// the two frames that stop at level 0
+template <int VAR, bool ANY, bool ENV>
+__device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfaceArgs a, const EnvParams env, int *s_stack, uint32_t (&s_tab)[128]) {
+    const FrameChildArgs none = {};
+    frame_lights_surface_body<VAR, ANY, ENV, 0>(a, env, none, s_stack, s_tab);
 }
 
 }  // namespace

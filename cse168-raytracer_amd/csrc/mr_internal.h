@@ -324,6 +324,17 @@ mr_status launch_level_lights_path(const DeviceScene &ds, const TexParams &tex, 
                                    float *d_ray_rgb, float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights,
                                    uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_out_count,
                                    unsigned long long *d_counts, hipStream_t stream);
+// the level-0 frame that also emits the rays of level 1 (mr_frame_level_lights.hip, mr_render_level_lights): launch_frame_lights_env's
+// frame (env all zero: a miss is worth 0) with the children of launch_level_lights (ld.children == MR_LEVEL_SPECULAR) or
+// launch_level_lights_path (MR_LEVEL_PATH; bounce 0, ids = sample indices) for rays that start at the eye with weight 1 and pixel
+// row * W + x; d_out_count is zeroed on `stream` (a one-word kernel), then one kernel (none for an empty window).
+// frame_level_lights_samples: the samples of fd's window, from the descriptor alone (no device call)
+mr_status frame_level_lights_samples(const char *who, const mr_frame_desc &fd, unsigned long long &n);
+mr_status launch_frame_level_lights(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
+                                    uint32_t n_lights, const mr_frame_desc &fd, const mr_frame_level_desc &ld, float *d_rgb, mr_hit *d_hits,
+                                    float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, mr_ray *d_out_rays,
+                                    float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_out_count,
+                                    unsigned long long *d_counts, hipStream_t stream);
 
 // the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
 // square light, side * side shadow rays per hit and light

@@ -37,6 +37,7 @@
 // d_out_count is zeroed by a one-word kernel of this unit, not a memset node (mr_level_lights.hip says why).
 #include <hip/hip_runtime.h>
 
+#include "mr_children_col.h"
 #include "mr_environment_body.h"
 #include "mr_hit_surface_body.h"
 #include "mr_internal.h"
@@ -82,52 +83,8 @@ struct LevelLightsPathArgs {
 #define MIRO_LEVEL_LIGHTS_PATH_WAVES 4
 #endif
 
-// Scene::getEnvironmentMap's lookup of the image a ray reads (Scene.cpp:678-681): the full one, or the low-res copy for a ray
-// that is isDiffuse -- shade_environment_kernel's choice of w, h and texel source, the copy read where it lies.  false:
-// undefined, val is left as it was.
-__device__ __forceinline__ bool env_lookup(const EnvParams &env, bool low, float dx, float dy, float dz, float val[3]) {
-    const int w = low ? (int)env.lw : (int)env.W, h = low ? (int)env.lh : (int)env.H;
-    float xe = 0.f, ye = 0.f;
-    int x1 = 0, x2 = 0, y1 = 0, y2 = 0;
-    if (!env_texels(env.rot, w, h, dx, dy, dz, x1, x2, y1, y2, xe, ye)) return false;
-    const float4 *img = low ? env.low : env.full;
-    const float4 *r1 = img + (size_t)y1 * w, *r2 = img + (size_t)y2 * w;
-    env_blend(r1[x1], r1[x2], r2[x1], r2[x2], xe, ye, env.max_intensity, val);
-    return true;
-}
-
-// rec::write_children<BLOCK, true> whose diffuse child (kind 3) carries w0 * col instead of make()'s w0 * m_diffuse, the rule of
-// write_children_col_at (mr_children_body.h), and which writes the child's low-res byte with it.  Called by all threads of the
-// workgroup.
-template <int BLOCK>
-__device__ __forceinline__ void write_children_col(const ChildQueue &q, uint8_t *out_lowres, const ChildGen<true> &g, const float col[3],
-                                                   const bool emit[4], uint32_t pix, uint32_t id) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long mk[4];
-    int cn[4], tot = 0;
-    for (int j = 0; j < 4; j++) { mk[j] = __ballot(emit[j]); cn[j] = __popcll(mk[j]); tot += cn[j]; }
-    const unsigned long long base = workgroup_reserve<BLOCK>((unsigned)tot, q.count);
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    unsigned long long before = base;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const unsigned long long s = before + __popcll(mk[j] & lt);
-        if (emit[j] && s < q.capacity) {
-            float org[3], dir[3], wgt[3];
-            g.make(j, org, dir, wgt);
-            if (j == 3)
-                for (int c = 0; c < 3; c++) wgt[c] = g.w0[c] * col[c];
-            reinterpret_cast<float4 *>(q.rays)[2 * s] = make_float4(org[0], org[1], org[2], 0.0f);
-            reinterpret_cast<float4 *>(q.rays)[2 * s + 1] = make_float4(dir[0], dir[1], dir[2], 1e12f);
-            q.weights[3 * s] = wgt[0]; q.weights[3 * s + 1] = wgt[1]; q.weights[3 * s + 2] = wgt[2];
-            q.pixels[s] = pix;
-            if (q.ids) q.ids[s] = child_id(id, j);
-            if (q.octants) q.octants[s] = rec::octant_of(dir);
-            if (out_lowres) out_lowres[s] = j == 3 ? (uint8_t)1 : (uint8_t)0;
-        }
-        before += cn[j];
-    }
-}
+// env_lookup (the image a missing ray reads, full or low-res) and write_children_col (the children, the diffuse one with the
+// looked-up colour, and their low-res bytes) are mr_children_col.h: the frame that emits level 1 ends in the same step.
 
 // VAR: the traversal variant of trace_ray (mr_traverse.h) for the ray and its shadow rays; CHILDREN: 0 none, 1 path tracing.
 // The arguments are taken BY VALUE (mr_lights_body.h says why).

@@ -71,6 +71,8 @@ SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map
                    "mr_render_lights_surface"]
 # every symbol include/miro_hip_frame.h declares (fused frame calls added after that list was held at 9 names)
 FRAME_SYMBOLS = ["mr_render_lights_environment", "mr_trace_level_lights", "mr_trace_level_lights_path"]
+# every symbol include/miro_hip_render.h declares (the frame that emits the next level, added after that list was held at 3 names)
+RENDER_SYMBOLS = ["mr_render_level_lights"]
 
 
 class MiroError(RuntimeError):
@@ -136,6 +138,13 @@ class LevelLightsPathDesc(C.Structure):
                 ("path_kinds", C.c_uint32), ("seed", C.c_uint32), ("bounce", C.c_uint32),
                 ("out_capacity_lo", C.c_uint32), ("out_capacity_hi", C.c_uint32), ("reserved", C.c_uint32 * 5),
                 ("d_out_octants", C.c_void_p), ("d_lowres", C.c_void_p), ("d_out_lowres", C.c_void_p)]
+
+
+class FrameLevelDesc(C.Structure):
+    """mr_frame_level_desc (miro_hip_render.h): the children half of mr_render_level_lights"""
+    _fields_ = [("children", C.c_uint32), ("environment", C.c_uint32), ("path_kinds", C.c_uint32), ("path_seed", C.c_uint32),
+                ("out_capacity_lo", C.c_uint32), ("out_capacity_hi", C.c_uint32), ("reserved", C.c_uint32 * 6),
+                ("d_out_octants", C.c_void_p), ("d_out_lowres", C.c_void_p)]
 
 
 class Material(C.Structure):
@@ -305,6 +314,7 @@ def load_library(path=None):
     L.mr_render_lights.argtypes = [vp, C.POINTER(FrameDesc), vp, vp, vp, vp, vp]
     L.mr_render_lights_surface.argtypes = [vp, C.POINTER(FrameDesc), vp, vp, vp, vp, vp, vp, vp]
     L.mr_render_lights_environment.argtypes = L.mr_render_lights_surface.argtypes
+    L.mr_render_level_lights.argtypes = [vp, C.POINTER(FrameDesc), C.POINTER(FrameLevelDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mr_tonemap.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.mr_scene_set_materials.argtypes = [vp, C.POINTER(Material), C.c_uint32, u32p]
     L.mr_shade_accumulate.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(Light), C.c_uint32, vp, vp]
@@ -356,10 +366,10 @@ def load_library(path=None):
     L.mr_irradiance_estimate.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, vp, vp, vp, vp]
     L.mr_photon_map_count_stats.argtypes = [vp, C.c_int32]
     L.mr_photon_map_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int32]
-    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS:
+    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS:
         if not hasattr(L, name):
             raise OSError("%s does not export %s" % (path, name))
-    for name in EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS:
         if hasattr(L, name) and getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = C.c_int32
     _lib = L
@@ -805,6 +815,36 @@ class Scene:
         fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
         _check(self.L.mr_render_lights_environment(self.h, C.byref(fd), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb),
                                                    _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_counts), _stream_ptr(stream)))
+
+    def render_level_lights(self, cam, W, H, d_rgb, y0=0, y1=None, bands=None, spp=1, jitter=False, seed=168, tiled=False, flags=0,
+                            d_hits=None, d_sample_rgb=None, d_sample_color=None, d_sample_normal=None, d_counts=None, stream=None,
+                            children=MR_LEVEL_LAST, environment=False, kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE,
+                            path_seed=168, d_out_rays=None, d_out_weights=None, d_out_pixels=None, d_out_ids=None, d_out_count=None,
+                            out_capacity=None, d_out_octants=None, d_out_lowres=None):
+        """mr_render_level_lights: render_lights_environment's level-0 frame (environment=False: a miss is worth 0 and is still
+        counted) that also writes the rays of level 1 in the same launch -- with children=MR_LEVEL_SPECULAR the children
+        trace_level_lights emits, with MR_LEVEL_PATH those of trace_level_lights_path (kinds, seed=path_seed, bounce 0, ids = the
+        sample indices of the launch's order) on gen_eye_rays' queue for the same window.  A child's pixel is row * W + x of THIS
+        call's d_rgb, so a later level adds into the same buffer.  d_out_count: one int64, zeroed by the call, then += children,
+        stored or not (out_capacity, None: the shortest output buffer).  d_out_ids, d_out_lowres (uint8 per stored child, 1 = the
+        diffuse child) with MR_LEVEL_PATH.  d_counts: FIVE words, as in render_lights_environment.  flags: MR_MATH_PRODUCT,
+        MR_TRACE_INCOHERENT only.  MR_LEVEL_LAST is render_lights_environment itself."""
+        fd = FrameDesc()
+        fd.camera = cam
+        fd.W, fd.H, fd.y0, fd.y1 = W, H, y0, H if y1 is None else y1
+        fd.band_rows, fd.band_rank, fd.band_world = bands if bands is not None else (1, 0, 1)
+        fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
+        ld = FrameLevelDesc()
+        ld.children, ld.environment, ld.path_kinds, ld.path_seed = children, 1 if environment else 0, kinds, path_seed
+        if out_capacity is None:
+            outs = [t for t in (d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_lowres, d_out_octants) if t is not None]
+            out_capacity = min(t.shape[0] for t in outs) if outs else 0
+        ld.out_capacity_lo, ld.out_capacity_hi = out_capacity & 0xFFFFFFFF, out_capacity >> 32
+        ld.d_out_octants, ld.d_out_lowres = _ptr(d_out_octants), _ptr(d_out_lowres)
+        _check(self.L.mr_render_level_lights(self.h, C.byref(fd), C.byref(ld), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb),
+                                             _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_out_rays), _ptr(d_out_weights),
+                                             _ptr(d_out_pixels), _ptr(d_out_ids), _ptr(d_out_count), _ptr(d_counts),
+                                             _stream_ptr(stream)))
 
     def final_gather(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb, max_dist=1e10, nphotons=500,
                      spp=1, stream=None):

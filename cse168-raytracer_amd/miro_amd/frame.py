@@ -267,13 +267,16 @@ class FrameRenderer:
     """All device buffers of one rank's share of a frame, resident for the lifetime of the object."""
 
     def __init__(self, scene, desc, W, H, spp=1, bands=None, jitter=None, seed=168, flags=0, device=None, rgb=None,
-                 tiled=None, lens=None, square_lights=None, square_samples=1):
+                 tiled=None, lens=None, square_lights=None, square_samples=1, resident_rays=True):
         """lens: dict(aperture, focus_plane) -- generate() then makes the eye rays of the thin-lens camera
         (mr_gen_eye_rays_lens, Camera::eyeRay under -DDOF) in image order; not with tiled=True.
         square_lights: a list of SquareLights (binding.SquareLightDesc objects or dicts) that every level of render_specular's
         batched path shades IN ADDITION to its point light / light list, with square_samples shadow rays per hit and light
         (mr_shade_square_lights; level l draws its pairs with seed + l; on a scene with a texture table, procedural or not,
-        mr_hit_surface and mr_shade_square_lights_surface with the same seeds).  Without either option nothing changes."""
+        mr_hit_surface and mr_shade_square_lights_surface with the same seeds).  Without either option nothing changes.
+        resident_rays=False: the ray, hit and shadow buffers (100 bytes per sample) are not allocated; what is left serves
+        render_specular(fused="frame_lights" | "frame_lights_path") without photon maps, whose level 0 keeps its rays in
+        registers.  Every method that needs those buffers then raises ValueError."""
         if isinstance(desc, str):
             desc = scenes.SCENES[desc]
         self.scene, self.desc, self.W, self.H, self.spp = scene, desc, W, H, spp
@@ -289,11 +292,14 @@ class FrameRenderer:
         self.n = self.n_pixels * spp
         n = max(self.n, 1)
         f32 = dict(dtype=torch.float32, device=self.device)
-        self.d_rays = torch.empty((n, 8), **f32)
-        self.d_hits = torch.empty((n, 4), **f32)
-        self.d_shadow_rays = torch.empty((n, 8), **f32)
-        self.d_shadow_hits = torch.empty((n, 4), **f32)
-        self.d_src = torch.empty(n, dtype=torch.int32, device=self.device)
+        self.resident_rays = bool(resident_rays)
+        self.d_rays = self.d_hits = self.d_shadow_rays = self.d_shadow_hits = self.d_src = None
+        if self.resident_rays:
+            self.d_rays = torch.empty((n, 8), **f32)
+            self.d_hits = torch.empty((n, 4), **f32)
+            self.d_shadow_rays = torch.empty((n, 8), **f32)
+            self.d_shadow_hits = torch.empty((n, 4), **f32)
+            self.d_src = torch.empty(n, dtype=torch.int32, device=self.device)
         self.d_count = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.d_gather = None                            # final_gather's scratch, allocated on first use
         # rgb: an external [n_pixels, 3] buffer to shade into (FrameGather.local on a multi-GPU node)
@@ -320,10 +326,15 @@ class FrameRenderer:
         own = [self.d_rays, self.d_hits, self.d_shadow_rays, self.d_shadow_hits, self.d_src, self.d_count, self.d_rgb]
         if self.tiled:
             own += [self.d_slots, self.d_slot_pixel]
-        return sum(t.numel() * t.element_size() for t in own)
+        return sum(t.numel() * t.element_size() for t in own if t is not None)
+
+    def _need_rays(self, what):
+        if not self.resident_rays:
+            raise ValueError("FrameRenderer: %s needs the resident ray, hit and shadow buffers (resident_rays=True)" % what)
 
     def generate(self, stream=None):
         """Camera::eyeRay for every owned row; the rays then stay resident in HBM."""
+        self._need_rays("generate()")
         off = 0
         for y0, y1 in self.bands:
             k = (y1 - y0) * self.W * self.spp
@@ -337,13 +348,16 @@ class FrameRenderer:
             off += k
 
     def trace_primary(self, stream=None):
+        self._need_rays("trace_primary()")
         self.scene.trace_device(self.d_rays, self.n, self.d_hits, self.flags, stream=stream)
 
     def make_shadow_rays(self, stream=None):
+        self._need_rays("make_shadow_rays()")
         self.scene.gen_shadow_rays(self.d_rays, self.d_hits, self.n, self.desc["light"], self.d_shadow_rays, self.d_src,
                                    self.d_count, stream=stream)
 
     def trace_shadow(self, stream=None, any_hit=False):
+        self._need_rays("trace_shadow()")
         fl = self.flags | (binding.MR_TRACE_ANY if any_hit else 0)
         self.scene.trace_indirect(self.d_shadow_rays, self.d_count, self.n, self.d_shadow_hits, fl, stream=stream)
 
@@ -360,6 +374,7 @@ class FrameRenderer:
             off += k
 
     def shade(self, stream=None):
+        self._need_rays("shade()")
         self.scene.shade_direct(self.d_rays, self.d_hits, self.n, self.d_shadow_hits, self.d_src, self.d_count,
                                 self.desc["light"], self.desc["wattage"], self.d_slots, spp=self.spp, stream=stream)
         self._untile(stream)
@@ -367,6 +382,7 @@ class FrameRenderer:
     def final_gather(self, global_map, caustic_map=None, nphotons=500, max_dist=1e10, stream=None):
         """BASELINE config 5: the photon-map term of Scene::traceScene (Scene.cpp:285-299) for the primary hits of this
         frame, added to d_rgb after `step()`.  The scratch (48 B per ray) is allocated on first use."""
+        self._need_rays("final_gather()")
         if self.n == 0:
             return
         if self.d_gather is None:
@@ -377,6 +393,7 @@ class FrameRenderer:
 
     def step(self, stream=None, any_hit=False):
         """One pass of the hot path over this rank's resident rays: primary batch, shadow batch, shade."""
+        self._need_rays("step()")
         if self.n == 0:
             return
         self.trace_primary(stream)
@@ -389,6 +406,7 @@ class FrameRenderer:
         kernels and a memset of tens of microseconds each -- and replay as one submission.  The step must have run
         once before (the library's grow-only scratch buffers are sized outside the capture).  Returns the graph;
         `graph.replay()` re-renders into d_rgb."""
+        self._need_rays("capture()")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(device=self.device)
@@ -473,12 +491,24 @@ class FrameRenderer:
         photon_maps=, path_seed and path_kinds, and raises ValueError with square lights, group_octants or surface_children=False.
         Its queues carry the ray ids and, with an environment, one byte per ray that marks the children of Ray::random: a miss
         of such a ray reads the low-res image, so an environment IMAGE with MR_PATH_DIFFUSE mixed with other kinds is accepted
-        on this route.  Opt-in as well."""
+        on this route.  Opt-in as well.
+        fused="frame_lights" | "frame_lights_path": "lights" / "lights_path" whose level 0 is ONE mr_render_level_lights straight
+        into d_rgb -- the fused frame that also writes the rays of level 1: no generate(), no zeroing of the pixels, no eye-ray
+        buffer, no atomics at level 0 (its pixels are deterministic) and no untile pass (the children's pixels index d_rgb, in
+        image order, also with tiled=True) -- and whose levels >= 1 are mr_trace_level_lights / _path on the children, adding
+        into d_rgb.  The checks of "lights" / "lights_path", and ValueError besides for lens eye rays (the batched path), more
+        than one band range (fused="lights" / "lights_path") and photon_maps with tiled=True (tiled=False, or "lights" /
+        "lights_path").  With photon_maps (image order) generate() runs as well, for mr_gather_level's level 0; without them a
+        FrameRenderer(resident_rays=False) serves.  The same rays, children and counts per level; level 0's pixel means are
+        pairwise sums where "lights" adds atomically.  Opt-in as well: fused="auto" never chooses them."""
         plan = self._resolve(stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights, environment, photon_maps,
                              nphotons, max_dist, surface_children)
         # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
         # each other on torch's current stream, so a torch Stream is made current here
         with contextlib.nullcontext() if stream is None else torch.cuda.stream(stream):
+            if plan.fused in ("frame_lights", "frame_lights_path"):
+                return self._frame_levels(plan, depth)
+            self._need_rays("render_specular(fused=%r)" % (fused,))
             self.d_slots.zero_()
             queue = Queue(self.d_rays, None, None, None, None, self.n)      # the eye rays, in image order
             per_level = []
@@ -499,6 +529,22 @@ class FrameRenderer:
         """render_specular's arguments and the scene's state as a LevelPlan: every check, and the two scene setters
         (set_environment, set_lights) between them"""
         sc = self.scene
+        frame_route = fused if isinstance(fused, str) and fused in ("frame_lights", "frame_lights_path") else None
+        if frame_route:
+            # level 0 is mr_render_level_lights: one window of pinhole eye rays, whose children carry image-order pixels
+            level_route = frame_route[len("frame_"):]
+            if self.lens is not None:
+                raise ValueError("render_specular: lens eye rays need the batched path (fused=False), not fused=\"%s\" "
+                                 "(mr_render_level_lights makes pinhole eye rays)" % frame_route)
+            if len(self.bands) > 1:
+                raise ValueError("render_specular: more than one band range needs fused=\"%s\", not fused=\"%s\" "
+                                 "(mr_render_level_lights renders one window per call)" % (level_route, frame_route))
+            if photon_maps is not None and self.tiled:
+                raise ValueError("render_specular: photon_maps with tiled=True need fused=\"%s\" (or tiled=False), not fused=\"%s\" "
+                                 "(mr_gather_level finds level 0's pixels from the ray index, in image order)" % (level_route, frame_route))
+            if photon_maps is not None:
+                self._need_rays("render_specular(fused=\"%s\", photon_maps=...)" % frame_route)
+            fused = level_route                 # the checks of that route hold here too; the plan carries the frame route
         level_lights = isinstance(fused, str) and fused == "lights"
         level_path = isinstance(fused, str) and fused == "lights_path"
         if level_path:
@@ -568,7 +614,8 @@ class FrameRenderer:
             raise TypeError("render_specular: pass a torch.cuda.Stream (or None for the current stream), not a raw handle")
         # square lights on a texture table of any kind read the surface pass's buffers (mr_shade_square_lights refuses the table)
         square = None if not self.square_lights else "surface" if sc.n_textures else "plain"
-        return LevelPlan(stream=stream, flags=self.flags, fused="lights" if level_lights else "lights_path" if level_path else fused,
+        return LevelPlan(stream=stream, flags=self.flags,
+                         fused=frame_route if frame_route else "lights" if level_lights else "lights_path" if level_path else fused,
                          path_tracing=path_tracing,
                          path_kinds=binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT if path_kinds is None else path_kinds,
                          fan=4 if path_tracing else 3, path_seed=path_seed, group_octants=group_octants, lights=lights is not None,
@@ -603,10 +650,11 @@ class FrameRenderer:
         host = cnts.tolist()
         return (n, host[1]), None if last else out.first(host[2])
 
-    def _level_lights(self, plan, q, level, last):
+    def _level_lights(self, plan, q, level, last, rgb=None):
         """One level as ONE launch of mr_trace_level_lights (then mr_gather_level, with photon maps); returns (rays, shadow rays)
-        and the next queue (None after the last)."""
+        and the next queue (None after the last).  rgb: the pixels the level adds to (None: d_slots)."""
         sc, n, stream = self.scene, q.n, plan.stream
+        rgb = self.d_slots if rgb is None else rgb
         f32 = dict(dtype=torch.float32, device=self.device)
         hits = normal = None
         if plan.photon_maps is not None:                # the photon term reads the level's hit records (and bumped normals)
@@ -614,22 +662,24 @@ class FrameRenderer:
             normal = torch.empty((n, 3), **f32) if plan.surface else None
         cnts = torch.zeros(6, dtype=torch.int64, device=self.device)        # the call's five counters, children
         out = NO_QUEUE if last else self._children(plan, n)
-        sc.trace_level_lights(q.rays, q.weights, q.pixels, n, self.d_slots,
+        sc.trace_level_lights(q.rays, q.weights, q.pixels, n, rgb,
                               children=binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_SPECULAR, environment=plan.environment,
                               d_hits=hits, d_normal=normal, d_out_rays=out.rays, d_out_weights=out.weights, d_out_pixels=out.pixels,
                               d_out_count=None if last else cnts[5:], d_counts=cnts[:5], spp=self.spp,
                               flags=plan.level_flags(level)[2], stream=stream)
         if plan.photon_maps is not None:
-            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), self.d_slots,
+            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), rgb,
                             d_normal=normal, d_weights=q.weights, d_pixels=q.pixels, max_dist=plan.max_dist,
                             nphotons=plan.nphotons, spp=self.spp, stream=stream)
         host = cnts.tolist()
         return (n, host[1]), None if last else out.first(host[5])
 
-    def _level_lights_path(self, plan, q, level, last):
+    def _level_lights_path(self, plan, q, level, last, rgb=None):
         """One level as ONE launch of mr_trace_level_lights_path (then mr_gather_level, with photon maps); returns (rays, shadow
-        rays) and the next queue (None after the last).  With an environment the children carry their low-res byte."""
+        rays) and the next queue (None after the last).  With an environment the children carry their low-res byte.  rgb: the
+        pixels the level adds to (None: d_slots)."""
         sc, n, stream = self.scene, q.n, plan.stream
+        rgb = self.d_slots if rgb is None else rgb
         f32 = dict(dtype=torch.float32, device=self.device)
         hits = normal = None
         if plan.photon_maps is not None:                # the photon term reads the level's hit records (and bumped normals)
@@ -639,18 +689,61 @@ class FrameRenderer:
         out = NO_QUEUE if last else self._children(plan, n)
         if not last and plan.environment:
             out = out._replace(low=torch.empty(out.n, dtype=torch.uint8, device=self.device))
-        sc.trace_level_lights_path(q.rays, q.weights, q.pixels, q.ids, n, self.d_slots,
+        sc.trace_level_lights_path(q.rays, q.weights, q.pixels, q.ids, n, rgb,
                                    children=binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_PATH, environment=plan.environment,
                                    d_hits=hits, d_normal=normal, d_out_rays=out.rays, d_out_weights=out.weights,
                                    d_out_pixels=out.pixels, d_out_ids=out.ids, d_out_count=None if last else cnts[5:],
                                    d_counts=cnts[:5], spp=self.spp, flags=plan.level_flags(level)[2], seed=plan.path_seed, bounce=level,
                                    kinds=plan.path_kinds, stream=stream, d_lowres=q.low, d_out_lowres=out.low)
         if plan.photon_maps is not None:
-            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), self.d_slots,
+            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), rgb,
                             d_normal=normal, d_weights=q.weights, d_pixels=q.pixels, max_dist=plan.max_dist,
                             nphotons=plan.nphotons, spp=self.spp, stream=stream)
         host = cnts.tolist()
         return (n, host[1]), None if last else out.first(host[5])
+
+    def _frame_levels(self, plan, depth):
+        """fused="frame_lights" | "frame_lights_path": level 0 as _frame_level0, the further levels as _level_lights /
+        _level_lights_path on its children, adding into d_rgb; returns (rays, shadow rays) per level."""
+        if self.n == 0 or depth < 0:
+            return []
+        counts, queue = self._frame_level0(plan, depth == 0)
+        per_level = [counts]
+        step = self._level_lights_path if plan.fused == "frame_lights_path" else self._level_lights
+        for level in range(1, depth + 1):
+            if queue.n == 0:
+                break
+            counts, queue = step(plan, queue, level, level == depth, rgb=self.d_rgb)
+            per_level.append(counts)
+        return per_level
+
+    def _frame_level0(self, plan, last):
+        """Level 0 as ONE mr_render_level_lights straight into d_rgb (then mr_gather_level, with photon maps, on generate()'s
+        rays); returns (rays, shadow rays) from the launch's counters and the queue of level 1 (None after the last)."""
+        sc, n, stream = self.scene, self.n, plan.stream
+        path = plan.fused == "frame_lights_path"
+        f32 = dict(dtype=torch.float32, device=self.device)
+        hits = normal = None
+        if plan.photon_maps is not None:                # the photon term reads level 0's rays, hit records (and bumped normals)
+            self.generate(stream)
+            hits = self.d_hits
+            normal = torch.empty((n, 3), **f32) if plan.surface else None
+        cnts = torch.zeros(6, dtype=torch.int64, device=self.device)        # the call's five counters, children
+        out = NO_QUEUE if last else self._children(plan, n)
+        if path and not last and plan.environment:
+            out = out._replace(low=torch.empty(out.n, dtype=torch.uint8, device=self.device))
+        (y0, y1), = self.bands
+        children = binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_PATH if path else binding.MR_LEVEL_SPECULAR
+        sc.render_level_lights(self.cam, self.W, self.H, self.d_rgb, y0=y0, y1=y1, spp=self.spp, jitter=self.jitter, seed=self.seed,
+                               tiled=self.tiled, flags=plan.level_flags(0)[2], d_hits=hits, d_sample_normal=normal, d_counts=cnts[:5],
+                               stream=stream, children=children, environment=plan.environment, kinds=plan.path_kinds,
+                               path_seed=plan.path_seed, d_out_rays=out.rays, d_out_weights=out.weights, d_out_pixels=out.pixels,
+                               d_out_ids=out.ids, d_out_count=None if last else cnts[5:], d_out_lowres=out.low)
+        if plan.photon_maps is not None:
+            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], self.d_rays, hits, n, torch.empty(12 * n, **f32), self.d_rgb,
+                            d_normal=normal, max_dist=plan.max_dist, nphotons=plan.nphotons, spp=self.spp, stream=stream)
+        host = cnts.tolist()
+        return (host[0], host[1]), None if last else out.first(host[5])
 
     def _level_batched(self, plan, q, level, last):
         """One level as separate launches: trace, environment, surface pass, shade, photon term, children -- whichever of

@@ -954,4 +954,5 @@ const char *mr_version(void);
 #endif
 #include "miro_hip_surface.h"
 #include "miro_hip_frame.h"
+#include "miro_hip_render.h"
 #endif /* MIRO_HIP_H */
