@@ -487,6 +487,12 @@ void build_environment_image(HostEnvironment &e, const float *px) {
         }
 }
 
+// one of the addresses `p` is no multiple of `align`, a power of two (NULL is aligned: an optional buffer passes)
+template <typename... P>
+bool misaligned(uintptr_t align, const P *...p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & (align - 1)) != 0;
+}
+
 }  // namespace
 }  // namespace mr
 
@@ -695,7 +701,7 @@ mr_status mr_trace(mr_scene *s, const mr_ray *rays, uint64_t n, mr_hit *hits, ui
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     MR_HIP_CHECK(hipSetDevice(s->device));
     const bool rays_dev = flags & MR_RAYS_ON_DEVICE, hits_dev = flags & MR_HITS_ON_DEVICE;
-    if ((rays_dev && (reinterpret_cast<uintptr_t>(rays) & 15)) || (hits_dev && (reinterpret_cast<uintptr_t>(hits) & 15)))
+    if ((rays_dev && misaligned(16, rays)) || (hits_dev && misaligned(16, hits)))
         return fail(MR_ERR_INVALID, "device ray/hit buffers must be 16-byte aligned");
     const mr_ray *d_rays = rays;
     mr_hit *d_hits = hits;
@@ -777,8 +783,7 @@ mr_status mr_trace_indirect(mr_scene *s, const mr_ray *d_rays, const uint64_t *d
     if (st != MR_OK) return st;
     if (max_rays == 0) return MR_OK;
     if (!d_rays || !d_hits || !d_count) return fail(MR_ERR_INVALID, "NULL argument");
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_count) & 7))
+    if (misaligned(16, d_rays, d_hits) || misaligned(8, d_count))
         return fail(MR_ERR_INVALID, "device ray/hit buffers must be 16-byte aligned, the count 8-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     TraceParams p = scene_trace_params(s->dev);
@@ -794,7 +799,7 @@ mr_status mr_order_by_octant(mr_scene *s, const mr_ray *d_rays, const uint8_t *d
     if (st != MR_OK) return st;
     if (n == 0) return MR_OK;
     if ((!d_rays && !d_octants) || !d_order) return fail(MR_ERR_INVALID, "NULL argument");
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_order) & 3))
+    if (misaligned(16, d_rays) || misaligned(4, d_order))
         return fail(MR_ERR_INVALID, "the ray buffer must be 16-byte aligned, the order buffer 4-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_octant_order(d_rays, d_octants, n, chunk_log2 ? chunk_log2 : 14u, d_order, static_cast<hipStream_t>(stream));
@@ -806,7 +811,7 @@ mr_status mr_trace_grouped(mr_scene *s, const mr_ray *d_rays, const uint8_t *d_o
     if (st != MR_OK) return st;
     if (n == 0) return MR_OK;
     if (!d_rays || !d_hits || !d_order) return fail(MR_ERR_INVALID, "NULL argument");
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_order) & 3))
+    if (misaligned(16, d_rays, d_hits) || misaligned(4, d_order))
         return fail(MR_ERR_INVALID, "device ray/hit buffers must be 16-byte aligned, the order buffer 4-byte aligned");
     if (flags & (MR_MATH_FAST | MR_COUNT_STATS))
         return fail(MR_ERR_INVALID, "mr_trace_grouped: flags may hold MR_TRACE_ANY, MR_MATH_PRODUCT, MR_TRACE_INCOHERENT only");
@@ -840,7 +845,7 @@ mr_status mr_gen_eye_rays(mr_scene *s, const mr_camera *cam, uint32_t W, uint32_
                           uint32_t spp, uint32_t jitter, uint32_t seed, mr_ray *d_rays, void *stream) {
     if (!s || !cam || !d_rays) return fail(MR_ERR_INVALID, "NULL argument");
     if (W == 0 || H == 0 || spp == 0 || y1 < y0 || y1 > H) return fail(MR_ERR_INVALID, "bad image window");
-    if (reinterpret_cast<uintptr_t>(d_rays) & 15) return fail(MR_ERR_INVALID, "d_rays must be 16-byte aligned");
+    if (misaligned(16, d_rays)) return fail(MR_ERR_INVALID, "d_rays must be 16-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_eye_rays(*cam, W, H, y0, y1, spp, jitter, seed, false, d_rays, static_cast<hipStream_t>(stream));
 }
@@ -850,7 +855,7 @@ mr_status mr_gen_eye_rays_tiled(mr_scene *s, const mr_camera *cam, uint32_t W, u
     if (!s || !cam || !d_rays) return fail(MR_ERR_INVALID, "NULL argument");
     if (W == 0 || H == 0 || spp == 0 || y1 < y0 || y1 > H) return fail(MR_ERR_INVALID, "bad image window");
     if ((uint64_t)W * (y1 - y0) > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "window of more than 2^32-1 pixels");
-    if (reinterpret_cast<uintptr_t>(d_rays) & 15) return fail(MR_ERR_INVALID, "d_rays must be 16-byte aligned");
+    if (misaligned(16, d_rays)) return fail(MR_ERR_INVALID, "d_rays must be 16-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_eye_rays(*cam, W, H, y0, y1, spp, jitter, seed, true, d_rays, static_cast<hipStream_t>(stream));
 }
@@ -946,8 +951,7 @@ mr_status mr_render_direct(mr_scene *s, const mr_frame_desc *frame, float *d_rgb
     if (!frame || !d_rgb) return fail(MR_ERR_INVALID, "NULL argument");
     if ((st = refuse_textured(s, "mr_render_direct")) != MR_OK) return st;
     if (frame->W == 0 || frame->H == 0) return fail(MR_ERR_INVALID, "empty image");
-    if ((reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_shadow_hits) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_counts) & 7) || (reinterpret_cast<uintptr_t>(d_rgb) & 3))
+    if (misaligned(16, d_hits, d_shadow_hits) || misaligned(8, d_counts) || misaligned(4, d_rgb))
         return fail(MR_ERR_INVALID, "hit buffers must be 16-byte aligned, counters 8-byte aligned");
     mr_frame_desc fd = *frame;
     if (fd.band_world <= 1) { fd.band_world = 1; fd.band_rank = 0; if (fd.band_rows == 0) fd.band_rows = 1; }
@@ -1059,8 +1063,8 @@ static mr_status check_gen_path_rays(const char *who, bool surface, mr_scene *s,
     if (!d_rays || !d_hits || !d_out_rays || !d_out_weights || !d_out_pixels || !d_count) return fail(MR_ERR_INVALID, "NULL argument");
     if (surface && !d_color) return fail(MR_ERR_INVALID, "%s: d_color is NULL", who);
     if (surface && !d_normal) return fail(MR_ERR_INVALID, "%s: d_normal is NULL", who);
-    if (surface && (reinterpret_cast<uintptr_t>(d_color) & 3)) return fail(MR_ERR_INVALID, "%s: d_color must be 4-byte aligned", who);
-    if (surface && (reinterpret_cast<uintptr_t>(d_normal) & 3)) return fail(MR_ERR_INVALID, "%s: d_normal must be 4-byte aligned", who);
+    if (surface && misaligned(4, d_color)) return fail(MR_ERR_INVALID, "%s: d_color must be 4-byte aligned", who);
+    if (surface && misaligned(4, d_normal)) return fail(MR_ERR_INVALID, "%s: d_normal must be 4-byte aligned", who);
     if (spp == 0) return fail(MR_ERR_INVALID, "spp is 0");
     if (n / spp > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "too many rays for 32-bit ray ids");
     if (kinds == 0 || (kinds & ~7u)) return fail(MR_ERR_INVALID, "kinds must be a combination of MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE");
@@ -1118,11 +1122,10 @@ mr_status mr_trace_level(mr_scene *s, const mr_level_desc *level, const mr_ray *
         return fail(MR_ERR_INVALID, "path_kinds must be a combination of MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE");
     if (level->flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT))
         return fail(MR_ERR_INVALID, "mr_trace_level: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT only");
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_out_rays) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_out_count) & 7) || (reinterpret_cast<uintptr_t>(d_counts) & 7))
+    if (misaligned(16, d_rays, d_out_rays) || misaligned(8, d_out_count, d_counts))
         return fail(MR_ERR_INVALID, "ray queues must be 16-byte aligned, counters 8-byte aligned");
     if (level->reserved != 0) return fail(MR_ERR_INVALID, "mr_level_desc.reserved must be 0");
-    if (reinterpret_cast<uintptr_t>(level->d_order) & 3) return fail(MR_ERR_INVALID, "mr_level_desc.d_order must be 4-byte aligned");
+    if (misaligned(4, level->d_order)) return fail(MR_ERR_INVALID, "mr_level_desc.d_order must be 4-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_level(s->dev, *level, d_rays, d_weights, d_pixels, d_ids, n, d_rgb, d_out_rays, d_out_weights, d_out_pixels,
                         d_out_ids, reinterpret_cast<unsigned long long *>(d_out_count),
@@ -1170,8 +1173,7 @@ static mr_status check_shade_lights(const char *who, mr_scene *s, const mr_ray *
         return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_TRACE_ANY only", who);
     if ((flags & MR_TRACE_ANY) && s->dev.refractive)
         return fail(MR_ERR_STATE, "%s: MR_TRACE_ANY with a refractive material (the nearest occluder decides, Phong.cpp:99-113)", who);
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
-        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3) || surface_misaligned)
+    if (misaligned(16, d_rays, d_hits) || misaligned(8, d_counts) || misaligned(4, d_rgb, d_ray_rgb) || surface_misaligned)
         return fail(MR_ERR_INVALID, "%s: ray / hit buffers must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned", who);
     return MR_OK;
 }
@@ -1216,6 +1218,18 @@ static mr_status environment_params(mr_scene *s, hipStream_t stream, EnvParams &
     return MR_OK;
 }
 
+// the scene as the textured light-list kernels take it, after the call's state checks: its device made current, its texture table
+// or none, and with `environment` its environment (without: all zero).  The two uploads happen only after a change
+// (texture_params, environment_params) and must lie outside a stream capture
+static mr_status lights_scene_params(mr_scene *s, bool environment, void *stream, TexParams &tex, EnvParams &env) {
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    mr_status st = MR_OK;
+    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
+    if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+    env = EnvParams{};
+    return environment ? environment_params(s, static_cast<hipStream_t>(stream), env) : MR_OK;
+}
+
 // mr_render_direct's window over mr_shade_lights' light list, in one launch (mr_frame_lights.hip).  What the arguments alone can
 // get wrong is answered first, before any device call and before the scene's state is read; then the scene's state.
 // What mr_render_lights and mr_render_lights_surface ask of their arguments and of the scene, in this order; `fd`: the
@@ -1231,8 +1245,7 @@ static mr_status check_render_lights_args(const char *who, mr_scene *s, const mr
     if (fd.band_world <= 1) { fd.band_world = 1; fd.band_rank = 0; if (fd.band_rows == 0) fd.band_rows = 1; }
     mr_status st = check_frame_lights(who, fd);
     if (st != MR_OK) return st;
-    if ((reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
-        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_sample_rgb) & 3) || surface_misaligned)
+    if (misaligned(16, d_hits) || misaligned(8, d_counts) || misaligned(4, d_rgb, d_sample_rgb) || surface_misaligned)
         return fail(MR_ERR_INVALID, "%s: the hit buffer must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned", who);
     return MR_OK;
 }
@@ -1272,13 +1285,11 @@ mr_status mr_render_lights_surface(mr_scene *s, const mr_frame_desc *frame, floa
                                    float *d_sample_color, float *d_sample_normal, uint64_t *d_counts, void *stream) {
     mr_frame_desc fd;
     mr_status st = check_render_lights("mr_render_lights_surface", s, frame, fd, d_rgb, d_hits, d_sample_rgb,
-                                       (reinterpret_cast<uintptr_t>(d_sample_color) & 3) || (reinterpret_cast<uintptr_t>(d_sample_normal) & 3),
-                                       d_counts, false);
+                                       misaligned(4, d_sample_color, d_sample_normal), d_counts, false);
     if (st != MR_OK) return st;
-    MR_HIP_CHECK(hipSetDevice(s->device));
     TexParams tex;
-    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
-    if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
+    EnvParams env;
+    if ((st = lights_scene_params(s, false, stream, tex, env)) != MR_OK) return st;
     return launch_frame_lights_surface(s->dev, tex, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
                                        d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts),
                                        static_cast<hipStream_t>(stream));
@@ -1291,56 +1302,53 @@ mr_status mr_render_lights_environment(mr_scene *s, const mr_frame_desc *frame, 
                                        float *d_sample_color, float *d_sample_normal, uint64_t *d_counts, void *stream) {
     mr_frame_desc fd;
     mr_status st = check_render_lights("mr_render_lights_environment", s, frame, fd, d_rgb, d_hits, d_sample_rgb,
-                                       (reinterpret_cast<uintptr_t>(d_sample_color) & 3) || (reinterpret_cast<uintptr_t>(d_sample_normal) & 3),
-                                       d_counts, false);
+                                       misaligned(4, d_sample_color, d_sample_normal), d_counts, false);
     if (st != MR_OK) return st;
-    MR_HIP_CHECK(hipSetDevice(s->device));
     TexParams tex;
-    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
-    if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
     EnvParams env;
-    if ((st = environment_params(s, static_cast<hipStream_t>(stream), env)) != MR_OK) return st;
+    if ((st = lights_scene_params(s, true, stream, tex, env)) != MR_OK) return st;
     return launch_frame_lights_env(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
                                    d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts),
                                    static_cast<hipStream_t>(stream));
 }
 
+// what the three calls that emit children ask of the queue they fill, in this order: the queue and its capacity with children
+// (fan: children at most per ray or sample, n of which the call runs), and n itself.  no_queue, no_room, too_many: the call's own
+// three refusals, formats over (who), (who, fan) and (who)
+static mr_status check_out_queue(const char *who, const char *no_queue, const char *no_room, const char *too_many, bool children,
+                                 unsigned fan, uint32_t capacity_lo, uint32_t capacity_hi, uint64_t n, const mr_ray *d_out_rays,
+                                 const float *d_out_weights, const uint32_t *d_out_pixels, const uint64_t *d_out_count) {
+    if (children && (!d_out_rays || !d_out_weights || !d_out_pixels || !d_out_count)) return fail(MR_ERR_INVALID, no_queue, who);
+    if (children && n > 0 && capacity_lo == 0 && capacity_hi == 0) return fail(MR_ERR_INVALID, no_room, who, fan);
+    if (n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, too_many, who);
+    return MR_OK;
+}
+
 // what mr_trace_level_lights and mr_trace_level_lights_path ask of their queues after the descriptor's own words, in this order:
-// the output queue and its capacity on a level with children (fan: children per ray at most), the ray count, the alignments.
-// more_misaligned: one of the buffers that the _path call takes besides is
+// check_out_queue, then the alignments.  more_misaligned: one of the buffers that the _path call takes besides is
 static mr_status check_level_lights_queue(const char *who, bool children, unsigned fan, uint32_t capacity_lo, uint32_t capacity_hi,
                                           const mr_ray *d_rays, const float *d_weights, const uint32_t *d_pixels, uint64_t n,
                                           const float *d_rgb, const mr_hit *d_hits, const float *d_ray_rgb, const float *d_color,
                                           const float *d_normal, const mr_ray *d_out_rays, const float *d_out_weights,
                                           const uint32_t *d_out_pixels, const uint64_t *d_out_count, const uint64_t *d_counts,
                                           bool more_misaligned) {
-    if (children && (!d_out_rays || !d_out_weights || !d_out_pixels || !d_out_count))
-        return fail(MR_ERR_INVALID, "%s: a level with children needs the output queue", who);
-    if (children && n > 0 && capacity_lo == 0 && capacity_hi == 0)
-        return fail(MR_ERR_INVALID, "%s: out_capacity is 0 (room for %un rays always suffices)", who, fan);
-    if (n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 rays per call", who);
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_out_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_out_count) & 7) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
-        (reinterpret_cast<uintptr_t>(d_weights) & 3) || (reinterpret_cast<uintptr_t>(d_pixels) & 3) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_color) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_out_weights) & 3) || (reinterpret_cast<uintptr_t>(d_out_pixels) & 3) || more_misaligned)
+    const mr_status st = check_out_queue(who, "%s: a level with children needs the output queue",
+                                         "%s: out_capacity is 0 (room for %un rays always suffices)", "%s: at most 2^32 - 1 rays per call",
+                                         children, fan, capacity_lo, capacity_hi, n, d_out_rays, d_out_weights, d_out_pixels, d_out_count);
+    if (st != MR_OK) return st;
+    if (misaligned(16, d_rays, d_out_rays, d_hits) || misaligned(8, d_out_count, d_counts) ||
+        misaligned(4, d_weights, d_pixels, d_rgb, d_ray_rgb, d_color, d_normal, d_out_weights, d_out_pixels) || more_misaligned)
         return fail(MR_ERR_INVALID, "%s: ray queues and the hit buffer must be 16-byte aligned, counters 8-byte, float and index buffers "
                                     "4-byte aligned", who);
     return MR_OK;
 }
 
-// ... and of the scene, after the arguments: built on a device, with lights; then the two uploads of
-// mr_render_lights_environment (texture table; environment image with `environment`), each only after a change
-static mr_status level_lights_params(const char *who, mr_scene *s, bool environment, hipStream_t stream, TexParams &tex, EnvParams &env) {
-    mr_status st = require_device(s);
+// ... and of the scene, after the arguments: built on a device, with lights; then lights_scene_params
+static mr_status level_lights_params(const char *who, mr_scene *s, bool environment, void *stream, TexParams &tex, EnvParams &env) {
+    const mr_status st = require_device(s);
     if (st != MR_OK) return st;
     if (s->lights.empty()) return fail(MR_ERR_STATE, "%s: the scene has no lights (mr_scene_set_lights)", who);
-    MR_HIP_CHECK(hipSetDevice(s->device));
-    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
-    if (!s->tex.blob.empty() && (st = texture_params(s, stream, tex)) != MR_OK) return st;
-    env = EnvParams{};
-    if (environment && (st = environment_params(s, stream, env)) != MR_OK) return st;
-    return MR_OK;
+    return lights_scene_params(s, environment, stream, tex, env);
 }
 
 // One level of the recursion over the light list on any scene, in one launch (mr_level_lights.hip).  What the arguments alone can
@@ -1370,7 +1378,7 @@ mr_status mr_trace_level_lights(mr_scene *s, const mr_level_lights_desc *level, 
     if (st != MR_OK) return st;
     TexParams tex;
     EnvParams env;
-    if ((st = level_lights_params(who, s, level->environment != 0, static_cast<hipStream_t>(stream), tex, env)) != MR_OK) return st;
+    if ((st = level_lights_params(who, s, level->environment != 0, stream, tex, env)) != MR_OK) return st;
     return launch_level_lights(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), *level, d_rays, d_weights, d_pixels, n,
                                d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights, d_out_pixels,
                                reinterpret_cast<unsigned long long *>(d_out_count), reinterpret_cast<unsigned long long *>(d_counts),
@@ -1401,12 +1409,11 @@ mr_status mr_trace_level_lights_path(mr_scene *s, const mr_level_lights_path_des
         if (level->reserved[k] != 0) return fail(MR_ERR_INVALID, "%s: mr_level_lights_path_desc.reserved must be 0", who);
     mr_status st = check_level_lights_queue(who, level->children != MR_LEVEL_LAST, 4u, level->out_capacity_lo, level->out_capacity_hi, d_rays,
                                             d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights,
-                                            d_out_pixels, d_out_count, d_counts,
-                                            (reinterpret_cast<uintptr_t>(d_ids) & 3) || (reinterpret_cast<uintptr_t>(d_out_ids) & 3));
+                                            d_out_pixels, d_out_count, d_counts, misaligned(4, d_ids, d_out_ids));
     if (st != MR_OK) return st;
     TexParams tex;
     EnvParams env;
-    if ((st = level_lights_params(who, s, level->environment != 0, static_cast<hipStream_t>(stream), tex, env)) != MR_OK) return st;
+    if ((st = level_lights_params(who, s, level->environment != 0, stream, tex, env)) != MR_OK) return st;
     return launch_level_lights_path(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), *level, d_rays, d_weights, d_pixels,
                                     d_ids, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights, d_out_pixels,
                                     d_out_ids, reinterpret_cast<unsigned long long *>(d_out_count),
@@ -1423,8 +1430,7 @@ mr_status mr_render_level_lights(mr_scene *s, const mr_frame_desc *frame, const 
     const char *who = "mr_render_level_lights";
     mr_frame_desc fd;
     mr_status st = check_render_lights_args(who, s, frame, fd, d_rgb, d_hits, d_sample_rgb,
-                                            (reinterpret_cast<uintptr_t>(d_sample_color) & 3) || (reinterpret_cast<uintptr_t>(d_sample_normal) & 3),
-                                            d_counts);
+                                            misaligned(4, d_sample_color, d_sample_normal), d_counts);
     if (st != MR_OK) return st;
     if (!level) return fail(MR_ERR_INVALID, "%s: NULL argument (level)", who);
     if (fd.flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT))
@@ -1439,27 +1445,21 @@ mr_status mr_render_level_lights(mr_scene *s, const mr_frame_desc *frame, const 
         if (level->reserved[k] != 0) return fail(MR_ERR_INVALID, "%s: mr_frame_level_desc.reserved must be 0", who);
     const bool children = level->children != MR_LEVEL_LAST;
     if (children) {
-        if (!d_out_rays || !d_out_weights || !d_out_pixels || !d_out_count)
-            return fail(MR_ERR_INVALID, "%s: a frame with children needs the output queue", who);
-        unsigned long long n = 0;
+        unsigned long long n = 0;                              // (the window has passed check_frame_lights: this cannot fail here)
         if ((st = frame_level_lights_samples(who, fd, n)) != MR_OK) return st;
-        if (n > 0 && level->out_capacity_lo == 0 && level->out_capacity_hi == 0)
-            return fail(MR_ERR_INVALID, "%s: out_capacity is 0 (room for %u rays per sample always suffices)", who,
-                        level->children == MR_LEVEL_PATH ? 4u : 3u);
-        if (n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 samples per call with children", who);
-        if ((reinterpret_cast<uintptr_t>(d_out_rays) & 15) || (reinterpret_cast<uintptr_t>(d_out_count) & 7) ||
-            (reinterpret_cast<uintptr_t>(d_out_weights) & 3) || (reinterpret_cast<uintptr_t>(d_out_pixels) & 3) ||
-            (reinterpret_cast<uintptr_t>(d_out_ids) & 3))
+        st = check_out_queue(who, "%s: a frame with children needs the output queue",
+                             "%s: out_capacity is 0 (room for %u rays per sample always suffices)",
+                             "%s: at most 2^32 - 1 samples per call with children", true, level->children == MR_LEVEL_PATH ? 4u : 3u,
+                             level->out_capacity_lo, level->out_capacity_hi, n, d_out_rays, d_out_weights, d_out_pixels, d_out_count);
+        if (st != MR_OK) return st;
+        if (misaligned(16, d_out_rays) || misaligned(8, d_out_count) || misaligned(4, d_out_weights, d_out_pixels, d_out_ids))
             return fail(MR_ERR_INVALID, "%s: the output rays must be 16-byte aligned, d_out_count 8-byte, weights, pixels and ids "
                                         "4-byte aligned", who);
     }
     if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
-    MR_HIP_CHECK(hipSetDevice(s->device));
     TexParams tex;
-    tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
-    if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
-    EnvParams env = EnvParams{};
-    if (level->environment && (st = environment_params(s, static_cast<hipStream_t>(stream), env)) != MR_OK) return st;
+    EnvParams env;
+    if ((st = lights_scene_params(s, level->environment != 0, stream, tex, env)) != MR_OK) return st;
     if (!children)
         return launch_frame_lights_env(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
                                        d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts),
@@ -1480,8 +1480,7 @@ mr_status mr_gen_eye_rays_lens(mr_scene *s, const mr_camera *cam, uint32_t W, ui
     if (!std::isfinite(lens->aperture) || lens->aperture < 0.0f) return fail(MR_ERR_INVALID, "mr_gen_eye_rays_lens: aperture must be finite and >= 0");
     if (!std::isfinite(lens->focus_plane) || !(lens->focus_plane > 0.0f)) return fail(MR_ERR_INVALID, "mr_gen_eye_rays_lens: focus_plane must be finite and > 0");
     if (W == 0 || H == 0 || spp == 0 || y1 < y0 || y1 > H) return fail(MR_ERR_INVALID, "bad image window");
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_samples_in) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_samples_out) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7))
+    if (misaligned(16, d_rays, d_samples_in, d_samples_out) || misaligned(8, d_counts))
         return fail(MR_ERR_INVALID, "d_rays and the sample buffers must be 16-byte aligned, counters 8-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_eye_rays_lens(*cam, W, H, y0, y1, spp, jitter, seed, *lens, d_samples_in, d_samples_out,
@@ -1522,10 +1521,9 @@ static mr_status check_shade_square_lights(const char *who, bool surface, mr_sce
     if (n > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32-1 rays per batch (the sample keys hold the ray index in 32 bits)", who);
     if (flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT | MR_TRACE_ANY))
         return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT, MR_TRACE_ANY only", who);
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
-        (reinterpret_cast<uintptr_t>(d_uv_in) & 7) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3))
+    if (misaligned(16, d_rays, d_hits) || misaligned(8, d_counts, d_uv_in) || misaligned(4, d_rgb, d_ray_rgb))
         return fail(MR_ERR_INVALID, "%s: ray / hit buffers must be 16-byte aligned, counters and d_uv_in 8-byte aligned", who);
-    if (surface && ((reinterpret_cast<uintptr_t>(d_color) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3)))
+    if (surface && misaligned(4, d_color, d_normal))
         return fail(MR_ERR_INVALID, "%s: d_color and d_normal must be 4-byte aligned", who);
     if ((st = require_device(s)) != MR_OK) return st;
     if (!surface) {
@@ -1624,9 +1622,7 @@ mr_status mr_shade_environment(mr_scene *s, const mr_ray *d_rays, const mr_hit *
     if (spp == 0) return fail(MR_ERR_INVALID, "spp is 0");
     if (n / spp > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "too many pixels");
     if (flags & ~(uint32_t)MR_ENV_LOWRES) return fail(MR_ERR_INVALID, "mr_shade_environment: flags may hold MR_ENV_LOWRES only");
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_counts) & 7) ||
-        (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_ray_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_weights) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_pixels) & 3))
+    if (misaligned(16, d_rays, d_hits) || misaligned(8, d_counts) || misaligned(4, d_rgb, d_ray_rgb, d_weights, d_pixels))
         return fail(MR_ERR_INVALID, "ray / hit buffers must be 16-byte aligned, counters 8-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     EnvParams p;
@@ -1800,7 +1796,7 @@ mr_status mr_hit_uv(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, uin
     mr_status st = require_device(s);
     if (st != MR_OK) return st;
     if (!d_hits || !d_uv) return fail(MR_ERR_INVALID, "NULL argument");
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_uv) & 3))
+    if (misaligned(16, d_rays, d_hits) || misaligned(4, d_uv))
         return fail(MR_ERR_INVALID, "ray / hit buffers must be 16-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_hit_uv(s->dev, d_rays, d_hits, n, d_uv, static_cast<hipStream_t>(stream));
@@ -1812,7 +1808,7 @@ mr_status mr_texture_lookup(mr_scene *s, uint32_t texture, const float *d_uv, ui
     if (s->tex.blob.empty()) return fail(MR_ERR_STATE, "mr_texture_lookup: the scene has no textures (mr_scene_set_textures)");
     if (texture >= s->tex.n_textures) return fail(MR_ERR_INVALID, "mr_texture_lookup: texture %u of %u", texture, s->tex.n_textures);
     if (!d_uv || !d_rgb) return fail(MR_ERR_INVALID, "NULL argument");
-    if ((reinterpret_cast<uintptr_t>(d_uv) & 3) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_counts) & 7))
+    if (misaligned(4, d_uv, d_rgb) || misaligned(8, d_counts))
         return fail(MR_ERR_INVALID, "float buffers must be 4-byte aligned, counters 8-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     TexParams tex;
@@ -1831,8 +1827,7 @@ mr_status mr_hit_surface(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits
     mr_status st = require_device(s);
     if (st != MR_OK) return st;
     if (!d_hits || !d_color || !d_normal) return fail(MR_ERR_INVALID, "mr_hit_surface: NULL argument");
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15) || (reinterpret_cast<uintptr_t>(d_color) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_normal) & 3) || (reinterpret_cast<uintptr_t>(d_counts) & 7))
+    if (misaligned(16, d_rays, d_hits) || misaligned(4, d_color, d_normal) || misaligned(8, d_counts))
         return fail(MR_ERR_INVALID, "mr_hit_surface: ray / hit buffers must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     TexParams tex;
@@ -1846,7 +1841,7 @@ mr_status mr_shade_lights_surface(mr_scene *s, const mr_ray *d_rays, const mr_hi
                                   const float *d_weights, const uint32_t *d_pixels, uint64_t n, uint32_t spp, uint32_t flags,
                                   float *d_rgb, float *d_ray_rgb, uint64_t *d_counts, void *stream) {
     const mr_status st = check_shade_lights("mr_shade_lights_surface", s, d_rays, d_hits, !d_color || !d_normal,
-                                            (reinterpret_cast<uintptr_t>(d_color) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3), n, spp,
+                                            misaligned(4, d_color, d_normal), n, spp,
                                             flags, d_rgb, d_ray_rgb, d_counts);
     if (st != MR_OK) return st;
     MR_HIP_CHECK(hipSetDevice(s->device));
@@ -1862,7 +1857,7 @@ mr_status mr_shade_accumulate_surface(mr_scene *s, const mr_ray *d_rays, const m
     mr_status st = check_shade_accumulate("mr_shade_accumulate_surface", s, d_rays, d_hits, !d_color || !d_normal, d_shadow_rays,
                                           d_shadow_hits, d_shadow_src, d_shadow_count, light, spp, d_rgb);
     if (st != MR_OK) return st;
-    if ((reinterpret_cast<uintptr_t>(d_color) & 3) || (reinterpret_cast<uintptr_t>(d_normal) & 3))
+    if (misaligned(4, d_color, d_normal))
         return fail(MR_ERR_INVALID, "mr_shade_accumulate_surface: float buffers must be 4-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     if ((st = reserve_light_scale(s, n)) != MR_OK) return st;
@@ -1879,7 +1874,7 @@ mr_status mr_texture_bump_height(mr_scene *s, uint32_t texture, const float *d_u
     if (s->tex.blob.empty()) return fail(MR_ERR_STATE, "mr_texture_bump_height: the scene has no textures (mr_scene_set_textures)");
     if (texture >= s->tex.n_textures) return fail(MR_ERR_INVALID, "mr_texture_bump_height: texture %u of %u", texture, s->tex.n_textures);
     if (!d_uv || !d_height) return fail(MR_ERR_INVALID, "mr_texture_bump_height: NULL argument");
-    if ((reinterpret_cast<uintptr_t>(d_uv) & 3) || (reinterpret_cast<uintptr_t>(d_height) & 3))
+    if (misaligned(4, d_uv, d_height))
         return fail(MR_ERR_INVALID, "mr_texture_bump_height: float buffers must be 4-byte aligned");
     MR_HIP_CHECK(hipSetDevice(s->device));
     uint32_t kind;
@@ -1894,8 +1889,7 @@ mr_status mr_texture_lookup3(mr_scene *s, uint32_t texture, const float *d_p, ui
     if (s->tex.blob.empty()) return fail(MR_ERR_STATE, "mr_texture_lookup3: the scene has no textures (mr_scene_set_textures)");
     if (texture >= s->tex.n_textures) return fail(MR_ERR_INVALID, "mr_texture_lookup3: texture %u of %u", texture, s->tex.n_textures);
     if (!d_p || !d_rgb) return fail(MR_ERR_INVALID, "mr_texture_lookup3: NULL argument");
-    if ((reinterpret_cast<uintptr_t>(d_p) & 3) || (reinterpret_cast<uintptr_t>(d_rgb) & 3) || (reinterpret_cast<uintptr_t>(d_coords) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_counts) & 7))
+    if (misaligned(4, d_p, d_rgb, d_coords) || misaligned(8, d_counts))
         return fail(MR_ERR_INVALID, "mr_texture_lookup3: float buffers must be 4-byte aligned, counters 8-byte aligned");
     uint32_t kind;
     memcpy(&kind, &s->tex.blob[3 * (size_t)texture].x, sizeof(kind));
@@ -1911,7 +1905,7 @@ mr_status mr_texture_lookup3(mr_scene *s, uint32_t texture, const float *d_p, ui
 mr_status mr_noise_probe(uint32_t which, const float *d_in, uint64_t n, float *d_out, void *stream) {
     if (which != MR_NOISE_PERLIN && which != MR_NOISE_WORLEY2) return fail(MR_ERR_INVALID, "mr_noise_probe: which must be MR_NOISE_PERLIN or MR_NOISE_WORLEY2");
     if (!d_in || !d_out) return fail(MR_ERR_INVALID, "mr_noise_probe: NULL argument");
-    if ((reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
+    if (misaligned(4, d_in, d_out))
         return fail(MR_ERR_INVALID, "mr_noise_probe: buffers must be 4-byte aligned");
     return launch_noise_probe(which, d_in, n, d_out, static_cast<hipStream_t>(stream));
 }

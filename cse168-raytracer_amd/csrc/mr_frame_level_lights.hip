@@ -54,7 +54,7 @@
 // and not enough to get those two under 108 bytes: waves_per_eu(4, 4), the queue's arguments staged through LDS, per-wave counters
 // in scalar registers, an opaque copy of the thread index for the compaction.  None of them is in the code.
 //
-// d_out_count is zeroed by a one-word kernel of this unit, not a memset node (mr_level_lights.hip says why).  Times against the
+// d_out_count is zeroed by a one-word kernel, not a memset node (launch_zero_count; mr_level_lights.hip says why).  Times against the
 // level kernels at level 0: DESIGN section 5c, profiles/frame_level_lights_ab.log.
 #include <hip/hip_runtime.h>
 
@@ -82,12 +82,6 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
     frame_lights_surface_body<VAR, false, true, CHILDREN>(a.f, a.env, a.ch, s_stack, s_tab);
 }
 
-// d_out_count = 0 on the launch's stream, as a kernel: a store from a kernel node replays from a graph as written
-// (mr_level_lights.hip, zero_count_kernel)
-__global__ void zero_frame_level_count_kernel(unsigned long long *count) {
-    if (threadIdx.x == 0) *count = 0ull;
-}
-
 template <int VAR, int CHILDREN>
 mr_status launch_frame_level_lights_t(const FrameLevelLightsArgs &a, hipStream_t stream) {
     size_t lds = 0;
@@ -113,11 +107,9 @@ mr_status launch_frame_level_lights(const DeviceScene &ds, const TexParams &tex,
                                     float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_out_count,
                                     unsigned long long *d_counts, hipStream_t stream) {
     FrameLevelLightsArgs a;
-    const mr_status st = fill_frame_lights_surface_args(a.f, "mr_render_level_lights", ds, tex, lights, n_lights, fd, d_rgb, d_hits,
-                                                        d_sample_rgb, d_sample_color, d_sample_normal, d_counts);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL(zero_frame_level_count_kernel, dim3(1), dim3(64), 0, stream, d_out_count);
-    MR_HIP_CHECK(hipGetLastError());
+    mr_status st = fill_frame_lights_surface_args(a.f, "mr_render_level_lights", ds, tex, lights, n_lights, fd, d_rgb, d_hits,
+                                                  d_sample_rgb, d_sample_color, d_sample_normal, d_counts);
+    if (st != MR_OK || (st = launch_zero_count(d_out_count, stream)) != MR_OK) return st;
     if (a.f.eye.n == 0) return MR_OK;
     a.env = env;
     a.ch.out.rays = d_out_rays; a.ch.out.weights = d_out_weights; a.ch.out.pixels = d_out_pixels;

@@ -307,6 +307,9 @@ struct EnvParams;
 mr_status launch_frame_lights_env(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
                                   uint32_t n_lights, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
                                   float *d_sample_color, float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream);
+// *d_count = 0 on `stream`, as a one-word kernel: the node that zeroes d_out_count in the three launchers below, which a captured
+// graph replays as written (mr_level_lights.hip says what a memset node did)
+mr_status launch_zero_count(unsigned long long *d_count, hipStream_t stream);
 // one level of the recursion over the light list on any scene (mr_level_lights.hip, mr_trace_level_lights): launch_level's queues
 // with that frame's texture table, environment (read with ld.environment only) and optional per-ray outputs; d_out_count is
 // zeroed on `stream` on a level with children (a one-word kernel), then one kernel (none for n == 0); d_counts: five words

@@ -451,6 +451,24 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags):
+    """an mr_frame_desc from the arguments every render_* method takes: the window, the bands and the samples"""
+    fd = FrameDesc()
+    fd.camera = cam
+    fd.W, fd.H, fd.y0, fd.y1 = W, H, y0, H if y1 is None else y1
+    fd.band_rows, fd.band_rank, fd.band_world = bands if bands is not None else (1, 0, 1)
+    fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
+    return fd
+
+
+def _out_capacity(given, *buffers):
+    """(out_capacity_lo, out_capacity_hi) of a level descriptor: `given`, or for None the rows of the shortest output buffer
+    (0 without one)"""
+    if given is None:
+        given = min([t.shape[0] for t in buffers if t is not None], default=0)
+    return given & 0xFFFFFFFF, given >> 32
+
+
 def _light(position, color, wattage):
     """an mr_light: the single point light of the calls that take one"""
     lt = Light()
@@ -694,10 +712,7 @@ class Scene:
         ld.light.color[:] = color
         ld.light.wattage = wattage
         ld.spp, ld.flags, ld.children, ld.path_kinds, ld.seed, ld.bounce = spp, flags, children, kinds, seed, bounce
-        if out_capacity is None:
-            outs = [t for t in (d_out_rays, d_out_weights, d_out_pixels, d_out_ids) if t is not None]
-            out_capacity = min(t.shape[0] for t in outs) if outs else 0
-        ld.out_capacity_lo, ld.out_capacity_hi = out_capacity & 0xFFFFFFFF, out_capacity >> 32
+        ld.out_capacity_lo, ld.out_capacity_hi = _out_capacity(out_capacity, d_out_rays, d_out_weights, d_out_pixels, d_out_ids)
         ld.d_out_octants, ld.d_order = _ptr(d_out_octants), _ptr(d_order)
         _check(self.L.mr_trace_level(self.h, C.byref(ld), d_rays.data_ptr(), _ptr(d_weights), _ptr(d_pixels), _ptr(d_ids), n,
                                      d_rgb.data_ptr(), _ptr(d_out_rays), _ptr(d_out_weights), _ptr(d_out_pixels), _ptr(d_out_ids),
@@ -716,10 +731,7 @@ class Scene:
         graph capture."""
         ld = LevelLightsDesc()
         ld.spp, ld.flags, ld.children, ld.environment = spp, flags, children, 1 if environment else 0
-        if out_capacity is None:
-            outs = [t for t in (d_out_rays, d_out_weights, d_out_pixels) if t is not None]
-            out_capacity = min(t.shape[0] for t in outs) if outs else 0
-        ld.out_capacity_lo, ld.out_capacity_hi = out_capacity & 0xFFFFFFFF, out_capacity >> 32
+        ld.out_capacity_lo, ld.out_capacity_hi = _out_capacity(out_capacity, d_out_rays, d_out_weights, d_out_pixels)
         ld.d_out_octants = _ptr(d_out_octants)
         _check(self.L.mr_trace_level_lights(self.h, C.byref(ld), d_rays.data_ptr(), _ptr(d_weights), _ptr(d_pixels), n, _ptr(d_rgb),
                                             _ptr(d_hits), _ptr(d_ray_rgb), _ptr(d_color), _ptr(d_normal), _ptr(d_out_rays),
@@ -740,10 +752,8 @@ class Scene:
         ld = LevelLightsPathDesc()
         ld.spp, ld.flags, ld.children, ld.environment = spp, flags, children, 1 if environment else 0
         ld.path_kinds, ld.seed, ld.bounce = kinds, seed, bounce
-        if out_capacity is None:
-            outs = [t for t in (d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_lowres) if t is not None]
-            out_capacity = min(t.shape[0] for t in outs) if outs else 0
-        ld.out_capacity_lo, ld.out_capacity_hi = out_capacity & 0xFFFFFFFF, out_capacity >> 32
+        ld.out_capacity_lo, ld.out_capacity_hi = _out_capacity(out_capacity, d_out_rays, d_out_weights, d_out_pixels, d_out_ids,
+                                                               d_out_lowres)
         ld.d_out_octants, ld.d_lowres, ld.d_out_lowres = _ptr(d_out_octants), _ptr(d_lowres), _ptr(d_out_lowres)
         _check(self.L.mr_trace_level_lights_path(self.h, C.byref(ld), d_rays.data_ptr(), _ptr(d_weights), _ptr(d_pixels), _ptr(d_ids), n,
                                                  _ptr(d_rgb), _ptr(d_hits), _ptr(d_ray_rgb), _ptr(d_color), _ptr(d_normal),
@@ -759,11 +769,7 @@ class Scene:
                       d_counts=None, stream=None):
         """mr_render_direct: eye rays -> trace -> shadow rays -> trace -> Phong shade -> pixel means in one launch.
         bands = (rows per band, rank, world) selects one rank's interleaved bands instead of the rows [y0,y1)."""
-        fd = FrameDesc()
-        fd.camera = cam
-        fd.W, fd.H, fd.y0, fd.y1 = W, H, y0, H if y1 is None else y1
-        fd.band_rows, fd.band_rank, fd.band_world = bands if bands is not None else (1, 0, 1)
-        fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
         fd.light.position[:] = light_pos
         fd.light.color[:] = color
         fd.light.wattage = wattage
@@ -776,11 +782,7 @@ class Scene:
         """mr_render_lights: render_direct's window shaded over the scene's light list (set_lights) with its material table --
         eye rays -> trace -> per light shadow ray, trace, Phong terms -> pixel means in one launch.  d_hits [n, 4] and
         d_sample_rgb [n, 3] (the un-weighted L of every sample) in sample order; d_counts[0] += samples, [1] += shadow rays."""
-        fd = FrameDesc()
-        fd.camera = cam
-        fd.W, fd.H, fd.y0, fd.y1 = W, H, y0, H if y1 is None else y1
-        fd.band_rows, fd.band_rank, fd.band_world = bands if bands is not None else (1, 0, 1)
-        fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
         _check(self.L.mr_render_lights(self.h, C.byref(fd), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb), _ptr(d_counts),
                                        _stream_ptr(stream)))
 
@@ -793,11 +795,7 @@ class Scene:
         [2] += hits whose lookup the reference leaves undefined.  A miss contributes 0: set_environment is not applied
         (render_lights_environment applies it).  The first call after set_textures uploads the table and must lie outside a
         graph capture."""
-        fd = FrameDesc()
-        fd.camera = cam
-        fd.W, fd.H, fd.y0, fd.y1 = W, H, y0, H if y1 is None else y1
-        fd.band_rows, fd.band_rank, fd.band_world = bands if bands is not None else (1, 0, 1)
-        fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
         _check(self.L.mr_render_lights_surface(self.h, C.byref(fd), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb),
                                                _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_counts), _stream_ptr(stream)))
 
@@ -808,11 +806,7 @@ class Scene:
         direction; the value is the sample's L (d_sample_rgb, the pixel's mean).  d_counts: FIVE words, [0..2] as in
         render_lights_surface, [3] += samples that missed, [4] += environment lookups the reference leaves undefined.  The first
         call after set_environment with an image uploads it and must lie outside a graph capture, like the texture table."""
-        fd = FrameDesc()
-        fd.camera = cam
-        fd.W, fd.H, fd.y0, fd.y1 = W, H, y0, H if y1 is None else y1
-        fd.band_rows, fd.band_rank, fd.band_world = bands if bands is not None else (1, 0, 1)
-        fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
         _check(self.L.mr_render_lights_environment(self.h, C.byref(fd), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb),
                                                    _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_counts), _stream_ptr(stream)))
 
@@ -829,17 +823,11 @@ class Scene:
         stored or not (out_capacity, None: the shortest output buffer).  d_out_ids, d_out_lowres (uint8 per stored child, 1 = the
         diffuse child) with MR_LEVEL_PATH.  d_counts: FIVE words, as in render_lights_environment.  flags: MR_MATH_PRODUCT,
         MR_TRACE_INCOHERENT only.  MR_LEVEL_LAST is render_lights_environment itself."""
-        fd = FrameDesc()
-        fd.camera = cam
-        fd.W, fd.H, fd.y0, fd.y1 = W, H, y0, H if y1 is None else y1
-        fd.band_rows, fd.band_rank, fd.band_world = bands if bands is not None else (1, 0, 1)
-        fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
         ld = FrameLevelDesc()
         ld.children, ld.environment, ld.path_kinds, ld.path_seed = children, 1 if environment else 0, kinds, path_seed
-        if out_capacity is None:
-            outs = [t for t in (d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_lowres, d_out_octants) if t is not None]
-            out_capacity = min(t.shape[0] for t in outs) if outs else 0
-        ld.out_capacity_lo, ld.out_capacity_hi = out_capacity & 0xFFFFFFFF, out_capacity >> 32
+        ld.out_capacity_lo, ld.out_capacity_hi = _out_capacity(out_capacity, d_out_rays, d_out_weights, d_out_pixels, d_out_ids,
+                                                               d_out_lowres, d_out_octants)
         ld.d_out_octants, ld.d_out_lowres = _ptr(d_out_octants), _ptr(d_out_lowres)
         _check(self.L.mr_render_level_lights(self.h, C.byref(fd), C.byref(ld), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb),
                                              _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_out_rays), _ptr(d_out_weights),

@@ -517,7 +517,7 @@ class FrameRenderer:
                     break
                 one_launch = plan.fused is True or (plan.fused == "auto" and
                                                     (level == 0 or per_level[-1][1] >= 0.9 * per_level[-1][0]))
-                step = self._level_lights if plan.fused == "lights" else self._level_lights_path if plan.fused == "lights_path" else \
+                step = self._level_lights if plan.fused in ("lights", "lights_path") else \
                     self._level_fused if one_launch else self._level_batched
                 counts, queue = step(plan, queue, level, level == depth)
                 per_level.append(counts)
@@ -545,32 +545,24 @@ class FrameRenderer:
             if photon_maps is not None:
                 self._need_rays("render_specular(fused=\"%s\", photon_maps=...)" % frame_route)
             fused = level_route                 # the checks of that route hold here too; the plan carries the frame route
-        level_lights = isinstance(fused, str) and fused == "lights"
-        level_path = isinstance(fused, str) and fused == "lights_path"
-        if level_path:
+        level_route = fused if isinstance(fused, str) and fused in ("lights", "lights_path") else None
+        if level_route:
+            path = level_route == "lights_path"
+            call = "mr_trace_level_lights_path" if path else "mr_trace_level_lights"
             if lights is None:
-                raise ValueError("render_specular: fused=\"lights_path\" needs lights=[...] (mr_trace_level_lights_path shades by the "
-                                 "scene's light list)")
-            if not path_tracing:
+                raise ValueError("render_specular: fused=\"%s\" needs lights=[...] (%s shades by the scene's light list)"
+                                 % (level_route, call))
+            if path and not path_tracing:
                 raise ValueError("render_specular: fused=\"lights_path\" needs path_tracing=True (the specular children are "
                                  "fused=\"lights\")")
-            refused = [("square lights", self.square_lights), ("group_octants", group_octants),
-                       ("surface_children=False", surface_children is False)]
+            refused = [("path_tracing", path_tracing and not path), ("square lights", self.square_lights),
+                       ("group_octants", group_octants), ("surface_children=%s" % (not path), surface_children is (not path))]
             for what, given in refused:
                 if given:
-                    raise ValueError("render_specular: %s needs the batched path, not fused=\"lights_path\" (mr_trace_level_lights_path "
-                                     "emits the children of mr_gen_path_rays_surface and shades point and disc lights only)" % what)
-            fused = False                       # the checks below speak of mr_trace_level; the plan carries "lights_path"
-        if level_lights:
-            if lights is None:
-                raise ValueError("render_specular: fused=\"lights\" needs lights=[...] (mr_trace_level_lights shades by the scene's light list)")
-            refused = [("path_tracing", path_tracing), ("square lights", self.square_lights), ("group_octants", group_octants),
-                       ("surface_children=True", surface_children is True)]
-            for what, given in refused:
-                if given:
-                    raise ValueError("render_specular: %s needs the batched path, not fused=\"lights\" (mr_trace_level_lights emits the "
-                                     "specular children and shades point and disc lights only)" % what)
-            fused = False                       # the checks below speak of mr_trace_level; the plan carries "lights"
+                    raise ValueError("render_specular: %s needs the batched path, not fused=\"%s\" (%s emits the %s and shades point "
+                                     "and disc lights only)" % (what, level_route, call,
+                                                                "children of mr_gen_path_rays_surface" if path else "specular children"))
+            fused = False                       # the checks below speak of mr_trace_level; the plan carries the route
         if sc.n_textures:
             fused = False
         if photon_maps is not None:
@@ -596,7 +588,7 @@ class FrameRenderer:
             has_image = sc.get_environment(0)[0] is not None
             kinds = binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT if path_kinds is None else path_kinds
             diffuse_children = path_tracing and bool(kinds & binding.MR_PATH_DIFFUSE)
-            if has_image and diffuse_children and kinds != binding.MR_PATH_DIFFUSE and not level_path:
+            if has_image and diffuse_children and kinds != binding.MR_PATH_DIFFUSE and level_route != "lights_path":
                 raise ValueError("render_specular: an environment image with MR_PATH_DIFFUSE mixed with other kinds "
                                  "(the queue does not record which child came from Ray::random)")
             if diffuse_children and kinds == binding.MR_PATH_DIFFUSE:
@@ -614,9 +606,7 @@ class FrameRenderer:
             raise TypeError("render_specular: pass a torch.cuda.Stream (or None for the current stream), not a raw handle")
         # square lights on a texture table of any kind read the surface pass's buffers (mr_shade_square_lights refuses the table)
         square = None if not self.square_lights else "surface" if sc.n_textures else "plain"
-        return LevelPlan(stream=stream, flags=self.flags,
-                         fused=frame_route if frame_route else "lights" if level_lights else "lights_path" if level_path else fused,
-                         path_tracing=path_tracing,
+        return LevelPlan(stream=stream, flags=self.flags, fused=frame_route or level_route or fused, path_tracing=path_tracing,
                          path_kinds=binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT if path_kinds is None else path_kinds,
                          fan=4 if path_tracing else 3, path_seed=path_seed, group_octants=group_octants, lights=lights is not None,
                          environment=environment, env_lowres=env_lowres, surface=surface, square=square,
@@ -650,98 +640,79 @@ class FrameRenderer:
         host = cnts.tolist()
         return (n, host[1]), None if last else out.first(host[2])
 
-    def _level_lights(self, plan, q, level, last, rgb=None):
-        """One level as ONE launch of mr_trace_level_lights (then mr_gather_level, with photon maps); returns (rays, shadow rays)
-        and the next queue (None after the last).  rgb: the pixels the level adds to (None: d_slots)."""
-        sc, n, stream = self.scene, q.n, plan.stream
-        rgb = self.d_slots if rgb is None else rgb
+    def _level_buffers(self, plan, n, level, last):
+        """What a one-launch light-list level of n rays (or samples) writes besides pixels: hit records, and bumped normals on a
+        procedural scene, with photon maps only; the call's five counters and the children's; the children's queue (NO_QUEUE
+        after the last level), under path tracing with an environment with their low-res bytes."""
         f32 = dict(dtype=torch.float32, device=self.device)
         hits = normal = None
         if plan.photon_maps is not None:                # the photon term reads the level's hit records (and bumped normals)
             hits = self.d_hits if level == 0 else torch.empty((n, 4), **f32)
             normal = torch.empty((n, 3), **f32) if plan.surface else None
-        cnts = torch.zeros(6, dtype=torch.int64, device=self.device)        # the call's five counters, children
+        cnts = torch.zeros(6, dtype=torch.int64, device=self.device)
         out = NO_QUEUE if last else self._children(plan, n)
-        sc.trace_level_lights(q.rays, q.weights, q.pixels, n, rgb,
-                              children=binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_SPECULAR, environment=plan.environment,
-                              d_hits=hits, d_normal=normal, d_out_rays=out.rays, d_out_weights=out.weights, d_out_pixels=out.pixels,
-                              d_out_count=None if last else cnts[5:], d_counts=cnts[:5], spp=self.spp,
-                              flags=plan.level_flags(level)[2], stream=stream)
-        if plan.photon_maps is not None:
-            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), rgb,
-                            d_normal=normal, d_weights=q.weights, d_pixels=q.pixels, max_dist=plan.max_dist,
-                            nphotons=plan.nphotons, spp=self.spp, stream=stream)
-        host = cnts.tolist()
-        return (n, host[1]), None if last else out.first(host[5])
-
-    def _level_lights_path(self, plan, q, level, last, rgb=None):
-        """One level as ONE launch of mr_trace_level_lights_path (then mr_gather_level, with photon maps); returns (rays, shadow
-        rays) and the next queue (None after the last).  With an environment the children carry their low-res byte.  rgb: the
-        pixels the level adds to (None: d_slots)."""
-        sc, n, stream = self.scene, q.n, plan.stream
-        rgb = self.d_slots if rgb is None else rgb
-        f32 = dict(dtype=torch.float32, device=self.device)
-        hits = normal = None
-        if plan.photon_maps is not None:                # the photon term reads the level's hit records (and bumped normals)
-            hits = self.d_hits if level == 0 else torch.empty((n, 4), **f32)
-            normal = torch.empty((n, 3), **f32) if plan.surface else None
-        cnts = torch.zeros(6, dtype=torch.int64, device=self.device)        # the call's five counters, children
-        out = NO_QUEUE if last else self._children(plan, n)
-        if not last and plan.environment:
+        if plan.path_tracing and not last and plan.environment:
             out = out._replace(low=torch.empty(out.n, dtype=torch.uint8, device=self.device))
-        sc.trace_level_lights_path(q.rays, q.weights, q.pixels, q.ids, n, rgb,
-                                   children=binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_PATH, environment=plan.environment,
-                                   d_hits=hits, d_normal=normal, d_out_rays=out.rays, d_out_weights=out.weights,
-                                   d_out_pixels=out.pixels, d_out_ids=out.ids, d_out_count=None if last else cnts[5:],
-                                   d_counts=cnts[:5], spp=self.spp, flags=plan.level_flags(level)[2], seed=plan.path_seed, bounce=level,
-                                   kinds=plan.path_kinds, stream=stream, d_lowres=q.low, d_out_lowres=out.low)
+        return hits, normal, cnts, out
+
+    def _gather(self, plan, q, hits, normal, rgb):
+        """The photon-map term of a level, where the plan has maps: mr_gather_level on the level's queue and hit records"""
         if plan.photon_maps is not None:
-            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), rgb,
-                            d_normal=normal, d_weights=q.weights, d_pixels=q.pixels, max_dist=plan.max_dist,
-                            nphotons=plan.nphotons, spp=self.spp, stream=stream)
+            scratch = torch.empty(12 * q.n, dtype=torch.float32, device=self.device)
+            self.scene.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, q.n, scratch, rgb, d_normal=normal,
+                                    d_weights=q.weights, d_pixels=q.pixels, max_dist=plan.max_dist, nphotons=plan.nphotons,
+                                    spp=self.spp, stream=plan.stream)
+
+    def _level_lights(self, plan, q, level, last, rgb=None):
+        """One level as ONE launch of mr_trace_level_lights or, under path tracing, of mr_trace_level_lights_path (then
+        mr_gather_level, with photon maps); returns (rays, shadow rays) and the next queue (None after the last).  rgb: the
+        pixels the level adds to (None: d_slots)."""
+        rgb = self.d_slots if rgb is None else rgb
+        hits, normal, cnts, out = self._level_buffers(plan, q.n, level, last)
+        common = dict(environment=plan.environment, d_hits=hits, d_normal=normal, d_out_rays=out.rays, d_out_weights=out.weights,
+                      d_out_pixels=out.pixels, d_out_count=None if last else cnts[5:], d_counts=cnts[:5], spp=self.spp,
+                      flags=plan.level_flags(level)[2], stream=plan.stream)
+        if plan.path_tracing:
+            self.scene.trace_level_lights_path(q.rays, q.weights, q.pixels, q.ids, q.n, rgb,
+                                               children=binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_PATH, d_out_ids=out.ids,
+                                               seed=plan.path_seed, bounce=level, kinds=plan.path_kinds, d_lowres=q.low,
+                                               d_out_lowres=out.low, **common)
+        else:
+            self.scene.trace_level_lights(q.rays, q.weights, q.pixels, q.n, rgb,
+                                          children=binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_SPECULAR, **common)
+        self._gather(plan, q, hits, normal, rgb)
         host = cnts.tolist()
-        return (n, host[1]), None if last else out.first(host[5])
+        return (q.n, host[1]), None if last else out.first(host[5])
 
     def _frame_levels(self, plan, depth):
-        """fused="frame_lights" | "frame_lights_path": level 0 as _frame_level0, the further levels as _level_lights /
-        _level_lights_path on its children, adding into d_rgb; returns (rays, shadow rays) per level."""
+        """fused="frame_lights" | "frame_lights_path": level 0 as _frame_level0, the further levels as _level_lights on its
+        children, adding into d_rgb; returns (rays, shadow rays) per level."""
         if self.n == 0 or depth < 0:
             return []
         counts, queue = self._frame_level0(plan, depth == 0)
         per_level = [counts]
-        step = self._level_lights_path if plan.fused == "frame_lights_path" else self._level_lights
         for level in range(1, depth + 1):
             if queue.n == 0:
                 break
-            counts, queue = step(plan, queue, level, level == depth, rgb=self.d_rgb)
+            counts, queue = self._level_lights(plan, queue, level, level == depth, rgb=self.d_rgb)
             per_level.append(counts)
         return per_level
 
     def _frame_level0(self, plan, last):
         """Level 0 as ONE mr_render_level_lights straight into d_rgb (then mr_gather_level, with photon maps, on generate()'s
         rays); returns (rays, shadow rays) from the launch's counters and the queue of level 1 (None after the last)."""
-        sc, n, stream = self.scene, self.n, plan.stream
-        path = plan.fused == "frame_lights_path"
-        f32 = dict(dtype=torch.float32, device=self.device)
-        hits = normal = None
-        if plan.photon_maps is not None:                # the photon term reads level 0's rays, hit records (and bumped normals)
-            self.generate(stream)
-            hits = self.d_hits
-            normal = torch.empty((n, 3), **f32) if plan.surface else None
-        cnts = torch.zeros(6, dtype=torch.int64, device=self.device)        # the call's five counters, children
-        out = NO_QUEUE if last else self._children(plan, n)
-        if path and not last and plan.environment:
-            out = out._replace(low=torch.empty(out.n, dtype=torch.uint8, device=self.device))
+        if plan.photon_maps is not None:                # the photon term reads level 0's rays
+            self.generate(plan.stream)
+        hits, normal, cnts, out = self._level_buffers(plan, self.n, 0, last)
         (y0, y1), = self.bands
-        children = binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_PATH if path else binding.MR_LEVEL_SPECULAR
-        sc.render_level_lights(self.cam, self.W, self.H, self.d_rgb, y0=y0, y1=y1, spp=self.spp, jitter=self.jitter, seed=self.seed,
-                               tiled=self.tiled, flags=plan.level_flags(0)[2], d_hits=hits, d_sample_normal=normal, d_counts=cnts[:5],
-                               stream=stream, children=children, environment=plan.environment, kinds=plan.path_kinds,
-                               path_seed=plan.path_seed, d_out_rays=out.rays, d_out_weights=out.weights, d_out_pixels=out.pixels,
-                               d_out_ids=out.ids, d_out_count=None if last else cnts[5:], d_out_lowres=out.low)
-        if plan.photon_maps is not None:
-            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], self.d_rays, hits, n, torch.empty(12 * n, **f32), self.d_rgb,
-                            d_normal=normal, max_dist=plan.max_dist, nphotons=plan.nphotons, spp=self.spp, stream=stream)
+        children = binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_PATH if plan.path_tracing else binding.MR_LEVEL_SPECULAR
+        self.scene.render_level_lights(self.cam, self.W, self.H, self.d_rgb, y0=y0, y1=y1, spp=self.spp, jitter=self.jitter,
+                                       seed=self.seed, tiled=self.tiled, flags=plan.level_flags(0)[2], d_hits=hits,
+                                       d_sample_normal=normal, d_counts=cnts[:5], stream=plan.stream, children=children,
+                                       environment=plan.environment, kinds=plan.path_kinds, path_seed=plan.path_seed,
+                                       d_out_rays=out.rays, d_out_weights=out.weights, d_out_pixels=out.pixels, d_out_ids=out.ids,
+                                       d_out_count=None if last else cnts[5:], d_out_lowres=out.low)
+        self._gather(plan, Queue(self.d_rays, None, None, None, None, self.n), hits, normal, self.d_rgb)
         host = cnts.tolist()
         return (host[0], host[1]), None if last else out.first(host[5])
 
@@ -766,10 +737,7 @@ class FrameRenderer:
             sc.hit_surface(q.rays, hits, n, color, normal, stream=stream)
         cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._shade(plan, q, hits, color, normal, cnt, level)
-        if plan.photon_maps is not None:
-            sc.gather_level(plan.photon_maps[0], plan.photon_maps[1], q.rays, hits, n, torch.empty(12 * n, **f32), self.d_slots,
-                            d_normal=normal if plan.surface else None, d_weights=q.weights, d_pixels=q.pixels,
-                            max_dist=plan.max_dist, nphotons=plan.nphotons, spp=self.spp, stream=stream)
+        self._gather(plan, q, hits, normal if plan.surface else None, self.d_slots)
         counts = (n, int(cnt.item()))
         return counts, None if last else self._generate(plan, q, hits, color, normal, level)
 

@@ -100,11 +100,10 @@ def timed(step):
 
 
 # every level of either route is one step of the driver: the launch, the allocation of its counters and queue before it and the
-# read-back of the counters after it.  Level 0 is _level_lights[_path] on the level route and _frame_level0 on the frame route, timed
+# read-back of the counters after it.  Level 0 is _level_lights on the level route and _frame_level0 on the frame route, timed
 # alike (as tools/level_lights_path_probe.py times its steps)
 for fr in renderers.values():
-    fr._level_lights, fr._level_lights_path = timed(fr._level_lights), timed(fr._level_lights_path)
-    fr._frame_level0 = timed(fr._frame_level0)
+    fr._level_lights, fr._frame_level0 = timed(fr._level_lights), timed(fr._frame_level0)
 lean = renderers[FRAME]
 kwargs = dict(path_tracing=True, path_kinds=KINDS, path_seed=29) if LEVEL == "lights_path" else {}
 

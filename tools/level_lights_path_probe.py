@@ -93,7 +93,7 @@ def timed(step):
     return run
 
 
-fr._level_lights_path, fr._level_batched = timed(fr._level_lights_path), timed(fr._level_batched)
+fr._level_lights, fr._level_batched = timed(fr._level_lights), timed(fr._level_batched)
 FUSED = "lights_path"
 
 
