@@ -1470,6 +1470,140 @@ mr_status mr_render_level_lights(mr_scene *s, const mr_frame_desc *frame, const 
                                      static_cast<hipStream_t>(stream));
 }
 
+// The workspace of mr_render_recursion: two queues of `cap` rays, each a run of arrays whose offsets are rounded up to 16 bytes
+// (the ray queue's alignment, which serves every other array).  The offsets of ONE queue's rays, weights, pixels, ids and low-res
+// bytes (ids / low: where the queue has none, the offset of its end) and its size in bytes
+struct RecursionQueue { uint64_t rays, weights, pixels, ids, low, bytes; };
+static RecursionQueue recursion_queue_layout(uint64_t cap, bool path, bool low) {
+    auto up = [](uint64_t v) { return (v + 15ull) & ~15ull; };
+    RecursionQueue q;
+    q.rays = 0;
+    q.weights = up(q.rays + 32ull * cap);
+    q.pixels = up(q.weights + 12ull * cap);
+    q.ids = up(q.pixels + 4ull * cap);
+    q.low = path ? up(q.ids + 4ull * cap) : q.ids;
+    q.bytes = path && low ? up(q.low + cap) : q.low;
+    return q;
+}
+// what mr_render_recursion_workspace and mr_render_recursion ask of the descriptor alone, in this order
+static mr_status check_recursion_desc(const char *who, const mr_recursion_desc *rd) {
+    if (!rd) return fail(MR_ERR_INVALID, "%s: NULL argument (desc)", who);
+    if (rd->depth > 64) return fail(MR_ERR_INVALID, "%s: depth must be 64 at most", who);
+    if (rd->environment > 1) return fail(MR_ERR_INVALID, "%s: environment must be 0 or 1", who);
+    for (int k = 0; k < 5; k++)
+        if (rd->reserved[k] != 0) return fail(MR_ERR_INVALID, "%s: mr_recursion_desc.reserved must be 0", who);
+    if (rd->depth == 0) return MR_OK;
+    if (rd->children != MR_LEVEL_SPECULAR && rd->children != MR_LEVEL_PATH)
+        return fail(MR_ERR_INVALID, "%s: children must be MR_LEVEL_SPECULAR or MR_LEVEL_PATH", who);
+    if (rd->children == MR_LEVEL_PATH && (rd->path_kinds == 0 || (rd->path_kinds & ~7u)))
+        return fail(MR_ERR_INVALID, "%s: path_kinds must be a combination of MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE", who);
+    if (rd->queue_capacity_lo == 0 && rd->queue_capacity_hi == 0)
+        return fail(MR_ERR_INVALID, "%s: queue_capacity is 0 (room for %u rays per sample always suffices for level 1)", who,
+                    rd->children == MR_LEVEL_PATH ? 4u : 3u);
+    if (rd->queue_capacity_hi != 0)
+        return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 rays per queue", who);
+    return MR_OK;
+}
+
+mr_status mr_render_recursion_workspace(const mr_recursion_desc *desc, uint64_t *bytes) {
+    const char *who = "mr_render_recursion_workspace";
+    if (!bytes) return fail(MR_ERR_INVALID, "%s: NULL argument (bytes)", who);
+    const mr_status st = check_recursion_desc(who, desc);
+    if (st != MR_OK) return st;
+    *bytes = desc->depth == 0 ? 0ull
+                              : 2ull * recursion_queue_layout(desc->queue_capacity_lo, desc->children == MR_LEVEL_PATH, desc->environment != 0).bytes;
+    return MR_OK;
+}
+
+// The whole recursive frame on one stream (include/miro_hip_recursion.h): the zeroing kernel, mr_render_level_lights' launcher for
+// level 0, then one queued level kernel (mr_level_lights_queued.hip) per further level, whose queue length is the word the level
+// before counted its children into.  The argument checks of mr_render_level_lights under this call's name, then this call's own,
+// all before the scene's state is read; then the state and the uploads; then nothing but launches.
+mr_status mr_render_recursion(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, float *d_rgb, void *d_workspace,
+                              uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
+    const char *who = "mr_render_recursion";
+    mr_frame_desc fd;
+    mr_status st = check_render_lights_args(who, s, frame, fd, d_rgb, nullptr, nullptr, false, d_level_counts);
+    if (st != MR_OK) return st;
+    if (!d_level_counts) return fail(MR_ERR_INVALID, "%s: NULL argument (d_level_counts)", who);
+    if (fd.flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT))
+        return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT only (the shadow rays are closest-hit, as in "
+                                    "mr_trace_level_lights)", who);
+    if ((st = check_recursion_desc(who, desc)) != MR_OK) return st;
+    const bool path = desc->children == MR_LEVEL_PATH, low = path && desc->environment != 0;
+    const uint64_t cap = desc->queue_capacity_lo;
+    const unsigned fan = path ? 4u : 3u;
+    unsigned long long samples = 0;
+    RecursionQueue q = {};
+    if (desc->depth > 0) {
+        if ((st = frame_level_lights_samples(who, fd, samples)) != MR_OK) return st;
+        if (samples > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 samples per call with children", who);
+        q = recursion_queue_layout(cap, path, desc->environment != 0);
+        if (!d_workspace || misaligned(16, d_workspace))
+            return fail(MR_ERR_INVALID, "%s: depth >= 1 needs a workspace, 16-byte aligned (mr_render_recursion_workspace)", who);
+        if (workspace_bytes < 2ull * q.bytes)
+            return fail(MR_ERR_INVALID, "%s: workspace_bytes is %llu, two queues of %llu rays need %llu (mr_render_recursion_workspace)", who,
+                        (unsigned long long)workspace_bytes, (unsigned long long)cap, 2ull * (unsigned long long)q.bytes);
+    }
+    if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
+    TexParams tex;
+    EnvParams env;
+    if ((st = lights_scene_params(s, desc->environment != 0, stream, tex, env)) != MR_OK) return st;
+
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_level_counts);
+    const ShadeLight *lights = s->lights.data();
+    const uint32_t n_lights = (uint32_t)s->lights.size();
+    if ((st = launch_zero_words(counts, 8ull * (desc->depth + 1ull), hs)) != MR_OK) return st;
+    if (desc->depth == 0)
+        return launch_frame_lights_env(s->dev, tex, env, lights, n_lights, fd, d_rgb, nullptr, nullptr, nullptr, nullptr, counts, hs);
+
+    // queue `w` of the workspace, array by array
+    struct Arrays { mr_ray *rays; float *weights; uint32_t *pixels, *ids; uint8_t *low; } qs[2];
+    for (int w = 0; w < 2; w++) {
+        uint8_t *base = static_cast<uint8_t *>(d_workspace) + (uint64_t)w * q.bytes;
+        qs[w].rays = reinterpret_cast<mr_ray *>(base + q.rays);
+        qs[w].weights = reinterpret_cast<float *>(base + q.weights);
+        qs[w].pixels = reinterpret_cast<uint32_t *>(base + q.pixels);
+        qs[w].ids = path ? reinterpret_cast<uint32_t *>(base + q.ids) : nullptr;
+        qs[w].low = low ? base + q.low : nullptr;
+    }
+    mr_frame_level_desc l0 = {};
+    l0.children = desc->children; l0.environment = desc->environment;
+    l0.path_kinds = desc->path_kinds; l0.path_seed = desc->path_seed;
+    l0.out_capacity_lo = desc->queue_capacity_lo; l0.out_capacity_hi = 0;
+    l0.d_out_lowres = qs[0].low;
+    if ((st = launch_frame_level_lights(s->dev, tex, env, lights, n_lights, fd, l0, d_rgb, nullptr, nullptr, nullptr, nullptr, qs[0].rays,
+                                        qs[0].weights, qs[0].pixels, qs[0].ids, &counts[5], counts, hs)) != MR_OK)
+        return st;
+
+    const uint32_t level_flags = (fd.flags & MR_MATH_PRODUCT) | MR_TRACE_INCOHERENT;     // a bounce queue is compacted in wave order
+    unsigned long long bound = samples;                                                   // fan^l x samples, saturating at the capacity
+    for (uint32_t l = 1; l <= desc->depth; l++) {
+        bound = bound > cap / fan ? cap : bound * fan;
+        const Arrays &in = qs[(l - 1) & 1], &out = qs[l & 1];
+        const bool last = l == desc->depth;
+        unsigned long long *row = counts + 8ull * l;
+        if (path) {
+            mr_level_lights_path_desc ld = {};
+            ld.spp = fd.spp; ld.flags = level_flags; ld.children = last ? MR_LEVEL_LAST : MR_LEVEL_PATH; ld.environment = desc->environment;
+            ld.path_kinds = desc->path_kinds; ld.seed = desc->path_seed; ld.bounce = l;
+            ld.out_capacity_lo = desc->queue_capacity_lo;
+            ld.d_lowres = in.low; ld.d_out_lowres = last ? nullptr : out.low;
+            st = launch_level_lights_path_queued(s->dev, tex, env, lights, n_lights, ld, in.rays, in.weights, in.pixels, in.ids, row - 8 + 5, cap,
+                                                 bound, d_rgb, out.rays, out.weights, out.pixels, out.ids, row + 5, row, hs);
+        } else {
+            mr_level_lights_desc ld = {};
+            ld.spp = fd.spp; ld.flags = level_flags; ld.children = last ? MR_LEVEL_LAST : MR_LEVEL_SPECULAR; ld.environment = desc->environment;
+            ld.out_capacity_lo = desc->queue_capacity_lo;
+            st = launch_level_lights_queued(s->dev, tex, env, lights, n_lights, ld, in.rays, in.weights, in.pixels, row - 8 + 5, cap, bound,
+                                            d_rgb, out.rays, out.weights, out.pixels, row + 5, row, hs);
+        }
+        if (st != MR_OK) return st;
+    }
+    return MR_OK;
+}
+
 mr_status mr_gen_eye_rays_lens(mr_scene *s, const mr_camera *cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp,
                                uint32_t jitter, uint32_t seed, mr_ray *d_rays, void *stream, const mr_lens_desc *lens,
                                const float *d_samples_in, float *d_samples_out, uint64_t *d_counts) {

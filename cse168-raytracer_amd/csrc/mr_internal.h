@@ -338,6 +338,25 @@ mr_status launch_frame_level_lights(const DeviceScene &ds, const TexParams &tex,
                                     float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, mr_ray *d_out_rays,
                                     float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_out_count,
                                     unsigned long long *d_counts, hipStream_t stream);
+// the two level launches for a queue whose length is a device word (mr_level_lights_queued.hip, mr_render_recursion): the queue
+// holds min(*d_n, n_cap) rays, read by the kernel; the grid is level_lights_queued_grid(n_cap, n_bound) workgroups, n_bound being
+// what the host knows the length cannot exceed, and workgroups beyond the length leave at once.  No per-ray outputs besides the
+// pixels; d_out_count is NOT zeroed (launch_zero_words: d_words[0 .. n) = 0 on `stream`, as a kernel); ONE kernel, also for an
+// empty queue.  ld.d_out_octants is not supported by the driver and passed as it is
+unsigned level_lights_queued_grid(unsigned long long n_cap, unsigned long long n_bound);
+mr_status launch_zero_words(unsigned long long *d_words, unsigned long long n, hipStream_t stream);
+mr_status launch_level_lights_queued(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
+                                     uint32_t n_lights, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
+                                     const uint32_t *d_pixels, const unsigned long long *d_n, unsigned long long n_cap,
+                                     unsigned long long n_bound, float *d_rgb, mr_ray *d_out_rays, float *d_out_weights,
+                                     uint32_t *d_out_pixels, unsigned long long *d_out_count, unsigned long long *d_counts,
+                                     hipStream_t stream);
+mr_status launch_level_lights_path_queued(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
+                                          uint32_t n_lights, const mr_level_lights_path_desc &ld, const mr_ray *d_rays,
+                                          const float *d_weights, const uint32_t *d_pixels, const uint32_t *d_ids,
+                                          const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_rgb,
+                                          mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids,
+                                          unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
 
 // the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
 // square light, side * side shadow rays per hit and light

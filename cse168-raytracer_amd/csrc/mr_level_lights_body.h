@@ -97,12 +97,15 @@ struct LevelLightsPathArgs {
 
 // VAR: the traversal variant of trace_ray (mr_traverse.h) for the ray and its shadow rays; CHILDREN: 0 none, 1 the build's own.
 // s_stack: the workgroup's dynamic LDS, [stack_depth][kTraceBlock]; s_tab: 128 words of static LDS for the two noise tables.
-template <int VAR, int CHILDREN, bool PATH, typename ARGS>
-__device__ __forceinline__ void level_lights_body(const ARGS a, int *s_stack, uint32_t (&s_tab)[128]) {
+// QUEUED: where the queue's length comes from -- false: a.tp.n, the host knows it; true: n_queued, a wave-uniform word the kernel
+// read from the device (mr_level_lights_queued.hip), and a.tp.n is not read.  A template argument and not a wrapper that hands
+// a.tp.n on: a second by-value layer around the block moves it out of the scalar registers (mr_lights_body.h).
+template <int VAR, int CHILDREN, bool PATH, bool QUEUED = false, typename ARGS>
+__device__ __forceinline__ void level_lights_body(const ARGS a, int *s_stack, uint32_t (&s_tab)[128], const unsigned long long n_queued = 0ull) {
     const NoiseTables nt = stage_noise_tables(s_tab);
     const int tid = threadIdx.x;
     const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
-    const unsigned long long n = a.tp.n;
+    const unsigned long long n = QUEUED ? n_queued : a.tp.n;
     const unsigned long long n_round = whole_workgroups(n);
     const bool table = a.t.mat_tex != nullptr;        // wave-uniform, out of the loop (hit_surface_kernel)
     const float4 *rays = reinterpret_cast<const float4 *>(a.tp.rays);

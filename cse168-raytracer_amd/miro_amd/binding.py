@@ -73,6 +73,8 @@ SURFACE_SYMBOLS = ["mr_trace_photons_surface", "mr_gather_level", "mr_photon_map
 FRAME_SYMBOLS = ["mr_render_lights_environment", "mr_trace_level_lights", "mr_trace_level_lights_path"]
 # every symbol include/miro_hip_render.h declares (the frame that emits the next level, added after that list was held at 3 names)
 RENDER_SYMBOLS = ["mr_render_level_lights"]
+# every symbol include/miro_hip_recursion.h declares (the whole recursive frame as one call, added after that list was held at 1 name)
+RECURSION_SYMBOLS = ["mr_render_recursion_workspace", "mr_render_recursion"]
 
 
 class MiroError(RuntimeError):
@@ -145,6 +147,13 @@ class FrameLevelDesc(C.Structure):
     _fields_ = [("children", C.c_uint32), ("environment", C.c_uint32), ("path_kinds", C.c_uint32), ("path_seed", C.c_uint32),
                 ("out_capacity_lo", C.c_uint32), ("out_capacity_hi", C.c_uint32), ("reserved", C.c_uint32 * 6),
                 ("d_out_octants", C.c_void_p), ("d_out_lowres", C.c_void_p)]
+
+
+class RecursionDesc(C.Structure):
+    """mr_recursion_desc (miro_hip_recursion.h): depth, children and queue capacity of mr_render_recursion"""
+    _fields_ = [("depth", C.c_uint32), ("children", C.c_uint32), ("environment", C.c_uint32), ("path_kinds", C.c_uint32),
+                ("path_seed", C.c_uint32), ("queue_capacity_lo", C.c_uint32), ("queue_capacity_hi", C.c_uint32),
+                ("reserved", C.c_uint32 * 5)]
 
 
 class Material(C.Structure):
@@ -315,6 +324,8 @@ def load_library(path=None):
     L.mr_render_lights_surface.argtypes = [vp, C.POINTER(FrameDesc), vp, vp, vp, vp, vp, vp, vp]
     L.mr_render_lights_environment.argtypes = L.mr_render_lights_surface.argtypes
     L.mr_render_level_lights.argtypes = [vp, C.POINTER(FrameDesc), C.POINTER(FrameLevelDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mr_render_recursion_workspace.argtypes = [C.POINTER(RecursionDesc), C.POINTER(C.c_uint64)]
+    L.mr_render_recursion.argtypes = [vp, C.POINTER(FrameDesc), C.POINTER(RecursionDesc), vp, vp, C.c_uint64, vp, vp]
     L.mr_tonemap.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.mr_scene_set_materials.argtypes = [vp, C.POINTER(Material), C.c_uint32, u32p]
     L.mr_shade_accumulate.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(Light), C.c_uint32, vp, vp]
@@ -366,10 +377,10 @@ def load_library(path=None):
     L.mr_irradiance_estimate.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, vp, vp, vp, vp]
     L.mr_photon_map_count_stats.argtypes = [vp, C.c_int32]
     L.mr_photon_map_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int32]
-    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS:
+    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS:
         if not hasattr(L, name):
             raise OSError("%s does not export %s" % (path, name))
-    for name in EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS:
         if hasattr(L, name) and getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = C.c_int32
     _lib = L
@@ -459,6 +470,15 @@ def _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags):
     fd.band_rows, fd.band_rank, fd.band_world = bands if bands is not None else (1, 0, 1)
     fd.spp, fd.jitter, fd.seed, fd.tiled, fd.flags = spp, 1 if jitter else 0, seed, 1 if tiled else 0, flags
     return fd
+
+
+def _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity):
+    """an mr_recursion_desc from the arguments of Scene.render_recursion / recursion_workspace_bytes"""
+    rd = RecursionDesc()
+    rd.depth, rd.children, rd.environment = depth, children, 1 if environment else 0
+    rd.path_kinds, rd.path_seed = kinds, path_seed
+    rd.queue_capacity_lo, rd.queue_capacity_hi = queue_capacity & 0xFFFFFFFF, queue_capacity >> 32
+    return rd
 
 
 def _out_capacity(given, *buffers):
@@ -833,6 +853,35 @@ class Scene:
                                              _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_out_rays), _ptr(d_out_weights),
                                              _ptr(d_out_pixels), _ptr(d_out_ids), _ptr(d_out_count), _ptr(d_counts),
                                              _stream_ptr(stream)))
+
+    def recursion_workspace_bytes(self, depth, queue_capacity, children=MR_LEVEL_SPECULAR, environment=False,
+                                  kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE):
+        """mr_render_recursion_workspace: the bytes render_recursion needs for two queues of queue_capacity rays (0 for depth 0);
+        host only."""
+        rd = _recursion_desc(depth, children, environment, kinds, 0, queue_capacity)
+        out = C.c_uint64(0)
+        _check(self.L.mr_render_recursion_workspace(C.byref(rd), C.byref(out)))
+        return out.value
+
+    def render_recursion(self, cam, W, H, d_rgb, d_level_counts, depth, d_workspace=None, queue_capacity=0, y0=0, y1=None, bands=None,
+                         spp=1, jitter=False, seed=168, tiled=False, flags=0, stream=None, children=MR_LEVEL_SPECULAR,
+                         environment=False, kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE, path_seed=168,
+                         workspace_bytes=None):
+        """mr_render_recursion: the whole recursive frame on one stream -- render_level_lights' level 0 straight into d_rgb, then
+        one level kernel per further level (trace_level_lights' with children=MR_LEVEL_SPECULAR, trace_level_lights_path's with
+        MR_LEVEL_PATH: kinds, path_seed, bounce = level) that reads the length of its queue from the count the level before
+        wrote: no read-back, no allocation and no synchronisation between the levels, so the call can be captured into a graph
+        (after a first call outside the capture, which uploads the texture table and the environment image).
+        d_level_counts: int64 [depth + 1, 8], zeroed by the call: per level rays, shadow rays, undefined texture lookups, misses,
+        undefined environment lookups, children emitted (stored or not), 0, 0.  A level whose children exceed queue_capacity was
+        truncated: read the counts once, afterwards.  d_workspace: a uint8 tensor of recursion_workspace_bytes(...) bytes (None
+        for depth 0); workspace_bytes: what to declare instead of its size."""
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
+        rd = _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity)
+        if workspace_bytes is None:
+            workspace_bytes = 0 if d_workspace is None else d_workspace.numel() * d_workspace.element_size()
+        _check(self.L.mr_render_recursion(self.h, C.byref(fd), C.byref(rd), d_rgb.data_ptr(), _ptr(d_workspace), workspace_bytes,
+                                          d_level_counts.data_ptr(), _stream_ptr(stream)))
 
     def final_gather(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb, max_dist=1e10, nphotons=500,
                      spp=1, stream=None):

@@ -302,6 +302,7 @@ class FrameRenderer:
             self.d_src = torch.empty(n, dtype=torch.int32, device=self.device)
         self.d_count = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.d_gather = None                            # final_gather's scratch, allocated on first use
+        self.d_recursion = self.d_level_counts = None   # mr_render_recursion's workspace and counters, allocated on first use
         # rgb: an external [n_pixels, 3] buffer to shade into (FrameGather.local on a multi-GPU node)
         self.d_rgb = torch.zeros((max(self.n_pixels, 1), 3), **f32) if rgb is None else rgb
         self.cam = binding.make_camera(desc["eye"], desc["lookat"], desc["up"], desc["fov"])
@@ -326,6 +327,7 @@ class FrameRenderer:
         own = [self.d_rays, self.d_hits, self.d_shadow_rays, self.d_shadow_hits, self.d_src, self.d_count, self.d_rgb]
         if self.tiled:
             own += [self.d_slots, self.d_slot_pixel]
+        own += [self.d_recursion, self.d_level_counts]
         return sum(t.numel() * t.element_size() for t in own if t is not None)
 
     def _need_rays(self, what):
@@ -421,7 +423,7 @@ class FrameRenderer:
 
     def render_specular(self, depth=10, stream=None, path_tracing=False, path_seed=168, path_kinds=None, fused=False,
                         group_octants=False, lights=None, environment=None, photon_maps=None, nphotons=500, max_dist=1e10,
-                        surface_children=None):
+                        surface_children=None, queue_capacity=None):
         """Scene::traceScene with reflective / refractive materials (Scene.cpp:270-346) as wavefront bounces: every
         level traces its queue, shades it (weight x Phong::shade added to the ray's pixel), and emits the reflect /
         Fresnel / refract children of the next level by ballot compaction.  depth = TRACE_DEPTH (Miro.h:13): rays are
@@ -500,7 +502,18 @@ class FrameRenderer:
         than one band range (fused="lights" / "lights_path") and photon_maps with tiled=True (tiled=False, or "lights" /
         "lights_path").  With photon_maps (image order) generate() runs as well, for mr_gather_level's level 0; without them a
         FrameRenderer(resident_rays=False) serves.  The same rays, children and counts per level; level 0's pixel means are
-        pairwise sums where "lights" adds atomically.  Opt-in as well: fused="auto" never chooses them."""
+        pairwise sums where "lights" adds atomically.  Opt-in as well: fused="auto" never chooses them.
+        fused="device_lights" | "device_lights_path": the frame of "frame_lights" / "frame_lights_path" as ONE library call,
+        mr_render_recursion, followed by ONE read of its counters: level 0 as there, every further level one kernel that reads the
+        length of its queue from the count the level before left on the device.  No read-back, allocation or torch op between
+        the levels (Scene.render_recursion alone can be captured into a graph).  The checks of those routes, and ValueError
+        besides with photon_maps ("frame_lights" / "frame_lights_path": mr_gather_level takes its n from the host).
+        queue_capacity: rays per queue, None: fan x samples (3 specular, 4 path traced), which always holds level 1; a level that
+        emits more children than that is truncated, and the call raises RuntimeError naming the level, its children and the
+        capacity (fan^depth x samples can never be exceeded).  The workspace (two queues) and the counters are allocated on
+        first use and kept (bytes_resident counts them).  The same rays, children and counts per level as "frame_lights[_path]",
+        cut at the first level with 0 rays; the pixel sums of levels >= 1 differ by the order of the float atomics.  Opt-in as
+        well."""
         plan = self._resolve(stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights, environment, photon_maps,
                              nphotons, max_dist, surface_children)
         # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
@@ -508,6 +521,8 @@ class FrameRenderer:
         with contextlib.nullcontext() if stream is None else torch.cuda.stream(stream):
             if plan.fused in ("frame_lights", "frame_lights_path"):
                 return self._frame_levels(plan, depth)
+            if plan.fused in ("device_lights", "device_lights_path"):
+                return self._device_levels(plan, depth, queue_capacity)
             self._need_rays("render_specular(fused=%r)" % (fused,))
             self.d_slots.zero_()
             queue = Queue(self.d_rays, None, None, None, None, self.n)      # the eye rays, in image order
@@ -529,10 +544,14 @@ class FrameRenderer:
         """render_specular's arguments and the scene's state as a LevelPlan: every check, and the two scene setters
         (set_environment, set_lights) between them"""
         sc = self.scene
-        frame_route = fused if isinstance(fused, str) and fused in ("frame_lights", "frame_lights_path") else None
+        frame_route = fused if isinstance(fused, str) and fused in ("frame_lights", "frame_lights_path", "device_lights",
+                                                                    "device_lights_path") else None
         if frame_route:
             # level 0 is mr_render_level_lights: one window of pinhole eye rays, whose children carry image-order pixels
-            level_route = frame_route[len("frame_"):]
+            level_route = frame_route[frame_route.index("_") + 1:]
+            if frame_route.startswith("device_") and photon_maps is not None:
+                raise ValueError("render_specular: photon_maps need fused=\"frame_%s\", not fused=\"%s\" (mr_gather_level takes the "
+                                 "length of its queue from the host)" % (level_route, frame_route))
             if self.lens is not None:
                 raise ValueError("render_specular: lens eye rays need the batched path (fused=False), not fused=\"%s\" "
                                  "(mr_render_level_lights makes pinhole eye rays)" % frame_route)
@@ -696,6 +715,37 @@ class FrameRenderer:
                 break
             counts, queue = self._level_lights(plan, queue, level, level == depth, rgb=self.d_rgb)
             per_level.append(counts)
+        return per_level
+
+    def _device_levels(self, plan, depth, queue_capacity):
+        """fused="device_lights" | "device_lights_path": ONE mr_render_recursion, then ONE read of its counters; returns (rays,
+        shadow rays) per level, cut at the first level without rays; RuntimeError if a level was truncated."""
+        if self.n == 0 or depth < 0:
+            return []
+        cap = plan.fan * self.n if queue_capacity is None else int(queue_capacity)
+        children = binding.MR_LEVEL_PATH if plan.path_tracing else binding.MR_LEVEL_SPECULAR
+        need = self.scene.recursion_workspace_bytes(depth, cap, children=children, environment=plan.environment,
+                                                    kinds=plan.path_kinds)
+        if self.d_recursion is None or self.d_recursion.numel() < need:
+            self.d_recursion = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        if self.d_level_counts is None or self.d_level_counts.shape[0] < depth + 1:
+            self.d_level_counts = torch.zeros((depth + 1, 8), dtype=torch.int64, device=self.device)
+        (y0, y1), = self.bands
+        self.scene.render_recursion(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth,
+                                    d_workspace=self.d_recursion if depth > 0 else None, queue_capacity=cap, y0=y0, y1=y1,
+                                    spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled,
+                                    flags=plan.level_flags(0)[2], stream=plan.stream, children=children,
+                                    environment=plan.environment, kinds=plan.path_kinds, path_seed=plan.path_seed,
+                                    workspace_bytes=need)
+        host = self.d_level_counts[:depth + 1].tolist()             # the one read-back of the frame
+        per_level = []
+        for level, row in enumerate(host):
+            if row[0] == 0:
+                break
+            per_level.append((row[0], row[1]))
+            if level < depth and row[5] > cap:
+                raise RuntimeError("render_specular: level %d emitted %d children, queue_capacity is %d: the frame was truncated "
+                                   "(%d x the samples always suffice)" % (level, row[5], cap, plan.fan ** depth))
         return per_level
 
     def _frame_level0(self, plan, last):

@@ -64,4 +64,5 @@ mr_status mr_render_level_lights(mr_scene *scene, const mr_frame_desc *frame, co
 #ifdef __cplusplus
 }
 #endif
+#include "miro_hip_recursion.h"       /* the whole recursive frame as one call, which chains the call above with the level kernels */
 #endif /* MIRO_HIP_RENDER_H */
