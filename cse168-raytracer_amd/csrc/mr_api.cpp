@@ -1591,15 +1591,188 @@ mr_status mr_render_recursion(mr_scene *s, const mr_frame_desc *frame, const mr_
             ld.out_capacity_lo = desc->queue_capacity_lo;
             ld.d_lowres = in.low; ld.d_out_lowres = last ? nullptr : out.low;
             st = launch_level_lights_path_queued(s->dev, tex, env, lights, n_lights, ld, in.rays, in.weights, in.pixels, in.ids, row - 8 + 5, cap,
-                                                 bound, d_rgb, out.rays, out.weights, out.pixels, out.ids, row + 5, row, hs);
+                                                 bound, d_rgb, nullptr, nullptr, out.rays, out.weights, out.pixels, out.ids, row + 5, row, hs);
         } else {
             mr_level_lights_desc ld = {};
             ld.spp = fd.spp; ld.flags = level_flags; ld.children = last ? MR_LEVEL_LAST : MR_LEVEL_SPECULAR; ld.environment = desc->environment;
             ld.out_capacity_lo = desc->queue_capacity_lo;
             st = launch_level_lights_queued(s->dev, tex, env, lights, n_lights, ld, in.rays, in.weights, in.pixels, row - 8 + 5, cap, bound,
-                                            d_rgb, out.rays, out.weights, out.pixels, row + 5, row, hs);
+                                            d_rgb, nullptr, nullptr, out.rays, out.weights, out.pixels, row + 5, row, hs);
         }
         if (st != MR_OK) return st;
+    }
+    return MR_OK;
+}
+
+// The workspace of mr_render_recursion_photons behind the two queues: hit records, normals and mr_gather_level's scratch for M
+// rays, M = max(samples, depth >= 1 ? queue_capacity : 0); each array's size rounded up to 16 bytes (offsets from the queues' end)
+struct RecursionPhotonsLayout { uint64_t queues, hits, normals, scratch, bytes; };
+static RecursionPhotonsLayout recursion_photons_layout(const mr_recursion_desc &rd, uint64_t samples) {
+    auto up = [](uint64_t v) { return (v + 15ull) & ~15ull; };
+    const uint64_t cap = rd.depth > 0 ? rd.queue_capacity_lo : 0ull, M = samples > cap ? samples : cap;
+    RecursionPhotonsLayout w;
+    w.queues = rd.depth == 0 ? 0ull : 2ull * recursion_queue_layout(cap, rd.children == MR_LEVEL_PATH, rd.environment != 0).bytes;
+    w.hits = w.queues;
+    w.normals = w.hits + up(16ull * M);
+    w.scratch = w.normals + up(12ull * M);
+    w.bytes = w.scratch + up(48ull * M);
+    return w;
+}
+// what both calls ask of the two descriptors, in this order: the frame's window, the descriptor's words, then what the photon
+// term adds -- image order, and no more rays per level than one estimate launch answers.  fd: the frame as the launchers take it
+static mr_status check_recursion_photons_descs(const char *who, const mr_frame_desc *frame, const mr_recursion_desc *desc, mr_frame_desc &fd,
+                                               unsigned long long &samples) {
+    if (!frame) return fail(MR_ERR_INVALID, "%s: NULL argument (frame)", who);
+    if (frame->W == 0 || frame->H == 0) return fail(MR_ERR_INVALID, "%s: empty image", who);
+    fd = *frame;
+    if (fd.band_world <= 1) { fd.band_world = 1; fd.band_rank = 0; if (fd.band_rows == 0) fd.band_rows = 1; }
+    mr_status st = check_frame_lights(who, fd);
+    if (st != MR_OK || (st = check_recursion_desc(who, desc)) != MR_OK) return st;
+    if (fd.tiled)
+        return fail(MR_ERR_INVALID, "%s: tiled sample order (level 0's photon term finds its pixel from the sample index, in image "
+                                    "order); use tiled = 0", who);
+    if ((st = frame_level_lights_samples(who, fd, samples)) != MR_OK) return st;
+    if (samples >= (1ull << 31) || (desc->depth > 0 && desc->queue_capacity_lo >= (1u << 31)))
+        return fail(MR_ERR_INVALID, "%s: at most 2^31 - 1 samples and a queue_capacity of at most 2^31 - 1 (one estimate launch answers "
+                                    "at most 2^31 - 1 queries)", who);
+    return MR_OK;
+}
+
+mr_status mr_render_recursion_photons_workspace(const mr_frame_desc *frame, const mr_recursion_desc *desc, uint64_t *bytes) {
+    const char *who = "mr_render_recursion_photons_workspace";
+    if (!bytes) return fail(MR_ERR_INVALID, "%s: NULL argument (bytes)", who);
+    mr_frame_desc fd;
+    unsigned long long samples = 0;
+    const mr_status st = check_recursion_photons_descs(who, frame, desc, fd, samples);
+    if (st != MR_OK) return st;
+    *bytes = recursion_photons_layout(*desc, samples).bytes;
+    return MR_OK;
+}
+
+// mr_render_recursion with the photon-map term after every level (include/miro_hip_recursion_photons.h): its sequence of launches,
+// restated here because every level launch also gets the workspace's hit and normal buffers, and after each level the three
+// kernels of mr_gather_queued.hip on that level's queue.  The argument checks first, all of them before the scene's or a map's
+// state is read; then the state and the uploads; then nothing but launches.
+mr_status mr_render_recursion_photons(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, mr_photon_map *global_map,
+                                      mr_photon_map *caustic_map, float max_dist, uint32_t nphotons, float *d_rgb, void *d_workspace,
+                                      uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
+    const char *who = "mr_render_recursion_photons";
+    mr_frame_desc fd;
+    mr_status st = check_render_lights_args(who, s, frame, fd, d_rgb, nullptr, nullptr, false, d_level_counts);
+    if (st != MR_OK) return st;
+    if (!d_level_counts) return fail(MR_ERR_INVALID, "%s: NULL argument (d_level_counts)", who);
+    if (fd.flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT))
+        return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT only (the shadow rays are closest-hit, as in "
+                                    "mr_trace_level_lights)", who);
+    unsigned long long samples = 0;
+    if ((st = check_recursion_photons_descs(who, frame, desc, fd, samples)) != MR_OK) return st;
+    mr_photon_map *maps[2] = {global_map, caustic_map};
+    if (!maps[0] && !maps[1]) return fail(MR_ERR_INVALID, "%s: NULL argument (global_map and caustic_map are both NULL)", who);
+    if (nphotons == 0 || nphotons > (uint32_t)kKnnMaxK) return fail(MR_ERR_INVALID, "%s: nphotons must be in [1, %d]", who, kKnnMaxK);
+    if (!(max_dist > 0.0f)) return fail(MR_ERR_INVALID, "%s: max_dist must be positive", who);
+    const RecursionPhotonsLayout ws = recursion_photons_layout(*desc, samples);
+    if (!d_workspace || misaligned(16, d_workspace))
+        return fail(MR_ERR_INVALID, "%s: the call needs a workspace, 16-byte aligned (mr_render_recursion_photons_workspace)", who);
+    if (workspace_bytes < ws.bytes)
+        return fail(MR_ERR_INVALID, "%s: workspace_bytes is %llu, this frame and descriptor need %llu (mr_render_recursion_photons_workspace)",
+                    who, (unsigned long long)workspace_bytes, (unsigned long long)ws.bytes);
+
+    if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
+    for (mr_photon_map *m : maps) {
+        if (m && !photon_map_resident(m)) return fail(MR_ERR_STATE, "%s: photon map is not balanced and resident on a device", who);
+        if (m && photon_map_device(m) != s->device)
+            return fail(MR_ERR_STATE, "%s: photon map lives on device %d, the scene on %d", who, photon_map_device(m), s->device);
+        if (m && photon_map_stored(m) >= (1u << 24))
+            return fail(MR_ERR_STATE, "%s: photon maps of 2^24 photons or more need a fifth layer of blocks", who);
+    }
+    TexParams tex;
+    EnvParams env;
+    if ((st = lights_scene_params(s, desc->environment != 0, stream, tex, env)) != MR_OK) return st;
+
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_level_counts);
+    const ShadeLight *lights = s->lights.data();
+    const uint32_t n_lights = (uint32_t)s->lights.size();
+    const bool path = desc->children == MR_LEVEL_PATH, low = path && desc->environment != 0;
+    const uint64_t cap = desc->queue_capacity_lo;
+    const unsigned fan = path ? 4u : 3u;
+    uint8_t *wbase = static_cast<uint8_t *>(d_workspace);
+    mr_hit *d_hits = reinterpret_cast<mr_hit *>(wbase + ws.hits);
+    // the normal Scene::trace hands on differs from the object's on a procedural texture only: elsewhere the query kernels form it
+    float *d_normal = s->tex.procedural ? reinterpret_cast<float *>(wbase + ws.normals) : nullptr;
+    float *d_scratch = reinterpret_cast<float *>(wbase + ws.scratch);
+
+    // steps 2 and 3 of a level's photon term on its queries (the level's query kernel has run): nb rays at most, mr_gather_level's
+    // scratch layout for nb; d_n / nb: the level's length as the kernels read it
+    auto estimate_and_add = [&](const unsigned long long *d_n, unsigned long long nb, const float *d_weights, const uint32_t *d_pixels) -> mr_status {
+        float *d_irr[2] = {nullptr, nullptr};
+        for (int i = 0; i < 2; i++) {
+            if (!maps[i]) continue;
+            d_irr[i] = d_scratch + (6 + 3 * i) * nb;
+            const mr_status e = photon_map_estimate_queued(maps[i], d_scratch, d_scratch + 3 * nb, d_n, nb, nb, max_dist, nphotons, d_irr[i], hs);
+            if (e != MR_OK) return e;
+        }
+        return launch_gather_queued_accumulate(d_irr[0], d_irr[1], d_weights, d_pixels, d_n, nb, nb, fd.spp, d_rgb, hs);
+    };
+
+    if ((st = launch_zero_words(counts, 8ull * (desc->depth + 1ull), hs)) != MR_OK) return st;
+    struct Arrays { mr_ray *rays; float *weights; uint32_t *pixels, *ids; uint8_t *low; } qs[2] = {};
+    if (desc->depth == 0) {
+        st = launch_frame_lights_env(s->dev, tex, env, lights, n_lights, fd, d_rgb, d_hits, nullptr, nullptr, d_normal, counts, hs);
+    } else {
+        const RecursionQueue q = recursion_queue_layout(cap, path, desc->environment != 0);
+        for (int w = 0; w < 2; w++) {                                      // queue `w` of the workspace, array by array
+            uint8_t *base = wbase + (uint64_t)w * q.bytes;
+            qs[w].rays = reinterpret_cast<mr_ray *>(base + q.rays);
+            qs[w].weights = reinterpret_cast<float *>(base + q.weights);
+            qs[w].pixels = reinterpret_cast<uint32_t *>(base + q.pixels);
+            qs[w].ids = path ? reinterpret_cast<uint32_t *>(base + q.ids) : nullptr;
+            qs[w].low = low ? base + q.low : nullptr;
+        }
+        mr_frame_level_desc l0 = {};
+        l0.children = desc->children; l0.environment = desc->environment;
+        l0.path_kinds = desc->path_kinds; l0.path_seed = desc->path_seed;
+        l0.out_capacity_lo = desc->queue_capacity_lo; l0.out_capacity_hi = 0;
+        l0.d_out_lowres = qs[0].low;
+        st = launch_frame_level_lights(s->dev, tex, env, lights, n_lights, fd, l0, d_rgb, d_hits, nullptr, nullptr, d_normal, qs[0].rays,
+                                       qs[0].weights, qs[0].pixels, qs[0].ids, &counts[5], counts, hs);
+    }
+    if (st != MR_OK) return st;
+    // level 0's photon term: its length is the window's, which the frame has added to counts[0]; weight 1, pixel k / spp
+    if ((st = launch_gather_eye_queries(s->dev, who, fd, d_hits, d_normal, d_scratch, d_scratch + 3 * samples, &counts[6], hs)) != MR_OK ||
+        (st = estimate_and_add(&counts[0], samples, nullptr, nullptr)) != MR_OK)
+        return st;
+
+    const uint32_t level_flags = (fd.flags & MR_MATH_PRODUCT) | MR_TRACE_INCOHERENT;     // a bounce queue is compacted in wave order
+    unsigned long long bound = samples;                                                   // fan^l x samples, saturating at the capacity
+    for (uint32_t l = 1; l <= desc->depth; l++) {
+        bound = bound > cap / fan ? cap : bound * fan;
+        const Arrays &in = qs[(l - 1) & 1], &out = qs[l & 1];
+        const bool last = l == desc->depth;
+        unsigned long long *row = counts + 8ull * l;
+        const unsigned long long *d_n = row - 8 + 5;                                      // the children level l - 1 counted
+        if (path) {
+            mr_level_lights_path_desc ld = {};
+            ld.spp = fd.spp; ld.flags = level_flags; ld.children = last ? MR_LEVEL_LAST : MR_LEVEL_PATH; ld.environment = desc->environment;
+            ld.path_kinds = desc->path_kinds; ld.seed = desc->path_seed; ld.bounce = l;
+            ld.out_capacity_lo = desc->queue_capacity_lo;
+            ld.d_lowres = in.low; ld.d_out_lowres = last ? nullptr : out.low;
+            st = launch_level_lights_path_queued(s->dev, tex, env, lights, n_lights, ld, in.rays, in.weights, in.pixels, in.ids, d_n, cap, bound,
+                                                 d_rgb, d_hits, d_normal, out.rays, out.weights, out.pixels, out.ids, row + 5, row, hs);
+        } else {
+            mr_level_lights_desc ld = {};
+            ld.spp = fd.spp; ld.flags = level_flags; ld.children = last ? MR_LEVEL_LAST : MR_LEVEL_SPECULAR; ld.environment = desc->environment;
+            ld.out_capacity_lo = desc->queue_capacity_lo;
+            st = launch_level_lights_queued(s->dev, tex, env, lights, n_lights, ld, in.rays, in.weights, in.pixels, d_n, cap, bound, d_rgb,
+                                            d_hits, d_normal, out.rays, out.weights, out.pixels, row + 5, row, hs);
+        }
+        if (st != MR_OK) return st;
+        // the level's photon term, before level l + 1 overwrites the hit records and (two levels on) this queue.  bound <= cap:
+        // the kernels take it as the capacity, so that no index reaches beyond the scratch laid out for `bound` rays
+        if ((st = launch_gather_queued_queries(s->dev, in.rays, d_hits, d_normal, d_n, bound, bound, d_scratch, d_scratch + 3 * bound, row + 6,
+                                               hs)) != MR_OK ||
+            (st = estimate_and_add(d_n, bound, in.weights, in.pixels)) != MR_OK)
+            return st;
     }
     return MR_OK;
 }

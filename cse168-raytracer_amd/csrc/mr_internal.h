@@ -340,23 +340,24 @@ mr_status launch_frame_level_lights(const DeviceScene &ds, const TexParams &tex,
                                     unsigned long long *d_counts, hipStream_t stream);
 // the two level launches for a queue whose length is a device word (mr_level_lights_queued.hip, mr_render_recursion): the queue
 // holds min(*d_n, n_cap) rays, read by the kernel; the grid is level_lights_queued_grid(n_cap, n_bound) workgroups, n_bound being
-// what the host knows the length cannot exceed, and workgroups beyond the length leave at once.  No per-ray outputs besides the
-// pixels; d_out_count is NOT zeroed (launch_zero_words: d_words[0 .. n) = 0 on `stream`, as a kernel); ONE kernel, also for an
+// what the host knows the length cannot exceed, and workgroups beyond the length leave at once.  Per-ray outputs besides the pixels:
+// d_hits and d_normal, both optional (the photon-map term of mr_render_recursion_photons reads them); d_out_count is NOT zeroed (launch_zero_words: d_words[0 .. n) = 0 on `stream`, as a kernel); ONE kernel, also for an
 // empty queue.  ld.d_out_octants is not supported by the driver and passed as it is
 unsigned level_lights_queued_grid(unsigned long long n_cap, unsigned long long n_bound);
 mr_status launch_zero_words(unsigned long long *d_words, unsigned long long n, hipStream_t stream);
 mr_status launch_level_lights_queued(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
                                      uint32_t n_lights, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
                                      const uint32_t *d_pixels, const unsigned long long *d_n, unsigned long long n_cap,
-                                     unsigned long long n_bound, float *d_rgb, mr_ray *d_out_rays, float *d_out_weights,
-                                     uint32_t *d_out_pixels, unsigned long long *d_out_count, unsigned long long *d_counts,
-                                     hipStream_t stream);
+                                     unsigned long long n_bound, float *d_rgb, mr_hit *d_hits, float *d_normal, mr_ray *d_out_rays,
+                                     float *d_out_weights, uint32_t *d_out_pixels, unsigned long long *d_out_count,
+                                     unsigned long long *d_counts, hipStream_t stream);
 mr_status launch_level_lights_path_queued(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
                                           uint32_t n_lights, const mr_level_lights_path_desc &ld, const mr_ray *d_rays,
                                           const float *d_weights, const uint32_t *d_pixels, const uint32_t *d_ids,
                                           const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_rgb,
-                                          mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids,
-                                          unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
+                                          mr_hit *d_hits, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
+                                          uint32_t *d_out_ids, unsigned long long *d_out_count, unsigned long long *d_counts,
+                                          hipStream_t stream);
 
 // the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
 // square light, side * side shadow rays per hit and light
@@ -482,6 +483,22 @@ mr_status launch_irradiance(const PhotonMapDev &pm, unsigned *work_counter, cons
                             float max_dist, uint32_t k, float *d_irrad, int32_t *d_found, float *d_r2, unsigned long long *d_stats,
                             hipStream_t stream);
 constexpr int kPhotonStats = 12;  // see mr_photon_map_get_stats (miro_hip.h)
+// The photon-map term for a queue whose length is a device word (mr_gather_queued.hip, mr_render_recursion_photons): the three
+// steps of mr_gather_level as kernels that read n = min(*d_n, n_cap) themselves.  Every grid is sized from min(n_cap, n_bound),
+// n_bound being what the host knows the length cannot exceed; nothing is launched where that is 0.  d_queries: one word, += the
+// queries made.  launch_gather_eye_queries: level 0 of the one-call frame, whose rays exist in registers only -- the eye ray of
+// sample k of fd's window is made again and joined with the hit record (and, given d_normal, the normal) the frame wrote.
+mr_status launch_gather_eye_queries(const DeviceScene &ds, const char *who, const mr_frame_desc &fd, const mr_hit *d_hits,
+                                    const float *d_normal, float *d_pos, float *d_nrm, unsigned long long *d_queries, hipStream_t stream);
+mr_status launch_gather_queued_queries(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_normal,
+                                       const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_pos,
+                                       float *d_nrm, unsigned long long *d_queries, hipStream_t stream);
+mr_status launch_irradiance_queued(const PhotonMapDev &pm, unsigned *work_counter, const float *d_pos, const float *d_normal,
+                                   const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float max_dist,
+                                   uint32_t k, float *d_irrad, unsigned long long *d_stats, hipStream_t stream);
+mr_status launch_gather_queued_accumulate(const float *d_irr_a, const float *d_irr_b, const float *d_weights, const uint32_t *d_pixels,
+                                          const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, uint32_t spp,
+                                          float *d_rgb, hipStream_t stream);
 
 // photon tracing (mr_photon_walk.hip): one round = emissions first ... first + count - 1 of one light, walked to their end
 struct PhotonWalkLight {
@@ -520,6 +537,12 @@ mr_status texture_params(mr_scene *s, hipStream_t stream, TexParams &p);
 int32_t photon_map_device(const mr_photon_map *m);
 bool photon_map_balanced(const mr_photon_map *m);
 uint32_t photon_map_stored(const mr_photon_map *m);
+// ... and mr_render_recursion_photons: balanced and resident on a device; one queued k-NN estimate on such a map, which takes the
+// next of the map's hand-out counters and the map's statistics as mr_irradiance_estimate's launch does
+bool photon_map_resident(const mr_photon_map *m);
+mr_status photon_map_estimate_queued(mr_photon_map *m, const float *d_pos, const float *d_normal, const unsigned long long *d_n,
+                                     unsigned long long n_cap, unsigned long long n_bound, float max_dist, uint32_t nphotons,
+                                     float *d_irrad, hipStream_t stream);
 
 // the photon map built on the device (mr_photon_build.hip; mr_photon_map_build_device): store + scale + balance of one batch of
 // records on an empty map.  The workspace lives from _begin to _end; the stages run in the order declared.

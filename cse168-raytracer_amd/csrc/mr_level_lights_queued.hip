@@ -102,11 +102,11 @@ mr_status launch_zero_words(unsigned long long *d_words, unsigned long long n, h
 mr_status launch_level_lights_queued(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
                                      uint32_t n_lights, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
                                      const uint32_t *d_pixels, const unsigned long long *d_n, unsigned long long n_cap,
-                                     unsigned long long n_bound, float *d_rgb, mr_ray *d_out_rays, float *d_out_weights,
-                                     uint32_t *d_out_pixels, unsigned long long *d_out_count, unsigned long long *d_counts,
-                                     hipStream_t stream) {
+                                     unsigned long long n_bound, float *d_rgb, mr_hit *d_hits, float *d_normal, mr_ray *d_out_rays,
+                                     float *d_out_weights, uint32_t *d_out_pixels, unsigned long long *d_out_count,
+                                     unsigned long long *d_counts, hipStream_t stream) {
     LevelLightsArgs a;
-    fill_level_lights_args(a, ds, tex, env, lights, n_lights, ld, d_rays, d_weights, d_pixels, 0ull, d_rgb, nullptr, nullptr, nullptr, nullptr,
+    fill_level_lights_args(a, ds, tex, env, lights, n_lights, ld, d_rays, d_weights, d_pixels, 0ull, d_rgb, d_hits, nullptr, nullptr, d_normal,
                            d_out_rays, d_out_weights, d_out_pixels, nullptr, d_out_count, d_counts);
 
     // the traversal variants of launch_level_lights: the same hit records from each of them
@@ -121,10 +121,11 @@ mr_status launch_level_lights_path_queued(const DeviceScene &ds, const TexParams
                                           uint32_t n_lights, const mr_level_lights_path_desc &ld, const mr_ray *d_rays,
                                           const float *d_weights, const uint32_t *d_pixels, const uint32_t *d_ids,
                                           const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_rgb,
-                                          mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids,
-                                          unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream) {
+                                          mr_hit *d_hits, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
+                                          uint32_t *d_out_ids, unsigned long long *d_out_count, unsigned long long *d_counts,
+                                          hipStream_t stream) {
     LevelLightsPathArgs a;
-    fill_level_lights_args(a, ds, tex, env, lights, n_lights, ld, d_rays, d_weights, d_pixels, 0ull, d_rgb, nullptr, nullptr, nullptr, nullptr,
+    fill_level_lights_args(a, ds, tex, env, lights, n_lights, ld, d_rays, d_weights, d_pixels, 0ull, d_rgb, d_hits, nullptr, nullptr, d_normal,
                            d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_count, d_counts);
     a.ids = d_ids; a.lowres = ld.d_lowres;
     a.all_lowres = (ld.flags & MR_ENV_LOWRES) ? 1u : 0u;

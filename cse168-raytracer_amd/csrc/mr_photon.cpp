@@ -188,6 +188,13 @@ namespace mr {
 int32_t photon_map_device(const mr_photon_map *m) { return m->device; }
 bool photon_map_balanced(const mr_photon_map *m) { return m->balanced; }
 uint32_t photon_map_stored(const mr_photon_map *m) { return m->count(); }
+bool photon_map_resident(const mr_photon_map *m) { return m->balanced && m->on_device; }
+mr_status photon_map_estimate_queued(mr_photon_map *m, const float *d_pos, const float *d_normal, const unsigned long long *d_n,
+                                     unsigned long long n_cap, unsigned long long n_bound, float max_dist, uint32_t nphotons,
+                                     float *d_irrad, hipStream_t stream) {
+    unsigned *counter = m->dev.work_counters + (m->next_counter.fetch_add(1) % kPhotonWorkCounters);
+    return launch_irradiance_queued(m->dev, counter, d_pos, d_normal, d_n, n_cap, n_bound, max_dist, nphotons, d_irrad, m->d_stats, stream);
+}
 }  // namespace mr
 
 extern "C" {

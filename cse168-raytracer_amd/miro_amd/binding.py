@@ -75,6 +75,8 @@ FRAME_SYMBOLS = ["mr_render_lights_environment", "mr_trace_level_lights", "mr_tr
 RENDER_SYMBOLS = ["mr_render_level_lights"]
 # every symbol include/miro_hip_recursion.h declares (the whole recursive frame as one call, added after that list was held at 1 name)
 RECURSION_SYMBOLS = ["mr_render_recursion_workspace", "mr_render_recursion"]
+# ... and the two of miro_hip_recursion_photons.h, which that header includes as its last line
+RECURSION_PHOTONS_SYMBOLS = ["mr_render_recursion_photons_workspace", "mr_render_recursion_photons"]
 
 
 class MiroError(RuntimeError):
@@ -326,6 +328,9 @@ def load_library(path=None):
     L.mr_render_level_lights.argtypes = [vp, C.POINTER(FrameDesc), C.POINTER(FrameLevelDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mr_render_recursion_workspace.argtypes = [C.POINTER(RecursionDesc), C.POINTER(C.c_uint64)]
     L.mr_render_recursion.argtypes = [vp, C.POINTER(FrameDesc), C.POINTER(RecursionDesc), vp, vp, C.c_uint64, vp, vp]
+    L.mr_render_recursion_photons_workspace.argtypes = [C.POINTER(FrameDesc), C.POINTER(RecursionDesc), C.POINTER(C.c_uint64)]
+    L.mr_render_recursion_photons.argtypes = [vp, C.POINTER(FrameDesc), C.POINTER(RecursionDesc), vp, vp, C.c_float, C.c_uint32, vp, vp,
+                                              C.c_uint64, vp, vp]
     L.mr_tonemap.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.mr_scene_set_materials.argtypes = [vp, C.POINTER(Material), C.c_uint32, u32p]
     L.mr_shade_accumulate.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(Light), C.c_uint32, vp, vp]
@@ -377,10 +382,10 @@ def load_library(path=None):
     L.mr_irradiance_estimate.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, vp, vp, vp, vp]
     L.mr_photon_map_count_stats.argtypes = [vp, C.c_int32]
     L.mr_photon_map_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int32]
-    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS:
+    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS:
         if not hasattr(L, name):
             raise OSError("%s does not export %s" % (path, name))
-    for name in EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS:
         if hasattr(L, name) and getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = C.c_int32
     _lib = L
@@ -882,6 +887,37 @@ class Scene:
             workspace_bytes = 0 if d_workspace is None else d_workspace.numel() * d_workspace.element_size()
         _check(self.L.mr_render_recursion(self.h, C.byref(fd), C.byref(rd), d_rgb.data_ptr(), _ptr(d_workspace), workspace_bytes,
                                           d_level_counts.data_ptr(), _stream_ptr(stream)))
+
+    def recursion_photons_workspace_bytes(self, cam, W, H, depth, queue_capacity, y0=0, y1=None, bands=None, spp=1,
+                                          children=MR_LEVEL_SPECULAR, environment=False,
+                                          kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE):
+        """mr_render_recursion_photons_workspace: the bytes render_recursion_photons needs -- recursion_workspace_bytes(...), then
+        hit records, normals and gather_level's scratch (16 + 12 + 48 bytes) for max(samples of the window, queue_capacity if
+        depth >= 1) rays; host only."""
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, False, 0, False, 0)
+        rd = _recursion_desc(depth, children, environment, kinds, 0, queue_capacity)
+        out = C.c_uint64(0)
+        _check(self.L.mr_render_recursion_photons_workspace(C.byref(fd), C.byref(rd), C.byref(out)))
+        return out.value
+
+    def render_recursion_photons(self, cam, W, H, d_rgb, d_level_counts, depth, global_map, caustic_map, d_workspace, queue_capacity=0,
+                                 max_dist=1e10, nphotons=500, y0=0, y1=None, bands=None, spp=1, jitter=False, seed=168, tiled=False,
+                                 flags=0, stream=None, children=MR_LEVEL_SPECULAR, environment=False,
+                                 kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE, path_seed=168, workspace_bytes=None):
+        """mr_render_recursion_photons: render_recursion with the photon-map term of Scene::traceScene (Scene.cpp:286-299) after
+        every level -- gather_level's queries, estimates (global_map, caustic_map: balanced and resident, either may be None) and
+        weight x (irradiance + caustic) / spp into d_rgb, by kernels that read the length of the level's queue from the device
+        as the level kernels do.  Still one call that only enqueues, capturable after a first call outside the capture.
+        d_level_counts: as in render_recursion, with word 6 of a level = the queries made there (diffuse hits).  d_workspace: a
+        uint8 tensor of recursion_photons_workspace_bytes(...) bytes, needed at depth 0 too.  tiled must be False."""
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
+        rd = _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity)
+        if workspace_bytes is None:
+            workspace_bytes = 0 if d_workspace is None else d_workspace.numel() * d_workspace.element_size()
+        _check(self.L.mr_render_recursion_photons(self.h, C.byref(fd), C.byref(rd), global_map.h if global_map is not None else None,
+                                                  caustic_map.h if caustic_map is not None else None, max_dist, nphotons,
+                                                  d_rgb.data_ptr(), _ptr(d_workspace), workspace_bytes, d_level_counts.data_ptr(),
+                                                  _stream_ptr(stream)))
 
     def final_gather(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb, max_dist=1e10, nphotons=500,
                      spp=1, stream=None):

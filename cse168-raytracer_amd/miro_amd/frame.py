@@ -275,8 +275,8 @@ class FrameRenderer:
         (mr_shade_square_lights; level l draws its pairs with seed + l; on a scene with a texture table, procedural or not,
         mr_hit_surface and mr_shade_square_lights_surface with the same seeds).  Without either option nothing changes.
         resident_rays=False: the ray, hit and shadow buffers (100 bytes per sample) are not allocated; what is left serves
-        render_specular(fused="frame_lights" | "frame_lights_path") without photon maps, whose level 0 keeps its rays in
-        registers.  Every method that needs those buffers then raises ValueError."""
+        render_specular(fused="frame_lights" | "frame_lights_path") without photon maps and fused="device_*", whose level 0 keeps
+        its rays in registers.  Every method that needs those buffers then raises ValueError."""
         if isinstance(desc, str):
             desc = scenes.SCENES[desc]
         self.scene, self.desc, self.W, self.H, self.spp = scene, desc, W, H, spp
@@ -513,7 +513,14 @@ class FrameRenderer:
         capacity (fan^depth x samples can never be exceeded).  The workspace (two queues) and the counters are allocated on
         first use and kept (bytes_resident counts them).  The same rays, children and counts per level as "frame_lights[_path]",
         cut at the first level with 0 rays; the pixel sums of levels >= 1 differ by the order of the float atomics.  Opt-in as
-        well."""
+        well.
+        fused="device_photons" | "device_photons_path": "device_lights" / "device_lights_path" WITH photon_maps=(global, caustic), as
+        ONE mr_render_recursion_photons and one read of its counters: after every level the photon-map term of that level's queue
+        (mr_gather_level's queries, estimates and adds) by kernels that read the queue's length from the device too.  nphotons,
+        max_dist and queue_capacity as above; the workspace also holds a level's hit records, normals and the scratch of the
+        estimates.  ValueError without photon_maps, with tiled=True ("lights" / "lights_path", or tiled=False), and with what
+        "device_lights" refuses.  The same rays, children, queries and counts per level as "frame_lights[_path]" with the same
+        maps; pixel sums differ by the order of the float atomics.  Opt-in as well."""
         plan = self._resolve(stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights, environment, photon_maps,
                              nphotons, max_dist, surface_children)
         # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
@@ -521,7 +528,7 @@ class FrameRenderer:
         with contextlib.nullcontext() if stream is None else torch.cuda.stream(stream):
             if plan.fused in ("frame_lights", "frame_lights_path"):
                 return self._frame_levels(plan, depth)
-            if plan.fused in ("device_lights", "device_lights_path"):
+            if plan.fused in ("device_lights", "device_lights_path", "device_photons", "device_photons_path"):
                 return self._device_levels(plan, depth, queue_capacity)
             self._need_rays("render_specular(fused=%r)" % (fused,))
             self.d_slots.zero_()
@@ -545,11 +552,20 @@ class FrameRenderer:
         (set_environment, set_lights) between them"""
         sc = self.scene
         frame_route = fused if isinstance(fused, str) and fused in ("frame_lights", "frame_lights_path", "device_lights",
-                                                                    "device_lights_path") else None
+                                                                    "device_lights_path", "device_photons",
+                                                                    "device_photons_path") else None
         if frame_route:
             # level 0 is mr_render_level_lights: one window of pinhole eye rays, whose children carry image-order pixels
-            level_route = frame_route[frame_route.index("_") + 1:]
-            if frame_route.startswith("device_") and photon_maps is not None:
+            level_route = "lights_path" if frame_route.endswith("_path") else "lights"
+            if frame_route.startswith("device_photons"):
+                if photon_maps is None:
+                    raise ValueError("render_specular: fused=\"%s\" needs photon_maps=(global, caustic); without maps the frame is "
+                                     "fused=\"device_%s\"" % (frame_route, level_route))
+                if self.tiled:
+                    raise ValueError("render_specular: photon_maps with tiled=True need fused=\"%s\" (or tiled=False), not "
+                                     "fused=\"%s\" (mr_render_recursion_photons finds level 0's pixels from the sample index, in "
+                                     "image order)" % (level_route, frame_route))
+            if frame_route.startswith("device_lights") and photon_maps is not None:
                 raise ValueError("render_specular: photon_maps need fused=\"frame_%s\", not fused=\"%s\" (mr_gather_level takes the "
                                  "length of its queue from the host)" % (level_route, frame_route))
             if self.lens is not None:
@@ -561,7 +577,7 @@ class FrameRenderer:
             if photon_maps is not None and self.tiled:
                 raise ValueError("render_specular: photon_maps with tiled=True need fused=\"%s\" (or tiled=False), not fused=\"%s\" "
                                  "(mr_gather_level finds level 0's pixels from the ray index, in image order)" % (level_route, frame_route))
-            if photon_maps is not None:
+            if photon_maps is not None and frame_route.startswith("frame_"):
                 self._need_rays("render_specular(fused=\"%s\", photon_maps=...)" % frame_route)
             fused = level_route                 # the checks of that route hold here too; the plan carries the frame route
         level_route = fused if isinstance(fused, str) and fused in ("lights", "lights_path") else None
@@ -718,25 +734,35 @@ class FrameRenderer:
         return per_level
 
     def _device_levels(self, plan, depth, queue_capacity):
-        """fused="device_lights" | "device_lights_path": ONE mr_render_recursion, then ONE read of its counters; returns (rays,
-        shadow rays) per level, cut at the first level without rays; RuntimeError if a level was truncated."""
+        """fused="device_lights[_path]": ONE mr_render_recursion; fused="device_photons[_path]": ONE mr_render_recursion_photons with
+        the plan's maps.  Then ONE read of the counters; returns (rays, shadow rays) per level, cut at the first level without rays;
+        RuntimeError if a level was truncated."""
         if self.n == 0 or depth < 0:
             return []
+        photons = plan.fused.startswith("device_photons")
         cap = plan.fan * self.n if queue_capacity is None else int(queue_capacity)
         children = binding.MR_LEVEL_PATH if plan.path_tracing else binding.MR_LEVEL_SPECULAR
-        need = self.scene.recursion_workspace_bytes(depth, cap, children=children, environment=plan.environment,
-                                                    kinds=plan.path_kinds)
+        (y0, y1), = self.bands
+        if photons:
+            need = self.scene.recursion_photons_workspace_bytes(self.cam, self.W, self.H, depth, cap, y0=y0, y1=y1, spp=self.spp,
+                                                                children=children, environment=plan.environment, kinds=plan.path_kinds)
+        else:
+            need = self.scene.recursion_workspace_bytes(depth, cap, children=children, environment=plan.environment,
+                                                        kinds=plan.path_kinds)
         if self.d_recursion is None or self.d_recursion.numel() < need:
             self.d_recursion = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
         if self.d_level_counts is None or self.d_level_counts.shape[0] < depth + 1:
             self.d_level_counts = torch.zeros((depth + 1, 8), dtype=torch.int64, device=self.device)
-        (y0, y1), = self.bands
-        self.scene.render_recursion(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth,
-                                    d_workspace=self.d_recursion if depth > 0 else None, queue_capacity=cap, y0=y0, y1=y1,
-                                    spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled,
-                                    flags=plan.level_flags(0)[2], stream=plan.stream, children=children,
-                                    environment=plan.environment, kinds=plan.path_kinds, path_seed=plan.path_seed,
-                                    workspace_bytes=need)
+        common = dict(queue_capacity=cap, y0=y0, y1=y1, spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled,
+                      flags=plan.level_flags(0)[2], stream=plan.stream, children=children, environment=plan.environment,
+                      kinds=plan.path_kinds, path_seed=plan.path_seed, workspace_bytes=need)
+        if photons:
+            self.scene.render_recursion_photons(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth, plan.photon_maps[0],
+                                                plan.photon_maps[1], self.d_recursion, max_dist=plan.max_dist, nphotons=plan.nphotons,
+                                                **common)
+        else:
+            self.scene.render_recursion(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth,
+                                        d_workspace=self.d_recursion if depth > 0 else None, **common)
         host = self.d_level_counts[:depth + 1].tolist()             # the one read-back of the frame
         per_level = []
         for level, row in enumerate(host):

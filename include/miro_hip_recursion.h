@@ -48,7 +48,7 @@ extern "C" {
  *   bits; more samples than 2^32 - 1); NULL desc or NULL d_level_counts (8-byte aligned); depth > 64; with depth >= 1: children
  *   that is neither MR_LEVEL_SPECULAR nor MR_LEVEL_PATH, queue_capacity 0, a NULL or misaligned workspace, workspace_bytes too
  *   small; non-zero reserved words.  MR_ERR_STATE: a scene that is unbuilt, built host_only, or has no lights.
- * Not part of this call: photon maps (mr_gather_level takes its n from the host), square lights, the thin lens, more than one
+ * Not part of this call: photon maps (mr_render_recursion_photons, miro_hip_recursion_photons.h, is this call with them), square lights, the thin lens, more than one
  *   band range per call, and octant bytes for grouped traversal (group_octants).  The per-level calls serve those. */
 typedef struct mr_recursion_desc {
     uint32_t depth;                 /* TRACE_DEPTH: levels 0..depth are run */
@@ -68,3 +68,4 @@ mr_status mr_render_recursion(mr_scene *scene, const mr_frame_desc *frame, const
 }
 #endif
 #endif /* MIRO_HIP_RECURSION_H */
+#include "miro_hip_recursion_photons.h"
