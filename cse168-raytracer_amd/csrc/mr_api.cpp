@@ -1219,15 +1219,19 @@ static mr_status environment_params(mr_scene *s, hipStream_t stream, EnvParams &
 }
 
 // the scene as the textured light-list kernels take it, after the call's state checks: its device made current, its texture table
-// or none, and with `environment` its environment (without: all zero).  The two uploads happen only after a change
-// (texture_params, environment_params) and must lie outside a stream capture
-static mr_status lights_scene_params(mr_scene *s, bool environment, void *stream, TexParams &tex, EnvParams &env) {
+// or none, with `environment` its environment (without: all zero), and its light list.  The two uploads happen only after a
+// change (texture_params, environment_params) and must lie outside a stream capture
+static mr_status lights_scene_params(mr_scene *s, bool environment, void *stream, LightScene &ls) {
     MR_HIP_CHECK(hipSetDevice(s->device));
     mr_status st = MR_OK;
+    ls.ds = &s->dev;
+    ls.lights = s->lights.data();
+    ls.n_lights = (uint32_t)s->lights.size();
+    TexParams &tex = ls.tex;
     tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
     if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
-    env = EnvParams{};
-    return environment ? environment_params(s, static_cast<hipStream_t>(stream), env) : MR_OK;
+    ls.env = EnvParams{};
+    return environment ? environment_params(s, static_cast<hipStream_t>(stream), ls.env) : MR_OK;
 }
 
 // mr_render_direct's window over mr_shade_lights' light list, in one launch (mr_frame_lights.hip).  What the arguments alone can
@@ -1237,13 +1241,18 @@ static mr_status lights_scene_params(mr_scene *s, bool environment, void *stream
 // besides is; refuse_table: the call shades without the lookup.
 // (the two halves: what the arguments alone can get wrong; then the scene's state.  mr_render_level_lights puts its own
 // argument checks between them)
+// the frame's own part of them, which mr_render_recursion_photons_workspace asks without a scene: a non-empty image, `fd` as
+// the launchers take it, check_frame_lights
+static mr_status check_render_lights_frame(const char *who, const mr_frame_desc &frame, mr_frame_desc &fd) {
+    if (frame.W == 0 || frame.H == 0) return fail(MR_ERR_INVALID, "%s: empty image", who);
+    fd = frame;
+    if (fd.band_world <= 1) { fd.band_world = 1; fd.band_rank = 0; if (fd.band_rows == 0) fd.band_rows = 1; }
+    return check_frame_lights(who, fd);
+}
 static mr_status check_render_lights_args(const char *who, mr_scene *s, const mr_frame_desc *frame, mr_frame_desc &fd, const float *d_rgb,
                                           const mr_hit *d_hits, const float *d_sample_rgb, bool surface_misaligned, const uint64_t *d_counts) {
     if (!s || !frame || !d_rgb) return fail(MR_ERR_INVALID, "%s: NULL argument", who);
-    if (frame->W == 0 || frame->H == 0) return fail(MR_ERR_INVALID, "%s: empty image", who);
-    fd = *frame;
-    if (fd.band_world <= 1) { fd.band_world = 1; fd.band_rank = 0; if (fd.band_rows == 0) fd.band_rows = 1; }
-    mr_status st = check_frame_lights(who, fd);
+    const mr_status st = check_render_lights_frame(who, *frame, fd);
     if (st != MR_OK) return st;
     if (misaligned(16, d_hits) || misaligned(8, d_counts) || misaligned(4, d_rgb, d_sample_rgb) || surface_misaligned)
         return fail(MR_ERR_INVALID, "%s: the hit buffer must be 16-byte aligned, float buffers 4-byte, counters 8-byte aligned", who);
@@ -1287,12 +1296,10 @@ mr_status mr_render_lights_surface(mr_scene *s, const mr_frame_desc *frame, floa
     mr_status st = check_render_lights("mr_render_lights_surface", s, frame, fd, d_rgb, d_hits, d_sample_rgb,
                                        misaligned(4, d_sample_color, d_sample_normal), d_counts, false);
     if (st != MR_OK) return st;
-    TexParams tex;
-    EnvParams env;
-    if ((st = lights_scene_params(s, false, stream, tex, env)) != MR_OK) return st;
-    return launch_frame_lights_surface(s->dev, tex, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
-                                       d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts),
-                                       static_cast<hipStream_t>(stream));
+    LightScene ls;
+    if ((st = lights_scene_params(s, false, stream, ls)) != MR_OK) return st;
+    return launch_frame_lights_surface(ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal,
+                                       reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
 // ... and a live sample whose primary ray misses is worth the scene's environment (mr_frame_lights_env.hip).  The first call after
@@ -1304,12 +1311,10 @@ mr_status mr_render_lights_environment(mr_scene *s, const mr_frame_desc *frame, 
     mr_status st = check_render_lights("mr_render_lights_environment", s, frame, fd, d_rgb, d_hits, d_sample_rgb,
                                        misaligned(4, d_sample_color, d_sample_normal), d_counts, false);
     if (st != MR_OK) return st;
-    TexParams tex;
-    EnvParams env;
-    if ((st = lights_scene_params(s, true, stream, tex, env)) != MR_OK) return st;
-    return launch_frame_lights_env(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
-                                   d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts),
-                                   static_cast<hipStream_t>(stream));
+    LightScene ls;
+    if ((st = lights_scene_params(s, true, stream, ls)) != MR_OK) return st;
+    return launch_frame_lights_env(ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal,
+                                   reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
 // what the three calls that emit children ask of the queue they fill, in this order: the queue and its capacity with children
@@ -1344,11 +1349,11 @@ static mr_status check_level_lights_queue(const char *who, bool children, unsign
 }
 
 // ... and of the scene, after the arguments: built on a device, with lights; then lights_scene_params
-static mr_status level_lights_params(const char *who, mr_scene *s, bool environment, void *stream, TexParams &tex, EnvParams &env) {
+static mr_status level_lights_params(const char *who, mr_scene *s, bool environment, void *stream, LightScene &ls) {
     const mr_status st = require_device(s);
     if (st != MR_OK) return st;
     if (s->lights.empty()) return fail(MR_ERR_STATE, "%s: the scene has no lights (mr_scene_set_lights)", who);
-    return lights_scene_params(s, environment, stream, tex, env);
+    return lights_scene_params(s, environment, stream, ls);
 }
 
 // One level of the recursion over the light list on any scene, in one launch (mr_level_lights.hip).  What the arguments alone can
@@ -1376,13 +1381,11 @@ mr_status mr_trace_level_lights(mr_scene *s, const mr_level_lights_desc *level, 
                                             d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights,
                                             d_out_pixels, d_out_count, d_counts, false);
     if (st != MR_OK) return st;
-    TexParams tex;
-    EnvParams env;
-    if ((st = level_lights_params(who, s, level->environment != 0, stream, tex, env)) != MR_OK) return st;
-    return launch_level_lights(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), *level, d_rays, d_weights, d_pixels, n,
-                               d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights, d_out_pixels,
-                               reinterpret_cast<unsigned long long *>(d_out_count), reinterpret_cast<unsigned long long *>(d_counts),
-                               static_cast<hipStream_t>(stream));
+    LightScene ls;
+    if ((st = level_lights_params(who, s, level->environment != 0, stream, ls)) != MR_OK) return st;
+    return launch_level_lights(ls, *level, d_rays, d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays,
+                               d_out_weights, d_out_pixels, reinterpret_cast<unsigned long long *>(d_out_count),
+                               reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
 // ... of a PATH_TRACING build (mr_level_lights_path.hip): the children of mr_gen_path_rays_surface, ids, the low-res byte.  The
@@ -1411,12 +1414,10 @@ mr_status mr_trace_level_lights_path(mr_scene *s, const mr_level_lights_path_des
                                             d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights,
                                             d_out_pixels, d_out_count, d_counts, misaligned(4, d_ids, d_out_ids));
     if (st != MR_OK) return st;
-    TexParams tex;
-    EnvParams env;
-    if ((st = level_lights_params(who, s, level->environment != 0, stream, tex, env)) != MR_OK) return st;
-    return launch_level_lights_path(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), *level, d_rays, d_weights, d_pixels,
-                                    d_ids, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays, d_out_weights, d_out_pixels,
-                                    d_out_ids, reinterpret_cast<unsigned long long *>(d_out_count),
+    LightScene ls;
+    if ((st = level_lights_params(who, s, level->environment != 0, stream, ls)) != MR_OK) return st;
+    return launch_level_lights_path(ls, *level, d_rays, d_weights, d_pixels, d_ids, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal,
+                                    d_out_rays, d_out_weights, d_out_pixels, d_out_ids, reinterpret_cast<unsigned long long *>(d_out_count),
                                     reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
@@ -1457,15 +1458,13 @@ mr_status mr_render_level_lights(mr_scene *s, const mr_frame_desc *frame, const 
                                         "4-byte aligned", who);
     }
     if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
-    TexParams tex;
-    EnvParams env;
-    if ((st = lights_scene_params(s, level->environment != 0, stream, tex, env)) != MR_OK) return st;
+    LightScene ls;
+    if ((st = lights_scene_params(s, level->environment != 0, stream, ls)) != MR_OK) return st;
     if (!children)
-        return launch_frame_lights_env(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), fd, d_rgb, d_hits, d_sample_rgb,
-                                       d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts),
-                                       static_cast<hipStream_t>(stream));
-    return launch_frame_level_lights(s->dev, tex, env, s->lights.data(), (uint32_t)s->lights.size(), fd, *level, d_rgb, d_hits,
-                                     d_sample_rgb, d_sample_color, d_sample_normal, d_out_rays, d_out_weights, d_out_pixels, d_out_ids,
+        return launch_frame_lights_env(ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal,
+                                       reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+    const RayQueue out = {d_out_rays, d_out_weights, d_out_pixels, d_out_ids, level->d_out_lowres};
+    return launch_frame_level_lights(ls, fd, *level, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal, out,
                                      reinterpret_cast<unsigned long long *>(d_out_count), reinterpret_cast<unsigned long long *>(d_counts),
                                      static_cast<hipStream_t>(stream));
 }
@@ -1473,7 +1472,7 @@ mr_status mr_render_level_lights(mr_scene *s, const mr_frame_desc *frame, const 
 // The workspace of mr_render_recursion: two queues of `cap` rays, each a run of arrays whose offsets are rounded up to 16 bytes
 // (the ray queue's alignment, which serves every other array).  The offsets of ONE queue's rays, weights, pixels, ids and low-res
 // bytes (ids / low: where the queue has none, the offset of its end) and its size in bytes
-struct RecursionQueue { uint64_t rays, weights, pixels, ids, low, bytes; };
+struct RecursionQueue { uint64_t rays, weights, pixels, ids, low, bytes; bool has_ids, has_low; };
 static RecursionQueue recursion_queue_layout(uint64_t cap, bool path, bool low) {
     auto up = [](uint64_t v) { return (v + 15ull) & ~15ull; };
     RecursionQueue q;
@@ -1483,9 +1482,24 @@ static RecursionQueue recursion_queue_layout(uint64_t cap, bool path, bool low) 
     q.ids = up(q.pixels + 4ull * cap);
     q.low = path ? up(q.ids + 4ull * cap) : q.ids;
     q.bytes = path && low ? up(q.low + cap) : q.low;
+    q.has_ids = path; q.has_low = path && low;
     return q;
 }
-// what mr_render_recursion_workspace and mr_render_recursion ask of the descriptor alone, in this order
+static RecursionQueue recursion_queue_layout(const mr_recursion_desc &rd) {
+    return recursion_queue_layout(rd.queue_capacity_lo, rd.children == MR_LEVEL_PATH, rd.environment != 0);
+}
+// the two queues of a workspace laid out as `q`, array by array
+static void recursion_queues(void *d_workspace, const RecursionQueue &q, RayQueue qs[2]) {
+    for (int w = 0; w < 2; w++) {
+        uint8_t *base = static_cast<uint8_t *>(d_workspace) + (uint64_t)w * q.bytes;
+        qs[w].rays = reinterpret_cast<mr_ray *>(base + q.rays);
+        qs[w].weights = reinterpret_cast<float *>(base + q.weights);
+        qs[w].pixels = reinterpret_cast<uint32_t *>(base + q.pixels);
+        qs[w].ids = q.has_ids ? reinterpret_cast<uint32_t *>(base + q.ids) : nullptr;
+        qs[w].low = q.has_low ? base + q.low : nullptr;
+    }
+}
+// what every call of the family asks of the descriptor alone, in this order
 static mr_status check_recursion_desc(const char *who, const mr_recursion_desc *rd) {
     if (!rd) return fail(MR_ERR_INVALID, "%s: NULL argument (desc)", who);
     if (rd->depth > 64) return fail(MR_ERR_INVALID, "%s: depth must be 64 at most", who);
@@ -1504,25 +1518,11 @@ static mr_status check_recursion_desc(const char *who, const mr_recursion_desc *
         return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 rays per queue", who);
     return MR_OK;
 }
-
-mr_status mr_render_recursion_workspace(const mr_recursion_desc *desc, uint64_t *bytes) {
-    const char *who = "mr_render_recursion_workspace";
-    if (!bytes) return fail(MR_ERR_INVALID, "%s: NULL argument (bytes)", who);
-    const mr_status st = check_recursion_desc(who, desc);
-    if (st != MR_OK) return st;
-    *bytes = desc->depth == 0 ? 0ull
-                              : 2ull * recursion_queue_layout(desc->queue_capacity_lo, desc->children == MR_LEVEL_PATH, desc->environment != 0).bytes;
-    return MR_OK;
-}
-
-// The whole recursive frame on one stream (include/miro_hip_recursion.h): the zeroing kernel, mr_render_level_lights' launcher for
-// level 0, then one queued level kernel (mr_level_lights_queued.hip) per further level, whose queue length is the word the level
-// before counted its children into.  The argument checks of mr_render_level_lights under this call's name, then this call's own,
-// all before the scene's state is read; then the state and the uploads; then nothing but launches.
-mr_status mr_render_recursion(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, float *d_rgb, void *d_workspace,
-                              uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
-    const char *who = "mr_render_recursion";
-    mr_frame_desc fd;
+// what mr_render_recursion and mr_render_recursion_photons ask first, in this order: the argument checks of
+// mr_render_level_lights under the call's name, the counters, the flags, the descriptor.  fd: the frame as the launchers take it;
+// samples: those of its window (which has passed check_frame_lights: counting them cannot fail)
+static mr_status check_recursion_args(const char *who, mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc,
+                                      const float *d_rgb, const uint64_t *d_level_counts, mr_frame_desc &fd, unsigned long long &samples) {
     mr_status st = check_render_lights_args(who, s, frame, fd, d_rgb, nullptr, nullptr, false, d_level_counts);
     if (st != MR_OK) return st;
     if (!d_level_counts) return fail(MR_ERR_INVALID, "%s: NULL argument (d_level_counts)", who);
@@ -1530,78 +1530,91 @@ mr_status mr_render_recursion(mr_scene *s, const mr_frame_desc *frame, const mr_
         return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT only (the shadow rays are closest-hit, as in "
                                     "mr_trace_level_lights)", who);
     if ((st = check_recursion_desc(who, desc)) != MR_OK) return st;
-    const bool path = desc->children == MR_LEVEL_PATH, low = path && desc->environment != 0;
-    const uint64_t cap = desc->queue_capacity_lo;
+    return frame_level_lights_samples(who, fd, samples);
+}
+
+mr_status mr_render_recursion_workspace(const mr_recursion_desc *desc, uint64_t *bytes) {
+    const char *who = "mr_render_recursion_workspace";
+    if (!bytes) return fail(MR_ERR_INVALID, "%s: NULL argument (bytes)", who);
+    const mr_status st = check_recursion_desc(who, desc);
+    if (st != MR_OK) return st;
+    *bytes = desc->depth == 0 ? 0ull : 2ull * recursion_queue_layout(*desc).bytes;
+    return MR_OK;
+}
+
+// The launches of a whole recursive frame on one stream, and nothing else: the kernel that zeroes the counters (`counts`:
+// [depth + 1][8]); level 0, mr_render_level_lights' launcher with its children in queue 0 of the workspace (depth 0: the plain
+// frame, no workspace); then one queued level kernel (mr_level_lights_queued.hip) per further level, from one queue into the
+// other, whose length is the word the level before counted its children into.  d_hits / d_normal: optional, every level's per-ray
+// records, each level overwriting the one before.  step(l, d_n, bound, in) is enqueued after level l, 0 included -- d_n: the
+// word that holds the level's length (level 0: the samples the frame counted), bound: what the host knows it cannot exceed (fan^l
+// x samples, saturating at the capacity), in: the queue the level read (level 0: none, its rays start at the eye)
+static mr_status no_level_step(uint32_t, const unsigned long long *, unsigned long long, const RayQueue &) { return MR_OK; }
+extern "C++" template <typename STEP>                                                  // (the entry points around it have C linkage)
+static mr_status enqueue_recursion(const LightScene &ls, const mr_frame_desc &fd, const mr_recursion_desc &rd, unsigned long long samples,
+                                   void *d_workspace, float *d_rgb, mr_hit *d_hits, float *d_normal, unsigned long long *counts,
+                                   hipStream_t hs, STEP step) {
+    mr_status st = launch_zero_words(counts, 8ull * (rd.depth + 1ull), hs);
+    if (st != MR_OK) return st;
+    const bool path = rd.children == MR_LEVEL_PATH;
+    const uint64_t cap = rd.queue_capacity_lo;
     const unsigned fan = path ? 4u : 3u;
-    unsigned long long samples = 0;
-    RecursionQueue q = {};
-    if (desc->depth > 0) {
-        if ((st = frame_level_lights_samples(who, fd, samples)) != MR_OK) return st;
-        if (samples > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 samples per call with children", who);
-        q = recursion_queue_layout(cap, path, desc->environment != 0);
-        if (!d_workspace || misaligned(16, d_workspace))
-            return fail(MR_ERR_INVALID, "%s: depth >= 1 needs a workspace, 16-byte aligned (mr_render_recursion_workspace)", who);
-        if (workspace_bytes < 2ull * q.bytes)
-            return fail(MR_ERR_INVALID, "%s: workspace_bytes is %llu, two queues of %llu rays need %llu (mr_render_recursion_workspace)", who,
-                        (unsigned long long)workspace_bytes, (unsigned long long)cap, 2ull * (unsigned long long)q.bytes);
+    RayQueue qs[2] = {};
+    if (rd.depth == 0) {
+        st = launch_frame_lights_env(ls, fd, d_rgb, d_hits, nullptr, nullptr, d_normal, counts, hs);
+    } else {
+        recursion_queues(d_workspace, recursion_queue_layout(rd), qs);
+        mr_frame_level_desc l0 = {};
+        l0.children = rd.children; l0.environment = rd.environment;
+        l0.path_kinds = rd.path_kinds; l0.path_seed = rd.path_seed;
+        l0.out_capacity_lo = rd.queue_capacity_lo; l0.out_capacity_hi = 0;
+        st = launch_frame_level_lights(ls, fd, l0, d_rgb, d_hits, nullptr, nullptr, d_normal, qs[0], &counts[5], counts, hs);
     }
-    if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
-    TexParams tex;
-    EnvParams env;
-    if ((st = lights_scene_params(s, desc->environment != 0, stream, tex, env)) != MR_OK) return st;
+    if (st != MR_OK || (st = step(0u, &counts[0], samples, RayQueue{})) != MR_OK) return st;
 
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_level_counts);
-    const ShadeLight *lights = s->lights.data();
-    const uint32_t n_lights = (uint32_t)s->lights.size();
-    if ((st = launch_zero_words(counts, 8ull * (desc->depth + 1ull), hs)) != MR_OK) return st;
-    if (desc->depth == 0)
-        return launch_frame_lights_env(s->dev, tex, env, lights, n_lights, fd, d_rgb, nullptr, nullptr, nullptr, nullptr, counts, hs);
-
-    // queue `w` of the workspace, array by array
-    struct Arrays { mr_ray *rays; float *weights; uint32_t *pixels, *ids; uint8_t *low; } qs[2];
-    for (int w = 0; w < 2; w++) {
-        uint8_t *base = static_cast<uint8_t *>(d_workspace) + (uint64_t)w * q.bytes;
-        qs[w].rays = reinterpret_cast<mr_ray *>(base + q.rays);
-        qs[w].weights = reinterpret_cast<float *>(base + q.weights);
-        qs[w].pixels = reinterpret_cast<uint32_t *>(base + q.pixels);
-        qs[w].ids = path ? reinterpret_cast<uint32_t *>(base + q.ids) : nullptr;
-        qs[w].low = low ? base + q.low : nullptr;
-    }
-    mr_frame_level_desc l0 = {};
-    l0.children = desc->children; l0.environment = desc->environment;
-    l0.path_kinds = desc->path_kinds; l0.path_seed = desc->path_seed;
-    l0.out_capacity_lo = desc->queue_capacity_lo; l0.out_capacity_hi = 0;
-    l0.d_out_lowres = qs[0].low;
-    if ((st = launch_frame_level_lights(s->dev, tex, env, lights, n_lights, fd, l0, d_rgb, nullptr, nullptr, nullptr, nullptr, qs[0].rays,
-                                        qs[0].weights, qs[0].pixels, qs[0].ids, &counts[5], counts, hs)) != MR_OK)
-        return st;
-
-    const uint32_t level_flags = (fd.flags & MR_MATH_PRODUCT) | MR_TRACE_INCOHERENT;     // a bounce queue is compacted in wave order
-    unsigned long long bound = samples;                                                   // fan^l x samples, saturating at the capacity
-    for (uint32_t l = 1; l <= desc->depth; l++) {
+    QueuedLevel lv = {};
+    lv.spp = fd.spp;
+    lv.flags = (fd.flags & MR_MATH_PRODUCT) | MR_TRACE_INCOHERENT;                      // a bounce queue is compacted in wave order
+    lv.path = path; lv.environment = rd.environment;
+    lv.path_kinds = rd.path_kinds; lv.seed = rd.path_seed;
+    lv.capacity = cap;
+    unsigned long long bound = samples;
+    for (uint32_t l = 1; l <= rd.depth; l++) {
         bound = bound > cap / fan ? cap : bound * fan;
-        const Arrays &in = qs[(l - 1) & 1], &out = qs[l & 1];
-        const bool last = l == desc->depth;
+        const RayQueue &in = qs[(l - 1) & 1], &out = qs[l & 1];
         unsigned long long *row = counts + 8ull * l;
-        if (path) {
-            mr_level_lights_path_desc ld = {};
-            ld.spp = fd.spp; ld.flags = level_flags; ld.children = last ? MR_LEVEL_LAST : MR_LEVEL_PATH; ld.environment = desc->environment;
-            ld.path_kinds = desc->path_kinds; ld.seed = desc->path_seed; ld.bounce = l;
-            ld.out_capacity_lo = desc->queue_capacity_lo;
-            ld.d_lowres = in.low; ld.d_out_lowres = last ? nullptr : out.low;
-            st = launch_level_lights_path_queued(s->dev, tex, env, lights, n_lights, ld, in.rays, in.weights, in.pixels, in.ids, row - 8 + 5, cap,
-                                                 bound, d_rgb, nullptr, nullptr, out.rays, out.weights, out.pixels, out.ids, row + 5, row, hs);
-        } else {
-            mr_level_lights_desc ld = {};
-            ld.spp = fd.spp; ld.flags = level_flags; ld.children = last ? MR_LEVEL_LAST : MR_LEVEL_SPECULAR; ld.environment = desc->environment;
-            ld.out_capacity_lo = desc->queue_capacity_lo;
-            st = launch_level_lights_queued(s->dev, tex, env, lights, n_lights, ld, in.rays, in.weights, in.pixels, row - 8 + 5, cap, bound,
-                                            d_rgb, nullptr, nullptr, out.rays, out.weights, out.pixels, row + 5, row, hs);
-        }
-        if (st != MR_OK) return st;
+        const unsigned long long *d_n = row - 8 + 5;                                      // the children level l - 1 counted
+        lv.last = l == rd.depth; lv.bounce = l;
+        if ((st = launch_level_lights_queued(ls, lv, in, out, d_n, cap, bound, d_rgb, d_hits, d_normal, row, hs)) != MR_OK ||
+            (st = step(l, d_n, bound, in)) != MR_OK)
+            return st;
     }
     return MR_OK;
+}
+
+// The whole recursive frame on one stream (include/miro_hip_recursion.h).  The argument checks first, all before the scene's
+// state is read; then the state and the uploads; then nothing but launches (enqueue_recursion).
+mr_status mr_render_recursion(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, float *d_rgb, void *d_workspace,
+                              uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
+    const char *who = "mr_render_recursion";
+    mr_frame_desc fd;
+    unsigned long long samples = 0;
+    mr_status st = check_recursion_args(who, s, frame, desc, d_rgb, d_level_counts, fd, samples);
+    if (st != MR_OK) return st;
+    if (desc->depth > 0) {
+        if (samples > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 samples per call with children", who);
+        const uint64_t need = 2ull * recursion_queue_layout(*desc).bytes;
+        if (!d_workspace || misaligned(16, d_workspace))
+            return fail(MR_ERR_INVALID, "%s: depth >= 1 needs a workspace, 16-byte aligned (mr_render_recursion_workspace)", who);
+        if (workspace_bytes < need)
+            return fail(MR_ERR_INVALID, "%s: workspace_bytes is %llu, two queues of %llu rays need %llu (mr_render_recursion_workspace)", who,
+                        (unsigned long long)workspace_bytes, (unsigned long long)desc->queue_capacity_lo, (unsigned long long)need);
+    }
+    if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
+    LightScene ls;
+    if ((st = lights_scene_params(s, desc->environment != 0, stream, ls)) != MR_OK) return st;
+    return enqueue_recursion(ls, fd, *desc, samples, d_workspace, d_rgb, nullptr, nullptr, reinterpret_cast<unsigned long long *>(d_level_counts),
+                             static_cast<hipStream_t>(stream), no_level_step);
 }
 
 // The workspace of mr_render_recursion_photons behind the two queues: hit records, normals and mr_gather_level's scratch for M
@@ -1611,28 +1624,20 @@ static RecursionPhotonsLayout recursion_photons_layout(const mr_recursion_desc &
     auto up = [](uint64_t v) { return (v + 15ull) & ~15ull; };
     const uint64_t cap = rd.depth > 0 ? rd.queue_capacity_lo : 0ull, M = samples > cap ? samples : cap;
     RecursionPhotonsLayout w;
-    w.queues = rd.depth == 0 ? 0ull : 2ull * recursion_queue_layout(cap, rd.children == MR_LEVEL_PATH, rd.environment != 0).bytes;
+    w.queues = rd.depth == 0 ? 0ull : 2ull * recursion_queue_layout(rd).bytes;
     w.hits = w.queues;
     w.normals = w.hits + up(16ull * M);
     w.scratch = w.normals + up(12ull * M);
     w.bytes = w.scratch + up(48ull * M);
     return w;
 }
-// what both calls ask of the two descriptors, in this order: the frame's window, the descriptor's words, then what the photon
-// term adds -- image order, and no more rays per level than one estimate launch answers.  fd: the frame as the launchers take it
-static mr_status check_recursion_photons_descs(const char *who, const mr_frame_desc *frame, const mr_recursion_desc *desc, mr_frame_desc &fd,
-                                               unsigned long long &samples) {
-    if (!frame) return fail(MR_ERR_INVALID, "%s: NULL argument (frame)", who);
-    if (frame->W == 0 || frame->H == 0) return fail(MR_ERR_INVALID, "%s: empty image", who);
-    fd = *frame;
-    if (fd.band_world <= 1) { fd.band_world = 1; fd.band_rank = 0; if (fd.band_rows == 0) fd.band_rows = 1; }
-    mr_status st = check_frame_lights(who, fd);
-    if (st != MR_OK || (st = check_recursion_desc(who, desc)) != MR_OK) return st;
+// what the photon term adds to the checks of the two descriptors, in this order: image order, and no more rays per level than
+// one estimate launch answers
+static mr_status check_recursion_photons_window(const char *who, const mr_frame_desc &fd, const mr_recursion_desc &rd, unsigned long long samples) {
     if (fd.tiled)
         return fail(MR_ERR_INVALID, "%s: tiled sample order (level 0's photon term finds its pixel from the sample index, in image "
                                     "order); use tiled = 0", who);
-    if ((st = frame_level_lights_samples(who, fd, samples)) != MR_OK) return st;
-    if (samples >= (1ull << 31) || (desc->depth > 0 && desc->queue_capacity_lo >= (1u << 31)))
+    if (samples >= (1ull << 31) || (rd.depth > 0 && rd.queue_capacity_lo >= (1u << 31)))
         return fail(MR_ERR_INVALID, "%s: at most 2^31 - 1 samples and a queue_capacity of at most 2^31 - 1 (one estimate launch answers "
                                     "at most 2^31 - 1 queries)", who);
     return MR_OK;
@@ -1641,31 +1646,29 @@ static mr_status check_recursion_photons_descs(const char *who, const mr_frame_d
 mr_status mr_render_recursion_photons_workspace(const mr_frame_desc *frame, const mr_recursion_desc *desc, uint64_t *bytes) {
     const char *who = "mr_render_recursion_photons_workspace";
     if (!bytes) return fail(MR_ERR_INVALID, "%s: NULL argument (bytes)", who);
+    if (!frame) return fail(MR_ERR_INVALID, "%s: NULL argument (frame)", who);
     mr_frame_desc fd;
     unsigned long long samples = 0;
-    const mr_status st = check_recursion_photons_descs(who, frame, desc, fd, samples);
-    if (st != MR_OK) return st;
+    mr_status st = check_render_lights_frame(who, *frame, fd);
+    if (st != MR_OK || (st = check_recursion_desc(who, desc)) != MR_OK || (st = frame_level_lights_samples(who, fd, samples)) != MR_OK ||
+        (st = check_recursion_photons_window(who, fd, *desc, samples)) != MR_OK)
+        return st;
     *bytes = recursion_photons_layout(*desc, samples).bytes;
     return MR_OK;
 }
 
-// mr_render_recursion with the photon-map term after every level (include/miro_hip_recursion_photons.h): its sequence of launches,
-// restated here because every level launch also gets the workspace's hit and normal buffers, and after each level the three
-// kernels of mr_gather_queued.hip on that level's queue.  The argument checks first, all of them before the scene's or a map's
-// state is read; then the state and the uploads; then nothing but launches.
+// mr_render_recursion with the photon-map term after every level (include/miro_hip_recursion_photons.h): enqueue_recursion with
+// the workspace's hit and normal buffers handed to every level launch, and as its step the three kernels of mr_gather_queued.hip
+// on that level's queue.  The argument checks first, all of them before the scene's or a map's state is read; then the state and
+// the uploads; then nothing but launches.
 mr_status mr_render_recursion_photons(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, mr_photon_map *global_map,
                                       mr_photon_map *caustic_map, float max_dist, uint32_t nphotons, float *d_rgb, void *d_workspace,
                                       uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
     const char *who = "mr_render_recursion_photons";
     mr_frame_desc fd;
-    mr_status st = check_render_lights_args(who, s, frame, fd, d_rgb, nullptr, nullptr, false, d_level_counts);
-    if (st != MR_OK) return st;
-    if (!d_level_counts) return fail(MR_ERR_INVALID, "%s: NULL argument (d_level_counts)", who);
-    if (fd.flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT))
-        return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT only (the shadow rays are closest-hit, as in "
-                                    "mr_trace_level_lights)", who);
     unsigned long long samples = 0;
-    if ((st = check_recursion_photons_descs(who, frame, desc, fd, samples)) != MR_OK) return st;
+    mr_status st = check_recursion_args(who, s, frame, desc, d_rgb, d_level_counts, fd, samples);
+    if (st != MR_OK || (st = check_recursion_photons_window(who, fd, *desc, samples)) != MR_OK) return st;
     mr_photon_map *maps[2] = {global_map, caustic_map};
     if (!maps[0] && !maps[1]) return fail(MR_ERR_INVALID, "%s: NULL argument (global_map and caustic_map are both NULL)", who);
     if (nphotons == 0 || nphotons > (uint32_t)kKnnMaxK) return fail(MR_ERR_INVALID, "%s: nphotons must be in [1, %d]", who, kKnnMaxK);
@@ -1685,96 +1688,32 @@ mr_status mr_render_recursion_photons(mr_scene *s, const mr_frame_desc *frame, c
         if (m && photon_map_stored(m) >= (1u << 24))
             return fail(MR_ERR_STATE, "%s: photon maps of 2^24 photons or more need a fifth layer of blocks", who);
     }
-    TexParams tex;
-    EnvParams env;
-    if ((st = lights_scene_params(s, desc->environment != 0, stream, tex, env)) != MR_OK) return st;
+    LightScene ls;
+    if ((st = lights_scene_params(s, desc->environment != 0, stream, ls)) != MR_OK) return st;
 
     hipStream_t hs = static_cast<hipStream_t>(stream);
     unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_level_counts);
-    const ShadeLight *lights = s->lights.data();
-    const uint32_t n_lights = (uint32_t)s->lights.size();
-    const bool path = desc->children == MR_LEVEL_PATH, low = path && desc->environment != 0;
-    const uint64_t cap = desc->queue_capacity_lo;
-    const unsigned fan = path ? 4u : 3u;
     uint8_t *wbase = static_cast<uint8_t *>(d_workspace);
     mr_hit *d_hits = reinterpret_cast<mr_hit *>(wbase + ws.hits);
     // the normal Scene::trace hands on differs from the object's on a procedural texture only: elsewhere the query kernels form it
     float *d_normal = s->tex.procedural ? reinterpret_cast<float *>(wbase + ws.normals) : nullptr;
     float *d_scratch = reinterpret_cast<float *>(wbase + ws.scratch);
 
-    // steps 2 and 3 of a level's photon term on its queries (the level's query kernel has run): nb rays at most, mr_gather_level's
-    // scratch layout for nb; d_n / nb: the level's length as the kernels read it
-    auto estimate_and_add = [&](const unsigned long long *d_n, unsigned long long nb, const float *d_weights, const uint32_t *d_pixels) -> mr_status {
-        float *d_irr[2] = {nullptr, nullptr};
-        for (int i = 0; i < 2; i++) {
-            if (!maps[i]) continue;
-            d_irr[i] = d_scratch + (6 + 3 * i) * nb;
-            const mr_status e = photon_map_estimate_queued(maps[i], d_scratch, d_scratch + 3 * nb, d_n, nb, nb, max_dist, nphotons, d_irr[i], hs);
-            if (e != MR_OK) return e;
-        }
-        return launch_gather_queued_accumulate(d_irr[0], d_irr[1], d_weights, d_pixels, d_n, nb, nb, fd.spp, d_rgb, hs);
+    // level l's photon term, before level l + 1 overwrites the hit records and (two levels on) this queue: queries, one estimate
+    // per map, the accumulate, over a scratch laid out for `bound` rays.  bound <= the queue's capacity, and the kernels take it
+    // as the capacity, so that no index reaches beyond that scratch.  Level 0 has no queue: its queries come from the eye rays
+    // made again, its length is the window's, which the frame has added to counts[0]; weight 1, pixel k / spp (in: all NULL)
+    auto photon_term = [&](uint32_t l, const unsigned long long *d_n, unsigned long long bound, const RayQueue &in) -> mr_status {
+        const GatherScratch sc = gather_scratch(d_scratch, bound, maps[0] != nullptr, maps[1] != nullptr);
+        unsigned long long *d_queries = counts + 8ull * l + 6;
+        mr_status e = l == 0 ? launch_gather_eye_queries(s->dev, who, fd, d_hits, d_normal, sc.pos, sc.nrm, d_queries, hs)
+                             : launch_gather_queued_queries(s->dev, in.rays, d_hits, d_normal, d_n, bound, sc.pos, sc.nrm, d_queries, hs);
+        for (int i = 0; i < 2 && e == MR_OK; i++)
+            if (maps[i]) e = photon_map_estimate_queued(maps[i], sc.pos, sc.nrm, d_n, bound, max_dist, nphotons, sc.irr[i], hs);
+        if (e != MR_OK) return e;
+        return launch_gather_queued_accumulate(sc.irr[0], sc.irr[1], in.weights, in.pixels, d_n, bound, fd.spp, d_rgb, hs);
     };
-
-    if ((st = launch_zero_words(counts, 8ull * (desc->depth + 1ull), hs)) != MR_OK) return st;
-    struct Arrays { mr_ray *rays; float *weights; uint32_t *pixels, *ids; uint8_t *low; } qs[2] = {};
-    if (desc->depth == 0) {
-        st = launch_frame_lights_env(s->dev, tex, env, lights, n_lights, fd, d_rgb, d_hits, nullptr, nullptr, d_normal, counts, hs);
-    } else {
-        const RecursionQueue q = recursion_queue_layout(cap, path, desc->environment != 0);
-        for (int w = 0; w < 2; w++) {                                      // queue `w` of the workspace, array by array
-            uint8_t *base = wbase + (uint64_t)w * q.bytes;
-            qs[w].rays = reinterpret_cast<mr_ray *>(base + q.rays);
-            qs[w].weights = reinterpret_cast<float *>(base + q.weights);
-            qs[w].pixels = reinterpret_cast<uint32_t *>(base + q.pixels);
-            qs[w].ids = path ? reinterpret_cast<uint32_t *>(base + q.ids) : nullptr;
-            qs[w].low = low ? base + q.low : nullptr;
-        }
-        mr_frame_level_desc l0 = {};
-        l0.children = desc->children; l0.environment = desc->environment;
-        l0.path_kinds = desc->path_kinds; l0.path_seed = desc->path_seed;
-        l0.out_capacity_lo = desc->queue_capacity_lo; l0.out_capacity_hi = 0;
-        l0.d_out_lowres = qs[0].low;
-        st = launch_frame_level_lights(s->dev, tex, env, lights, n_lights, fd, l0, d_rgb, d_hits, nullptr, nullptr, d_normal, qs[0].rays,
-                                       qs[0].weights, qs[0].pixels, qs[0].ids, &counts[5], counts, hs);
-    }
-    if (st != MR_OK) return st;
-    // level 0's photon term: its length is the window's, which the frame has added to counts[0]; weight 1, pixel k / spp
-    if ((st = launch_gather_eye_queries(s->dev, who, fd, d_hits, d_normal, d_scratch, d_scratch + 3 * samples, &counts[6], hs)) != MR_OK ||
-        (st = estimate_and_add(&counts[0], samples, nullptr, nullptr)) != MR_OK)
-        return st;
-
-    const uint32_t level_flags = (fd.flags & MR_MATH_PRODUCT) | MR_TRACE_INCOHERENT;     // a bounce queue is compacted in wave order
-    unsigned long long bound = samples;                                                   // fan^l x samples, saturating at the capacity
-    for (uint32_t l = 1; l <= desc->depth; l++) {
-        bound = bound > cap / fan ? cap : bound * fan;
-        const Arrays &in = qs[(l - 1) & 1], &out = qs[l & 1];
-        const bool last = l == desc->depth;
-        unsigned long long *row = counts + 8ull * l;
-        const unsigned long long *d_n = row - 8 + 5;                                      // the children level l - 1 counted
-        if (path) {
-            mr_level_lights_path_desc ld = {};
-            ld.spp = fd.spp; ld.flags = level_flags; ld.children = last ? MR_LEVEL_LAST : MR_LEVEL_PATH; ld.environment = desc->environment;
-            ld.path_kinds = desc->path_kinds; ld.seed = desc->path_seed; ld.bounce = l;
-            ld.out_capacity_lo = desc->queue_capacity_lo;
-            ld.d_lowres = in.low; ld.d_out_lowres = last ? nullptr : out.low;
-            st = launch_level_lights_path_queued(s->dev, tex, env, lights, n_lights, ld, in.rays, in.weights, in.pixels, in.ids, d_n, cap, bound,
-                                                 d_rgb, d_hits, d_normal, out.rays, out.weights, out.pixels, out.ids, row + 5, row, hs);
-        } else {
-            mr_level_lights_desc ld = {};
-            ld.spp = fd.spp; ld.flags = level_flags; ld.children = last ? MR_LEVEL_LAST : MR_LEVEL_SPECULAR; ld.environment = desc->environment;
-            ld.out_capacity_lo = desc->queue_capacity_lo;
-            st = launch_level_lights_queued(s->dev, tex, env, lights, n_lights, ld, in.rays, in.weights, in.pixels, d_n, cap, bound, d_rgb,
-                                            d_hits, d_normal, out.rays, out.weights, out.pixels, row + 5, row, hs);
-        }
-        if (st != MR_OK) return st;
-        // the level's photon term, before level l + 1 overwrites the hit records and (two levels on) this queue.  bound <= cap:
-        // the kernels take it as the capacity, so that no index reaches beyond the scratch laid out for `bound` rays
-        if ((st = launch_gather_queued_queries(s->dev, in.rays, d_hits, d_normal, d_n, bound, bound, d_scratch, d_scratch + 3 * bound, row + 6,
-                                               hs)) != MR_OK ||
-            (st = estimate_and_add(d_n, bound, in.weights, in.pixels)) != MR_OK)
-            return st;
-    }
-    return MR_OK;
+    return enqueue_recursion(ls, fd, *desc, samples, d_workspace, d_rgb, d_hits, d_normal, counts, hs, photon_term);
 }
 
 mr_status mr_gen_eye_rays_lens(mr_scene *s, const mr_camera *cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp,

@@ -101,26 +101,25 @@ mr_status frame_level_lights_samples(const char *who, const mr_frame_desc &fd, u
     return st;
 }
 
-mr_status launch_frame_level_lights(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                                    uint32_t n_lights, const mr_frame_desc &fd, const mr_frame_level_desc &ld, float *d_rgb, mr_hit *d_hits,
-                                    float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, mr_ray *d_out_rays,
-                                    float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_out_count,
-                                    unsigned long long *d_counts, hipStream_t stream) {
+mr_status launch_frame_level_lights(const LightScene &ls, const mr_frame_desc &fd, const mr_frame_level_desc &ld, float *d_rgb, mr_hit *d_hits,
+                                    float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, const RayQueue &out,
+                                    unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream) {
     FrameLevelLightsArgs a;
-    mr_status st = fill_frame_lights_surface_args(a.f, "mr_render_level_lights", ds, tex, lights, n_lights, fd, d_rgb, d_hits,
-                                                  d_sample_rgb, d_sample_color, d_sample_normal, d_counts);
+    mr_status st = fill_frame_lights_surface_args(a.f, "mr_render_level_lights", ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color,
+                                                  d_sample_normal, d_counts);
     if (st != MR_OK || (st = launch_zero_count(d_out_count, stream)) != MR_OK) return st;
     if (a.f.eye.n == 0) return MR_OK;
-    a.env = env;
-    a.ch.out.rays = d_out_rays; a.ch.out.weights = d_out_weights; a.ch.out.pixels = d_out_pixels;
-    a.ch.out.ids = ld.children == MR_LEVEL_PATH ? d_out_ids : nullptr;
+    a.env = ls.env;
+    a.ch.out.rays = out.rays; a.ch.out.weights = out.weights; a.ch.out.pixels = out.pixels;
+    a.ch.out.ids = ld.children == MR_LEVEL_PATH ? out.ids : nullptr;
     a.ch.out.count = d_out_count;
-    a.ch.out.capacity = ((unsigned long long)ld.out_capacity_hi << 32) | ld.out_capacity_lo;
+    a.ch.out.capacity = out_capacity_of(ld);
     a.ch.out.octants = ld.d_out_octants;
-    a.ch.out_lowres = ld.d_out_lowres;
+    a.ch.out_lowres = out.low;
     a.ch.kinds = ld.path_kinds; a.ch.hbase = pcg32(ld.path_seed);
 
     // the traversal variants of launch_frame_lights_env / launch_level_lights: the same hit records from each of them
+    const DeviceScene &ds = *ls.ds;
     return with_trace_variant(ds.n_planes || ds.n_spheres, fd.flags & MR_MATH_PRODUCT, fd.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
         return ld.children == MR_LEVEL_PATH ? launch_frame_level_lights_t<VAR, 2>(a, stream) : launch_frame_level_lights_t<VAR, 1>(a, stream);

@@ -65,20 +65,19 @@ struct FrameLightsSurfaceArgs {
 };
 
 // what launch_frame_lights_surface and launch_frame_lights_env put into the block; `who`: the entry point the window's messages name
-inline mr_status fill_frame_lights_surface_args(FrameLightsSurfaceArgs &a, const char *who, const DeviceScene &ds, const TexParams &tex,
-                                                const ShadeLight *lights, uint32_t n_lights, const mr_frame_desc &fd, float *d_rgb,
-                                                mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color, float *d_sample_normal,
-                                                unsigned long long *d_counts) {
+inline mr_status fill_frame_lights_surface_args(FrameLightsSurfaceArgs &a, const char *who, const LightScene &ls, const mr_frame_desc &fd,
+                                                float *d_rgb, mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color,
+                                                float *d_sample_normal, unsigned long long *d_counts) {
     const mr_status st = frame_window_of(who, fd, a.eye);
     if (st != MR_OK) return st;
-    a.tp = scene_trace_params(ds);
+    a.tp = scene_trace_params(*ls.ds);
     a.tp.n = a.eye.n;
-    a.m = mesh_of(ds);
-    a.t = tex;
+    a.m = mesh_of(*ls.ds);
+    a.t = ls.tex;
     a.hits = d_hits; a.sample_rgb = d_sample_rgb; a.sample_color = d_sample_color; a.sample_normal = d_sample_normal;
     a.rgb = d_rgb; a.counts = d_counts;
-    a.n_lights = n_lights;
-    for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = lights[i < n_lights ? i : 0];
+    a.n_lights = ls.n_lights;
+    for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = ls.lights[i < ls.n_lights ? i : 0];
     return MR_OK;
 }
 

@@ -2,11 +2,12 @@
 // device (mr_render_recursion_photons, mr_api.cpp): the three steps of mr_gather_level -- queries, one k-NN estimate per map,
 // accumulate -- as kernels that read
 //
-//   n = min(*d_n, n_cap)      d_n: the word a level counted its rays or children into, n_cap: what the queue can hold
+//   n = min(*d_n, bound)      d_n: the word a level counted its rays or children into, bound: what the host knows the length
+//                             cannot exceed, at most what the queue can hold (the kernels take it as the queue's capacity)
 //
 // themselves, by every lane from the same address before anything else: a wave-uniform load from a kernel argument's pointer,
-// which comes out as a scalar load (mr_level_lights_queued.hip has the pattern).  The host sizes every grid from an upper bound
-// of n, never from n.  The per-ray steps are the definitions the host-n kernels call (mr_gather_level_body.h,
+// which comes out as a scalar load (mr_level_lights_queued.hip has the pattern).  The host sizes every grid from that bound,
+// never from n.  The per-ray steps are the definitions the host-n kernels call (mr_gather_level_body.h,
 // mr_irradiance_body.h), so a level's queries, estimates and pixel adds are what mr_gather_level makes of the same queue.
 //
 //   gather_queued_queries_kernel     gather_level_queries_kernel's step for rays [0, n); the queries made are counted into one
@@ -104,8 +105,6 @@ __global__ __launch_bounds__(kBlock) void gather_queued_accumulate_kernel(Accumu
         gather_accumulate_step(a, k, k < n);
 }
 
-inline unsigned long long least(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
-
 }  // namespace
 
 mr_status launch_gather_eye_queries(const DeviceScene &ds, const char *who, const mr_frame_desc &fd, const mr_hit *d_hits,
@@ -122,13 +121,12 @@ mr_status launch_gather_eye_queries(const DeviceScene &ds, const char *who, cons
 }
 
 mr_status launch_gather_queued_queries(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_normal,
-                                       const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_pos,
-                                       float *d_nrm, unsigned long long *d_queries, hipStream_t stream) {
-    const unsigned long long bound = least(n_cap, n_bound);
+                                       const unsigned long long *d_n, unsigned long long bound, float *d_pos, float *d_nrm,
+                                       unsigned long long *d_queries, hipStream_t stream) {
     if (bound == 0) return MR_OK;
     QueryArgs a;
     a.m = rec::mesh_of(ds);
-    a.rays = d_rays; a.hits = d_hits; a.normal = d_normal; a.n = n_cap;
+    a.rays = d_rays; a.hits = d_hits; a.normal = d_normal; a.n = bound;
     a.pos = d_pos; a.nrm = d_nrm; a.counts = d_queries;
     hipLaunchKernelGGL(gather_queued_queries_kernel, dim3(grid_for(bound)), dim3(kBlock), 0, stream, a, d_n);
     MR_HIP_CHECK(hipGetLastError());
@@ -136,9 +134,8 @@ mr_status launch_gather_queued_queries(const DeviceScene &ds, const mr_ray *d_ra
 }
 
 mr_status launch_irradiance_queued(const PhotonMapDev &pm, unsigned *work_counter, const float *d_pos, const float *d_normal,
-                                   const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float max_dist,
-                                   uint32_t k, float *d_irrad, unsigned long long *d_stats, hipStream_t stream) {
-    const unsigned long long bound = least(n_cap, n_bound);
+                                   const unsigned long long *d_n, unsigned long long bound, float max_dist, uint32_t k, float *d_irrad,
+                                   unsigned long long *d_stats, hipStream_t stream) {
     if (bound == 0) return MR_OK;
     int stack_cap = 0;
     size_t lds = 0;
@@ -146,23 +143,22 @@ mr_status launch_irradiance_queued(const PhotonMapDev &pm, unsigned *work_counte
     const mr_status st = irradiance_launch_shape(pm, work_counter, bound, stack_cap, lds, blocks);
     if (st != MR_OK) return st;
     if (d_stats)
-        hipLaunchKernelGGL(irradiance_queued_kernel<true>, dim3(blocks), dim3(kIrrBlock), lds, stream, pm, d_pos, d_normal, d_n, n_cap,
+        hipLaunchKernelGGL(irradiance_queued_kernel<true>, dim3(blocks), dim3(kIrrBlock), lds, stream, pm, d_pos, d_normal, d_n, bound,
                            max_dist, (int)k, d_irrad, d_stats, stack_cap, work_counter);
     else
-        hipLaunchKernelGGL(irradiance_queued_kernel<false>, dim3(blocks), dim3(kIrrBlock), lds, stream, pm, d_pos, d_normal, d_n, n_cap,
+        hipLaunchKernelGGL(irradiance_queued_kernel<false>, dim3(blocks), dim3(kIrrBlock), lds, stream, pm, d_pos, d_normal, d_n, bound,
                            max_dist, (int)k, d_irrad, d_stats, stack_cap, work_counter);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;
 }
 
 mr_status launch_gather_queued_accumulate(const float *d_irr_a, const float *d_irr_b, const float *d_weights, const uint32_t *d_pixels,
-                                          const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, uint32_t spp,
-                                          float *d_rgb, hipStream_t stream) {
-    const unsigned long long bound = least(n_cap, n_bound);
+                                          const unsigned long long *d_n, unsigned long long bound, uint32_t spp, float *d_rgb,
+                                          hipStream_t stream) {
     if (bound == 0) return MR_OK;
     AccumulateArgs a;
     a.irr_a = d_irr_a; a.irr_b = d_irr_b; a.weights = d_weights; a.pixels = d_pixels;
-    a.n = n_cap; a.spp = spp; a.inv_spp = 1.0f / (float)spp;
+    a.n = bound; a.spp = spp; a.inv_spp = 1.0f / (float)spp;
     a.rgb = d_rgb; a.ray_rgb = nullptr;
     hipLaunchKernelGGL(gather_queued_accumulate_kernel, dim3(grid_for(bound)), dim3(kBlock), 0, stream, a, d_n);
     MR_HIP_CHECK(hipGetLastError());

@@ -297,15 +297,12 @@ mr_status launch_frame_lights(const DeviceScene &ds, const ShadeLight *lights, u
 // ... on any scene (mr_frame_lights_surface.hip, mr_render_lights_surface): every hit's diffuse colour and normal from
 // hit_color_normal between the primary trace and the light loop.  tex: as mr_hit_surface hands it to launch_hit_surface
 // (recs / mat_tex nullptr without a texture table); d_sample_color / d_sample_normal optional; d_counts: three words
-struct TexParams;
-mr_status launch_frame_lights_surface(const DeviceScene &ds, const TexParams &tex, const ShadeLight *lights, uint32_t n_lights,
-                                      const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color,
-                                      float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream);
+struct LightScene;
+mr_status launch_frame_lights_surface(const LightScene &ls, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
+                                      float *d_sample_color, float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream);
 // ... with the environment for rays that miss (mr_frame_lights_env.hip, mr_render_lights_environment): a live sample whose
-// primary ray misses is worth env.bg, or the lookup of the full image (env.full); d_counts: five words
-struct EnvParams;
-mr_status launch_frame_lights_env(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                                  uint32_t n_lights, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
+// primary ray misses is worth ls.env.bg, or the lookup of the full image (ls.env.full); d_counts: five words
+mr_status launch_frame_lights_env(const LightScene &ls, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
                                   float *d_sample_color, float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream);
 // *d_count = 0 on `stream`, as a one-word kernel: the node that zeroes d_out_count in the three launchers below, which a captured
 // graph replays as written (mr_level_lights.hip says what a memset node did)
@@ -313,51 +310,58 @@ mr_status launch_zero_count(unsigned long long *d_count, hipStream_t stream);
 // one level of the recursion over the light list on any scene (mr_level_lights.hip, mr_trace_level_lights): launch_level's queues
 // with that frame's texture table, environment (read with ld.environment only) and optional per-ray outputs; d_out_count is
 // zeroed on `stream` on a level with children (a one-word kernel), then one kernel (none for n == 0); d_counts: five words
-mr_status launch_level_lights(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                              uint32_t n_lights, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
+mr_status launch_level_lights(const LightScene &ls, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
                               const uint32_t *d_pixels, unsigned long long n, float *d_rgb, mr_hit *d_hits, float *d_ray_rgb,
                               float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
                               unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
 // ... of a PATH_TRACING build (mr_level_lights_path.hip, mr_trace_level_lights_path): the same level with the children of
 // mr_gen_path_rays_surface (ids in and out, ld.path_kinds / seed / bounce), the low-res environment image for the rays that
 // ld.d_lowres or MR_ENV_LOWRES names, and ld.d_out_lowres for the next level
-mr_status launch_level_lights_path(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                                   uint32_t n_lights, const mr_level_lights_path_desc &ld, const mr_ray *d_rays, const float *d_weights,
+mr_status launch_level_lights_path(const LightScene &ls, const mr_level_lights_path_desc &ld, const mr_ray *d_rays, const float *d_weights,
                                    const uint32_t *d_pixels, const uint32_t *d_ids, unsigned long long n, float *d_rgb, mr_hit *d_hits,
                                    float *d_ray_rgb, float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights,
                                    uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_out_count,
                                    unsigned long long *d_counts, hipStream_t stream);
+// A queue of rays between two levels, array by array: what a level with children writes and the next level reads.  ids: the path
+// tracer's stable ray ids, low: its byte per ray that says whether Ray::random made the ray; nullptr where the queue has none
+struct RayQueue {
+    mr_ray *rays;
+    float *weights;
+    uint32_t *pixels, *ids;
+    uint8_t *low;
+};
+// the capacity of the output queue as a level's descriptor spells it (mr_level_lights_desc, mr_level_lights_path_desc, mr_frame_level_desc)
+template <typename DESC>
+unsigned long long out_capacity_of(const DESC &ld) { return ((unsigned long long)ld.out_capacity_hi << 32) | ld.out_capacity_lo; }
 // the level-0 frame that also emits the rays of level 1 (mr_frame_level_lights.hip, mr_render_level_lights): launch_frame_lights_env's
 // frame (env all zero: a miss is worth 0) with the children of launch_level_lights (ld.children == MR_LEVEL_SPECULAR) or
 // launch_level_lights_path (MR_LEVEL_PATH; bounce 0, ids = sample indices) for rays that start at the eye with weight 1 and pixel
-// row * W + x; d_out_count is zeroed on `stream` (a one-word kernel), then one kernel (none for an empty window).
+// row * W + x, written to `out` (out.low takes the place of ld.d_out_lowres, which is not read); d_out_count is zeroed on `stream`
+// (a one-word kernel), then one kernel (none for an empty window).
 // frame_level_lights_samples: the samples of fd's window, from the descriptor alone (no device call)
 mr_status frame_level_lights_samples(const char *who, const mr_frame_desc &fd, unsigned long long &n);
-mr_status launch_frame_level_lights(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                                    uint32_t n_lights, const mr_frame_desc &fd, const mr_frame_level_desc &ld, float *d_rgb, mr_hit *d_hits,
-                                    float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, mr_ray *d_out_rays,
-                                    float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_out_count,
-                                    unsigned long long *d_counts, hipStream_t stream);
-// the two level launches for a queue whose length is a device word (mr_level_lights_queued.hip, mr_render_recursion): the queue
-// holds min(*d_n, n_cap) rays, read by the kernel; the grid is level_lights_queued_grid(n_cap, n_bound) workgroups, n_bound being
-// what the host knows the length cannot exceed, and workgroups beyond the length leave at once.  Per-ray outputs besides the pixels:
-// d_hits and d_normal, both optional (the photon-map term of mr_render_recursion_photons reads them); d_out_count is NOT zeroed (launch_zero_words: d_words[0 .. n) = 0 on `stream`, as a kernel); ONE kernel, also for an
-// empty queue.  ld.d_out_octants is not supported by the driver and passed as it is
+mr_status launch_frame_level_lights(const LightScene &ls, const mr_frame_desc &fd, const mr_frame_level_desc &ld, float *d_rgb, mr_hit *d_hits,
+                                    float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, const RayQueue &out,
+                                    unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
+// One level of mr_render_recursion, whose queue's length is a device word (mr_level_lights_queued.hip).  What the level is:
+// path: the PATH_TRACING build's kernel (children of bounce `bounce` from path_kinds / seed, ids, low-res bytes), else the
+// specular one; last: no children; capacity: the rays the output queue holds
+struct QueuedLevel {
+    uint32_t spp, flags;
+    bool last, path;
+    uint32_t environment, path_kinds, seed, bounce;
+    unsigned long long capacity;
+};
+// `in` holds min(*d_n, n_cap) rays, read by the kernel; the grid is level_lights_queued_grid(n_cap, n_bound) workgroups, n_bound
+// being what the host knows the length cannot exceed, and workgroups beyond the length leave at once.  Per-ray outputs besides
+// the pixels: d_hits and d_normal, both optional (the photon-map term of mr_render_recursion_photons reads them).  row: the
+// level's eight counters -- [0 .. 5) as launch_level_lights' d_counts, [5] += children into `out`, stored or not, and NOT zeroed
+// here (launch_zero_words: d_words[0 .. n) = 0 on `stream`, as a kernel); ONE kernel, also for an empty queue
 unsigned level_lights_queued_grid(unsigned long long n_cap, unsigned long long n_bound);
 mr_status launch_zero_words(unsigned long long *d_words, unsigned long long n, hipStream_t stream);
-mr_status launch_level_lights_queued(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                                     uint32_t n_lights, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
-                                     const uint32_t *d_pixels, const unsigned long long *d_n, unsigned long long n_cap,
-                                     unsigned long long n_bound, float *d_rgb, mr_hit *d_hits, float *d_normal, mr_ray *d_out_rays,
-                                     float *d_out_weights, uint32_t *d_out_pixels, unsigned long long *d_out_count,
-                                     unsigned long long *d_counts, hipStream_t stream);
-mr_status launch_level_lights_path_queued(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                                          uint32_t n_lights, const mr_level_lights_path_desc &ld, const mr_ray *d_rays,
-                                          const float *d_weights, const uint32_t *d_pixels, const uint32_t *d_ids,
-                                          const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_rgb,
-                                          mr_hit *d_hits, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
-                                          uint32_t *d_out_ids, unsigned long long *d_out_count, unsigned long long *d_counts,
-                                          hipStream_t stream);
+mr_status launch_level_lights_queued(const LightScene &ls, const QueuedLevel &lv, const RayQueue &in, const RayQueue &out,
+                                     const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_rgb,
+                                     mr_hit *d_hits, float *d_normal, unsigned long long *row, hipStream_t stream);
 
 // the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
 // square light, side * side shadow rays per hit and light
@@ -452,6 +456,17 @@ mr_status launch_shade_environment(const EnvParams &env, const mr_ray *d_rays, c
                                    const uint32_t *d_pixels, const uint8_t *d_lowres, unsigned long long n, uint32_t spp,
                                    uint32_t flags, float *d_rgb, float *d_ray_rgb, unsigned long long *d_counts, hipStream_t stream);
 
+// What every light-list launch reads from the scene (lights_scene_params, mr_api.cpp): the device arrays, the texture table or
+// none, the environment (all zero where the call has none) and the light list.  Made for ONE API call and not kept: ds and lights
+// point into the mr_scene (s->dev, s->lights), which the next mr_scene_set_* call may change
+struct LightScene {
+    const DeviceScene *ds;
+    TexParams tex;
+    EnvParams env;
+    const ShadeLight *lights;
+    uint32_t n_lights;
+};
+
 // photon map on the device: three float4 planes in kd-tree heap order, 1-based (children of i: 2i, 2i+1)
 struct PhotonMapDev {
     float4 *rec = nullptr;        // two per photon, one 32-byte record: (x, y, z, split axis as int bits), then the incoming
@@ -484,21 +499,28 @@ mr_status launch_irradiance(const PhotonMapDev &pm, unsigned *work_counter, cons
                             hipStream_t stream);
 constexpr int kPhotonStats = 12;  // see mr_photon_map_get_stats (miro_hip.h)
 // The photon-map term for a queue whose length is a device word (mr_gather_queued.hip, mr_render_recursion_photons): the three
-// steps of mr_gather_level as kernels that read n = min(*d_n, n_cap) themselves.  Every grid is sized from min(n_cap, n_bound),
-// n_bound being what the host knows the length cannot exceed; nothing is launched where that is 0.  d_queries: one word, += the
-// queries made.  launch_gather_eye_queries: level 0 of the one-call frame, whose rays exist in registers only -- the eye ray of
-// sample k of fd's window is made again and joined with the hit record (and, given d_normal, the normal) the frame wrote.
+// steps of mr_gather_level as kernels that read n = min(*d_n, bound) themselves.  bound: what the host knows the length cannot
+// exceed, at most the queue's capacity -- every grid is sized from it and every buffer holds that many rays; nothing is launched
+// where it is 0.  d_queries: one word, += the queries made.  launch_gather_eye_queries: level 0 of the one-call frame, whose rays
+// exist in registers only -- the eye ray of sample k of fd's window is made again and joined with the hit record (and, given
+// d_normal, the normal) the frame wrote.
 mr_status launch_gather_eye_queries(const DeviceScene &ds, const char *who, const mr_frame_desc &fd, const mr_hit *d_hits,
                                     const float *d_normal, float *d_pos, float *d_nrm, unsigned long long *d_queries, hipStream_t stream);
 mr_status launch_gather_queued_queries(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_normal,
-                                       const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_pos,
-                                       float *d_nrm, unsigned long long *d_queries, hipStream_t stream);
+                                       const unsigned long long *d_n, unsigned long long bound, float *d_pos, float *d_nrm,
+                                       unsigned long long *d_queries, hipStream_t stream);
 mr_status launch_irradiance_queued(const PhotonMapDev &pm, unsigned *work_counter, const float *d_pos, const float *d_normal,
-                                   const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float max_dist,
-                                   uint32_t k, float *d_irrad, unsigned long long *d_stats, hipStream_t stream);
+                                   const unsigned long long *d_n, unsigned long long bound, float max_dist, uint32_t k, float *d_irrad,
+                                   unsigned long long *d_stats, hipStream_t stream);
 mr_status launch_gather_queued_accumulate(const float *d_irr_a, const float *d_irr_b, const float *d_weights, const uint32_t *d_pixels,
-                                          const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, uint32_t spp,
-                                          float *d_rgb, hipStream_t stream);
+                                          const unsigned long long *d_n, unsigned long long bound, uint32_t spp, float *d_rgb,
+                                          hipStream_t stream);
+// The scratch of the photon-map term for n rays (mr_gather_level's d_scratch, 12 n floats): positions, normals (NaN = no query),
+// then the global map's estimate and the caustic map's; irr[i]: nullptr without map i
+struct GatherScratch { float *pos, *nrm, *irr[2]; };
+inline GatherScratch gather_scratch(float *d_scratch, unsigned long long n, bool global_map, bool caustic_map) {
+    return {d_scratch, d_scratch + 3 * n, {global_map ? d_scratch + 6 * n : nullptr, caustic_map ? d_scratch + 9 * n : nullptr}};
+}
 
 // photon tracing (mr_photon_walk.hip): one round = emissions first ... first + count - 1 of one light, walked to their end
 struct PhotonWalkLight {
@@ -541,8 +563,7 @@ uint32_t photon_map_stored(const mr_photon_map *m);
 // next of the map's hand-out counters and the map's statistics as mr_irradiance_estimate's launch does
 bool photon_map_resident(const mr_photon_map *m);
 mr_status photon_map_estimate_queued(mr_photon_map *m, const float *d_pos, const float *d_normal, const unsigned long long *d_n,
-                                     unsigned long long n_cap, unsigned long long n_bound, float max_dist, uint32_t nphotons,
-                                     float *d_irrad, hipStream_t stream);
+                                     unsigned long long bound, float max_dist, uint32_t nphotons, float *d_irrad, hipStream_t stream);
 
 // the photon map built on the device (mr_photon_build.hip; mr_photon_map_build_device): store + scale + balance of one batch of
 // records on an empty map.  The workspace lives from _begin to _end; the stages run in the order declared.

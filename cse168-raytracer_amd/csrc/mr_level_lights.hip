@@ -55,8 +55,7 @@ mr_status launch_zero_count(unsigned long long *d_count, hipStream_t stream) {
     return MR_OK;
 }
 
-mr_status launch_level_lights(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                              uint32_t n_lights, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
+mr_status launch_level_lights(const LightScene &ls, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
                               const uint32_t *d_pixels, unsigned long long n, float *d_rgb, mr_hit *d_hits, float *d_ray_rgb,
                               float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
                               unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream) {
@@ -66,10 +65,11 @@ mr_status launch_level_lights(const DeviceScene &ds, const TexParams &tex, const
     }
     if (n == 0) return MR_OK;
     LevelLightsArgs a;
-    fill_level_lights_args(a, ds, tex, env, lights, n_lights, ld, d_rays, d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal,
-                           d_out_rays, d_out_weights, d_out_pixels, nullptr, d_out_count, d_counts);
+    fill_level_lights_args(a, ls, ld.spp, ld.environment, d_rays, d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal,
+                           d_out_rays, d_out_weights, d_out_pixels, nullptr, d_out_count, out_capacity_of(ld), ld.d_out_octants, d_counts);
 
     // the traversal variants of launch_level / launch_frame_lights_env: the same hit records from each of them
+    const DeviceScene &ds = *ls.ds;
     return with_trace_variant(ds.n_planes || ds.n_spheres, ld.flags & MR_MATH_PRODUCT, ld.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
         return launch_level_lights_t(ld.children == MR_LEVEL_LAST ? &level_lights_kernel<VAR, 0> : &level_lights_kernel<VAR, 1>, a, stream);

@@ -222,27 +222,37 @@ __device__ __forceinline__ void level_lights_body(const ARGS a, int *s_stack, ui
     }
 }
 
-// what launch_level_lights and launch_level_lights_path both put into their block; `ld`: either call's descriptor
-template <typename ARGS, typename DESC>
-void fill_level_lights_args(ARGS &a, const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                            uint32_t n_lights, const DESC &ld, const mr_ray *d_rays, const float *d_weights, const uint32_t *d_pixels,
-                            unsigned long long n, float *d_rgb, mr_hit *d_hits, float *d_ray_rgb, float *d_color, float *d_normal,
-                            mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids,
-                            unsigned long long *d_out_count, unsigned long long *d_counts) {
-    a.tp = scene_trace_params(ds);
+// what every level launch puts into its block, of either build; out_capacity, d_out_octants: the output queue's, as the level's
+// descriptor names them
+template <typename ARGS>
+void fill_level_lights_args(ARGS &a, const LightScene &ls, uint32_t spp, uint32_t environment, const mr_ray *d_rays, const float *d_weights,
+                            const uint32_t *d_pixels, unsigned long long n, float *d_rgb, mr_hit *d_hits, float *d_ray_rgb, float *d_color,
+                            float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids,
+                            unsigned long long *d_out_count, unsigned long long out_capacity, uint8_t *d_out_octants,
+                            unsigned long long *d_counts) {
+    a.tp = scene_trace_params(*ls.ds);
     a.tp.rays = d_rays; a.tp.n = n;
-    a.m = mesh_of(ds);
-    a.t = tex;
-    a.env = env;
+    a.m = mesh_of(*ls.ds);
+    a.t = ls.tex;
+    a.env = ls.env;
     a.weights = d_weights; a.pixels = d_pixels;
-    a.spp = ld.spp; a.environment = ld.environment; a.inv_spp = 1.0f / (float)ld.spp;
+    a.spp = spp; a.environment = environment; a.inv_spp = 1.0f / (float)spp;
     a.hits = d_hits; a.ray_rgb = d_ray_rgb; a.color = d_color; a.normal = d_normal; a.rgb = d_rgb;
     a.out.rays = d_out_rays; a.out.weights = d_out_weights; a.out.pixels = d_out_pixels; a.out.ids = d_out_ids; a.out.count = d_out_count;
-    a.out.capacity = ((unsigned long long)ld.out_capacity_hi << 32) | ld.out_capacity_lo;
-    a.out.octants = ld.d_out_octants;
+    a.out.capacity = out_capacity;
+    a.out.octants = d_out_octants;
     a.counts = d_counts;
-    a.n_lights = n_lights;
-    for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = lights[i < n_lights ? i : 0];
+    a.n_lights = ls.n_lights;
+    for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = ls.lights[i < ls.n_lights ? i : 0];
+}
+// ... and what the PATH_TRACING build's block holds besides: the queue's ids and low-res bytes (every ray's with MR_ENV_LOWRES in
+// `flags`), the children's generators and the low-res bytes of the output queue
+inline void fill_level_lights_path_args(LevelLightsPathArgs &a, const uint32_t *d_ids, const uint8_t *d_lowres, uint32_t flags, uint32_t seed,
+                                        uint32_t bounce, uint32_t path_kinds, uint8_t *d_out_lowres) {
+    a.ids = d_ids; a.lowres = d_lowres;
+    a.all_lowres = (flags & MR_ENV_LOWRES) ? 1u : 0u;
+    a.hbase = pcg32(seed); a.bounce = bounce; a.kinds = path_kinds;
+    a.out_lowres = d_out_lowres;
 }
 
 // one workgroup per kTraceBlock rays of the queue, the traversal stack in dynamic LDS

@@ -54,8 +54,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
 
 }  // namespace
 
-mr_status launch_level_lights_path(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                                   uint32_t n_lights, const mr_level_lights_path_desc &ld, const mr_ray *d_rays, const float *d_weights,
+mr_status launch_level_lights_path(const LightScene &ls, const mr_level_lights_path_desc &ld, const mr_ray *d_rays, const float *d_weights,
                                    const uint32_t *d_pixels, const uint32_t *d_ids, unsigned long long n, float *d_rgb, mr_hit *d_hits,
                                    float *d_ray_rgb, float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights,
                                    uint32_t *d_out_pixels, uint32_t *d_out_ids, unsigned long long *d_out_count,
@@ -66,14 +65,12 @@ mr_status launch_level_lights_path(const DeviceScene &ds, const TexParams &tex, 
     }
     if (n == 0) return MR_OK;
     LevelLightsPathArgs a;
-    fill_level_lights_args(a, ds, tex, env, lights, n_lights, ld, d_rays, d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal,
-                           d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_count, d_counts);
-    a.ids = d_ids; a.lowres = ld.d_lowres;
-    a.all_lowres = (ld.flags & MR_ENV_LOWRES) ? 1u : 0u;
-    a.hbase = pcg32(ld.seed); a.bounce = ld.bounce; a.kinds = ld.path_kinds;
-    a.out_lowres = ld.d_out_lowres;
+    fill_level_lights_args(a, ls, ld.spp, ld.environment, d_rays, d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal,
+                           d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_count, out_capacity_of(ld), ld.d_out_octants, d_counts);
+    fill_level_lights_path_args(a, d_ids, ld.d_lowres, ld.flags, ld.seed, ld.bounce, ld.path_kinds, ld.d_out_lowres);
 
     // the traversal variants of launch_level_lights: the same hit records from each of them
+    const DeviceScene &ds = *ls.ds;
     return with_trace_variant(ds.n_planes || ds.n_spheres, ld.flags & MR_MATH_PRODUCT, ld.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
         return launch_level_lights_t(ld.children == MR_LEVEL_LAST ? &level_lights_path_kernel<VAR, 0> : &level_lights_path_kernel<VAR, 1>, a,

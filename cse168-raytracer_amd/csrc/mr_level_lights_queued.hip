@@ -99,43 +99,32 @@ mr_status launch_zero_words(unsigned long long *d_words, unsigned long long n, h
     return MR_OK;
 }
 
-mr_status launch_level_lights_queued(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                                     uint32_t n_lights, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
-                                     const uint32_t *d_pixels, const unsigned long long *d_n, unsigned long long n_cap,
-                                     unsigned long long n_bound, float *d_rgb, mr_hit *d_hits, float *d_normal, mr_ray *d_out_rays,
-                                     float *d_out_weights, uint32_t *d_out_pixels, unsigned long long *d_out_count,
-                                     unsigned long long *d_counts, hipStream_t stream) {
-    LevelLightsArgs a;
-    fill_level_lights_args(a, ds, tex, env, lights, n_lights, ld, d_rays, d_weights, d_pixels, 0ull, d_rgb, d_hits, nullptr, nullptr, d_normal,
-                           d_out_rays, d_out_weights, d_out_pixels, nullptr, d_out_count, d_counts);
-
+// LevelLightsArgs or LevelLightsPathArgs for level `lv` between the two queues, and the kernel of that build
+mr_status launch_level_lights_queued(const LightScene &ls, const QueuedLevel &lv, const RayQueue &in, const RayQueue &out,
+                                     const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_rgb,
+                                     mr_hit *d_hits, float *d_normal, unsigned long long *row, hipStream_t stream) {
+    const DeviceScene &ds = *ls.ds;
+    auto fill = [&](auto &a) {
+        fill_level_lights_args(a, ls, lv.spp, lv.environment, in.rays, in.weights, in.pixels, 0ull, d_rgb, d_hits, nullptr, nullptr, d_normal,
+                               out.rays, out.weights, out.pixels, out.ids, row + 5, lv.capacity, nullptr, row);
+    };
     // the traversal variants of launch_level_lights: the same hit records from each of them
-    return with_trace_variant(ds.n_planes || ds.n_spheres, ld.flags & MR_MATH_PRODUCT, ld.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
-        constexpr int VAR = decltype(var)::value;
-        return launch_queued_t(ld.children == MR_LEVEL_LAST ? &level_lights_queued_kernel<VAR, 0> : &level_lights_queued_kernel<VAR, 1>, a, d_n,
-                               n_cap, n_bound, stream);
-    });
-}
-
-mr_status launch_level_lights_path_queued(const DeviceScene &ds, const TexParams &tex, const EnvParams &env, const ShadeLight *lights,
-                                          uint32_t n_lights, const mr_level_lights_path_desc &ld, const mr_ray *d_rays,
-                                          const float *d_weights, const uint32_t *d_pixels, const uint32_t *d_ids,
-                                          const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_rgb,
-                                          mr_hit *d_hits, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
-                                          uint32_t *d_out_ids, unsigned long long *d_out_count, unsigned long long *d_counts,
-                                          hipStream_t stream) {
+    if (!lv.path) {
+        LevelLightsArgs a;
+        fill(a);
+        return with_trace_variant(ds.n_planes || ds.n_spheres, lv.flags & MR_MATH_PRODUCT, lv.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
+            constexpr int VAR = decltype(var)::value;
+            return launch_queued_t(lv.last ? &level_lights_queued_kernel<VAR, 0> : &level_lights_queued_kernel<VAR, 1>, a, d_n, n_cap, n_bound,
+                                   stream);
+        });
+    }
     LevelLightsPathArgs a;
-    fill_level_lights_args(a, ds, tex, env, lights, n_lights, ld, d_rays, d_weights, d_pixels, 0ull, d_rgb, d_hits, nullptr, nullptr, d_normal,
-                           d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_count, d_counts);
-    a.ids = d_ids; a.lowres = ld.d_lowres;
-    a.all_lowres = (ld.flags & MR_ENV_LOWRES) ? 1u : 0u;
-    a.hbase = pcg32(ld.seed); a.bounce = ld.bounce; a.kinds = ld.path_kinds;
-    a.out_lowres = ld.d_out_lowres;
-
-    return with_trace_variant(ds.n_planes || ds.n_spheres, ld.flags & MR_MATH_PRODUCT, ld.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
+    fill(a);
+    fill_level_lights_path_args(a, in.ids, in.low, lv.flags, lv.seed, lv.bounce, lv.path_kinds, lv.last ? nullptr : out.low);
+    return with_trace_variant(ds.n_planes || ds.n_spheres, lv.flags & MR_MATH_PRODUCT, lv.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
-        return launch_queued_t(ld.children == MR_LEVEL_LAST ? &level_lights_path_queued_kernel<VAR, 0> : &level_lights_path_queued_kernel<VAR, 1>,
-                               a, d_n, n_cap, n_bound, stream);
+        return launch_queued_t(lv.last ? &level_lights_path_queued_kernel<VAR, 0> : &level_lights_path_queued_kernel<VAR, 1>, a, d_n, n_cap,
+                               n_bound, stream);
     });
 }
 

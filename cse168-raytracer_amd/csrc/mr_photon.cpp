@@ -163,20 +163,19 @@ mr_status estimate(mr_photon_map *m, const float *d_pos, const float *d_normal, 
     return launch_irradiance(m->dev, counter, d_pos, d_normal, n_queries, max_dist, nphotons, d_irrad, d_found, d_r2, m->d_stats, stream);
 }
 
-// What mr_final_gather and mr_gather_level do between their own checks and their own accumulate step.  d_scratch, in floats:
-// [0, 3n) positions, [3n, 6n) normals (NaN = no query), [6n, 9n) the global map's estimate, [9n, 12n) the caustic map's.
-// d_irr[i]: where map i's estimate is, NULL without that map.
+// What mr_final_gather and mr_gather_level do between their own checks and their own accumulate step.  d_scratch: laid out by
+// gather_scratch (mr_internal.h); d_irr[i]: where map i's estimate is, NULL without that map.
 mr_status gather_estimates(mr_scene *s, mr_photon_map *const maps[2], const mr_ray *d_rays, const mr_hit *d_hits, const float *d_normal,
                            uint64_t n, float max_dist, uint32_t nphotons, float *d_scratch, uint64_t *d_counts, hipStream_t stream,
                            float *d_irr[2]) {
     MR_HIP_CHECK(hipSetDevice(s->device));
-    float *d_pos = d_scratch, *d_nrm = d_scratch + 3 * n;
-    mr_status st = launch_gather_level_queries(s->dev, d_rays, d_hits, d_normal, n, d_pos, d_nrm, reinterpret_cast<unsigned long long *>(d_counts), stream);
+    const GatherScratch sc = gather_scratch(d_scratch, n, maps[0] != nullptr, maps[1] != nullptr);
+    mr_status st = launch_gather_level_queries(s->dev, d_rays, d_hits, d_normal, n, sc.pos, sc.nrm, reinterpret_cast<unsigned long long *>(d_counts), stream);
     if (st != MR_OK) return st;
     for (int i = 0; i < 2; i++) {
-        d_irr[i] = maps[i] ? d_scratch + (6 + 3 * i) * n : nullptr;
+        d_irr[i] = sc.irr[i];
         if (!maps[i]) continue;
-        st = estimate(maps[i], d_pos, d_nrm, n, max_dist, nphotons, d_irr[i], nullptr, nullptr, stream);
+        st = estimate(maps[i], sc.pos, sc.nrm, n, max_dist, nphotons, d_irr[i], nullptr, nullptr, stream);
         if (st != MR_OK) return st;
     }
     return MR_OK;
@@ -190,10 +189,9 @@ bool photon_map_balanced(const mr_photon_map *m) { return m->balanced; }
 uint32_t photon_map_stored(const mr_photon_map *m) { return m->count(); }
 bool photon_map_resident(const mr_photon_map *m) { return m->balanced && m->on_device; }
 mr_status photon_map_estimate_queued(mr_photon_map *m, const float *d_pos, const float *d_normal, const unsigned long long *d_n,
-                                     unsigned long long n_cap, unsigned long long n_bound, float max_dist, uint32_t nphotons,
-                                     float *d_irrad, hipStream_t stream) {
+                                     unsigned long long bound, float max_dist, uint32_t nphotons, float *d_irrad, hipStream_t stream) {
     unsigned *counter = m->dev.work_counters + (m->next_counter.fetch_add(1) % kPhotonWorkCounters);
-    return launch_irradiance_queued(m->dev, counter, d_pos, d_normal, d_n, n_cap, n_bound, max_dist, nphotons, d_irrad, m->d_stats, stream);
+    return launch_irradiance_queued(m->dev, counter, d_pos, d_normal, d_n, bound, max_dist, nphotons, d_irrad, m->d_stats, stream);
 }
 }  // namespace mr
 
