@@ -70,14 +70,18 @@ __device__ __forceinline__ void shade_point_of(const A &a, unsigned long long k,
     mt = rec::material_of(a.m, __float_as_uint(h.y));
 }
 // the ray's L to d_ray_rgb, and weight * L / spp to its pixel.  Called by all lanes of the wave (accumulate_runs).
+// One product per ray, hit or miss, as the level kernels form it (mr_level_lights_body.h): Scene::traceScene answers true for a
+// ray that leaves the scene (Scene.cpp:338-342), so the parent adds weight * m_bgColor = weight * 0 (Scene.cpp:309, 325, 334),
+// which is NaN for a weight that is not finite -- the weight of a child made at a hit whose normal is NaN.  For a finite weight
+// the product is a zero, which accumulate_runs does not add.  L is 0 for a ray that missed.
 template <typename A>
-__device__ __forceinline__ void store_shaded(const A &a, unsigned long long k, bool live, bool hit, const float L[3]) {
+__device__ __forceinline__ void store_shaded(const A &a, unsigned long long k, bool live, const float L[3]) {
     if (a.ray_rgb && live) { a.ray_rgb[3 * k] = L[0]; a.ray_rgb[3 * k + 1] = L[1]; a.ray_rgb[3 * k + 2] = L[2]; }
     if (a.rgb) {                                                       // wave-uniform
         uint32_t pix = 0xFFFFFFFFu;
         float v[3] = {0.f, 0.f, 0.f};
-        if (live) pix = rec::pixel_of(a.pixels, k, a.spp);
-        if (hit) {
+        if (live) {
+            pix = rec::pixel_of(a.pixels, k, a.spp);
             float w[3];
             rec::weight_of(a.weights, k, w);
             for (int c = 0; c < 3; c++) v[c] = L[c] * w[c] * a.inv_spp;
@@ -106,7 +110,7 @@ __device__ __forceinline__ void shade_lights_body(const LightsArgs a, const TexP
     for (unsigned long long k = (unsigned long long)xcd_block_id() * kTraceBlock + tid; k < n_round; k += stride) {
         const bool live = k < n;
         const float4 h = hit_record_of(a.s, k, live);
-        const bool hit = __float_as_uint(h.y) != MR_MISS;              // a miss contributes nothing (m_bgColor = 0)
+        const bool hit = __float_as_uint(h.y) != MR_MISS;              // a miss keeps L = 0 (m_bgColor); store_shaded forms weight * 0
         float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 1.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
         const float *mt = a.s.m.mats;
         float col[3] = {0.f, 0.f, 0.f};                                // diffuseColor, unless the material's own
@@ -147,7 +151,7 @@ __device__ __forceinline__ void shade_lights_body(const LightsArgs a, const TexP
                 L[0] += out[0]; L[1] += out[1]; L[2] += out[2];
             }
         }
-        store_shaded(a.s, k, live, hit, L);
+        store_shaded(a.s, k, live, L);
     }
 
     if (a.s.counts) workgroup_add<kTraceBlock>(my_shadow_rays, &a.s.counts[0]);

@@ -85,7 +85,7 @@ __device__ __forceinline__ void shade_square_lights_body(const SquareArgs a, con
     for (unsigned long long k = (unsigned long long)xcd_block_id() * kTraceBlock + tid; k < n_round; k += stride) {
         const bool live = k < n;
         const float4 h = hit_record_of(a, k, live);
-        const bool hit = __float_as_uint(h.y) != MR_MISS;              // a miss contributes nothing
+        const bool hit = __float_as_uint(h.y) != MR_MISS;              // a miss keeps L = 0; store_shaded forms weight * 0
         float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 1.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
         const float *mt = a.m.mats;
         float col[3] = {0.f, 0.f, 0.f};                                // diffuseColor, unless the material's own
@@ -123,7 +123,7 @@ __device__ __forceinline__ void shade_square_lights_body(const SquareArgs a, con
                     }
                 }
         }
-        store_shaded(a, k, live, hit, L);
+        store_shaded(a, k, live, L);
     }
 
     if (a.counts) workgroup_add<kTraceBlock>(my_shadow_rays, &a.counts[0]);

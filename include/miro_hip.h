@@ -411,7 +411,9 @@ mr_status mr_trace_level(mr_scene *scene, const mr_level_desc *level, const mr_r
  * arguments).  Only mr_shade_lights reads it: every other shading entry keeps its single mr_light argument.
  *   MR_LIGHT_POINT  PointLight (PointLight.h:8-59): position, color, wattage; normal and radius are ignored.
  *   MR_LIGHT_DISC   DirectionalAreaLight (DirectionalAreaLight.h:7-38 on SquareLight.h): the light mr_trace_photons emits from.
- * mr_shade_lights is Phong::shade (Phong.cpp:44-160) for n traced rays: per ray with a hit (a miss contributes nothing), L = 0;
+ * mr_shade_lights is Phong::shade (Phong.cpp:44-160) for n traced rays: per ray with a hit (a miss keeps L = 0: its product
+ * weight * 0 is a zero, which is not added, unless the weight is not finite -- then it is the NaN that Scene.cpp:309-342 adds for
+ * a child that leaves the scene, and that mr_trace_level_lights adds; mr_shade_accumulate skips every miss), L = 0;
  * for every light IN LIST ORDER the shadow ray is built (Phong.cpp:80-92) and traced (Scene::trace, closest hit: the occluder's
  * material matters), the occluder's light scale applied (Phong.cpp:97-113: opaque -> the light is skipped, refractive ->
  * dot(N, l), skipped if negative or < epsilon), and the light's diffuse term times the scale plus its highlight

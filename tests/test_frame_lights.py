@@ -5,7 +5,8 @@ The yardstick everywhere is the batched chain on the same scene, camera, seed an
 
     gen_eye_rays[_tiled] -> trace -> shade_lights(..., d_ray_rgb=...)
 
-which tests/test_lights.py holds against the oracle and the restatement.  The comparisons are EXACT: both sides run the same
+which tests/test_lights.py holds against the oracle and the restatement, and tests/test_lights_fuzz.py does so -- chain and
+frame -- on seeded tie and NaN scenes.  The comparisons are EXACT: both sides run the same
 device functions in the same order under -ffp-contract=off.  Hit records are compared on their bits, per-sample L with
 np.array_equal(equal_nan=True), and d_rgb against the pairwise tree over the chain's per-sample L (x[:, 0::2] + x[:, 1::2] in
 float32 until one value is left, times float32(1 / spp) when spp > 1 -- the xor-butterfly of the kernel, seen from sample 0)."""

@@ -8,7 +8,8 @@ The yardstick everywhere is the batched chain on the same queue,
     trace -> hit_surface -> shade_lights_surface(..., d_ray_rgb) || shade_environment(flags 0, d_ray_rgb) -> gen_secondary_rays
 
 which tests/test_procedural.py, tests/test_solid_textures.py, tests/test_lights.py, tests/test_environment.py and
-tests/test_specular.py hold against the oracle and the restatements.  Per-ray outputs and counters are compared EXACTLY (both
+tests/test_specular.py hold against the oracle and the restatements (tests/test_lights_fuzz.py: the light loop and this kernel
+against its chain on seeded tie and NaN scenes).  Per-ray outputs and counters are compared EXACTLY (both
 sides run the same device functions in the same order under -ffp-contract=off), the children as sets (the two compactions order
 them differently), the pixel sums within the bound of tests/test_level.py (float atomics).
 

@@ -33,7 +33,21 @@ def dot3(a, b):
 
 
 def normalised(N):                                              # Scene.cpp:262
-    return (N * (F(1) / np.sqrt(dot3(N, N)))[:, None]).astype(F)
+    with np.errstate(divide="ignore", invalid="ignore"):                        # a zero-length N: 0 * inf = NaN, as in the reference
+        return (N * (F(1) / np.sqrt(dot3(N, N)))[:, None]).astype(F)
+
+
+def std_max(a, b):
+    """std::max(a, b) = (a < b) ? b : a.  A NaN b gives a, where np.maximum gives NaN: Phong.cpp:146-154 call it with the literal
+    first, so a NaN normal (a zero-length HitInfo::N, normalised) leaves a diffuse term of 0 and a clamped e.r of 1"""
+    with np.errstate(invalid="ignore"):
+        return np.where(a < b, b, a).astype(F)
+
+
+def std_min(a, b):
+    """std::min(a, b) = (b < a) ? b : a"""
+    with np.errstate(invalid="ignore"):
+        return np.where(b < a, b, a).astype(F)
 
 
 def rays_of(po, o, d, tmax):
@@ -120,13 +134,13 @@ def restate_shade(room, rays, hits, light):
     else:
         nDotL = dot3(N, l)                                                              # :139
         f2 = F(1.0) / (falloff * F(4.0) * PI * PI)                                      # :140
-    diff = np.maximum(F(0), nDotL * f2 * watt)
+    diff = std_max(F(0), nDotL * f2 * watt)
     out = color[None, :] * (diff[:, None] * mt[:, 0:3] * mt[:, 0:3]) * intensity[:, None]              # :146
     shiny = mt[:, 9] < np.inf                                                           # :149
     two = 2 * dot3(l, N)
     rv = (-l + two[:, None] * N).astype(F)                                              # :151
-    edr = np.power(np.maximum(F(0), np.minimum(F(1), dot3(e, rv))), F(500)).astype(F)   # :152
-    high = np.where(shiny, np.maximum(F(0), edr * f2 * watt), F(0)).astype(F)           # :154
+    edr = np.power(std_max(F(0), std_min(F(1), dot3(e, rv))), F(500)).astype(F)         # :152
+    high = np.where(shiny, std_max(F(0), edr * f2 * watt), F(0)).astype(F)              # :154
     out = (out + high[:, None]).astype(F)
     out[skip] = 0
     L[idx] = out

@@ -67,9 +67,11 @@ def scene(miro, name, env):
     return s, desc, lights
 
 
-def frames(miro, name, env, children, spp, kinds=7, depth=DEPTH, capacity=None, device=True, window=None):
+def frames(miro, name, env, children, spp, kinds=7, depth=DEPTH, capacity=None, device=True, window=None, own=None):
     """The yardstick frame and the frame under test with the same arguments.  Returns (ref, dev): each with per_level, rgb and
-    counts [levels, 6+]; ref besides with pixels, the pixel column of every queue it ran (levels >= 1)."""
+    counts [levels, 6+]; ref besides with pixels, the pixel column of every queue it ran (levels >= 1).
+    own: (scene, description, lights, environment) of a caller's own scene, the environment as the arguments of
+    Scene.set_environment or None -- `name` and `env` are then not looked at."""
     import torch
     from miro_amd import frame
 
@@ -83,9 +85,15 @@ def frames(miro, name, env, children, spp, kinds=7, depth=DEPTH, capacity=None, 
             self.seen_pixels.append(q.pixels)
             return super()._level_lights(plan, q, level, last, rgb=rgb)
 
-    s, desc, lights = scene(miro, name, env)
+    if own is None:
+        s, desc, lights = scene(miro, name, env)
+        environment = ENVS[env]
+    else:
+        s, desc, lights, environment = own
+        s.set_lights(lights)
+        s.set_environment(**(environment or {}))
     w, h = window or WINDOWS[spp]
-    kw = dict(depth=depth, lights=lights, environment=ENVS[env])
+    kw = dict(depth=depth, lights=lights, environment=environment)
     if children == PATH:
         kw.update(path_tracing=True, path_kinds=kinds, path_seed=SEED)
     route = "lights_path" if children == PATH else "lights"
