@@ -1421,14 +1421,28 @@ mr_status mr_trace_level_lights_path(mr_scene *s, const mr_level_lights_path_des
                                     reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
 }
 
+// what the three calls of include/miro_hip_lens.h ask after the list of their pinhole twin, in this order: the lens as
+// mr_gen_eye_rays_lens checks it, then image order (that generator, which the calls are held to, makes no other)
+static mr_status check_frame_lens(const char *who, const mr_lens_desc *lens, const mr_frame_desc &fd) {
+    if (!lens) return fail(MR_ERR_INVALID, "%s: NULL lens", who);
+    for (int k = 0; k < 6; k++)
+        if (lens->reserved[k] != 0) return fail(MR_ERR_INVALID, "%s: mr_lens_desc.reserved must be 0", who);
+    if (!std::isfinite(lens->aperture) || lens->aperture < 0.0f) return fail(MR_ERR_INVALID, "%s: aperture must be finite and >= 0", who);
+    if (!std::isfinite(lens->focus_plane) || !(lens->focus_plane > 0.0f))
+        return fail(MR_ERR_INVALID, "%s: focus_plane must be finite and > 0", who);
+    if (fd.tiled)
+        return fail(MR_ERR_INVALID, "%s: tiled sample order (the thin-lens rays are mr_gen_eye_rays_lens', in image order); use tiled = 0", who);
+    return MR_OK;
+}
+
 // The level-0 frame that also emits the rays of level 1 (mr_frame_level_lights.hip).  The frame call's argument checks under this
 // call's name, then the level calls' in their order, all before the scene's state is read; then the state and the uploads of
-// mr_render_lights_environment.  MR_LEVEL_LAST is that frame itself.
-mr_status mr_render_level_lights(mr_scene *s, const mr_frame_desc *frame, const mr_frame_level_desc *level, float *d_rgb, mr_hit *d_hits,
-                                 float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, mr_ray *d_out_rays,
-                                 float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, uint64_t *d_out_count,
-                                 uint64_t *d_counts, void *stream) {
-    const char *who = "mr_render_level_lights";
+// mr_render_lights_environment.  MR_LEVEL_LAST is that frame itself.  with_lens: mr_render_level_lights_lens (mr_frame_lens.hip),
+// whose lens checks follow the list and whose MR_LEVEL_LAST is its own kernel
+static mr_status render_level_lights(const char *who, bool with_lens, mr_scene *s, const mr_frame_desc *frame, const mr_lens_desc *lens,
+                                     const mr_frame_level_desc *level, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
+                                     float *d_sample_color, float *d_sample_normal, mr_ray *d_out_rays, float *d_out_weights,
+                                     uint32_t *d_out_pixels, uint32_t *d_out_ids, uint64_t *d_out_count, uint64_t *d_counts, void *stream) {
     mr_frame_desc fd;
     mr_status st = check_render_lights_args(who, s, frame, fd, d_rgb, d_hits, d_sample_rgb,
                                             misaligned(4, d_sample_color, d_sample_normal), d_counts);
@@ -1457,16 +1471,36 @@ mr_status mr_render_level_lights(mr_scene *s, const mr_frame_desc *frame, const 
             return fail(MR_ERR_INVALID, "%s: the output rays must be 16-byte aligned, d_out_count 8-byte, weights, pixels and ids "
                                         "4-byte aligned", who);
     }
+    if (with_lens && (st = check_frame_lens(who, lens, fd)) != MR_OK) return st;
     if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
     LightScene ls;
     if ((st = lights_scene_params(s, level->environment != 0, stream, ls)) != MR_OK) return st;
+    const RayQueue out = {d_out_rays, d_out_weights, d_out_pixels, d_out_ids, level->d_out_lowres};
+    if (with_lens)
+        return launch_frame_lens(who, ls, fd, *lens, *level, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal, out,
+                                 reinterpret_cast<unsigned long long *>(d_out_count), reinterpret_cast<unsigned long long *>(d_counts),
+                                 static_cast<hipStream_t>(stream));
     if (!children)
         return launch_frame_lights_env(ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal,
                                        reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
-    const RayQueue out = {d_out_rays, d_out_weights, d_out_pixels, d_out_ids, level->d_out_lowres};
     return launch_frame_level_lights(ls, fd, *level, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal, out,
                                      reinterpret_cast<unsigned long long *>(d_out_count), reinterpret_cast<unsigned long long *>(d_counts),
                                      static_cast<hipStream_t>(stream));
+}
+mr_status mr_render_level_lights(mr_scene *s, const mr_frame_desc *frame, const mr_frame_level_desc *level, float *d_rgb, mr_hit *d_hits,
+                                 float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, mr_ray *d_out_rays,
+                                 float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids, uint64_t *d_out_count,
+                                 uint64_t *d_counts, void *stream) {
+    return render_level_lights("mr_render_level_lights", false, s, frame, nullptr, level, d_rgb, d_hits, d_sample_rgb, d_sample_color,
+                               d_sample_normal, d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_count, d_counts, stream);
+}
+// ... through the thin lens (include/miro_hip_lens.h; Camera.cpp:135-160, Miro.h:18-19)
+mr_status mr_render_level_lights_lens(mr_scene *s, const mr_frame_desc *frame, const mr_lens_desc *lens, const mr_frame_level_desc *level,
+                                      float *d_rgb, mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color, float *d_sample_normal,
+                                      mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids,
+                                      uint64_t *d_out_count, uint64_t *d_counts, void *stream) {
+    return render_level_lights("mr_render_level_lights_lens", true, s, frame, lens, level, d_rgb, d_hits, d_sample_rgb, d_sample_color,
+                               d_sample_normal, d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_count, d_counts, stream);
 }
 
 // The workspace of mr_render_recursion: two queues of `cap` rays, each a run of arrays whose offsets are rounded up to 16 bytes
@@ -1548,11 +1582,12 @@ mr_status mr_render_recursion_workspace(const mr_recursion_desc *desc, uint64_t 
 // other, whose length is the word the level before counted its children into.  d_hits / d_normal: optional, every level's per-ray
 // records, each level overwriting the one before.  step(l, d_n, bound, in) is enqueued after level l, 0 included -- d_n: the
 // word that holds the level's length (level 0: the samples the frame counted), bound: what the host knows it cannot exceed (fan^l
-// x samples, saturating at the capacity), in: the queue the level read (level 0: none, its rays start at the eye)
+// x samples, saturating at the capacity), in: the queue the level read (level 0: none, its rays start at the eye).  lens
+// (optional): level 0 is the thin-lens frame's launcher (mr_frame_lens.hip), at depth 0 too; the further levels do not differ
 static mr_status no_level_step(uint32_t, const unsigned long long *, unsigned long long, const RayQueue &) { return MR_OK; }
 extern "C++" template <typename STEP>                                                  // (the entry points around it have C linkage)
-static mr_status enqueue_recursion(const LightScene &ls, const mr_frame_desc &fd, const mr_recursion_desc &rd, unsigned long long samples,
-                                   void *d_workspace, float *d_rgb, mr_hit *d_hits, float *d_normal, unsigned long long *counts,
+static mr_status enqueue_recursion(const LightScene &ls, const mr_frame_desc &fd, const mr_lens_desc *lens, const mr_recursion_desc &rd,
+                                   unsigned long long samples, void *d_workspace, float *d_rgb, mr_hit *d_hits, float *d_normal, unsigned long long *counts,
                                    hipStream_t hs, STEP step) {
     mr_status st = launch_zero_words(counts, 8ull * (rd.depth + 1ull), hs);
     if (st != MR_OK) return st;
@@ -1560,16 +1595,20 @@ static mr_status enqueue_recursion(const LightScene &ls, const mr_frame_desc &fd
     const uint64_t cap = rd.queue_capacity_lo;
     const unsigned fan = path ? 4u : 3u;
     RayQueue qs[2] = {};
-    if (rd.depth == 0) {
-        st = launch_frame_lights_env(ls, fd, d_rgb, d_hits, nullptr, nullptr, d_normal, counts, hs);
-    } else {
+    mr_frame_level_desc l0 = {};
+    l0.children = MR_LEVEL_LAST; l0.environment = rd.environment;
+    if (rd.depth > 0) {
         recursion_queues(d_workspace, recursion_queue_layout(rd), qs);
-        mr_frame_level_desc l0 = {};
-        l0.children = rd.children; l0.environment = rd.environment;
+        l0.children = rd.children;
         l0.path_kinds = rd.path_kinds; l0.path_seed = rd.path_seed;
         l0.out_capacity_lo = rd.queue_capacity_lo; l0.out_capacity_hi = 0;
-        st = launch_frame_level_lights(ls, fd, l0, d_rgb, d_hits, nullptr, nullptr, d_normal, qs[0], &counts[5], counts, hs);
     }
+    if (lens)
+        st = launch_frame_lens("mr_render_level_lights_lens", ls, fd, *lens, l0, d_rgb, d_hits, nullptr, nullptr, d_normal, qs[0], &counts[5], counts, hs);
+    else if (rd.depth == 0)
+        st = launch_frame_lights_env(ls, fd, d_rgb, d_hits, nullptr, nullptr, d_normal, counts, hs);
+    else
+        st = launch_frame_level_lights(ls, fd, l0, d_rgb, d_hits, nullptr, nullptr, d_normal, qs[0], &counts[5], counts, hs);
     if (st != MR_OK || (st = step(0u, &counts[0], samples, RayQueue{})) != MR_OK) return st;
 
     QueuedLevel lv = {};
@@ -1594,9 +1633,10 @@ static mr_status enqueue_recursion(const LightScene &ls, const mr_frame_desc &fd
 
 // The whole recursive frame on one stream (include/miro_hip_recursion.h).  The argument checks first, all before the scene's
 // state is read; then the state and the uploads; then nothing but launches (enqueue_recursion).
-mr_status mr_render_recursion(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, float *d_rgb, void *d_workspace,
-                              uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
-    const char *who = "mr_render_recursion";
+// with_lens: mr_render_recursion_lens, whose lens checks follow the list
+static mr_status render_recursion(const char *who, bool with_lens, mr_scene *s, const mr_frame_desc *frame, const mr_lens_desc *lens,
+                                  const mr_recursion_desc *desc, float *d_rgb, void *d_workspace, uint64_t workspace_bytes,
+                                  uint64_t *d_level_counts, void *stream) {
     mr_frame_desc fd;
     unsigned long long samples = 0;
     mr_status st = check_recursion_args(who, s, frame, desc, d_rgb, d_level_counts, fd, samples);
@@ -1610,11 +1650,21 @@ mr_status mr_render_recursion(mr_scene *s, const mr_frame_desc *frame, const mr_
             return fail(MR_ERR_INVALID, "%s: workspace_bytes is %llu, two queues of %llu rays need %llu (mr_render_recursion_workspace)", who,
                         (unsigned long long)workspace_bytes, (unsigned long long)desc->queue_capacity_lo, (unsigned long long)need);
     }
+    if (with_lens && (st = check_frame_lens(who, lens, fd)) != MR_OK) return st;
     if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
     LightScene ls;
     if ((st = lights_scene_params(s, desc->environment != 0, stream, ls)) != MR_OK) return st;
-    return enqueue_recursion(ls, fd, *desc, samples, d_workspace, d_rgb, nullptr, nullptr, reinterpret_cast<unsigned long long *>(d_level_counts),
-                             static_cast<hipStream_t>(stream), no_level_step);
+    return enqueue_recursion(ls, fd, with_lens ? lens : nullptr, *desc, samples, d_workspace, d_rgb, nullptr, nullptr,
+                             reinterpret_cast<unsigned long long *>(d_level_counts), static_cast<hipStream_t>(stream), no_level_step);
+}
+mr_status mr_render_recursion(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, float *d_rgb, void *d_workspace,
+                              uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
+    return render_recursion("mr_render_recursion", false, s, frame, nullptr, desc, d_rgb, d_workspace, workspace_bytes, d_level_counts, stream);
+}
+// ... through the thin lens (include/miro_hip_lens.h; Camera.cpp:135-160, Miro.h:18-19)
+mr_status mr_render_recursion_lens(mr_scene *s, const mr_frame_desc *frame, const mr_lens_desc *lens, const mr_recursion_desc *desc, float *d_rgb,
+                                   void *d_workspace, uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
+    return render_recursion("mr_render_recursion_lens", true, s, frame, lens, desc, d_rgb, d_workspace, workspace_bytes, d_level_counts, stream);
 }
 
 // The workspace of mr_render_recursion_photons behind the two queues: hit records, normals and mr_gather_level's scratch for M
@@ -1661,10 +1711,11 @@ mr_status mr_render_recursion_photons_workspace(const mr_frame_desc *frame, cons
 // the workspace's hit and normal buffers handed to every level launch, and as its step the three kernels of mr_gather_queued.hip
 // on that level's queue.  The argument checks first, all of them before the scene's or a map's state is read; then the state and
 // the uploads; then nothing but launches.
-mr_status mr_render_recursion_photons(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, mr_photon_map *global_map,
-                                      mr_photon_map *caustic_map, float max_dist, uint32_t nphotons, float *d_rgb, void *d_workspace,
-                                      uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
-    const char *who = "mr_render_recursion_photons";
+// with_lens: mr_render_recursion_photons_lens, whose lens checks follow the list and whose level 0 makes the lens ray again
+static mr_status render_recursion_photons(const char *who, bool with_lens, mr_scene *s, const mr_frame_desc *frame, const mr_lens_desc *lens,
+                                          const mr_recursion_desc *desc, mr_photon_map *global_map, mr_photon_map *caustic_map,
+                                          float max_dist, uint32_t nphotons, float *d_rgb, void *d_workspace, uint64_t workspace_bytes,
+                                          uint64_t *d_level_counts, void *stream) {
     mr_frame_desc fd;
     unsigned long long samples = 0;
     mr_status st = check_recursion_args(who, s, frame, desc, d_rgb, d_level_counts, fd, samples);
@@ -1679,6 +1730,7 @@ mr_status mr_render_recursion_photons(mr_scene *s, const mr_frame_desc *frame, c
     if (workspace_bytes < ws.bytes)
         return fail(MR_ERR_INVALID, "%s: workspace_bytes is %llu, this frame and descriptor need %llu (mr_render_recursion_photons_workspace)",
                     who, (unsigned long long)workspace_bytes, (unsigned long long)ws.bytes);
+    if (with_lens && (st = check_frame_lens(who, lens, fd)) != MR_OK) return st;
 
     if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
     for (mr_photon_map *m : maps) {
@@ -1706,14 +1758,28 @@ mr_status mr_render_recursion_photons(mr_scene *s, const mr_frame_desc *frame, c
     auto photon_term = [&](uint32_t l, const unsigned long long *d_n, unsigned long long bound, const RayQueue &in) -> mr_status {
         const GatherScratch sc = gather_scratch(d_scratch, bound, maps[0] != nullptr, maps[1] != nullptr);
         unsigned long long *d_queries = counts + 8ull * l + 6;
-        mr_status e = l == 0 ? launch_gather_eye_queries(s->dev, who, fd, d_hits, d_normal, sc.pos, sc.nrm, d_queries, hs)
+        mr_status e = l == 0 ? (with_lens ? launch_gather_eye_queries_lens(s->dev, who, fd, *lens, d_hits, d_normal, sc.pos, sc.nrm, d_queries, hs)
+                                          : launch_gather_eye_queries(s->dev, who, fd, d_hits, d_normal, sc.pos, sc.nrm, d_queries, hs))
                              : launch_gather_queued_queries(s->dev, in.rays, d_hits, d_normal, d_n, bound, sc.pos, sc.nrm, d_queries, hs);
         for (int i = 0; i < 2 && e == MR_OK; i++)
             if (maps[i]) e = photon_map_estimate_queued(maps[i], sc.pos, sc.nrm, d_n, bound, max_dist, nphotons, sc.irr[i], hs);
         if (e != MR_OK) return e;
         return launch_gather_queued_accumulate(sc.irr[0], sc.irr[1], in.weights, in.pixels, d_n, bound, fd.spp, d_rgb, hs);
     };
-    return enqueue_recursion(ls, fd, *desc, samples, d_workspace, d_rgb, d_hits, d_normal, counts, hs, photon_term);
+    return enqueue_recursion(ls, fd, with_lens ? lens : nullptr, *desc, samples, d_workspace, d_rgb, d_hits, d_normal, counts, hs, photon_term);
+}
+mr_status mr_render_recursion_photons(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, mr_photon_map *global_map,
+                                      mr_photon_map *caustic_map, float max_dist, uint32_t nphotons, float *d_rgb, void *d_workspace,
+                                      uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
+    return render_recursion_photons("mr_render_recursion_photons", false, s, frame, nullptr, desc, global_map, caustic_map, max_dist, nphotons,
+                                    d_rgb, d_workspace, workspace_bytes, d_level_counts, stream);
+}
+// ... through the thin lens (include/miro_hip_lens.h; Camera.cpp:135-160, Miro.h:18-19)
+mr_status mr_render_recursion_photons_lens(mr_scene *s, const mr_frame_desc *frame, const mr_lens_desc *lens, const mr_recursion_desc *desc,
+                                           mr_photon_map *global_map, mr_photon_map *caustic_map, float max_dist, uint32_t nphotons,
+                                           float *d_rgb, void *d_workspace, uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
+    return render_recursion_photons("mr_render_recursion_photons_lens", true, s, frame, lens, desc, global_map, caustic_map, max_dist, nphotons,
+                                    d_rgb, d_workspace, workspace_bytes, d_level_counts, stream);
 }
 
 mr_status mr_gen_eye_rays_lens(mr_scene *s, const mr_camera *cam, uint32_t W, uint32_t H, uint32_t y0, uint32_t y1, uint32_t spp,

@@ -36,12 +36,9 @@ using namespace rec;
 // ---------------------------------------------------------------------------------------------------------------------------
 // the thin lens
 // ---------------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kLensRounds = 32;                  // rounds of sampleDisc's rejection loop before the sample is (0, 0)
-constexpr uint32_t kLensDomain = 0x4c454e53u;         // "LENS": the lens draws' keys, see mr_gen_eye_rays_lens (miro_hip.h)
-
+// The per-sample arithmetic is mr_eye.h's (eye_lens_draw, eye_lens_ray), which the fused lens frame (mr_frame_lens.hip) calls too.
 struct LensArgs {
-    float focus[3];                  // m_eye + m_viewDir * DOF_FOCUS_PLANE (Camera.cpp:142), computed on the host
-    float aperture;
+    LensParams p;                    // the focus point and the aperture
     const float *in;                 // optional: dx, dy, lx, ly per ray
     float *out;                      // optional: the values used
     unsigned long long *counts;      // optional: [0] += rays written, [1] += samples that exhausted kLensRounds
@@ -57,26 +54,13 @@ __global__ __launch_bounds__(kBlock) void eye_rays_lens_kernel(EyeFrame f, LensA
         if (ln.in) {
             const float4 s = reinterpret_cast<const float4 *>(ln.in)[k];
             dx = s.x; dy = s.y; lx = s.z; ly = s.w;
-        } else {
-            const uint32_t h = eye_sample_key(f, x, y, sm);
-            if (f.jitter) eye_jitter_of(h, dx, dy);
-            bool found = false;
-            for (uint32_t r = 0; r < kLensRounds && !found; r++) {                      // sampleDisc (Utility.h:86-89)
-                const float fx = unit01(pcg32(h ^ (kLensDomain + 2u * r))), fy = unit01(pcg32(h ^ (kLensDomain + 2u * r + 1u)));
-                const float xr = (2 * fx - 1) * ln.aperture, yr = (2 * fy - 1) * ln.aperture;
-                if (!(xr * xr + yr * yr > ln.aperture * ln.aperture)) { lx = xr; ly = yr; found = true; }
-            }
-            if (!found) mine[1]++;
+        } else if (!eye_lens_draw(f, ln.p.aperture, x, y, sm, dx, dy, lx, ly)) {
+            mine[1]++;
         }
-        float up, vp, e[3], lw[3];
-        eye_film_of(f, x, y, dx, dy, up, vp);
-        for (int c = 0; c < 3; c++) {
-            e[c] = f.eye[c] + (lx * f.u[c] + ly * f.v[c]);                                 // Camera.cpp:140
-            lw[c] = -(ln.focus[c] - e[c]);                                                 // :142, :145
-        }
-        normalize3(lw);
-        reinterpret_cast<float4 *>(rays)[2 * k] = make_float4(e[0], e[1], e[2], 0.0f);
-        reinterpret_cast<float4 *>(rays)[2 * k + 1] = eye_direction_of(f, up, vp, lw);     // :160, uDir / vDir of the unmoved eye
+        float4 ra, rb;
+        eye_lens_ray(f, ln.p, x, y, dx, dy, lx, ly, ra, rb);
+        reinterpret_cast<float4 *>(rays)[2 * k] = ra;
+        reinterpret_cast<float4 *>(rays)[2 * k + 1] = rb;
         if (ln.out) reinterpret_cast<float4 *>(ln.out)[k] = make_float4(dx, dy, lx, ly);
         mine[0]++;
     }
@@ -103,8 +87,8 @@ mr_status launch_eye_rays_lens(const mr_camera &cam, uint32_t W, uint32_t H, uin
     const EyeFrame f = make_eye_frame(cam, W, H, y0, y1, spp, jitter, seed, false, view);
     if (f.n == 0) return MR_OK;
     LensArgs ln;
-    for (int c = 0; c < 3; c++) ln.focus[c] = cam.eye[c] + view[c] * lens.focus_plane;    // Camera.cpp:142's first two terms
-    ln.aperture = lens.aperture; ln.in = d_samples_in; ln.out = d_samples_out; ln.counts = d_counts;
+    ln.p = lens_params_of(cam, view, lens);
+    ln.in = d_samples_in; ln.out = d_samples_out; ln.counts = d_counts;
     hipLaunchKernelGGL(eye_rays_lens_kernel, dim3(grid_for(f.n)), dim3(kBlock), 0, stream, f, ln, d_rays);
     MR_HIP_CHECK(hipGetLastError());
     return MR_OK;

@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "mr_internal.h"
+#include "mr_surface.h"
 #include "mr_tile.h"
 
 namespace mr {
@@ -106,6 +107,61 @@ __device__ __forceinline__ void eye_ray_of(const EyeFrame &f, uint32_t x, uint32
     eye_film_of(f, x, y, dx, dy, up, vp);
     a = make_float4(f.eye[0], f.eye[1], f.eye[2], 0.0f);
     b = eye_direction_of(f, up, vp, f.w);
+}
+#endif
+
+// ---- the thin lens: Camera::eyeRay under -DDOF (Camera.cpp:135-160, Miro.h:18-19, sampleDisc Utility.h:82-95).  The batched
+// generator (eye_rays_lens_kernel, mr_distribution.hip) and the fused lens frame (mr_frame_lens.hip) share the definitions
+// below, so their rays are the same bits.
+constexpr uint32_t kLensRounds = 32;                  // rounds of sampleDisc's rejection loop before the sample is (0, 0)
+constexpr uint32_t kLensDomain = 0x4c454e53u;         // "LENS": the lens draws' keys, see mr_gen_eye_rays_lens (miro_hip.h)
+
+struct LensParams {
+    float focus[3];              // m_eye + m_viewDir * DOF_FOCUS_PLANE (Camera.cpp:142), computed on the host
+    float aperture;
+};
+// what launch_eye_rays_lens and the lens frames put into the block; view: make_eye_frame's view_dir
+inline LensParams lens_params_of(const mr_camera &cam, const float view[3], const mr_lens_desc &lens) {
+    LensParams ln;
+    for (int c = 0; c < 3; c++) ln.focus[c] = cam.eye[c] + view[c] * lens.focus_plane;    // Camera.cpp:142's first two terms
+    ln.aperture = lens.aperture;
+    return ln;
+}
+
+#if defined(__HIPCC__)
+// the random numbers of sample `sm` of pixel (x, y): its offset inside the pixel (with f.jitter) and sampleDisc's point on the
+// lens (Utility.h:86-89).  false: the rejection loop exhausted kLensRounds, and the point is the lens centre
+__device__ __forceinline__ bool eye_lens_draw(const EyeFrame &f, float aperture, uint32_t x, uint32_t y, uint32_t sm, float &dx, float &dy,
+                                              float &lx, float &ly) {
+    const uint32_t h = eye_sample_key(f, x, y, sm);
+    if (f.jitter) eye_jitter_of(h, dx, dy);
+    bool found = false;
+    for (uint32_t r = 0; r < kLensRounds && !found; r++) {
+        const float fx = unit01(pcg32(h ^ (kLensDomain + 2u * r))), fy = unit01(pcg32(h ^ (kLensDomain + 2u * r + 1u)));
+        const float xr = (2 * fx - 1) * aperture, yr = (2 * fy - 1) * aperture;
+        if (!(xr * xr + yr * yr > aperture * aperture)) { lx = xr; ly = yr; found = true; }
+    }
+    return found;
+}
+// the ray of pixel (x, y) at offset (dx, dy) through the lens point (lx, ly)
+__device__ __forceinline__ void eye_lens_ray(const EyeFrame &f, const LensParams &ln, uint32_t x, uint32_t y, float dx, float dy, float lx,
+                                             float ly, float4 &a, float4 &b) {
+    float up, vp, e[3], lw[3];
+    eye_film_of(f, x, y, dx, dy, up, vp);
+    for (int c = 0; c < 3; c++) {
+        e[c] = f.eye[c] + (lx * f.u[c] + ly * f.v[c]);                                 // Camera.cpp:140
+        lw[c] = -(ln.focus[c] - e[c]);                                                 // :142, :145
+    }
+    normalize3(lw);
+    a = make_float4(e[0], e[1], e[2], 0.0f);
+    b = eye_direction_of(f, up, vp, lw);                                               // :160, uDir / vDir of the unmoved eye
+}
+// Camera::eyeRay under -DDOF for sample `sm` of pixel (x, y): a = (the point on the lens, tMin = 0), b = (direction, tMax)
+__device__ __forceinline__ void eye_ray_lens_of(const EyeFrame &f, const LensParams &ln, uint32_t x, uint32_t y, uint32_t sm, float4 &a,
+                                                float4 &b) {
+    float dx = 0.5f, dy = 0.5f, lx = 0.0f, ly = 0.0f;
+    eye_lens_draw(f, ln.aperture, x, y, sm, dx, dy, lx, ly);
+    eye_lens_ray(f, ln, x, y, dx, dy, lx, ly, a, b);
 }
 #endif
 

@@ -90,9 +90,12 @@ struct FrameChildArgs {
 
 // VAR, ANY: as in frame_lights_kernel.  s_stack: the workgroup's dynamic LDS, [stack_depth][kTraceBlock]; s_tab: 128 words of
 // static LDS for the two noise tables.
-template <int VAR, bool ANY, bool ENV, int CHILDREN>
-__device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfaceArgs a, const EnvParams env, const FrameChildArgs &ch, int *s_stack,
-                                                          uint32_t (&s_tab)[128]) {
+// LENS: the eye ray is Camera::eyeRay under -DDOF (eye_ray_lens_of, mr_eye.h; ln: the focus point and the aperture) -- the
+// three places that make the eye ray make the lens ray, and the hit point of a sphere or a plane starts from the sample's own
+// point on the lens, which is made again there, not held across the traversal.  With LENS false nothing of `ln` is read.
+template <int VAR, bool ANY, bool ENV, int CHILDREN, bool LENS>
+__device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfaceArgs a, const EnvParams env, const FrameChildArgs &ch, const LensParams &ln,
+                                                          int *s_stack, uint32_t (&s_tab)[128]) {
     const NoiseTables nt = stage_noise_tables(s_tab);
     const int tid = threadIdx.x;
     const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
@@ -111,7 +114,8 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
         float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = make_float4(1.f, 1.f, 1.f, -1.f);
         if (live) {
             eye_sample_of(a.eye, idx, x, row, y, sm);
-            eye_ray_of(a.eye, x, y, sm, ra, rb);
+            if constexpr (LENS) eye_ray_lens_of(a.eye, ln, x, y, sm, ra, rb);
+            else eye_ray_of(a.eye, x, y, sm, ra, rb);
         }
         // ---- primary ray: a closest hit; a lane past the end of the window gets the miss record
         const mr_hit h = trace_hit<true, false, false, VAR>(a.tp, ra, rb, rb.w, live, s_stack, tid, st);
@@ -123,7 +127,14 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
         const float *mt = a.m.mats;
         if (hit) {
             // the ray's origin is the eye (a hit lane is a live one): read from the arguments, uniform, where it is used
-            surface_od<true>(a.m.s, a.eye.eye[0], a.eye.eye[1], a.eye.eye[2], rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
+            // (LENS: the sample's point on the lens and its direction, made again)
+            if constexpr (LENS) {
+                eye_sample_of(a.eye, idx, x, row, y, sm);
+                eye_ray_lens_of(a.eye, ln, x, y, sm, ra, rb);
+                surface_od<true>(a.m.s, ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
+            } else {
+                surface_od<true>(a.m.s, a.eye.eye[0], a.eye.eye[1], a.eye.eye[2], rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
+            }
             bool ok = true;
             if (table) {
                 hit_color_normal(a.m, a.t, nt, h.prim, P, N, col, ok);
@@ -143,7 +154,8 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
         float d[3] = {0.f, 0.f, 0.f};
         if (ENV ? live : hit) {
             eye_sample_of(a.eye, idx, x, row, y, sm);
-            eye_ray_of(a.eye, x, y, sm, ra, rb);
+            if constexpr (LENS) eye_ray_lens_of(a.eye, ln, x, y, sm, ra, rb);
+            else eye_ray_of(a.eye, x, y, sm, ra, rb);
             d[0] = rb.x; d[1] = rb.y; d[2] = rb.z;
         }
 
@@ -228,6 +240,14 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
         }
         if (blockIdx.x == 0 && tid == 0) atomicAdd(&a.counts[0], n);
     }
+}
+
+// the frames of the pinhole camera
+template <int VAR, bool ANY, bool ENV, int CHILDREN>
+__device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfaceArgs a, const EnvParams env, const FrameChildArgs &ch, int *s_stack,
+                                                          uint32_t (&s_tab)[128]) {
+    const LensParams none = {};
+    frame_lights_surface_body<VAR, ANY, ENV, CHILDREN, false>(a, env, ch, none, s_stack, s_tab);
 }
 
 // the two frames that stop at level 0

@@ -343,6 +343,12 @@ mr_status frame_level_lights_samples(const char *who, const mr_frame_desc &fd, u
 mr_status launch_frame_level_lights(const LightScene &ls, const mr_frame_desc &fd, const mr_frame_level_desc &ld, float *d_rgb, mr_hit *d_hits,
                                     float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, const RayQueue &out,
                                     unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
+// ... for the thin-lens camera (mr_frame_lens.hip, mr_render_level_lights_lens): the eye ray of a sample is the one
+// launch_eye_rays_lens makes for it without caller-supplied samples.  ld.children == MR_LEVEL_LAST launches the frame without
+// children and touches neither `out` nor d_out_count.  `who`: the entry point the window's messages name
+mr_status launch_frame_lens(const char *who, const LightScene &ls, const mr_frame_desc &fd, const mr_lens_desc &lens, const mr_frame_level_desc &ld,
+                            float *d_rgb, mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, const RayQueue &out,
+                            unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
 // One level of mr_render_recursion, whose queue's length is a device word (mr_level_lights_queued.hip).  What the level is:
 // path: the PATH_TRACING build's kernel (children of bounce `bounce` from path_kinds / seed, ids, low-res bytes), else the
 // specular one; last: no children; capacity: the rays the output queue holds
@@ -506,6 +512,10 @@ constexpr int kPhotonStats = 12;  // see mr_photon_map_get_stats (miro_hip.h)
 // d_normal, the normal) the frame wrote.
 mr_status launch_gather_eye_queries(const DeviceScene &ds, const char *who, const mr_frame_desc &fd, const mr_hit *d_hits,
                                     const float *d_normal, float *d_pos, float *d_nrm, unsigned long long *d_queries, hipStream_t stream);
+// ... of the lens frame (mr_frame_lens.hip): the lens ray of sample k made again
+mr_status launch_gather_eye_queries_lens(const DeviceScene &ds, const char *who, const mr_frame_desc &fd, const mr_lens_desc &lens,
+                                         const mr_hit *d_hits, const float *d_normal, float *d_pos, float *d_nrm,
+                                         unsigned long long *d_queries, hipStream_t stream);
 mr_status launch_gather_queued_queries(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_normal,
                                        const unsigned long long *d_n, unsigned long long bound, float *d_pos, float *d_nrm,
                                        unsigned long long *d_queries, hipStream_t stream);

@@ -77,6 +77,9 @@ RENDER_SYMBOLS = ["mr_render_level_lights"]
 RECURSION_SYMBOLS = ["mr_render_recursion_workspace", "mr_render_recursion"]
 # ... and the two of miro_hip_recursion_photons.h, which that header includes as its last line
 RECURSION_PHOTONS_SYMBOLS = ["mr_render_recursion_photons_workspace", "mr_render_recursion_photons"]
+# ... and the three of miro_hip_lens.h (the fused frame and the one-call recursions through the thin lens), which that header
+# includes as its last line in turn
+LENS_SYMBOLS = ["mr_render_level_lights_lens", "mr_render_recursion_lens", "mr_render_recursion_photons_lens"]
 
 
 class MiroError(RuntimeError):
@@ -382,10 +385,16 @@ def load_library(path=None):
     L.mr_irradiance_estimate.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, vp, vp, vp, vp]
     L.mr_photon_map_count_stats.argtypes = [vp, C.c_int32]
     L.mr_photon_map_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int32]
-    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS:
+    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS + LENS_SYMBOLS:
         if not hasattr(L, name):
             raise OSError("%s does not export %s" % (path, name))
-    for name in EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS:
+    lens = [C.POINTER(LensDesc)]                                   # `lens` follows `frame` (miro_hip_lens.h)
+    L.mr_render_level_lights_lens.argtypes = L.mr_render_level_lights.argtypes[:2] + lens + L.mr_render_level_lights.argtypes[2:]
+    L.mr_render_recursion_lens.argtypes = L.mr_render_recursion.argtypes[:2] + lens + L.mr_render_recursion.argtypes[2:]
+    L.mr_render_recursion_photons_lens.argtypes = (L.mr_render_recursion_photons.argtypes[:2] + lens +
+                                                   L.mr_render_recursion_photons.argtypes[2:])
+    for name in (EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS +
+                 LENS_SYMBOLS):
         if hasattr(L, name) and getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = C.c_int32
     _lib = L
@@ -918,6 +927,64 @@ class Scene:
                                                   caustic_map.h if caustic_map is not None else None, max_dist, nphotons,
                                                   d_rgb.data_ptr(), _ptr(d_workspace), workspace_bytes, d_level_counts.data_ptr(),
                                                   _stream_ptr(stream)))
+
+    def render_level_lights_lens(self, cam, W, H, d_rgb, aperture, focus_plane, y0=0, y1=None, bands=None, spp=1, jitter=False, seed=168,
+                                 tiled=False, flags=0, d_hits=None, d_sample_rgb=None, d_sample_color=None, d_sample_normal=None,
+                                 d_counts=None, stream=None, children=MR_LEVEL_LAST, environment=False,
+                                 kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE, path_seed=168, d_out_rays=None, d_out_weights=None,
+                                 d_out_pixels=None, d_out_ids=None, d_out_count=None, out_capacity=None, d_out_octants=None,
+                                 d_out_lowres=None):
+        """mr_render_level_lights_lens: render_level_lights through the thin lens (Camera::eyeRay under -DDOF, Camera.cpp:135-160;
+        aperture, focus_plane: DOF_APERTURE / DOF_FOCUS_PLANE, Miro.h:18-19).  The eye ray of sample k is the one gen_eye_rays_lens
+        makes for it for the same window, seed, spp and lens without d_samples_in; every output and counter is what the batched
+        calls write for those rays, the children the set trace_level_lights[_path] emits on that queue.  MR_LEVEL_LAST runs this
+        call's own kernels.  tiled must be False; every other argument is render_level_lights'."""
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
+        lens = LensDesc()
+        lens.aperture, lens.focus_plane = aperture, focus_plane
+        ld = FrameLevelDesc()
+        ld.children, ld.environment, ld.path_kinds, ld.path_seed = children, 1 if environment else 0, kinds, path_seed
+        ld.out_capacity_lo, ld.out_capacity_hi = _out_capacity(out_capacity, d_out_rays, d_out_weights, d_out_pixels, d_out_ids,
+                                                               d_out_lowres, d_out_octants)
+        ld.d_out_octants, ld.d_out_lowres = _ptr(d_out_octants), _ptr(d_out_lowres)
+        _check(self.L.mr_render_level_lights_lens(self.h, C.byref(fd), C.byref(lens), C.byref(ld), d_rgb.data_ptr(), _ptr(d_hits),
+                                                  _ptr(d_sample_rgb), _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_out_rays),
+                                                  _ptr(d_out_weights), _ptr(d_out_pixels), _ptr(d_out_ids), _ptr(d_out_count),
+                                                  _ptr(d_counts), _stream_ptr(stream)))
+
+    def render_recursion_lens(self, cam, W, H, d_rgb, d_level_counts, depth, aperture, focus_plane, d_workspace=None, queue_capacity=0,
+                              y0=0, y1=None, bands=None, spp=1, jitter=False, seed=168, tiled=False, flags=0, stream=None,
+                              children=MR_LEVEL_SPECULAR, environment=False, kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE,
+                              path_seed=168, workspace_bytes=None):
+        """mr_render_recursion_lens: render_recursion whose level 0 is render_level_lights_lens (depth 0: with MR_LEVEL_LAST); the
+        further levels, the counters and the workspace (recursion_workspace_bytes) are render_recursion's.  tiled must be False."""
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
+        lens = LensDesc()
+        lens.aperture, lens.focus_plane = aperture, focus_plane
+        rd = _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity)
+        if workspace_bytes is None:
+            workspace_bytes = 0 if d_workspace is None else d_workspace.numel() * d_workspace.element_size()
+        _check(self.L.mr_render_recursion_lens(self.h, C.byref(fd), C.byref(lens), C.byref(rd), d_rgb.data_ptr(), _ptr(d_workspace),
+                                               workspace_bytes, d_level_counts.data_ptr(), _stream_ptr(stream)))
+
+    def render_recursion_photons_lens(self, cam, W, H, d_rgb, d_level_counts, depth, global_map, caustic_map, d_workspace, aperture,
+                                      focus_plane, queue_capacity=0, max_dist=1e10, nphotons=500, y0=0, y1=None, bands=None, spp=1,
+                                      jitter=False, seed=168, tiled=False, flags=0, stream=None, children=MR_LEVEL_SPECULAR,
+                                      environment=False, kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE, path_seed=168,
+                                      workspace_bytes=None):
+        """mr_render_recursion_photons_lens: render_recursion_photons whose level 0 is render_level_lights_lens and whose level-0
+        queries are formed from the lens ray of each sample; the workspace is recursion_photons_workspace_bytes'."""
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
+        lens = LensDesc()
+        lens.aperture, lens.focus_plane = aperture, focus_plane
+        rd = _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity)
+        if workspace_bytes is None:
+            workspace_bytes = 0 if d_workspace is None else d_workspace.numel() * d_workspace.element_size()
+        _check(self.L.mr_render_recursion_photons_lens(self.h, C.byref(fd), C.byref(lens), C.byref(rd),
+                                                       global_map.h if global_map is not None else None,
+                                                       caustic_map.h if caustic_map is not None else None, max_dist, nphotons,
+                                                       d_rgb.data_ptr(), _ptr(d_workspace), workspace_bytes, d_level_counts.data_ptr(),
+                                                       _stream_ptr(stream)))
 
     def final_gather(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb, max_dist=1e10, nphotons=500,
                      spp=1, stream=None):

@@ -233,9 +233,15 @@ class Queue(collections.namedtuple("Queue", "rays weights pixels ids octs n low"
 NO_QUEUE = Queue(None, None, None, None, None, 0)
 
 
+# render_specular's routes through the thin lens, and the pinhole route each of them is in every other respect
+LENS_ROUTES = {"frame_lens": "frame_lights", "frame_lens_path": "frame_lights_path", "device_lens": "device_lights",
+               "device_lens_path": "device_lights_path", "device_lens_photons": "device_photons",
+               "device_lens_photons_path": "device_photons_path"}
+
+
 class LevelPlan(collections.namedtuple("LevelPlan", (
         "stream", "flags", "fused", "path_tracing", "path_kinds", "fan", "path_seed", "group_octants", "lights", "environment",
-        "env_lowres", "surface", "square", "square_lights", "surface_children", "photon_maps", "nphotons", "max_dist"))):
+        "env_lowres", "surface", "square", "square_lights", "surface_children", "photon_maps", "nphotons", "max_dist", "lens"))):
     """What FrameRenderer.render_specular decides once per call, from its arguments and the scene's state (_resolve):
     stream: the torch Stream of every launch, None for the current one; flags: the renderer's trace flags;
     fused: False / True / "auto", already False on a scene with a texture table, or "lights" (every level is one
@@ -269,7 +275,8 @@ class FrameRenderer:
     def __init__(self, scene, desc, W, H, spp=1, bands=None, jitter=None, seed=168, flags=0, device=None, rgb=None,
                  tiled=None, lens=None, square_lights=None, square_samples=1, resident_rays=True):
         """lens: dict(aperture, focus_plane) -- generate() then makes the eye rays of the thin-lens camera
-        (mr_gen_eye_rays_lens, Camera::eyeRay under -DDOF) in image order; not with tiled=True.
+        (mr_gen_eye_rays_lens, Camera::eyeRay under -DDOF) in image order; not with tiled=True.  render_specular's fused="frame_lens*" |
+        "device_lens*" routes make the same rays inside the fused frame and need it.
         square_lights: a list of SquareLights (binding.SquareLightDesc objects or dicts) that every level of render_specular's
         batched path shades IN ADDITION to its point light / light list, with square_samples shadow rays per hit and light
         (mr_shade_square_lights; level l draws its pairs with seed + l; on a scene with a texture table, procedural or not,
@@ -520,7 +527,18 @@ class FrameRenderer:
         max_dist and queue_capacity as above; the workspace also holds a level's hit records, normals and the scratch of the
         estimates.  ValueError without photon_maps, with tiled=True ("lights" / "lights_path", or tiled=False), and with what
         "device_lights" refuses.  The same rays, children, queries and counts per level as "frame_lights[_path]" with the same
-        maps; pixel sums differ by the order of the float atomics.  Opt-in as well."""
+        maps; pixel sums differ by the order of the float atomics.  Opt-in as well.
+        fused="frame_lens" | "frame_lens_path": "frame_lights" / "frame_lights_path" of a FrameRenderer(lens=dict(aperture=...,
+        focus_plane=...)): level 0 is ONE mr_render_level_lights_lens, the fused frame whose eye rays go through the thin lens
+        (Camera::eyeRay under -DDOF, the rays generate() makes for the same lens, made in registers), the further levels are
+        mr_trace_level_lights / _path as there.  With photon_maps generate() runs for mr_gather_level's level 0: it already makes
+        lens rays.  Every check of the pinhole twin, and ValueError besides without a lens (naming the pinhole route) and with
+        tiled=True.  The same rays, children and counts per level as the batched lens frame (fused="lights" / "lights_path").
+        fused="device_lens" | "device_lens_path": that frame as ONE mr_render_recursion_lens and one read of its counters, as
+        "device_lights" / "device_lights_path"; the same checks, queue_capacity, workspace and truncation rule.
+        fused="device_lens_photons" | "device_lens_photons_path": ONE mr_render_recursion_photons_lens with photon_maps, as
+        "device_photons" / "device_photons_path".  All six are opt-in: fused="auto" never chooses them, and the pinhole routes go
+        on refusing a lens."""
         plan = self._resolve(stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights, environment, photon_maps,
                              nphotons, max_dist, surface_children)
         # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
@@ -551,34 +569,44 @@ class FrameRenderer:
         """render_specular's arguments and the scene's state as a LevelPlan: every check, and the two scene setters
         (set_environment, set_lights) between them"""
         sc = self.scene
+        lens_route = fused if isinstance(fused, str) and fused in LENS_ROUTES else None
+        if lens_route:
+            # the pinhole twin's route with the lens calls at level 0: its checks hold, under this route's name
+            if self.lens is None:
+                raise ValueError("render_specular: fused=\"%s\" needs FrameRenderer(lens=dict(aperture=..., focus_plane=...)); "
+                                 "the pinhole frame is fused=\"%s\"" % (lens_route, LENS_ROUTES[lens_route]))
+            if self.tiled:
+                raise ValueError("render_specular: fused=\"%s\" needs tiled=False (lens eye rays come in image order only)" % lens_route)
+            fused = LENS_ROUTES[lens_route]
         frame_route = fused if isinstance(fused, str) and fused in ("frame_lights", "frame_lights_path", "device_lights",
                                                                     "device_lights_path", "device_photons",
                                                                     "device_photons_path") else None
         if frame_route:
             # level 0 is mr_render_level_lights: one window of pinhole eye rays, whose children carry image-order pixels
             level_route = "lights_path" if frame_route.endswith("_path") else "lights"
+            shown = lens_route or frame_route
             if frame_route.startswith("device_photons"):
                 if photon_maps is None:
                     raise ValueError("render_specular: fused=\"%s\" needs photon_maps=(global, caustic); without maps the frame is "
-                                     "fused=\"device_%s\"" % (frame_route, level_route))
+                                     "fused=\"device_%s\"" % (shown, "lens" + level_route[6:] if lens_route else level_route))
                 if self.tiled:
                     raise ValueError("render_specular: photon_maps with tiled=True need fused=\"%s\" (or tiled=False), not "
                                      "fused=\"%s\" (mr_render_recursion_photons finds level 0's pixels from the sample index, in "
-                                     "image order)" % (level_route, frame_route))
+                                     "image order)" % (level_route, shown))
             if frame_route.startswith("device_lights") and photon_maps is not None:
                 raise ValueError("render_specular: photon_maps need fused=\"frame_%s\", not fused=\"%s\" (mr_gather_level takes the "
-                                 "length of its queue from the host)" % (level_route, frame_route))
-            if self.lens is not None:
+                                 "length of its queue from the host)" % ("lens" + level_route[6:] if lens_route else level_route, shown))
+            if self.lens is not None and not lens_route:
                 raise ValueError("render_specular: lens eye rays need the batched path (fused=False), not fused=\"%s\" "
                                  "(mr_render_level_lights makes pinhole eye rays)" % frame_route)
             if len(self.bands) > 1:
                 raise ValueError("render_specular: more than one band range needs fused=\"%s\", not fused=\"%s\" "
-                                 "(mr_render_level_lights renders one window per call)" % (level_route, frame_route))
+                                 "(mr_render_level_lights renders one window per call)" % (level_route, shown))
             if photon_maps is not None and self.tiled:
                 raise ValueError("render_specular: photon_maps with tiled=True need fused=\"%s\" (or tiled=False), not fused=\"%s\" "
-                                 "(mr_gather_level finds level 0's pixels from the ray index, in image order)" % (level_route, frame_route))
+                                 "(mr_gather_level finds level 0's pixels from the ray index, in image order)" % (level_route, shown))
             if photon_maps is not None and frame_route.startswith("frame_"):
-                self._need_rays("render_specular(fused=\"%s\", photon_maps=...)" % frame_route)
+                self._need_rays("render_specular(fused=\"%s\", photon_maps=...)" % shown)
             fused = level_route                 # the checks of that route hold here too; the plan carries the frame route
         level_route = fused if isinstance(fused, str) and fused in ("lights", "lights_path") else None
         if level_route:
@@ -646,7 +674,7 @@ class FrameRenderer:
                          fan=4 if path_tracing else 3, path_seed=path_seed, group_octants=group_octants, lights=lights is not None,
                          environment=environment, env_lowres=env_lowres, surface=surface, square=square,
                          square_lights=self.square_lights, surface_children=surface_children, photon_maps=photon_maps,
-                         nphotons=nphotons, max_dist=max_dist)
+                         nphotons=nphotons, max_dist=max_dist, lens=self.lens if lens_route else None)
 
     def _children(self, plan, n):
         """The buffers for the children of a level of n rays, at most plan.fan each: ids under path tracing only, octant bytes
@@ -756,13 +784,16 @@ class FrameRenderer:
         common = dict(queue_capacity=cap, y0=y0, y1=y1, spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled,
                       flags=plan.level_flags(0)[2], stream=plan.stream, children=children, environment=plan.environment,
                       kinds=plan.path_kinds, path_seed=plan.path_seed, workspace_bytes=need)
+        if plan.lens is not None:                       # the same call through the thin lens
+            common.update(aperture=plan.lens["aperture"], focus_plane=plan.lens["focus_plane"])
+        recursion_photons = self.scene.render_recursion_photons_lens if plan.lens is not None else self.scene.render_recursion_photons
+        recursion = self.scene.render_recursion_lens if plan.lens is not None else self.scene.render_recursion
         if photons:
-            self.scene.render_recursion_photons(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth, plan.photon_maps[0],
-                                                plan.photon_maps[1], self.d_recursion, max_dist=plan.max_dist, nphotons=plan.nphotons,
-                                                **common)
+            recursion_photons(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth, plan.photon_maps[0], plan.photon_maps[1],
+                              self.d_recursion, max_dist=plan.max_dist, nphotons=plan.nphotons, **common)
         else:
-            self.scene.render_recursion(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth,
-                                        d_workspace=self.d_recursion if depth > 0 else None, **common)
+            recursion(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth, d_workspace=self.d_recursion if depth > 0 else None,
+                      **common)
         host = self.d_level_counts[:depth + 1].tolist()             # the one read-back of the frame
         per_level = []
         for level, row in enumerate(host):
@@ -782,12 +813,15 @@ class FrameRenderer:
         hits, normal, cnts, out = self._level_buffers(plan, self.n, 0, last)
         (y0, y1), = self.bands
         children = binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_PATH if plan.path_tracing else binding.MR_LEVEL_SPECULAR
-        self.scene.render_level_lights(self.cam, self.W, self.H, self.d_rgb, y0=y0, y1=y1, spp=self.spp, jitter=self.jitter,
-                                       seed=self.seed, tiled=self.tiled, flags=plan.level_flags(0)[2], d_hits=hits,
-                                       d_sample_normal=normal, d_counts=cnts[:5], stream=plan.stream, children=children,
-                                       environment=plan.environment, kinds=plan.path_kinds, path_seed=plan.path_seed,
-                                       d_out_rays=out.rays, d_out_weights=out.weights, d_out_pixels=out.pixels, d_out_ids=out.ids,
-                                       d_out_count=None if last else cnts[5:], d_out_lowres=out.low)
+        common = dict(y0=y0, y1=y1, spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled, flags=plan.level_flags(0)[2], d_hits=hits,
+                      d_sample_normal=normal, d_counts=cnts[:5], stream=plan.stream, children=children, environment=plan.environment,
+                      kinds=plan.path_kinds, path_seed=plan.path_seed, d_out_rays=out.rays, d_out_weights=out.weights,
+                      d_out_pixels=out.pixels, d_out_ids=out.ids, d_out_count=None if last else cnts[5:], d_out_lowres=out.low)
+        if plan.lens is not None:                       # the same frame through the thin lens
+            self.scene.render_level_lights_lens(self.cam, self.W, self.H, self.d_rgb, plan.lens["aperture"], plan.lens["focus_plane"],
+                                                **common)
+        else:
+            self.scene.render_level_lights(self.cam, self.W, self.H, self.d_rgb, **common)
         self._gather(plan, Queue(self.d_rays, None, None, None, None, self.n), hits, normal, self.d_rgb)
         host = cnts.tolist()
         return (host[0], host[1]), None if last else out.first(host[5])

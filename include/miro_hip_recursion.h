@@ -48,8 +48,8 @@ extern "C" {
  *   bits; more samples than 2^32 - 1); NULL desc or NULL d_level_counts (8-byte aligned); depth > 64; with depth >= 1: children
  *   that is neither MR_LEVEL_SPECULAR nor MR_LEVEL_PATH, queue_capacity 0, a NULL or misaligned workspace, workspace_bytes too
  *   small; non-zero reserved words.  MR_ERR_STATE: a scene that is unbuilt, built host_only, or has no lights.
- * Not part of this call: photon maps (mr_render_recursion_photons, miro_hip_recursion_photons.h, is this call with them), square lights, the thin lens, more than one
- *   band range per call, and octant bytes for grouped traversal (group_octants).  The per-level calls serve those. */
+ * Not part of this call: photon maps (mr_render_recursion_photons, miro_hip_recursion_photons.h, is this call with them), square lights, the thin lens (mr_render_recursion_lens,
+ *   miro_hip_lens.h, is this call with it), more than one band range per call, and octant bytes for grouped traversal (group_octants).  The per-level calls serve those. */
 typedef struct mr_recursion_desc {
     uint32_t depth;                 /* TRACE_DEPTH: levels 0..depth are run */
     uint32_t children;              /* MR_LEVEL_SPECULAR or MR_LEVEL_PATH (depth 0: ignored) */

@@ -44,7 +44,8 @@ extern "C" {
  *   (NaN included); frame->tiled (the level-0 pixel is k / spp, image order); a NULL or misaligned workspace or workspace_bytes
  *   too small, at any depth; 2^31 samples or more, or a queue_capacity of 2^31 or more (one estimate launch answers at most
  *   2^31 - 1 queries).  MR_ERR_STATE: mr_render_recursion's cases; a map that is not balanced and resident, or lives on another
- *   device than the scene.  A scene with a procedural texture is accepted: the call passes the normal buffer itself. */
+ *   device than the scene.  A scene with a procedural texture is accepted: the call passes the normal buffer itself.
+ * The thin lens is not part of this call: mr_render_recursion_photons_lens (miro_hip_lens.h) is this call with it. */
 mr_status mr_render_recursion_photons_workspace(const mr_frame_desc *frame, const mr_recursion_desc *desc, uint64_t *bytes);   /* host only */
 mr_status mr_render_recursion_photons(mr_scene *scene, const mr_frame_desc *frame, const mr_recursion_desc *desc,
                                       mr_photon_map *global_map, mr_photon_map *caustic_map, float max_dist, uint32_t nphotons,
@@ -55,3 +56,4 @@ mr_status mr_render_recursion_photons(mr_scene *scene, const mr_frame_desc *fram
 }
 #endif
 #endif /* MIRO_HIP_RECURSION_PHOTONS_H */
+#include "miro_hip_lens.h"

@@ -46,7 +46,8 @@ extern "C" {
  *   > 1; with MR_LEVEL_PATH, path_kinds 0 or with unknown bits; non-zero reserved words; children without an output queue
  *   (d_out_rays, d_out_weights, d_out_pixels, d_out_count) or, on a window that is not empty, with out_capacity 0; misalignment
  *   (out rays 16 bytes, d_out_count 8, weights, pixels and ids 4; octants and low-res bytes may lie anywhere).  MR_ERR_STATE: a
- *   scene that is unbuilt, built host_only, or has no lights.  Square lights and the thin lens are not part of this call. */
+ *   scene that is unbuilt, built host_only, or has no lights.  Square lights are not part of this call; the thin lens is
+ *   mr_render_level_lights_lens (miro_hip_lens.h), this call with a mr_lens_desc. */
 typedef struct mr_frame_level_desc {
     uint32_t children;                 /* MR_LEVEL_LAST, MR_LEVEL_SPECULAR or MR_LEVEL_PATH */
     uint32_t environment;              /* 0: a miss is worth 0.  1: Scene::getEnvironmentMap of mr_scene_set_environment */
