@@ -1298,8 +1298,20 @@ mr_status mr_render_lights_surface(mr_scene *s, const mr_frame_desc *frame, floa
     if (st != MR_OK) return st;
     LightScene ls;
     if ((st = lights_scene_params(s, false, stream, ls)) != MR_OK) return st;
-    return launch_frame_lights_surface(ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal,
-                                       reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+    const FrameOutputs o = {d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts)};
+    return launch_frame_lights_surface(ls, fd, o, static_cast<hipStream_t>(stream));
+}
+
+// Level 0 of the light-list frame with the environment, whichever call asks for it; the only caller of its three launchers.  A lens
+// (optional) selects the thin-lens frame (mr_frame_lens.hip), with or without children; without a lens, ld.children ==
+// MR_LEVEL_LAST is the plain frame (mr_frame_lights_env.hip), which reads neither `out` nor d_out_count, and a level with children
+// the frame that emits them into `out` (mr_frame_level_lights.hip).  who: the entry point the lens frame's window messages name
+static mr_status launch_level0_lights(const char *who, const LightScene &ls, const mr_frame_desc &fd, const mr_lens_desc *lens,
+                                      const mr_frame_level_desc &ld, const FrameOutputs &o, const RayQueue &out,
+                                      unsigned long long *d_out_count, hipStream_t stream) {
+    if (lens) return launch_frame_lens(who, ls, fd, *lens, ld, o, out, d_out_count, stream);
+    if (ld.children == MR_LEVEL_LAST) return launch_frame_lights_env(ls, fd, o, stream);
+    return launch_frame_level_lights(ls, fd, ld, o, out, d_out_count, stream);
 }
 
 // ... and a live sample whose primary ray misses is worth the scene's environment (mr_frame_lights_env.hip).  The first call after
@@ -1313,8 +1325,10 @@ mr_status mr_render_lights_environment(mr_scene *s, const mr_frame_desc *frame, 
     if (st != MR_OK) return st;
     LightScene ls;
     if ((st = lights_scene_params(s, true, stream, ls)) != MR_OK) return st;
-    return launch_frame_lights_env(ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal,
-                                   reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
+    const FrameOutputs o = {d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts)};
+    mr_frame_level_desc last = {};
+    last.children = MR_LEVEL_LAST;
+    return launch_level0_lights("mr_render_lights_environment", ls, fd, nullptr, last, o, RayQueue{}, nullptr, static_cast<hipStream_t>(stream));
 }
 
 // what the three calls that emit children ask of the queue they fill, in this order: the queue and its capacity with children
@@ -1476,16 +1490,9 @@ static mr_status render_level_lights(const char *who, bool with_lens, mr_scene *
     LightScene ls;
     if ((st = lights_scene_params(s, level->environment != 0, stream, ls)) != MR_OK) return st;
     const RayQueue out = {d_out_rays, d_out_weights, d_out_pixels, d_out_ids, level->d_out_lowres};
-    if (with_lens)
-        return launch_frame_lens(who, ls, fd, *lens, *level, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal, out,
-                                 reinterpret_cast<unsigned long long *>(d_out_count), reinterpret_cast<unsigned long long *>(d_counts),
-                                 static_cast<hipStream_t>(stream));
-    if (!children)
-        return launch_frame_lights_env(ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal,
-                                       reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream));
-    return launch_frame_level_lights(ls, fd, *level, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal, out,
-                                     reinterpret_cast<unsigned long long *>(d_out_count), reinterpret_cast<unsigned long long *>(d_counts),
-                                     static_cast<hipStream_t>(stream));
+    const FrameOutputs o = {d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal, reinterpret_cast<unsigned long long *>(d_counts)};
+    return launch_level0_lights(who, ls, fd, with_lens ? lens : nullptr, *level, o, out, reinterpret_cast<unsigned long long *>(d_out_count),
+                                static_cast<hipStream_t>(stream));
 }
 mr_status mr_render_level_lights(mr_scene *s, const mr_frame_desc *frame, const mr_frame_level_desc *level, float *d_rgb, mr_hit *d_hits,
                                  float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, mr_ray *d_out_rays,
@@ -1577,7 +1584,7 @@ mr_status mr_render_recursion_workspace(const mr_recursion_desc *desc, uint64_t 
 }
 
 // The launches of a whole recursive frame on one stream, and nothing else: the kernel that zeroes the counters (`counts`:
-// [depth + 1][8]); level 0, mr_render_level_lights' launcher with its children in queue 0 of the workspace (depth 0: the plain
+// [depth + 1][8]); level 0, mr_render_level_lights' launcher (launch_level0_lights) with its children in queue 0 of the workspace (depth 0: the plain
 // frame, no workspace); then one queued level kernel (mr_level_lights_queued.hip) per further level, from one queue into the
 // other, whose length is the word the level before counted its children into.  d_hits / d_normal: optional, every level's per-ray
 // records, each level overwriting the one before.  step(l, d_n, bound, in) is enqueued after level l, 0 included -- d_n: the
@@ -1603,12 +1610,9 @@ static mr_status enqueue_recursion(const LightScene &ls, const mr_frame_desc &fd
         l0.path_kinds = rd.path_kinds; l0.path_seed = rd.path_seed;
         l0.out_capacity_lo = rd.queue_capacity_lo; l0.out_capacity_hi = 0;
     }
-    if (lens)
-        st = launch_frame_lens("mr_render_level_lights_lens", ls, fd, *lens, l0, d_rgb, d_hits, nullptr, nullptr, d_normal, qs[0], &counts[5], counts, hs);
-    else if (rd.depth == 0)
-        st = launch_frame_lights_env(ls, fd, d_rgb, d_hits, nullptr, nullptr, d_normal, counts, hs);
-    else
-        st = launch_frame_level_lights(ls, fd, l0, d_rgb, d_hits, nullptr, nullptr, d_normal, qs[0], &counts[5], counts, hs);
+    FrameOutputs o = {};
+    o.rgb = d_rgb; o.hits = d_hits; o.sample_normal = d_normal; o.counts = counts;
+    st = launch_level0_lights("mr_render_level_lights_lens", ls, fd, lens, l0, o, qs[0], &counts[5], hs);
     if (st != MR_OK || (st = step(0u, &counts[0], samples, RayQueue{})) != MR_OK) return st;
 
     QueuedLevel lv = {};

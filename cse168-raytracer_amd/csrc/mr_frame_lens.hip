@@ -74,16 +74,6 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
     frame_lights_surface_body<VAR, false, true, CHILDREN, true>(a.f, a.env, a.ch, a.ln, s_stack, s_tab);
 }
 
-template <int VAR, int CHILDREN>
-mr_status launch_frame_lens_t(const FrameLensArgs &a, hipStream_t stream) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(&frame_lens_kernel<VAR, CHILDREN>, a.f.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL((frame_lens_kernel<VAR, CHILDREN>), dim3(trace_grid(a.f.eye.n)), dim3(kTraceBlock), lds, stream, a);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
-}
-
 // the focus point of fd's camera: m_viewDir is make_eye_frame's, as launch_eye_rays_lens takes it
 LensParams lens_params_of_frame(const mr_frame_desc &fd, const mr_lens_desc &lens) {
     float view[3];
@@ -124,31 +114,23 @@ __global__ __launch_bounds__(kBlock) void gather_eye_queries_lens_kernel(EyeLens
 }  // namespace
 
 mr_status launch_frame_lens(const char *who, const LightScene &ls, const mr_frame_desc &fd, const mr_lens_desc &lens, const mr_frame_level_desc &ld,
-                            float *d_rgb, mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, const RayQueue &out,
-                            unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream) {
+                            const FrameOutputs &o, const RayQueue &out, unsigned long long *d_out_count, hipStream_t stream) {
     FrameLensArgs a = {};
     const bool children = ld.children != MR_LEVEL_LAST;
-    mr_status st = fill_frame_lights_surface_args(a.f, who, ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color, d_sample_normal, d_counts);
+    mr_status st = fill_frame_lights_surface_args(a.f, who, ls, fd, o);
     if (st != MR_OK || (children && (st = launch_zero_count(d_out_count, stream)) != MR_OK)) return st;
     if (a.f.eye.n == 0) return MR_OK;
     a.env = ls.env;
     a.ln = lens_params_of_frame(fd, lens);
-    if (children) {
-        a.ch.out.rays = out.rays; a.ch.out.weights = out.weights; a.ch.out.pixels = out.pixels;
-        a.ch.out.ids = ld.children == MR_LEVEL_PATH ? out.ids : nullptr;
-        a.ch.out.count = d_out_count;
-        a.ch.out.capacity = out_capacity_of(ld);
-        a.ch.out.octants = ld.d_out_octants;
-        a.ch.out_lowres = out.low;
-        a.ch.kinds = ld.path_kinds; a.ch.hbase = pcg32(ld.path_seed);
-    }
+    if (children) fill_frame_child_args(a.ch, ld, out, d_out_count);
 
     // the traversal variants of launch_frame_level_lights: the same hit records from each of them
     const DeviceScene &ds = *ls.ds;
     return with_trace_variant(ds.n_planes || ds.n_spheres, fd.flags & MR_MATH_PRODUCT, fd.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
-        if (!children) return launch_frame_lens_t<VAR, 0>(a, stream);
-        return ld.children == MR_LEVEL_PATH ? launch_frame_lens_t<VAR, 2>(a, stream) : launch_frame_lens_t<VAR, 1>(a, stream);
+        auto kern = &frame_lens_kernel<VAR, 0>;
+        if (children) kern = ld.children == MR_LEVEL_PATH ? &frame_lens_kernel<VAR, 2> : &frame_lens_kernel<VAR, 1>;
+        return launch_traversal(kern, trace_grid(a.f.eye.n), a.f.tp.stack_depth, stream, a);
     });
 }
 

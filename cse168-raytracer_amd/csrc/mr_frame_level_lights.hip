@@ -82,16 +82,6 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIR
     frame_lights_surface_body<VAR, false, true, CHILDREN>(a.f, a.env, a.ch, s_stack, s_tab);
 }
 
-template <int VAR, int CHILDREN>
-mr_status launch_frame_level_lights_t(const FrameLevelLightsArgs &a, hipStream_t stream) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(&frame_level_lights_kernel<VAR, CHILDREN>, a.f.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL((frame_level_lights_kernel<VAR, CHILDREN>), dim3(trace_grid(a.f.eye.n)), dim3(kTraceBlock), lds, stream, a);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
-}
-
 }  // namespace
 
 mr_status frame_level_lights_samples(const char *who, const mr_frame_desc &fd, unsigned long long &n) {
@@ -101,28 +91,21 @@ mr_status frame_level_lights_samples(const char *who, const mr_frame_desc &fd, u
     return st;
 }
 
-mr_status launch_frame_level_lights(const LightScene &ls, const mr_frame_desc &fd, const mr_frame_level_desc &ld, float *d_rgb, mr_hit *d_hits,
-                                    float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, const RayQueue &out,
-                                    unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream) {
+mr_status launch_frame_level_lights(const LightScene &ls, const mr_frame_desc &fd, const mr_frame_level_desc &ld, const FrameOutputs &o,
+                                    const RayQueue &out, unsigned long long *d_out_count, hipStream_t stream) {
     FrameLevelLightsArgs a;
-    mr_status st = fill_frame_lights_surface_args(a.f, "mr_render_level_lights", ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color,
-                                                  d_sample_normal, d_counts);
+    mr_status st = fill_frame_lights_surface_args(a.f, "mr_render_level_lights", ls, fd, o);
     if (st != MR_OK || (st = launch_zero_count(d_out_count, stream)) != MR_OK) return st;
     if (a.f.eye.n == 0) return MR_OK;
     a.env = ls.env;
-    a.ch.out.rays = out.rays; a.ch.out.weights = out.weights; a.ch.out.pixels = out.pixels;
-    a.ch.out.ids = ld.children == MR_LEVEL_PATH ? out.ids : nullptr;
-    a.ch.out.count = d_out_count;
-    a.ch.out.capacity = out_capacity_of(ld);
-    a.ch.out.octants = ld.d_out_octants;
-    a.ch.out_lowres = out.low;
-    a.ch.kinds = ld.path_kinds; a.ch.hbase = pcg32(ld.path_seed);
+    fill_frame_child_args(a.ch, ld, out, d_out_count);
 
     // the traversal variants of launch_frame_lights_env / launch_level_lights: the same hit records from each of them
     const DeviceScene &ds = *ls.ds;
     return with_trace_variant(ds.n_planes || ds.n_spheres, fd.flags & MR_MATH_PRODUCT, fd.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
-        return ld.children == MR_LEVEL_PATH ? launch_frame_level_lights_t<VAR, 2>(a, stream) : launch_frame_level_lights_t<VAR, 1>(a, stream);
+        const auto kern = ld.children == MR_LEVEL_PATH ? &frame_level_lights_kernel<VAR, 2> : &frame_level_lights_kernel<VAR, 1>;
+        return launch_traversal(kern, trace_grid(a.f.eye.n), a.f.tp.stack_depth, stream, a);
     });
 }
 

@@ -8,8 +8,8 @@
 //
 // It is mr_frame.hip's frame with mr_lights.hip's light loop in the place of its one shadow ray.  One sample per lane: the
 // primary ray is generated in registers (eye_sample_of / eye_ray_of, mr_eye.h) and traced (trace_hit, mr_traverse.h); P, N and
-// the material come from the hit still in registers; the walk over the list is the body of shade_lights_body
-// (mr_lights_body.h) with kColorMaterial -- the list (at most MR_MAX_LIGHTS records) sits in the kernel arguments and the loop
+// the material come from the hit still in registers; the walk over the list is shade_light_list (mr_light_loop.h), the loop
+// of shade_lights_body (mr_lights_body.h), with the material's own colour -- the list (at most MR_MAX_LIGHTS records) sits in the kernel arguments and the loop
 // index is wave-uniform --; the pixel's samples meet in frame_kernel's xor-butterfly.  No ray, hit or per-ray colour buffer
 // exists: the batched form (mr_gen_eye_rays[_tiled] -> mr_trace -> mr_shade_lights) keeps 32 + 16 + 12 bytes per sample
 // resident and moves them through HBM twice; this kernel writes 12 bytes per PIXEL (plus, on request, the 16-byte hit record
@@ -32,6 +32,7 @@
 #include "mr_frame_window.h"
 #include "mr_internal.h"
 #include "mr_launch.h"
+#include "mr_light_loop.h"
 #include "mr_phong.h"
 #include "mr_surface.h"
 #include "mr_tile.h"
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(fra
         const mr_hit h = trace_hit<true, false, false, VAR>(a.tp, ra, rb, rb.w, live, s_stack, tid, st);
         if (a.hits && live) reinterpret_cast<float4 *>(a.hits)[idx] = *reinterpret_cast<const float4 *>(&h);
 
-        // ---- Phong::shade over the light list (shade_lights_body with kColorMaterial); a miss contributes nothing (m_bgColor = 0)
+        // ---- Phong::shade over the light list (the material's own colour, as kColorMaterial); a miss contributes nothing (m_bgColor = 0)
         const bool hit = live && h.prim != MR_MISS;
         float P[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 1.f, 0.f};
         const float d[3] = {rb.x, rb.y, rb.z};
@@ -106,33 +107,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(fra
             my_shadow_rays += a.n_lights;
         }
         float L[3] = {0.f, 0.f, 0.f};
-        for (uint32_t li = 0; li < a.n_lights; li++) {                 // Phong.cpp:63, wave-uniform
-            const ShadeLight &lt = a.lights[li];
-            float4 sh;
-            {
-                float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(1.f, 1.f, 1.f, -1.f);
-                if (hit) shadow_ray_for(lt, P, sa, sb);
-                const mr_hit hs = trace_hit<true, ANY, false, VAR>(a.tp, sa, sb, sb.w, hit, s_stack, tid, st);
-                sh = *reinterpret_cast<const float4 *>(&hs);
-            }
-            if (hit) {
-                float4 sa, sb;
-                shadow_ray_for(lt, P, sa, sb);                         // rebuilt rather than kept across the traversal
-                const float scale = light_scale_of(a.m, sa, sb, sh);
-                float diffuse[3] = {0.f, 0.f, 0.f}, highlight = 0.0f, out[3] = {0.f, 0.f, 0.f};
-                bool lit = scale != 0.0f;                              // Phong.cpp:100-111: the light is skipped
-                if (lit) {
-                    if (lt.kind == MR_LIGHT_DISC) {
-                        const float l[3] = {sb.x, sb.y, sb.z};
-                        lit = disc_terms(lt, mt, mt, P, N, l, d[0], d[1], d[2], diffuse, highlight);
-                    } else {
-                        phong_terms(lt.position, lt.color, lt.wattage, mt, mt, P, N, d[0], d[1], d[2], diffuse, highlight);
-                    }
-                }
-                if (lit) phong_combine(diffuse, highlight, scale, out);
-                L[0] += out[0]; L[1] += out[1]; L[2] += out[2];
-            }
-        }
+        shade_light_list<VAR, ANY>(a.tp, a.m, a.lights, a.n_lights, hit, P, N, mt, mt, d, s_stack, tid, st, L);
         if (a.sample_rgb && live) { a.sample_rgb[3 * idx] = L[0]; a.sample_rgb[3 * idx + 1] = L[1]; a.sample_rgb[3 * idx + 2] = L[2]; }
 
         // ---- the pixel's mean (Scene.cpp:126-139), as frame_kernel forms it: spp is a power of two <= 64 (checked by the
@@ -189,12 +164,7 @@ mr_status launch_frame_lights(const DeviceScene &ds, const ShadeLight *lights, u
     return with_trace_variant(ds.n_planes || ds.n_spheres, fd.flags & MR_MATH_PRODUCT, fd.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
         const auto kern = any ? &frame_lights_kernel<VAR, true> : &frame_lights_kernel<VAR, false>;
-        size_t lds = 0;
-        const mr_status ls = stack_lds(kern, a.tp.stack_depth, kStackLdsShared, lds);
-        if (ls != MR_OK) return ls;
-        hipLaunchKernelGGL(kern, dim3(trace_grid(a.eye.n)), dim3(kTraceBlock), lds, stream, a);
-        MR_HIP_CHECK(hipGetLastError());
-        return MR_OK;
+        return launch_traversal(kern, trace_grid(a.eye.n), a.tp.stack_depth, stream, a);
     });
 }
 

@@ -68,11 +68,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(fra
 
 }  // namespace
 
-mr_status launch_frame_lights_env(const LightScene &ls, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
-                                  float *d_sample_color, float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream) {
+mr_status launch_frame_lights_env(const LightScene &ls, const mr_frame_desc &fd, const FrameOutputs &o, hipStream_t stream) {
     FrameLightsEnvArgs a;
-    const mr_status st = fill_frame_lights_surface_args(a.f, "mr_render_lights_environment", ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color,
-                                                        d_sample_normal, d_counts);
+    const mr_status st = fill_frame_lights_surface_args(a.f, "mr_render_lights_environment", ls, fd, o);
     if (st != MR_OK) return st;
     if (a.f.eye.n == 0) return MR_OK;
     a.env = ls.env;
@@ -83,12 +81,7 @@ mr_status launch_frame_lights_env(const LightScene &ls, const mr_frame_desc &fd,
     return with_trace_variant(ds.n_planes || ds.n_spheres, fd.flags & MR_MATH_PRODUCT, fd.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
         const auto kern = any ? &frame_lights_env_kernel<VAR, true> : &frame_lights_env_kernel<VAR, false>;
-        size_t lds = 0;
-        const mr_status ss = stack_lds(kern, a.f.tp.stack_depth, kStackLdsShared, lds);
-        if (ss != MR_OK) return ss;
-        hipLaunchKernelGGL(kern, dim3(trace_grid(a.f.eye.n)), dim3(kTraceBlock), lds, stream, a);
-        MR_HIP_CHECK(hipGetLastError());
-        return MR_OK;
+        return launch_traversal(kern, trace_grid(a.f.eye.n), a.f.tp.stack_depth, stream, a);
     });
 }
 

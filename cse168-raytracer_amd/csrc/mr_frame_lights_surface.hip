@@ -71,11 +71,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(fra
 
 }  // namespace
 
-mr_status launch_frame_lights_surface(const LightScene &ls, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
-                                      float *d_sample_color, float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream) {
+mr_status launch_frame_lights_surface(const LightScene &ls, const mr_frame_desc &fd, const FrameOutputs &o, hipStream_t stream) {
     FrameLightsSurfaceArgs a;
-    const mr_status st = fill_frame_lights_surface_args(a, "mr_render_lights_surface", ls, fd, d_rgb, d_hits, d_sample_rgb, d_sample_color,
-                                                        d_sample_normal, d_counts);
+    const mr_status st = fill_frame_lights_surface_args(a, "mr_render_lights_surface", ls, fd, o);
     if (st != MR_OK) return st;
     if (a.eye.n == 0) return MR_OK;
 
@@ -85,12 +83,7 @@ mr_status launch_frame_lights_surface(const LightScene &ls, const mr_frame_desc 
     return with_trace_variant(ds.n_planes || ds.n_spheres, fd.flags & MR_MATH_PRODUCT, fd.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
         const auto kern = any ? &frame_lights_surface_kernel<VAR, true> : &frame_lights_surface_kernel<VAR, false>;
-        size_t lds = 0;
-        const mr_status ss = stack_lds(kern, a.tp.stack_depth, kStackLdsShared, lds);
-        if (ss != MR_OK) return ss;
-        hipLaunchKernelGGL(kern, dim3(trace_grid(a.eye.n)), dim3(kTraceBlock), lds, stream, a);
-        MR_HIP_CHECK(hipGetLastError());
-        return MR_OK;
+        return launch_traversal(kern, trace_grid(a.eye.n), a.tp.stack_depth, stream, a);
     });
 }
 

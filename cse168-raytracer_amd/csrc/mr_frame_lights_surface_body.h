@@ -64,18 +64,17 @@ struct FrameLightsSurfaceArgs {
     ShadeLight lights[MR_MAX_LIGHTS];
 };
 
-// what launch_frame_lights_surface and launch_frame_lights_env put into the block; `who`: the entry point the window's messages name
+// what every launcher of this frame puts into the block; `who`: the entry point the window's messages name
 inline mr_status fill_frame_lights_surface_args(FrameLightsSurfaceArgs &a, const char *who, const LightScene &ls, const mr_frame_desc &fd,
-                                                float *d_rgb, mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color,
-                                                float *d_sample_normal, unsigned long long *d_counts) {
+                                                const FrameOutputs &o) {
     const mr_status st = frame_window_of(who, fd, a.eye);
     if (st != MR_OK) return st;
     a.tp = scene_trace_params(*ls.ds);
     a.tp.n = a.eye.n;
     a.m = mesh_of(*ls.ds);
     a.t = ls.tex;
-    a.hits = d_hits; a.sample_rgb = d_sample_rgb; a.sample_color = d_sample_color; a.sample_normal = d_sample_normal;
-    a.rgb = d_rgb; a.counts = d_counts;
+    a.hits = o.hits; a.sample_rgb = o.sample_rgb; a.sample_color = o.sample_color; a.sample_normal = o.sample_normal;
+    a.rgb = o.rgb; a.counts = o.counts;
     a.n_lights = ls.n_lights;
     for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = ls.lights[i < ls.n_lights ? i : 0];
     return MR_OK;
@@ -87,6 +86,16 @@ struct FrameChildArgs {
     uint8_t *out_lowres;         // CHILDREN == 2, optional: per stored child, 1 for the child of Ray::random (kind 3), 0 otherwise
     uint32_t kinds, hbase;       // CHILDREN == 2: MR_PATH_* wanted, pcg32(path seed)
 };
+// the queue `out`, counted into d_out_count, as level 0's descriptor has it (out.low takes the place of ld.d_out_lowres)
+inline void fill_frame_child_args(FrameChildArgs &ch, const mr_frame_level_desc &ld, const RayQueue &out, unsigned long long *d_out_count) {
+    ch.out.rays = out.rays; ch.out.weights = out.weights; ch.out.pixels = out.pixels;
+    ch.out.ids = ld.children == MR_LEVEL_PATH ? out.ids : nullptr;
+    ch.out.count = d_out_count;
+    ch.out.capacity = out_capacity_of(ld);
+    ch.out.octants = ld.d_out_octants;
+    ch.out_lowres = out.low;
+    ch.kinds = ld.path_kinds; ch.hbase = pcg32(ld.path_seed);
+}
 
 // VAR, ANY: as in frame_lights_kernel.  s_stack: the workgroup's dynamic LDS, [stack_depth][kTraceBlock]; s_tab: 128 words of
 // static LDS for the two noise tables.

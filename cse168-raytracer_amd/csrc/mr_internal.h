@@ -296,14 +296,13 @@ mr_status launch_frame_lights(const DeviceScene &ds, const ShadeLight *lights, u
                               mr_hit *d_hits, float *d_sample_rgb, unsigned long long *d_counts, hipStream_t stream);
 // ... on any scene (mr_frame_lights_surface.hip, mr_render_lights_surface): every hit's diffuse colour and normal from
 // hit_color_normal between the primary trace and the light loop.  tex: as mr_hit_surface hands it to launch_hit_surface
-// (recs / mat_tex nullptr without a texture table); d_sample_color / d_sample_normal optional; d_counts: three words
+// (recs / mat_tex nullptr without a texture table); o (FrameOutputs, below): sample_color / sample_normal optional; counts: three words
 struct LightScene;
-mr_status launch_frame_lights_surface(const LightScene &ls, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
-                                      float *d_sample_color, float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream);
+struct FrameOutputs;
+mr_status launch_frame_lights_surface(const LightScene &ls, const mr_frame_desc &fd, const FrameOutputs &o, hipStream_t stream);
 // ... with the environment for rays that miss (mr_frame_lights_env.hip, mr_render_lights_environment): a live sample whose
-// primary ray misses is worth ls.env.bg, or the lookup of the full image (ls.env.full); d_counts: five words
-mr_status launch_frame_lights_env(const LightScene &ls, const mr_frame_desc &fd, float *d_rgb, mr_hit *d_hits, float *d_sample_rgb,
-                                  float *d_sample_color, float *d_sample_normal, unsigned long long *d_counts, hipStream_t stream);
+// primary ray misses is worth ls.env.bg, or the lookup of the full image (ls.env.full); o.counts: five words
+mr_status launch_frame_lights_env(const LightScene &ls, const mr_frame_desc &fd, const FrameOutputs &o, hipStream_t stream);
 // *d_count = 0 on `stream`, as a one-word kernel: the node that zeroes d_out_count in the three launchers below, which a captured
 // graph replays as written (mr_level_lights.hip says what a memset node did)
 mr_status launch_zero_count(unsigned long long *d_count, hipStream_t stream);
@@ -330,6 +329,14 @@ struct RayQueue {
     uint32_t *pixels, *ids;
     uint8_t *low;
 };
+// What a light-list frame on any scene writes: the pixels; per sample, each optional, the primary hit record, the un-weighted L,
+// the hit's diffuseColor and the normal Scene::trace hands on; the launch's counters (optional)
+struct FrameOutputs {
+    float *rgb;
+    mr_hit *hits;
+    float *sample_rgb, *sample_color, *sample_normal;
+    unsigned long long *counts;
+};
 // the capacity of the output queue as a level's descriptor spells it (mr_level_lights_desc, mr_level_lights_path_desc, mr_frame_level_desc)
 template <typename DESC>
 unsigned long long out_capacity_of(const DESC &ld) { return ((unsigned long long)ld.out_capacity_hi << 32) | ld.out_capacity_lo; }
@@ -340,15 +347,13 @@ unsigned long long out_capacity_of(const DESC &ld) { return ((unsigned long long
 // (a one-word kernel), then one kernel (none for an empty window).
 // frame_level_lights_samples: the samples of fd's window, from the descriptor alone (no device call)
 mr_status frame_level_lights_samples(const char *who, const mr_frame_desc &fd, unsigned long long &n);
-mr_status launch_frame_level_lights(const LightScene &ls, const mr_frame_desc &fd, const mr_frame_level_desc &ld, float *d_rgb, mr_hit *d_hits,
-                                    float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, const RayQueue &out,
-                                    unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
+mr_status launch_frame_level_lights(const LightScene &ls, const mr_frame_desc &fd, const mr_frame_level_desc &ld, const FrameOutputs &o,
+                                    const RayQueue &out, unsigned long long *d_out_count, hipStream_t stream);
 // ... for the thin-lens camera (mr_frame_lens.hip, mr_render_level_lights_lens): the eye ray of a sample is the one
 // launch_eye_rays_lens makes for it without caller-supplied samples.  ld.children == MR_LEVEL_LAST launches the frame without
 // children and touches neither `out` nor d_out_count.  `who`: the entry point the window's messages name
 mr_status launch_frame_lens(const char *who, const LightScene &ls, const mr_frame_desc &fd, const mr_lens_desc &lens, const mr_frame_level_desc &ld,
-                            float *d_rgb, mr_hit *d_hits, float *d_sample_rgb, float *d_sample_color, float *d_sample_normal, const RayQueue &out,
-                            unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
+                            const FrameOutputs &o, const RayQueue &out, unsigned long long *d_out_count, hipStream_t stream);
 // One level of mr_render_recursion, whose queue's length is a device word (mr_level_lights_queued.hip).  What the level is:
 // path: the PATH_TRACING build's kernel (children of bounce `bounce` from path_kinds / seed, ids, low-res bytes), else the
 // specular one; last: no children; capacity: the rays the output queue holds

@@ -106,6 +106,18 @@ mr_status stack_lds(K kern, int32_t stack_depth, StackLds limit, size_t &lds, si
     return MR_OK;
 }
 
+// One launch of a traversal kernel that keeps static LDS beside its stack (the level, frame and light-list kernels): `grid`
+// workgroups of kTraceBlock lanes with the stack of `stack_depth` levels as dynamic LDS, `args` the kernel's arguments
+template <typename K, typename... Args>
+mr_status launch_traversal(K kern, unsigned grid, int32_t stack_depth, hipStream_t stream, const Args &...args) {
+    size_t lds = 0;
+    const mr_status st = stack_lds(kern, stack_depth, kStackLdsShared, lds);
+    if (st != MR_OK) return st;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kTraceBlock), lds, stream, args...);
+    MR_HIP_CHECK(hipGetLastError());
+    return MR_OK;
+}
+
 // `grid` = the workgroups of `kern` the device holds at once, `want` at most and one at least
 template <typename K>
 mr_status resident_grid(K kern, size_t lds, unsigned long long want, unsigned &grid) {

@@ -136,25 +136,6 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(CHI
     }
 }
 
-template <int VAR, int CHILDREN>
-mr_status launch_level_t(const LevelArgs &a, hipStream_t stream) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(&level_kernel<VAR, CHILDREN>, a.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL((level_kernel<VAR, CHILDREN>), dim3(trace_grid(a.tp.n)), dim3(kTraceBlock), lds, stream, a);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
-}
-
-template <int VAR>
-mr_status launch_level_c(const LevelArgs &a, uint32_t children, hipStream_t stream) {
-    switch (children) {
-        case MR_LEVEL_LAST: return launch_level_t<VAR, 0>(a, stream);
-        case MR_LEVEL_SPECULAR: return launch_level_t<VAR, 1>(a, stream);
-        default: return launch_level_t<VAR, 2>(a, stream);
-    }
-}
-
 }  // namespace
 
 mr_status launch_level(const DeviceScene &ds, const mr_level_desc &ld, const mr_ray *d_rays, const float *d_weights,
@@ -176,8 +157,12 @@ mr_status launch_level(const DeviceScene &ds, const mr_level_desc &ld, const mr_
     a.out.octants = ld.d_out_octants;
     a.counts = d_counts;
 
-    return with_trace_variant(ds.n_planes || ds.n_spheres, ld.flags & MR_MATH_PRODUCT, ld.flags & MR_TRACE_INCOHERENT,
-                              [&](auto var) { return launch_level_c<decltype(var)::value>(a, ld.children, stream); });
+    return with_trace_variant(ds.n_planes || ds.n_spheres, ld.flags & MR_MATH_PRODUCT, ld.flags & MR_TRACE_INCOHERENT, [&](auto var) {
+        constexpr int VAR = decltype(var)::value;
+        auto kern = &level_kernel<VAR, 0>;
+        if (ld.children != MR_LEVEL_LAST) kern = ld.children == MR_LEVEL_SPECULAR ? &level_kernel<VAR, 1> : &level_kernel<VAR, 2>;
+        return launch_traversal(kern, trace_grid(n), a.tp.stack_depth, stream, a);
+    });
 }
 
 }  // namespace mr

@@ -222,23 +222,23 @@ __device__ __forceinline__ void level_lights_body(const ARGS a, int *s_stack, ui
     }
 }
 
-// what every level launch puts into its block, of either build; out_capacity, d_out_octants: the output queue's, as the level's
-// descriptor names them
+// what every level launch puts into its block, of either build.  in: the queue the level reads, its first n rays (rays, weights,
+// pixels; only read); out: the queue of its children (rays, weights, pixels, ids), counted into d_out_count; out_capacity,
+// d_out_octants: the output queue's, as the level's descriptor names them
 template <typename ARGS>
-void fill_level_lights_args(ARGS &a, const LightScene &ls, uint32_t spp, uint32_t environment, const mr_ray *d_rays, const float *d_weights,
-                            const uint32_t *d_pixels, unsigned long long n, float *d_rgb, mr_hit *d_hits, float *d_ray_rgb, float *d_color,
-                            float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels, uint32_t *d_out_ids,
+void fill_level_lights_args(ARGS &a, const LightScene &ls, uint32_t spp, uint32_t environment, const RayQueue &in, unsigned long long n,
+                            float *d_rgb, mr_hit *d_hits, float *d_ray_rgb, float *d_color, float *d_normal, const RayQueue &out,
                             unsigned long long *d_out_count, unsigned long long out_capacity, uint8_t *d_out_octants,
                             unsigned long long *d_counts) {
     a.tp = scene_trace_params(*ls.ds);
-    a.tp.rays = d_rays; a.tp.n = n;
+    a.tp.rays = in.rays; a.tp.n = n;
     a.m = mesh_of(*ls.ds);
     a.t = ls.tex;
     a.env = ls.env;
-    a.weights = d_weights; a.pixels = d_pixels;
+    a.weights = in.weights; a.pixels = in.pixels;
     a.spp = spp; a.environment = environment; a.inv_spp = 1.0f / (float)spp;
     a.hits = d_hits; a.ray_rgb = d_ray_rgb; a.color = d_color; a.normal = d_normal; a.rgb = d_rgb;
-    a.out.rays = d_out_rays; a.out.weights = d_out_weights; a.out.pixels = d_out_pixels; a.out.ids = d_out_ids; a.out.count = d_out_count;
+    a.out.rays = out.rays; a.out.weights = out.weights; a.out.pixels = out.pixels; a.out.ids = out.ids; a.out.count = d_out_count;
     a.out.capacity = out_capacity;
     a.out.octants = d_out_octants;
     a.counts = d_counts;
@@ -253,17 +253,6 @@ inline void fill_level_lights_path_args(LevelLightsPathArgs &a, const uint32_t *
     a.all_lowres = (flags & MR_ENV_LOWRES) ? 1u : 0u;
     a.hbase = pcg32(seed); a.bounce = bounce; a.kinds = path_kinds;
     a.out_lowres = d_out_lowres;
-}
-
-// one workgroup per kTraceBlock rays of the queue, the traversal stack in dynamic LDS
-template <typename ARGS>
-mr_status launch_level_lights_t(void (*kern)(const ARGS), const ARGS &a, hipStream_t stream) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(kern, a.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL(kern, dim3(trace_grid(a.tp.n)), dim3(kTraceBlock), lds, stream, a);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
 }
 
 }  // namespace

@@ -65,16 +65,18 @@ mr_status launch_level_lights_path(const LightScene &ls, const mr_level_lights_p
     }
     if (n == 0) return MR_OK;
     LevelLightsPathArgs a;
-    fill_level_lights_args(a, ls, ld.spp, ld.environment, d_rays, d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal,
-                           d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_count, out_capacity_of(ld), ld.d_out_octants, d_counts);
+    const RayQueue in = {const_cast<mr_ray *>(d_rays), const_cast<float *>(d_weights), const_cast<uint32_t *>(d_pixels), nullptr, nullptr};   // only read
+    const RayQueue out = {d_out_rays, d_out_weights, d_out_pixels, d_out_ids, nullptr};
+    fill_level_lights_args(a, ls, ld.spp, ld.environment, in, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, out, d_out_count,
+                           out_capacity_of(ld), ld.d_out_octants, d_counts);
     fill_level_lights_path_args(a, d_ids, ld.d_lowres, ld.flags, ld.seed, ld.bounce, ld.path_kinds, ld.d_out_lowres);
 
     // the traversal variants of launch_level_lights: the same hit records from each of them
     const DeviceScene &ds = *ls.ds;
     return with_trace_variant(ds.n_planes || ds.n_spheres, ld.flags & MR_MATH_PRODUCT, ld.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
-        return launch_level_lights_t(ld.children == MR_LEVEL_LAST ? &level_lights_path_kernel<VAR, 0> : &level_lights_path_kernel<VAR, 1>, a,
-                                     stream);
+        const auto kern = ld.children == MR_LEVEL_LAST ? &level_lights_path_kernel<VAR, 0> : &level_lights_path_kernel<VAR, 1>;
+        return launch_traversal(kern, trace_grid(n), a.tp.stack_depth, stream, a);
     });
 }
 

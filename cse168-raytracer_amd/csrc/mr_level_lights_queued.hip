@@ -74,18 +74,6 @@ __global__ void zero_words_kernel(unsigned long long *words, unsigned long long 
     if (k < n) words[k] = 0ull;
 }
 
-// trace_grid(min(n_cap, n_bound)) workgroups, the traversal stack in dynamic LDS
-template <typename ARGS>
-mr_status launch_queued_t(void (*kern)(const ARGS, const unsigned long long *, const unsigned long long), const ARGS &a,
-                          const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, hipStream_t stream) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(kern, a.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL(kern, dim3(level_lights_queued_grid(n_cap, n_bound)), dim3(kTraceBlock), lds, stream, a, d_n, n_cap);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
-}
-
 }  // namespace
 
 unsigned level_lights_queued_grid(unsigned long long n_cap, unsigned long long n_bound) {
@@ -104,9 +92,10 @@ mr_status launch_level_lights_queued(const LightScene &ls, const QueuedLevel &lv
                                      const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_rgb,
                                      mr_hit *d_hits, float *d_normal, unsigned long long *row, hipStream_t stream) {
     const DeviceScene &ds = *ls.ds;
+    const unsigned grid = level_lights_queued_grid(n_cap, n_bound);
     auto fill = [&](auto &a) {
-        fill_level_lights_args(a, ls, lv.spp, lv.environment, in.rays, in.weights, in.pixels, 0ull, d_rgb, d_hits, nullptr, nullptr, d_normal,
-                               out.rays, out.weights, out.pixels, out.ids, row + 5, lv.capacity, nullptr, row);
+        fill_level_lights_args(a, ls, lv.spp, lv.environment, in, 0ull, d_rgb, d_hits, nullptr, nullptr, d_normal, out, row + 5, lv.capacity,
+                               nullptr, row);
     };
     // the traversal variants of launch_level_lights: the same hit records from each of them
     if (!lv.path) {
@@ -114,8 +103,8 @@ mr_status launch_level_lights_queued(const LightScene &ls, const QueuedLevel &lv
         fill(a);
         return with_trace_variant(ds.n_planes || ds.n_spheres, lv.flags & MR_MATH_PRODUCT, lv.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
             constexpr int VAR = decltype(var)::value;
-            return launch_queued_t(lv.last ? &level_lights_queued_kernel<VAR, 0> : &level_lights_queued_kernel<VAR, 1>, a, d_n, n_cap, n_bound,
-                                   stream);
+            const auto kern = lv.last ? &level_lights_queued_kernel<VAR, 0> : &level_lights_queued_kernel<VAR, 1>;
+            return launch_traversal(kern, grid, a.tp.stack_depth, stream, a, d_n, n_cap);
         });
     }
     LevelLightsPathArgs a;
@@ -123,8 +112,8 @@ mr_status launch_level_lights_queued(const LightScene &ls, const QueuedLevel &lv
     fill_level_lights_path_args(a, in.ids, in.low, lv.flags, lv.seed, lv.bounce, lv.path_kinds, lv.last ? nullptr : out.low);
     return with_trace_variant(ds.n_planes || ds.n_spheres, lv.flags & MR_MATH_PRODUCT, lv.flags & MR_TRACE_INCOHERENT, [&](auto var) -> mr_status {
         constexpr int VAR = decltype(var)::value;
-        return launch_queued_t(lv.last ? &level_lights_path_queued_kernel<VAR, 0> : &level_lights_path_queued_kernel<VAR, 1>, a, d_n, n_cap,
-                               n_bound, stream);
+        const auto kern = lv.last ? &level_lights_path_queued_kernel<VAR, 0> : &level_lights_path_queued_kernel<VAR, 1>;
+        return launch_traversal(kern, grid, a.tp.stack_depth, stream, a, d_n, n_cap);
     });
 }
 

@@ -1,10 +1,10 @@
 // mr_light_loop.h -- Phong::shade's loop over Scene::lights() (Phong.cpp:63-156) for ONE hit that a lane holds in registers, as a
 // device function: per light the shadow ray, its closest-hit (or any-hit) traversal on the workgroup's LDS stack, the occluder's
-// light scale, the point or disc terms, summed into L in list order.  Two callers: the per-sample body of the fused light-list
-// frames (mr_frame_lights_surface_body.h: mr_render_lights_surface, mr_render_lights_environment) and the fused level of the
-// recursion (mr_level_lights.hip: mr_trace_level_lights).  The batched light-list kernels (mr_lights_body.h) run the same steps
-// on the same shared pieces -- shadow_ray_for / light_scale_of / disc_terms / phong_terms / phong_combine of mr_phong.h -- so a
-// ray's L is the same bits on every route.
+// light scale, the point or disc terms, summed into L in list order.  Every fused kernel calls it: the light-list frames
+// (mr_frame_lights.hip; mr_frame_lights_surface_body.h: mr_render_lights_surface, mr_render_lights_environment and the frames
+// that emit level 1) and the level of the recursion (mr_level_lights_body.h).  The batched light-list kernels (shade_lights_body,
+// mr_lights_body.h, which says why) keep the same steps written out, on the same shared pieces -- shadow_ray_for /
+// light_scale_of / disc_terms / phong_terms / phong_combine of mr_phong.h -- so a ray's L is the same bits on every route.
 //
 // Called by ALL lanes of the wave (trace_hit is): a lane without a hit brings hit = false, traces the idle ray and leaves L as it
 // was.  The shadow ray is built again after its traversal rather than kept live across it.  n_lights is wave-uniform.

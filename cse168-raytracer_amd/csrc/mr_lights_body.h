@@ -8,7 +8,7 @@
 // reference to the kernel's argument block the same body compiles to other register and scratch figures.  Measured when
 // kColorSurface joined the other two (hipcc, gfx950, the Makefile's flags): a source leaves the code of the other sources'
 // kernels alone -- the device assembly of mr_lights.hip, mr_textures.hip and mr_bounce.hip did not change by an instruction.
-// The launch plumbing of the three forms is launch_lights below.  Included by the .hip units that instantiate it (everything
+// The three forms fill their arguments with lights_args_of below and launch with launch_traversal (mr_launch.h).  Included by the .hip units that instantiate it (everything
 // here is local to its unit).
 #pragma once
 
@@ -51,8 +51,11 @@ inline void fill_shade_args(A &a, const DeviceScene &ds, uint32_t n_lights, cons
     a.rgb = d_rgb; a.ray_rgb = d_ray_rgb; a.counts = d_counts;
 }
 
-// The parts of a light-list kernel around its loop over the lights; the shadow traversal itself (trace_hit, then the ray built
-// again and light_scale_of) stays written out in each kernel.  A: ShadeArgs, or a block with the same fields.
+// The parts of a light-list kernel around its loop over the lights.  The loop of the fused kernels is shade_light_list
+// (mr_light_loop.h); shade_lights_body below keeps the same statements written out, on a measurement: through that function
+// the kernels of mr_lights.hip were slower than before by more than the run-to-run spread on the sponza stand-in (up to 0.5 %,
+// profiles/light_loop_ab.log).  A change to one copy goes into the other; tests/test_lights_fuzz.py and the
+// parity tests hold the two to the same bits.  A: ShadeArgs, or a block with the same fields.
 // ray k's hit record: a miss for a lane past the end of the batch
 template <typename A>
 __device__ __forceinline__ float4 hit_record_of(const A &a, unsigned long long k, bool live) {
@@ -165,18 +168,6 @@ inline LightsArgs lights_args_of(const DeviceScene &ds, const ShadeLight *lights
     fill_shade_args(a.s, ds, n_lights, d_rays, d_hits, d_weights, d_pixels, n, spp, d_rgb, d_ray_rgb, d_counts);
     for (uint32_t i = 0; i < MR_MAX_LIGHTS; i++) a.lights[i] = lights[i < n_lights ? i : 0];
     return a;
-}
-
-// ... and launch the same way: `kern` is the unit's own light-list kernel for the batch's traversal variant, `rest` its
-// arguments after the LightsArgs
-template <typename K, typename... Rest>
-mr_status launch_lights(K kern, const LightsArgs &a, hipStream_t stream, Rest... rest) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(kern, a.s.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL(kern, dim3(trace_grid(a.s.tp.n)), dim3(kTraceBlock), lds, stream, a, rest...);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
 }
 
 }  // namespace

@@ -184,7 +184,8 @@ mr_status launch_shade_lights_surf(const DeviceScene &ds, const ShadeLight *ligh
     const bool any = flags & MR_TRACE_ANY;
     return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT, [&](auto var) {
         constexpr int VAR = decltype(var)::value;
-        return launch_lights(any ? &shade_lights_surf_kernel<VAR, true> : &shade_lights_surf_kernel<VAR, false>, a, stream, d_color, d_normal);
+        return launch_traversal(any ? &shade_lights_surf_kernel<VAR, true> : &shade_lights_surf_kernel<VAR, false>, trace_grid(n), a.s.tp.stack_depth, stream, a,
+                                d_color, d_normal);
     });
 }
 

@@ -15,7 +15,7 @@
 // kColorSurface keeps the colour (three registers) across up to 64 shadow traversals per light.  The arguments are taken BY
 // VALUE, for the reason mr_lights_body.h gives; the two buffers are kernel arguments of their own rather than fields of
 // SquareArgs, so that the plain kernel's argument block is what it was.  The host work of the two launchers -- the argument
-// block with tangents, cell sizes and hseed, and the launch by traversal variant -- is square_args_of / launch_square below.
+// block with tangents, cell sizes and hseed, and the launch by traversal variant -- is square_args_of / launch_square_variant below.
 // Included by the .hip units that instantiate it (everything here is local to its unit).
 #pragma once
 
@@ -152,24 +152,13 @@ inline SquareArgs square_args_of(const DeviceScene &ds, const mr_square_light_de
     return a;
 }
 
-// ... and launch the same way: `kern` is the unit's own square-light kernel for the batch's traversal variant, `rest` its
-// arguments after the SquareArgs
-template <typename K, typename... Rest>
-mr_status launch_square(K kern, const SquareArgs &a, hipStream_t stream, Rest... rest) {
-    size_t lds = 0;
-    const mr_status st = stack_lds(kern, a.tp.stack_depth, kStackLdsShared, lds);
-    if (st != MR_OK) return st;
-    hipLaunchKernelGGL(kern, dim3(trace_grid(a.tp.n)), dim3(kTraceBlock), lds, stream, a, rest...);
-    MR_HIP_CHECK(hipGetLastError());
-    return MR_OK;
-}
-// the variant by scene and flags.  pick(var, any): the unit's kernel<VAR, ANY> for two std::integral_constants (a kernel
-// template cannot be handed over itself)
+// ... and launch the same way, the variant by scene and flags.  pick(var, any): the unit's kernel<VAR, ANY> for two
+// std::integral_constants (a kernel template cannot be handed over itself); `rest`: its arguments after the SquareArgs
 template <typename Pick, typename... Rest>
 mr_status launch_square_variant(const DeviceScene &ds, uint32_t flags, const SquareArgs &a, hipStream_t stream, Pick pick, Rest... rest) {
     return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT, [&](auto var) {
-        return (flags & MR_TRACE_ANY) ? launch_square(pick(var, std::true_type()), a, stream, rest...)
-                                      : launch_square(pick(var, std::false_type()), a, stream, rest...);
+        const auto kern = (flags & MR_TRACE_ANY) ? pick(var, std::true_type()) : pick(var, std::false_type());
+        return launch_traversal(kern, trace_grid(a.tp.n), a.tp.stack_depth, stream, a, rest...);
     });
 }
 

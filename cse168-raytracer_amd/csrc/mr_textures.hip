@@ -72,7 +72,7 @@ mr_status launch_shade_lights_tex(const DeviceScene &ds, const TexParams &tex, c
     const bool any = flags & MR_TRACE_ANY;
     return with_trace_variant(ds.n_planes || ds.n_spheres, flags & MR_MATH_PRODUCT, flags & MR_TRACE_INCOHERENT, [&](auto var) {
         constexpr int VAR = decltype(var)::value;
-        return launch_lights(any ? &shade_lights_tex_kernel<VAR, true> : &shade_lights_tex_kernel<VAR, false>, a, stream, tex);
+        return launch_traversal(any ? &shade_lights_tex_kernel<VAR, true> : &shade_lights_tex_kernel<VAR, false>, trace_grid(n), a.s.tp.stack_depth, stream, a, tex);
     });
 }
 
