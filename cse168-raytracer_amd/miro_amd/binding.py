@@ -476,6 +476,24 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def _map_handle(photon_map):
+    """the handle of an optional PhotonMap argument: NULL for None"""
+    return photon_map.h if photon_map is not None else None
+
+
+def _workspace_bytes(given, d_workspace):
+    """the workspace size a recursion declares: `given`, or for None the bytes of the tensor (0 without one)"""
+    if given is not None:
+        return given
+    return 0 if d_workspace is None else d_workspace.numel() * d_workspace.element_size()
+
+
+def _lens_desc(aperture, focus_plane):
+    lens = LensDesc()
+    lens.aperture, lens.focus_plane = aperture, focus_plane
+    return lens
+
+
 def _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags):
     """an mr_frame_desc from the arguments every render_* method takes: the window, the bands and the samples"""
     fd = FrameDesc()
@@ -683,8 +701,7 @@ class Scene:
         """mr_gen_eye_rays_lens: Camera::eyeRay under -DDOF for rows [y0, y1), in mr_gen_eye_rays' ray order.  d_samples_in /
         d_samples_out: 4 floats per ray (dx, dy, lx, ly), given / used; d_counts: [0] += rays, [1] += exhausted lens samples."""
         y1 = H if y1 is None else y1
-        lens = LensDesc()
-        lens.aperture, lens.focus_plane = aperture, focus_plane
+        lens = _lens_desc(aperture, focus_plane)
         _check(self.L.mr_gen_eye_rays_lens(self.h, C.byref(cam), W, H, y0, y1, spp, 1 if jitter else 0, seed, d_rays.data_ptr(),
                                            _stream_ptr(stream), C.byref(lens), _ptr(d_samples_in), _ptr(d_samples_out), _ptr(d_counts)))
         return (y1 - y0) * W * spp
@@ -857,16 +874,39 @@ class Scene:
         stored or not (out_capacity, None: the shortest output buffer).  d_out_ids, d_out_lowres (uint8 per stored child, 1 = the
         diffuse child) with MR_LEVEL_PATH.  d_counts: FIVE words, as in render_lights_environment.  flags: MR_MATH_PRODUCT,
         MR_TRACE_INCOHERENT only.  MR_LEVEL_LAST is render_lights_environment itself."""
+        self._level_lights_frame(None, cam, W, H, d_rgb, y0, y1, bands, spp, jitter, seed, tiled, flags, d_hits, d_sample_rgb,
+                                 d_sample_color, d_sample_normal, d_counts, stream, children, environment, kinds, path_seed, d_out_rays,
+                                 d_out_weights, d_out_pixels, d_out_ids, d_out_count, out_capacity, d_out_octants, d_out_lowres)
+
+    def _frame_call(self, name, fd, lens, *rest):
+        """The library's entry `name` as name(scene, frame, ...), or with lens = (aperture, focus_plane) its twin name + "_lens"
+        as twin(scene, frame, lens, ...).  This is the call site of mr_render_level_lights_lens, mr_render_recursion_lens and
+        mr_render_recursion_photons_lens."""
+        head = (C.byref(fd),) if lens is None else (C.byref(fd), C.byref(_lens_desc(*lens)))
+        _check(getattr(self.L, name if lens is None else name + "_lens")(self.h, *head, *rest))
+
+    def _level_lights_frame(self, lens, cam, W, H, d_rgb, y0, y1, bands, spp, jitter, seed, tiled, flags, d_hits, d_sample_rgb,
+                            d_sample_color, d_sample_normal, d_counts, stream, children, environment, kinds, path_seed, d_out_rays,
+                            d_out_weights, d_out_pixels, d_out_ids, d_out_count, out_capacity, d_out_octants, d_out_lowres):
+        """render_level_lights (lens None) and render_level_lights_lens: the two descriptors and the call"""
         fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
         ld = FrameLevelDesc()
         ld.children, ld.environment, ld.path_kinds, ld.path_seed = children, 1 if environment else 0, kinds, path_seed
         ld.out_capacity_lo, ld.out_capacity_hi = _out_capacity(out_capacity, d_out_rays, d_out_weights, d_out_pixels, d_out_ids,
                                                                d_out_lowres, d_out_octants)
         ld.d_out_octants, ld.d_out_lowres = _ptr(d_out_octants), _ptr(d_out_lowres)
-        _check(self.L.mr_render_level_lights(self.h, C.byref(fd), C.byref(ld), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb),
-                                             _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_out_rays), _ptr(d_out_weights),
-                                             _ptr(d_out_pixels), _ptr(d_out_ids), _ptr(d_out_count), _ptr(d_counts),
-                                             _stream_ptr(stream)))
+        self._frame_call("mr_render_level_lights", fd, lens, C.byref(ld), d_rgb.data_ptr(), _ptr(d_hits), _ptr(d_sample_rgb),
+                         _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_out_rays), _ptr(d_out_weights), _ptr(d_out_pixels),
+                         _ptr(d_out_ids), _ptr(d_out_count), _ptr(d_counts), _stream_ptr(stream))
+
+    def _recursion(self, name, lens, photon_args, cam, W, H, d_rgb, d_level_counts, depth, d_workspace, queue_capacity, y0, y1, bands,
+                   spp, jitter, seed, tiled, flags, stream, children, environment, kinds, path_seed, workspace_bytes):
+        """The four one-call recursions: the two descriptors and the call -- the entry `name` or (lens given) its _lens twin, with
+        photon_args (the two map handles, max_dist, nphotons; () without maps) between the recursion descriptor and d_rgb"""
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
+        rd = _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity)
+        self._frame_call(name, fd, lens, C.byref(rd), *photon_args, d_rgb.data_ptr(), _ptr(d_workspace),
+                         _workspace_bytes(workspace_bytes, d_workspace), d_level_counts.data_ptr(), _stream_ptr(stream))
 
     def recursion_workspace_bytes(self, depth, queue_capacity, children=MR_LEVEL_SPECULAR, environment=False,
                                   kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE):
@@ -890,12 +930,8 @@ class Scene:
         undefined environment lookups, children emitted (stored or not), 0, 0.  A level whose children exceed queue_capacity was
         truncated: read the counts once, afterwards.  d_workspace: a uint8 tensor of recursion_workspace_bytes(...) bytes (None
         for depth 0); workspace_bytes: what to declare instead of its size."""
-        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
-        rd = _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity)
-        if workspace_bytes is None:
-            workspace_bytes = 0 if d_workspace is None else d_workspace.numel() * d_workspace.element_size()
-        _check(self.L.mr_render_recursion(self.h, C.byref(fd), C.byref(rd), d_rgb.data_ptr(), _ptr(d_workspace), workspace_bytes,
-                                          d_level_counts.data_ptr(), _stream_ptr(stream)))
+        self._recursion("mr_render_recursion", None, (), cam, W, H, d_rgb, d_level_counts, depth, d_workspace, queue_capacity, y0, y1,
+                        bands, spp, jitter, seed, tiled, flags, stream, children, environment, kinds, path_seed, workspace_bytes)
 
     def recursion_photons_workspace_bytes(self, cam, W, H, depth, queue_capacity, y0=0, y1=None, bands=None, spp=1,
                                           children=MR_LEVEL_SPECULAR, environment=False,
@@ -919,14 +955,9 @@ class Scene:
         as the level kernels do.  Still one call that only enqueues, capturable after a first call outside the capture.
         d_level_counts: as in render_recursion, with word 6 of a level = the queries made there (diffuse hits).  d_workspace: a
         uint8 tensor of recursion_photons_workspace_bytes(...) bytes, needed at depth 0 too.  tiled must be False."""
-        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
-        rd = _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity)
-        if workspace_bytes is None:
-            workspace_bytes = 0 if d_workspace is None else d_workspace.numel() * d_workspace.element_size()
-        _check(self.L.mr_render_recursion_photons(self.h, C.byref(fd), C.byref(rd), global_map.h if global_map is not None else None,
-                                                  caustic_map.h if caustic_map is not None else None, max_dist, nphotons,
-                                                  d_rgb.data_ptr(), _ptr(d_workspace), workspace_bytes, d_level_counts.data_ptr(),
-                                                  _stream_ptr(stream)))
+        self._recursion("mr_render_recursion_photons", None, (_map_handle(global_map), _map_handle(caustic_map), max_dist, nphotons),
+                        cam, W, H, d_rgb, d_level_counts, depth, d_workspace, queue_capacity, y0, y1, bands, spp, jitter, seed, tiled,
+                        flags, stream, children, environment, kinds, path_seed, workspace_bytes)
 
     def render_level_lights_lens(self, cam, W, H, d_rgb, aperture, focus_plane, y0=0, y1=None, bands=None, spp=1, jitter=False, seed=168,
                                  tiled=False, flags=0, d_hits=None, d_sample_rgb=None, d_sample_color=None, d_sample_normal=None,
@@ -939,18 +970,9 @@ class Scene:
         makes for it for the same window, seed, spp and lens without d_samples_in; every output and counter is what the batched
         calls write for those rays, the children the set trace_level_lights[_path] emits on that queue.  MR_LEVEL_LAST runs this
         call's own kernels.  tiled must be False; every other argument is render_level_lights'."""
-        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
-        lens = LensDesc()
-        lens.aperture, lens.focus_plane = aperture, focus_plane
-        ld = FrameLevelDesc()
-        ld.children, ld.environment, ld.path_kinds, ld.path_seed = children, 1 if environment else 0, kinds, path_seed
-        ld.out_capacity_lo, ld.out_capacity_hi = _out_capacity(out_capacity, d_out_rays, d_out_weights, d_out_pixels, d_out_ids,
-                                                               d_out_lowres, d_out_octants)
-        ld.d_out_octants, ld.d_out_lowres = _ptr(d_out_octants), _ptr(d_out_lowres)
-        _check(self.L.mr_render_level_lights_lens(self.h, C.byref(fd), C.byref(lens), C.byref(ld), d_rgb.data_ptr(), _ptr(d_hits),
-                                                  _ptr(d_sample_rgb), _ptr(d_sample_color), _ptr(d_sample_normal), _ptr(d_out_rays),
-                                                  _ptr(d_out_weights), _ptr(d_out_pixels), _ptr(d_out_ids), _ptr(d_out_count),
-                                                  _ptr(d_counts), _stream_ptr(stream)))
+        self._level_lights_frame((aperture, focus_plane), cam, W, H, d_rgb, y0, y1, bands, spp, jitter, seed, tiled, flags, d_hits,
+                                 d_sample_rgb, d_sample_color, d_sample_normal, d_counts, stream, children, environment, kinds, path_seed,
+                                 d_out_rays, d_out_weights, d_out_pixels, d_out_ids, d_out_count, out_capacity, d_out_octants, d_out_lowres)
 
     def render_recursion_lens(self, cam, W, H, d_rgb, d_level_counts, depth, aperture, focus_plane, d_workspace=None, queue_capacity=0,
                               y0=0, y1=None, bands=None, spp=1, jitter=False, seed=168, tiled=False, flags=0, stream=None,
@@ -958,14 +980,9 @@ class Scene:
                               path_seed=168, workspace_bytes=None):
         """mr_render_recursion_lens: render_recursion whose level 0 is render_level_lights_lens (depth 0: with MR_LEVEL_LAST); the
         further levels, the counters and the workspace (recursion_workspace_bytes) are render_recursion's.  tiled must be False."""
-        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
-        lens = LensDesc()
-        lens.aperture, lens.focus_plane = aperture, focus_plane
-        rd = _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity)
-        if workspace_bytes is None:
-            workspace_bytes = 0 if d_workspace is None else d_workspace.numel() * d_workspace.element_size()
-        _check(self.L.mr_render_recursion_lens(self.h, C.byref(fd), C.byref(lens), C.byref(rd), d_rgb.data_ptr(), _ptr(d_workspace),
-                                               workspace_bytes, d_level_counts.data_ptr(), _stream_ptr(stream)))
+        self._recursion("mr_render_recursion", (aperture, focus_plane), (), cam, W, H, d_rgb, d_level_counts, depth, d_workspace,
+                        queue_capacity, y0, y1, bands, spp, jitter, seed, tiled, flags, stream, children, environment, kinds, path_seed,
+                        workspace_bytes)
 
     def render_recursion_photons_lens(self, cam, W, H, d_rgb, d_level_counts, depth, global_map, caustic_map, d_workspace, aperture,
                                       focus_plane, queue_capacity=0, max_dist=1e10, nphotons=500, y0=0, y1=None, bands=None, spp=1,
@@ -974,25 +991,16 @@ class Scene:
                                       workspace_bytes=None):
         """mr_render_recursion_photons_lens: render_recursion_photons whose level 0 is render_level_lights_lens and whose level-0
         queries are formed from the lens ray of each sample; the workspace is recursion_photons_workspace_bytes'."""
-        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
-        lens = LensDesc()
-        lens.aperture, lens.focus_plane = aperture, focus_plane
-        rd = _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity)
-        if workspace_bytes is None:
-            workspace_bytes = 0 if d_workspace is None else d_workspace.numel() * d_workspace.element_size()
-        _check(self.L.mr_render_recursion_photons_lens(self.h, C.byref(fd), C.byref(lens), C.byref(rd),
-                                                       global_map.h if global_map is not None else None,
-                                                       caustic_map.h if caustic_map is not None else None, max_dist, nphotons,
-                                                       d_rgb.data_ptr(), _ptr(d_workspace), workspace_bytes, d_level_counts.data_ptr(),
-                                                       _stream_ptr(stream)))
+        self._recursion("mr_render_recursion_photons", (aperture, focus_plane),
+                        (_map_handle(global_map), _map_handle(caustic_map), max_dist, nphotons), cam, W, H, d_rgb, d_level_counts, depth,
+                        d_workspace, queue_capacity, y0, y1, bands, spp, jitter, seed, tiled, flags, stream, children, environment, kinds,
+                        path_seed, workspace_bytes)
 
     def final_gather(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb, max_dist=1e10, nphotons=500,
                      spp=1, stream=None):
         """Scene.cpp:285-299: irradiance + caustic estimate at every diffuse hit, added to the pixels."""
-        _check(self.L.mr_final_gather(self.h, global_map.h if global_map is not None else None,
-                                      caustic_map.h if caustic_map is not None else None, d_rays.data_ptr(),
-                                      d_hits.data_ptr(), n, max_dist, nphotons, spp, d_scratch.data_ptr(), d_rgb.data_ptr(),
-                                      _stream_ptr(stream)))
+        _check(self.L.mr_final_gather(self.h, _map_handle(global_map), _map_handle(caustic_map), d_rays.data_ptr(), d_hits.data_ptr(), n,
+                                      max_dist, nphotons, spp, d_scratch.data_ptr(), d_rgb.data_ptr(), _stream_ptr(stream)))
 
     def gather_level(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb=None, d_normal=None, d_weights=None,
                      d_pixels=None, max_dist=1e10, nphotons=500, spp=1, d_ray_rgb=None, d_counts=None, stream=None):
@@ -1003,10 +1011,9 @@ class Scene:
         or hit_surface's [n, 3] buffer (required on a scene with a procedural texture).  d_scratch: 12 * n floats, whose
         layout is documented (positions, normals with NaN = no query, the two estimates).  d_counts[0] += queries,
         d_counts[1] += rays."""
-        _check(self.L.mr_gather_level(self.h, global_map.h if global_map is not None else None,
-                                      caustic_map.h if caustic_map is not None else None, _ptr(d_rays), _ptr(d_hits),
-                                      _ptr(d_normal), _ptr(d_weights), _ptr(d_pixels), n, max_dist, nphotons, spp, _ptr(d_scratch),
-                                      _ptr(d_rgb), _ptr(d_ray_rgb), _ptr(d_counts), _stream_ptr(stream)))
+        _check(self.L.mr_gather_level(self.h, _map_handle(global_map), _map_handle(caustic_map), _ptr(d_rays), _ptr(d_hits), _ptr(d_normal),
+                                      _ptr(d_weights), _ptr(d_pixels), n, max_dist, nphotons, spp, _ptr(d_scratch), _ptr(d_rgb),
+                                      _ptr(d_ray_rgb), _ptr(d_counts), _stream_ptr(stream)))
 
     def trace_photons(self, photon_map, light, target, max_emissions, caustic=False, seed=168, max_depth=0, round_emissions=0,
                       d_records=None, records_capacity=None, stream=None, surface=False, resident=False):

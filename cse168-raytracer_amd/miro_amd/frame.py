@@ -233,26 +233,61 @@ class Queue(collections.namedtuple("Queue", "rays weights pixels ids octs n low"
 NO_QUEUE = Queue(None, None, None, None, None, 0)
 
 
-# render_specular's routes through the thin lens, and the pinhole route each of them is in every other respect
-LENS_ROUTES = {"frame_lens": "frame_lights", "frame_lens_path": "frame_lights_path", "device_lens": "device_lights",
-               "device_lens_path": "device_lights_path", "device_lens_photons": "device_photons",
-               "device_lens_photons_path": "device_photons_path"}
+# One value of render_specular's `fused` as independent choices.
+# driver: who runs level 0 and the loop -- "queue" (generate()'s rays, one step per level), "frame" (_frame_level0, then
+# _level_lights) or "device" (_device_levels: one library call);
+# level: the level form -- "batched", "point" (mr_trace_level), "auto" (point where the queue hits, else batched) or "lights"
+# (mr_trace_level_lights / _path); besides, "unlisted" for a truthy `fused` outside the table (route_of): checked like "point",
+# run like "batched";
+# path: the _path kernel form of "lights" (the batched path takes it from path_tracing); lens: level 0 goes through the thin
+# lens; photons: the maps go into the one device call.
+Route = collections.namedtuple("Route", "driver level path lens photons", defaults=(False, False, False))
+
+# every accepted value of `fused`; this table is the only place that knows the strings
+ROUTES = {
+    False: Route("queue", "batched"),
+    True: Route("queue", "point"),
+    "auto": Route("queue", "auto"),
+    "lights": Route("queue", "lights"),
+    "lights_path": Route("queue", "lights", path=True),
+    "frame_lights": Route("frame", "lights"),
+    "frame_lights_path": Route("frame", "lights", path=True),
+    "device_lights": Route("device", "lights"),
+    "device_lights_path": Route("device", "lights", path=True),
+    "device_photons": Route("device", "lights", photons=True),
+    "device_photons_path": Route("device", "lights", path=True, photons=True),
+    "frame_lens": Route("frame", "lights", lens=True),
+    "frame_lens_path": Route("frame", "lights", path=True, lens=True),
+    "device_lens": Route("device", "lights", lens=True),
+    "device_lens_path": Route("device", "lights", path=True, lens=True),
+    "device_lens_photons": Route("device", "lights", lens=True, photons=True),
+    "device_lens_photons_path": Route("device", "lights", path=True, lens=True, photons=True),
+}
+ROUTES_BY_FIELDS = {route: name for name, route in ROUTES.items()}      # a route's name, as the messages print it
+QUEUE_FORM = dict(driver="queue", lens=False, photons=False)            # the fields that make a route its per-level sibling
+
+
+def route_of(fused):
+    """ROUTES[fused].  A value outside the table keeps what it always did: a falsy one is the batched path; any other passes
+    mr_trace_level's checks as a truthy `fused` and then runs the batched steps (level "unlisted")."""
+    if isinstance(fused, (bool, str)) and fused in ROUTES:
+        return ROUTES[fused]
+    return Route("queue", "unlisted" if fused else "batched")
 
 
 class LevelPlan(collections.namedtuple("LevelPlan", (
-        "stream", "flags", "fused", "path_tracing", "path_kinds", "fan", "path_seed", "group_octants", "lights", "environment",
+        "stream", "flags", "route", "path_tracing", "path_kinds", "fan", "path_seed", "group_octants", "lights", "environment",
         "env_lowres", "surface", "square", "square_lights", "surface_children", "photon_maps", "nphotons", "max_dist", "lens"))):
     """What FrameRenderer.render_specular decides once per call, from its arguments and the scene's state (_resolve):
     stream: the torch Stream of every launch, None for the current one; flags: the renderer's trace flags;
-    fused: False / True / "auto", already False on a scene with a texture table, or "lights" (every level is one
-    mr_trace_level_lights, on any scene) or "lights_path" (every level is one mr_trace_level_lights_path: path tracing);
+    route: the Route of `fused`; its level is already "batched" where a scene with a texture table turned "point" or "auto" away;
     path_tracing, path_kinds (never None), fan (children per ray, at most), path_seed, group_octants: as given;
     lights: the scene's light list shades, not the description's point light; environment: misses are shaded, after the
     first level with env_lowres (MR_ENV_LOWRES or 0);
     surface: the scene has a procedural texture, so shading reads the surface pass's colour and normal;
     square: None, "plain" (mr_shade_square_lights) or "surface" (any texture table), for square_lights;
     surface_children: the path tracer's children come from mr_gen_path_rays_surface;
-    photon_maps: None or (global, caustic), gathered with nphotons / max_dist."""
+    photon_maps: None or (global, caustic), gathered with nphotons / max_dist; lens: the renderer's lens on a lens route, else None."""
     __slots__ = ()
 
     def surface_pass(self, last):
@@ -486,67 +521,89 @@ class FrameRenderer:
         mr_hit_surface just filled (the bumped normal, Scene.cpp:290), otherwise the object's normal.  The scratch (12 floats per
         ray) is allocated with the level's other buffers.  `fused` must be falsy: mr_trace_level keeps no hit records.  None: no
         launch is added.
-        fused="lights": every level is ONE launch of mr_trace_level_lights on ANY scene -- trace, the environment of a miss, the
-        surface step (texture table or none, bumped normal), the loop over the light list, weight x L to the pixel, the specular
-        children -- where the batched path runs trace -> mr_shade_environment -> mr_hit_surface -> mr_shade_lights[_surface] ->
-        mr_gen_secondary_rays.  It needs lights=[...], takes environment= in every form and photon_maps= (the launch then also
-        writes the level's hit records, and bumped normals on a procedural scene, and mr_gather_level follows it), and raises
-        ValueError with path_tracing, square lights, group_octants or surface_children=True.  The same rays, children and counts;
-        the pixel sums differ by the order of the float atomics.  Opt-in: fused="auto" never chooses it (a level whose rays rarely
-        hit runs its light loop at that lane utilisation; DESIGN section 5c has the times).
-        fused="lights_path": the same for a PATH_TRACING build: every level is ONE launch of mr_trace_level_lights_path, whose
-        children are those of mr_gen_path_rays_surface (about the bumped normal, the diffuse child with the looked-up colour) --
-        the batched path with surface_children=True.  It needs lights=[...] and path_tracing=True, takes environment=,
-        photon_maps=, path_seed and path_kinds, and raises ValueError with square lights, group_octants or surface_children=False.
-        Its queues carry the ray ids and, with an environment, one byte per ray that marks the children of Ray::random: a miss
-        of such a ray reads the low-res image, so an environment IMAGE with MR_PATH_DIFFUSE mixed with other kinds is accepted
-        on this route.  Opt-in as well.
-        fused="frame_lights" | "frame_lights_path": "lights" / "lights_path" whose level 0 is ONE mr_render_level_lights straight
-        into d_rgb -- the fused frame that also writes the rays of level 1: no generate(), no zeroing of the pixels, no eye-ray
-        buffer, no atomics at level 0 (its pixels are deterministic) and no untile pass (the children's pixels index d_rgb, in
-        image order, also with tiled=True) -- and whose levels >= 1 are mr_trace_level_lights / _path on the children, adding
-        into d_rgb.  The checks of "lights" / "lights_path", and ValueError besides for lens eye rays (the batched path), more
-        than one band range (fused="lights" / "lights_path") and photon_maps with tiled=True (tiled=False, or "lights" /
-        "lights_path").  With photon_maps (image order) generate() runs as well, for mr_gather_level's level 0; without them a
-        FrameRenderer(resident_rays=False) serves.  The same rays, children and counts per level; level 0's pixel means are
-        pairwise sums where "lights" adds atomically.  Opt-in as well: fused="auto" never chooses them.
-        fused="device_lights" | "device_lights_path": the frame of "frame_lights" / "frame_lights_path" as ONE library call,
-        mr_render_recursion, followed by ONE read of its counters: level 0 as there, every further level one kernel that reads the
-        length of its queue from the count the level before left on the device.  No read-back, allocation or torch op between
-        the levels (Scene.render_recursion alone can be captured into a graph).  The checks of those routes, and ValueError
-        besides with photon_maps ("frame_lights" / "frame_lights_path": mr_gather_level takes its n from the host).
-        queue_capacity: rays per queue, None: fan x samples (3 specular, 4 path traced), which always holds level 1; a level that
-        emits more children than that is truncated, and the call raises RuntimeError naming the level, its children and the
-        capacity (fan^depth x samples can never be exceeded).  The workspace (two queues) and the counters are allocated on
-        first use and kept (bytes_resident counts them).  The same rays, children and counts per level as "frame_lights[_path]",
-        cut at the first level with 0 rays; the pixel sums of levels >= 1 differ by the order of the float atomics.  Opt-in as
-        well.
-        fused="device_photons" | "device_photons_path": "device_lights" / "device_lights_path" WITH photon_maps=(global, caustic), as
-        ONE mr_render_recursion_photons and one read of its counters: after every level the photon-map term of that level's queue
-        (mr_gather_level's queries, estimates and adds) by kernels that read the queue's length from the device too.  nphotons,
-        max_dist and queue_capacity as above; the workspace also holds a level's hit records, normals and the scratch of the
-        estimates.  ValueError without photon_maps, with tiled=True ("lights" / "lights_path", or tiled=False), and with what
-        "device_lights" refuses.  The same rays, children, queries and counts per level as "frame_lights[_path]" with the same
-        maps; pixel sums differ by the order of the float atomics.  Opt-in as well.
-        fused="frame_lens" | "frame_lens_path": "frame_lights" / "frame_lights_path" of a FrameRenderer(lens=dict(aperture=...,
-        focus_plane=...)): level 0 is ONE mr_render_level_lights_lens, the fused frame whose eye rays go through the thin lens
-        (Camera::eyeRay under -DDOF, the rays generate() makes for the same lens, made in registers), the further levels are
-        mr_trace_level_lights / _path as there.  With photon_maps generate() runs for mr_gather_level's level 0: it already makes
-        lens rays.  Every check of the pinhole twin, and ValueError besides without a lens (naming the pinhole route) and with
-        tiled=True.  The same rays, children and counts per level as the batched lens frame (fused="lights" / "lights_path").
-        fused="device_lens" | "device_lens_path": that frame as ONE mr_render_recursion_lens and one read of its counters, as
-        "device_lights" / "device_lights_path"; the same checks, queue_capacity, workspace and truncation rule.
-        fused="device_lens_photons" | "device_lens_photons_path": ONE mr_render_recursion_photons_lens with photon_maps, as
-        "device_photons" / "device_photons_path".  All six are opt-in: fused="auto" never chooses them, and the pinhole routes go
-        on refusing a lens."""
+        The routes.  Besides False, True and "auto", `fused` takes 14 strings.  Each is one combination of five independent
+        choices, the fields of frame.Route; frame.ROUTES is the table at the end.  All 14 are opt-in: fused="auto" never chooses
+        one (a level whose rays rarely hit runs its light loop at that lane utilisation; DESIGN section 5c has the times).
+        driver -- who runs level 0 and the loop:
+          "queue": generate()'s eye rays are level 0's queue, d_slots is zeroed, one step per level (the level form below), each
+            with its counters and queue allocated before it and its child count read back after it, then the untile pass.  It
+            needs the resident ray buffers, and serves a lens (generate() makes lens rays), tiled=True and any number of band ranges.
+          "frame": level 0 is ONE mr_render_level_lights straight into d_rgb -- the fused frame that also writes the rays of level 1:
+            no generate(), no zeroing of the pixels, no eye-ray buffer, no atomics at level 0 (its pixels are deterministic) and no
+            untile pass (the children's pixels index d_rgb, in image order, also with tiled=True) -- and the levels >= 1 are
+            mr_trace_level_lights / _path on the children, adding into d_rgb.  One window per call: ValueError for more than one
+            band range (the "queue" driver takes them).  photon_maps= are taken (image order only: ValueError with tiled=True, which
+            needs tiled=False or the "queue" driver): generate() then runs as well, for mr_gather_level's level 0; without maps a
+            FrameRenderer(resident_rays=False) serves.  The same rays, children and counts per level as the "queue" driver; level 0's
+            pixel means are pairwise sums where that one adds atomically.
+          "device": that frame as ONE library call, mr_render_recursion, followed by ONE read of its counters: level 0 as there,
+            every further level one kernel that reads the length of its queue from the count the level before left on the device.
+            No read-back, allocation or torch op between the levels (Scene.render_recursion alone can be captured into a graph); a
+            FrameRenderer(resident_rays=False) serves.  The checks of "frame", and ValueError besides with photon_maps unless
+            photons is set (the "frame" driver takes them: mr_gather_level takes its n from the host).
+            queue_capacity: rays per queue, None: fan x samples (3 specular, 4 path traced), which always holds level 1; a level that
+            emits more children than that is truncated, and the call raises RuntimeError naming the level, its children and the
+            capacity (fan^depth x samples can never be exceeded).  The workspace (two queues) and the counters are allocated on
+            first use and kept (bytes_resident counts them).  The same rays, children and counts per level as the "frame" driver,
+            cut at the first level with 0 rays; the pixel sums of levels >= 1 differ by the order of the float atomics.
+        level -- the form of a level ("frame" and "device" exist for "lights" only):
+          "batched" (False), "point" (True: mr_trace_level, one point light) and "auto": above.  A truthy value outside the table
+            is "unlisted": it passes the checks of "point" and then runs the batched steps; a falsy one is "batched".
+          "lights": every level is ONE launch of mr_trace_level_lights on ANY scene -- trace, the environment of a miss, the surface
+            step (texture table or none, bumped normal), the loop over the light list, weight x L to the pixel, the specular children
+            -- where the batched path runs trace -> mr_shade_environment -> mr_hit_surface -> mr_shade_lights[_surface] ->
+            mr_gen_secondary_rays.  It needs lights=[...], takes environment= in every form and photon_maps= (the launch then also
+            writes the level's hit records, and bumped normals on a procedural scene, and mr_gather_level follows it), and raises
+            ValueError with path_tracing, square lights, group_octants or surface_children=True.  The same rays, children and counts
+            as the batched path; the pixel sums differ by the order of the float atomics.
+        path -- the same for a PATH_TRACING build: every level is ONE launch of mr_trace_level_lights_path, whose children are those
+          of mr_gen_path_rays_surface (about the bumped normal, the diffuse child with the looked-up colour) -- the batched path with
+          surface_children=True.  It needs lights=[...] and path_tracing=True, takes environment=, photon_maps=, path_seed and
+          path_kinds, and raises ValueError with square lights, group_octants or surface_children=False.  Its queues carry the ray
+          ids and, with an environment, one byte per ray that marks the children of Ray::random: a miss of such a ray reads the
+          low-res image, so an environment IMAGE with MR_PATH_DIFFUSE mixed with other kinds is accepted on these routes.
+        lens -- the "frame" or "device" driver of a FrameRenderer(lens=dict(aperture=..., focus_plane=...)): level 0 is ONE
+          mr_render_level_lights_lens (inside the one call: mr_render_recursion_lens, mr_render_recursion_photons_lens), the fused
+          frame whose eye rays go through the thin lens (Camera::eyeRay under -DDOF, the rays generate() makes for the same lens,
+          made in registers); the further levels, the checks, queue_capacity, the workspace and the truncation rule are the pinhole
+          twin's.  With photon_maps on the "frame" driver generate() runs for mr_gather_level's level 0: it already makes lens rays.
+          ValueError besides without a lens (naming the pinhole route) and with tiled=True; the pinhole routes go on refusing a lens
+          (the batched path or the "queue" driver takes it).  The same rays, children and counts per level as the batched lens
+          frame (fused="lights" / "lights_path").
+        photons -- the "device" driver WITH photon_maps=(global, caustic), as ONE mr_render_recursion_photons and one read of its
+          counters: after every level the photon-map term of that level's queue (mr_gather_level's queries, estimates and adds) by
+          kernels that read the queue's length from the device too.  nphotons, max_dist and queue_capacity as above; the workspace
+          also holds a level's hit records, normals and the scratch of the estimates.  ValueError without photon_maps (naming the
+          route without photons), with tiled=True ("lights" / "lights_path", or tiled=False), and with what the "device" driver
+          refuses.  The same rays, children, queries and counts per level as the "frame" driver with the same maps; pixel sums
+          differ by the order of the float atomics.
+          fused                        driver  level    path lens photons  refuses (ValueError), besides a missing light list
+          False                        queue   batched  -    -    -        (what each option above says)
+          True                         queue   point    -    -    -        photon_maps, surface_children, environment, lights, square lights
+          "auto"                       queue   auto     -    -    -        as True
+          "lights"                     queue   lights   -    -    -        path_tracing, square lights, group_octants, surface_children=True
+          "lights_path"                queue   lights   yes  -    -        no path_tracing, square lights, group_octants, surface_children=False
+          "frame_lights"               frame   lights   -    -    -        as "lights"; a lens, two band ranges, maps with tiled=True
+          "frame_lights_path"          frame   lights   yes  -    -        as "lights_path"; the same three
+          "device_lights"              device  lights   -    -    -        as "frame_lights"; photon_maps
+          "device_lights_path"         device  lights   yes  -    -        as "frame_lights_path"; photon_maps
+          "device_photons"             device  lights   -    -    yes      as "frame_lights"; no photon_maps, tiled=True
+          "device_photons_path"        device  lights   yes  -    yes      as "frame_lights_path"; no photon_maps, tiled=True
+          "frame_lens"                 frame   lights   -    yes  -        as "frame_lights" but for the lens; no lens, tiled=True
+          "frame_lens_path"            frame   lights   yes  yes  -        as "frame_lights_path" but for the lens; no lens, tiled=True
+          "device_lens"                device  lights   -    yes  -        as "device_lights" but for the lens; no lens, tiled=True
+          "device_lens_path"           device  lights   yes  yes  -        as "device_lights_path" but for the lens; no lens, tiled=True
+          "device_lens_photons"        device  lights   -    yes  yes      as "device_photons" but for the lens; no lens
+          "device_lens_photons_path"   device  lights   yes  yes  yes      as "device_photons_path" but for the lens; no lens
+        On a scene with a texture table True and "auto" are False (above); the 14 strings are unchanged by it."""
         plan = self._resolve(stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights, environment, photon_maps,
                              nphotons, max_dist, surface_children)
         # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
         # each other on torch's current stream, so a torch Stream is made current here
         with contextlib.nullcontext() if stream is None else torch.cuda.stream(stream):
-            if plan.fused in ("frame_lights", "frame_lights_path"):
+            if plan.route.driver == "frame":
                 return self._frame_levels(plan, depth)
-            if plan.fused in ("device_lights", "device_lights_path", "device_photons", "device_photons_path"):
+            if plan.route.driver == "device":
                 return self._device_levels(plan, depth, queue_capacity)
             self._need_rays("render_specular(fused=%r)" % (fused,))
             self.d_slots.zero_()
@@ -555,10 +612,9 @@ class FrameRenderer:
             for level in range(depth + 1):
                 if queue.n == 0:
                     break
-                one_launch = plan.fused is True or (plan.fused == "auto" and
-                                                    (level == 0 or per_level[-1][1] >= 0.9 * per_level[-1][0]))
-                step = self._level_lights if plan.fused in ("lights", "lights_path") else \
-                    self._level_fused if one_launch else self._level_batched
+                form = plan.route.level
+                one_launch = form == "point" or (form == "auto" and (level == 0 or per_level[-1][1] >= 0.9 * per_level[-1][0]))
+                step = self._level_lights if form == "lights" else self._level_fused if one_launch else self._level_batched
                 counts, queue = step(plan, queue, level, level == depth)
                 per_level.append(counts)
             self._untile(stream)
@@ -568,68 +624,57 @@ class FrameRenderer:
                  nphotons, max_dist, surface_children):
         """render_specular's arguments and the scene's state as a LevelPlan: every check, and the two scene setters
         (set_environment, set_lights) between them"""
-        sc = self.scene
-        lens_route = fused if isinstance(fused, str) and fused in LENS_ROUTES else None
-        if lens_route:
-            # the pinhole twin's route with the lens calls at level 0: its checks hold, under this route's name
+        sc, route, maps = self.scene, route_of(fused), photon_maps is not None
+        name = lambda **changed: ROUTES_BY_FIELDS[route._replace(**changed)]   # noqa: E731  the route's name, or a sibling's
+        if route.lens:
             if self.lens is None:
                 raise ValueError("render_specular: fused=\"%s\" needs FrameRenderer(lens=dict(aperture=..., focus_plane=...)); "
-                                 "the pinhole frame is fused=\"%s\"" % (lens_route, LENS_ROUTES[lens_route]))
+                                 "the pinhole frame is fused=\"%s\"" % (name(), name(lens=False)))
             if self.tiled:
-                raise ValueError("render_specular: fused=\"%s\" needs tiled=False (lens eye rays come in image order only)" % lens_route)
-            fused = LENS_ROUTES[lens_route]
-        frame_route = fused if isinstance(fused, str) and fused in ("frame_lights", "frame_lights_path", "device_lights",
-                                                                    "device_lights_path", "device_photons",
-                                                                    "device_photons_path") else None
-        if frame_route:
-            # level 0 is mr_render_level_lights: one window of pinhole eye rays, whose children carry image-order pixels
-            level_route = "lights_path" if frame_route.endswith("_path") else "lights"
-            shown = lens_route or frame_route
-            if frame_route.startswith("device_photons"):
-                if photon_maps is None:
-                    raise ValueError("render_specular: fused=\"%s\" needs photon_maps=(global, caustic); without maps the frame is "
-                                     "fused=\"device_%s\"" % (shown, "lens" + level_route[6:] if lens_route else level_route))
-                if self.tiled:
-                    raise ValueError("render_specular: photon_maps with tiled=True need fused=\"%s\" (or tiled=False), not "
-                                     "fused=\"%s\" (mr_render_recursion_photons finds level 0's pixels from the sample index, in "
-                                     "image order)" % (level_route, shown))
-            if frame_route.startswith("device_lights") and photon_maps is not None:
-                raise ValueError("render_specular: photon_maps need fused=\"frame_%s\", not fused=\"%s\" (mr_gather_level takes the "
-                                 "length of its queue from the host)" % ("lens" + level_route[6:] if lens_route else level_route, shown))
-            if self.lens is not None and not lens_route:
+                raise ValueError("render_specular: fused=\"%s\" needs tiled=False (lens eye rays come in image order only)" % name())
+        if route.driver != "queue":
+            # level 0 is mr_render_level_lights[_lens]: one window of eye rays, whose children carry image-order pixels
+            if route.photons and not maps:
+                raise ValueError("render_specular: fused=\"%s\" needs photon_maps=(global, caustic); without maps the frame is "
+                                 "fused=\"%s\"" % (name(), name(photons=False)))
+            if route.photons and self.tiled:
+                raise ValueError("render_specular: photon_maps with tiled=True need fused=\"%s\" (or tiled=False), not "
+                                 "fused=\"%s\" (mr_render_recursion_photons finds level 0's pixels from the sample index, in "
+                                 "image order)" % (name(**QUEUE_FORM), name()))
+            if route.driver == "device" and maps and not route.photons:
+                raise ValueError("render_specular: photon_maps need fused=\"%s\", not fused=\"%s\" (mr_gather_level takes the "
+                                 "length of its queue from the host)" % (name(driver="frame"), name()))
+            if self.lens is not None and not route.lens:
                 raise ValueError("render_specular: lens eye rays need the batched path (fused=False), not fused=\"%s\" "
-                                 "(mr_render_level_lights makes pinhole eye rays)" % frame_route)
+                                 "(mr_render_level_lights makes pinhole eye rays)" % name())
             if len(self.bands) > 1:
                 raise ValueError("render_specular: more than one band range needs fused=\"%s\", not fused=\"%s\" "
-                                 "(mr_render_level_lights renders one window per call)" % (level_route, shown))
-            if photon_maps is not None and self.tiled:
+                                 "(mr_render_level_lights renders one window per call)" % (name(**QUEUE_FORM), name()))
+            if maps and self.tiled:
                 raise ValueError("render_specular: photon_maps with tiled=True need fused=\"%s\" (or tiled=False), not fused=\"%s\" "
-                                 "(mr_gather_level finds level 0's pixels from the ray index, in image order)" % (level_route, shown))
-            if photon_maps is not None and frame_route.startswith("frame_"):
-                self._need_rays("render_specular(fused=\"%s\", photon_maps=...)" % shown)
-            fused = level_route                 # the checks of that route hold here too; the plan carries the frame route
-        level_route = fused if isinstance(fused, str) and fused in ("lights", "lights_path") else None
-        if level_route:
-            path = level_route == "lights_path"
-            call = "mr_trace_level_lights_path" if path else "mr_trace_level_lights"
+                                 "(mr_gather_level finds level 0's pixels from the ray index, in image order)" % (name(**QUEUE_FORM), name()))
+            if maps and route.driver == "frame":
+                self._need_rays("render_specular(fused=\"%s\", photon_maps=...)" % name())
+        if route.level == "lights":
+            call = "mr_trace_level_lights_path" if route.path else "mr_trace_level_lights"
             if lights is None:
                 raise ValueError("render_specular: fused=\"%s\" needs lights=[...] (%s shades by the scene's light list)"
-                                 % (level_route, call))
-            if path and not path_tracing:
-                raise ValueError("render_specular: fused=\"lights_path\" needs path_tracing=True (the specular children are "
-                                 "fused=\"lights\")")
-            refused = [("path_tracing", path_tracing and not path), ("square lights", self.square_lights),
-                       ("group_octants", group_octants), ("surface_children=%s" % (not path), surface_children is (not path))]
+                                 % (name(**QUEUE_FORM), call))
+            if route.path and not path_tracing:
+                raise ValueError("render_specular: fused=\"%s\" needs path_tracing=True (the specular children are fused=\"%s\")"
+                                 % (name(**QUEUE_FORM), name(path=False, **QUEUE_FORM)))
+            refused = [("path_tracing", path_tracing and not route.path), ("square lights", self.square_lights),
+                       ("group_octants", group_octants), ("surface_children=%s" % (not route.path), surface_children is (not route.path))]
             for what, given in refused:
                 if given:
                     raise ValueError("render_specular: %s needs the batched path, not fused=\"%s\" (%s emits the %s and shades point "
-                                     "and disc lights only)" % (what, level_route, call,
-                                                                "children of mr_gen_path_rays_surface" if path else "specular children"))
-            fused = False                       # the checks below speak of mr_trace_level; the plan carries the route
-        if sc.n_textures:
-            fused = False
+                                     "and disc lights only)" % (what, name(**QUEUE_FORM), call,
+                                                                "children of mr_gen_path_rays_surface" if route.path else "specular children"))
+        if sc.n_textures and route.level != "lights":
+            route = ROUTES[False]                       # mr_trace_level refuses a texture table
+        point = route.level in ("point", "auto", "unlisted")    # the checks below speak of mr_trace_level
         if photon_maps is not None:
-            if fused:
+            if point:
                 raise ValueError("render_specular: photon maps need fused=False (mr_trace_level keeps no hit records)")
             global_map, caustic_map = photon_maps
             photon_maps = (global_map, caustic_map)
@@ -640,18 +685,18 @@ class FrameRenderer:
             raise ValueError("render_specular: surface_children=False with MR_PATH_DIFFUSE on a scene with a procedural texture "
                              "(mr_gen_path_rays bounces about the un-bumped normal and refuses the scene)")
         surface_children = bool(surface_children) and path_tracing
-        if surface_children and fused:
+        if surface_children and point:
             raise ValueError("render_specular: surface_children needs fused=False (mr_trace_level keeps no hit records)")
         env_lowres = 0
         if environment is not None and environment is not False:
-            if fused:
+            if point:
                 raise ValueError("render_specular: an environment needs fused=False (mr_trace_level keeps no hit records)")
             if environment is not True:
                 sc.set_environment(**environment)
             has_image = sc.get_environment(0)[0] is not None
             kinds = binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT if path_kinds is None else path_kinds
             diffuse_children = path_tracing and bool(kinds & binding.MR_PATH_DIFFUSE)
-            if has_image and diffuse_children and kinds != binding.MR_PATH_DIFFUSE and level_route != "lights_path":
+            if has_image and diffuse_children and kinds != binding.MR_PATH_DIFFUSE and not (route.level == "lights" and route.path):
                 raise ValueError("render_specular: an environment image with MR_PATH_DIFFUSE mixed with other kinds "
                                  "(the queue does not record which child came from Ray::random)")
             if diffuse_children and kinds == binding.MR_PATH_DIFFUSE:
@@ -660,21 +705,21 @@ class FrameRenderer:
         else:
             environment = False
         if lights is not None:
-            if fused:
+            if point:
                 raise ValueError("render_specular: a light list needs fused=False (mr_trace_level shades by one point light)")
             sc.set_lights(lights)
-        if self.square_lights and fused:
+        if self.square_lights and point:
             raise ValueError("render_specular: square lights need fused=False (mr_trace_level keeps no hit records)")
         if stream is not None and not isinstance(stream, torch.cuda.Stream):
             raise TypeError("render_specular: pass a torch.cuda.Stream (or None for the current stream), not a raw handle")
         # square lights on a texture table of any kind read the surface pass's buffers (mr_shade_square_lights refuses the table)
         square = None if not self.square_lights else "surface" if sc.n_textures else "plain"
-        return LevelPlan(stream=stream, flags=self.flags, fused=frame_route or level_route or fused, path_tracing=path_tracing,
+        return LevelPlan(stream=stream, flags=self.flags, route=route, path_tracing=path_tracing,
                          path_kinds=binding.MR_PATH_MIRROR | binding.MR_PATH_REFRACT if path_kinds is None else path_kinds,
                          fan=4 if path_tracing else 3, path_seed=path_seed, group_octants=group_octants, lights=lights is not None,
                          environment=environment, env_lowres=env_lowres, surface=surface, square=square,
                          square_lights=self.square_lights, surface_children=surface_children, photon_maps=photon_maps,
-                         nphotons=nphotons, max_dist=max_dist, lens=self.lens if lens_route else None)
+                         nphotons=nphotons, max_dist=max_dist, lens=self.lens if route.lens else None)
 
     def _children(self, plan, n):
         """The buffers for the children of a level of n rays, at most plan.fan each: ids under path tracing only, octant bytes
@@ -748,7 +793,7 @@ class FrameRenderer:
         return (q.n, host[1]), None if last else out.first(host[5])
 
     def _frame_levels(self, plan, depth):
-        """fused="frame_lights" | "frame_lights_path": level 0 as _frame_level0, the further levels as _level_lights on its
+        """The "frame" driver: level 0 as _frame_level0, the further levels as _level_lights on its
         children, adding into d_rgb; returns (rays, shadow rays) per level."""
         if self.n == 0 or depth < 0:
             return []
@@ -761,19 +806,31 @@ class FrameRenderer:
             per_level.append(counts)
         return per_level
 
+    def _eye_call(self, plan, name):
+        """A Scene call that makes level 0's eye rays for the renderer's one window, as (method, lens, keywords).  The pinhole or
+        lens choice: Scene's method `name` and lens = (), or on a lens route its _lens twin and lens = (aperture, focus plane).
+        The keywords: the window, the sampling and the plan's, which every such call takes."""
+        (y0, y1), = self.bands
+        common = dict(y0=y0, y1=y1, spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled, flags=plan.level_flags(0)[2],
+                      stream=plan.stream, environment=plan.environment, kinds=plan.path_kinds, path_seed=plan.path_seed)
+        if plan.lens is None:
+            return getattr(self.scene, name), (), common
+        return getattr(self.scene, name + "_lens"), (plan.lens["aperture"], plan.lens["focus_plane"]), common
+
     def _device_levels(self, plan, depth, queue_capacity):
-        """fused="device_lights[_path]": ONE mr_render_recursion; fused="device_photons[_path]": ONE mr_render_recursion_photons with
-        the plan's maps.  Then ONE read of the counters; returns (rays, shadow rays) per level, cut at the first level without rays;
-        RuntimeError if a level was truncated."""
+        """The "device" driver: ONE mr_render_recursion, or on a route with photons ONE mr_render_recursion_photons with the plan's
+        maps, each through the thin lens on a lens route (_eye_call).  Then ONE read of the counters; returns (rays, shadow rays)
+        per level, cut at the first level without rays; RuntimeError if a level was truncated."""
         if self.n == 0 or depth < 0:
             return []
-        photons = plan.fused.startswith("device_photons")
+        photons = plan.route.photons
         cap = plan.fan * self.n if queue_capacity is None else int(queue_capacity)
         children = binding.MR_LEVEL_PATH if plan.path_tracing else binding.MR_LEVEL_SPECULAR
-        (y0, y1), = self.bands
+        recursion, lens, common = self._eye_call(plan, "render_recursion_photons" if photons else "render_recursion")
         if photons:
-            need = self.scene.recursion_photons_workspace_bytes(self.cam, self.W, self.H, depth, cap, y0=y0, y1=y1, spp=self.spp,
-                                                                children=children, environment=plan.environment, kinds=plan.path_kinds)
+            need = self.scene.recursion_photons_workspace_bytes(self.cam, self.W, self.H, depth, cap, y0=common["y0"], y1=common["y1"],
+                                                                spp=self.spp, children=children, environment=plan.environment,
+                                                                kinds=plan.path_kinds)
         else:
             need = self.scene.recursion_workspace_bytes(depth, cap, children=children, environment=plan.environment,
                                                         kinds=plan.path_kinds)
@@ -781,16 +838,11 @@ class FrameRenderer:
             self.d_recursion = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
         if self.d_level_counts is None or self.d_level_counts.shape[0] < depth + 1:
             self.d_level_counts = torch.zeros((depth + 1, 8), dtype=torch.int64, device=self.device)
-        common = dict(queue_capacity=cap, y0=y0, y1=y1, spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled,
-                      flags=plan.level_flags(0)[2], stream=plan.stream, children=children, environment=plan.environment,
-                      kinds=plan.path_kinds, path_seed=plan.path_seed, workspace_bytes=need)
-        if plan.lens is not None:                       # the same call through the thin lens
-            common.update(aperture=plan.lens["aperture"], focus_plane=plan.lens["focus_plane"])
-        recursion_photons = self.scene.render_recursion_photons_lens if plan.lens is not None else self.scene.render_recursion_photons
-        recursion = self.scene.render_recursion_lens if plan.lens is not None else self.scene.render_recursion
+        # the recursions take the lens by keyword
+        common.update(zip(("aperture", "focus_plane"), lens), queue_capacity=cap, children=children, workspace_bytes=need)
         if photons:
-            recursion_photons(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth, plan.photon_maps[0], plan.photon_maps[1],
-                              self.d_recursion, max_dist=plan.max_dist, nphotons=plan.nphotons, **common)
+            recursion(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth, plan.photon_maps[0], plan.photon_maps[1],
+                      self.d_recursion, max_dist=plan.max_dist, nphotons=plan.nphotons, **common)
         else:
             recursion(self.cam, self.W, self.H, self.d_rgb, self.d_level_counts, depth, d_workspace=self.d_recursion if depth > 0 else None,
                       **common)
@@ -806,22 +858,16 @@ class FrameRenderer:
         return per_level
 
     def _frame_level0(self, plan, last):
-        """Level 0 as ONE mr_render_level_lights straight into d_rgb (then mr_gather_level, with photon maps, on generate()'s
+        """Level 0 as ONE mr_render_level_lights[_lens] straight into d_rgb (then mr_gather_level, with photon maps, on generate()'s
         rays); returns (rays, shadow rays) from the launch's counters and the queue of level 1 (None after the last)."""
         if plan.photon_maps is not None:                # the photon term reads level 0's rays
             self.generate(plan.stream)
         hits, normal, cnts, out = self._level_buffers(plan, self.n, 0, last)
-        (y0, y1), = self.bands
         children = binding.MR_LEVEL_LAST if last else binding.MR_LEVEL_PATH if plan.path_tracing else binding.MR_LEVEL_SPECULAR
-        common = dict(y0=y0, y1=y1, spp=self.spp, jitter=self.jitter, seed=self.seed, tiled=self.tiled, flags=plan.level_flags(0)[2], d_hits=hits,
-                      d_sample_normal=normal, d_counts=cnts[:5], stream=plan.stream, children=children, environment=plan.environment,
-                      kinds=plan.path_kinds, path_seed=plan.path_seed, d_out_rays=out.rays, d_out_weights=out.weights,
-                      d_out_pixels=out.pixels, d_out_ids=out.ids, d_out_count=None if last else cnts[5:], d_out_lowres=out.low)
-        if plan.lens is not None:                       # the same frame through the thin lens
-            self.scene.render_level_lights_lens(self.cam, self.W, self.H, self.d_rgb, plan.lens["aperture"], plan.lens["focus_plane"],
-                                                **common)
-        else:
-            self.scene.render_level_lights(self.cam, self.W, self.H, self.d_rgb, **common)
+        render, lens, common = self._eye_call(plan, "render_level_lights")
+        render(self.cam, self.W, self.H, self.d_rgb, *lens, d_hits=hits, d_sample_normal=normal, d_counts=cnts[:5], children=children,
+               d_out_rays=out.rays, d_out_weights=out.weights, d_out_pixels=out.pixels, d_out_ids=out.ids,
+               d_out_count=None if last else cnts[5:], d_out_lowres=out.low, **common)
         self._gather(plan, Queue(self.d_rays, None, None, None, None, self.n), hits, normal, self.d_rgb)
         host = cnts.tolist()
         return (host[0], host[1]), None if last else out.first(host[5])
