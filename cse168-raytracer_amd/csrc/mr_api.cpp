@@ -84,6 +84,8 @@ void release_device(mr_scene *s) {
     (void)hipFree(s->d_tex);
     s->d_tex = nullptr;
     s->tex_dirty = !s->tex.blob.empty();   // and so does the texture table
+    (void)hipFree(s->d_finish_state);
+    s->d_finish_state = nullptr;
 }
 
 inline int32_t leaf_ref(uint32_t first, uint32_t count) {
@@ -1562,11 +1564,13 @@ static mr_status check_recursion_desc(const char *who, const mr_recursion_desc *
 // what mr_render_recursion and mr_render_recursion_photons ask first, in this order: the argument checks of
 // mr_render_level_lights under the call's name, the counters, the flags, the descriptor.  fd: the frame as the launchers take it;
 // samples: those of its window (which has passed check_frame_lights: counting them cannot fail)
+// (counts_name: what the call names its counters, d_level_counts or d_pass_counts)
 static mr_status check_recursion_args(const char *who, mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc,
-                                      const float *d_rgb, const uint64_t *d_level_counts, mr_frame_desc &fd, unsigned long long &samples) {
+                                      const float *d_rgb, const uint64_t *d_level_counts, mr_frame_desc &fd, unsigned long long &samples,
+                                      const char *counts_name = "d_level_counts") {
     mr_status st = check_render_lights_args(who, s, frame, fd, d_rgb, nullptr, nullptr, false, d_level_counts);
     if (st != MR_OK) return st;
-    if (!d_level_counts) return fail(MR_ERR_INVALID, "%s: NULL argument (d_level_counts)", who);
+    if (!d_level_counts) return fail(MR_ERR_INVALID, "%s: NULL argument (%s)", who, counts_name);
     if (fd.flags & ~(uint32_t)(MR_MATH_PRODUCT | MR_TRACE_INCOHERENT))
         return fail(MR_ERR_INVALID, "%s: flags may hold MR_MATH_PRODUCT, MR_TRACE_INCOHERENT only (the shadow rays are closest-hit, as in "
                                     "mr_trace_level_lights)", who);
@@ -1583,19 +1587,72 @@ mr_status mr_render_recursion_workspace(const mr_recursion_desc *desc, uint64_t 
     return MR_OK;
 }
 
+// ---- the passes of a frame of S samples per pixel (include/miro_hip_passes.h).  The rule: from sample_begin, whole passes of
+// frame_spp while they fit below sample_end, then the remainder as powers of two in descending order.  Writes the first
+// `capacity` passes (base / spp: either may be NULL) and returns how many there are
+static uint32_t passes_plan(uint32_t frame_spp, uint32_t begin, uint32_t end, uint32_t *base, uint32_t *spp, uint32_t capacity) {
+    uint32_t n = 0;
+    for (uint32_t at = begin, p; at < end; at += p, n++) {
+        for (p = frame_spp; p > end - at;) p >>= 1;
+        if (n < capacity && base) base[n] = at;
+        if (n < capacity && spp) spp[n] = p;
+    }
+    return n;
+}
+// what the descriptor alone can get wrong, in this order; frame_spp: a power of two <= 64
+static mr_status check_passes_desc(const char *who, const mr_passes_desc *pd, uint32_t frame_spp) {
+    if (!pd) return fail(MR_ERR_INVALID, "%s: NULL argument (passes)", who);
+    for (int k = 0; k < 5; k++)
+        if (pd->reserved[k] != 0) return fail(MR_ERR_INVALID, "%s: mr_passes_desc.reserved must be 0", who);
+    if (pd->spp_total == 0) return fail(MR_ERR_INVALID, "%s: spp_total must be at least 1", who);
+    if (pd->sample_begin >= pd->sample_end || pd->sample_end > pd->spp_total)
+        return fail(MR_ERR_INVALID, "%s: samples [%u, %u) are no non-empty range inside [0, spp_total = %u)", who, pd->sample_begin,
+                    pd->sample_end, pd->spp_total);
+    if (pd->sample_begin % frame_spp != 0)
+        return fail(MR_ERR_INVALID, "%s: sample_begin (%u) must be a multiple of the frame's spp (%u)", who, pd->sample_begin, frame_spp);
+    return MR_OK;
+}
+mr_status mr_render_passes_plan(uint32_t frame_spp, const mr_passes_desc *desc, uint32_t *n_passes, uint32_t *base, uint32_t *spp,
+                                uint32_t capacity) {
+    const char *who = "mr_render_passes_plan";
+    if (!n_passes) return fail(MR_ERR_INVALID, "%s: NULL argument (n_passes)", who);
+    if (frame_spp == 0 || frame_spp > 64 || (frame_spp & (frame_spp - 1)))
+        return fail(MR_ERR_INVALID, "%s: spp must be a power of two <= 64 (got %u)", who, frame_spp);
+    const mr_status st = check_passes_desc(who, desc, frame_spp);
+    if (st != MR_OK) return st;
+    *n_passes = passes_plan(frame_spp, desc->sample_begin, desc->sample_end, base, spp, capacity);
+    return MR_OK;
+}
+// what the two passes calls ask after their parent call's list (and the lens checks), in this order; fd: the frame as the launchers
+// take it, samples: those of its window
+static mr_status check_passes(const char *who, const mr_frame_desc &fd, const mr_recursion_desc &rd, unsigned long long samples,
+                              const mr_passes_desc *pd) {
+    if (fd.tiled)
+        return fail(MR_ERR_INVALID, "%s: tiled sample order (a sample's frame-wide index is pixel * spp_total + sample, in image "
+                                    "order); use tiled = 0", who);
+    const mr_status st = check_passes_desc(who, pd, fd.spp);
+    if (st != MR_OK) return st;
+    if (rd.depth >= 1 && samples / fd.spp * pd->spp_total > 0xFFFFFFFFull)
+        return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 samples per frame with children (%llu pixels x spp_total %u: ray ids are "
+                                    "32 bits)", who, samples / fd.spp, pd->spp_total);
+    return MR_OK;
+}
 // The launches of a whole recursive frame on one stream, and nothing else: the kernel that zeroes the counters (`counts`:
 // [depth + 1][8]); level 0, mr_render_level_lights' launcher (launch_level0_lights) with its children in queue 0 of the workspace (depth 0: the plain
 // frame, no workspace); then one queued level kernel (mr_level_lights_queued.hip) per further level, from one queue into the
 // other, whose length is the word the level before counted its children into.  d_hits / d_normal: optional, every level's per-ray
-// records, each level overwriting the one before.  step(l, d_n, bound, in) is enqueued after level l, 0 included -- d_n: the
+// records, each level overwriting the one before.  step(l, row, d_n, bound, in, pass) is enqueued after level l, 0 included -- row: the
+// level's eight counters, d_n: the
 // word that holds the level's length (level 0: the samples the frame counted), bound: what the host knows it cannot exceed (fan^l
 // x samples, saturating at the capacity), in: the queue the level read (level 0: none, its rays start at the eye).  lens
 // (optional): level 0 is the thin-lens frame's launcher (mr_frame_lens.hip), at depth 0 too; the further levels do not differ
-static mr_status no_level_step(uint32_t, const unsigned long long *, unsigned long long, const RayQueue &) { return MR_OK; }
+// pass (optional): the call is one pass of a frame of pass->S samples per pixel (mr_render_recursion_passes): level 0 is
+// mr_frame_passes.hip's kernel for either camera, the further levels divide by S, and `step` is handed the pass
+static mr_status no_level_step(uint32_t, unsigned long long *, const unsigned long long *, unsigned long long, const RayQueue &, const FramePass *) { return MR_OK; }
 extern "C++" template <typename STEP>                                                  // (the entry points around it have C linkage)
 static mr_status enqueue_recursion(const LightScene &ls, const mr_frame_desc &fd, const mr_lens_desc *lens, const mr_recursion_desc &rd,
                                    unsigned long long samples, void *d_workspace, float *d_rgb, mr_hit *d_hits, float *d_normal, unsigned long long *counts,
-                                   hipStream_t hs, STEP step) {
+                                   hipStream_t hs, STEP step, const FramePass *pass = nullptr) {
     mr_status st = launch_zero_words(counts, 8ull * (rd.depth + 1ull), hs);
     if (st != MR_OK) return st;
     const bool path = rd.children == MR_LEVEL_PATH;
@@ -1612,11 +1669,12 @@ static mr_status enqueue_recursion(const LightScene &ls, const mr_frame_desc &fd
     }
     FrameOutputs o = {};
     o.rgb = d_rgb; o.hits = d_hits; o.sample_normal = d_normal; o.counts = counts;
-    st = launch_level0_lights("mr_render_level_lights_lens", ls, fd, lens, l0, o, qs[0], &counts[5], hs);
-    if (st != MR_OK || (st = step(0u, &counts[0], samples, RayQueue{})) != MR_OK) return st;
+    st = pass ? launch_frame_pass("mr_render_recursion_passes", ls, fd, lens, l0, *pass, o, qs[0], &counts[5], hs)
+              : launch_level0_lights("mr_render_level_lights_lens", ls, fd, lens, l0, o, qs[0], &counts[5], hs);
+    if (st != MR_OK || (st = step(0u, counts, &counts[0], samples, RayQueue{}, pass)) != MR_OK) return st;
 
     QueuedLevel lv = {};
-    lv.spp = fd.spp;
+    lv.spp = pass ? pass->S : fd.spp;
     lv.flags = (fd.flags & MR_MATH_PRODUCT) | MR_TRACE_INCOHERENT;                      // a bounce queue is compacted in wave order
     lv.path = path; lv.environment = rd.environment;
     lv.path_kinds = rd.path_kinds; lv.seed = rd.path_seed;
@@ -1629,8 +1687,27 @@ static mr_status enqueue_recursion(const LightScene &ls, const mr_frame_desc &fd
         const unsigned long long *d_n = row - 8 + 5;                                      // the children level l - 1 counted
         lv.last = l == rd.depth; lv.bounce = l;
         if ((st = launch_level_lights_queued(ls, lv, in, out, d_n, cap, bound, d_rgb, d_hits, d_normal, row, hs)) != MR_OK ||
-            (st = step(l, d_n, bound, in)) != MR_OK)
+            (st = step(l, row, d_n, bound, in, pass)) != MR_OK)
             return st;
+    }
+    return MR_OK;
+}
+
+// one enqueue_recursion per pass of the plan (passes_plan's rule), the passes' counter blocks ([depth + 1][8] each) one after the
+// other; pixels: those of fd's window
+extern "C++" template <typename STEP>
+static mr_status enqueue_recursion_passes(const LightScene &ls, const mr_frame_desc &fd, const mr_lens_desc *lens, const mr_recursion_desc &rd,
+                                          const mr_passes_desc &pd, unsigned long long pixels, void *d_workspace, float *d_rgb, mr_hit *d_hits,
+                                          float *d_normal, unsigned long long *counts, hipStream_t hs, STEP step) {
+    uint32_t i = 0;
+    for (uint32_t at = pd.sample_begin, p; at < pd.sample_end; at += p, i++) {
+        for (p = fd.spp; p > pd.sample_end - at;) p >>= 1;
+        mr_frame_desc fp = fd;
+        fp.spp = p;
+        const FramePass pass = {pd.spp_total, at};
+        const mr_status st = enqueue_recursion(ls, fp, lens, rd, pixels * p, d_workspace, d_rgb, d_hits, d_normal,
+                                               counts + 8ull * (rd.depth + 1ull) * i, hs, step, &pass);
+        if (st != MR_OK) return st;
     }
     return MR_OK;
 }
@@ -1638,12 +1715,14 @@ static mr_status enqueue_recursion(const LightScene &ls, const mr_frame_desc &fd
 // The whole recursive frame on one stream (include/miro_hip_recursion.h).  The argument checks first, all before the scene's
 // state is read; then the state and the uploads; then nothing but launches (enqueue_recursion).
 // with_lens: mr_render_recursion_lens, whose lens checks follow the list
+// with_passes: mr_render_recursion_passes -- the call once per pass of `passes` (check_passes follows the lens checks); the
+// counters are d_pass_counts
 static mr_status render_recursion(const char *who, bool with_lens, mr_scene *s, const mr_frame_desc *frame, const mr_lens_desc *lens,
                                   const mr_recursion_desc *desc, float *d_rgb, void *d_workspace, uint64_t workspace_bytes,
-                                  uint64_t *d_level_counts, void *stream) {
+                                  uint64_t *d_level_counts, void *stream, bool with_passes = false, const mr_passes_desc *passes = nullptr) {
     mr_frame_desc fd;
     unsigned long long samples = 0;
-    mr_status st = check_recursion_args(who, s, frame, desc, d_rgb, d_level_counts, fd, samples);
+    mr_status st = check_recursion_args(who, s, frame, desc, d_rgb, d_level_counts, fd, samples, with_passes ? "d_pass_counts" : "d_level_counts");
     if (st != MR_OK) return st;
     if (desc->depth > 0) {
         if (samples > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 samples per call with children", who);
@@ -1655,11 +1734,23 @@ static mr_status render_recursion(const char *who, bool with_lens, mr_scene *s, 
                         (unsigned long long)workspace_bytes, (unsigned long long)desc->queue_capacity_lo, (unsigned long long)need);
     }
     if (with_lens && (st = check_frame_lens(who, lens, fd)) != MR_OK) return st;
+    if (with_passes && (st = check_passes(who, fd, *desc, samples, passes)) != MR_OK) return st;
     if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
     LightScene ls;
     if ((st = lights_scene_params(s, desc->environment != 0, stream, ls)) != MR_OK) return st;
+    if (with_passes)
+        return enqueue_recursion_passes(ls, fd, with_lens ? lens : nullptr, *desc, *passes, samples / fd.spp, d_workspace, d_rgb, nullptr,
+                                        nullptr, reinterpret_cast<unsigned long long *>(d_level_counts), static_cast<hipStream_t>(stream),
+                                        no_level_step);
     return enqueue_recursion(ls, fd, with_lens ? lens : nullptr, *desc, samples, d_workspace, d_rgb, nullptr, nullptr,
                              reinterpret_cast<unsigned long long *>(d_level_counts), static_cast<hipStream_t>(stream), no_level_step);
+}
+// ... once per pass of a frame of passes->spp_total samples per pixel (include/miro_hip_passes.h); lens: optional
+mr_status mr_render_recursion_passes(mr_scene *s, const mr_frame_desc *frame, const mr_lens_desc *lens, const mr_recursion_desc *desc,
+                                     const mr_passes_desc *passes, float *d_rgb, void *d_workspace, uint64_t workspace_bytes,
+                                     uint64_t *d_pass_counts, void *stream) {
+    return render_recursion("mr_render_recursion_passes", lens != nullptr, s, frame, lens, desc, d_rgb, d_workspace, workspace_bytes,
+                            d_pass_counts, stream, true, passes);
 }
 mr_status mr_render_recursion(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, float *d_rgb, void *d_workspace,
                               uint64_t workspace_bytes, uint64_t *d_level_counts, void *stream) {
@@ -1719,10 +1810,11 @@ mr_status mr_render_recursion_photons_workspace(const mr_frame_desc *frame, cons
 static mr_status render_recursion_photons(const char *who, bool with_lens, mr_scene *s, const mr_frame_desc *frame, const mr_lens_desc *lens,
                                           const mr_recursion_desc *desc, mr_photon_map *global_map, mr_photon_map *caustic_map,
                                           float max_dist, uint32_t nphotons, float *d_rgb, void *d_workspace, uint64_t workspace_bytes,
-                                          uint64_t *d_level_counts, void *stream) {
+                                          uint64_t *d_level_counts, void *stream, bool with_passes = false,
+                                          const mr_passes_desc *passes = nullptr) {
     mr_frame_desc fd;
     unsigned long long samples = 0;
-    mr_status st = check_recursion_args(who, s, frame, desc, d_rgb, d_level_counts, fd, samples);
+    mr_status st = check_recursion_args(who, s, frame, desc, d_rgb, d_level_counts, fd, samples, with_passes ? "d_pass_counts" : "d_level_counts");
     if (st != MR_OK || (st = check_recursion_photons_window(who, fd, *desc, samples)) != MR_OK) return st;
     mr_photon_map *maps[2] = {global_map, caustic_map};
     if (!maps[0] && !maps[1]) return fail(MR_ERR_INVALID, "%s: NULL argument (global_map and caustic_map are both NULL)", who);
@@ -1735,6 +1827,7 @@ static mr_status render_recursion_photons(const char *who, bool with_lens, mr_sc
         return fail(MR_ERR_INVALID, "%s: workspace_bytes is %llu, this frame and descriptor need %llu (mr_render_recursion_photons_workspace)",
                     who, (unsigned long long)workspace_bytes, (unsigned long long)ws.bytes);
     if (with_lens && (st = check_frame_lens(who, lens, fd)) != MR_OK) return st;
+    if (with_passes && (st = check_passes(who, fd, *desc, samples, passes)) != MR_OK) return st;
 
     if ((st = check_render_lights_state(who, s, fd, false)) != MR_OK) return st;
     for (mr_photon_map *m : maps) {
@@ -1758,19 +1851,38 @@ static mr_status render_recursion_photons(const char *who, bool with_lens, mr_sc
     // level l's photon term, before level l + 1 overwrites the hit records and (two levels on) this queue: queries, one estimate
     // per map, the accumulate, over a scratch laid out for `bound` rays.  bound <= the queue's capacity, and the kernels take it
     // as the capacity, so that no index reaches beyond that scratch.  Level 0 has no queue: its queries come from the eye rays
-    // made again, its length is the window's, which the frame has added to counts[0]; weight 1, pixel k / spp (in: all NULL)
-    auto photon_term = [&](uint32_t l, const unsigned long long *d_n, unsigned long long bound, const RayQueue &in) -> mr_status {
+    // made again, its length is the window's, which the frame has added to counts[0]; weight 1, pixel k / spp (in: all NULL).
+    // row: the level's eight counters.  pass (optional): the pass of a longer frame this is -- a level-0 sample's pixel is k / the
+    // pass's spp (bound / the window's pixels), the divisor pass->S
+    const unsigned long long pixels = samples / fd.spp;
+    auto photon_term = [&](uint32_t l, unsigned long long *row, const unsigned long long *d_n, unsigned long long bound, const RayQueue &in,
+                           const FramePass *pass) -> mr_status {
         const GatherScratch sc = gather_scratch(d_scratch, bound, maps[0] != nullptr, maps[1] != nullptr);
-        unsigned long long *d_queries = counts + 8ull * l + 6;
-        mr_status e = l == 0 ? (with_lens ? launch_gather_eye_queries_lens(s->dev, who, fd, *lens, d_hits, d_normal, sc.pos, sc.nrm, d_queries, hs)
-                                          : launch_gather_eye_queries(s->dev, who, fd, d_hits, d_normal, sc.pos, sc.nrm, d_queries, hs))
-                             : launch_gather_queued_queries(s->dev, in.rays, d_hits, d_normal, d_n, bound, sc.pos, sc.nrm, d_queries, hs);
+        unsigned long long *d_queries = row + 6;
+        mr_frame_desc fp = fd;
+        if (pass) fp.spp = (uint32_t)(bound / pixels);
+        mr_status e = l > 0 ? launch_gather_queued_queries(s->dev, in.rays, d_hits, d_normal, d_n, bound, sc.pos, sc.nrm, d_queries, hs)
+                      : pass ? launch_gather_eye_queries_pass(s->dev, who, fp, with_lens ? lens : nullptr, *pass, d_hits, d_normal, sc.pos, sc.nrm,
+                                                              d_queries, hs)
+                      : with_lens ? launch_gather_eye_queries_lens(s->dev, who, fd, *lens, d_hits, d_normal, sc.pos, sc.nrm, d_queries, hs)
+                                  : launch_gather_eye_queries(s->dev, who, fd, d_hits, d_normal, sc.pos, sc.nrm, d_queries, hs);
         for (int i = 0; i < 2 && e == MR_OK; i++)
             if (maps[i]) e = photon_map_estimate_queued(maps[i], sc.pos, sc.nrm, d_n, bound, max_dist, nphotons, sc.irr[i], hs);
         if (e != MR_OK) return e;
-        return launch_gather_queued_accumulate(sc.irr[0], sc.irr[1], in.weights, in.pixels, d_n, bound, fd.spp, d_rgb, hs);
+        return launch_gather_queued_accumulate(sc.irr[0], sc.irr[1], in.weights, in.pixels, d_n, bound, fp.spp, pass ? pass->S : fd.spp, d_rgb, hs);
     };
+    if (with_passes)
+        return enqueue_recursion_passes(ls, fd, with_lens ? lens : nullptr, *desc, *passes, pixels, d_workspace, d_rgb, d_hits, d_normal, counts,
+                                        hs, photon_term);
     return enqueue_recursion(ls, fd, with_lens ? lens : nullptr, *desc, samples, d_workspace, d_rgb, d_hits, d_normal, counts, hs, photon_term);
+}
+// ... once per pass of a frame of passes->spp_total samples per pixel (include/miro_hip_passes.h); lens: optional
+mr_status mr_render_recursion_photons_passes(mr_scene *s, const mr_frame_desc *frame, const mr_lens_desc *lens, const mr_recursion_desc *desc,
+                                             const mr_passes_desc *passes, mr_photon_map *global_map, mr_photon_map *caustic_map,
+                                             float max_dist, uint32_t nphotons, float *d_rgb, void *d_workspace, uint64_t workspace_bytes,
+                                             uint64_t *d_pass_counts, void *stream) {
+    return render_recursion_photons("mr_render_recursion_photons_passes", lens != nullptr, s, frame, lens, desc, global_map, caustic_map,
+                                    max_dist, nphotons, d_rgb, d_workspace, workspace_bytes, d_pass_counts, stream, true, passes);
 }
 mr_status mr_render_recursion_photons(mr_scene *s, const mr_frame_desc *frame, const mr_recursion_desc *desc, mr_photon_map *global_map,
                                       mr_photon_map *caustic_map, float max_dist, uint32_t nphotons, float *d_rgb, void *d_workspace,
@@ -2230,6 +2342,23 @@ mr_status mr_tonemap(mr_scene *s, const float *d_rgb, uint64_t n_values, uint8_t
     if (!s || !d_rgb || !d_out) return fail(MR_ERR_INVALID, "NULL argument");
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_tonemap(d_rgb, n_values, d_out, static_cast<hipStream_t>(stream));
+}
+
+// Scene.cpp:150-163, 184-197 and Image.cpp:47-52 (include/miro_hip_passes.h).  The first call allocates the scene's three state
+// words and must lie outside a stream capture; after it the call is two kernels on `stream`
+mr_status mr_finish_image(mr_scene *s, const float *d_rgb, uint64_t n_pixels, uint8_t *d_out8, float *d_minmax, void *stream) {
+    const char *who = "mr_finish_image";
+    if (!s || !d_rgb || !d_out8) return fail(MR_ERR_INVALID, "%s: NULL argument", who);
+    if (n_pixels == 0) return fail(MR_ERR_INVALID, "%s: empty image", who);
+    if (n_pixels > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "%s: at most 2^32 - 1 pixels", who);
+    if (misaligned(4, d_rgb, d_minmax)) return fail(MR_ERR_INVALID, "%s: d_rgb and d_minmax must be 4-byte aligned", who);
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    if (!s->d_finish_state) {
+        const uint32_t identity[3] = {kFinishMaxIdentity, kFinishMinIdentity, 0u};
+        MR_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&s->d_finish_state), sizeof(identity)));
+        MR_HIP_CHECK(hipMemcpy(s->d_finish_state, identity, sizeof(identity), hipMemcpyHostToDevice));
+    }
+    return launch_finish_image(d_rgb, 3ull * n_pixels, d_out8, d_minmax, s->d_finish_state, static_cast<hipStream_t>(stream));
 }
 
 mr_status mr_untile_pixels(mr_scene *s, const float *d_slots, float *d_image, uint32_t W, uint32_t rows, uint32_t spp,

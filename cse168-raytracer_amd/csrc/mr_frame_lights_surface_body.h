@@ -97,20 +97,33 @@ inline void fill_frame_child_args(FrameChildArgs &ch, const mr_frame_level_desc 
     ch.kinds = ld.path_kinds; ch.hbase = pcg32(ld.path_seed);
 }
 
+// One pass of a frame of S samples per pixel (PASS; mr_frame_passes.hip): the launch renders samples [base, base + eye.spp) of every
+// pixel of the window.  add: the pixel's lane adds its value to what rgb holds (a plain load, add and store) instead of storing it
+struct PassParams {
+    uint32_t S, base, add;
+};
+
 // VAR, ANY: as in frame_lights_kernel.  s_stack: the workgroup's dynamic LDS, [stack_depth][kTraceBlock]; s_tab: 128 words of
 // static LDS for the two noise tables.
 // LENS: the eye ray is Camera::eyeRay under -DDOF (eye_ray_lens_of, mr_eye.h; ln: the focus point and the aperture) -- the
 // three places that make the eye ray make the lens ray, and the hit point of a sphere or a plane starts from the sample's own
 // point on the lens, which is made again there, not held across the traversal.  With LENS false nothing of `ln` is read.
-template <int VAR, bool ANY, bool ENV, int CHILDREN, bool LENS>
+// PASS: the launch is one pass of a frame of ps.S samples per pixel, whose samples are numbered 0 .. S - 1 whatever the passes --
+// the sample's random numbers are those of sample ps.base + sm (at the three places that make the ray), the path tracer's hash
+// and the child's id come from the frame-wide index pixel * S + base + sm (the index a single launch at spp = S would give the
+// sample; the window is in image order), the pixel's value is its lanes' sum times 1 / S, stored or added (ps.add).  With PASS
+// false nothing of `ps` is read.
+template <int VAR, bool ANY, bool ENV, int CHILDREN, bool LENS, bool PASS = false>
 __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfaceArgs a, const EnvParams env, const FrameChildArgs &ch, const LensParams &ln,
-                                                          int *s_stack, uint32_t (&s_tab)[128]) {
+                                                          int *s_stack, uint32_t (&s_tab)[128], const PassParams &ps = PassParams{}) {
     const NoiseTables nt = stage_noise_tables(s_tab);
     const int tid = threadIdx.x;
     const unsigned long long stride = (unsigned long long)gridDim.x * kTraceBlock;
     const unsigned long long n = a.eye.n;
     const unsigned long long n_round = whole_workgroups(n);
     const uint32_t spp = a.eye.spp;
+    // the number the sample's key is made from
+    auto key_sample = [&](uint32_t sm) -> uint32_t { if constexpr (PASS) return ps.base + sm; else return sm; };
     const bool table = a.t.mat_tex != nullptr;        // wave-uniform, out of the loop (hit_surface_kernel)
     Stats st = {0ull, 0ull};
     unsigned my_shadow_rays = 0, my_undefined = 0, my_misses = 0, my_env_undefined = 0;
@@ -123,8 +136,8 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
         float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = make_float4(1.f, 1.f, 1.f, -1.f);
         if (live) {
             eye_sample_of(a.eye, idx, x, row, y, sm);
-            if constexpr (LENS) eye_ray_lens_of(a.eye, ln, x, y, sm, ra, rb);
-            else eye_ray_of(a.eye, x, y, sm, ra, rb);
+            if constexpr (LENS) eye_ray_lens_of(a.eye, ln, x, y, key_sample(sm), ra, rb);
+            else eye_ray_of(a.eye, x, y, key_sample(sm), ra, rb);
         }
         // ---- primary ray: a closest hit; a lane past the end of the window gets the miss record
         const mr_hit h = trace_hit<true, false, false, VAR>(a.tp, ra, rb, rb.w, live, s_stack, tid, st);
@@ -139,7 +152,7 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
             // (LENS: the sample's point on the lens and its direction, made again)
             if constexpr (LENS) {
                 eye_sample_of(a.eye, idx, x, row, y, sm);
-                eye_ray_lens_of(a.eye, ln, x, y, sm, ra, rb);
+                eye_ray_lens_of(a.eye, ln, x, y, key_sample(sm), ra, rb);
                 surface_od<true>(a.m.s, ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
             } else {
                 surface_od<true>(a.m.s, a.eye.eye[0], a.eye.eye[1], a.eye.eye[2], rb.x, rb.y, rb.z, h.t, h.prim, h.beta, h.gamma, P, N);
@@ -163,8 +176,8 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
         float d[3] = {0.f, 0.f, 0.f};
         if (ENV ? live : hit) {
             eye_sample_of(a.eye, idx, x, row, y, sm);
-            if constexpr (LENS) eye_ray_lens_of(a.eye, ln, x, y, sm, ra, rb);
-            else eye_ray_of(a.eye, x, y, sm, ra, rb);
+            if constexpr (LENS) eye_ray_lens_of(a.eye, ln, x, y, key_sample(sm), ra, rb);
+            else eye_ray_of(a.eye, x, y, key_sample(sm), ra, rb);
             d[0] = rb.x; d[1] = rb.y; d[2] = rb.z;
         }
 
@@ -176,6 +189,9 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
         // and no children
         if (CHILDREN != 0) {
             const uint32_t pix = (ENV ? live : hit) ? row * a.eye.W + x : 0xFFFFFFFFu;
+            // the sample's index in the launch's order, or (PASS) in the frame's: x, row and sm are the sample's, computed just above
+            uint32_t id = (uint32_t)idx;
+            if constexpr (PASS) id = (row * a.eye.W + x) * ps.S + ps.base + sm;
             ChildGen<CHILDREN == 2> g;
             bool emit[4] = {false, false, false, false};
             if (hit) {
@@ -194,12 +210,12 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
                     for (int c = 0; c < 3; c++) { g.P[c] = P[c]; g.N[c] = N[c]; }
                     g.d[0] = d[0]; g.d[1] = d[1]; g.d[2] = d[2];
                     g.w0[0] = 1.f; g.w0[1] = 1.f; g.w0[2] = 1.f;
-                    if (CHILDREN == 2) g.hray = pcg32(ch.hbase ^ (uint32_t)idx);               // bounce 0
+                    if (CHILDREN == 2) g.hray = pcg32(ch.hbase ^ id);                          // bounce 0
                     g.plan(refl, refr, diff, emit);
                 }
             }
             if constexpr (CHILDREN == 2)
-                write_children_col<kTraceBlock>(ch.out, ch.out_lowres, g, col, emit, pix, (uint32_t)idx);
+                write_children_col<kTraceBlock>(ch.out, ch.out_lowres, g, col, emit, pix, id);
             else
                 write_children<kTraceBlock, false>(ch.out, g, emit, pix, 0u);
         }
@@ -229,11 +245,13 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
         }
         if (live) eye_sample_of(a.eye, idx, x, row, y, sm);      // recomputed: cheaper than live registers across the traversals
         if (live && sm == 0) {
-            if (spp > 1) {
-                const float inv_spp = 1.0f / (float)spp;
+            const uint32_t mean_of = PASS ? ps.S : spp;
+            if (mean_of > 1) {
+                const float inv_spp = 1.0f / (float)mean_of;
                 L[0] *= inv_spp; L[1] *= inv_spp; L[2] *= inv_spp;
             }
             float *o = a.rgb + 3 * ((size_t)row * a.eye.W + x);
+            if (PASS && ps.add) { L[0] += o[0]; L[1] += o[1]; L[2] += o[2]; }
             o[0] = L[0]; o[1] = L[1]; o[2] = L[2];
         }
     }

@@ -153,12 +153,12 @@ mr_status launch_irradiance_queued(const PhotonMapDev &pm, unsigned *work_counte
 }
 
 mr_status launch_gather_queued_accumulate(const float *d_irr_a, const float *d_irr_b, const float *d_weights, const uint32_t *d_pixels,
-                                          const unsigned long long *d_n, unsigned long long bound, uint32_t spp, float *d_rgb,
-                                          hipStream_t stream) {
+                                          const unsigned long long *d_n, unsigned long long bound, uint32_t spp, uint32_t spp_total,
+                                          float *d_rgb, hipStream_t stream) {
     if (bound == 0) return MR_OK;
     AccumulateArgs a;
     a.irr_a = d_irr_a; a.irr_b = d_irr_b; a.weights = d_weights; a.pixels = d_pixels;
-    a.n = bound; a.spp = spp; a.inv_spp = 1.0f / (float)spp;
+    a.n = bound; a.spp = spp; a.inv_spp = 1.0f / (float)spp_total;
     a.rgb = d_rgb; a.ray_rgb = nullptr;
     hipLaunchKernelGGL(gather_queued_accumulate_kernel, dim3(grid_for(bound)), dim3(kBlock), 0, stream, a, d_n);
     MR_HIP_CHECK(hipGetLastError());

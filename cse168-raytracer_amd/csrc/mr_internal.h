@@ -206,6 +206,12 @@ mr_status launch_gather_level_queries(const DeviceScene &ds, const mr_ray *d_ray
 mr_status launch_gather_level_accumulate(const float *d_irr_a, const float *d_irr_b, const float *d_weights, const uint32_t *d_pixels,
                                          unsigned long long n, uint32_t spp, float *d_rgb, float *d_ray_rgb, hipStream_t stream);
 mr_status launch_tonemap(const float *d_rgb, unsigned long long n_values, uint8_t *d_out, hipStream_t stream);
+// mr_finish_image (mr_finish_image.hip): two kernels on `stream`.  d_state: three words owned by the scene -- the order-preserving
+// integer images of the running maximum and minimum and a ticket --, which hold finish_state_identity() between calls: the second
+// kernel's last workgroup puts that back.  d_minmax: optional, (max, min) for the caller
+constexpr uint32_t kFinishMaxIdentity = 0x007FFFFFu, kFinishMinIdentity = 0xFF800000u;   // the images of -inf and +inf
+mr_status launch_finish_image(const float *d_rgb, unsigned long long n_values, uint8_t *d_out, float *d_minmax, uint32_t *d_state,
+                              hipStream_t stream);
 mr_status launch_deinterleave(const float *d_recv, float *d_full, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t world,
                               uint32_t shard_rows, uint32_t fpp, hipStream_t stream);
 mr_status launch_untile(const float *d_slots, float *d_image, uint32_t W, uint32_t rows, uint32_t spp, uint32_t channels,
@@ -354,6 +360,14 @@ mr_status launch_frame_level_lights(const LightScene &ls, const mr_frame_desc &f
 // children and touches neither `out` nor d_out_count.  `who`: the entry point the window's messages name
 mr_status launch_frame_lens(const char *who, const LightScene &ls, const mr_frame_desc &fd, const mr_lens_desc &lens, const mr_frame_level_desc &ld,
                             const FrameOutputs &o, const RayQueue &out, unsigned long long *d_out_count, hipStream_t stream);
+// One pass of a frame of S samples per pixel (mr_frame_passes.hip, mr_render_recursion_passes): the launch renders samples
+// [base, base + fd.spp) of every pixel, numbered as a single launch at spp = S would number them (keys, path hashes, child ids);
+// a pixel's value is its lanes' sum / S, stored by the pass with base == 0 and added by every other.  lens: optional.  Otherwise
+// launch_frame_lens' contract, MR_LEVEL_LAST included.
+struct FramePass { uint32_t S, base; };
+mr_status launch_frame_pass(const char *who, const LightScene &ls, const mr_frame_desc &fd, const mr_lens_desc *lens, const mr_frame_level_desc &ld,
+                            const FramePass &pass, const FrameOutputs &o, const RayQueue &out, unsigned long long *d_out_count,
+                            hipStream_t stream);
 // One level of mr_render_recursion, whose queue's length is a device word (mr_level_lights_queued.hip).  What the level is:
 // path: the PATH_TRACING build's kernel (children of bounce `bounce` from path_kinds / seed, ids, low-res bytes), else the
 // specular one; last: no children; capacity: the rays the output queue holds
@@ -512,7 +526,8 @@ constexpr int kPhotonStats = 12;  // see mr_photon_map_get_stats (miro_hip.h)
 // The photon-map term for a queue whose length is a device word (mr_gather_queued.hip, mr_render_recursion_photons): the three
 // steps of mr_gather_level as kernels that read n = min(*d_n, bound) themselves.  bound: what the host knows the length cannot
 // exceed, at most the queue's capacity -- every grid is sized from it and every buffer holds that many rays; nothing is launched
-// where it is 0.  d_queries: one word, += the queries made.  launch_gather_eye_queries: level 0 of the one-call frame, whose rays
+// where it is 0.  launch_gather_queued_accumulate: spp finds the pixel of a level-0 sample (k / spp, d_pixels NULL), spp_total is the
+// divisor -- the same number except in a pass of a longer frame (mr_render_recursion_photons_passes).  d_queries: one word, += the queries made.  launch_gather_eye_queries: level 0 of the one-call frame, whose rays
 // exist in registers only -- the eye ray of sample k of fd's window is made again and joined with the hit record (and, given
 // d_normal, the normal) the frame wrote.
 mr_status launch_gather_eye_queries(const DeviceScene &ds, const char *who, const mr_frame_desc &fd, const mr_hit *d_hits,
@@ -528,8 +543,12 @@ mr_status launch_irradiance_queued(const PhotonMapDev &pm, unsigned *work_counte
                                    const unsigned long long *d_n, unsigned long long bound, float max_dist, uint32_t k, float *d_irrad,
                                    unsigned long long *d_stats, hipStream_t stream);
 mr_status launch_gather_queued_accumulate(const float *d_irr_a, const float *d_irr_b, const float *d_weights, const uint32_t *d_pixels,
-                                          const unsigned long long *d_n, unsigned long long bound, uint32_t spp, float *d_rgb,
-                                          hipStream_t stream);
+                                          const unsigned long long *d_n, unsigned long long bound, uint32_t spp, uint32_t spp_total,
+                                          float *d_rgb, hipStream_t stream);
+// ... level 0 of one pass (mr_frame_passes.hip): the ray of sample pass.base + k % fd.spp made again, through `lens` if given
+mr_status launch_gather_eye_queries_pass(const DeviceScene &ds, const char *who, const mr_frame_desc &fd, const mr_lens_desc *lens,
+                                         const FramePass &pass, const mr_hit *d_hits, const float *d_normal, float *d_pos, float *d_nrm,
+                                         unsigned long long *d_queries, hipStream_t stream);
 // The scratch of the photon-map term for n rays (mr_gather_level's d_scratch, 12 n floats): positions, normals (NaN = no query),
 // then the global map's estimate and the caustic map's; irr[i]: nullptr without map i
 struct GatherScratch { float *pos, *nrm, *irr[2]; };
@@ -646,4 +665,6 @@ struct mr_scene {
     mr::HostTextures tex;
     float4 *d_tex = nullptr;
     bool tex_dirty = false;
+    // mr_finish_image's three words (launch_finish_image), allocated and set to their identities by the first call
+    uint32_t *d_finish_state = nullptr;
 };

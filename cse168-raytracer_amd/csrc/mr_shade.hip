@@ -16,6 +16,7 @@
 #include "mr_phong.h"
 #include "mr_surface.h"
 #include "mr_tile.h"
+#include "mr_tonemap.h"
 
 namespace mr {
 namespace {
@@ -116,12 +117,7 @@ __global__ __launch_bounds__(kBlock) void gather_accumulate_kernel(const float *
 
 __global__ __launch_bounds__(kBlock) void tonemap_kernel(const float *rgb, unsigned long long n_values, uint8_t *out) {
     const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; i < n_values; i += stride) {
-        float v = rgb[i];
-        v = 1.0f / (1.0f + expf(-(6.0f * v - 3.0f)));               // sigmoid(6v-3), Scene.cpp:89, Utility.h:19-22
-        const float m = 255.0f * v;                                 // Image.cpp:44-50
-        out[i] = m > 255.0f ? 255 : (uint8_t)m;
-    }
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; i < n_values; i += stride) out[i] = tonemap_byte(rgb[i]);
 }
 
 // pixel slots of a tiled window (mr_gen_eye_rays_tiled) -> image order: `channels` floats per pixel

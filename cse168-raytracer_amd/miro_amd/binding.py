@@ -80,6 +80,9 @@ RECURSION_PHOTONS_SYMBOLS = ["mr_render_recursion_photons_workspace", "mr_render
 # ... and the three of miro_hip_lens.h (the fused frame and the one-call recursions through the thin lens), which that header
 # includes as its last line in turn
 LENS_SYMBOLS = ["mr_render_level_lights_lens", "mr_render_recursion_lens", "mr_render_recursion_photons_lens"]
+# ... and the four of miro_hip_passes.h (the one-call frames at any sample count and the image finish), which that header includes
+# below its declarations in turn
+PASSES_SYMBOLS = ["mr_render_passes_plan", "mr_render_recursion_passes", "mr_render_recursion_photons_passes", "mr_finish_image"]
 
 
 class MiroError(RuntimeError):
@@ -159,6 +162,27 @@ class RecursionDesc(C.Structure):
     _fields_ = [("depth", C.c_uint32), ("children", C.c_uint32), ("environment", C.c_uint32), ("path_kinds", C.c_uint32),
                 ("path_seed", C.c_uint32), ("queue_capacity_lo", C.c_uint32), ("queue_capacity_hi", C.c_uint32),
                 ("reserved", C.c_uint32 * 5)]
+
+
+class PassesDesc(C.Structure):
+    """mr_passes_desc (miro_hip_passes.h): the samples [sample_begin, sample_end) of a frame of spp_total samples per pixel"""
+    _fields_ = [("spp_total", C.c_uint32), ("sample_begin", C.c_uint32), ("sample_end", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+def passes_desc(samples, sample_begin=0, sample_end=None):
+    pd = PassesDesc()
+    pd.spp_total, pd.sample_begin, pd.sample_end = samples, sample_begin, samples if sample_end is None else sample_end
+    return pd
+
+
+def passes_plan(spp, samples, sample_begin=0, sample_end=None):
+    """mr_render_passes_plan: the passes of samples [sample_begin, sample_end) of a frame of `samples` samples per pixel rendered
+    at a pass size of `spp`, as a list of (base, spp); host only."""
+    pd, n = passes_desc(samples, sample_begin, sample_end), C.c_uint32(0)
+    _check(lib().mr_render_passes_plan(spp, C.byref(pd), C.byref(n), None, None, 0))
+    base, size = (C.c_uint32 * n.value)(), (C.c_uint32 * n.value)()
+    _check(lib().mr_render_passes_plan(spp, C.byref(pd), C.byref(n), base, size, n.value))
+    return list(zip(base, size))
 
 
 class Material(C.Structure):
@@ -385,7 +409,7 @@ def load_library(path=None):
     L.mr_irradiance_estimate.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, vp, vp, vp, vp]
     L.mr_photon_map_count_stats.argtypes = [vp, C.c_int32]
     L.mr_photon_map_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int32]
-    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS + LENS_SYMBOLS:
+    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS + LENS_SYMBOLS + PASSES_SYMBOLS:
         if not hasattr(L, name):
             raise OSError("%s does not export %s" % (path, name))
     lens = [C.POINTER(LensDesc)]                                   # `lens` follows `frame` (miro_hip_lens.h)
@@ -393,8 +417,14 @@ def load_library(path=None):
     L.mr_render_recursion_lens.argtypes = L.mr_render_recursion.argtypes[:2] + lens + L.mr_render_recursion.argtypes[2:]
     L.mr_render_recursion_photons_lens.argtypes = (L.mr_render_recursion_photons.argtypes[:2] + lens +
                                                    L.mr_render_recursion_photons.argtypes[2:])
+    passes = [C.POINTER(PassesDesc)]                               # `passes` follows the recursion descriptor (miro_hip_passes.h)
+    L.mr_render_passes_plan.argtypes = [C.c_uint32, C.POINTER(PassesDesc), u32p, u32p, u32p, C.c_uint32]
+    L.mr_render_recursion_passes.argtypes = L.mr_render_recursion_lens.argtypes[:4] + passes + L.mr_render_recursion_lens.argtypes[4:]
+    L.mr_render_recursion_photons_passes.argtypes = (L.mr_render_recursion_photons_lens.argtypes[:4] + passes +
+                                                     L.mr_render_recursion_photons_lens.argtypes[4:])
+    L.mr_finish_image.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
     for name in (EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS +
-                 LENS_SYMBOLS):
+                 LENS_SYMBOLS + PASSES_SYMBOLS):
         if hasattr(L, name) and getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = C.c_int32
     _lib = L
@@ -995,6 +1025,50 @@ class Scene:
                         (_map_handle(global_map), _map_handle(caustic_map), max_dist, nphotons), cam, W, H, d_rgb, d_level_counts, depth,
                         d_workspace, queue_capacity, y0, y1, bands, spp, jitter, seed, tiled, flags, stream, children, environment, kinds,
                         path_seed, workspace_bytes)
+
+    def _recursion_passes(self, name, photon_args, cam, W, H, d_rgb, d_pass_counts, depth, samples, sample_begin, sample_end, lens,
+                          d_workspace, queue_capacity, y0, y1, bands, spp, jitter, seed, tiled, flags, stream, children, environment,
+                          kinds, path_seed, workspace_bytes):
+        """The two passes calls: the three descriptors, the lens (dict(aperture, focus_plane)) or NULL, and the call"""
+        fd = _frame_desc(cam, W, H, y0, y1, bands, spp, jitter, seed, tiled, flags)
+        rd = _recursion_desc(depth, children, environment, kinds, path_seed, queue_capacity)
+        pd = passes_desc(samples, sample_begin, sample_end)
+        ln = None if lens is None else C.byref(_lens_desc(lens["aperture"], lens["focus_plane"]))
+        _check(getattr(self.L, name)(self.h, C.byref(fd), ln, C.byref(rd), C.byref(pd), *photon_args, d_rgb.data_ptr(), _ptr(d_workspace),
+                                     _workspace_bytes(workspace_bytes, d_workspace), d_pass_counts.data_ptr(), _stream_ptr(stream)))
+
+    def render_recursion_passes(self, cam, W, H, d_rgb, d_pass_counts, depth, samples, sample_begin=0, sample_end=None, lens=None,
+                                d_workspace=None, queue_capacity=0, y0=0, y1=None, bands=None, spp=1, jitter=False, seed=168, tiled=False,
+                                flags=0, stream=None, children=MR_LEVEL_SPECULAR, environment=False,
+                                kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE, path_seed=168, workspace_bytes=None):
+        """mr_render_recursion_passes: samples [sample_begin, sample_end) (default: all) of a frame of `samples` samples per pixel
+        as render_recursion[_lens] (lens: dict(aperture, focus_plane) or None) enqueued once per pass of passes_plan(spp, ...).
+        A sample's key, path hash and child ids are those of a single launch at spp = samples, whatever the passes; a pixel is
+        the sum of its samples / samples.  The pass with base 0 stores, every other adds to d_rgb.  d_pass_counts: int64
+        [passes, depth + 1, 8], each block render_recursion's d_level_counts for that pass.  d_workspace: the parent call's for
+        `spp`, reused by the passes.  tiled must be False."""
+        self._recursion_passes("mr_render_recursion_passes", (), cam, W, H, d_rgb, d_pass_counts, depth, samples, sample_begin, sample_end,
+                               lens, d_workspace, queue_capacity, y0, y1, bands, spp, jitter, seed, tiled, flags, stream, children,
+                               environment, kinds, path_seed, workspace_bytes)
+
+    def render_recursion_photons_passes(self, cam, W, H, d_rgb, d_pass_counts, depth, samples, global_map, caustic_map, d_workspace,
+                                        sample_begin=0, sample_end=None, lens=None, queue_capacity=0, max_dist=1e10, nphotons=500, y0=0,
+                                        y1=None, bands=None, spp=1, jitter=False, seed=168, tiled=False, flags=0, stream=None,
+                                        children=MR_LEVEL_SPECULAR, environment=False,
+                                        kinds=MR_PATH_MIRROR | MR_PATH_REFRACT | MR_PATH_DIFFUSE, path_seed=168, workspace_bytes=None):
+        """mr_render_recursion_photons_passes: render_recursion_passes over render_recursion_photons[_lens], with that call's maps,
+        max_dist, nphotons and workspace (recursion_photons_workspace_bytes for `spp`)."""
+        self._recursion_passes("mr_render_recursion_photons_passes", (_map_handle(global_map), _map_handle(caustic_map), max_dist, nphotons),
+                               cam, W, H, d_rgb, d_pass_counts, depth, samples, sample_begin, sample_end, lens, d_workspace, queue_capacity,
+                               y0, y1, bands, spp, jitter, seed, tiled, flags, stream, children, environment, kinds, path_seed,
+                               workspace_bytes)
+
+    def finish_image(self, d_rgb, n_pixels, d_out8, d_minmax=None, stream=None):
+        """mr_finish_image (Scene.cpp:150-163, 184-197; Image.cpp:47-52): the maximum and minimum over all non-NaN channel values
+        of d_rgb [n_pixels, 3], every NaN channel replaced by that maximum, then tonemap's bytes into d_out8 (uint8
+        [n_pixels, 3]).  d_minmax: optional float32 [2], (maximum, minimum).  Two kernels, no read-back; the first call on a
+        scene must lie outside a graph capture."""
+        _check(self.L.mr_finish_image(self.h, d_rgb.data_ptr(), n_pixels, d_out8.data_ptr(), _ptr(d_minmax), _stream_ptr(stream)))
 
     def final_gather(self, global_map, caustic_map, d_rays, d_hits, n, d_scratch, d_rgb, max_dist=1e10, nphotons=500,
                      spp=1, stream=None):

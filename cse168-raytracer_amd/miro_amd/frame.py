@@ -345,6 +345,7 @@ class FrameRenderer:
         self.d_count = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.d_gather = None                            # final_gather's scratch, allocated on first use
         self.d_recursion = self.d_level_counts = None   # mr_render_recursion's workspace and counters, allocated on first use
+        self.d_pass_counts = self.d_bytes = None        # mr_render_recursion_passes' counters, finish()'s bytes: likewise
         # rgb: an external [n_pixels, 3] buffer to shade into (FrameGather.local on a multi-GPU node)
         self.d_rgb = torch.zeros((max(self.n_pixels, 1), 3), **f32) if rgb is None else rgb
         self.cam = binding.make_camera(desc["eye"], desc["lookat"], desc["up"], desc["fov"])
@@ -369,7 +370,7 @@ class FrameRenderer:
         own = [self.d_rays, self.d_hits, self.d_shadow_rays, self.d_shadow_hits, self.d_src, self.d_count, self.d_rgb]
         if self.tiled:
             own += [self.d_slots, self.d_slot_pixel]
-        own += [self.d_recursion, self.d_level_counts]
+        own += [self.d_recursion, self.d_level_counts, self.d_pass_counts, self.d_bytes]
         return sum(t.numel() * t.element_size() for t in own if t is not None)
 
     def _need_rays(self, what):
@@ -465,7 +466,7 @@ class FrameRenderer:
 
     def render_specular(self, depth=10, stream=None, path_tracing=False, path_seed=168, path_kinds=None, fused=False,
                         group_octants=False, lights=None, environment=None, photon_maps=None, nphotons=500, max_dist=1e10,
-                        surface_children=None, queue_capacity=None):
+                        surface_children=None, queue_capacity=None, samples=None):
         """Scene::traceScene with reflective / refractive materials (Scene.cpp:270-346) as wavefront bounces: every
         level traces its queue, shades it (weight x Phong::shade added to the ray's pixel), and emits the reflect /
         Fresnel / refract children of the next level by ballot compaction.  depth = TRACE_DEPTH (Miro.h:13): rays are
@@ -595,7 +596,16 @@ class FrameRenderer:
           "device_lens_path"           device  lights   yes  yes  -        as "device_lights_path" but for the lens; no lens, tiled=True
           "device_lens_photons"        device  lights   -    yes  yes      as "device_photons" but for the lens; no lens
           "device_lens_photons_path"   device  lights   yes  yes  yes      as "device_photons_path" but for the lens; no lens
-        On a scene with a texture table True and "auto" are False (above); the 14 strings are unchanged by it."""
+        On a scene with a texture table True and "auto" are False (above); the 14 strings are unchanged by it.
+        samples=S (fused="device_*" only; any other route raises ValueError): the frame has S samples per pixel, of any number,
+        rendered by ONE mr_render_recursion_passes (on a photons route mr_render_recursion_photons_passes) in passes of the
+        renderer's spp, the remainder as powers of two (binding.passes_plan) -- sample s of a pixel has the key, the path hash and
+        the child ids of a single launch at spp = S, whatever the pass size.  The workspace and queue_capacity are those of ONE
+        pass.  Returns per_level summed over the passes; RuntimeError names the first truncated pass.  The jitter is the
+        renderer's: FrameRenderer(spp=1, jitter=True) for one-sample passes.  Without `samples` nothing changes."""
+        if samples is not None and route_of(fused).driver != "device":
+            raise ValueError("render_specular: samples=%r needs a fused=\"device_*\" route (mr_render_recursion_passes); the other "
+                             "routes render the renderer's spp samples per pixel" % (samples,))
         plan = self._resolve(stream, path_tracing, path_seed, path_kinds, fused, group_octants, lights, environment, photon_maps,
                              nphotons, max_dist, surface_children)
         # this driver mixes library launches (on `stream`) with torch ops and .item() read-backs: they only order against
@@ -604,7 +614,7 @@ class FrameRenderer:
             if plan.route.driver == "frame":
                 return self._frame_levels(plan, depth)
             if plan.route.driver == "device":
-                return self._device_levels(plan, depth, queue_capacity)
+                return self._device_levels(plan, depth, queue_capacity, samples)
             self._need_rays("render_specular(fused=%r)" % (fused,))
             self.d_slots.zero_()
             queue = Queue(self.d_rays, None, None, None, None, self.n)      # the eye rays, in image order
@@ -817,12 +827,15 @@ class FrameRenderer:
             return getattr(self.scene, name), (), common
         return getattr(self.scene, name + "_lens"), (plan.lens["aperture"], plan.lens["focus_plane"]), common
 
-    def _device_levels(self, plan, depth, queue_capacity):
+    def _device_levels(self, plan, depth, queue_capacity, samples=None):
         """The "device" driver: ONE mr_render_recursion, or on a route with photons ONE mr_render_recursion_photons with the plan's
         maps, each through the thin lens on a lens route (_eye_call).  Then ONE read of the counters; returns (rays, shadow rays)
-        per level, cut at the first level without rays; RuntimeError if a level was truncated."""
+        per level, cut at the first level without rays; RuntimeError if a level was truncated.
+        samples: the frame's samples per pixel -- ONE mr_render_recursion[_photons]_passes instead (_device_passes)."""
         if self.n == 0 or depth < 0:
             return []
+        if samples is not None:
+            return self._device_passes(plan, depth, queue_capacity, int(samples))
         photons = plan.route.photons
         cap = plan.fan * self.n if queue_capacity is None else int(queue_capacity)
         children = binding.MR_LEVEL_PATH if plan.path_tracing else binding.MR_LEVEL_SPECULAR
@@ -856,6 +869,59 @@ class FrameRenderer:
                 raise RuntimeError("render_specular: level %d emitted %d children, queue_capacity is %d: the frame was truncated "
                                    "(%d x the samples always suffice)" % (level, row[5], cap, plan.fan ** depth))
         return per_level
+
+    def _device_passes(self, plan, depth, queue_capacity, samples):
+        """_device_levels for a frame of `samples` samples per pixel in passes of the renderer's spp: the workspace of ONE pass, the
+        counters of every pass, one call, one read-back; per_level summed over the passes."""
+        photons = plan.route.photons
+        cap = plan.fan * self.n if queue_capacity is None else int(queue_capacity)
+        children = binding.MR_LEVEL_PATH if plan.path_tracing else binding.MR_LEVEL_SPECULAR
+        _, _, common = self._eye_call(plan, "render_recursion")
+        if photons:
+            need = self.scene.recursion_photons_workspace_bytes(self.cam, self.W, self.H, depth, cap, y0=common["y0"], y1=common["y1"],
+                                                                spp=self.spp, children=children, environment=plan.environment,
+                                                                kinds=plan.path_kinds)
+        else:
+            need = self.scene.recursion_workspace_bytes(depth, cap, children=children, environment=plan.environment,
+                                                        kinds=plan.path_kinds)
+        n_passes = len(binding.passes_plan(self.spp, samples))
+        if self.d_recursion is None or self.d_recursion.numel() < need:
+            self.d_recursion = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        if self.d_pass_counts is None or self.d_pass_counts.shape[0] < n_passes or self.d_pass_counts.shape[1] != depth + 1:
+            self.d_pass_counts = torch.zeros((n_passes, depth + 1, 8), dtype=torch.int64, device=self.device)
+        common.update(lens=plan.lens, queue_capacity=cap, children=children, workspace_bytes=need)
+        if photons:
+            self.scene.render_recursion_photons_passes(self.cam, self.W, self.H, self.d_rgb, self.d_pass_counts, depth, samples,
+                                                       plan.photon_maps[0], plan.photon_maps[1], self.d_recursion,
+                                                       max_dist=plan.max_dist, nphotons=plan.nphotons, **common)
+        else:
+            self.scene.render_recursion_passes(self.cam, self.W, self.H, self.d_rgb, self.d_pass_counts, depth, samples,
+                                               d_workspace=self.d_recursion if depth > 0 else None, **common)
+        host = self.d_pass_counts[:n_passes].tolist()               # the one read-back of the frame
+        total = [[0, 0] for _ in range(depth + 1)]
+        for index, block in enumerate(host):
+            for level, row in enumerate(block):
+                total[level][0] += row[0]
+                total[level][1] += row[1]
+                if level < depth and row[5] > cap:
+                    raise RuntimeError("render_specular: pass %d, level %d emitted %d children, queue_capacity is %d: the frame was "
+                                       "truncated (%d x a pass's samples always suffice)" % (index, level, row[5], cap, plan.fan ** depth))
+        per_level = []
+        for rays, shadow in total:
+            if rays == 0:
+                break
+            per_level.append((rays, shadow))
+        return per_level
+
+    def finish(self, d_minmax=None, stream=None):
+        """mr_finish_image on d_rgb (Scene.cpp:150-163, 184-197; Image.cpp:47-52): the image's maximum over its non-NaN channel
+        values in place of every NaN channel, then the tone map.  Returns the bytes, a uint8 tensor [n_pixels, 3] that the
+        renderer keeps."""
+        if self.d_bytes is None:
+            self.d_bytes = torch.zeros((max(self.n_pixels, 1), 3), dtype=torch.uint8, device=self.device)
+        if self.n_pixels:
+            self.scene.finish_image(self.d_rgb, self.n_pixels, self.d_bytes, d_minmax=d_minmax, stream=stream)
+        return self.d_bytes
 
     def _frame_level0(self, plan, last):
         """Level 0 as ONE mr_render_level_lights[_lens] straight into d_rgb (then mr_gather_level, with photon maps, on generate()'s

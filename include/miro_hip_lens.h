@@ -61,4 +61,6 @@ mr_status mr_render_recursion_photons_lens(mr_scene *scene, const mr_frame_desc 
 #ifdef __cplusplus
 }
 #endif
+/* the frames of more than 64 samples per pixel and the image finish, below the declarations they build on */
+#include "miro_hip_passes.h"
 #endif /* MIRO_HIP_LENS_H */
