@@ -1040,18 +1040,50 @@ mr_status mr_shade_accumulate(mr_scene *s, const mr_ray *d_rays, const mr_hit *d
                                    d_rgb, textured ? &tex : nullptr, static_cast<hipStream_t>(stream));
 }
 
-mr_status mr_gen_secondary_rays(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
-                                const uint32_t *d_pixels, uint64_t n, uint32_t spp, mr_ray *d_out_rays, float *d_out_weights,
-                                uint32_t *d_out_pixels, uint64_t *d_count, uint64_t out_capacity, uint8_t *d_out_octants, void *stream) {
-    mr_status st = require_device(s);
+// What mr_gen_secondary_rays and mr_gen_secondary_rays_surface ask, in this order.  surface: the _surface call, which takes
+// d_normal besides and reads every hit's N from it, so that a reflective STONE material is no reason to refuse.
+static mr_status check_gen_secondary_rays(const char *who, bool surface, mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits,
+                                          const float *d_normal, uint64_t n, uint32_t spp, const mr_ray *d_out_rays,
+                                          const float *d_out_weights, const uint32_t *d_out_pixels, const uint64_t *d_count,
+                                          uint64_t out_capacity) {
+    const mr_status st = require_device(s);
     if (st != MR_OK) return st;
     if (!d_rays || !d_hits || !d_out_rays || !d_out_weights || !d_out_pixels || !d_count) return fail(MR_ERR_INVALID, "NULL argument");
     if (spp == 0) return fail(MR_ERR_INVALID, "spp is 0");
     if (n / spp > 0xFFFFFFFFull) return fail(MR_ERR_INVALID, "too many pixels");
-    if (out_capacity == 0 && n > 0) return fail(MR_ERR_INVALID, "mr_gen_secondary_rays: out_capacity is 0 (room for 3n rays always suffices)");
+    if (out_capacity == 0 && n > 0) return fail(MR_ERR_INVALID, "%s: out_capacity is 0 (room for 3n rays always suffices)", who);
+    if (surface && !d_normal) return fail(MR_ERR_INVALID, "%s: d_normal is NULL", who);
+    if (surface && misaligned(4, d_normal)) return fail(MR_ERR_INVALID, "%s: d_normal must be 4-byte aligned", who);
+    if (!surface && s->tex.bumped_specular)                   // Ray::reflect bounces about N, which this call does not bump
+        return fail(MR_ERR_STATE, "%s: a material of the scene names a STONE texture and has a non-zero ks (its mirror child bounces "
+                                  "about the bump-mapped normal, which this call does not have; mr_gen_secondary_rays_surface reads "
+                                  "mr_hit_surface's normal)", who);
+    return MR_OK;
+}
+
+mr_status mr_gen_secondary_rays(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
+                                const uint32_t *d_pixels, uint64_t n, uint32_t spp, mr_ray *d_out_rays, float *d_out_weights,
+                                uint32_t *d_out_pixels, uint64_t *d_count, uint64_t out_capacity, uint8_t *d_out_octants, void *stream) {
+    const mr_status st = check_gen_secondary_rays("mr_gen_secondary_rays", false, s, d_rays, d_hits, nullptr, n, spp, d_out_rays,
+                                                  d_out_weights, d_out_pixels, d_count, out_capacity);
+    if (st != MR_OK) return st;
     MR_HIP_CHECK(hipSetDevice(s->device));
     return launch_secondary_rays(s->dev, d_rays, d_hits, d_weights, d_pixels, n, spp, d_out_rays, d_out_weights, d_out_pixels,
                                  reinterpret_cast<unsigned long long *>(d_count), out_capacity, d_out_octants, static_cast<hipStream_t>(stream));
+}
+
+// ... about the normal Scene::trace hands on (include/miro_hip_bump.h, mr_bump_surface.hip)
+mr_status mr_gen_secondary_rays_surface(mr_scene *s, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_normal,
+                                        const float *d_weights, const uint32_t *d_pixels, uint64_t n, uint32_t spp, mr_ray *d_out_rays,
+                                        float *d_out_weights, uint32_t *d_out_pixels, uint64_t *d_count, uint64_t out_capacity,
+                                        uint8_t *d_out_octants, void *stream) {
+    const mr_status st = check_gen_secondary_rays("mr_gen_secondary_rays_surface", true, s, d_rays, d_hits, d_normal, n, spp, d_out_rays,
+                                                  d_out_weights, d_out_pixels, d_count, out_capacity);
+    if (st != MR_OK) return st;
+    MR_HIP_CHECK(hipSetDevice(s->device));
+    return launch_secondary_rays_surface(s->dev, d_rays, d_hits, d_normal, d_weights, d_pixels, n, spp, d_out_rays, d_out_weights,
+                                         d_out_pixels, reinterpret_cast<unsigned long long *>(d_count), out_capacity, d_out_octants,
+                                         static_cast<hipStream_t>(stream));
 }
 
 // What mr_gen_path_rays and mr_gen_path_rays_surface ask, in this order.  surface: the _surface call, which takes d_color /
@@ -1075,6 +1107,10 @@ static mr_status check_gen_path_rays(const char *who, bool surface, mr_scene *s,
         return fail(MR_ERR_STATE, "%s: MR_PATH_DIFFUSE on a scene whose texture table holds a procedural texture (STONE, STEM, "
                                   "PETAL, LEAF or FLOWER_CENTER; Ray::random bounces about the un-bumped N here; mr_gen_path_rays_surface "
                                   "reads mr_hit_surface's normal and colour)", who);
+    if (!surface && (kinds & 1u) && s->tex.bumped_specular)   // MR_PATH_MIRROR: the lobe lies about Ray::reflect's direction, likewise
+        return fail(MR_ERR_STATE, "%s: MR_PATH_MIRROR on a scene with a material that names a STONE texture and has a non-zero ks (its "
+                                  "mirror child bounces about the bump-mapped normal, which this call does not have; "
+                                  "mr_gen_path_rays_surface reads mr_hit_surface's normal and colour)", who);
     return MR_OK;
 }
 
@@ -1229,6 +1265,7 @@ static mr_status lights_scene_params(mr_scene *s, bool environment, void *stream
     ls.ds = &s->dev;
     ls.lights = s->lights.data();
     ls.n_lights = (uint32_t)s->lights.size();
+    ls.bumped_specular = s->tex.bumped_specular;
     TexParams &tex = ls.tex;
     tex.recs = nullptr; tex.texels = nullptr; tex.mat_tex = nullptr; tex.texcoords = s->dev.texcoords; tex.ti = s->dev.ti;
     if (!s->tex.blob.empty() && (st = texture_params(s, static_cast<hipStream_t>(stream), tex)) != MR_OK) return st;
@@ -2114,7 +2151,8 @@ mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, ui
     for (uint32_t i = 0; i < n_textures; i++) {
         const mr_texture_desc &in = textures[i];
         if (in.kind > MR_TEX_FLOWER_CENTER) return fail(MR_ERR_INVALID, "texture %u: unknown kind %u", i, in.kind);
-        for (int k = 0; k < 5; k++)
+        // reserved[0] of a STONE texture is its flag word (miro_hip_bump.h): MR_TEX_REFLECTIVE or 0
+        for (int k = (in.kind == MR_TEX_STONE && in.reserved[0] == MR_TEX_REFLECTIVE) ? 1 : 0; k < 5; k++)
             if (in.reserved[k] != 0) return fail(MR_ERR_INVALID, "texture %u: mr_texture_desc.reserved must be 0", i);
         if (in.kind == MR_TEX_CHECKER) {
             for (int c = 0; c < 3; c++)
@@ -2145,19 +2183,36 @@ mr_status mr_scene_set_textures(mr_scene *s, const mr_texture_desc *textures, ui
         for (uint32_t i = 0; i < n_mats; i++)
             if (material_texture[i] != kNoTexture && material_texture[i] >= n_textures)
                 return fail(MR_ERR_INVALID, "material %u names texture %u of %u", i, material_texture[i], n_textures);
-    // a bump-mapped material is diffuse only, as the reference's own are (assignment1.cpp:232,313): the reflect / refract
-    // generators and the light through a refractive occluder (Phong.cpp:99-113) work on the un-bumped N.
-    // mr_render_level_lights RESTS on this rule (and on mr_scene_set_materials being refused while a table is set): its specular
-    // children bounce about the normal of the surface step, which is the object's own on every material but STONE
-    // (mr_frame_lights_surface_body.h, the children step).  Whoever relaxes the rule gives that kernel the hit record back.
+    // A bump-mapped material may reflect (ks != 0; the reference's author tried one, assignment1.cpp:134) where its texture says
+    // MR_TEX_REFLECTIVE, and may not transmit: the light through a refractive occluder reads the occluder's N (Phong.cpp:99-113),
+    // which no shadow loop here bumps, and with kt == 0 a STONE material never is such an occluder.  The flag is the caller's word
+    // that it renders the scene through the calls that have the bumped normal: without it the table is refused as it always was,
+    // here, at set-up, and not by mr_gen_secondary_rays in the middle of a frame.  A reflective one is remembered
+    // (bumped_specular): its mirror
+    // child bounces about the normal Scene::trace hands on (Scene.cpp:234-263, Ray.h:156), so every route takes the children's N
+    // from the surface step -- mr_gen_secondary_rays_surface and the PATH generators' _surface form from mr_hit_surface's buffer,
+    // the BUMPED level kernels (mr_level_lights_bump.hip, mr_level_lights_queued_bump.hip), the fused frames and the PATH level
+    // kernels from their own surface step -- and the two generators that compute the object's normal refuse the scene.  The flag
+    // holds while the table does: mr_scene_set_materials is refused while a table is set.
     if (material_texture)
         for (uint32_t i = 0; i < n_mats; i++) {
             if (material_texture[i] == kNoTexture || textures[material_texture[i]].kind != MR_TEX_STONE) continue;
             const float *o = &s->materials[11 * (size_t)i];
-            for (int c = 3; c < 9; c++)
+            for (int c = 6; c < 9; c++)
                 if (o[c] != 0.0f)
-                    return fail(MR_ERR_INVALID, "material %u names the STONE texture %u and has a non-zero ks or kt: a bump-mapped "
-                                                "material must be diffuse only", i, material_texture[i]);
+                    return fail(MR_ERR_INVALID, "material %u names the STONE texture %u and has a non-zero kt: a bump-mapped material "
+                                                "has no transmission (light through a refractive occluder reads the occluder's N, "
+                                                "Phong.cpp:99-113, and the shadow loops do not bump it); ks may be non-zero",
+                                i, material_texture[i]);
+            for (int c = 3; c < 6; c++)
+                if (o[c] != 0.0f) {
+                    if (textures[material_texture[i]].reserved[0] != MR_TEX_REFLECTIVE)
+                        return fail(MR_ERR_INVALID, "material %u names the STONE texture %u and has a non-zero ks: a bump-mapped material "
+                                                    "reflects only where the texture says MR_TEX_REFLECTIVE (mr_texture_desc.reserved[0], "
+                                                    "miro_hip_bump.h: its mirror child bounces about the bumped normal, which "
+                                                    "mr_gen_secondary_rays does not have)", i, material_texture[i]);
+                    h.bumped_specular = true;
+                }
         }
 
     h.texel_base = 3 * (size_t)n_textures;

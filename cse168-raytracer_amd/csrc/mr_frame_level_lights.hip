@@ -12,8 +12,9 @@
 // slots zeroed, mr_gen_eye_rays' 32 bytes per sample written to HBM and read back twice, the pixel re-derived from the ray index
 // and float atomics for a sum whose terms all sit in one wave.  Here the kernel is frame_lights_surface_body<VAR, false, true,
 // CHILDREN>: the frame body with the level kernels' last step in it, with the eye as the ray's origin, weight 1 and pixel row * W + x --
-//   CHILDREN 1 (MR_LEVEL_SPECULAR)  rec::ChildGen<false> about the object's own normal -- the surface step's, which only a STONE
-//                                   material bumps, and such a material has no specular child -- rec::write_children
+//   CHILDREN 1 (MR_LEVEL_SPECULAR)  rec::ChildGen<false> about the normal Scene::trace hands on -- the surface step's, which only a STONE
+//                                   material bumps (a reflective one's mirror child bounces about the bumped normal, as the
+//                                   BUMPED level kernels' do) -- rec::write_children
 //   CHILDREN 2 (MR_LEVEL_PATH)      rec::ChildGen<true> about the normal of the surface step, hray = pcg32(pcg32(seed) ^ sample
 //                                   index), the diffuse child with the looked-up colour, write_children_col (mr_children_col.h)
 // -- one body with one more template argument, not a second body: with CHILDREN == 0 nothing of it is compiled, and the records

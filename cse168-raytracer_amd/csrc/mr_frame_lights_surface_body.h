@@ -15,9 +15,9 @@
 // (mr_frame_level_lights.hip, mr_render_level_lights):
 //   0  none: the two frames above; nothing of FrameChildArgs is read and the code is what it was (their records hold)
 //   1  the reflect / Fresnel / refract children of mr_level_lights.hip's last step: rec::ChildGen<false>, rec::write_children,
-//      about the object's own normal -- which is taken from the surface step, not computed again from the hit record: the step
-//      bumps the normal on a STONE material only, and such a material has no specular child (the children step says on what
-//      that rests)
+//      about the normal of the surface step, the one Scene::trace hands on (the step bumps it on a STONE material only): the
+//      object's own wherever no STONE material reflects, the bumped one on a reflective STONE (the children step says which
+//      level kernels that matches)
 //   2  the PATH_TRACING children of mr_level_lights_path.hip's last step: rec::ChildGen<true> about the normal of the surface
 //      step (the bumped one on stone), the diffuse child with the looked-up colour, write_children_col -- the bumped normal and
 //      the colour are the light loop's own
@@ -202,11 +202,12 @@ __device__ __forceinline__ void frame_lights_surface_body(const FrameLightsSurfa
                 if (refl || refr || diff) {
                     // The hit point and the normal of the surface step, not rebuilt from the hit record.  P is surface_od's for this very ray and record: the bits
                     // surface_point_od(eye, d, h) gives the level kernels.  N is normalize3 of surface_od's normal, bumped before
-                    // on a STONE material only (hit_color_normal): what CHILDREN == 2 asks for; and for CHILDREN == 1, whose
-                    // children bounce about the object's own normal, the same bits wherever a child exists -- a material that
-                    // names a STONE texture has ks = kt = 0 (mr_scene_set_textures refuses any other, and mr_scene_set_materials
-                    // is refused while a table is set; both in mr_api.cpp, which names this dependence), and on every other hit
-                    // N is surface_point_od's normalize3 of the same three values.
+                    // on a STONE material only (hit_color_normal): the normal Scene::trace hands on, which is what both builds'
+                    // children bounce about (Ray.h:156).  CHILDREN == 2 asks for it on every scene.  For CHILDREN == 1 it is
+                    // the level kernels' N on every scene too: where no STONE material reflects (mr_scene_set_textures:
+                    // bumped_specular; none transmits) N is surface_point_od's normalize3 of the same three values wherever a
+                    // child exists, and where one does the level kernels run their BUMPED form (mr_level_lights_body.h), which
+                    // takes the surface step's N as this step does.
                     for (int c = 0; c < 3; c++) { g.P[c] = P[c]; g.N[c] = N[c]; }
                     g.d[0] = d[0]; g.d[1] = d[1]; g.d[2] = d[2];
                     g.w0[0] = 1.f; g.w0[1] = 1.f; g.w0[2] = 1.f;

@@ -266,6 +266,12 @@ mr_status launch_secondary_rays(const DeviceScene &ds, const mr_ray *d_rays, con
                                 float *d_out_weights, uint32_t *d_out_pixels, unsigned long long *d_count,
                                 unsigned long long out_capacity, uint8_t *d_out_octants, hipStream_t stream);
 
+// ... with every hit's N read from the surface pass's normal buffer (mr_bump_surface.hip, mr_gen_secondary_rays_surface)
+mr_status launch_secondary_rays_surface(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_normal,
+                                        const float *d_weights, const uint32_t *d_pixels, unsigned long long n, uint32_t spp,
+                                        mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels, unsigned long long *d_count,
+                                        unsigned long long out_capacity, uint8_t *d_out_octants, hipStream_t stream);
+
 // PATH_TRACING generators (mr_bounce.hip): kinds bit 0 mirror, 1 refraction pair, 2 diffuse bounce
 mr_status launch_path_rays(const DeviceScene &ds, const mr_ray *d_rays, const mr_hit *d_hits, const float *d_weights,
                            const uint32_t *d_pixels, const uint32_t *d_ids, unsigned long long n, uint32_t spp, uint32_t seed,
@@ -319,6 +325,13 @@ mr_status launch_level_lights(const LightScene &ls, const mr_level_lights_desc &
                               const uint32_t *d_pixels, unsigned long long n, float *d_rgb, mr_hit *d_hits, float *d_ray_rgb,
                               float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
                               unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
+// ... with specular children on a scene whose reflective STONE material bump-maps the mirror direction (ls.bumped_specular;
+// mr_level_lights_bump.hip): launch_level_lights hands a level with children on such a scene on to this one, which zeroes
+// d_out_count and launches level_lights_body's BUMPED form -- the children bounce about the surface step's normal
+mr_status launch_level_lights_bumped(const LightScene &ls, const mr_level_lights_desc &ld, const mr_ray *d_rays, const float *d_weights,
+                                     const uint32_t *d_pixels, unsigned long long n, float *d_rgb, mr_hit *d_hits, float *d_ray_rgb,
+                                     float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
+                                     unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream);
 // ... of a PATH_TRACING build (mr_level_lights_path.hip, mr_trace_level_lights_path): the same level with the children of
 // mr_gen_path_rays_surface (ids in and out, ld.path_kinds / seed / bounce), the low-res environment image for the rays that
 // ld.d_lowres or MR_ENV_LOWRES names, and ld.d_out_lowres for the next level
@@ -387,6 +400,11 @@ mr_status launch_zero_words(unsigned long long *d_words, unsigned long long n, h
 mr_status launch_level_lights_queued(const LightScene &ls, const QueuedLevel &lv, const RayQueue &in, const RayQueue &out,
                                      const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_rgb,
                                      mr_hit *d_hits, float *d_normal, unsigned long long *row, hipStream_t stream);
+// ... its specular level with children on a scene with ls.bumped_specular (mr_level_lights_queued_bump.hip), to which
+// launch_level_lights_queued hands such a level on: the BUMPED form of the same kernel, the same grid
+mr_status launch_level_lights_queued_bumped(const LightScene &ls, const QueuedLevel &lv, const RayQueue &in, const RayQueue &out,
+                                            const unsigned long long *d_n, unsigned long long n_cap, unsigned long long n_bound, float *d_rgb,
+                                            mr_hit *d_hits, float *d_normal, unsigned long long *row, hipStream_t stream);
 
 // the thin-lens camera and Phong::shade over SquareLights (mr_distribution.hip).  side: the sample cells along an edge of a
 // square light, side * side shadow rays per hit and light
@@ -412,6 +430,8 @@ struct HostTextures {
     size_t texel_base = 0, mat_base = 0;       // offsets into blob, in float4
     std::vector<float4> blob;                  // empty: the scene has no texture table
     bool procedural = false;                   // some texture is a STONE, a STEM or a UVW kind: only the _surface calls shade such a scene
+    bool bumped_specular = false;              // some material names a STONE texture and has ks != 0: its mirror child bounces about
+                                               // the bumped normal, which only the surface pass (or a fused surface step) has
 };
 struct TexParams {                             // the table as the kernels take it
     const float4 *recs;                        // 3 per texture: (kind, W, H, first texel as bits) (color1 | max_intensity, hdr) (color2)
@@ -490,6 +510,7 @@ struct LightScene {
     EnvParams env;
     const ShadeLight *lights;
     uint32_t n_lights;
+    bool bumped_specular = false;              // HostTextures::bumped_specular: the specular level kernels take their BUMPED form
 };
 
 // photon map on the device: three float4 planes in kd-tree heap order, 1-based (children of i: 2i, 2i+1)

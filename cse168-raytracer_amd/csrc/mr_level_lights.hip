@@ -11,9 +11,13 @@
 //   mr_trace -> mr_shade_environment -> mr_hit_surface -> mr_shade_lights_surface -> mr_gen_secondary_rays;
 // tests/test_level_lights.py compares level by level on the same queues.
 //
-// The children bounce about the normal and material mr_gen_secondary_rays uses -- the object's own normal, normalised, not the
-// bumped one; a stone material has ks = kt = 0 by rule and no children.  A specular child is never isDiffuse: the low-res image
-// is not read.  Times against the batched route: DESIGN section 5c, profiles/level_lights_ab.log.
+// The children bounce about the normal and material mr_gen_secondary_rays uses -- the object's own normal, normalised.  That is
+// the normal Scene::trace hands on wherever a child exists, unless a STONE material reflects (mr_scene_set_textures:
+// bumped_specular; a STONE material never transmits): a level with children on such a scene is handed on to
+// mr_level_lights_bump.hip, whose kernels are this body with BUMPED set and take the children's N from the surface step, as
+// mr_gen_secondary_rays_surface reads it from mr_hit_surface's buffer.  A unit of its own so that this unit's twelve kernels and
+// their record stay what they are.  A specular child is never isDiffuse: the low-res image is not read.  Times against the
+// batched route: DESIGN section 5c, profiles/level_lights_ab.log.
 //
 // Live state, besides what the body lists: the children's own normal is computed again from the hit record.  Four waves per SIMD,
 // as every frame_lights_env_kernel: at six the specular level_kernel of mr_level.hip already spills 30 VGPRs without a light loop
@@ -59,6 +63,9 @@ mr_status launch_level_lights(const LightScene &ls, const mr_level_lights_desc &
                               const uint32_t *d_pixels, unsigned long long n, float *d_rgb, mr_hit *d_hits, float *d_ray_rgb,
                               float *d_color, float *d_normal, mr_ray *d_out_rays, float *d_out_weights, uint32_t *d_out_pixels,
                               unsigned long long *d_out_count, unsigned long long *d_counts, hipStream_t stream) {
+    if (ls.bumped_specular && ld.children != MR_LEVEL_LAST)
+        return launch_level_lights_bumped(ls, ld, d_rays, d_weights, d_pixels, n, d_rgb, d_hits, d_ray_rgb, d_color, d_normal, d_out_rays,
+                                          d_out_weights, d_out_pixels, d_out_count, d_counts, stream);
     if (ld.children != MR_LEVEL_LAST) {
         const mr_status zs = launch_zero_count(d_out_count, stream);
         if (zs != MR_OK) return zs;

@@ -9,8 +9,8 @@
 //   its pixel  ->  the children of the next level (Scene.cpp:302-336), compacted into the next queue
 //
 // One ray per lane.  PATH says which build of the reference the level is; the two differ in two steps only:
-//   false  a miss reads the full image (env_lookup_full); the children are Ray::reflect / getReflectionCoefficient / refract about
-//          the object's own normal: rec::ChildGen<false>, rec::write_children (mr_level_lights.hip)
+//   false  a miss reads the full image (env_lookup_full); the children are Ray::reflect / getReflectionCoefficient / refract:
+//          rec::ChildGen<false>, rec::write_children (mr_level_lights.hip).  About which normal is BUMPED's to say (below)
 //   true   a miss of a ray that is isDiffuse reads the low-res copy (env_lookup); the children are the PATH_TRACING build's, about
 //          the normal Scene::trace hands on and with the looked-up colour: rec::ChildGen<true>, write_children_col
 //          (mr_level_lights_path.hip).  Only this form reads the fields that LevelLightsPathArgs has besides.
@@ -100,7 +100,14 @@ struct LevelLightsPathArgs {
 // QUEUED: where the queue's length comes from -- false: a.tp.n, the host knows it; true: n_queued, a wave-uniform word the kernel
 // read from the device (mr_level_lights_queued.hip), and a.tp.n is not read.  A template argument and not a wrapper that hands
 // a.tp.n on: a second by-value layer around the block moves it out of the scalar registers (mr_lights_body.h).
-template <int VAR, int CHILDREN, bool PATH, bool QUEUED = false, typename ARGS>
+// BUMPED (read with PATH false and CHILDREN 1 only): about which normal the specular children bounce --
+//   false  the object's own, rebuilt from the hit record with the hit point (surface_point_od): mr_gen_secondary_rays' bits.  The
+//          launchers pick it on every scene without a reflective STONE material, where the surface step's N is that normal
+//          wherever a child exists;
+//   true   the surface step's N, the one Scene::trace hands on (Scene.cpp:234-263), as the PATH arm takes it: the bits
+//          mr_gen_secondary_rays_surface reads from mr_hit_surface's buffer.  For a scene with bumped_specular
+//          (mr_level_lights_bump.hip, mr_level_lights_queued_bump.hip).  N is live through the light loop either way.
+template <int VAR, int CHILDREN, bool PATH, bool QUEUED = false, bool BUMPED = false, typename ARGS>
 __device__ __forceinline__ void level_lights_body(const ARGS a, int *s_stack, uint32_t (&s_tab)[128], const unsigned long long n_queued = 0ull) {
     const NoiseTables nt = stage_noise_tables(s_tab);
     const int tid = threadIdx.x;
@@ -201,8 +208,10 @@ __device__ __forceinline__ void level_lights_body(const ARGS a, int *s_stack, ui
                     surface_point_od(a.m, ra.x, ra.y, ra.z, d[0], d[1], d[2], h.t, h.prim, h.beta, h.gamma, g.P, g.N);
                     g.d[0] = d[0]; g.d[1] = d[1]; g.d[2] = d[2];
                     g.w0[0] = w0[0]; g.w0[1] = w0[1]; g.w0[2] = w0[2];
-                    if constexpr (PATH) {
+                    if constexpr (PATH || BUMPED) {
                         g.N[0] = N[0]; g.N[1] = N[1]; g.N[2] = N[2];   // (the object's normal is overwritten before anything reads it)
+                    }
+                    if constexpr (PATH) {
                         id = a.ids ? a.ids[k] : (uint32_t)k;
                         g.hray = pcg32(a.hbase ^ id) + a.bounce * 4u;
                     }
@@ -220,6 +229,14 @@ __device__ __forceinline__ void level_lights_body(const ARGS a, int *s_stack, ui
         workgroup_add<kTraceBlock>(mine, &a.counts[1]);
         if (blockIdx.x == 0 && tid == 0) atomicAdd(&a.counts[0], n);
     }
+}
+
+// A queue whose length is a word on the device (mr_level_lights_queued.hip says why): the length, and whether this workgroup has
+// a ray of it
+__device__ __forceinline__ bool queued_length(const unsigned long long *d_n, unsigned long long n_cap, unsigned long long &n) {
+    const unsigned long long have = *d_n;             // every lane, one address: wave-uniform
+    n = have < n_cap ? have : n_cap;
+    return (unsigned long long)xcd_block_id() * kTraceBlock < n;
 }
 
 // what every level launch puts into its block, of either build.  in: the queue the level reads, its first n rays (rays, weights,

@@ -40,14 +40,8 @@ namespace {
 #define MIRO_LEVEL_LIGHTS_QUEUED_WAVES 4
 #endif
 
-// the queue's length, and whether this workgroup has a ray of it
-__device__ __forceinline__ bool queued_length(const unsigned long long *d_n, unsigned long long n_cap, unsigned long long &n) {
-    const unsigned long long have = *d_n;             // every lane, one address: wave-uniform
-    n = have < n_cap ? have : n_cap;
-    return (unsigned long long)xcd_block_id() * kTraceBlock < n;
-}
-
 // VAR, CHILDREN: as in level_lights_kernel / level_lights_path_kernel.  The arguments are taken BY VALUE (mr_lights_body.h says why).
+// queued_length (mr_level_lights_body.h): the queue's length, and whether this workgroup has a ray of it.
 template <int VAR, int CHILDREN>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(MIRO_LEVEL_LIGHTS_QUEUED_WAVES, 8))) void level_lights_queued_kernel(
     const LevelLightsArgs a, const unsigned long long *d_n, const unsigned long long n_cap) {
@@ -93,6 +87,8 @@ mr_status launch_level_lights_queued(const LightScene &ls, const QueuedLevel &lv
                                      mr_hit *d_hits, float *d_normal, unsigned long long *row, hipStream_t stream) {
     const DeviceScene &ds = *ls.ds;
     const unsigned grid = level_lights_queued_grid(n_cap, n_bound);
+    if (ls.bumped_specular && !lv.path && !lv.last)   // the children bounce about the bumped normal: mr_level_lights_queued_bump.hip
+        return launch_level_lights_queued_bumped(ls, lv, in, out, d_n, n_cap, n_bound, d_rgb, d_hits, d_normal, row, stream);
     auto fill = [&](auto &a) {
         fill_level_lights_args(a, ls, lv.spp, lv.environment, in, 0ull, d_rgb, d_hits, nullptr, nullptr, d_normal, out, row + 5, lv.capacity,
                                nullptr, row);

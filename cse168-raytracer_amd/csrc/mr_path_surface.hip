@@ -7,8 +7,9 @@
 //                          the buffers hold the object's normal and the material's colour, and the children are the plain
 //                          kernel's bit for bit.
 //
-// There is no surface form of the non-path generators: they emit no diffuse child, a STONE material must have ks = kt = 0, and
-// nothing bumps another material's normal.
+// The surface form of the non-path generators is mr_bump_surface.hip (mr_gen_secondary_rays_surface): they emit no diffuse child
+// and read the normal buffer alone, for the mirror child of a STONE material with ks != 0 (a STONE material has kt = 0, and
+// nothing bumps another material's normal).
 //
 // A unit of its own because the kernels of mr_bounce.hip are held to tests/golden/kernel_budget.json; this unit's record is
 // kernel_budget_path_surface.json.  Compiled with -ffp-contract=off like the rest of the library.

@@ -10,7 +10,7 @@
 //                   term and the highlight, as Phong.cpp:139,151 read hit.N.  P is still rebuilt from ray and hit.  Both
 //                   buffers are read for rays with a hit only: mr_hit_surface leaves the six floats of a miss untouched.
 // The occluder's side keeps the object's own normal in both forms: light_scale_of reads the shadow hit's normal
-// (Phong.cpp:102-109) only for a refractive occluder, a STONE material must have ks = kt = 0 and so never is one, and nothing
+// (Phong.cpp:102-109) only for a refractive occluder, a STONE material must have kt = 0 (ks is free) and so never is one, and nothing
 // bumps a UVW material -- the bumped normal and the object's are the same wherever that arm looks.
 // kColorSurface keeps the colour (three registers) across up to 64 shadow traversals per light.  The arguments are taken BY
 // VALUE, for the reason mr_lights_body.h gives; the two buffers are kernel arguments of their own rather than fields of

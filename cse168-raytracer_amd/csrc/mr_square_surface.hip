@@ -8,7 +8,7 @@
 //                                     normal and the light is the plain kernel's.
 //
 // The shadow side is untouched: light_scale_of reads the occluder's own normal for a refractive occluder alone
-// (Phong.cpp:102-109), a STONE material must have ks = kt = 0 and so is never one, and nothing bumps a UVW material.
+// (Phong.cpp:102-109), a STONE material must have kt = 0 (ks is free) and so is never one, and nothing bumps a UVW material.
 //
 // A unit of its own because the kernel lists of mr_distribution.hip and mr_procedural.hip are held to their records
 // (tests/golden/kernel_budget_distribution.json, kernel_budget_procedural.json); this unit's record is

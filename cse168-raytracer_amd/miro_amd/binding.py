@@ -40,6 +40,7 @@ MR_TEX_CHECKER, MR_TEX_IMAGE, MR_TEX_STONE, MR_TEX_STEM = 0, 1, 2, 3
 MR_TEX_PETAL, MR_TEX_LEAF, MR_TEX_FLOWER_CENTER = 4, 5, 6           # the UVW kinds: looked up at the hit point itself
 MR_NOISE_PERLIN, MR_NOISE_WORLEY2 = 0, 1
 MR_MAX_TEXTURES = 16
+MR_TEX_REFLECTIVE = 1                                               # TextureDesc.reserved[0] of a STONE (miro_hip_bump.h)
 MR_NO_TEXTURE = MR_NO_TEXCOORD = 0xFFFFFFFF
 
 MR_OK, MR_ERR_INVALID, MR_ERR_IO, MR_ERR_NOMEM, MR_ERR_HIP, MR_ERR_STATE = 0, -1, -2, -3, -4, -5
@@ -83,6 +84,9 @@ LENS_SYMBOLS = ["mr_render_level_lights_lens", "mr_render_recursion_lens", "mr_r
 # ... and the four of miro_hip_passes.h (the one-call frames at any sample count and the image finish), which that header includes
 # below its declarations in turn
 PASSES_SYMBOLS = ["mr_render_passes_plan", "mr_render_recursion_passes", "mr_render_recursion_photons_passes", "mr_finish_image"]
+# ... and the one of miro_hip_bump.h (the specular generators about the surface pass's normal: reflective bump-mapped
+# materials), which that header includes below its declarations in turn
+BUMP_SYMBOLS = ["mr_gen_secondary_rays_surface"]
 
 
 class MiroError(RuntimeError):
@@ -409,7 +413,8 @@ def load_library(path=None):
     L.mr_irradiance_estimate.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, vp, vp, vp, vp]
     L.mr_photon_map_count_stats.argtypes = [vp, C.c_int32]
     L.mr_photon_map_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int32]
-    for name in SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS + LENS_SYMBOLS + PASSES_SYMBOLS:
+    for name in (SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS + LENS_SYMBOLS +
+                 PASSES_SYMBOLS + BUMP_SYMBOLS):
         if not hasattr(L, name):
             raise OSError("%s does not export %s" % (path, name))
     lens = [C.POINTER(LensDesc)]                                   # `lens` follows `frame` (miro_hip_lens.h)
@@ -423,8 +428,10 @@ def load_library(path=None):
     L.mr_render_recursion_photons_passes.argtypes = (L.mr_render_recursion_photons_lens.argtypes[:4] + passes +
                                                      L.mr_render_recursion_photons_lens.argtypes[4:])
     L.mr_finish_image.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+    # `d_normal` follows `d_hits` (miro_hip_bump.h)
+    L.mr_gen_secondary_rays_surface.argtypes = L.mr_gen_secondary_rays.argtypes[:3] + [vp] + L.mr_gen_secondary_rays.argtypes[3:]
     for name in (EXPORTED_SYMBOLS + SURFACE_SYMBOLS + FRAME_SYMBOLS + RENDER_SYMBOLS + RECURSION_SYMBOLS + RECURSION_PHOTONS_SYMBOLS +
-                 LENS_SYMBOLS + PASSES_SYMBOLS):
+                 LENS_SYMBOLS + PASSES_SYMBOLS + BUMP_SYMBOLS):
         if hasattr(L, name) and getattr(L, name).restype is C.c_int:
             getattr(L, name).restype = C.c_int32
     _lib = L
@@ -584,6 +591,8 @@ class Scene:
         self.device = device
         self.n_textures = 0            # textures of the last set_textures (FrameRenderer.render_specular reads it)
         self.procedural = False        # whether one of them is procedural (a stone, stem or UVW kind), likewise
+        self._specular = []            # per material of the last set_materials: ks != 0
+        self._bumped_specular = False  # the bumped_specular property, likewise
 
     def close(self):
         if getattr(self, "h", None):
@@ -1149,6 +1158,7 @@ class Scene:
         if prim_material is not None:
             pm = np.ascontiguousarray(prim_material, dtype=np.uint32)
         _check(self.L.mr_scene_set_materials(self.h, arr, len(materials), _u32p(pm) if pm is not None else None))
+        self._specular = [any(float(c) != 0.0 for c in ks) for _, ks, _, _, _ in materials]
 
     def shade_accumulate(self, d_rays, d_hits, d_weights, d_pixels, n, d_shadow_rays, d_shadow_hits, d_shadow_src,
                          d_shadow_count, light_pos, wattage, d_rgb, spp=1, color=(1.0, 1.0, 1.0), stream=None):
@@ -1164,6 +1174,18 @@ class Scene:
         _check(self.L.mr_gen_secondary_rays(self.h, d_rays.data_ptr(), d_hits.data_ptr(), _ptr(d_weights), _ptr(d_pixels), n, spp,
                                             d_out_rays.data_ptr(), d_out_weights.data_ptr(), d_out_pixels.data_ptr(),
                                             d_count.data_ptr(), out_capacity, _ptr(d_out_octants), _stream_ptr(stream)))
+
+    def gen_secondary_rays_surface(self, d_rays, d_hits, d_normal, d_weights, d_pixels, n, d_out_rays, d_out_weights, d_out_pixels,
+                                   d_count, spp=1, stream=None, out_capacity=None, d_out_octants=None):
+        """mr_gen_secondary_rays_surface: gen_secondary_rays with every hit's normal read from hit_surface's buffer -- the normal
+        Scene::trace hands on, bumped on a STONE material, about which Ray::reflect bounces.  The call of a scene with
+        bumped_specular; on any other its children are gen_secondary_rays' bit for bit."""
+        if out_capacity is None:
+            out_capacity = min(t.shape[0] for t in (d_out_rays, d_out_weights, d_out_pixels))
+        _check(self.L.mr_gen_secondary_rays_surface(self.h, d_rays.data_ptr(), d_hits.data_ptr(), _ptr(d_normal), _ptr(d_weights),
+                                                    _ptr(d_pixels), n, spp, d_out_rays.data_ptr(), d_out_weights.data_ptr(),
+                                                    d_out_pixels.data_ptr(), d_count.data_ptr(), out_capacity, _ptr(d_out_octants),
+                                                    _stream_ptr(stream)))
 
     def set_lights(self, lights):
         """mr_scene_set_lights: Scene::addLight for the whole list (replaces an earlier one; an empty list clears it).
@@ -1262,7 +1284,8 @@ class Scene:
 
     def set_textures(self, textures, material_texture=None):
         """mr_scene_set_textures.  textures: TextureDesc objects or dicts -- dict(color1, color2, scale) is a checker,
-        dict(pixels [H, W, 3] float32 with row 0 = the bottom scanline, hdr) an image, dict(stone=scale) a StoneTexture,
+        dict(pixels [H, W, 3] float32 with row 0 = the bottom scanline, hdr) an image, dict(stone=scale) a StoneTexture
+        (with MR_TEX_REFLECTIVE, so that a material with ks != 0 may name it; reflective=False leaves the flag out),
         dict(stem=scale) a StemTexture; the UVW kinds dict(petal=(pivot, radius)) a PetalTexture, dict(leaf=scale) a LeafTexture,
         dict(flower_center=(pivot, radius)) a FlowerCenterTexture; an empty list clears the table.
         material_texture: a texture id per material (MR_NO_TEXTURE = plain Phong).  A material that names a texture becomes a
@@ -1282,6 +1305,8 @@ class Scene:
             elif "stone" in t or "stem" in t:
                 arr[i].kind = MR_TEX_STONE if "stone" in t else MR_TEX_STEM
                 arr[i].scale = t["stone"] if "stone" in t else t["stem"]
+                if "stone" in t and t.get("reflective", True):       # a material that names it may have ks != 0 (bumped_specular)
+                    arr[i].reserved[0] = MR_TEX_REFLECTIVE
             elif "petal" in t or "flower_center" in t:
                 arr[i].kind = MR_TEX_PETAL if "petal" in t else MR_TEX_FLOWER_CENTER
                 pivot, radius = t["petal"] if "petal" in t else t["flower_center"]
@@ -1301,6 +1326,18 @@ class Scene:
         _check(self.L.mr_scene_set_textures(self.h, arr, len(textures), _u32p(mt) if mt is not None else None))
         self.n_textures = len(textures)
         self.procedural = any(arr[i].kind >= MR_TEX_STONE for i in range(len(textures)))
+        # what mr_scene_set_textures remembers of an accepted table: some material names a STONE texture and has ks != 0
+        # (set_materials is refused while a table is set, so the list is the table's)
+        self._bumped_specular = bool(mt is not None and len(textures) > 0) and any(
+            t != MR_NO_TEXTURE and arr[int(t)].kind == MR_TEX_STONE and arr[int(t)].reserved[0] == MR_TEX_REFLECTIVE and shiny
+            for t, shiny in zip(mt.tolist(), self._specular))
+
+    @property
+    def bumped_specular(self):
+        """Some material names a STONE texture and has a non-zero ks (mr_scene_set_textures accepted it): mirror children bounce
+        about the bump-mapped normal, so gen_secondary_rays and gen_path_rays(MR_PATH_MIRROR) refuse the scene and their _surface
+        forms serve it.  Read-only: it changes with set_textures alone."""
+        return self._bumped_specular
 
     def hit_uv(self, d_rays, d_hits, n, d_uv, stream=None):
         """mr_hit_uv: Object::toUVCoordinates(hit.P) of n traced rays into d_uv [n, 2] ((0, 0) for a miss)"""

@@ -689,6 +689,13 @@ class FrameRenderer:
             global_map, caustic_map = photon_maps
             photon_maps = (global_map, caustic_map)
         surface = bool(sc.procedural)
+        # a reflective STONE material (Scene.bumped_specular; `is True`: a stand-in scene answers every name with a method): the
+        # mirror child bounces about the bumped normal, so under path tracing the children are mr_gen_path_rays_surface's
+        bumped = sc.bumped_specular is True
+        if bumped and path_tracing and surface_children is not None and not surface_children:
+            raise ValueError("render_specular: surface_children=False on a scene with a reflective STONE material "
+                             "(Scene.bumped_specular: the mirror child bounces about the bump-mapped normal, which mr_gen_path_rays "
+                             "does not have; it refuses the scene)")
         if surface_children is None:
             surface_children = surface
         elif not surface_children and surface and path_tracing and path_kinds is not None and path_kinds & binding.MR_PATH_DIFFUSE:
@@ -1000,11 +1007,15 @@ class FrameRenderer:
 
     def _generate(self, plan, q, hits, color, normal, level):
         """The next level's queue by ballot compaction: the path-tracing generators (from the surface buffers where the plan
-        says so) or the reflect / Fresnel / refract children."""
+        says so) or the reflect / Fresnel / refract children (about the surface pass's normal on a scene with bumped_specular,
+        which is procedural, so every level has run the pass)."""
         sc, n = self.scene, q.n
         out = self._children(plan, n)
         cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
-        if not plan.path_tracing:
+        if not plan.path_tracing and sc.bumped_specular is True:      # a reflective STONE material: N from the surface pass
+            sc.gen_secondary_rays_surface(q.rays, hits, normal, q.weights, q.pixels, n, out.rays, out.weights, out.pixels, cnt,
+                                          spp=self.spp, stream=plan.stream, d_out_octants=out.octs)
+        elif not plan.path_tracing:
             sc.gen_secondary_rays(q.rays, hits, q.weights, q.pixels, n, out.rays, out.weights, out.pixels, cnt, spp=self.spp,
                                   stream=plan.stream, d_out_octants=out.octs)
         elif plan.surface_children:

@@ -327,9 +327,25 @@ def photon_room_stone():
                           [dict(stone=3.0), dict(stone=20.0)], [0, 1, _NONE, _NONE, _NONE], [0, 8])
 
 
+_POLISHED_FLOOR = (_WHITE, (0.3, 0.3, 0.3), _ZERO, 20.0, 1.0)
+_POLISHED_WALL = (_WHITE, (0.1, 0.1, 0.1), _ZERO, 20.0, 1.0)
+
+
+def photon_room_polished():
+    """photon_room_stone() with REFLECTIVE bump-mapped surfaces (Scene.bumped_specular): material 0, the STONE of scale 3 on the
+    floor plane, is (kd 1, ks 0.3, kt 0, shininess 20, index 1) -- a polished stone floor, whose mirror child bounces about the
+    bumped normal (Scene.cpp:234-263, Ray.h:156) -- and the wall x = -2 takes a material of its own, 5, the STONE of scale 20 with
+    ks 0.1 (shininess 20); the wall z = -2 keeps material 1, diffuse only, and 2, 3, 4 are the plain wall, the glass and the
+    mirror as there.  The kd given is the constructor's argument: its energy clamp (Phong.cpp:24-31) is applied by
+    set_materials, and set_textures stores what TexturedPhong's constructor makes of kd = 1."""
+    return _textured_room([_POLISHED_FLOOR, _TEXTURED, _WALL, _GLASS, _MIRROR, _POLISHED_WALL],
+                          [5, 5, 2, 2, 2, 2, 2, 2, 1, 1, 2, 2, 3, 4], 0,
+                          [dict(stone=3.0), dict(stone=20.0)], [0, 1, _NONE, _NONE, _NONE, 1], [0, 8])
+
+
 def textured_room_setup(scene, desc, leaf_size=4):
-    """populate() a miro_amd.Scene with photon_room_mixed() / photon_room_stone(), build it, and set its texture coordinates,
-    materials and textures"""
+    """populate() a miro_amd.Scene with photon_room_mixed() / photon_room_stone() / photon_room_polished(), build it, and set its
+    texture coordinates, materials and textures"""
     populate(scene, desc)
     scene.build(leaf_size)
     scene.set_texcoords(desc["texcoords"], desc["tidx"])

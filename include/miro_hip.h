@@ -693,7 +693,8 @@ mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_h
  * Errors (MR_ERR_INVALID, the earlier table stays): NULL scene, n_textures > MR_MAX_TEXTURES, NULL list, unknown kind, non-zero
  *   reserved word, non-finite field (also one the kind does not read) or pixel, W or H of 0 (or above 65536), NULL pixels,
  *   hdr > 1, a texture id >= n_textures, a material_texture given without a material table, a STONE texture named by a material
- *   with a non-zero ks or kt, a PETAL or FLOWER_CENTER texture whose radius is not finite and greater than 0.
+ *   with a non-zero kt, or with a non-zero ks unless the texture says MR_TEX_REFLECTIVE (miro_hip_bump.h says what such a scene
+ *   changes), a PETAL or FLOWER_CENTER texture whose radius is not finite and greater than 0.
  *
  * mr_hit_uv -- toUVCoordinates(hit.P) of n traced rays: d_uv receives 2n floats, (0, 0) for a miss.  d_rays may be NULL for
  *   scenes of triangles only.  mr_texture_lookup -- lookup2D of texture `texture` at n coordinates (d_uv: 2n floats): d_rgb
@@ -743,8 +744,9 @@ mr_status mr_shade_environment(mr_scene *scene, const mr_ray *d_rays, const mr_h
  * and mr_gen_path_rays with MR_PATH_DIFFUSE (Ray::random bounces about N; mr_gen_path_rays_surface is its form).  The first
  * three have no lookup3D; the last would bounce about the right normal on a UVW scene, whose normals nothing bumps, but would
  * still carry m_diffuse instead of the looked-up colour.  A scene without them runs the kernels it ran before.  Still without a
- * surface form: mr_gen_secondary_rays needs none (no diffuse child; a STONE material has ks = kt = 0), and mr_trace_level
- * refuses every texture table. */
+ * surface form: mr_trace_level, which refuses every texture table.  mr_gen_secondary_rays emits no diffuse child and needs its
+ * surface form, mr_gen_secondary_rays_surface (miro_hip_bump.h), only where a STONE material has ks != 0: on such a scene it
+ * and mr_gen_path_rays with MR_PATH_MIRROR return MR_ERR_STATE and name their _surface form; a STONE material has kt = 0. */
 enum { MR_TEX_CHECKER = 0, MR_TEX_IMAGE = 1, MR_TEX_STONE = 2, MR_TEX_STEM = 3, MR_TEX_PETAL = 4, MR_TEX_LEAF = 5, MR_TEX_FLOWER_CENTER = 6 };
 #define MR_MAX_TEXTURES 16
 #define MR_NO_TEXTURE  0xFFFFFFFFu
@@ -755,7 +757,7 @@ typedef struct mr_texture_desc {
                                                          MR_TEX_PETAL and MR_TEX_FLOWER_CENTER: color1 = pivot, color2[0] = radius */
     const float *pixels;                              /* MR_TEX_IMAGE: host, W*H*3 floats, row 0 = bottom */
     uint32_t W, H, hdr;
-    uint32_t reserved[5];                             /* must be 0 */
+    uint32_t reserved[5];                             /* must be 0; [0] of a MR_TEX_STONE may be MR_TEX_REFLECTIVE (miro_hip_bump.h) */
 } mr_texture_desc;
 mr_status mr_scene_set_texcoords(mr_scene *scene, const float *texcoords, uint32_t n_texcoords, const uint32_t *tidx);
 mr_status mr_scene_get_texcoords(const mr_scene *scene, uint32_t *n_texcoords, float *texcoords, uint32_t *tidx);

@@ -80,4 +80,5 @@ mr_status mr_finish_image(mr_scene *scene, const float *d_rgb, uint64_t n_pixels
 #ifdef __cplusplus
 }
 #endif
+#include "miro_hip_bump.h"
 #endif /* MIRO_HIP_PASSES_H */
